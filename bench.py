@@ -8,12 +8,21 @@ N = 1 (headline; BASELINE.json "100M-row RangeFilter", SURVEY 8d config C2 at 10
 segments resident in HBM (int32 uniform in [0, 2^30) from splitmix64, rotated so the 256 MiB Infinity Cache cannot
 serve the reads), predicate GT(2^28) AND LT(3*2^28), ~50 % selectivity.  One STEP = one pass of ScanOp -> SelectOp(GT)
 -> SelectOp(LT) over one segment: the fused scan+select kernel producing the selection bitmap (12.5 MB) and the
-selected-row count (reduced inside the same kernel).  The line also carries an `extra` block, measured in the same
-run: C3 (range on age and id + Project), C4 (Match(state) + Project), group-by aggregation, and C5 at G = 1 (extra.c5).
+selected-row count (reduced inside the same kernel).
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, dtype, ms_per_step, config,
+staging).  Everything else moves behind --full: the numpy parity gate before timing, the event-timed second pass and the
+roofline object, the CPU baselines, and the `extra` block: C3 (range on age and id + Project), C4 (Match(state) +
+Project), group-by aggregation, and C5 at G = 1 (extra.c5); at N > 1 extra.c5 (below) as well.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the path receives it (rank 0): DIR/count.npy
+(the selected-row count, float64[1]) and DIR/bitmap_u32.npy (the selection bitmap as little-endian uint32 halves of its
+uint64 words, float64).  A bitmap above the size cap is written as a fixed seeded sample, its positions in
+DIR/bitmap_u32_index.npy.  The inputs are seeded: the same arguments give the same arrays from run to run.
 
 N > 1: `value` stays the SAME workload -- every rank runs the N = 1 step on its own segments (weak scaling: per-GPU work
 fixed), value = N x 1e8 rows x K / max-over-ranks wall time -- so a scaling curve read from `value` compares like with like.
-BASELINE config C5 (strong scaling) rides in `extra.c5` at every N: 8 segments x 100 M rows (segment s: age from splitmix64
+BASELINE config C5 (strong scaling) rides in `extra.c5` at every N under --full: 8 segments x 100 M rows (segment s: age from splitmix64
 seed 100+s, id = s*10^8 + i), segment s on rank s mod N (Engine.scala:176-180 fans out one pipeline per segment), query
 RangeFilter(age) AND RangeFilter(id) + Project(id, age); one pass = every rank's segments followed by ONE count all-reduce:
 ncclAllReduce(sum, uint64, 1) over RCCL / xGMI, issued by libimm3 (imm3_comm_allreduce_count) on the communicator's stream
@@ -22,8 +31,8 @@ one hipGraph (imm3_graph_launch; --no-graph: kernel by kernel).  At N > 1 extra.
 point of the curve measured in the same run: every rank runs all 8 segments alone on its own GPU, max over ranks (--no-g1
 skips it) -- and `efficiency` = value / (N x g1_same_run.value).
 
-Prints ONE JSON line on rank 0.  Inputs are resident in HBM before any timed region.  roofline.achieved = algorithmic
-bytes per launch / mean kernel duration measured live with HIP events on the launching stream.  cpu_baseline = the
+Prints ONE JSON line on rank 0.  Inputs are resident in HBM before any timed region.  roofline.achieved (--full) = algorithmic
+bytes per launch / mean kernel duration measured live with HIP events on the launching stream.  cpu_baseline (--full) = the
 oracle's faithful C restatement of the reference CPU operators (kind "port": the Scala/JVM reference cannot run
 here), one thread -- the reference runs one thread per segment -- timed on rank 0 at N = 1 only.
 """
@@ -407,7 +416,37 @@ KERNEL_NAMES = {0: "scan_select", 1: "offsets_scan", 2: "compact_gather", 3: "co
 # =====================================================================================================================
 # C2: the N = 1 headline (and the weak-scaling leg at N > 1)
 # =====================================================================================================================
-def measure_c2(env: Env, steps: int, warmup: int, with_cpu_baseline: bool):
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: all arrays together
+DUMP_SAMPLE_SEED = 20240917
+
+
+def dump_c2_outputs(out_dir: str, words: np.ndarray, count: int) -> None:
+    """What a caller of the C2 step receives -- the selection bitmap and the selected-row count -- as float64 arrays: the
+    bitmap's uint64 words as their little-endian uint32 halves (exact in float64).  Above the cap, a fixed seeded sample of
+    the halves and its positions."""
+    os.makedirs(out_dir, exist_ok=True)
+    halves = np.ascontiguousarray(words, dtype="<u8").view("<u4")
+    np.save(os.path.join(out_dir, "count.npy"), np.array([count], dtype=np.float64))
+    cap = (DUMP_MAX_BYTES - 4096) // 8
+    if halves.size <= cap:
+        np.save(os.path.join(out_dir, "bitmap_u32.npy"), halves.astype(np.float64))
+    else:
+        pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(halves.size, size=cap // 2, replace=False))
+        np.save(os.path.join(out_dir, "bitmap_u32.npy"), halves[pick].astype(np.float64))
+        np.save(os.path.join(out_dir, "bitmap_u32_index.npy"), pick.astype(np.float64))
+
+
+def c2_config(env: Env, n: int) -> dict:
+    return {
+        "workload": "C2@100M: RangeFilter GT(2^28) AND LT(3*2^28) over one 100M-row DENSE_INT segment "
+                    "-> selection bitmap + selected-row count",
+        "rows_per_step_per_gpu": n, "block_rows": 1024, "segments_rotated_per_gpu": env.args.segments, "selectivity": 0.5,
+        "parallelism": "1 GPU" if env.world == 1 else f"every rank scans its own segments (weak scaling) x{env.world}",
+    }
+
+
+def measure_c2(env: Env, steps: int, warmup: int, with_cpu_baseline: bool, full: bool = True, dump_dir: str = None):
+    """full = False: staging, warm-up, the timed steps and the line's headline fields only."""
     torch, native, synth, ctx, args = env.torch, env.native, env.synth, env.ctx, env.args
     n = args.rows
     sels = [(0, native.GT, float(2 ** 28)), (0, native.LT, float(3 * 2 ** 28))]
@@ -424,19 +463,38 @@ def measure_c2(env: Env, steps: int, warmup: int, with_cpu_baseline: bool):
         del v
     stage_s = time.perf_counter() - t_stage
 
-    # parity gate for the reported number: popcount(bitmap) == count == numpy evaluation of this rank's segment 0
-    queries[0].run_select()
-    words, cnt = queries[0].bitmap(), queries[0].count()
-    keep = (host0 > 2 ** 28) & (host0 < 3 * 2 ** 28)
-    assert cnt == int(keep.sum()), (cnt, int(keep.sum()))
-    assert words.tobytes() == np.packbits(keep, bitorder="little").tobytes(), "bitmap mismatch"
-    del keep, words
+    if full:
+        # parity gate for the reported number: popcount(bitmap) == count == numpy evaluation of this rank's segment 0
+        queries[0].run_select()
+        words, cnt = queries[0].bitmap(), queries[0].count()
+        keep = (host0 > 2 ** 28) & (host0 < 3 * 2 ** 28)
+        assert cnt == int(keep.sum()), (cnt, int(keep.sum()))
+        assert words.tobytes() == np.packbits(keep, bitorder="little").tobytes(), "bitmap mismatch"
+        del keep, words
     nq = len(queries)
 
     def step(i: int):
         queries[i % nq].run_select()                    # fused ScanOp -> SelectOp(GT) -> SelectOp(LT) kernel (+ count)
 
     elapsed = env.timed_steps(step, steps, warmup)
+    if dump_dir is not None and env.rank == 0:         # the last timed step's outputs, before anything else runs
+        last = queries[(steps - 1) % nq]
+        dump_c2_outputs(dump_dir, last.bitmap(), last.count())
+
+    if not full:
+        out = None
+        if env.rank == 0:
+            out = {
+                "value": float(n) * steps * env.world / elapsed,
+                "ms_per_step": elapsed / steps * 1e3,
+                "config": c2_config(env, n),
+                "staging": {"host_to_hbm_s_per_segment": stage_s / args.segments, "note": "PCIe staging incl. synthetic generation; never part of value"},
+            }
+        for q in queries:
+            q.close()
+        for s in segs:
+            s.close()
+        return out
 
     # the same K steps again with the scan+select kernel bracketed by HIP events on its stream (and device-clock stamps)
     ctx.timing_enable(steps + 8)
@@ -479,12 +537,7 @@ def measure_c2(env: Env, steps: int, warmup: int, with_cpu_baseline: bool):
             "value": float(n) * steps * env.world / elapsed,
             "ms_per_step": elapsed / steps * 1e3,
             "ms_per_step_with_kernel_events": elapsed_events / steps * 1e3,
-            "config": {
-                "workload": "C2@100M: RangeFilter GT(2^28) AND LT(3*2^28) over one 100M-row DENSE_INT segment "
-                            "-> selection bitmap + selected-row count",
-                "rows_per_step_per_gpu": n, "block_rows": 1024, "segments_rotated_per_gpu": args.segments, "selectivity": 0.5,
-                "parallelism": "1 GPU" if env.world == 1 else f"every rank scans its own segments (weak scaling) x{env.world}",
-            },
+            "config": c2_config(env, n),
             "roofline": {
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                 "traffic": traffic, "traffic_source": tsrc,
@@ -969,12 +1022,18 @@ def main():
     ap.add_argument("--c5-per-segment", action="store_true", help="C5: one query (one launch) per owned segment, as round 4 ran it, instead of one table query per rank")
     ap.add_argument("--no-readme-table", action="store_true", help="leave the README-shaped 98-segment table out of the extra block")
     ap.add_argument("--no-limit", action="store_true", help="leave the `limit` queries out of the extra block (profiling runs: their chunks are launches of the headline kernel's instance)")
-    ap.add_argument("--extra", action="store_true", help="(kept for compatibility: the extra block is on by default)")
+    ap.add_argument("--extra", action="store_true", help="(kept for compatibility: the extra block is part of --full; this implies --full)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: the parity gate, the event-timed "
+                    "pass and roofline, the CPU baselines and the extra block (C3, C4, aggregation, C5); the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's bitmap and count to DIR/*.npy (float64; rank 0)")
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--grid", type=int, default=0)
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    args.full = args.full or args.extra
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
@@ -987,7 +1046,13 @@ def main():
             "higher_is_better": True, "vs_baseline": None, "data": "synthetic"}
     result = None
     # `value` is ONE workload at every N: the headline C2 step, every rank on its own segments (weak scaling)
-    c2 = measure_c2(env, args.steps, args.warmup, with_cpu_baseline=(env.world == 1 and not args.no_cpu_baseline))
+    c2 = measure_c2(env, args.steps, args.warmup, with_cpu_baseline=(args.full and env.world == 1 and not args.no_cpu_baseline),
+                    full=args.full, dump_dir=args.dump_outputs)
+    if not args.full:                                   # a plain run: the headline and nothing else
+        env.close()
+        if env.rank == 0:
+            print(json.dumps(dict(base, scaling="weak", dtype="i32", **c2)))
+        return
     if env.rank == 0:
         result = dict(base, scaling="weak", dtype="i32", **{k: c2[k] for k in ("value", "ms_per_step", "ms_per_step_with_kernel_events", "config", "roofline", "staging", "per_rank")})
         result["cpu_baseline"] = c2.get("cpu_baseline") if env.world == 1 else None     # timed at N = 1 only (contract)

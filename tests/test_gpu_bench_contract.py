@@ -1,5 +1,5 @@
-"""GPU suite: bench.py prints ONE JSON line that carries the driver's contract fields, the roofline object and (when
-asked) the cpu_baseline object.  Small sizes: this checks the shape of the line, not the numbers."""
+"""GPU suite: bench.py prints ONE JSON line that carries the driver's contract fields; under --full also the roofline object
+and (when asked) the cpu_baseline object.  Small sizes: this checks the shape of the line, not the numbers."""
 import json
 import os
 import subprocess
@@ -20,7 +20,7 @@ def run_bench(*flags):
 
 
 def test_bench_line_has_the_contract_fields():
-    d = run_bench("--rows", "2000000", "--steps", "10", "--warmup", "3", "--segments", "2", "--no-cpu-baseline", "--no-extra")
+    d = run_bench("--full", "--rows", "2000000", "--steps", "10", "--warmup", "3", "--segments", "2", "--no-cpu-baseline", "--no-extra")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -37,9 +37,9 @@ def test_bench_line_has_the_contract_fields():
 
 
 def test_bench_cpu_baseline_and_extra_block():
-    """Default line: cpu_baseline plus the extra block -- C3, C4 (algorithmic bytes, per-kernel ms, frac), aggregation and
+    """--full line: cpu_baseline plus the extra block -- C3, C4 (algorithmic bytes, per-kernel ms, frac), aggregation and
     the G = 1 point of the C5 curve (real one-rank RCCL count all-reduce inside libimm3)."""
-    d = run_bench("--rows", "1000000", "--steps", "5", "--warmup", "2", "--segments", "2")
+    d = run_bench("--full", "--rows", "1000000", "--steps", "5", "--warmup", "2", "--segments", "2")
     c = d["cpu_baseline"]
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c, k
@@ -75,7 +75,7 @@ def test_bench_gpus_2_launches_its_own_ranks():
     is the headline C2 workload (weak scaling) and whose extra.c5 is the sharded C5 job.  One-device rehearsal: both ranks share cuda:0, so the count all-reduce goes over gloo (RCCL refuses that)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["IMM3_BENCH_ONE_DEVICE"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "1000000", "--steps", "4", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--rows", "1000000", "--steps", "4", "--warmup", "1",
                         "--segments", "2"], capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -98,6 +98,29 @@ def test_bench_gpus_2_launches_its_own_ranks():
     env2 = dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "100000"], capture_output=True, text=True, cwd=ROOT, timeout=300, env=env2)
     assert p.returncode != 0 and "WORLD_SIZE" in p.stderr
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run prints the headline alone (nothing --full measures), and --dump-outputs writes the last timed step's bitmap
+    and count: 5 steps over 2 rotated segments end on segment 0 (splitmix64 seed 1), evaluated here with numpy."""
+    import numpy as np
+    from immutable3_amd import synth
+    n = 2000000
+    d = run_bench("--rows", str(n), "--steps", "5", "--warmup", "2", "--segments", "2", "--dump-outputs", str(tmp_path))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["dtype"] == "i32" and d["unit"] == "rows/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - n * 5 / (d["ms_per_step"] * 1e-3 * 5)) / d["value"] < 1e-6
+    for k in ("roofline", "cpu_baseline", "extra", "ms_per_step_with_kernel_events"):
+        assert k not in d, k
+    v = synth.uniform_int30(1, n)
+    keep = (v > 2 ** 28) & (v < 3 * 2 ** 28)
+    count = np.load(tmp_path / "count.npy")
+    halves = np.load(tmp_path / "bitmap_u32.npy")
+    assert count.dtype == np.float64 and count.tolist() == [float(keep.sum())]
+    assert halves.dtype == np.float64 and not (tmp_path / "bitmap_u32_index.npy").exists()
+    words = halves.astype(np.uint32).view(np.uint64)
+    assert words.tobytes() == np.packbits(keep, bitorder="little").tobytes()
 
 
 def test_count_log():

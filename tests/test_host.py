@@ -357,3 +357,24 @@ def test_bench_traffic_entries_are_stamped_with_the_kernel_sources(tmp_path, mon
     assert "no entry" in bench.stamped_traffic("readme_table_c3")["source"]
     (tmp_path / "profiles" / "traffic.json").unlink()
     assert "missing" in bench.stamped_traffic("c3_range_age_id_project")["source"]
+
+
+def test_bench_dump_outputs_are_exact_and_capped(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the bitmap's uint64 words as exact float64 uint32 halves plus the count; above the size cap a fixed
+    seeded sample with its positions, the same sample every time, all files together within the cap."""
+    import numpy as np
+    import bench
+    words = np.random.default_rng(3).integers(0, 2 ** 63, size=1000, dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+    bench.dump_c2_outputs(str(tmp_path / "full"), words, 12345)
+    halves = np.load(tmp_path / "full" / "bitmap_u32.npy")
+    assert halves.dtype == np.float64 and halves.astype(np.uint32).view(np.uint64).tolist() == words.tolist()
+    assert np.load(tmp_path / "full" / "count.npy").tolist() == [12345.0]
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096 + 8 * 600)      # room for 600 float64 values: 300 sampled halves + positions
+    for d in ("a", "b"):
+        bench.dump_c2_outputs(str(tmp_path / d), words, 12345)
+    pick = np.load(tmp_path / "a" / "bitmap_u32_index.npy")
+    got = np.load(tmp_path / "a" / "bitmap_u32.npy")
+    assert pick.size == got.size == 300 and (np.diff(pick) > 0).all()
+    assert (got == words.view("<u4")[pick.astype(np.int64)].astype(np.float64)).all()
+    assert (pick == np.load(tmp_path / "b" / "bitmap_u32_index.npy")).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_MAX_BYTES

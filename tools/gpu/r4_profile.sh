@@ -3,13 +3,13 @@
 TAG=${1:-r04b}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 G=gpurun_out
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $G/${TAG}_trace -o $TAG -- python3 bench.py --no-cpu-baseline --no-c5 --no-limit > $G/${TAG}_trace.log 2>$G/${TAG}_trace.err || { tail -5 $G/${TAG}_trace.err; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $G/${TAG}_trace -o $TAG -- python3 bench.py --full --no-cpu-baseline --no-c5 --no-limit > $G/${TAG}_trace.log 2>$G/${TAG}_trace.err || { tail -5 $G/${TAG}_trace.err; exit 1; }
 echo trace done
-timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $G/${TAG}_fetch -o $TAG -- python3 bench.py --no-cpu-baseline --no-c5 --no-limit --steps 20 --warmup 3 > $G/${TAG}_fetch.log 2>$G/${TAG}_fetch.err || { tail -5 $G/${TAG}_fetch.err; exit 1; }
+timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $G/${TAG}_fetch -o $TAG -- python3 bench.py --full --no-cpu-baseline --no-c5 --no-limit --steps 20 --warmup 3 > $G/${TAG}_fetch.log 2>$G/${TAG}_fetch.err || { tail -5 $G/${TAG}_fetch.err; exit 1; }
 echo fetch done
-timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $G/${TAG}_write -o $TAG -- python3 bench.py --no-cpu-baseline --no-c5 --no-limit --steps 20 --warmup 3 > $G/${TAG}_write.log 2>$G/${TAG}_write.err || { tail -5 $G/${TAG}_write.err; exit 1; }
+timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $G/${TAG}_write -o $TAG -- python3 bench.py --full --no-cpu-baseline --no-c5 --no-limit --steps 20 --warmup 3 > $G/${TAG}_write.log 2>$G/${TAG}_write.err || { tail -5 $G/${TAG}_write.err; exit 1; }
 echo write done
-timeout -k 10 600 python3 bench.py > $G/${TAG}_bench_plain.json 2>$G/${TAG}_bench_plain.err || { tail -5 $G/${TAG}_bench_plain.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $G/${TAG}_bench_plain.json 2>$G/${TAG}_bench_plain.err || { tail -5 $G/${TAG}_bench_plain.err; exit 1; }
 echo bench done
 timeout -k 10 300 python3 tools/kinds_bench.py > $G/${TAG}_kinds_tool_output.txt 2>&1
 IMM3_VARIANTS=0,6,3 timeout -k 10 400 python3 tools/proj_bench.py > $G/${TAG}_projection_tool_output.txt 2>&1

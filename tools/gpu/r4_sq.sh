@@ -4,7 +4,7 @@ O=$R/gpurun_out/r04a_sq
 mkdir -p $O
 timeout -k 10 600 python -m pytest tests/test_gpu_plan_quality.py -x -q -m gpu > gpurun_out/r4_pq.log 2>&1 || { tail -30 gpurun_out/r4_pq.log; exit 1; }
 tail -2 gpurun_out/r4_pq.log
-timeout -k 10 600 python3 bench.py > gpurun_out/r04a_bench_plain.json 2>gpurun_out/r04a_bench_plain.err || { tail -5 gpurun_out/r04a_bench_plain.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > ${O%/*}/r04a_bench_plain.json 2>${O%/*}/r04a_bench_plain.err || { tail -5 ${O%/*}/r04a_bench_plain.err; exit 1; }
 cd /tmp && export TMPDIR=/tmp
 i=0
 for pmc in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_BUSY_CYCLES SQ_WAVE_CYCLES"; do

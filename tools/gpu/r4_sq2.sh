@@ -2,7 +2,7 @@ cd $GRAFT_REPO_ROOT
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r04b_sq
 mkdir -p $O
-timeout -k 10 600 python3 bench.py > gpurun_out/r04b_bench_plain.json 2>gpurun_out/r04b_bench_plain.err || { tail -5 gpurun_out/r04b_bench_plain.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > ${O%/*}/r04b_bench_plain.json 2>${O%/*}/r04b_bench_plain.err || { tail -5 ${O%/*}/r04b_bench_plain.err; exit 1; }
 cd /tmp && export TMPDIR=/tmp
 i=0
 for pmc in "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_BUSY_CYCLES SQ_WAVE_CYCLES" "SQ_WAIT_INST_LDS SQ_WAIT_ANY SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM_RD"; do

@@ -65,7 +65,7 @@ def kernel(sub):
             "hbm_bytes_fetch_raw": (f * 1024 + w * 1024) if f is not None and w is not None else None}
 
 
-summary = {"tag": tag, "command": "rocprofv3 --kernel-trace --stats -f csv -- python3 bench.py --no-cpu-baseline --no-c5   (+ --pmc FETCH_SIZE and --pmc WRITE_SIZE passes, --steps 20)",
+summary = {"tag": tag, "command": "rocprofv3 --kernel-trace --stats -f csv -- python3 bench.py --full --no-cpu-baseline --no-c5   (+ --pmc FETCH_SIZE and --pmc WRITE_SIZE passes, --steps 20)",
            "peak_GBps": 8000.0}
 head = kernel("k_filter_tile<0, 3, 3, 1, false, true, false>")
 calib = kernel("k_read_stream")

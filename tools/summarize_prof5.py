@@ -96,7 +96,7 @@ def kernel(sub, pick=None):
 
 
 x = line["extra"] if line else {}
-summary = {"tag": tag, "command": "rocprofv3 --kernel-trace --stats -f csv -- python3 bench.py --no-cpu-baseline --no-limit   (+ --pmc FETCH_SIZE and --pmc WRITE_SIZE passes, --steps 20)",
+summary = {"tag": tag, "command": "rocprofv3 --kernel-trace --stats -f csv -- python3 bench.py --full --no-cpu-baseline --no-limit   (+ --pmc FETCH_SIZE and --pmc WRITE_SIZE passes, --steps 20)",
            "peak_GBps": 8000.0}
 head = kernel("k_filter_tile<0, 3, 3, 1, false, true, false>")
 calib = kernel("k_read_stream")
