@@ -243,25 +243,12 @@ extern "C" int imm3_graph_launch(imm3_graph *g) {
     }
     HIPCHK(hipSetDevice(g->ctx->device));
     HIPCHK(hipGraphLaunch(g->exec, g->ctx->stream));
-    // A replay is the recorded runs again: every recorded query gets back the state it had after its recorded run (a getter of a
+    // A replay is the recorded runs again: every recorded query gets back the run record it had after its recorded run (a getter of a
     // single-pass run then reads THIS replay's status word -- round 3 left `sp_verified` set by an earlier getter, or
     // `ran_single_pass` cleared by an earlier fallback, and a busy or abandoned replay went unnoticed).
     for (size_t i = 0; i < g->queries.size() && i < g->states.size(); ++i) {
-        imm3_query *q = g->queries[i];
-        const QueryRunState &st = g->states[i];
-        q->ran_select = st.ran_select;
-        q->ran_project = st.ran_project;
-        q->bitmap_valid = st.bitmap_valid;
-        q->ran_single_pass = st.ran_single_pass;
-        q->stage_written = st.stage_written;
-        q->bitmap_lazy = st.bitmap_lazy;
-        q->agg_select_skipped = st.agg_select_skipped;
-        q->count_pending_scan = st.count_pending_scan;
-        q->has_pfor_pass = st.has_pfor_pass;
-        q->ran_agg = st.ran_agg;
-        q->offsets_valid = st.offsets_valid;
-        q->select_partial = st.select_partial;
-        q->sp_verified = false;
+        g->queries[i]->run = g->states[i];
+        g->queries[i]->run.sp_verified = false;
     }
     return IMM3_OK;
 }
@@ -1627,27 +1614,24 @@ static int join_total(imm3_query *q, hipStream_t s) {
     if (q->total_on_aux) HIPCHK(hipStreamWaitEvent(s, q->ev_total_done, 0));
     return IMM3_OK;
 }
-static int settle_whole_select(imm3_query *q);
-// (imm3_comm_allreduce_count: the word that goes into the collective is the segment's count -- a run that stopped at its limit is
-// followed by the whole select here, enqueued, no host wait)
-static int settle_agg_select(imm3_query *q);
-int imm3::join_query_count(imm3_query *q, hipStream_t s) {
-    int rc = settle_agg_select(q);
-    if (!rc) rc = settle_whole_select(q);
-    return rc ? rc : join_total(q, s);
-}
 
-
-// count_in_scan: a projection follows on the same stream; its offsets scan publishes the count (no k_total launch)
-// count_only: the caller wants selected.size alone -- a chain that is ONE tile launch then stores no bitmap
+// What a caller of run_select wants, OR-ed together; SEL_DEFAULT: store the bitmap, reduce the count on the main stream.
+enum SelectMode : unsigned {
+    SEL_DEFAULT = 0,
+    SEL_OVERLAP_TOTAL = 1u << 0, // nothing on the main stream needs the count: reduce it on the aux stream (tuning variant 2)
+    SEL_COUNT_IN_SCAN = 1u << 1, // a projection follows on the same stream; its offsets scan publishes the count (no k_total launch)
+    SEL_COUNT_ONLY = 1u << 2,    // the caller wants selected.size alone -- a chain that is ONE tile launch then stores no bitmap
+    SEL_WHOLE = 1u << 3,         // never in chunks (the getters' full select)
+    SEL_PLAIN = 1u << 4,         // stage no survivor records: the bitmap is what the caller wants (settle_lazy_bitmap)
+};
 // Chunks of a limit scan: they end at tiles 1024, 8192, 32 768, 131 072, ... (x 4) and at the segment's end -- four launches for
 // 100 M rows.  A `limit 10` is usually met in the first megarow: the chunks behind it cost their dispatch only (1 - 4 us each, which
 // is why there are few of them); a limit met at 5 % of the segment stops at 8 %; one met in the second half scans everything, as a
 // whole select would.  Multiples of kChunkTiles (the offsets scan's unit).
 static constexpr int64_t kLimitSecondEndTiles = 8192; // (kLimitFirstChunkTiles: imm3_api_internal.h)
 
-// whole: never in chunks (the getters' full select)
-static int run_select(imm3_query *q, bool overlap_total, bool count_in_scan = false, bool count_only = false, bool whole = false) {
+static int run_select(imm3_query *q, unsigned mode) {
+    const bool overlap_total = mode & SEL_OVERLAP_TOTAL, count_in_scan = mode & SEL_COUNT_IN_SCAN, count_only = mode & SEL_COUNT_ONLY;
     imm3_ctx *ctx = q->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
@@ -1656,15 +1640,15 @@ static int run_select(imm3_query *q, bool overlap_total, bool count_in_scan = fa
         if (jrc) return jrc;
         q->total_on_aux = false;
     }
-    q->offsets_valid = false; // (a new bitmap)
-    q->select_partial = false;
+    q->run.offsets_valid = false; // (a new bitmap)
+    q->run.select_partial = false;
     if (q->always_false || q->n_tiles == 0) {
         // an empty interval / empty IN-list clears every bit; nothing to read
         HIPCHK(hipMemsetAsync(q->d_total, 0, 2 * sizeof(unsigned long long), s)); // (an always-false query logs nothing)
         HIPCHK(hipMemsetAsync(q->d_bitmap, 0, (size_t)std::max<int64_t>(q->n_tiles * kTileWords, 1) * sizeof(uint64_t), s));
-        q->ran_select = true;
-        q->bitmap_valid = true;
-        q->ran_single_pass = false;
+        q->run.ran_select = true;
+        q->run.bitmap_valid = true;
+        q->run.ran_single_pass = false;
         return IMM3_OK;
     }
     // Plan the passes.  Uniform layouts: numeric and 2-byte-string predicates go through the tile kernel, up
@@ -1700,20 +1684,20 @@ static int run_select(imm3_query *q, bool overlap_total, bool count_in_scan = fa
     int pass = 0;
     int grid = 1;
     bool count_done = false; // the filter kernel's last work-group has written total / n_emit
-    q->stage_written = false;
-    q->bitmap_lazy = false;
-    q->ran_single_pass = false;
+    q->run.stage_written = false;
+    q->run.bitmap_lazy = false;
+    q->run.ran_single_pass = false;
     // exactly ONE launch in the whole select chain: only then may that launch publish the count (and append to the count
     // log) itself, and only then are the survivors' values staged
     const bool single_tile_pass = generic_preds.empty() && pfor_preds.empty() && tile_passes.size() == 1;
     const bool skip_bitmap = count_only && single_tile_pass && !q->table && !overlap_total && ctx->filter_variant != 7;
-    q->bitmap_valid = !skip_bitmap;
+    q->run.bitmap_valid = !skip_bitmap;
     // `limit` stops the scan (Project.scala:73-80; Engine.scala:166,253-258: the reference's workers stall on the full queue once the
     // consumer has its rows): a projection with a limit whose select chain is one tile launch over one uniform segment runs that
     // launch as chunks of growing size; every chunk first looks at the rows selected so far (a device word) and leaves at once when
     // the limit has been reached -- nothing is read, no bitmap line written.  Enqueued blindly: no host wait.  Tuning variant 14: off.
     LimitScanInputs li;
-    li.whole = whole;
+    li.whole = mode & SEL_WHOLE;
     li.count_log_on = q->count_log_on;
     li.count_in_scan = count_in_scan;
     li.limit = q->limit;
@@ -1736,7 +1720,7 @@ static int run_select(imm3_query *q, bool overlap_total, bool count_in_scan = fa
             a.kinds[k] = tile_kind(fp);
             fill_tile_col(q, fp, a.cols[k], a.kinds[k]);
         }
-        if (single_tile_pass && q->d_stage_rec && !skip_bitmap && !q->force_plain_select) { // the columns are in the order the records were laid out for (same sort)
+        if (single_tile_pass && q->d_stage_rec && !skip_bitmap && !(mode & SEL_PLAIN)) { // the columns are in the order the records were laid out for (same sort)
             bool same = true;
             for (int k = 0; k < kMaxTileCols; ++k) same = same && a.kinds[k] == q->stage_kinds[k] && (k >= n || take[(size_t)k]->seg_col == q->stage_seg_col[k]);
             if (!same) return fail(IMM3_ERR_ARG, "internal: staged record layout does not match the tile launch");
@@ -1744,7 +1728,7 @@ static int run_select(imm3_query *q, bool overlap_total, bool count_in_scan = fa
             a.tile_start = q->d_tile_start;
             a.wave_cap = q->stage_wave_cap;
             a.max_slots = q->stage_max_slots;
-            q->stage_written = true;
+            q->run.stage_written = true;
         }
         a.ablate = (ctx->filter_variant >= 20 && ctx->filter_variant <= 22) ? ctx->filter_variant.load() : 0; // (tools' build only)
         a.and_existing = pass > 0;
@@ -1755,10 +1739,10 @@ static int run_select(imm3_query *q, bool overlap_total, bool count_in_scan = fa
         // A records run whose offsets scan follows (imm3_query_run of a projection) stores NO bitmap: the records carry the positions
         // and the scan takes the tiles' counts from the arenas (round 5: 12.5 MB of 128-byte line stores in between the streaming
         // loads, and 12.5 MB read back by k_scan -- C4 107 -> 100 us).  imm3_query_bitmap materialises it on demand.  Tuning 19: off.
-        q->bitmap_lazy = q->stage_written && count_in_scan && !q->count_log_on && ctx->filter_variant != 19;
-        if (q->bitmap_lazy) {
+        q->run.bitmap_lazy = q->run.stage_written && count_in_scan && !q->count_log_on && ctx->filter_variant != 19;
+        if (q->run.bitmap_lazy) {
             a.bitmap = nullptr;
-            q->bitmap_valid = false;
+            q->run.bitmap_valid = false;
         }
         a.block_partials = q->d_block_partials;
         a.tile_rows = q->table ? q->table->d_tile_rows : nullptr; // table query: address the columns through the tile table
@@ -1770,7 +1754,7 @@ static int run_select(imm3_query *q, bool overlap_total, bool count_in_scan = fa
         }
         bool stamped = false;
         grid = filter_grid(q->n_tiles, false, any_i32, ctx->grid_blocks, narrow_bytes); // (no column at all: the store-only kernel also likes 1536 groups, 9.9 vs 17.2 us)
-        if (q->stage_written) grid = q->stage_grid; // fixed at creation: the arena layout depends on it
+        if (q->run.stage_written) grid = q->stage_grid; // fixed at creation: the arena layout depends on it
         // A select chain that is ONE tile pass also reduces its count in the kernel (one relaxed atomic per work-group into a
         // two-level tally, finish_add): no k_total launch.  Variant 7 = never; variant 13 = only at <= 512 work-groups (what
         // round 1 did: with a single tally the 1536 atomics of a narrow-column launch cost more than the launch they saved).
@@ -1781,7 +1765,7 @@ static int run_select(imm3_query *q, bool overlap_total, bool count_in_scan = fa
         // bitmap lines parked in LDS and stored in bursts: no staging (whose LDS and 2048 work-groups
         // leave no room for 32 KiB more per group); tuning variant 12 switches it off
         // (64 lines = 32 KiB per work-group at <= 4 groups per CU; 16 lines = 8 KiB for the 1536-group narrow-column kernels)
-        a.defer_lines = (ctx->filter_variant == 12 || q->bitmap_lazy) ? 0 : (q->stage_written ? 16 : (grid <= 1024 ? kDeferLines : 16)); // (no bitmap, no lines to park)
+        a.defer_lines = (ctx->filter_variant == 12 || q->run.bitmap_lazy) ? 0 : (q->run.stage_written ? 16 : (grid <= 1024 ? kDeferLines : 16)); // (no bitmap, no lines to park)
         if (skip_bitmap) { // count-only: the kernel instance that stores nothing (the count is reduced in the kernel)
             a.bitmap = nullptr;
             a.defer_lines = 0;
@@ -1821,7 +1805,7 @@ static int run_select(imm3_query *q, bool overlap_total, bool count_in_scan = fa
                 len = tile0 == kLimitFirstChunkTiles ? kLimitSecondEndTiles - tile0 : tile0 * 3; // (the next chunk ends at 4 x this one's end)
             }
             count_done = true;
-            q->select_partial = true;
+            q->run.select_partial = true;
             ++pass;
             continue;
         }
@@ -1831,7 +1815,7 @@ static int run_select(imm3_query *q, bool overlap_total, bool count_in_scan = fa
         ++pass;
     }
     // PFOR_INT passes: one compressed column per launch, decoded in LDS and compared in registers
-    q->has_pfor_pass = !pfor_preds.empty();
+    q->run.has_pfor_pass = !pfor_preds.empty();
     for (const FoldedPred *fp : pfor_preds) {
         const SegCol &sc = q->seg->cols[(size_t)fp->seg_col];
         PforArgs a;
@@ -1884,7 +1868,7 @@ static int run_select(imm3_query *q, bool overlap_total, bool count_in_scan = fa
         gi += take;
         ++pass;
     }
-    q->count_pending_scan = !count_done && count_in_scan;
+    q->run.count_pending_scan = !count_done && count_in_scan;
     if (!count_done && !count_in_scan) { // the last pass's per-workgroup partials -> selected-row count (+ rows ProjectOp will emit)
         TotalArgs ta;
         std::memset(&ta, 0, sizeof(ta));
@@ -1919,7 +1903,7 @@ static int run_select(imm3_query *q, bool overlap_total, bool count_in_scan = fa
         }
     }
     HIPCHK(hipGetLastError());
-    q->ran_select = true;
+    q->run.ran_select = true;
     return IMM3_OK;
 }
 
@@ -2111,15 +2095,15 @@ static int run_single_pass(imm3_query *q) {
         HIPCHK(hipGetLastError());
         if (chained) HIPCHK(hipEventRecord(dev->last, s));
     }
-    q->stage_written = false;
-    q->count_pending_scan = false;
-    q->has_pfor_pass = false;
-    q->ran_select = true;
-    q->bitmap_valid = true;
-    q->ran_project = true;
-    q->ran_single_pass = true;
-    q->sp_verified = false;
-    q->offsets_valid = false;
+    q->run.stage_written = false;
+    q->run.count_pending_scan = false;
+    q->run.has_pfor_pass = false;
+    q->run.ran_select = true;
+    q->run.bitmap_valid = true;
+    q->run.ran_project = true;
+    q->run.ran_single_pass = true;
+    q->run.sp_verified = false;
+    q->run.offsets_valid = false;
     return IMM3_OK;
 }
 
@@ -2154,7 +2138,7 @@ static int launch_emit_records(imm3_query *q) {
 static int launch_project(imm3_query *q) {
     imm3_ctx *ctx = q->ctx;
     hipStream_t s = ctx->stream;
-    if (q->stage_written) return launch_emit_records(q);
+    if (q->run.stage_written) return launch_emit_records(q);
     GatherArgs g;
     std::memset(&g, 0, sizeof(g));
     g.bitmap = q->d_bitmap;
@@ -2167,7 +2151,7 @@ static int launch_project(imm3_query *q) {
     g.n_staged_tiles = 0;
     g.word_row_base = q->d_word_row_base;
     g.tile_rows = q->table ? q->table->d_tile_rows : nullptr;
-    g.scanned_tiles = q->select_partial ? q->d_total + kFinishLimitTiles : nullptr;
+    g.scanned_tiles = q->run.select_partial ? q->d_total + kFinishLimitTiles : nullptr;
     // more SELECT-list columns than one launch carries: gather in groups (row indices written by the first)
     size_t done = 0;
     const size_t np = q->proj.size();
@@ -2197,7 +2181,7 @@ static int launch_project(imm3_query *q) {
 // `select id ... limit 10`: 7 + 9 us of k_scan + k_gather -> ~5.  Tuning variant 15: off.
 constexpr int kLimitGatherGrid = 256;
 static bool limit_gather_applies(const imm3_query *q) {
-    if (!q->select_partial || !(q->limit > 0) || q->limit > kLimitGatherMaxRows || q->table || q->d_word_row_base || q->stage_written || q->ctx->filter_variant == 15) return false;
+    if (!q->run.select_partial || !(q->limit > 0) || q->limit > kLimitGatherMaxRows || q->table || q->d_word_row_base || q->run.stage_written || q->ctx->filter_variant == 15) return false;
     if (q->n_chunks > (int64_t)kLimitGatherGrid * kLimitGatherMaxChunks || q->proj.size() > (size_t)kMaxProj || !q->d_limit_state) return false;
     for (int32_t pj : q->proj) {
         const SegCol &sc = q->seg->cols[(size_t)q->used[(size_t)pj]];
@@ -2241,12 +2225,12 @@ static int run_project(imm3_query *q) {
         }
         const int rc = launch_limit_gather_for(q);
         if (rc) return rc;
-        q->offsets_valid = false; // (no offsets scan has run on this bitmap)
-        q->ran_project = true;
-        q->limit_gather_ran = true;
+        q->run.offsets_valid = false; // (no offsets scan has run on this bitmap)
+        q->run.ran_project = true;
+        q->run.limit_gather_ran = true;
         return IMM3_OK;
     }
-    q->limit_gather_ran = false;
+    q->run.limit_gather_ran = false;
     if (q->n_tiles > 0) {
         ScanArgs sa;
         std::memset(&sa, 0, sizeof(sa));
@@ -2254,9 +2238,9 @@ static int run_project(imm3_query *q) {
         sa.tile_offsets = q->d_tile_offsets;
         sa.chunk_sums = q->d_chunk_sums;
         sa.n_tiles = q->n_tiles;
-        sa.finish = q->count_pending_scan ? q->d_total : nullptr;
-        sa.scanned_tiles = q->select_partial ? q->d_total + kFinishLimitTiles : nullptr;
-        if (q->stage_written && q->bitmap_lazy) { // no bitmap was stored: the tiles' counts come from the records' start table
+        sa.finish = q->run.count_pending_scan ? q->d_total : nullptr;
+        sa.scanned_tiles = q->run.select_partial ? q->d_total + kFinishLimitTiles : nullptr;
+        if (q->run.stage_written && q->run.bitmap_lazy) { // no bitmap was stored: the tiles' counts come from the records' start table
             sa.rec_tile_start = q->d_tile_start;
             sa.rec_n_waves = (int64_t)q->stage_grid * kWavesPerBlock;
             sa.rec_main_tiles = q->stage_main_tiles;
@@ -2268,7 +2252,7 @@ static int run_project(imm3_query *q) {
             launch_scan(sa, s, t.start, t.stop);
         }
         HIPCHK(hipGetLastError());
-        q->offsets_valid = true;
+        q->run.offsets_valid = true;
     }
     if (!(q->limit > 0) && !q->reserved && !q->d_row_index) {
         // Unlimited projection, no reservation, FIRST run: the output size is the count -> one synchronisation.  The arrays get
@@ -2280,7 +2264,7 @@ static int run_project(imm3_query *q) {
         // rows) say how densely they sit where they sit and how many of them in fully surviving chunks -- the whole segment, where
         // the sample at creation saw 0.5 % of it (a range of a sorted key between two sample chunks showed it nothing)
         std::vector<uint32_t> chunk_counts;
-        if (!q->plan_pinned && !q->table && q->n_chunks > 0 && q->n_chunks <= (1 << 20) && q->offsets_valid) {
+        if (!q->plan_pinned && !q->table && q->n_chunks > 0 && q->n_chunks <= (1 << 20) && q->run.offsets_valid) {
             chunk_counts.resize((size_t)q->n_chunks);
             HIPCHK(hipMemcpyAsync(chunk_counts.data(), q->d_chunk_sums, chunk_counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         }
@@ -2311,10 +2295,10 @@ static int run_project(imm3_query *q) {
                 q->sp_restore_survivors = total;
             }
             records_drop_if_narrow(q, total); // (this run's rows then come from the bitmap)
-            if (!q->d_stage_rec && q->bitmap_lazy) { // ... which the staging launch did not store: the select chain runs once more, plainly (the offsets stand: same counts)
-                const int prc = run_select(q, false, false, false, true);
+            if (!q->d_stage_rec && q->run.bitmap_lazy) { // ... which the staging launch did not store: the select chain runs once more, plainly (the offsets stand: same counts)
+                const int prc = run_select(q, SEL_WHOLE);
                 if (prc) return prc;
-                q->offsets_valid = true;
+                q->run.offsets_valid = true;
             }
         }
         const unsigned long long want = std::min<unsigned long long>((unsigned long long)std::max<int64_t>(q->n_rows, 1), total + total / 8 + 1024);
@@ -2328,7 +2312,7 @@ static int run_project(imm3_query *q) {
         const int rc = launch_project(q);
         if (rc) return rc;
     }
-    q->ran_project = true;
+    q->run.ran_project = true;
     return IMM3_OK;
 }
 
@@ -2361,59 +2345,37 @@ static int capture_note(imm3_query *q, int rc) {
     auto &qs = ctx->capture->queries;
     const auto it = std::find(qs.begin(), qs.end(), q);
     if (it == qs.end()) return rc;
-    QueryRunState &st = ctx->capture->states[(size_t)(it - qs.begin())];
-    st.ran_select = q->ran_select;
-    st.ran_project = q->ran_project;
-    st.bitmap_valid = q->bitmap_valid;
-    st.ran_single_pass = q->ran_single_pass;
-    st.stage_written = q->stage_written;
-    st.bitmap_lazy = q->bitmap_lazy;
-    st.agg_select_skipped = q->agg_select_skipped;
-    st.count_pending_scan = q->count_pending_scan;
-    st.has_pfor_pass = q->has_pfor_pass;
-    st.ran_agg = q->ran_agg;
-    st.offsets_valid = q->offsets_valid;
-    st.select_partial = q->select_partial;
+    ctx->capture->states[(size_t)(it - qs.begin())] = q->run;
     return rc;
 }
 
-extern "C" int imm3_query_run_select(imm3_query *q) {
+// The three run calls: the context's capture gate held for the whole run, the run admitted into an open capture and noted there
+// (capture_note); `plan` is what the call launches.
+static int run_entry(imm3_query *q, int (*plan)(imm3_query *)) {
     if (!q) return fail(IMM3_ERR_ARG, "query is null");
     CTX_LIVE_RUN(q->ctx);
     const int ca = capture_admit(q);
     if (ca) return ca;
-    q->ran_project = false;
-    return capture_note(q, run_select(q, q->ctx->filter_variant == 2));
+    q->run.ran_project = false;
+    return capture_note(q, plan(q));
+}
+
+extern "C" int imm3_query_run_select(imm3_query *q) {
+    return run_entry(q, [](imm3_query *r) { return run_select(r, r->ctx->filter_variant == 2 ? SEL_OVERLAP_TOTAL : SEL_DEFAULT); });
 }
 
 extern "C" int imm3_query_run_count(imm3_query *q) {
-    if (!q) return fail(IMM3_ERR_ARG, "query is null");
-    CTX_LIVE_RUN(q->ctx);
-    const int ca = capture_admit(q);
-    if (ca) return ca;
-    q->ran_project = false;
-    return capture_note(q, run_select(q, false, false, true));
+    return run_entry(q, [](imm3_query *r) { return run_select(r, SEL_COUNT_ONLY); });
 }
 
 extern "C" int imm3_query_join_count(imm3_query *q) {
     if (!q) return fail(IMM3_ERR_ARG, "query is null");
     CTX_LIVE(q->ctx);
     HIPCHK(hipSetDevice(q->ctx->device));
-    // (the hand-off to device-side consumers of the count word: after a limit scan that stopped early the word holds the scanned
-    // prefix's count -- the whole select runs first, as for imm3_query_count and the count all-reduce)
-    const int arc = settle_agg_select(q);
-    if (arc) return arc;
-    const int wrc = settle_whole_select(q);
-    if (wrc) return wrc;
-    return join_total(q, q->ctx->stream);
+    return imm3::join_query_count(q);
 }
 
-extern "C" int imm3_query_run(imm3_query *q) {
-    if (!q) return fail(IMM3_ERR_ARG, "query is null");
-    CTX_LIVE_RUN(q->ctx);
-    const int ca = capture_admit(q);
-    if (ca) return ca;
-    q->ran_project = false;
+static int run_query(imm3_query *q) {
     // Reducing the count on the aux stream (tuning variant 2) measured SLOWER on MI355X / ROCm 7.2 (75.6 vs 67.1 us
     // per step: the cross-queue event packets cost more than the two same-queue launch gaps they remove), so the
     // default keeps the reduce on the main stream.
@@ -2421,17 +2383,20 @@ extern "C" int imm3_query_run(imm3_query *q) {
         const int rrc = single_pass_restore(q, q->sp_restore_survivors);
         if (rrc) return rrc;
     }
-    if (q->single_pass && !q->proj.empty() && !q->always_false && q->n_tiles > 0) return capture_note(q, run_single_pass(q));
+    if (q->single_pass && !q->proj.empty() && !q->always_false && q->n_tiles > 0) return run_single_pass(q);
     const bool select_only = q->proj.empty() && !q->is_agg && q->ctx->filter_variant == 2;
+    const bool count_in_scan = !q->proj.empty() && q->n_tiles > 0 && !q->always_false && q->ctx->filter_variant != 7;
     int rc = IMM3_OK;
-    q->agg_select_skipped = agg_run_fuses(q);
-    if (q->agg_select_skipped) q->ran_select = true; // (bitmap and count on demand: settle_agg_select)
-    else rc = run_select(q, select_only, !q->proj.empty() && q->n_tiles > 0 && !q->always_false && q->ctx->filter_variant != 7);
+    q->run.agg_select_skipped = agg_run_fuses(q);
+    if (q->run.agg_select_skipped) q->run.ran_select = true; // (bitmap and count on demand: settle_agg_select)
+    else rc = run_select(q, (select_only ? SEL_OVERLAP_TOTAL : SEL_DEFAULT) | (count_in_scan ? SEL_COUNT_IN_SCAN : SEL_DEFAULT));
     if (rc) return rc;
     if (!q->proj.empty()) rc = run_project(q);
     if (!rc && q->is_agg) rc = run_agg(q);
-    return capture_note(q, rc);
+    return rc;
 }
+
+extern "C" int imm3_query_run(imm3_query *q) { return run_entry(q, run_query); }
 
 extern "C" int imm3_query_sync(imm3_query *q) {
     if (!q) return fail(IMM3_ERR_ARG, "query is null");
@@ -2486,17 +2451,17 @@ extern "C" int imm3_query_log_counts(imm3_query *q, uint64_t *device_log, uint64
 
 // the offsets scan over the bitmap of the last run (for a gather from the bitmap): tile offsets and chunk sums
 static int scan_offsets(imm3_query *q) {
-    if (q->offsets_valid || q->n_tiles <= 0) return IMM3_OK;
+    if (q->run.offsets_valid || q->n_tiles <= 0) return IMM3_OK;
     ScanArgs sa;
     std::memset(&sa, 0, sizeof(sa));
     sa.bitmap = q->d_bitmap;
     sa.tile_offsets = q->d_tile_offsets;
     sa.chunk_sums = q->d_chunk_sums;
     sa.n_tiles = q->n_tiles;
-    sa.scanned_tiles = q->select_partial ? q->d_total + kFinishLimitTiles : nullptr;
+    sa.scanned_tiles = q->run.select_partial ? q->d_total + kFinishLimitTiles : nullptr;
     launch_scan(sa, q->ctx->stream, nullptr, nullptr); // (finish = null: the count is already published)
     HIPCHK(hipGetLastError());
-    q->offsets_valid = true;
+    q->run.offsets_valid = true;
     return IMM3_OK;
 }
 
@@ -2508,28 +2473,24 @@ static unsigned long long single_pass_flags(const unsigned long long *head) {
     return status & (kStatusAbandoned | kStatusBusy);
 }
 
+// The last run was a records run that stored no bitmap (run_select: bitmap_lazy): a getter wants it -- the select chain runs once
+// more, plainly.  The rows that run emitted stay what they are (the same rows); a later re-gather takes them from the bitmap.
+static int settle_lazy_bitmap(imm3_query *q) {
+    if (q->run.bitmap_valid || !q->run.bitmap_lazy) return IMM3_OK;
+    if (q->ctx->capture) return fail(IMM3_ERR_STATE, "a graph capture is open on this context");
+    return run_select(q, SEL_WHOLE | SEL_PLAIN); // (offsets_valid stands: the offsets scan counted the same survivors from the records)
+}
+
 // A projection with a limit stops its scan when the limit is reached (run_select, chunks): the bitmap and the count then cover the
 // tiles scanned so far.  The reference never sees the batches behind the limit either (Project.scala:73-80); a caller that asks for
 // the segment's count or bitmap all the same gets them exact: the whole select runs now, once (the rows were emitted from the scanned
 // prefix and stay what they are -- they are the first `limit` survivors either way).
-// The last run was a records run that stored no bitmap (run_select: bitmap_lazy): a getter wants it -- the select chain runs once
-// more, plainly.  The rows that run emitted stay what they are (the same rows); a later re-gather takes them from the bitmap.
-static int settle_lazy_bitmap(imm3_query *q) {
-    if (q->bitmap_valid || !q->bitmap_lazy) return IMM3_OK;
-    if (q->ctx->capture) return fail(IMM3_ERR_STATE, "a graph capture is open on this context");
-    q->force_plain_select = true;
-    const int rc = run_select(q, false, false, false, true);
-    q->force_plain_select = false;
-    if (rc) return rc;
-    return IMM3_OK; // (offsets_valid stands: the offsets scan counted the same survivors from the records)
-}
-
 static int settle_whole_select(imm3_query *q) {
-    if (!q->select_partial) return IMM3_OK;
+    if (!q->run.select_partial) return IMM3_OK;
     if (q->ctx->capture) return fail(IMM3_ERR_STATE, "a graph capture is open on this context");
-    const int rc = run_select(q, false, false, false, true);
+    const int rc = run_select(q, SEL_WHOLE);
     if (rc) return rc;
-    q->offsets_valid = false;
+    q->run.offsets_valid = false;
     return IMM3_OK;
 }
 
@@ -2540,13 +2501,13 @@ static int settle_whole_select(imm3_query *q) {
 // every work-group resident?): the query keeps the bitmap path from now on.  Busy (another launch of the kernel owned the device --
 // also when that made other work-groups of this launch time out, flags = busy | abandoned): this run only.
 static int settle_single_pass(imm3_query *q) {
-    if (!q->ran_single_pass || q->sp_verified) return IMM3_OK;
+    if (!q->run.ran_single_pass || q->run.sp_verified) return IMM3_OK;
     imm3_ctx *ctx = q->ctx;
     static_assert(kFinishStatus == 2 && kFinishEpoch < kFinishDense, "count, status word, run counter and dense tally are fetched together");
     unsigned long long head[kFinishDense + 1] = {0}; // {count, rows emitted, status, ..., run counter, dense ranges}
     HIPCHK(hipMemcpyAsync(head, q->d_total, sizeof(head), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    q->sp_verified = true;
+    q->run.sp_verified = true;
     const unsigned long long flags = single_pass_flags(head);
     if (!flags) {
         if (!q->plan_have_density && head[0] > 0 && q->n_rows > 0) { // no sample: what this run saw -- ranges that outgrew their ring mean dense stretches
@@ -2569,32 +2530,53 @@ static int settle_single_pass(imm3_query *q) {
         graphs_mark_stale(ctx, q); // (a recorded run would take the abandoned path again)
         q->single_pass = false;
     }
-    q->ran_single_pass = false; // (the rows the getters see come from the bitmap path)
-    q->stage_written = false;
+    q->run.ran_single_pass = false; // (the rows the getters see come from the bitmap path)
+    q->run.stage_written = false;
     int rc = scan_offsets(q);
     if (rc) return rc;
     return q->n_tiles > 0 ? launch_project(q) : IMM3_OK;
 }
 
+static int settle_agg_select(imm3_query *q);
+// The one settle path of the getters: each names what it needs of the last run, settle() runs those steps, always in this order.
+// A step is a no-op unless the run record (q->run) says the run left that work undone.
+enum SettleStep : unsigned {
+    SETTLE_AGG_SELECT = 1u << 0,   // the select an aggregation fused into its launch (settle_agg_select)
+    SETTLE_LAZY_BITMAP = 1u << 1,  // the bitmap a records run did not store (settle_lazy_bitmap)
+    SETTLE_SINGLE_PASS = 1u << 2,  // a single-pass run's status word: its rows gathered again if it gave up on them (settle_single_pass)
+    SETTLE_WHOLE_SELECT = 1u << 3, // the tiles a limit scan never reached (settle_whole_select)
+    SETTLE_JOIN = 1u << 4,         // the count reduced on the aux stream, joined into the context's stream (join_total)
+};
+enum SettleNeed : unsigned {
+    NEED_HOST_COUNT = SETTLE_AGG_SELECT | SETTLE_SINGLE_PASS | SETTLE_WHOLE_SELECT | SETTLE_JOIN,
+    NEED_DEVICE_COUNT = SETTLE_AGG_SELECT | SETTLE_WHOLE_SELECT | SETTLE_JOIN, // (enqueued only: no host wait)
+    NEED_BITMAP = SETTLE_AGG_SELECT | SETTLE_LAZY_BITMAP | SETTLE_SINGLE_PASS | SETTLE_WHOLE_SELECT,
+    NEED_ROWS = SETTLE_SINGLE_PASS, // (settle_rows then looks at k_limit_gather's give-up tag itself)
+};
+static int settle(imm3_query *q, SettleNeed need) {
+    int rc = IMM3_OK;
+    if (need & SETTLE_AGG_SELECT) rc = settle_agg_select(q);
+    if (!rc && (need & SETTLE_LAZY_BITMAP)) rc = settle_lazy_bitmap(q);
+    if (!rc && (need & SETTLE_SINGLE_PASS)) rc = settle_single_pass(q);
+    if (!rc && (need & SETTLE_WHOLE_SELECT)) rc = settle_whole_select(q);
+    if (!rc && (need & SETTLE_JOIN)) rc = join_total(q, q->ctx->stream);
+    return rc;
+}
+
+// The hand-off to device-side consumers of the count word (imm3_query_join_count, imm3_comm_allreduce_count): it is the segment's
+// count -- after a limit scan that stopped early the whole select runs first, enqueued, no host wait.
+int imm3::join_query_count(imm3_query *q) { return settle(q, NEED_DEVICE_COUNT); }
+
 extern "C" int imm3_query_count(imm3_query *q, uint64_t *selected_rows) {
     if (!q || !selected_rows) return fail(IMM3_ERR_ARG, "null argument");
     CTX_LIVE(q->ctx);
-    if (!q->ran_select) return fail(IMM3_ERR_STATE, "imm3_query_run has not been called");
+    if (!q->run.ran_select) return fail(IMM3_ERR_STATE, "imm3_query_run has not been called");
     HIPCHK(hipSetDevice(q->ctx->device));
-    unsigned long long total = 0;
-    {
-        const int arc = settle_agg_select(q);
-        if (arc) return arc;
-        const int src = settle_single_pass(q);
-        if (src) return src;
-        const int wrc = settle_whole_select(q);
-        if (wrc) return wrc;
-        const int jrc = join_total(q, q->ctx->stream);
-        if (jrc) return jrc;
-    }
-    unsigned long long status = 0;
+    const int rc = settle(q, NEED_HOST_COUNT);
+    if (rc) return rc;
+    unsigned long long total = 0, status = 0;
     HIPCHK(hipMemcpyAsync(&total, q->d_total, sizeof(total), hipMemcpyDeviceToHost, q->ctx->stream));
-    if (q->has_pfor_pass) HIPCHK(hipMemcpyAsync(&status, q->d_total + 2, sizeof(status), hipMemcpyDeviceToHost, q->ctx->stream));
+    if (q->run.has_pfor_pass) HIPCHK(hipMemcpyAsync(&status, q->d_total + 2, sizeof(status), hipMemcpyDeviceToHost, q->ctx->stream));
     HIPCHK(hipStreamSynchronize(q->ctx->stream));
     if (status) return fail(IMM3_ERR_LAYOUT, "malformed PFOR_INT block (width above 32, data past the block end, or count mismatch)");
     *selected_rows = total;
@@ -2604,24 +2586,13 @@ extern "C" int imm3_query_count(imm3_query *q, uint64_t *selected_rows) {
 extern "C" int imm3_query_bitmap(imm3_query *q, uint64_t *words_out, int64_t n_words) {
     if (!q) return fail(IMM3_ERR_ARG, "query is null");
     CTX_LIVE(q->ctx);
-    if (!q->ran_select) return fail(IMM3_ERR_STATE, "imm3_query_run has not been called");
-    if (!q->bitmap_valid && q->bitmap_lazy) {
-        HIPCHK(hipSetDevice(q->ctx->device));
-        const int lrc = settle_lazy_bitmap(q);
-        if (lrc) return lrc;
-    }
-    if (!q->bitmap_valid) return fail(IMM3_ERR_STATE, "the last run was count-only (imm3_query_run_count): it stored no bitmap");
+    if (!q->run.ran_select) return fail(IMM3_ERR_STATE, "imm3_query_run has not been called");
     if (n_words < 0 || n_words > q->n_words) return fail(IMM3_ERR_ARG, "n_words exceeds the bitmap");
     if (n_words && !words_out) return fail(IMM3_ERR_ARG, "words_out is null");
     HIPCHK(hipSetDevice(q->ctx->device));
-    {
-        const int arc = settle_agg_select(q);
-        if (arc) return arc;
-        const int src = settle_single_pass(q);
-        if (src) return src;
-        const int wrc = settle_whole_select(q);
-        if (wrc) return wrc;
-    }
+    const int rc = settle(q, NEED_BITMAP);
+    if (rc) return rc;
+    if (!q->run.bitmap_valid) return fail(IMM3_ERR_STATE, "the last run was count-only (imm3_query_run_count): it stored no bitmap");
     if (n_words) HIPCHK(hipMemcpyAsync(words_out, q->d_bitmap, (size_t)n_words * sizeof(uint64_t), hipMemcpyDeviceToHost, q->ctx->stream));
     HIPCHK(hipStreamSynchronize(q->ctx->stream));
     return IMM3_OK;
@@ -2629,14 +2600,12 @@ extern "C" int imm3_query_bitmap(imm3_query *q, uint64_t *words_out, int64_t n_w
 
 static int settle_rows(imm3_query *q, uint64_t *rows) {
     CTX_LIVE(q->ctx);
-    if (!q->ran_project) return fail(IMM3_ERR_STATE, "no projection has been run (n_proj == 0 or imm3_query_run not called)");
+    if (!q->run.ran_project) return fail(IMM3_ERR_STATE, "no projection has been run (n_proj == 0 or imm3_query_run not called)");
     HIPCHK(hipSetDevice(q->ctx->device));
-    {
-        const int src = settle_single_pass(q);
-        if (src) return src;
-    }
+    const int src = settle(q, NEED_ROWS);
+    if (src) return src;
     unsigned long long emit = 0;
-    if (q->n_tiles > 0 && q->limit_gather_ran) {
+    if (q->n_tiles > 0 && q->run.limit_gather_ran) {
         // k_limit_gather's look-back is bounded: a launch whose wait ran out tagged finish[kFinishLimitGaveUp] with its run and
         // wrote only some of the rows -- gather them the two-launch way (one copy brings the row count, the epoch and the tag)
         unsigned long long head[kFinishLimitGaveUp + 1];
@@ -2645,7 +2614,7 @@ static int settle_rows(imm3_query *q, uint64_t *rows) {
         emit = head[1];
         if (head[kFinishLimitGaveUp] == (((head[kFinishEpoch] & 0x7FFFFFULL) << 1) | 1ULL)) {
             ++q->limit_gather_gave_up;
-            q->limit_gather_ran = false;
+            q->run.limit_gather_ran = false;
             int rc = scan_offsets(q);
             if (rc) return rc;
             rc = launch_project(q);
@@ -2716,7 +2685,7 @@ extern "C" int imm3_query_device_ptr(imm3_query *q, int32_t which, void **ptr) {
 extern "C" int imm3_query_plan(const imm3_query *q, int64_t *out, int32_t n) {
     if (!q || !out) return fail(IMM3_ERR_ARG, "null argument");
     const int64_t v[11] = {q->single_pass ? 1 : 0, q->sp_P, q->sp_grid, q->sp_spans, q->d_stage_rec ? 1 : 0,
-                           (q->single_pass || q->d_stage_rec) ? rec_layout(q->stage_kinds, -1).dwords : 0, q->ran_single_pass ? 1 : 0, (int64_t)q->run_syncs,
+                           (q->single_pass || q->d_stage_rec) ? rec_layout(q->stage_kinds, -1).dwords : 0, q->run.ran_single_pass ? 1 : 0, (int64_t)q->run_syncs,
                            (int64_t)q->sp_abandoned_runs, (int64_t)q->sp_busy_runs, (int64_t)q->limit_gather_gave_up};
     for (int32_t i = 0; i < n && i < 11; ++i) out[i] = v[i];
     return IMM3_OK;
@@ -2886,11 +2855,11 @@ static bool agg_run_fuses(const imm3_query *q) {
 }
 // A getter wants the bitmap or the selected-row count of an aggregation whose last run fused the select: the select chain runs now.
 static int settle_agg_select(imm3_query *q) {
-    if (!q->agg_select_skipped) return IMM3_OK;
+    if (!q->run.agg_select_skipped) return IMM3_OK;
     if (q->ctx->capture) return fail(IMM3_ERR_STATE, "a graph capture is open on this context");
-    const int rc = run_select(q, false);
+    const int rc = run_select(q, SEL_DEFAULT);
     if (rc) return rc;
-    q->agg_select_skipped = false;
+    q->run.agg_select_skipped = false;
     return IMM3_OK;
 }
 
@@ -2898,18 +2867,18 @@ static int run_agg(imm3_query *q) {
     imm3_ctx *ctx = q->ctx;
     AggArgs a;
     agg_launch_args(q, a);
-    if (!q->agg_select_skipped) { a.n_fused = 0; a.fused_all = 0; } // (the select ran: the bitmap is what this launch reads)
+    if (!q->run.agg_select_skipped) { a.n_fused = 0; a.fused_all = 0; } // (the select ran: the bitmap is what this launch reads)
     LaunchTimer t(ctx, 4);
     launch_group_agg(a, ctx->stream, t.start, t.stop);
     HIPCHK(hipGetLastError());
-    q->ran_agg = true;
+    q->run.ran_agg = true;
     return IMM3_OK;
 }
 
 // collect the occupied slots; grows the dense output and collects again if it was too small
 static int settle_groups(imm3_query *q, uint32_t *n_groups) {
     CTX_LIVE(q->ctx);
-    if (!q->is_agg || !q->ran_agg) return fail(IMM3_ERR_STATE, "no aggregation has been run");
+    if (!q->is_agg || !q->run.ran_agg) return fail(IMM3_ERR_STATE, "no aggregation has been run");
     imm3_ctx *ctx = q->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;

@@ -317,8 +317,8 @@ static int local_sum(imm3_comm *c, imm3_query *const *queries, int32_t n_queries
             imm3_query *q = queries[base + i];
             if (!q) return fail(IMM3_ERR_ARG, "query is null");
             if (q->ctx != ctx) return fail(IMM3_ERR_ARG, "the query runs on another context than the communicator");
-            if (!q->ran_select) return fail(IMM3_ERR_STATE, "imm3_query_run has not been called");
-            const int jrc = join_query_count(q, s);
+            if (!q->run.ran_select) return fail(IMM3_ERR_STATE, "imm3_query_run has not been called");
+            const int jrc = join_query_count(q);
             if (jrc) return jrc;
             a.src[i] = q->d_total;
         }
@@ -426,7 +426,7 @@ int same_spec(imm3_query *const *queries, int32_t n, const char **why) {
         imm3_query *q = queries[i];
         if (!q) { *why = "query is null"; return IMM3_ERR_ARG; }
         if (!q->is_agg) { *why = "not an aggregation query"; return IMM3_ERR_ARG; }
-        if (!q->ran_agg) { *why = "imm3_query_run has not been called"; return IMM3_ERR_STATE; }
+        if (!q->run.ran_agg) { *why = "imm3_query_run has not been called"; return IMM3_ERR_STATE; }
         imm3_query *q0 = queries[0];
         if (q->aggs.size() != q0->aggs.size() || q->group_cols.size() != q0->group_cols.size()) { *why = "the queries aggregate differently"; return IMM3_ERR_ARG; }
         for (size_t j = 0; j < q->aggs.size(); ++j)

@@ -82,13 +82,26 @@ struct imm3_ctx {
     std::atomic<uint32_t> fault_max_polls{0};
 };
 
-// What a run leaves in the query handle for the getters: which outputs exist and how they have to be settled.  A graph keeps the
-// state each recorded query had after its (last) recorded run and puts it back at every imm3_graph_launch: a replay IS that run
-// again, whatever direct runs, fallbacks or getters did to the handle in between.
+// What a run leaves in the query handle for the getters: which outputs exist and how they have to be settled (imm3_api.cpp: settle).
+// Every flag that describes the last run lives here and nowhere else.  A graph keeps the record each recorded query had after its
+// (last) recorded run and puts it back whole at every imm3_graph_launch: a replay IS that run again, whatever direct runs, fallbacks
+// or getters did to the handle in between.  Counters, diagnostics, stream bookkeeping and the plan are not run results: they stay
+// in imm3_query, and a replay does not rewind them.
 struct QueryRunState {
-    bool ran_select = false, ran_project = false, bitmap_valid = false, ran_single_pass = false, stage_written = false;
-    bool count_pending_scan = false, has_pfor_pass = false, ran_agg = false, offsets_valid = false, select_partial = false;
-    bool bitmap_lazy = false, agg_select_skipped = false;
+    bool ran_select = false, ran_project = false;
+    bool bitmap_valid = false;       // the last run stored the selection bitmap (a count-only run does not)
+    bool has_pfor_pass = false;      // a k_filter_pfor pass may flag malformed blocks in the status word
+    bool count_pending_scan = false; // the last select run left the count to the projection's offsets scan
+    bool select_partial = false;     // the last select pass was a limit scan in chunks: the bitmap and the count cover the tiles scanned until
+                                     // the limit was reached (finish[kFinishLimitTiles]); imm3_query_count / _bitmap run the whole select first
+    bool offsets_valid = false;      // d_tile_offsets / d_chunk_sums describe the last run's bitmap (an offsets scan has run since)
+    bool stage_written = false;      // the last select run filled the records
+    bool bitmap_lazy = false;        // ... and stored NO bitmap (a records run of imm3_query_run: the records carry the positions, the offsets scan counts them): imm3_query_bitmap runs the select chain then
+    bool ran_agg = false;
+    bool agg_select_skipped = false; // the last run fused the select into the aggregation launch: bitmap and count do not exist until a getter asks (settle_agg_select)
+    bool limit_gather_ran = false;   // the last projection was k_limit_gather's one launch: settle_rows looks at its give-up tag
+    bool ran_single_pass = false;    // the last run went through k_filter_project ...
+    bool sp_verified = false;        // ... and its status word has been read since (rows complete, or gathered again from the bitmap)
 };
 
 // A recorded sequence of query runs (hipGraph): launching it enqueues every kernel of those runs with one call.
@@ -97,7 +110,7 @@ struct imm3_graph {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     std::vector<imm3_query *> queries;    // the queries whose runs were recorded (not retained: destroying one makes the graph stale)
-    std::vector<QueryRunState> states;    // per query: its state after the recorded run
+    std::vector<QueryRunState> states;    // per query: its run state after the recorded run
     bool stale = false;
 };
 
@@ -211,7 +224,6 @@ struct imm3_query {
     uint32_t *d_tile_offsets = nullptr, *d_chunk_sums = nullptr, *d_block_partials = nullptr;
     unsigned long long *d_limit_state = nullptr; // k_limit_gather: per-work-group survivor counts, tagged with the run (small limits only)
     unsigned long long *d_total = nullptr, *d_n_emit = nullptr; // adjacent: d_n_emit = d_total + 1; d_total + 2 = status word
-    bool has_pfor_pass = false;   // a k_filter_pfor pass may flag malformed blocks in the status word
     std::vector<unsigned long long> h_init; // host image of the whole finish block at creation (copied asynchronously: lives with the query)
     std::vector<uint32_t> h_word_row_base;  // ragged layouts: host images of the per-word row map (same reason)
     std::vector<uint8_t> h_word_nvalid;
@@ -221,8 +233,7 @@ struct imm3_query {
     std::vector<uint8_t *> d_proj;
     uint64_t cap_rows = 0;
     bool reserved = false;
-    bool ran_select = false, ran_project = false;
-    bool bitmap_valid = false;     // the last run stored the selection bitmap (a count-only run does not)
+    QueryRunState run;             // what the last run left for the getters
     uint32_t run_syncs = 0;        // times imm3_query_run had to wait for the device (diagnostics: imm3_query_plan)
     // group-by aggregation
     bool is_agg = false;
@@ -233,11 +244,8 @@ struct imm3_query {
     uint32_t *d_afirst = nullptr, *d_ofirst = nullptr, *d_ameta = nullptr; // d_ameta: {n_groups, overflow}
     long long *d_avals = nullptr, *d_ovals = nullptr;
     uint32_t out_cap = 0;
-    bool ran_agg = false;
     bool agg_fusable = false;          // the select chain is closed intervals over <= 2 dense int8 / int32 columns of one uniform segment (or empty): the aggregation kernel can evaluate it itself
-    bool limit_gather_ran = false;     // the last projection was k_limit_gather's one launch: settle_rows looks at its give-up tag
-    uint64_t limit_gather_gave_up = 0; // ... and how often it had to gather the rows again with k_scan + k_gather
-    bool agg_select_skipped = false;   // the last run fused the select into the aggregation launch: bitmap and count do not exist until a getter asks (settle_agg_select)
+    uint64_t limit_gather_gave_up = 0; // times settle_rows found k_limit_gather's give-up tag and gathered the rows again with k_scan + k_gather
     int32_t agg_first_form = imm3::AGG_FORM_LANES; // first kernel form to try: raised past the forms this query's keys overflowed
     // select-only runs: the count reduce goes to ctx->aux, fenced by these events
     hipEvent_t ev_filter_done = nullptr, ev_total_done = nullptr;
@@ -251,9 +259,6 @@ struct imm3_query {
     uint32_t *d_tile_start = nullptr;
     int32_t stage_grid = 0, stage_T = 1, stage_max_slots = 0;
     int64_t stage_wave_cap = 0, stage_main_tiles = 0;
-    bool stage_written = false;   // the last select run filled the records
-    bool bitmap_lazy = false;     // ... and stored NO bitmap (a records run of imm3_query_run: the records carry the positions, the offsets scan counts them): imm3_query_bitmap runs the select chain then
-    bool force_plain_select = false; // the next run_select stages nothing (settle_lazy_bitmap)
     // single-pass projection (k_filter_project, imm3_project.hip): planned at creation for the same queries as the records
     bool single_pass = false;
     int32_t sp_P = 0, sp_grid = 0;          // tiles per wave per span; work-groups (all resident: they wait on each other)
@@ -280,14 +285,8 @@ struct imm3_query {
     unsigned long long *d_desc = nullptr;   // per-span descriptors of the chained scan
     size_t sp_trash_off = 0;                // byte offset of the writers' trash lines in d_desc's allocation
     imm3::ProjectTile *d_tile_desc = nullptr; // table queries: one descriptor per tile of the table for the launch's columns (k_filter_project's TABLE instances)
-    bool ran_single_pass = false;           // the last run went through k_filter_project ...
-    bool sp_verified = false;               // ... and its status word has been read since (rows complete, or gathered again from the bitmap)
-    bool offsets_valid = false;             // d_tile_offsets / d_chunk_sums describe the last run's bitmap (an offsets scan has run since)
     bool count_log_on = false;              // imm3_query_log_counts is installed: every run logs the segment's count (a limit query then scans whole)
-    bool select_partial = false;            // the last select pass was a limit scan in chunks: the bitmap and the count cover the tiles scanned until the
-                                            // limit was reached (finish[kFinishLimitTiles]); imm3_query_count / _bitmap run the whole select first
     uint32_t sp_abandoned_runs = 0, sp_busy_runs = 0; // single-pass runs whose rows were gathered from the bitmap instead: a prefix never came / the device was busy (imm3_query_plan)
-    bool count_pending_scan = false; // the last select run left the count to the projection's offsets scan
 };
 
 
@@ -295,6 +294,6 @@ struct imm3_query {
 namespace imm3 {
 void ctx_retain(imm3_ctx *c);
 void ctx_release(imm3_ctx *c);
-int join_query_count(imm3_query *q, hipStream_t s); // make `s` wait for the query's count if it was reduced on the aux stream
+int join_query_count(imm3_query *q); // settle the query's count word for device-side consumers on the context's stream (enqueued, no host wait)
 int query_groups(imm3_query *q, uint32_t *n_groups);  // the aggregation's dense group list is complete in q->d_o* (synchronises)
 }

@@ -259,7 +259,7 @@ int single_pass_stream_columns(imm3_query *q, uint64_t survivors) {
     pool_release(ctx, q->d_tile_start);
     q->d_stage_rec = nullptr;
     q->d_tile_start = nullptr;
-    q->stage_written = false;
+    q->run.stage_written = false;
     q->alt_ok = false;
     single_pass_adapt(q, survivors, -1);
     return IMM3_OK;
@@ -279,7 +279,7 @@ void records_drop_if_narrow(imm3_query *q, uint64_t survivors) {
     pool_release(ctx, q->d_tile_start);
     q->d_stage_rec = nullptr;
     q->d_tile_start = nullptr;
-    q->stage_written = false;
+    q->run.stage_written = false;
     q->alt_ok = false; // (settled: three launches from the bitmap)
 }
 
@@ -368,7 +368,7 @@ int single_pass_restore(imm3_query *q, uint64_t survivors) {
     pool_release(ctx, q->d_tile_start);
     q->d_stage_rec = nullptr;
     q->d_tile_start = nullptr;
-    q->stage_written = false;
+    q->run.stage_written = false;
     q->sp_model_dropped = false;
     q->sp_narrow_checked = true; // (decided on a count: no second look)
     single_pass_adapt(q, survivors, -1);

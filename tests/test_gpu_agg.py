@@ -280,6 +280,57 @@ def test_lanes_form_overflows_into_the_next_form(ctx):
     seg.close()
 
 
+def test_fused_select_getters_after_run_and_replay(ctx):
+    """A run whose select chain is fused into the lanes launch stores neither bitmap nor count; bitmap(), count() and the device
+    count word behind join_count() run the select then (settle_agg_select) -- on a fresh query, whose first getter once found no
+    bitmap and refused, and after every replay of a recorded graph."""
+    import ctypes as C
+    hip = C.CDLL("libamdhip64.so")
+    rng = np.random.default_rng(5)
+    n = 300 * 1024 + 77
+    br = blocks_of(n, 1024)
+    ids = rng.integers(-1000, 1000, size=n).astype(np.int32)
+    age = rng.integers(-128, 128, size=n).astype(np.int8)
+    st = np.array([list(CODES[i]) for i in rng.integers(0, len(CODES), size=n)], dtype=np.uint8).reshape(n, 2)
+    seg = native.DeviceSegment(ctx, [RawColumn(DENSE_INT, 4, ids, br).native(), RawColumn(DENSE_TINYINT, 1, age, br).native(),
+                                     RawColumn(DENSE_STRING, 2, st, br).native()])
+    keep = (age > 18) & (age < 30)
+    # where (age > 18 and age < 30) group by state: count(id), max(age)   -> used columns [age, state, id]
+    q = native.DeviceQuery(ctx, seg, [1, 2, 0], [(0, GT, 18.0), (0, LT, 30.0)], (), 0, 1024,
+                           group_cols=[1], aggs=[(KIND["count"], 2), (KIND["max"], 0)])
+    words = np.packbits(keep, bitorder="little").tobytes().ljust(q.total_words * 8, b"\0")
+
+    def device_count():
+        q.join_count()
+        ctx.sync()
+        out = np.zeros(1, np.uint64)
+        assert hip.hipMemcpy(C.c_void_p(out.ctypes.data), C.c_void_p(q.device_ptr(1)), C.c_size_t(8), C.c_int(2)) == 0
+        return int(out[0])
+
+    getters = (("bitmap", lambda: q.bitmap().tobytes() == words), ("count", lambda: q.count() == int(keep.sum())),
+               ("device count", lambda: device_count() == int(keep.sum())))
+    ctx.timing_enable(64)
+    try:
+        q.run()
+        assert ctx.timing_collect(0).size == 0 and ctx.timing_collect(4).size == 1       # no filter launch: the select ran fused
+    finally:
+        ctx.timing_enable(0)
+    for name, ok in getters:                                                           # each getter first after a fused run
+        if name != "bitmap":
+            q.run()
+        assert ok(), name
+    _, _, counts, vals = q.fetch_groups()
+    assert int(counts.sum()) == int(keep.sum()) and vals[:, 1].max() == 29
+    with ctx.capture() as cap:
+        q.run()
+    for name, ok in getters:
+        cap.graph.launch()
+        assert ok(), ("replay", name)
+    cap.graph.close()
+    q.close()
+    seg.close()
+
+
 # ---- cross-segment merge behind the C ABI: imm3_comm_merge_groups (ProjectAggregateQueueOp) ------------------------------------
 def _decode_merged(ucols, group, aggs, keys, counts, vals):
     got = []

@@ -13,8 +13,8 @@ Project.scala:37-64, done by the offsets scan + k_gather instead).  Round 3 only
   * a foreign ticket in the device's lock word (any build) makes every launch find the device busy: same checks, and the query
     keeps the one-launch plan for later runs;
   * graph replays: a replay that goes wrong after a getter has already verified an earlier run is noticed (round 3 kept the stale
-    `verified` flag), and two graphs replayed from two contexts without any host ordering give right rows whichever of them the
-    device lock refused.
+    `verified` flag), two graphs replayed from two contexts without any host ordering give right rows whichever of them the
+    device lock refused, and every replay of a small-limit gather that gave up has its rows gathered again.
 
 One process loads one build of the library, so the checks run in a child process with IMM3_LIB_PATH set."""
 import os
@@ -72,10 +72,10 @@ def check_rows(q, tag):
     assert q.bitmap().tobytes() == bitmap[: q.total_words * 8].ljust(q.total_words * 8, b"\0"), tag
 
 _ff = np.full(rows.size, 0xFFFFFFFF, np.uint32)
-def poison(q):
-    """Overwrite the query's row-index array on the device (the caller has synchronised): rows left over from an earlier, good run
-    must not pass for the rows of a run that gave up on them."""
-    assert hip.hipMemcpy(C.c_void_p(q.device_ptr(2)), C.c_void_p(_ff.ctypes.data), C.c_size_t(4 * rows.size), C.c_int(1)) == 0
+def poison(q, k=rows.size):
+    """Overwrite the first k entries of the query's row-index array on the device (the caller has synchronised): rows left over
+    from an earlier, good run must not pass for the rows of a run that gave up on them."""
+    assert hip.hipMemcpy(C.c_void_p(q.device_ptr(2)), C.c_void_p(_ff.ctypes.data), C.c_size_t(4 * k), C.c_int(1)) == 0
 
 def fresh(cx=None, sg=None):
     cx, sg = cx or ctx, sg or seg
@@ -323,6 +323,19 @@ for wg in (0, 3):
     q.run()
     idx, vals = q.fetch_rows()
     assert (idx == rows[:LIM]).all() and q.plan()["limit_gather_gave_up"] == 1, q.plan()
+    # a recorded run that gives up: every replay is that run again, and its rows are gathered again after each of them
+    ctx.inject_fault(wg, 0, 200)
+    with ctx.capture() as cap:
+        q.run()
+    ctx.inject_fault(-1, -1, 0)
+    for rep in (1, 2):
+        poison(q, LIM)                                                  # (the fetches above grew the row arrays past LIM)
+        cap.graph.launch(); ctx.sync()
+        idx, vals = q.fetch_rows()
+        assert idx.size == LIM and (idx == rows[:LIM]).all(), ("limit gather gave up in a replay", wg, rep)
+        assert vals[0].tobytes() == np.ascontiguousarray(a[rows[:LIM]]).tobytes() and vals[1].tobytes() == np.ascontiguousarray(c[rows[:LIM]]).tobytes()
+        assert q.plan()["limit_gather_gave_up"] == 1 + rep, q.plan()
+    cap.graph.close()
     q.close()
 print("limit gather ok", flush=True)
 comm.close(); seg.close(); ctx.close()
