@@ -989,15 +989,9 @@ static int segment_layout(const imm3_segment *cseg, const std::vector<int32_t> &
     return IMM3_OK;
 }
 
-// Can this folded predicate go through the tile kernel?
-static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_table *table,
-                                 const int32_t *used_cols, int32_t n_used,
-                                 const imm3_select *sels, int32_t n_sels,
-                                 const int32_t *proj, int32_t n_proj, int64_t limit,
-                                 int32_t table_block_size, imm3_query **out) {
-    if (!seg || !out) return fail(IMM3_ERR_ARG, "null argument");
-    *out = nullptr;
-    CTX_LIVE(ctx);
+// Query creation, step 1: the arguments and the SelectOp conditions.
+static int check_create_args(imm3_ctx *ctx, const imm3_segment *seg, const imm3_table *table, const int32_t *used_cols, int32_t n_used,
+                             const imm3_select *sels, int32_t n_sels, const int32_t *proj, int32_t n_proj) {
     if (seg->closed || (table && table->closed)) return fail(IMM3_ERR_STATE, "the segment / table has been destroyed");
     if (seg->ctx->device != ctx->device) return fail(IMM3_ERR_ARG, "segment lives on another device");
     if (n_used <= 0 || !used_cols) return fail(IMM3_ERR_ARG, "a scan needs at least one used column");
@@ -1017,9 +1011,8 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
         const int wrc = segment_await(ctx, seg);
         if (wrc) return wrc;
     }
-
-    // (1) SelectOp.iterator (Select.scala:17-23) rejects NotMatch / NoOp when the chain is built,
-    //     whether or not the segment has any block.
+    // SelectOp.iterator (Select.scala:17-23) rejects NotMatch / NoOp when the chain is built,
+    // whether or not the segment has any block.
     for (int32_t i = 0; i < n_sels; ++i) {
         const int c = sels[i].cond;
         if (c != IMM3_MATCH && c != IMM3_GT && c != IMM3_LT && c != IMM3_EQ)
@@ -1027,24 +1020,15 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
         if (c == IMM3_MATCH && sels[i].n_match > 0 && (!sels[i].match_bytes || !sels[i].match_lens))
             return fail(IMM3_ERR_ARG, "Match without values");
     }
+    return IMM3_OK;
+}
 
-    std::unique_ptr<imm3_query, void (*)(imm3_query *)> q(new imm3_query(), query_free);
-    q->ctx = ctx;
-    ctx_retain(ctx);
-    q->seg = seg;
-    q->table = table;
-    if (table) const_cast<imm3_table *>(table)->refs.fetch_add(1, std::memory_order_relaxed); // (the table holds its segments)
-    else segment_retain(seg);
-    q->table_block_size = table_block_size;
-    q->used.assign(used_cols, used_cols + n_used);
-    q->proj.assign(proj, proj + n_proj);
-    q->limit = limit;
-
-    // (2) batches (segment_layout); a table query concatenates the segments' batches, each segment's bitmap starting
-    //     on a fresh tile of the virtual row space
-    int32_t nb = 0;
-    if (!table) {
-        const int lrc = segment_layout(seg, q->used, q->layout);
+// Step 2: the batches (segment_layout), returned in `nb`; a table query concatenates the segments' batches, each segment's bitmap
+// starting on a fresh tile of the virtual row space.  When there are batches, the codecs and vector types ScanOp and SelectOp
+// dispatch on are checked.
+static int scan_layout(imm3_query *q, const imm3_select *sels, int32_t n_sels, int32_t &nb) {
+    if (!q->table) {
+        const int lrc = segment_layout(q->seg, q->used, q->layout);
         if (lrc) return lrc;
         const SegLayout &L = *q->layout;
         nb = (int32_t)L.size.size();
@@ -1055,113 +1039,121 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
     } else {
         // every column of a table shares one block layout (imm3_table_create), so the batches do not depend on which
         // columns are used: they live in the table
-        nb = (int32_t)table->batch_size.size();
-        q->n_rows = table->n_rows;
-        q->n_tiles = table->n_tiles;
-        q->n_words = table->n_tiles * kTileWords; // virtual: every segment padded to whole tiles
+        nb = (int32_t)q->table->batch_size.size();
+        q->n_rows = q->table->n_rows;
+        q->n_tiles = q->table->n_tiles;
+        q->n_words = q->table->n_tiles * kTileWords; // virtual: every segment padded to whole tiles
     }
     q->n_chunks = (q->n_tiles + kChunkTiles - 1) / kChunkTiles;
+    if (nb < 1) return IMM3_OK;
+    // ScanOp.next dispatches on the codec of every used column (Scan.scala:37-50) ...
+    for (int32_t sci : q->used) {
+        const SegCol &sc = q->seg->cols[(size_t)sci];
+        // PFOR_INT: the reference dispatches it too (Scan.scala:37-39) but its decode throws on every block
+        // (PFORCodec.scala:43-50); here the blocks its encoder writes are decoded (imm3_codec.hip).
+        // Snappy-coded columns (IMM3_SNAPPY_*) are this library's extension: the reference only has the encoder.
+        if (sc.vcodec != IMM3_DENSE_INT && sc.vcodec != IMM3_DENSE_TINYINT && sc.vcodec != IMM3_DENSE_STRING)
+            return fail(IMM3_ERR_NO_CODEC, "No implementation for codec " + std::to_string(sc.codec));
+        if ((sc.vcodec == IMM3_DENSE_INT && sc.width != 4) || (sc.vcodec == IMM3_DENSE_TINYINT && sc.width != 1))
+            return fail(IMM3_ERR_ARG, "width does not match codec");
+    }
+    // ... and each SelectIterator dispatches on the vector type (Select.scala:41,80,118,156).
+    for (int32_t i = 0; i < n_sels; ++i) {
+        const SegCol &sc = q->seg->cols[(size_t)q->used[(size_t)sels[i].column]];
+        const bool is_str = sc.vcodec == IMM3_DENSE_STRING;
+        if ((sels[i].cond == IMM3_MATCH) != is_str) return fail(IMM3_ERR_UNSUPPORTED_VECTOR, "Unsupported column vector");
+    }
+    return IMM3_OK;
+}
 
-    if (nb >= 1) {
-        // ScanOp.next dispatches on the codec of every used column (Scan.scala:37-50) ...
-        for (int32_t i = 0; i < n_used; ++i) {
-            const SegCol &sc = seg->cols[(size_t)q->used[(size_t)i]];
-            // PFOR_INT: the reference dispatches it too (Scan.scala:37-39) but its decode throws on every block
-            // (PFORCodec.scala:43-50); here the blocks its encoder writes are decoded (imm3_codec.hip).
-            // Snappy-coded columns (IMM3_SNAPPY_*) are this library's extension: the reference only has the encoder.
-            if (sc.vcodec != IMM3_DENSE_INT && sc.vcodec != IMM3_DENSE_TINYINT && sc.vcodec != IMM3_DENSE_STRING)
-                return fail(IMM3_ERR_NO_CODEC, "No implementation for codec " + std::to_string(sc.codec));
-            if ((sc.vcodec == IMM3_DENSE_INT && sc.width != 4) || (sc.vcodec == IMM3_DENSE_TINYINT && sc.width != 1))
-                return fail(IMM3_ERR_ARG, "width does not match codec");
+// Step 3 (a segment with batches): fold the SelectOp leaves per column into q->preds.  Every leaf only clears bits
+// (Select.scala:37,68,106,144) and runOps ignores AND/OR (Engine.scala:240), so the chain is a conjunction and order is irrelevant.
+static int fold_selects(imm3_query *q, const imm3_select *sels, int32_t n_sels) {
+    for (int32_t i = 0; i < n_sels; ++i) {
+        const int32_t sci = q->used[(size_t)sels[i].column];
+        const SegCol &sc = q->seg->cols[(size_t)sci];
+        FoldedPred *fp = pred_on(q->preds, sci);
+        const bool fresh = !fp;
+        if (fresh) {
+            q->preds.push_back(unfolded_pred(sci, sc.vcodec, sc.width));
+            fp = &q->preds.back();
         }
-        // ... and each SelectIterator dispatches on the vector type (Select.scala:41,80,118,156).
-        for (int32_t i = 0; i < n_sels; ++i) {
-            const SegCol &sc = seg->cols[(size_t)q->used[(size_t)sels[i].column]];
-            const bool is_str = sc.vcodec == IMM3_DENSE_STRING;
-            if ((sels[i].cond == IMM3_MATCH) != is_str) return fail(IMM3_ERR_UNSUPPORTED_VECTOR, "Unsupported column vector");
+        if (fp->kind == KIND_STR) {
+            std::vector<std::string> vals;
+            int64_t off = 0;
+            for (int32_t m = 0; m < sels[i].n_match; ++m) {
+                const int32_t len = sels[i].match_lens[m];
+                if (len < 0) return fail(IMM3_ERR_ARG, "negative match length");
+                // String.equals can only hold for a value of exactly `width` bytes (DataType.scala:69-70)
+                if (len == sc.width) {
+                    std::string v((const char *)sels[i].match_bytes + off, (size_t)len);
+                    if (std::find(vals.begin(), vals.end(), v) == vals.end()) vals.push_back(v);
+                }
+                off += len;
+            }
+            if (fresh) fp->match = vals;
+            else {
+                std::vector<std::string> both;
+                for (auto &v : fp->match)
+                    if (std::find(vals.begin(), vals.end(), v) != vals.end()) both.push_back(v);
+                fp->match = both;
+            }
+        } else {
+            const int64_t t = fp->kind == KIND_I32 ? (int64_t)jvm_d2i(sels[i].value) : (int64_t)jvm_d2b(sels[i].value);
+            if (sels[i].cond == IMM3_GT) fp->lo = std::max(fp->lo, t + 1);      // strict >, Select.scala:68,76
+            else if (sels[i].cond == IMM3_LT) fp->hi = std::min(fp->hi, t - 1); // strict <, Select.scala:106,114
+            else { fp->lo = std::max(fp->lo, t); fp->hi = std::min(fp->hi, t); } // ==, Select.scala:144,152
         }
     }
+    for (const auto &p : q->preds)
+        if (p.kind == KIND_STR ? p.match.empty() : p.lo > p.hi) q->always_false = true;
+    return IMM3_OK;
+}
 
-    // (3) fold the SelectOp leaves per column.  Every leaf only clears bits (Select.scala:37,68,106,144) and
-    //     runOps ignores AND/OR (Engine.scala:240), so the chain is a conjunction and order is irrelevant.
-    if (nb >= 1) {
-        for (int32_t i = 0; i < n_sels; ++i) {
-            const int32_t sci = q->used[(size_t)sels[i].column];
-            const SegCol &sc = seg->cols[(size_t)sci];
-            FoldedPred *fp = nullptr;
-            for (auto &p : q->preds)
-                if (p.seg_col == sci) fp = &p;
-            const bool fresh = !fp;
-            if (fresh) {
-                q->preds.emplace_back();
-                fp = &q->preds.back();
-                fp->seg_col = sci;
-                fp->width = sc.width;
-                if (sc.vcodec == IMM3_DENSE_INT) { fp->kind = KIND_I32; fp->lo = INT32_MIN; fp->hi = INT32_MAX; }
-                else if (sc.vcodec == IMM3_DENSE_TINYINT) { fp->kind = KIND_I8; fp->lo = -128; fp->hi = 127; }
-                else fp->kind = KIND_STR;
-            }
-            if (fp->kind == KIND_STR) {
-                std::vector<std::string> vals;
-                int64_t off = 0;
-                for (int32_t m = 0; m < sels[i].n_match; ++m) {
-                    const int32_t len = sels[i].match_lens[m];
-                    if (len < 0) return fail(IMM3_ERR_ARG, "negative match length");
-                    // String.equals can only hold for a value of exactly `width` bytes (DataType.scala:69-70)
-                    if (len == sc.width) {
-                        std::string v((const char *)sels[i].match_bytes + off, (size_t)len);
-                        if (std::find(vals.begin(), vals.end(), v) == vals.end()) vals.push_back(v);
-                    }
-                    off += len;
-                }
-                if (fresh) fp->match = vals;
-                else {
-                    std::vector<std::string> both;
-                    for (auto &v : fp->match)
-                        if (std::find(vals.begin(), vals.end(), v) != vals.end()) both.push_back(v);
-                    fp->match = both;
-                }
-            } else {
-                const int64_t t = fp->kind == KIND_I32 ? (int64_t)jvm_d2i(sels[i].value) : (int64_t)jvm_d2b(sels[i].value);
-                if (sels[i].cond == IMM3_GT) fp->lo = std::max(fp->lo, t + 1);      // strict >, Select.scala:68,76
-                else if (sels[i].cond == IMM3_LT) fp->hi = std::min(fp->hi, t - 1); // strict <, Select.scala:106,114
-                else { fp->lo = std::max(fp->lo, t); fp->hi = std::min(fp->hi, t); } // ==, Select.scala:144,152
-            }
-        }
-        // PFOR_INT columns: a predicate-only column of a tile-aligned segment is evaluated on its compressed blocks
-        // (k_filter_pfor); anything else reads the decoded column, made once per segment.
-        for (int32_t i = 0; i < n_used; ++i) {
-            const int32_t sci = q->used[(size_t)i];
-            const SegCol &sc = seg->cols[(size_t)sci];
-            if (!is_compressed(sc.codec)) continue;
-            bool projected = false;
-            for (int32_t pj : q->proj) projected |= (pj == i);
-            FoldedPred *fp = nullptr;
-            for (auto &p : q->preds)
-                if (p.seg_col == sci) fp = &p;
-            const bool fused = sc.codec == IMM3_PFOR_INT && fp && !table && !q->ragged && sc.tile_aligned && !projected &&
-                               ctx->filter_variant != 1 && ctx->filter_variant != 5;
-            if (fused) fp->pfor = true;
-            else if (!table) { // a table decodes its PFOR_INT columns when it is created
-                const int drc = ensure_dense(ctx, seg, sci);
-                if (drc) return drc;
-            }
-        }
-        for (auto &p : q->preds) {
-            if (p.kind == KIND_STR ? p.match.empty() : p.lo > p.hi) q->always_false = true;
-            if (p.kind == KIND_STR && (p.width > 8 || p.match.size() > (size_t)kMaxMatch) && !p.match.empty()) {
-                std::string blob;
-                for (auto &v : p.match) blob += v;
-                void *d = nullptr;
-                HIPCHK(pool_alloc(ctx, &d, blob.size()));
-                p.d_blob = (uint8_t *)d;
-                HIPCHK(hipMemcpyAsync(d, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
-                HIPCHK(hipStreamSynchronize(ctx->stream));
-            }
+// Step 4: where compressed columns are read.  A PFOR_INT predicate-only column of a tile-aligned segment is evaluated on its
+// compressed blocks (k_filter_pfor); anything else reads the decoded column, made once per segment.  `row_cols` are the used
+// columns an aggregation reads row by row (its group and aggregate columns; matched by segment column: a predicate on the same
+// column is not fused either).  Without batches only those are decoded.
+static int place_compressed(imm3_query *q, bool have_batches, const std::vector<int32_t> &row_cols) {
+    const int fv = q->ctx->filter_variant;
+    for (int32_t i = 0; i < (int32_t)q->used.size(); ++i) {
+        const int32_t sci = q->used[(size_t)i];
+        const SegCol &sc = q->seg->cols[(size_t)sci];
+        bool agg_reads = false;
+        for (int32_t r : row_cols) agg_reads |= r >= 0 && r < (int32_t)q->used.size() && q->used[(size_t)r] == sci;
+        if (!is_compressed(sc.codec) || !(have_batches || agg_reads)) continue;
+        bool projected = false;
+        for (int32_t pj : q->proj) projected |= (pj == i);
+        FoldedPred *fp = pred_on(q->preds, sci);
+        const bool fused = sc.codec == IMM3_PFOR_INT && fp && !q->table && !q->ragged && sc.tile_aligned && !projected && !agg_reads &&
+                           fv != TV_GENERIC_ONLY && fv != TV_PFOR_DECODED;
+        if (fused) fp->pfor = true;
+        else if (!q->table) { // a table decodes its PFOR_INT columns when it is created
+            const int drc = ensure_dense(q->ctx, q->seg, sci);
+            if (drc) return drc;
         }
     }
+    return IMM3_OK;
+}
 
-    // (4) device buffers
+// Step 5: IN-lists too long for the kernel arguments go to the device.
+static int upload_match_blobs(imm3_query *q) {
+    for (auto &p : q->preds) {
+        if (p.kind != KIND_STR || p.match.empty() || (p.width <= 8 && p.match.size() <= (size_t)kMaxMatch)) continue;
+        std::string blob;
+        for (auto &v : p.match) blob += v;
+        void *d = nullptr;
+        HIPCHK(pool_alloc(q->ctx, &d, blob.size()));
+        p.d_blob = (uint8_t *)d;
+        HIPCHK(hipMemcpyAsync(d, blob.data(), blob.size(), hipMemcpyHostToDevice, q->ctx->stream));
+        HIPCHK(hipStreamSynchronize(q->ctx->stream));
+    }
+    return IMM3_OK;
+}
+
+// Step 6: the device buffers every query has, and their initial contents.
+static int alloc_buffers(imm3_query *q) {
+    imm3_ctx *ctx = q->ctx;
     void *p = nullptr;
     const size_t words_alloc = (size_t)std::max<int64_t>(q->n_tiles * kTileWords, 1);
     HIPCHK(pool_alloc(ctx, &p, words_alloc * sizeof(uint64_t)));
@@ -1172,7 +1164,7 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
     q->d_chunk_sums = (uint32_t *)p;
     HIPCHK(pool_alloc(ctx, &p, kMaxFilterGrid * sizeof(uint32_t)));
     q->d_block_partials = (uint32_t *)p;
-    if (limit > 0 && limit <= kLimitGatherMaxRows && !table) { // (k_limit_gather's per-work-group counts: pooled memory, so cleared -- a run's tag is never zero)
+    if (q->limit > 0 && q->limit <= kLimitGatherMaxRows && !q->table) { // (k_limit_gather's per-work-group counts: pooled memory, so cleared -- a run's tag is never zero)
         HIPCHK(pool_alloc(ctx, &p, 256 * sizeof(unsigned long long)));
         q->d_limit_state = (unsigned long long *)p;
         HIPCHK(hipMemsetAsync(q->d_limit_state, 0, 256 * sizeof(unsigned long long), ctx->stream));
@@ -1186,22 +1178,18 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
     // n_words in its last tile need to be zero (the offsets scan and the aggregation read whole tiles): every run writes all the
     // others before anything reads them.
     q->h_init.assign((size_t)kFinishWords, 0ULL);
-    q->h_init[3] = (unsigned long long)limit;
+    q->h_init[3] = (unsigned long long)q->limit;
     HIPCHK(hipMemcpyAsync(q->d_total, q->h_init.data(), (size_t)kFinishWords * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
-    {
-        const size_t first_pad = (size_t)std::min<int64_t>(std::max<int64_t>(q->n_words, 0), (int64_t)words_alloc);
-        const size_t from = first_pad; // (words [n_words, words_alloc): at most one tile's worth)
-        if (from < words_alloc) HIPCHK(hipMemsetAsync(q->d_bitmap + from, 0, (words_alloc - from) * sizeof(uint64_t), ctx->stream));
-    }
-    if (q->ragged) {
+    const size_t from = (size_t)std::min<int64_t>(std::max<int64_t>(q->n_words, 0), (int64_t)words_alloc); // (words [n_words, words_alloc): at most one tile's worth)
+    if (from < words_alloc) HIPCHK(hipMemsetAsync(q->d_bitmap + from, 0, (words_alloc - from) * sizeof(uint64_t), ctx->stream));
+    if (q->ragged) { // the first row and the valid rows of every bitmap word
         std::vector<uint32_t> &base = q->h_word_row_base;
         std::vector<uint8_t> &nvalid = q->h_word_nvalid;
         base.assign((size_t)q->n_tiles * kTileWords, 0u);
         nvalid.assign((size_t)q->n_tiles * kTileWords, 0);
         int64_t row = 0;
         size_t w = 0;
-        for (int32_t k = 0; k < nb; ++k) {
-            const int64_t n = q->layout->size[(size_t)k];
+        for (const int64_t n : q->layout->size) {
             for (int64_t r = 0; r < n; r += 64) {
                 base[w] = (uint32_t)(row + r);
                 nvalid[w] = (uint8_t)std::min<int64_t>(64, n - r);
@@ -1218,156 +1206,41 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
             HIPCHK(hipMemcpyAsync(q->d_word_nvalid, nvalid.data(), nvalid.size(), hipMemcpyHostToDevice, ctx->stream));
         }
     }
-    if (n_proj > 0 && limit > 0) {
-        const int rc = ensure_row_capacity(q.get(), (uint64_t)std::min<int64_t>(limit, std::max<int64_t>(q->n_rows, 1)));
-        if (rc) return rc;
-    }
-    // Survivor records (k_filter_tile STAGE -> k_emit): an unlimited projection over one uniform segment whose select chain
-    // is ONE tile launch (<= 3 predicate columns of int32 / int8 / 2-byte string, at most one string; none is also fine:
-    // the record is then the position alone) and whose SELECT list is 1-, 2- and 4-byte columns, at most kMaxEmitGather of
-    // them not predicate columns.
-    // A table query (every segment the GPU owns as one scan unit) takes the ONE-LAUNCH plan under the same conditions when no
-    // SELECT-list column has to be gathered (round 5; its TABLE instances walk the tile table); survivor records and streamed
-    // gathers are one-segment plans, the bitmap path is a table's other plan.
-    if (n_proj > 0 && limit <= 0 && !q->ragged && !q->always_false && nb >= 1 && q->n_rows > 0 && ctx->filter_variant != 1 &&
-        ctx->filter_variant != 3 && q->preds.size() <= (size_t)kMaxTileCols && n_proj <= kMaxProj) {
-        std::vector<const FoldedPred *> order;
-        int n_s2 = 0;
-        bool ok = true;
-        for (const auto &fp : q->preds) {
-            const int tk = fp.pfor ? (int)TK_NONE : tile_kind(fp);
-            if (tk == TK_NONE) ok = false;
-            n_s2 += tk == TK_S2;
-            order.push_back(&fp);
-        }
-        ok = ok && n_s2 <= 1;
-        std::stable_sort(order.begin(), order.end(), [](const FoldedPred *x, const FoldedPred *y) { return tile_kind(*x) < tile_kind(*y); });
-        int n_gather = 0;
-        int n_pred_proj = 0;       // predicate columns in the SELECT list (first mentions: their values ride in the records) ...
-        bool pred_proj_wide = false; // ... and whether one of them is wider than a byte
-        std::vector<int32_t> seen; // predicate columns already mentioned in the SELECT list: a second mention is gathered
-        for (int32_t pj : q->proj) {
-            const int32_t sci = q->used[(size_t)pj];
-            const int32_t w = seg->cols[(size_t)sci].width;
-            if (w != 1 && w != 2 && w != 4) ok = false;
-            bool is_pred = false;
-            for (const FoldedPred *fp : order) is_pred |= fp->seg_col == sci;
-            if (is_pred && std::find(seen.begin(), seen.end(), sci) != seen.end()) is_pred = false;
-            if (is_pred) {
-                seen.push_back(sci);
-                ++n_pred_proj;
-                pred_proj_wide |= w > 1;
-            }
-            n_gather += !is_pred;
-        }
-        if (ok && n_gather <= kMaxEmitGather && (!table || (n_gather == 0 && ctx->filter_variant != 6))) {
-            for (size_t k = 0; k < order.size(); ++k) {
-                q->stage_kinds[k] = tile_kind(*order[k]);
-                q->stage_seg_col[k] = order[k]->seg_col;
-            }
-            {   // what the cost model needs to know (imm3_plan.h)
-                PlanShape &ps = q->plan_shape;
-                ps = PlanShape();
-                ps.n_rows = q->n_rows;
-                for (const FoldedPred *fp : order) {
-                    if (ps.n_pred >= kPlanMaxCols) break;
-                    ps.pred_width[ps.n_pred] = fp->width;
-                    ps.pred_match[ps.n_pred] = tile_kind(*fp) == TK_S2 ? (int32_t)fp->match.size() : 0;
-                    ++ps.n_pred;
-                }
-                std::vector<int32_t> first; // predicate columns already mentioned (a second mention is gathered)
-                for (int32_t pj : q->proj) {
-                    if (ps.n_proj >= kPlanMaxCols) break;
-                    const int32_t sci = q->used[(size_t)pj];
-                    bool is_pred = false;
-                    for (const FoldedPred *fp : order) is_pred |= fp->seg_col == sci;
-                    if (is_pred && std::find(first.begin(), first.end(), sci) != first.end()) is_pred = false;
-                    if (is_pred) first.push_back(sci);
-                    ps.proj_width[ps.n_proj] = seg->cols[(size_t)sci].width;
-                    ps.proj_is_pred[ps.n_proj] = is_pred;
-                    ++ps.n_proj;
-                }
-                ps.rec_bytes = 4 * rec_layout(q->stage_kinds, -1).dwords;
-                q->plan_pinned = ctx->filter_variant == 12;
-            }
-            // Single pass (k_filter_project): the filter kernel writes the rows itself.  Tuning variant 6 keeps the
-            // three-launch form (records -> k_scan -> k_emit) for A/B runs.
-            // Only when every SELECT-list column is a predicate column (its values ride in the records): gathers issued by the
-            // four writer waves of a CU are latency-bound (C4 154 us against 118 us with the emit kernel's 2048 work-groups).
-            if (ctx->filter_variant != 6 && (n_gather == 0 || ctx->filter_variant == 8)) {
-                const int rc = single_pass_setup(q.get());
-                if (rc) return rc;
-            }
-            if (!q->single_pass && n_gather > 0 && ctx->filter_variant != 6 && !table) {
-                // The alternative the first count may switch to (single_pass_stream_columns): every gathered column of the SELECT list
-                // (first mentions; dense int32 / int8) as a tile column that lets every value pass.
-                std::vector<FoldedPred> pass;
-                bool alt = true;
-                for (int32_t pj : q->proj) {
-                    const int32_t sci = q->used[(size_t)pj];
-                    bool have = false;
-                    for (const FoldedPred *fp : order) have |= fp->seg_col == sci;
-                    for (const FoldedPred &fp : pass) have |= fp.seg_col == sci;
-                    if (have) continue;
-                    const SegCol &sc = seg->cols[(size_t)sci];
-                    FoldedPred fp;
-                    fp.seg_col = sci;
-                    fp.width = sc.width;
-                    if (sc.codec == IMM3_DENSE_INT && sc.width == 4) { fp.kind = KIND_I32; fp.lo = INT32_MIN; fp.hi = INT32_MAX; }
-                    else if (sc.codec == IMM3_DENSE_TINYINT && sc.width == 1) { fp.kind = KIND_I8; fp.lo = -128; fp.hi = 127; }
-                    else { alt = false; break; }
-                    if (!col_flat(sc)) { alt = false; break; }
-                    pass.push_back(fp);
-                }
-                if (alt && !pass.empty() && order.size() + pass.size() <= (size_t)kMaxTileCols) {
-                    q->sp_pass = pass;
-                    std::vector<const FoldedPred *> all(order);
-                    for (const FoldedPred &fp : q->sp_pass) all.push_back(&fp);
-                    std::stable_sort(all.begin(), all.end(), [](const FoldedPred *x, const FoldedPred *y) { return tile_kind(*x) < tile_kind(*y); });
-                    bool any4 = false;
-                    for (int k = 0; k < kMaxTileCols; ++k) {
-                        q->alt_kinds[k] = (size_t)k < all.size() ? tile_kind(*all[(size_t)k]) : (int)TK_NONE;
-                        q->alt_seg_col[k] = (size_t)k < all.size() ? all[(size_t)k]->seg_col : -1;
-                    }
-                    for (const FoldedPred &fp : q->sp_pass) any4 |= fp.width == 4;
-                    bool any_s2 = false;
-                    for (int k = 0; k < kMaxTileCols; ++k) any_s2 |= q->alt_kinds[k] == TK_S2;
-                    // Whether they ARE streamed is the cost model's call once the survivors are known (single_pass_stream_columns: the
-                    // sample at creation, a reservation or the first count).  Measured at 100 M rows (one launch / three launches):
-                    // age < 10 -> id, 10 %: 117 / 123 us; 3 %: 107 / 79; 30 %: 204 / 168; 99 %: 534 / 372 -- a window around 10 %.
-                    // Not with a string predicate (the 2-byte match streams at 74 us with the one-launch kernel's 8 streaming waves per
-                    // CU against 47), and not for 1-byte columns alone (their gather reads every line of the column from ~3 % on and
-                    // still costs 33 us at 10 %).
-                    q->alt_ok = any4 && !any_s2;
-                }
-            }
-            // Survivor records pay when the predicate columns' values are wanted: the staging instances of the filter kernel cost
-            // 12 (string) to 33 us (int8) per 100 M rows more than the plain ones, and buy the emit kernel the projected predicate
-            // columns.  When none is projected they buy nothing -- state in (5 values) -> age, 10 %: 120 us with records, 87 without
-            // (filter -> offsets scan -> gather from the bitmap); age in (18, 30) -> id, 11 %: 167 / 122; 3 %: 106 / 79.
-            q->records_narrow_only = n_pred_proj > 0 && !pred_proj_wide;
-            if (q->single_pass || table || (n_gather > 0 && n_pred_proj == 0 && ctx->filter_variant != 11)) { /* no survivor records in HBM */ } else {
-                const int rc = records_setup(q.get());
-                if (rc) return rc;
-            }
-        }
-    }
-    {
-        const int src = single_pass_sample(q.get()); // (the one synchronisation a creation may contain: segments of 4 M rows and more, undecided plans)
-        if (src) return src;
-        // No sample (a segment below 4 M rows -- there the sample costs what it saves): the plans are compared for one survivor in
-        // ten, spread evenly; the first count corrects it.  (At 4 M rows the bitmap path wins nearly every shape: the one launch
-        // starts at ~27 us, three small launches at 16-20.)
-        imm3_query *qq = q.get();
-        if (!qq->plan_have_density && !qq->plan_pinned && !qq->sp_P_fixed && ctx->filter_variant != 10 && qq->plan_shape.n_rows > 0 &&
-            (qq->single_pass || qq->alt_ok || qq->d_stage_rec)) {
-            const uint64_t guess = (uint64_t)(qq->n_rows / 10);
-            const int rc2 = single_pass_stream_columns(qq, guess);
-            if (rc2) return rc2;
-            records_drop_if_narrow(qq, guess);
-            single_pass_drop_if_narrow(qq, guess);
-        }
-    }
+    if (!q->proj.empty() && q->limit > 0) return ensure_row_capacity(q, (uint64_t)std::min<int64_t>(q->limit, std::max<int64_t>(q->n_rows, 1)));
+    return IMM3_OK;
+}
+
+// `row_cols`: the used columns an aggregation reads row by row (place_compressed); empty for a projection.
+static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_table *table,
+                                 const int32_t *used_cols, int32_t n_used,
+                                 const imm3_select *sels, int32_t n_sels,
+                                 const int32_t *proj, int32_t n_proj, int64_t limit,
+                                 int32_t table_block_size, const std::vector<int32_t> &row_cols, imm3_query **out) {
+    if (!seg || !out) return fail(IMM3_ERR_ARG, "null argument");
+    *out = nullptr;
+    CTX_LIVE(ctx); // (the context's gate is held until creation returns)
+    int rc = check_create_args(ctx, seg, table, used_cols, n_used, sels, n_sels, proj, n_proj);
+    if (rc) return rc;
+
+    std::unique_ptr<imm3_query, void (*)(imm3_query *)> q(new imm3_query(), query_free);
+    q->ctx = ctx;
+    ctx_retain(ctx);
+    q->seg = seg;
+    q->table = table;
+    if (table) const_cast<imm3_table *>(table)->refs.fetch_add(1, std::memory_order_relaxed); // (the table holds its segments)
+    else segment_retain(seg);
+    q->table_block_size = table_block_size;
+    q->used.assign(used_cols, used_cols + n_used);
+    q->proj.assign(proj, proj + n_proj);
+    q->limit = limit;
+
+    int32_t nb = 0;
+    rc = scan_layout(q.get(), sels, n_sels, nb); if (rc) return rc;
+    if (nb >= 1) { rc = fold_selects(q.get(), sels, n_sels); if (rc) return rc; }
+    rc = place_compressed(q.get(), nb >= 1, row_cols); if (rc) return rc;
+    rc = upload_match_blobs(q.get()); if (rc) return rc;
+    rc = alloc_buffers(q.get()); if (rc) return rc;
+    rc = plan_projection(q.get()); if (rc) return rc;
     *out = q.release();
     return IMM3_OK;
 }
@@ -1377,7 +1250,7 @@ extern "C" int imm3_query_create(imm3_ctx *ctx, const imm3_segment *seg,
                                  const imm3_select *sels, int32_t n_sels,
                                  const int32_t *proj, int32_t n_proj, int64_t limit,
                                  int32_t table_block_size, imm3_query **out) {
-    return query_create_impl(ctx, seg, nullptr, used_cols, n_used, sels, n_sels, proj, n_proj, limit, table_block_size, out);
+    return query_create_impl(ctx, seg, nullptr, used_cols, n_used, sels, n_sels, proj, n_proj, limit, table_block_size, {}, out);
 }
 
 extern "C" int imm3_query_create_table(imm3_ctx *ctx, const imm3_table *table,
@@ -1386,7 +1259,7 @@ extern "C" int imm3_query_create_table(imm3_ctx *ctx, const imm3_table *table,
                                        const int32_t *proj, int32_t n_proj, int64_t limit,
                                        int32_t table_block_size, imm3_query **out) {
     if (!table || table->segs.empty()) return fail(IMM3_ERR_ARG, "table is null or empty");
-    return query_create_impl(ctx, table->segs[0], table, used_cols, n_used, sels, n_sels, proj, n_proj, limit, table_block_size, out);
+    return query_create_impl(ctx, table->segs[0], table, used_cols, n_used, sels, n_sels, proj, n_proj, limit, table_block_size, {}, out);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1618,7 +1491,7 @@ static int join_total(imm3_query *q, hipStream_t s) {
 // What a caller of run_select wants, OR-ed together; SEL_DEFAULT: store the bitmap, reduce the count on the main stream.
 enum SelectMode : unsigned {
     SEL_DEFAULT = 0,
-    SEL_OVERLAP_TOTAL = 1u << 0, // nothing on the main stream needs the count: reduce it on the aux stream (tuning variant 2)
+    SEL_OVERLAP_TOTAL = 1u << 0, // nothing on the main stream needs the count: reduce it on the aux stream (TV_COUNT_ON_AUX)
     SEL_COUNT_IN_SCAN = 1u << 1, // a projection follows on the same stream; its offsets scan publishes the count (no k_total launch)
     SEL_COUNT_ONLY = 1u << 2,    // the caller wants selected.size alone -- a chain that is ONE tile launch then stores no bitmap
     SEL_WHOLE = 1u << 3,         // never in chunks (the getters' full select)
@@ -1651,36 +1524,10 @@ static int run_select(imm3_query *q, unsigned mode) {
         q->run.ran_single_pass = false;
         return IMM3_OK;
     }
-    // Plan the passes.  Uniform layouts: numeric and 2-byte-string predicates go through the tile kernel, up
-    // to 3 columns (at most one string) per launch; everything else -- other string widths, long IN-lists,
-    // ragged layouts -- through the word-at-a-time kernel, up to 4 columns per launch.  Every pass after the
-    // first ANDs into the bitmap in memory.
-    std::vector<const FoldedPred *> tile_preds, generic_preds, pfor_preds;
-    for (const auto &p : q->preds) {
-        if (p.pfor) pfor_preds.push_back(&p);
-        else if (!q->ragged && ctx->filter_variant != 1 && tile_kind(p) != TK_NONE) tile_preds.push_back(&p);
-        else generic_preds.push_back(&p);
-    }
-    if (q->table && !generic_preds.empty()) return fail(IMM3_ERR_ARG, "table queries support int32 / int8 / 2-byte string predicates (<= 8 IN-list values); use per-segment queries");
-    std::stable_sort(tile_preds.begin(), tile_preds.end(),
-                     [](const FoldedPred *x, const FoldedPred *y) { return tile_kind(*x) < tile_kind(*y); });
-    // Plan the tile passes first: up to 3 columns per launch, numeric kinds first (sorted), at most one 2-byte string
-    // column per launch -- so two string predicates are two passes even when only two columns are filtered.  A query
-    // without predicates is one tile pass with zero columns.
-    std::vector<std::vector<const FoldedPred *>> tile_passes;
-    while (!tile_preds.empty()) {
-        std::vector<const FoldedPred *> take;
-        int n_s2 = 0;
-        for (size_t i = 0; i < tile_preds.size() && take.size() < (size_t)kMaxTileCols; ++i) {
-            const int tk = tile_kind(*tile_preds[i]);
-            if (tk == TK_S2 && n_s2 == 1) continue;
-            take.push_back(tile_preds[i]);
-            n_s2 += tk == TK_S2;
-        }
-        for (const FoldedPred *fp : take) tile_preds.erase(std::find(tile_preds.begin(), tile_preds.end(), fp));
-        tile_passes.push_back(take);
-    }
-    if (q->preds.empty() && !q->ragged && ctx->filter_variant != 1) tile_passes.emplace_back();
+    // (planned on every run: the tuning variant may have changed since creation)
+    const SelectChain chain = plan_select_chain(q);
+    if (q->table && !chain.generic.empty()) return fail(IMM3_ERR_ARG, "table queries support int32 / int8 / 2-byte string predicates (<= 8 IN-list values); use per-segment queries");
+    const int fv = ctx->filter_variant;
     int pass = 0;
     int grid = 1;
     bool count_done = false; // the filter kernel's last work-group has written total / n_emit
@@ -1689,27 +1536,26 @@ static int run_select(imm3_query *q, unsigned mode) {
     q->run.ran_single_pass = false;
     // exactly ONE launch in the whole select chain: only then may that launch publish the count (and append to the count
     // log) itself, and only then are the survivors' values staged
-    const bool single_tile_pass = generic_preds.empty() && pfor_preds.empty() && tile_passes.size() == 1;
-    const bool skip_bitmap = count_only && single_tile_pass && !q->table && !overlap_total && ctx->filter_variant != 7;
+    const bool skip_bitmap = count_only && chain.single_tile_pass && !q->table && !overlap_total && fv != TV_COUNT_BY_K_TOTAL;
     q->run.bitmap_valid = !skip_bitmap;
     // `limit` stops the scan (Project.scala:73-80; Engine.scala:166,253-258: the reference's workers stall on the full queue once the
     // consumer has its rows): a projection with a limit whose select chain is one tile launch over one uniform segment runs that
     // launch as chunks of growing size; every chunk first looks at the rows selected so far (a device word) and leaves at once when
-    // the limit has been reached -- nothing is read, no bitmap line written.  Enqueued blindly: no host wait.  Tuning variant 14: off.
+    // the limit has been reached -- nothing is read, no bitmap line written.  Enqueued blindly: no host wait.  TV_NO_LIMIT_CHUNKS: off.
     LimitScanInputs li;
     li.whole = mode & SEL_WHOLE;
     li.count_log_on = q->count_log_on;
     li.count_in_scan = count_in_scan;
     li.limit = q->limit;
-    li.single_tile_pass = single_tile_pass;
+    li.single_tile_pass = chain.single_tile_pass;
     li.table = q->table != nullptr;
     li.records = q->d_stage_rec != nullptr;
     li.skip_bitmap = skip_bitmap;
     li.overlap_total = overlap_total;
-    li.filter_variant = ctx->filter_variant;
+    li.filter_variant = fv;
     li.n_tiles = q->n_tiles;
     const bool chunked = limit_scan_applies(li);
-    for (const auto &take : tile_passes) {
+    for (const auto &take : chain.tile_passes) {
         TileArgs a;
         std::memset(&a, 0, sizeof(a));
         const int n = (int)take.size();
@@ -1720,7 +1566,7 @@ static int run_select(imm3_query *q, unsigned mode) {
             a.kinds[k] = tile_kind(fp);
             fill_tile_col(q, fp, a.cols[k], a.kinds[k]);
         }
-        if (single_tile_pass && q->d_stage_rec && !skip_bitmap && !(mode & SEL_PLAIN)) { // the columns are in the order the records were laid out for (same sort)
+        if (chain.single_tile_pass && q->d_stage_rec && !skip_bitmap && !(mode & SEL_PLAIN)) { // the columns are in the order the records were laid out for (same sort)
             bool same = true;
             for (int k = 0; k < kMaxTileCols; ++k) same = same && a.kinds[k] == q->stage_kinds[k] && (k >= n || take[(size_t)k]->seg_col == q->stage_seg_col[k]);
             if (!same) return fail(IMM3_ERR_ARG, "internal: staged record layout does not match the tile launch");
@@ -1730,7 +1576,7 @@ static int run_select(imm3_query *q, unsigned mode) {
             a.max_slots = q->stage_max_slots;
             q->run.stage_written = true;
         }
-        a.ablate = (ctx->filter_variant >= 20 && ctx->filter_variant <= 22) ? ctx->filter_variant.load() : 0; // (tools' build only)
+        a.ablate = tile_ablation(fv); // (tools' build only)
         a.and_existing = pass > 0;
         a.n_rows = q->n_rows;
         a.n_words = q->n_words;
@@ -1738,8 +1584,8 @@ static int run_select(imm3_query *q, unsigned mode) {
         a.bitmap = q->d_bitmap;
         // A records run whose offsets scan follows (imm3_query_run of a projection) stores NO bitmap: the records carry the positions
         // and the scan takes the tiles' counts from the arenas (round 5: 12.5 MB of 128-byte line stores in between the streaming
-        // loads, and 12.5 MB read back by k_scan -- C4 107 -> 100 us).  imm3_query_bitmap materialises it on demand.  Tuning 19: off.
-        q->run.bitmap_lazy = q->run.stage_written && count_in_scan && !q->count_log_on && ctx->filter_variant != 19;
+        // loads, and 12.5 MB read back by k_scan -- C4 107 -> 100 us).  imm3_query_bitmap materialises it on demand.  TV_EAGER_BITMAP: off.
+        q->run.bitmap_lazy = q->run.stage_written && count_in_scan && !q->count_log_on && fv != TV_EAGER_BITMAP;
         if (q->run.bitmap_lazy) {
             a.bitmap = nullptr;
             q->run.bitmap_valid = false;
@@ -1756,16 +1602,16 @@ static int run_select(imm3_query *q, unsigned mode) {
         grid = filter_grid(q->n_tiles, false, any_i32, ctx->grid_blocks, narrow_bytes); // (no column at all: the store-only kernel also likes 1536 groups, 9.9 vs 17.2 us)
         if (q->run.stage_written) grid = q->stage_grid; // fixed at creation: the arena layout depends on it
         // A select chain that is ONE tile pass also reduces its count in the kernel (one relaxed atomic per work-group into a
-        // two-level tally, finish_add): no k_total launch.  Variant 7 = never; variant 13 = only at <= 512 work-groups (what
+        // two-level tally, finish_add): no k_total launch.  TV_COUNT_BY_K_TOTAL = never; TV_COUNT_SMALL_GRID = only at <= 512 work-groups (what
         // round 1 did: with a single tally the 1536 atomics of a narrow-column launch cost more than the launch they saved).
-        if (single_tile_pass && !overlap_total && ctx->filter_variant != 7 && (grid <= 512 || ctx->filter_variant != 13)) {
+        if (chain.single_tile_pass && !overlap_total && fv != TV_COUNT_BY_K_TOTAL && (grid <= 512 || fv != TV_COUNT_SMALL_GRID)) {
             a.finish = q->d_total;
             count_done = true;
         }
         // bitmap lines parked in LDS and stored in bursts: no staging (whose LDS and 2048 work-groups
-        // leave no room for 32 KiB more per group); tuning variant 12 switches it off
+        // leave no room for 32 KiB more per group); TV_PLAN_PINNED switches it off
         // (64 lines = 32 KiB per work-group at <= 4 groups per CU; 16 lines = 8 KiB for the 1536-group narrow-column kernels)
-        a.defer_lines = (ctx->filter_variant == 12 || q->run.bitmap_lazy) ? 0 : (q->run.stage_written ? 16 : (grid <= 1024 ? kDeferLines : 16)); // (no bitmap, no lines to park)
+        a.defer_lines = (fv == TV_PLAN_PINNED || q->run.bitmap_lazy) ? 0 : (q->run.stage_written ? 16 : (grid <= 1024 ? kDeferLines : 16)); // (no bitmap, no lines to park)
         if (skip_bitmap) { // count-only: the kernel instance that stores nothing (the count is reduced in the kernel)
             a.bitmap = nullptr;
             a.defer_lines = 0;
@@ -1797,7 +1643,7 @@ static int run_select(imm3_query *q, unsigned mode) {
                 c.chunked = tile0 == 0 ? 2 : 1; // (the first chunk starts the running words over)
                 c.stamps = nullptr;
                 const int cgrid = filter_grid(c.n_tiles, false, any_i32, ctx->grid_blocks, narrow_bytes);
-                c.defer_lines = ctx->filter_variant == 12 ? 0 : (cgrid <= 1024 ? kDeferLines : 16);
+                c.defer_lines = fv == TV_PLAN_PINNED ? 0 : (cgrid <= 1024 ? kDeferLines : 16);
                 LaunchTimer t(ctx, 0);
                 if (!launch_filter_tile(c, cgrid, s, t.start, t.stop)) return fail(IMM3_ERR_ARG, "internal: no tile kernel for this column combination");
                 HIPCHK(hipGetLastError());
@@ -1815,8 +1661,8 @@ static int run_select(imm3_query *q, unsigned mode) {
         ++pass;
     }
     // PFOR_INT passes: one compressed column per launch, decoded in LDS and compared in registers
-    q->run.has_pfor_pass = !pfor_preds.empty();
-    for (const FoldedPred *fp : pfor_preds) {
+    q->run.has_pfor_pass = !chain.pfor.empty();
+    for (const FoldedPred *fp : chain.pfor) {
         const SegCol &sc = q->seg->cols[(size_t)fp->seg_col];
         PforArgs a;
         std::memset(&a, 0, sizeof(a));
@@ -1845,11 +1691,11 @@ static int run_select(imm3_query *q, unsigned mode) {
     // generic passes
     size_t gi = 0;
     const bool need_empty_generic = q->preds.empty() && pass == 0;
-    while (gi < generic_preds.size() || (need_empty_generic && pass == 0)) {
+    while (gi < chain.generic.size() || (need_empty_generic && pass == 0)) {
         FilterArgs a;
         std::memset(&a, 0, sizeof(a));
-        const size_t take = std::min<size_t>(kMaxPredCols, generic_preds.size() - gi);
-        for (size_t i = 0; i < take; ++i) fill_colpred(q, *generic_preds[gi + i], a.cols[i]);
+        const size_t take = std::min<size_t>(kMaxPredCols, chain.generic.size() - gi);
+        for (size_t i = 0; i < take; ++i) fill_colpred(q, *chain.generic[gi + i], a.cols[i]);
         a.ncols = (int32_t)take;
         a.and_existing = pass > 0;
         a.n_rows = q->n_rows;
@@ -1908,6 +1754,7 @@ static int run_select(imm3_query *q, unsigned mode) {
 }
 
 // the SELECT-list columns as the unpacking kernels take them: gathered columns first, then the ones the record carries
+// (every mention of a staged column reads the record; the plan counts only the first as riding in it: proj_rides_in_records)
 static int fill_emit_cols(const imm3_query *q, EmitCol *out, int &n_out) {
     std::vector<EmitCol> gathered, staged;
     for (size_t j = 0; j < q->proj.size(); ++j) {
@@ -2064,8 +1911,7 @@ static int run_single_pass(imm3_query *q) {
         }
         a.n_gather = ng;
     }
-    const int fv = ctx->filter_variant;
-    a.ablate = (fv >= 50 && fv <= 50 + 255) ? fv - 50 : 0; // (tools' build only: a mask -- 1 no unpack, 2 no chained scan, 4 no records, 16 no output stores, 32 plain instead of non-temporal stores in the straight copy of fully surviving dense ranges)
+    a.ablate = project_ablation(ctx->filter_variant); // (tools' build only: a mask -- 1 no unpack, 2 no chained scan, 4 no records, 16 no output stores, 32 plain instead of non-temporal stores in the straight copy of fully surviving dense ranges)
     a.max_polls = ctx->fault_max_polls; // (tools' build only: imm3_ctx_inject_fault)
     a.fault_wg = ctx->fault_wg;
     a.fault_span = ctx->fault_span;
@@ -2119,7 +1965,7 @@ static int launch_emit_records(imm3_query *q) {
     e.main_tiles = q->stage_main_tiles;
     e.max_slots = q->stage_max_slots;
     e.T = q->stage_T;
-    e.ablate = (ctx->filter_variant >= 34 && ctx->filter_variant <= 35) ? ctx->filter_variant.load() : 0; // (tools' build only)
+    e.ablate = emit_ablation(ctx->filter_variant); // (tools' build only)
     e.tile_offsets = q->d_tile_offsets;
     e.chunk_sums = q->d_chunk_sums;
     e.n_tiles = q->n_tiles;
@@ -2178,10 +2024,10 @@ static int launch_project(imm3_query *q) {
 }
 
 // A small limit behind a limit scan: the offsets scan and the gather in ONE launch over the scanned tiles (k_limit_gather).
-// `select id ... limit 10`: 7 + 9 us of k_scan + k_gather -> ~5.  Tuning variant 15: off.
+// `select id ... limit 10`: 7 + 9 us of k_scan + k_gather -> ~5.  TV_LIMIT_NO_FUSED_GATHER: off.
 constexpr int kLimitGatherGrid = 256;
 static bool limit_gather_applies(const imm3_query *q) {
-    if (!q->run.select_partial || !(q->limit > 0) || q->limit > kLimitGatherMaxRows || q->table || q->d_word_row_base || q->run.stage_written || q->ctx->filter_variant == 15) return false;
+    if (!q->run.select_partial || !(q->limit > 0) || q->limit > kLimitGatherMaxRows || q->table || q->d_word_row_base || q->run.stage_written || q->ctx->filter_variant == TV_LIMIT_NO_FUSED_GATHER) return false;
     if (q->n_chunks > (int64_t)kLimitGatherGrid * kLimitGatherMaxChunks || q->proj.size() > (size_t)kMaxProj || !q->d_limit_state) return false;
     for (int32_t pj : q->proj) {
         const SegCol &sc = q->seg->cols[(size_t)q->used[(size_t)pj]];
@@ -2323,7 +2169,7 @@ static bool agg_run_fuses(const imm3_query *q);
 static int capture_admit(imm3_query *q) {
     imm3_ctx *ctx = q->ctx;
     if (!ctx->capture) return IMM3_OK;
-    if (ctx->filter_variant == 2) return fail(IMM3_ERR_STATE, "tuning variant 2 (count reduce on the aux stream) cannot be captured");
+    if (ctx->filter_variant == TV_COUNT_ON_AUX) return fail(IMM3_ERR_STATE, "tuning variant 2 (count reduce on the aux stream) cannot be captured");
     const bool sp = q->single_pass && !q->proj.empty() && !q->always_false && q->n_tiles > 0; // (writes its rows without knowing the count)
     if (!q->proj.empty() && !(q->limit > 0) && !q->reserved && !sp && !q->d_row_index)
         return fail(IMM3_ERR_STATE, "an unlimited projection sizes its output from the count on its first run (a synchronisation): run it once, or call imm3_query_reserve_rows, before capturing it");
@@ -2361,7 +2207,7 @@ static int run_entry(imm3_query *q, int (*plan)(imm3_query *)) {
 }
 
 extern "C" int imm3_query_run_select(imm3_query *q) {
-    return run_entry(q, [](imm3_query *r) { return run_select(r, r->ctx->filter_variant == 2 ? SEL_OVERLAP_TOTAL : SEL_DEFAULT); });
+    return run_entry(q, [](imm3_query *r) { return run_select(r, r->ctx->filter_variant == TV_COUNT_ON_AUX ? SEL_OVERLAP_TOTAL : SEL_DEFAULT); });
 }
 
 extern "C" int imm3_query_run_count(imm3_query *q) {
@@ -2376,7 +2222,7 @@ extern "C" int imm3_query_join_count(imm3_query *q) {
 }
 
 static int run_query(imm3_query *q) {
-    // Reducing the count on the aux stream (tuning variant 2) measured SLOWER on MI355X / ROCm 7.2 (75.6 vs 67.1 us
+    // Reducing the count on the aux stream (TV_COUNT_ON_AUX) measured SLOWER on MI355X / ROCm 7.2 (75.6 vs 67.1 us
     // per step: the cross-queue event packets cost more than the two same-queue launch gaps they remove), so the
     // default keeps the reduce on the main stream.
     if (q->sp_restore_pending && !q->ctx->capture) {
@@ -2384,8 +2230,8 @@ static int run_query(imm3_query *q) {
         if (rrc) return rrc;
     }
     if (q->single_pass && !q->proj.empty() && !q->always_false && q->n_tiles > 0) return run_single_pass(q);
-    const bool select_only = q->proj.empty() && !q->is_agg && q->ctx->filter_variant == 2;
-    const bool count_in_scan = !q->proj.empty() && q->n_tiles > 0 && !q->always_false && q->ctx->filter_variant != 7;
+    const bool select_only = q->proj.empty() && !q->is_agg && q->ctx->filter_variant == TV_COUNT_ON_AUX;
+    const bool count_in_scan = !q->proj.empty() && q->n_tiles > 0 && !q->always_false && q->ctx->filter_variant != TV_COUNT_BY_K_TOTAL;
     int rc = IMM3_OK;
     q->run.agg_select_skipped = agg_run_fuses(q);
     if (q->run.agg_select_skipped) q->run.ran_select = true; // (bitmap and count on demand: settle_agg_select)
@@ -2705,7 +2551,9 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
     if (n_group < 0 || n_group > kMaxGroupCols || (n_group > 0 && !group_cols)) return fail(IMM3_ERR_ARG, "0..4 group columns are supported on the GPU path");
     if (n_aggs < 1 || n_aggs > kMaxAggs || !aggs) return fail(IMM3_ERR_ARG, "1..4 aggregates are supported on the GPU path");
     imm3_query *q = nullptr;
-    int rc = query_create_impl(ctx, seg, table, used_cols, n_used, sels, n_sels, nullptr, 0, 0, table_block_size, &q);
+    std::vector<int32_t> row_cols(group_cols, group_cols + n_group); // read row by row: PFOR_INT ones through their decoded form
+    for (int32_t j = 0; j < n_aggs; ++j) row_cols.push_back(aggs[j].column);
+    int rc = query_create_impl(ctx, seg, table, used_cols, n_used, sels, n_sels, nullptr, 0, 0, table_block_size, row_cols, &q);
     if (rc) return rc;
     std::unique_ptr<imm3_query, void (*)(imm3_query *)> guard(q, query_free);
     int key_bytes = 0;
@@ -2723,18 +2571,6 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
         // ProjectAggregate.scala:176-220: a String vector only takes CountAggr / MaxStringAggr
         if (has_batches && is_str && aggs[j].kind == IMM3_AGG_MIN) return fail(IMM3_ERR_UNSUPPORTED_VECTOR, "bad aggregator for this data type");
         if (is_str && aggs[j].kind == IMM3_AGG_MAX && sc.width > 8) return fail(IMM3_ERR_ARG, "MAX over strings wider than 8 bytes is not supported on the GPU path");
-    }
-    // group / aggregate columns are read row by row: PFOR_INT ones through their decoded form
-    if (!table) {
-        auto need_dense = [&](int32_t used_idx) -> int {
-            const int32_t sci = q->used[(size_t)used_idx];
-            if (!is_compressed(seg->cols[(size_t)sci].codec)) return IMM3_OK;
-            for (auto &fp : q->preds)
-                if (fp.seg_col == sci) fp.pfor = false;
-            return ensure_dense(ctx, seg, sci);
-        };
-        for (int32_t g = 0; g < n_group; ++g) { rc = need_dense(group_cols[g]); if (rc) return rc; }
-        for (int32_t j = 0; j < n_aggs; ++j) { rc = need_dense(aggs[j].column); if (rc) return rc; }
     }
     q->is_agg = true;
     q->group_cols.assign(group_cols, group_cols + n_group);
@@ -2810,7 +2646,7 @@ static void fill_agg_args(const imm3_query *q, AggArgs &a) {
         a.aggs[j].is_str = sc.vcodec == IMM3_DENSE_STRING;
     }
     a.n_agg = (int32_t)q->aggs.size();
-    if (q->agg_fusable && q->ctx->filter_variant != 17) { // (tuning 17: filter launch + aggregation launch, as before round 5)
+    if (q->agg_fusable && q->ctx->filter_variant != TV_AGG_SELECT_LAUNCH) { // (filter launch + aggregation launch, as before round 5)
         int first_value = -1; // the aggregate whose rows the lanes form keeps in registers: the first one that is not a count
         for (size_t j = 0; j < q->aggs.size() && first_value < 0; ++j)
             if (q->aggs[j].kind != IMM3_AGG_COUNT) first_value = (int)j;
@@ -2841,10 +2677,10 @@ static void fill_agg_args(const imm3_query *q, AggArgs &a) {
 
 static void agg_launch_args(const imm3_query *q, AggArgs &a) {
     fill_agg_args(q, a);
-    // tuning variants 100 + AggForm start the chain at that form (tools/aggexp.py); 140 + x: ablation x of the tools' build
+    // (tools/aggexp.py: TV_AGG_FORM + form starts the chain at that form)
     const int fv = q->ctx->filter_variant;
-    a.first_form = (fv >= 100 && fv <= 100 + AGG_FORM_GENERAL) ? fv - 100 : q->agg_first_form; // (agg_first_form: past the forms this query's keys overflowed)
-    a.ablate = fv >= 140 ? fv - 100 : 0;
+    a.first_form = agg_form_variant(fv) >= 0 ? agg_form_variant(fv) : q->agg_first_form; // (agg_first_form: past the forms this query's keys overflowed)
+    a.ablate = agg_ablation(fv);
 }
 // will this run's aggregation launch evaluate the select chain itself?  (then no select launch precedes it)
 static bool agg_run_fuses(const imm3_query *q) {

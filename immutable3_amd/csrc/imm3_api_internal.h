@@ -33,7 +33,17 @@ int records_setup(imm3_query *q);
 void single_pass_drop_if_narrow(imm3_query *q, uint64_t survivors);
 bool single_pass_restore_wanted(const imm3_query *q, uint64_t survivors);
 int single_pass_restore(imm3_query *q, uint64_t survivors);
-int single_pass_sample(imm3_query *q);
+
+// The select chain's passes as run_select enqueues them, from the query's folded predicates and the tuning variant read NOW: tile passes
+// of up to kMaxTileCols columns (numeric kinds first, at most one 2-byte string each; a query without predicates is one tile pass
+// with zero columns), then one k_filter_pfor pass per fused PFOR_INT predicate, then the word-at-a-time passes.
+struct SelectChain {
+    std::vector<std::vector<const FoldedPred *>> tile_passes;
+    std::vector<const FoldedPred *> pfor, generic;
+    bool single_tile_pass = false; // exactly ONE launch in the whole chain: its column order is the records' and the one launch's
+};
+SelectChain plan_select_chain(const imm3_query *q);
+int plan_projection(imm3_query *q); // query creation: the projection's plan (records, one launch, streamed alternative), then the sample
 
 struct LimitScanInputs {
     bool whole = false, count_log_on = false, count_in_scan = false, single_tile_pass = false, table = false, records = false, skip_bitmap = false, overlap_total = false;

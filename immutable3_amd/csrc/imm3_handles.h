@@ -49,6 +49,45 @@ struct HipBlockBackend {
     static int alloc(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
     static void free(void *p) { (void)hipFree(p); }
 };
+namespace imm3 {
+// Tuning variants (imm3_ctx_set_tuning, include/imm3_diag.h): each pins one decision for A/B runs and tests.  The numbers are the
+// interface -- tests and tools/ pass them as integers.  Read where the decision is made (creation or run), so a query created under
+// one variant may run under another.
+enum TuningVariant : int {
+    TV_DEFAULT = 0,
+    TV_GENERIC_ONLY = 1,        // every predicate through the word-at-a-time kernel: no tile launch, no PFOR_INT pass, no records / one launch
+    TV_COUNT_ON_AUX = 2,        // select-only runs reduce the count on the aux stream (cannot be captured)
+    TV_NO_RECORDS = 3,          // no survivor records and no one launch at creation, and the cost model never picks either
+    TV_PFOR_DECODED = 5,        // PFOR_INT predicates read the decoded column instead of the compressed blocks
+    TV_NO_ONE_LAUNCH = 6,       // projections never take the one launch (nor streamed columns); the cost model keeps survivor records
+    TV_COUNT_BY_K_TOTAL = 7,    // the count by a k_total launch: none in the filter kernel or the offsets scan, no count-only instance, no limit chunks
+    TV_ONE_LAUNCH_GATHERS = 8,  // the one launch with gathered SELECT-list columns too, and the cost model never leaves it
+    TV_STREAM_ALWAYS = 9,       // gathered int32 columns streamed through the one launch whatever the prediction
+    TV_NO_SAMPLE = 10,          // no sample and no guess at creation: the plan adapts from the first run's count on
+    TV_RECORDS_ALWAYS = 11,     // survivor records even when no predicate column is projected; the cost model drops neither them nor the one launch
+    TV_PLAN_PINNED = 12,        // the plan made at creation stands whatever the cost model says (P still adapts); also: no bitmap lines parked in LDS
+    TV_COUNT_SMALL_GRID = 13,   // a one-launch select chain reduces its count in the kernel only at <= 512 work-groups
+    TV_NO_LIMIT_CHUNKS = 14,    // a `limit` query scans the whole segment in one launch
+    TV_LIMIT_NO_FUSED_GATHER = 15, // a small limit takes k_scan + k_gather instead of k_limit_gather
+    TV_NO_CU_RESERVATION = 16,  // one-launch projections use every CU while a communicator is attached
+    TV_AGG_SELECT_LAUNCH = 17,  // an aggregation's select chain runs as its own launch, not inside the aggregation launch
+    TV_EAGER_BITMAP = 19,       // a projection through survivor records stores its bitmap in the staging launch
+    TV_TILE_ABLATION = 20,      // 20 .. 22: k_filter_tile's ablation switches (tools' build only)
+    TV_EMIT_ABLATION = 34,      // 34 .. 35: k_emit's ablation switches (tools' build only)
+    TV_PROJECT_ABLATION = 50,   // 50 + mask (mask <= 255): k_filter_project's ablation mask (tools' build only)
+    TV_AGG_FORM = 100,          // 100 + AggForm: the aggregation's form chain starts at that form
+    TV_AGG_ABLATION = 140,      // 140 and above: ablation (variant - 100) of the aggregation kernels (tools' build only)
+    TV_FIXED_P = 200,           // 200 + P (1 <= P <= kProjectMaxP): the one launch takes P tiles per range, never adapted
+};
+// the ranges: what the variant passes on to a launch or the planner (0, or -1 for the form, when the variant is not in the range)
+inline int tile_ablation(int v) { return v >= TV_TILE_ABLATION && v <= TV_TILE_ABLATION + 2 ? v : 0; }
+inline int emit_ablation(int v) { return v >= TV_EMIT_ABLATION && v <= TV_EMIT_ABLATION + 1 ? v : 0; }
+inline int project_ablation(int v) { return v >= TV_PROJECT_ABLATION && v <= TV_PROJECT_ABLATION + 255 ? v - TV_PROJECT_ABLATION : 0; }
+inline int agg_form_variant(int v) { return v >= TV_AGG_FORM && v <= TV_AGG_FORM + AGG_FORM_GENERAL ? v - TV_AGG_FORM : -1; }
+inline int agg_ablation(int v) { return v >= TV_AGG_ABLATION ? v - TV_AGG_FORM : 0; }
+inline int fixed_P(int v) { return v > TV_FIXED_P && v <= TV_FIXED_P + kProjectMaxP ? v - TV_FIXED_P : 0; }
+} // namespace imm3
+
 // Threading: see imm3_sync.h.  A context may be used by any number of threads at once; `gate` serialises a graph capture
 // against the other threads' calls, `mu` guards the small mutable state below, the buffer pool has its own lock.
 struct imm3_ctx {
@@ -62,7 +101,7 @@ struct imm3_ctx {
     hipStream_t aux = nullptr;      // count reduce of select-only runs: overlaps the next scan on `stream`
     hipStream_t copy = nullptr;     // host -> HBM staging of segments: never on the query stream, so staging overlaps queries
     std::map<void *, int> pinned;   // host ranges pinned in place for asynchronous staging, by start address, with a use count
-    std::atomic<int> filter_variant{0};
+    std::atomic<int> filter_variant{0}; // imm3::TuningVariant
     std::atomic<int> grid_blocks{0};
     std::atomic<bool> timing{false};
     std::atomic<uint32_t> timing_mask{0xFFFFFFFFu};
@@ -204,6 +243,23 @@ struct FoldedPred { // all SelectOp leaves on one segment column, folded
     uint8_t *d_blob = nullptr;             // device copy when it does not fit the kernel arguments
     bool pfor = false;                     // PFOR_INT column evaluated on its compressed blocks (k_filter_pfor)
 };
+// The predicate no leaf has narrowed yet, for a column of DENSE_* codec `codec`: an int32 / int8 interval every value passes; a
+// string's IN-list is the first leaf's.
+static inline FoldedPred unfolded_pred(int32_t seg_col, int32_t codec, int32_t width) {
+    FoldedPred fp;
+    fp.seg_col = seg_col;
+    fp.width = width;
+    if (codec == IMM3_DENSE_INT) { fp.kind = imm3::KIND_I32; fp.lo = INT32_MIN; fp.hi = INT32_MAX; }
+    else if (codec == IMM3_DENSE_TINYINT) { fp.kind = imm3::KIND_I8; fp.lo = -128; fp.hi = 127; }
+    else fp.kind = imm3::KIND_STR;
+    return fp;
+}
+// the folded predicate on segment column `sci` (at most one per column), or null
+static inline FoldedPred *pred_on(std::vector<FoldedPred> &preds, int32_t sci) {
+    for (auto &p : preds)
+        if (p.seg_col == sci) return &p;
+    return nullptr;
+}
 
 struct imm3_query {
     imm3_ctx *ctx = nullptr;

@@ -5,7 +5,8 @@
 //   * the cost model's decisions between the one launch, survivor records and the bitmap path (imm3_plan.h) on an estimate --
 //     the sample at creation, a reservation -- or on a run's count (single_pass_stream_columns, records_drop_if_narrow,
 //     single_pass_drop_if_narrow, single_pass_restore);
-//   * whether a projection with a `limit` scans in chunks (limit_scan_applies).
+//   * whether a projection with a `limit` scans in chunks (limit_scan_applies);
+//   * the select chain's passes (plan_select_chain) and the plan query creation makes for a projection (plan_projection).
 // The reference has no planner to mirror: its Engine builds ScanOp -> SelectOp* -> ProjectOp per segment unconditionally
 // (engine/src/main/scala/immutabledb/engine/Engine.scala:158-196); these are choices between equivalent executions of that chain.
 #include "../../include/imm3.h"
@@ -33,7 +34,7 @@ namespace imm3 {
 bool limit_scan_applies(const LimitScanInputs &in) {
     if (in.whole || in.count_log_on || !in.count_in_scan || !(in.limit > 0) || !in.single_tile_pass) return false;
     if (in.table || in.records || in.skip_bitmap || in.overlap_total) return false;
-    if (in.filter_variant == 7 || in.filter_variant == 14) return false;
+    if (in.filter_variant == TV_COUNT_BY_K_TOTAL || in.filter_variant == TV_NO_LIMIT_CHUNKS) return false;
     return in.n_tiles > kLimitFirstChunkTiles;
 }
 
@@ -42,6 +43,39 @@ int tile_kind(const FoldedPred &fp) {
     if (fp.kind == KIND_I8) return TK_I8;
     if (fp.kind == KIND_STR && fp.width == 2 && !fp.match.empty() && fp.match.size() <= (size_t)kMaxTileMatch) return TK_S2;
     return TK_NONE;
+}
+
+SelectChain plan_select_chain(const imm3_query *q) {
+    // Uniform layouts: numeric and 2-byte-string predicates go through the tile kernel; everything else -- other string widths, long
+    // IN-lists, ragged layouts -- through the word-at-a-time kernel, up to 4 columns per launch.  Every pass after the first ANDs
+    // into the bitmap in memory.
+    const bool tiles = !q->ragged && q->ctx->filter_variant != TV_GENERIC_ONLY;
+    SelectChain c;
+    std::vector<const FoldedPred *> tile_preds;
+    for (const auto &p : q->preds) {
+        if (p.pfor) c.pfor.push_back(&p);
+        else if (tiles && tile_kind(p) != TK_NONE) tile_preds.push_back(&p);
+        else c.generic.push_back(&p);
+    }
+    std::stable_sort(tile_preds.begin(), tile_preds.end(),
+                     [](const FoldedPred *x, const FoldedPred *y) { return tile_kind(*x) < tile_kind(*y); });
+    // up to 3 columns per launch, numeric kinds first (sorted), at most one 2-byte string column per launch -- so two string
+    // predicates are two passes even when only two columns are filtered
+    while (!tile_preds.empty()) {
+        std::vector<const FoldedPred *> take;
+        int n_s2 = 0;
+        for (size_t i = 0; i < tile_preds.size() && take.size() < (size_t)kMaxTileCols; ++i) {
+            const int tk = tile_kind(*tile_preds[i]);
+            if (tk == TK_S2 && n_s2 == 1) continue;
+            take.push_back(tile_preds[i]);
+            n_s2 += tk == TK_S2;
+        }
+        for (const FoldedPred *fp : take) tile_preds.erase(std::find(tile_preds.begin(), tile_preds.end(), fp));
+        c.tile_passes.push_back(take);
+    }
+    if (q->preds.empty() && tiles) c.tile_passes.emplace_back();
+    c.single_tile_pass = c.generic.empty() && c.pfor.empty() && c.tile_passes.size() == 1;
+    return c;
 }
 
 // ---- single-pass projection: tiles per wave and span (P) ----
@@ -56,7 +90,7 @@ int tile_kind(const FoldedPred &fp) {
 constexpr int kXcds = 8;
 constexpr int kCommReservedCUs = kXcds;
 bool single_pass_reserves(const imm3_query *q) {
-    return q->ctx->comms_attached.load(std::memory_order_relaxed) > 0 && q->ctx->filter_variant != 16 && q->sp_max_grid > 4 * kCommReservedCUs; // (tuning 16: no reservation, for A/B runs)
+    return q->ctx->comms_attached.load(std::memory_order_relaxed) > 0 && q->ctx->filter_variant != TV_NO_CU_RESERVATION && q->sp_max_grid > 4 * kCommReservedCUs;
 }
 int32_t single_pass_run_grid(const imm3_query *q) {
     const int64_t g = single_pass_reserves(q) ? q->sp_max_grid - kCommReservedCUs : q->sp_max_grid;
@@ -148,8 +182,8 @@ int single_pass_setup(imm3_query *q) {
     };
     int64_t P = plan_P(maxg);
     const int64_t P_reserved = plan_P(maxg > 4 * kCommReservedCUs ? maxg - kCommReservedCUs : maxg);
-    const bool fixed = ctx->filter_variant > 200 && ctx->filter_variant <= 200 + kProjectMaxP;
-    if (fixed) P = ctx->filter_variant - 200; // tuning: variant 200 + P
+    const bool fixed = fixed_P(ctx->filter_variant) > 0;
+    if (fixed) P = fixed_P(ctx->filter_variant);
     if (maxg < 1 || q->n_tiles < 1) return IMM3_OK;
     // One allocation: round totals and round counters first (at the same place whatever P a run uses), then the span
     // descriptors of the smallest P a run may use, then one 64-byte trash line per writer wave.  The plan is committed only
@@ -223,6 +257,16 @@ double plan_cost_three_launches(const imm3_query *q, const PlanDensity &d, bool 
     return std::min(b, c);
 }
 
+// The survivor records' buffers go back to the pool (a graph that recorded a run on them is stale now).
+static void records_release(imm3_query *q) {
+    graphs_mark_stale(q->ctx, q);
+    pool_release(q->ctx, q->d_stage_rec);
+    pool_release(q->ctx, q->d_tile_start);
+    q->d_stage_rec = nullptr;
+    q->d_tile_start = nullptr;
+    q->run.stage_written = false;
+}
+
 // A projection with gathered SELECT-list columns was planned as three launches (records -> k_scan -> k_emit).  Now the host
 // knows how many rows survive: when that is enough for a gather to touch most 128-byte lines of the column anyway, the
 // column is STREAMED instead -- it joins the one-launch kernel as a tile column whose predicate every value passes, and its
@@ -232,7 +276,7 @@ double plan_cost_three_launches(const imm3_query *q, const PlanDensity &d, bool 
 int single_pass_stream_columns(imm3_query *q, uint64_t survivors) {
     imm3_ctx *ctx = q->ctx;
     if (!q->alt_ok || q->single_pass || ctx->capture || q->n_rows <= 0) return IMM3_OK;
-    if (ctx->filter_variant != 9) { // (9: streamed whatever the prediction)
+    if (ctx->filter_variant != TV_STREAM_ALWAYS) {
         if (q->plan_pinned) return IMM3_OK;
         const PlanDensity d = plan_density_for(q, survivors);
         const double now = q->d_stage_rec ? std::min(plan_cost('B', q->plan_shape, d), plan_cost('C', q->plan_shape, d)) : plan_cost('C', q->plan_shape, d);
@@ -254,12 +298,7 @@ int single_pass_stream_columns(imm3_query *q, uint64_t survivors) {
         q->alt_ok = false;
         return rc;
     }
-    graphs_mark_stale(ctx, q); // (a graph that recorded the three launches points at buffers that go now)
-    pool_release(ctx, q->d_stage_rec);
-    pool_release(ctx, q->d_tile_start);
-    q->d_stage_rec = nullptr;
-    q->d_tile_start = nullptr;
-    q->run.stage_written = false;
+    records_release(q);
     q->alt_ok = false;
     single_pass_adapt(q, survivors, -1);
     return IMM3_OK;
@@ -271,15 +310,11 @@ int single_pass_stream_columns(imm3_query *q, uint64_t survivors) {
 // values) -> id, state, age: 277 / 243).  The records' buffers go back to the pool.
 void records_drop_if_narrow(imm3_query *q, uint64_t survivors) {
     imm3_ctx *ctx = q->ctx;
-    if (q->single_pass || !q->d_stage_rec || q->plan_pinned || ctx->capture || ctx->filter_variant == 11 || ctx->filter_variant == 6 || q->n_rows <= 0) return;
+    if (q->single_pass || !q->d_stage_rec || q->plan_pinned || ctx->capture || ctx->filter_variant == TV_RECORDS_ALWAYS ||
+        ctx->filter_variant == TV_NO_ONE_LAUNCH || q->n_rows <= 0) return;
     const PlanDensity d = plan_density_for(q, survivors);
     if (!(plan_cost('C', q->plan_shape, d) < kPlanKeepMargin * plan_cost('B', q->plan_shape, d))) return;
-    graphs_mark_stale(ctx, q);
-    pool_release(ctx, q->d_stage_rec);
-    pool_release(ctx, q->d_tile_start);
-    q->d_stage_rec = nullptr;
-    q->d_tile_start = nullptr;
-    q->run.stage_written = false;
+    records_release(q);
     q->alt_ok = false; // (settled: three launches from the bitmap)
 }
 
@@ -324,10 +359,11 @@ int records_setup(imm3_query *q) {
 // gathered (state = CA -> state, 2 %: 62 us with records, 75 from the bitmap): the cheaper of the two is taken.
 void single_pass_drop_if_narrow(imm3_query *q, uint64_t survivors) {
     imm3_ctx *ctx = q->ctx;
-    if (!q->single_pass || !q->sp_pass.empty() || q->sp_P_fixed || q->plan_pinned || ctx->capture || ctx->filter_variant == 8 || ctx->filter_variant == 11 || q->n_rows <= 0) return;
+    if (!q->single_pass || !q->sp_pass.empty() || q->sp_P_fixed || q->plan_pinned || ctx->capture || ctx->filter_variant == TV_ONE_LAUNCH_GATHERS ||
+        ctx->filter_variant == TV_RECORDS_ALWAYS || q->n_rows <= 0) return;
     const PlanDensity d = plan_density_for(q, survivors);
     bool use_records = false;
-    const double other = plan_cost_three_launches(q, d, ctx->filter_variant != 3 && !q->table, &use_records); // (a table has no survivor records: the bitmap path)
+    const double other = plan_cost_three_launches(q, d, ctx->filter_variant != TV_NO_RECORDS && !q->table, &use_records); // (a table has no survivor records: the bitmap path)
     if (!(other < kPlanKeepMargin * plan_cost('A', q->plan_shape, d))) return;
     graphs_mark_stale(ctx, q);
     q->single_pass = false;
@@ -350,7 +386,8 @@ void single_pass_drop_if_narrow(imm3_query *q, uint64_t survivors) {
 // one launch, 37 in three; a range of the sorted key that the sample's chunks missed).
 bool single_pass_restore_wanted(const imm3_query *q, uint64_t survivors) {
     const imm3_ctx *ctx = q->ctx;
-    if (q->single_pass || !q->sp_model_dropped || q->plan_pinned || ctx->capture || ctx->filter_variant == 6 || ctx->filter_variant == 3 || q->n_rows <= 0) return false;
+    if (q->single_pass || !q->sp_model_dropped || q->plan_pinned || ctx->capture || ctx->filter_variant == TV_NO_ONE_LAUNCH ||
+        ctx->filter_variant == TV_NO_RECORDS || q->n_rows <= 0) return false;
     const PlanDensity d = plan_density_for(q, survivors);
     const double now = q->d_stage_rec ? plan_cost('B', q->plan_shape, d) : plan_cost('C', q->plan_shape, d);
     return plan_cost('A', q->plan_shape, d) < kPlanKeepMargin * now;
@@ -363,12 +400,7 @@ int single_pass_restore(imm3_query *q, uint64_t survivors) {
     if (q->single_pass || !q->sp_model_dropped || q->plan_pinned || ctx->capture) return IMM3_OK;
     const int rc = single_pass_setup(q);
     if (rc || !q->single_pass) return rc; // (cannot run here: the three launches stay)
-    graphs_mark_stale(ctx, q);
-    pool_release(ctx, q->d_stage_rec);
-    pool_release(ctx, q->d_tile_start);
-    q->d_stage_rec = nullptr;
-    q->d_tile_start = nullptr;
-    q->run.stage_written = false;
+    records_release(q);
     q->sp_model_dropped = false;
     q->sp_narrow_checked = true; // (decided on a count: no second look)
     single_pass_adapt(q, survivors, -1);
@@ -437,11 +469,11 @@ int sample_tile_ptrs(imm3_ctx *ctx, const imm3_segment *cseg, int32_t col, int64
     return IMM3_OK;
 }
 
-int single_pass_sample(imm3_query *q) {
+static int single_pass_sample(imm3_query *q) {
     imm3_ctx *ctx = q->ctx;
     const int64_t n_full = q->table ? q->n_tiles : q->n_rows / kTileRows; // (a table's sample may hold a segment's partial last tile: the kernel's rolled path)
     const bool undecided = q->single_pass || q->alt_ok || q->d_stage_rec;
-    if (!undecided || q->sp_P_fixed || q->plan_pinned || ctx->filter_variant == 10 || n_full < 4096) return IMM3_OK; // (below ~4 M rows the sample costs what it saves)
+    if (!undecided || q->sp_P_fixed || q->plan_pinned || ctx->filter_variant == TV_NO_SAMPLE || n_full < 4096) return IMM3_OK; // (below ~4 M rows the sample costs what it saves)
     if (q->table && !q->table->d_sample_rows) return IMM3_OK;
     // ONE count-only launch of the scan+select kernel's table instance over the sample's tile table (round 3: eight launches, a
     // memset and a strided copy): 128 work-groups, one tile per wave, so that work-groups 16 i .. 16 i + 15 hold chunk i's count
@@ -452,9 +484,7 @@ int single_pass_sample(imm3_query *q) {
     for (int k = 0; k < kMaxTileCols; ++k) {
         a.kinds[k] = q->stage_kinds[k];
         if (a.kinds[k] == TK_NONE) continue;
-        const FoldedPred *fp = nullptr;
-        for (const auto &p : q->preds)
-            if (p.seg_col == q->stage_seg_col[k]) fp = &p;
+        const FoldedPred *fp = pred_on(q->preds, q->stage_seg_col[k]);
         if (!fp) return IMM3_OK; // (a streamed column already: nothing left to decide)
         if (is_compressed(q->seg->cols[(size_t)fp->seg_col].codec) && !q->seg->cols[(size_t)fp->seg_col].d_dense) return IMM3_OK;
         fill_tile_col(q, *fp, a.cols[k], a.kinds[k]);
@@ -509,6 +539,138 @@ int single_pass_sample(imm3_query *q) {
     records_drop_if_narrow(q, estimate);
     single_pass_drop_if_narrow(q, estimate);
     if (sum > 0.0) single_pass_pick_P(q, sigma_local, false);
+    return IMM3_OK;
+}
+
+// ---- the plan query creation makes for a projection ----
+// The SELECT-list entries whose values ride in the records (and in the one launch's): the first mention of each predicate column;
+// every other entry is gathered.  (fill_emit_cols, imm3_api.cpp, lets a later mention of a staged column read the record too: the
+// plan counts it as gathered -- one rule for both would change which launches run.)
+static std::vector<bool> proj_rides_in_records(imm3_query *q) {
+    std::vector<bool> rides(q->proj.size(), false);
+    for (size_t j = 0; j < q->proj.size(); ++j) {
+        const int32_t sci = q->used[(size_t)q->proj[j]];
+        bool first = true;
+        for (size_t i = 0; i < j; ++i) first &= q->used[(size_t)q->proj[i]] != sci;
+        rides[j] = first && pred_on(q->preds, sci) != nullptr;
+    }
+    return rides;
+}
+
+// The alternative the first count may switch to (single_pass_stream_columns): every gathered column of the SELECT list (first
+// mentions; dense int32 / int8) as a tile column that lets every value pass.
+static void plan_stream_alternative(imm3_query *q, const std::vector<const FoldedPred *> &order) {
+    std::vector<FoldedPred> pass;
+    for (int32_t pj : q->proj) {
+        const int32_t sci = q->used[(size_t)pj];
+        bool have = false;
+        for (const FoldedPred *fp : order) have |= fp->seg_col == sci;
+        for (const FoldedPred &fp : pass) have |= fp.seg_col == sci;
+        if (have) continue;
+        const SegCol &sc = q->seg->cols[(size_t)sci];
+        const bool dense_int = (sc.codec == IMM3_DENSE_INT && sc.width == 4) || (sc.codec == IMM3_DENSE_TINYINT && sc.width == 1);
+        if (!dense_int || !col_flat(sc)) return;
+        pass.push_back(unfolded_pred(sci, sc.codec, sc.width));
+    }
+    if (pass.empty() || order.size() + pass.size() > (size_t)kMaxTileCols) return;
+    q->sp_pass = pass;
+    std::vector<const FoldedPred *> all(order);
+    for (const FoldedPred &fp : q->sp_pass) all.push_back(&fp);
+    std::stable_sort(all.begin(), all.end(), [](const FoldedPred *x, const FoldedPred *y) { return tile_kind(*x) < tile_kind(*y); });
+    bool any4 = false, any_s2 = false;
+    for (int k = 0; k < kMaxTileCols; ++k) {
+        q->alt_kinds[k] = (size_t)k < all.size() ? tile_kind(*all[(size_t)k]) : (int)TK_NONE;
+        q->alt_seg_col[k] = (size_t)k < all.size() ? all[(size_t)k]->seg_col : -1;
+        any_s2 |= q->alt_kinds[k] == TK_S2;
+    }
+    for (const FoldedPred &fp : q->sp_pass) any4 |= fp.width == 4;
+    // Whether they ARE streamed is the cost model's call once the survivors are known (single_pass_stream_columns: the
+    // sample at creation, a reservation or the first count).  Measured at 100 M rows (one launch / three launches):
+    // age < 10 -> id, 10 %: 117 / 123 us; 3 %: 107 / 79; 30 %: 204 / 168; 99 %: 534 / 372 -- a window around 10 %.
+    // Not with a string predicate (the 2-byte match streams at 74 us with the one-launch kernel's 8 streaming waves per
+    // CU against 47), and not for 1-byte columns alone (their gather reads every line of the column from ~3 % on and
+    // still costs 33 us at 10 %).
+    q->alt_ok = any4 && !any_s2;
+}
+
+// The plans of an unlimited projection whose select chain is ONE tile launch (<= 3 predicate columns of int32 / int8 / 2-byte
+// string, at most one string; none is also fine: the record is then the position alone), `order` its columns: survivor records
+// (k_filter_tile STAGE -> k_emit), the one launch, the streamed alternative.  The SELECT list must be 1-, 2- and 4-byte columns,
+// at most kMaxEmitGather of them gathered.
+// A table query (every segment the GPU owns as one scan unit) takes the ONE-LAUNCH plan under the same conditions when no
+// SELECT-list column has to be gathered (round 5; its TABLE instances walk the tile table); survivor records and streamed
+// gathers are one-segment plans, the bitmap path is a table's other plan.
+static int plan_one_tile_pass(imm3_query *q, const std::vector<const FoldedPred *> &order) {
+    const int fv = q->ctx->filter_variant;
+    const std::vector<bool> rides = proj_rides_in_records(q);
+    int n_gather = 0;
+    int n_pred_proj = 0;         // predicate columns in the SELECT list whose values ride in the records ...
+    bool pred_proj_wide = false; // ... and whether one of them is wider than a byte
+    for (size_t j = 0; j < q->proj.size(); ++j) {
+        const int32_t w = q->seg->cols[(size_t)q->used[(size_t)q->proj[j]]].width;
+        if (w != 1 && w != 2 && w != 4) return IMM3_OK;
+        n_gather += !rides[j];
+        n_pred_proj += rides[j];
+        pred_proj_wide |= rides[j] && w > 1;
+    }
+    if (n_gather > kMaxEmitGather || (q->table && (n_gather > 0 || fv == TV_NO_ONE_LAUNCH))) return IMM3_OK;
+    for (size_t k = 0; k < order.size(); ++k) {
+        q->stage_kinds[k] = tile_kind(*order[k]);
+        q->stage_seg_col[k] = order[k]->seg_col;
+    }
+    PlanShape &ps = q->plan_shape; // what the cost model needs to know (imm3_plan.h)
+    ps = PlanShape();
+    ps.n_rows = q->n_rows;
+    for (size_t k = 0; k < order.size() && ps.n_pred < kPlanMaxCols; ++k, ++ps.n_pred) {
+        ps.pred_width[ps.n_pred] = order[k]->width;
+        ps.pred_match[ps.n_pred] = tile_kind(*order[k]) == TK_S2 ? (int32_t)order[k]->match.size() : 0;
+    }
+    for (size_t j = 0; j < q->proj.size() && ps.n_proj < kPlanMaxCols; ++j, ++ps.n_proj) {
+        ps.proj_width[ps.n_proj] = q->seg->cols[(size_t)q->used[(size_t)q->proj[j]]].width;
+        ps.proj_is_pred[ps.n_proj] = rides[j];
+    }
+    ps.rec_bytes = 4 * rec_layout(q->stage_kinds, -1).dwords;
+    q->plan_pinned = fv == TV_PLAN_PINNED;
+    // Single pass (k_filter_project): the filter kernel writes the rows itself.  Only when every SELECT-list column is a predicate
+    // column (its values ride in the records): gathers issued by the four writer waves of a CU are latency-bound (C4 154 us against
+    // 118 us with the emit kernel's 2048 work-groups).
+    if (fv != TV_NO_ONE_LAUNCH && (n_gather == 0 || fv == TV_ONE_LAUNCH_GATHERS)) {
+        const int rc = single_pass_setup(q);
+        if (rc) return rc;
+    }
+    if (!q->single_pass && n_gather > 0 && fv != TV_NO_ONE_LAUNCH && !q->table) plan_stream_alternative(q, order);
+    // Survivor records pay when the predicate columns' values are wanted: the staging instances of the filter kernel cost
+    // 12 (string) to 33 us (int8) per 100 M rows more than the plain ones, and buy the emit kernel the projected predicate
+    // columns.  When none is projected they buy nothing -- state in (5 values) -> age, 10 %: 120 us with records, 87 without
+    // (filter -> offsets scan -> gather from the bitmap); age in (18, 30) -> id, 11 %: 167 / 122; 3 %: 106 / 79.
+    q->records_narrow_only = n_pred_proj > 0 && !pred_proj_wide;
+    if (q->single_pass || q->table || (n_gather > 0 && n_pred_proj == 0 && fv != TV_RECORDS_ALWAYS)) return IMM3_OK; // (no survivor records in HBM)
+    return records_setup(q);
+}
+
+int plan_projection(imm3_query *q) {
+    // (anything but an unlimited projection whose select chain is ONE tile launch takes the bitmap path, which needs no set-up)
+    if (!q->proj.empty() && q->limit <= 0 && !q->always_false && q->n_rows > 0 && q->ctx->filter_variant != TV_NO_RECORDS &&
+        q->proj.size() <= (size_t)kMaxProj) {
+        const SelectChain chain = plan_select_chain(q); // (a ragged layout, TV_GENERIC_ONLY: no tile pass)
+        if (chain.single_tile_pass) {
+            const int rc = plan_one_tile_pass(q, chain.tile_passes[0]);
+            if (rc) return rc;
+        }
+    }
+    const int rc = single_pass_sample(q); // (the one synchronisation a creation may contain: segments of 4 M rows and more, undecided plans)
+    if (rc) return rc;
+    // No sample (a segment below 4 M rows -- there the sample costs what it saves): the plans are compared for one survivor in
+    // ten, spread evenly; the first count corrects it.  (At 4 M rows the bitmap path wins nearly every shape: the one launch
+    // starts at ~27 us, three small launches at 16-20.)
+    if (!q->plan_have_density && !q->plan_pinned && !q->sp_P_fixed && q->ctx->filter_variant != TV_NO_SAMPLE && q->plan_shape.n_rows > 0 &&
+        (q->single_pass || q->alt_ok || q->d_stage_rec)) {
+        const uint64_t guess = (uint64_t)(q->n_rows / 10);
+        const int rc2 = single_pass_stream_columns(q, guess);
+        if (rc2) return rc2;
+        records_drop_if_narrow(q, guess);
+        single_pass_drop_if_narrow(q, guess);
+    }
     return IMM3_OK;
 }
 

@@ -44,13 +44,17 @@ int imm3_ctx_measure_read_gbps(imm3_ctx *ctx, uint64_t bytes, int32_t iters, dou
  * 6 = projections never use the one-launch kernel, 8 = they use it with gathered SELECT-list columns too, 9 = gathered int32
  * columns are streamed through it whatever the selectivity, 10 = no sampled selectivity estimate at query creation (the plan
  * then adapts from the first run's count on), 11 = survivor records are staged even when no predicate column is projected,
- * 12 = the plan made at creation stands whatever the cost model predicts (tests of one plan's kernels; P still adapts),
- * 14 = a `limit` query scans the whole segment in one launch instead of in chunks behind a limit-reached word (decided per run),
+ * 12 = the plan made at creation stands whatever the cost model predicts (tests of one plan's kernels; P still adapts) and no
+ * bitmap lines are parked in LDS, 13 = a one-launch select chain reduces its count inside the filter kernel only at <= 512
+ * work-groups (default: at every grid), 14 = a `limit` query scans the whole segment in one launch instead of in chunks behind a limit-reached word (decided per run),
  * 15 = a small limit behind a limit scan takes k_scan + k_gather instead of the one fused launch (k_limit_gather),
  * 16 = one-launch projections use every CU even while a communicator whose collectives launch kernels is attached (default: one
  * CU per XCD is left to the collective's kernel), 17 = an aggregation's select chain runs as its own launch instead of inside the
  * aggregation launch, 19 = a projection through survivor records stores its bitmap in the staging launch (default: the bitmap is
- * materialised when imm3_query_bitmap asks), 200 + P = fixed tiles per range. */
+ * materialised when imm3_query_bitmap asks), 20 - 22 and 34 - 35 = ablation switches of k_filter_tile and k_emit (tools' build,
+ * libimm3_ablate.so, only), 50 + mask = ablation mask of k_filter_project (tools' build), 100 + AggForm = the aggregation starts at
+ * that kernel form, 140 and above = aggregation ablations (tools' build), 200 + P = fixed tiles per range.  The names of these
+ * numbers are csrc/imm3_handles.h's TuningVariant. */
 int imm3_ctx_set_tuning(imm3_ctx *ctx, int32_t filter_variant, int32_t grid_blocks);
 
 /* The projection planner's cost model (csrc/imm3_plan.h): predicted microseconds of one run's kernels under plan A (one launch), B

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Plan-quality sweep of the projection planner (imm3_api.cpp: query_create_impl and what it calls).
+"""Plan-quality sweep of the projection planner (imm3_planner.cpp: plan_projection, which query creation calls, and what it calls).
 
 For every cell -- rows x survivors per row x spread / clustered x SELECT-list shape -- the query is created and run under the planner's
 own choice (tuning variant 0, with the sample it takes at creation) and under every forced alternative:
