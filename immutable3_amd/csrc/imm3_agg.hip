@@ -1,4 +1,4 @@
-// imm3_agg.hip -- group-by aggregation (count / min / max) over the selected rows of one segment: the GPU
+// imm3_agg.hip -- group-by aggregation (count / min / max / sum) over the selected rows of one segment: the GPU
 // counterpart of ProjectAggOp.ProjectAggIterator.runAggs
 // (engine/src/main/scala/immutabledb/engine/operator/ProjectAggregate.scala:115-227).
 //
@@ -11,7 +11,8 @@
 //              (work-group, group).  k_group_collect compacts the occupied entries; the host orders them by
 //              first_row, which IS the LinkedHashMap's first-seen order.
 // Numeric min/max stay int32 (exact); the host converts to Double like value.toDouble.  String max compares the
-// value bytes big-endian-packed into a u64 == lexicographic byte order == String.compareTo for ASCII.
+// value bytes big-endian-packed into a u64 == lexicographic byte order == String.compareTo for ASCII.  SUM (AvgDoubleAggr's sum)
+// is an exact int64 -- at most 2^32 rows of |value| <= 2^31; where each form keeps its partial sums: DESIGN.md §10.
 #include "imm3_internal.h"
 #include "imm3_device.h"
 #include "imm3_tile.h"
@@ -70,6 +71,7 @@ __device__ __forceinline__ void agg_update_global(const AggArgs &a, uint32_t g, 
     for (int j = 0; j < a.n_agg; ++j) {
         long long *slot = &a.vals[(size_t)g * kMaxAggs + j];
         if (a.aggs[j].kind == AGG_MIN) atomicMin(slot, vals[j]);
+        else if (a.aggs[j].kind == AGG_SUM) atomicAdd((unsigned long long *)slot, (unsigned long long)vals[j]);
         else if (a.aggs[j].kind == AGG_MAX) {
             if (a.aggs[j].is_str) atomicMax((unsigned long long *)slot, (unsigned long long)vals[j]);
             else atomicMax(slot, vals[j]);
@@ -139,12 +141,14 @@ __device__ __forceinline__ void agg_fold(const AggArgs &a, const LdsTable &t, co
     if (r.slot >= 0) {
         long long *p = &t.vals[r.slot * kMaxAggs + j];
         // read before the atomic: once a group's extreme is established almost every row is a no-op
-        if (kind == AGG_MIN) { if (v < *p) atomicMin(p, v); }
+        if (kind == AGG_SUM) atomicAdd((unsigned long long *)p, (unsigned long long)v);
+        else if (kind == AGG_MIN) { if (v < *p) atomicMin(p, v); }
         else if (str) { if ((unsigned long long)v > (unsigned long long)*p) atomicMax((unsigned long long *)p, (unsigned long long)v); }
         else if (v > *p) atomicMax(p, v);
     } else if (r.gslot != 0xFFFFFFFFu) {
         long long *p = &a.vals[(size_t)r.gslot * kMaxAggs + j];
-        if (kind == AGG_MIN) atomicMin(p, v);
+        if (kind == AGG_SUM) atomicAdd((unsigned long long *)p, (unsigned long long)v);
+        else if (kind == AGG_MIN) atomicMin(p, v);
         else if (str) atomicMax((unsigned long long *)p, (unsigned long long)v);
         else atomicMax(p, v);
     }
@@ -226,7 +230,7 @@ __global__ __launch_bounds__(kAggThreads) void k_group_agg(const AggArgs a) {
         for (int j = 0; j < kMaxAggs; ++j) {
             const int kind = j < a.n_agg ? a.aggs[j].kind : AGG_COUNT;
             const bool str = j < a.n_agg && a.aggs[j].is_str;
-            s_vals[i * kMaxAggs + j] = kind == AGG_MIN ? INT64_MAX : (str ? 0 : INT64_MIN);
+            s_vals[i * kMaxAggs + j] = kind == AGG_MIN ? INT64_MAX : ((str || kind == AGG_SUM) ? 0 : INT64_MIN);
         }
     }
     __syncthreads();
@@ -357,7 +361,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_group_agg_tile(const AggArgs 
         for (int j = 0; j < kMaxAggs; ++j) {
             const int kind = j < a.n_agg ? a.aggs[j].kind : AGG_COUNT;
             const bool str = j < a.n_agg && a.aggs[j].is_str;
-            s_vals[j][i] = kind == AGG_MIN ? (uint32_t)INT32_MAX : (str ? 0u : (uint32_t)INT32_MIN);
+            s_vals[j][i] = kind == AGG_MIN ? (uint32_t)INT32_MAX : ((str || kind == AGG_SUM) ? 0u : (uint32_t)INT32_MIN);
         }
     }
     __syncthreads();
@@ -425,6 +429,8 @@ __global__ __launch_bounds__(kBlockThreads) void k_group_agg_tile(const AggArgs 
                     if (str) { // big-endian pack: integer order == byte-lexicographic order
                         const uint32_t be = w == 4 ? __builtin_bswap32(v[j]) : (w == 2 ? (uint32_t)__builtin_bswap16((uint16_t)v[j]) : v[j]);
                         atomicMax(p, be);
+                    } else if (kind == AGG_SUM) { // int8 only (tile_sum_ok): the value biased to 0 .. 255, un-biased at the flush
+                        atomicAdd(p, (v[j] ^ 0x80u) & 0xFFu);
                     } else {
                         const int32_t x = w == 4 ? (int32_t)v[j] : (int32_t)(int8_t)v[j];
                         if (kind == AGG_MIN) atomicMin((int32_t *)p, x);
@@ -446,7 +452,8 @@ __global__ __launch_bounds__(kBlockThreads) void k_group_agg_tile(const AggArgs 
         long long vals[kMaxAggs];
         for (int j = 0; j < kMaxAggs; ++j) {
             const bool str = j < a.n_agg && a.aggs[j].is_str;
-            vals[j] = str ? (long long)(unsigned long long)s_vals[j][i] : (long long)(int32_t)s_vals[j][i];
+            if (j < a.n_agg && a.aggs[j].kind == AGG_SUM) vals[j] = (long long)s_vals[j][i] - 128LL * (long long)s_count[i];
+            else vals[j] = str ? (long long)(unsigned long long)s_vals[j][i] : (long long)(int32_t)s_vals[j][i];
         }
         agg_update_global(a, g, s_first[i], (unsigned long long)s_count[i], vals);
     }
@@ -471,6 +478,7 @@ __global__ __launch_bounds__(kDirectThreads) void k_group_agg_direct(const AggAr
     __shared__ uint32_t s_first[kDirectSlots];
     __shared__ uint32_t s_count[kDirectSlots];
     __shared__ uint32_t s_vals[kMaxAggs][kDirectSlots];
+    __shared__ unsigned long long s_sum[kMaxAggs][kDirectSlots]; // SUM aggregates: 64-bit LDS adds (a work-group covers up to 2^24 rows)
     __shared__ uint32_t s_nslots;
     __shared__ __attribute__((aligned(16))) uint8_t s_xp[kDirectWaves][2048];
     // LDS atomics retire ~1.4 lanes per cycle per CU whatever the addresses (measured: each atomic per row costs ~115 us per
@@ -489,9 +497,10 @@ __global__ __launch_bounds__(kDirectThreads) void k_group_agg_direct(const AggAr
         s_first[i] = 0xFFFFFFFFu;
         s_count[i] = 0;
         for (int j = 0; j < kMaxAggs; ++j) {
+            s_sum[j][i] = 0ULL;
             const int kind = j < a.n_agg ? a.aggs[j].kind : AGG_COUNT;
             const bool str = j < a.n_agg && a.aggs[j].is_str;
-            s_vals[j][i] = kind == AGG_MIN ? (uint32_t)INT32_MAX : (str ? 0u : (uint32_t)INT32_MIN);
+            s_vals[j][i] = kind == AGG_MIN ? (uint32_t)INT32_MAX : ((str || kind == AGG_SUM) ? 0u : (uint32_t)INT32_MIN);
         }
     }
     if (t == 0) s_nslots = 0;
@@ -586,7 +595,10 @@ __global__ __launch_bounds__(kDirectThreads) void k_group_agg_direct(const AggAr
                 if (__builtin_amdgcn_inverse_ballot_w64(m[j])) {
                     const uint32_t raw = late[j];
                     uint32_t *p = &s_vals[q][sid[j]];
-                    if (str) { // big-endian pack: integer order == byte-lexicographic order
+                    if (kind == AGG_SUM) {
+                        const long long x = w == 4 ? (long long)(int32_t)raw : (long long)(int8_t)raw;
+                        atomicAdd(&s_sum[q][sid[j]], (unsigned long long)x);
+                    } else if (str) { // big-endian pack: integer order == byte-lexicographic order
                         const uint32_t be = w == 4 ? __builtin_bswap32(raw) : (w == 2 ? (uint32_t)__builtin_bswap16((uint16_t)raw) : raw);
                         atomicMax(p, be);
                     } else {
@@ -609,7 +621,8 @@ __global__ __launch_bounds__(kDirectThreads) void k_group_agg_direct(const AggAr
         long long vals[kMaxAggs];
         for (int j = 0; j < kMaxAggs; ++j) {
             const bool str = j < a.n_agg && a.aggs[j].is_str;
-            vals[j] = str ? (long long)(unsigned long long)s_vals[j][i] : (long long)(int32_t)s_vals[j][i];
+            if (j < a.n_agg && a.aggs[j].kind == AGG_SUM) vals[j] = (long long)s_sum[j][i];
+            else vals[j] = str ? (long long)(unsigned long long)s_vals[j][i] : (long long)(int32_t)s_vals[j][i];
         }
         agg_update_global(a, g, s_first[i], (unsigned long long)s_count[i], vals);
     }
@@ -647,13 +660,19 @@ struct LanesShared { // fixed part of the dynamic LDS; [l2 .. first] start as al
     uint8_t l1[256];
     uint32_t slotkey[kLaneSlots];
     uint32_t count[kLaneSlots];
-    uint32_t val[kLaneSlots];
-    uint32_t val2[kLaneSlots];
+    union { // (8-byte aligned: l2 .. count are 9728 bytes)
+        struct {
+            uint32_t val[kLaneSlots];
+            uint32_t val2[kLaneSlots];
+        };
+        unsigned long long sum[kLaneSlots]; // SUM instances (one value aggregate): the work-group's sums, biased
+    };
     uint32_t nslots, npages, pad[2];
 };
 constexpr int kLanesOnesBytes = (kLanePages + 1) * 256 + kLaneSlots * 4;
 constexpr int kLanesFixedBytes = (int)((sizeof(LanesShared) + 255) / 256 * 256);
-constexpr int lanes_wave_bytes(int vw, bool v2 = false, int ns = 64) {
+constexpr int lanes_wave_bytes(int vw, bool v2 = false, int ns = 64, bool sum = false) {
+    if (sum) return vw == 1 ? ns * 64 * 4 + ns * 4 : ns * 64 * (4 + 4);
     return v2 ? ns * 64 * 4 + ns * 4 : (vw <= 1 ? ns * 64 * 2 + ns * 4 : ns * 64 * (vw == 4 ? 2 + 4 : 4));
 }
 
@@ -792,14 +811,19 @@ __device__ __forceinline__ uint64_t wave_or64(uint64_t v) {
 // KS: key shape -- 0: one 1-byte column, 1: one 2-byte column, 2: two 1-byte columns.  VW: bytes of the aggregated column (0: counts only).
 // V2: a second min / max aggregate, both over 1-byte columns (e.g. max(age), min(age)).
 // NS: rows of a lane's table (64 or 128, the last one the trash slot): 63 or 127 distinct keys per work-group.
+// SUM: the one value aggregate is a SUM (VW 1 or 4).  The per-lane entries ADD what MIN / MAX would max: the value biased to unsigned
+// (x = v + 2^(8 VW - 1)), un-biased at the flush with the slot's count.  VW 1: u32 = biased sum << 8 | count, the 8-bit counts folded
+// like V2 (a lane's rows of one slot stay below 2^16: the sum below 2^24).  VW 4: u32 value sum + u32 = carries << 16 | count (a lane's
+// rows -- so its carries out of the u32 -- stay below 2^16): one add and one compare more per row than a max, 8 bytes per entry.
 // FUSED: the select chain is evaluated HERE, on the sixteen rows a lane holds -- a.fused[] closed intervals over int8 / int32
 // columns (a predicate on the value aggregate's own column reads nothing more), or no predicate at all -- instead of being read
 // from the bitmap a filter launch wrote: SelectOp fused into ProjectAggOp (ProjectAggregate.scala:158-177 walks the selected
 // positions of the batch it was handed).  Round 4 ran `group by state where age in (18, 30)` as filter 22 us + aggregation 82 us
 // with the bitmap written and read back and `age` read twice.
-template <int KS, int VW, bool V2, int NS, bool FUSED>
+template <int KS, int VW, bool V2, int NS, bool FUSED, bool SUM>
 __global__ __launch_bounds__(1024) void k_group_agg_lanes(const AggArgs a, const int vq, const int vq2) {
     static_assert(!V2 || VW == 1, "two value aggregates: 1-byte columns only");
+    static_assert(!SUM || ((VW == 1 || VW == 4) && !V2), "SUM: one int8 or int32 value aggregate");
     static_assert(NS == 64 || NS == 128, "the map's markers (253 .. 255) must have a bit set that no slot number has");
     constexpr uint32_t kTrash = NS - 1;
     constexpr int kWords = NS / 64; // 64-bit words of a slot set
@@ -809,20 +833,21 @@ __global__ __launch_bounds__(1024) void k_group_agg_lanes(const AggArgs a, const
     const int lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int n_waves = (int)(blockDim.x >> 6);
-    constexpr int kWaveBytes = lanes_wave_bytes(VW, V2, NS);
+    constexpr int kWaveBytes = lanes_wave_bytes(VW, V2, NS, SUM);
     constexpr int NV = VW == 4 ? 4 : (VW == 2 ? 2 : 1);
     // entry of one (slot, lane):  VW 0: u16 count.  VW 1: u16 = value << 8 | count, the 8-bit counts folded into a per-wave
     // u32 table every 15 tiles (a lane adds at most 16 per tile).  VW 2: u32 = value << 16 | count.  VW 4: u16 count + u32 value.
     // The 16-bit forms halve the tables, which is what doubles the waves per CU (16): the row path is latency-bound.
     // V2: u32 = value2 << 16 | value << 8 | count, counts folded like VW 1.
-    constexpr bool kE16 = VW <= 1 && !V2;
+    constexpr bool kE16 = VW <= 1 && !V2 && !SUM;
     constexpr bool kPacked = VW == 2;
+    constexpr bool kSum1 = SUM && VW == 1, kSum4 = SUM && VW == 4;
     uint8_t *wbase = s_dyn + wave * kWaveBytes;
     uint16_t *t16 = (uint16_t *)wbase + (lane & 31) * 2 + (lane >> 5);      // 16-bit: [slot * 64]; lanes l and l + 32 share a dword, so each half-wave hits 32 banks
-    uint32_t *wcnt = (uint32_t *)(wbase + NS * 64 * (V2 ? 4 : 2));  // VW 1: [slot] counts folded so far (owned by lane = slot)
-    uint32_t *tab = (uint32_t *)wbase + lane;                               // packed: [slot * 64]
+    uint32_t *wcnt = (uint32_t *)(wbase + NS * 64 * ((V2 || kSum1) ? 4 : 2)); // VW 1: [slot] counts folded so far (owned by lane = slot)
+    uint32_t *tab = (uint32_t *)wbase + lane;                               // packed, V2, SUM: [slot * 64]
     uint16_t *cnt = (uint16_t *)wbase + lane;                               // VW == 4: counts [slot * 64] ...
-    uint32_t *val = (uint32_t *)(wbase + NS * 64 * 2) + lane;               // ... and values [slot * 64]
+    uint32_t *val = (uint32_t *)(wbase + NS * 64 * (kSum4 ? 4 : 2)) + lane; // ... and values [slot * 64]
     for (int i = t; i < (int)(sizeof(LanesShared) / 4); i += (int)blockDim.x) ((uint32_t *)&S)[i] = i < kLanesOnesBytes / 4 ? 0xFFFFFFFFu : 0u; // l2 + first: ones
     for (int i = t; i < n_waves * kWaveBytes / 4; i += (int)blockDim.x) ((uint32_t *)s_dyn)[i] = 0u;
     __syncthreads();
@@ -918,7 +943,7 @@ __global__ __launch_bounds__(1024) void k_group_agg_lanes(const AggArgs a, const
             uint32_t c = 0;
             // (eight reads, then their eight writes: with a write behind every read the compiler -- which cannot know that the rotated
             // indices never collide -- kept the 64 round trips in sequence)
-            if constexpr (V2) {
+            if constexpr (V2 || kSum1) {
                 uint32_t *row = (uint32_t *)wbase + slot * 64;
 #pragma unroll 1
                 for (int j0 = 0; j0 < 64; j0 += 8) {
@@ -955,7 +980,15 @@ __global__ __launch_bounds__(1024) void k_group_agg_lanes(const AggArgs a, const
             if (vstr) raw = VW == 4 ? __builtin_bswap32(raw) : (VW == 2 ? (uint32_t)__builtin_bswap16((uint16_t)raw) : raw); // big-endian pack: integer order == byte order
             x = (raw ^ vflip) & vmask;
         }
-        if constexpr (V2) {
+        if constexpr (kSum1) {
+            const uint32_t old = tab[s * 64];
+            tab[s * 64] = old + 1u + (x << 8);
+        } else if constexpr (kSum4) {
+            const uint32_t oc = tab[s * 64], ov = val[s * 64];
+            const uint32_t nv = ov + x;
+            tab[s * 64] = oc + (nv < x ? 0x10001u : 1u); // count + 1, and a carry out of the value sum into the high half
+            val[s * 64] = nv;
+        } else if constexpr (V2) {
             const uint32_t x2 = (raw2 ^ vflip2) & 0xFFu; // (1-byte strings need no byte swap)
             const uint32_t old = tab[s * 64];
             tab[s * 64] = ((old + 1u) & 0xFFu) | max(old & 0xFF00u, x << 8) | max(old & 0xFF0000u, x2 << 16);
@@ -1196,11 +1229,18 @@ __global__ __launch_bounds__(1024) void k_group_agg_lanes(const AggArgs a, const
     for (int p = 0; p < kWords; ++p) {
         const int slot = 64 * p + lane;
         uint32_t c = 0, m = 0, m2 = 0;
+        unsigned long long sum = 0;
         if constexpr (VW == 1) c = wcnt[slot];
 #pragma unroll 8
         for (int l = 0; l < 64; ++l) { // (eight reads in flight: rolled, this was 64 dependent LDS round trips per wave)
             const int src = (l + lane) & 63;
-            if constexpr (V2) {
+            if constexpr (kSum1) {
+                sum += ((const uint32_t *)wbase)[slot * 64 + src] >> 8;
+            } else if constexpr (kSum4) {
+                const uint32_t e = ((const uint32_t *)wbase)[slot * 64 + src];
+                c += e & 0xFFFFu;
+                sum += ((unsigned long long)(e >> 16) << 32) + ((const uint32_t *)(wbase + NS * 64 * 4))[slot * 64 + src];
+            } else if constexpr (V2) {
                 const uint32_t e = ((const uint32_t *)wbase)[slot * 64 + src];
                 m = max(m, (e >> 8) & 0xFFu);
                 m2 = max(m2, (e >> 16) & 0xFFu);
@@ -1219,7 +1259,8 @@ __global__ __launch_bounds__(1024) void k_group_agg_lanes(const AggArgs a, const
         }
         if ((uint32_t)slot < kTrash && c) {
             atomicAdd(&S.count[slot], c);
-            if constexpr (VW != 0) atomicMax(&S.val[slot], m);
+            if constexpr (SUM) atomicAdd(&S.sum[slot], sum);
+            else if constexpr (VW != 0) atomicMax(&S.val[slot], m);
             if constexpr (V2) atomicMax(&S.val2[slot], m2);
         }
     }
@@ -1231,7 +1272,9 @@ __global__ __launch_bounds__(1024) void k_group_agg_lanes(const AggArgs a, const
         const uint32_t g = global_slot(a, (unsigned long long)S.slotkey[t]);
         if (g != 0xFFFFFFFFu) {
             long long vals[kMaxAggs] = {0, 0, 0, 0};
-            if constexpr (VW != 0) {
+            if constexpr (SUM) { // sum of x = v + 2^(8 VW - 1) over the slot's rows
+                vals[vq] = (long long)(S.sum[t] - ((unsigned long long)S.count[t] << (8 * VW - 1)));
+            } else if constexpr (VW != 0) {
                 const uint32_t u = (S.val[t] ^ vflip) & vmask;
                 vals[vq] = vstr ? (long long)(unsigned long long)u : (VW == 4 ? (long long)(int32_t)u : (VW == 2 ? (long long)(int16_t)u : (long long)(int8_t)u));
             }
@@ -1278,7 +1321,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_group_init(const AggArgs a) {
         for (int j = 0; j < kMaxAggs; ++j) {
             const int kind = j < a.n_agg ? a.aggs[j].kind : AGG_COUNT;
             const bool str = j < a.n_agg && a.aggs[j].is_str;
-            a.vals[(size_t)i * kMaxAggs + j] = kind == AGG_MIN ? INT64_MAX : (str ? 0 : INT64_MIN);
+            a.vals[(size_t)i * kMaxAggs + j] = kind == AGG_MIN ? INT64_MAX : ((str || kind == AGG_SUM) ? 0 : INT64_MIN);
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -1306,8 +1349,17 @@ bool group_agg_fast_ok(const AggArgs &a) {
     return true;
 }
 
+// k_group_agg_tile keeps a SUM in a u32 per (work-group, group): int8 values biased to 0 .. 255, exact while a work-group's rows
+// stay below 2^32 / 255 (its grid of <= 768 work-groups over <= 2^22 tiles keeps them below 2^23).  int32 sums go to the general kernel.
+static bool tile_sum_ok(const AggArgs &a, int grid) {
+    const int64_t rows_per_wg = (a.n_tiles + (int64_t)grid * kWavesPerBlock - 1) / ((int64_t)grid * kWavesPerBlock) * kWavesPerBlock * kTileRows;
+    for (int q = 0; q < a.n_agg; ++q)
+        if (a.aggs[q].kind == AGG_SUM && (a.aggs[q].width != 1 || rows_per_wg * 255 >= (1LL << 32))) return false;
+    return true;
+}
+
 // which form of k_group_agg_lanes takes this aggregation (false: none).  waves: as many as the LDS holds.
-struct LanesPlan { int ks, vw, vq, vq2, v2, ns, waves, lds_bytes; };
+struct LanesPlan { int ks, vw, vq, vq2, v2, sum, ns, waves, lds_bytes; };
 static bool lanes_plan(const AggArgs &a, int ns, LanesPlan &p) {
     p.ns = ns;
     if (!group_agg_fast_ok(a)) return false;
@@ -1318,6 +1370,7 @@ static bool lanes_plan(const AggArgs &a, int ns, LanesPlan &p) {
     p.vw = 0;
     p.vq = p.vq2 = 0;
     p.v2 = 0;
+    p.sum = 0;
     int n_val = 0;
     for (int q = 0; q < a.n_agg; ++q)
         if (a.aggs[q].kind != AGG_COUNT) {
@@ -1325,14 +1378,16 @@ static bool lanes_plan(const AggArgs &a, int ns, LanesPlan &p) {
                 p.vq = q;
                 p.vw = a.aggs[q].width;
             } else p.vq2 = q;
+            p.sum |= a.aggs[q].kind == AGG_SUM ? 1 : 0;
             ++n_val;
         }
     if (n_val > 2) return false;
+    if (p.sum && (n_val != 1 || (p.vw != 1 && p.vw != 4))) return false; // a SUM: as the one value aggregate (the entries hold one sum)
     if (n_val == 2) { // two min / max aggregates: both over 1-byte columns
         if (p.vw != 1 || a.aggs[p.vq2].width != 1) return false;
         p.v2 = 1;
     }
-    const int per_wave = lanes_wave_bytes(p.vw, p.v2 != 0, ns);
+    const int per_wave = lanes_wave_bytes(p.vw, p.v2 != 0, ns, p.sum != 0);
     p.waves = std::min(16, (160 * 1024 - kLanesFixedBytes) / per_wave);
     const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((a.n_tiles + p.waves - 1) / p.waves, 256));
     const int64_t tiles_per_wave = (a.n_tiles + grid * p.waves - 1) / (grid * p.waves);
@@ -1342,7 +1397,7 @@ static bool lanes_plan(const AggArgs &a, int ns, LanesPlan &p) {
 }
 
 // false: the device refused the kernel's dynamic LDS size (the caller falls through to the next form)
-template <int KS, int VW, bool V2, int NS, bool FUSED>
+template <int KS, int VW, bool V2, int NS, bool FUSED, bool SUM>
 static bool launch_lanes(const AggArgs &a, const LanesPlan &p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     // The dynamic-LDS limit of a kernel function is raised once per DEVICE (a process may drive all eight GPUs, one
     // context each, from several threads): 0 = not yet, 1 = raised, 2 = refused.
@@ -1351,14 +1406,14 @@ static bool launch_lanes(const AggArgs &a, const LanesPlan &p, hipStream_t s, hi
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return false;
     int st = raised[dev].load(std::memory_order_acquire);
     if (st == 0) { // (two threads may both get here: the call is idempotent)
-        const hipError_t e = hipFuncSetAttribute((const void *)k_group_agg_lanes<KS, VW, V2, NS, FUSED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - kLanesFixedBytes);
+        const hipError_t e = hipFuncSetAttribute((const void *)k_group_agg_lanes<KS, VW, V2, NS, FUSED, SUM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - kLanesFixedBytes);
         if (e != hipSuccess) (void)hipGetLastError();
         st = e == hipSuccess ? 1 : 2;
         raised[dev].store(st, std::memory_order_release);
     }
     if (st != 1) return false;
     const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((a.n_tiles + p.waves - 1) / p.waves, 256)); // one work-group per CU
-    IMM3_LAUNCH_LDS((k_group_agg_lanes<KS, VW, V2, NS, FUSED>), (unsigned)grid, p.waves * 64, (size_t)p.lds_bytes, s, ev0, ev1, a, p.vq, p.vq2);
+    IMM3_LAUNCH_LDS((k_group_agg_lanes<KS, VW, V2, NS, FUSED, SUM>), (unsigned)grid, p.waves * 64, (size_t)p.lds_bytes, s, ev0, ev1, a, p.vq, p.vq2);
     return true;
 }
 
@@ -1384,7 +1439,7 @@ bool group_agg_fuses_select(const AggArgs &a) {
     return true;
 }
 
-void launch_group_agg(const AggArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+int launch_group_agg(const AggArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     const int64_t n = (int64_t)a.mask + 2;
     const int init_grid = (int)std::min<int64_t>((n + kBlockThreads - 1) / kBlockThreads, 2048);
     hipLaunchKernelGGL(k_group_init, dim3(init_grid), dim3(kBlockThreads), 0, s, a);
@@ -1396,16 +1451,19 @@ void launch_group_agg(const AggArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_
     // private per-lane tables, no atomics: 63 keys per work-group, then 127
     if (a.first_form <= AGG_FORM_LANES_WIDE && lanes_plan(a, a.first_form == AGG_FORM_LANES_WIDE ? 128 : 64, lp)) {
         const bool fuse = group_agg_fuses_select(a); // (the host has then skipped the select launch: imm3_api.cpp, run_agg)
-#define IMM3_LANES(KS, VW, V2)                                                                       \
-    if (lp.ks == KS && lp.vw == VW && (lp.v2 != 0) == V2) {                                          \
-        const bool ok = fuse ? launch_lanes<KS, VW, V2, 64, true>(a, lp, s, ev0, ev1)                \
-                             : (lp.ns == 64 ? launch_lanes<KS, VW, V2, 64, false>(a, lp, s, ev0, ev1) \
-                                            : launch_lanes<KS, VW, V2, 128, false>(a, lp, s, ev0, ev1)); \
-        if (ok) return;                                                                              \
+#define IMM3_LANES(KS, VW, V2, SUM)                                                                            \
+    if (lp.ks == KS && lp.vw == VW && (lp.v2 != 0) == V2 && (lp.sum != 0) == SUM) {                           \
+        const bool ok = fuse ? launch_lanes<KS, VW, V2, 64, true, SUM>(a, lp, s, ev0, ev1)                     \
+                             : (lp.ns == 64 ? launch_lanes<KS, VW, V2, 64, false, SUM>(a, lp, s, ev0, ev1)      \
+                                            : launch_lanes<KS, VW, V2, 128, false, SUM>(a, lp, s, ev0, ev1));   \
+        if (ok) return lp.ns == 64 ? AGG_FORM_LANES : AGG_FORM_LANES_WIDE;                                     \
     }
-        IMM3_LANES(0, 0, false) IMM3_LANES(0, 1, false) IMM3_LANES(0, 2, false) IMM3_LANES(0, 4, false) IMM3_LANES(0, 1, true)
-        IMM3_LANES(1, 0, false) IMM3_LANES(1, 1, false) IMM3_LANES(1, 2, false) IMM3_LANES(1, 4, false) IMM3_LANES(1, 1, true)
-        IMM3_LANES(2, 0, false) IMM3_LANES(2, 1, false) IMM3_LANES(2, 2, false) IMM3_LANES(2, 4, false) IMM3_LANES(2, 1, true)
+        IMM3_LANES(0, 0, false, false) IMM3_LANES(0, 1, false, false) IMM3_LANES(0, 2, false, false) IMM3_LANES(0, 4, false, false) IMM3_LANES(0, 1, true, false)
+        IMM3_LANES(1, 0, false, false) IMM3_LANES(1, 1, false, false) IMM3_LANES(1, 2, false, false) IMM3_LANES(1, 4, false, false) IMM3_LANES(1, 1, true, false)
+        IMM3_LANES(2, 0, false, false) IMM3_LANES(2, 1, false, false) IMM3_LANES(2, 2, false, false) IMM3_LANES(2, 4, false, false) IMM3_LANES(2, 1, true, false)
+        IMM3_LANES(0, 1, false, true) IMM3_LANES(0, 4, false, true)
+        IMM3_LANES(1, 1, false, true) IMM3_LANES(1, 4, false, true)
+        IMM3_LANES(2, 1, false, true) IMM3_LANES(2, 4, false, true)
 #undef IMM3_LANES
     }
     if (a.first_form <= AGG_FORM_DIRECT && group_agg_fast_ok(a) && key_bytes <= 2) { // the key indexes a slot map directly
@@ -1413,17 +1471,20 @@ void launch_group_agg(const AggArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_
         const int64_t want = (a.n_tiles + kDirectWaves - 1) / kDirectWaves;
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(want, 256)); // one 1024-thread work-group per CU
         IMM3_LAUNCH_LDS(k_group_agg_direct, grid, kDirectThreads, (size_t)map_bytes, s, ev0, ev1, a, map_bytes);
-        return;
+        return AGG_FORM_DIRECT;
     }
     if (a.first_form <= AGG_FORM_TILE && group_agg_fast_ok(a)) {
         const int64_t want = (a.n_tiles + kWavesPerBlock - 1) / kWavesPerBlock;
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(want, 768)); // ~41 KiB of LDS: 3 per CU
-        IMM3_LAUNCH(k_group_agg_tile, grid, kBlockThreads, s, ev0, ev1, a);
-        return;
+        if (tile_sum_ok(a, grid)) {
+            IMM3_LAUNCH(k_group_agg_tile, grid, kBlockThreads, s, ev0, ev1, a);
+            return AGG_FORM_TILE;
+        }
     }
     const int64_t want = ((a.n_words + 3) / 4 + kAggWaves - 1) / kAggWaves;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(want, 768)); // 512-thread work-groups, 48 KiB LDS: 3 per CU
     IMM3_LAUNCH(k_group_agg, grid, kAggThreads, s, ev0, ev1, a);
+    return AGG_FORM_GENERAL;
 }
 
 // ---- merge of group tables (imm3_comm_merge_groups): direct-indexed tables for keys of <= 2 bytes, a hash table for wider keys ----
@@ -1434,7 +1495,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_merge_init(const MergeArgs a)
         if (a.t_keys) a.t_keys[i] = kEmptyKey;
         for (int j = 0; j < kMaxAggs; ++j) {
             const int kind = j < a.n_agg ? a.kinds[j] : AGG_COUNT;
-            a.t_vals[(size_t)j * a.slots + i] = kind == AGG_MIN ? INT64_MAX : ((j < a.n_agg && a.is_str[j]) ? 0 : INT64_MIN);
+            a.t_vals[(size_t)j * a.slots + i] = kind == AGG_MIN ? INT64_MAX : ((kind == AGG_SUM || (j < a.n_agg && a.is_str[j])) ? 0 : INT64_MIN);
         }
     }
     if (a.out_n && blockIdx.x == 0 && threadIdx.x == 0) *a.out_n = 0ULL;
@@ -1464,6 +1525,7 @@ __device__ __forceinline__ void merge_update(const MergeArgs &a, uint32_t slot, 
             if (a.is_str[j]) atomicMax((unsigned long long *)t, (unsigned long long)v);
             else atomicMax(t, v);
         } else if (a.kinds[j] == AGG_MIN) atomicMin(t, v);
+        else if (a.kinds[j] == AGG_SUM) atomicAdd((unsigned long long *)t, (unsigned long long)v);
     }
 }
 

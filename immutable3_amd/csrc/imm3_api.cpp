@@ -2567,9 +2567,10 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
         if (aggs[j].column < 0 || aggs[j].column >= n_used) return fail(IMM3_ERR_ARG, "aggregate column is not among the used columns");
         const SegCol &sc = seg->cols[(size_t)q->used[(size_t)aggs[j].column]];
         const bool is_str = sc.vcodec == IMM3_DENSE_STRING;
-        if (aggs[j].kind != IMM3_AGG_COUNT && aggs[j].kind != IMM3_AGG_MIN && aggs[j].kind != IMM3_AGG_MAX) return fail(IMM3_ERR_ARG, "Unknown Aggregate type");
-        // ProjectAggregate.scala:176-220: a String vector only takes CountAggr / MaxStringAggr
-        if (has_batches && is_str && aggs[j].kind == IMM3_AGG_MIN) return fail(IMM3_ERR_UNSUPPORTED_VECTOR, "bad aggregator for this data type");
+        if (aggs[j].kind != IMM3_AGG_COUNT && aggs[j].kind != IMM3_AGG_MIN && aggs[j].kind != IMM3_AGG_MAX && aggs[j].kind != IMM3_AGG_SUM)
+            return fail(IMM3_ERR_ARG, "Unknown Aggregate type");
+        // ProjectAggregate.scala:176-220: a String vector only takes CountAggr / MaxStringAggr (AvgDoubleAggr's sum is numeric only)
+        if (has_batches && is_str && (aggs[j].kind == IMM3_AGG_MIN || aggs[j].kind == IMM3_AGG_SUM)) return fail(IMM3_ERR_UNSUPPORTED_VECTOR, "bad aggregator for this data type");
         if (is_str && aggs[j].kind == IMM3_AGG_MAX && sc.width > 8) return fail(IMM3_ERR_ARG, "MAX over strings wider than 8 bytes is not supported on the GPU path");
     }
     q->is_agg = true;
@@ -2705,7 +2706,7 @@ static int run_agg(imm3_query *q) {
     agg_launch_args(q, a);
     if (!q->run.agg_select_skipped) { a.n_fused = 0; a.fused_all = 0; } // (the select ran: the bitmap is what this launch reads)
     LaunchTimer t(ctx, 4);
-    launch_group_agg(a, ctx->stream, t.start, t.stop);
+    q->agg_form_ran = launch_group_agg(a, ctx->stream, t.start, t.stop);
     HIPCHK(hipGetLastError());
     q->run.ran_agg = true;
     return IMM3_OK;
@@ -2739,7 +2740,7 @@ static int settle_groups(imm3_query *q, uint32_t *n_groups) {
                 g.n_fused = 0;
                 g.fused_all = 0;
             }
-            launch_group_agg(g, s, nullptr, nullptr);
+            q->agg_form_ran = launch_group_agg(g, s, nullptr, nullptr);
             HIPCHK(hipGetLastError());
             continue;
         }
@@ -2809,6 +2810,13 @@ extern "C" int imm3_query_fetch_groups(imm3_query *q, uint64_t *keys, uint32_t *
             for (size_t j = 0; j < na; ++j)
                 vals[(size_t)o * na + j] = q->aggs[j].kind == IMM3_AGG_COUNT ? (int64_t)hc[i] : (int64_t)hv[(size_t)i * kMaxAggs + j];
     }
+    return IMM3_OK;
+}
+
+extern "C" int imm3_query_agg_form(const imm3_query *q, int32_t *form) {
+    if (!q || !form) return fail(IMM3_ERR_ARG, "null argument");
+    if (!q->is_agg) return fail(IMM3_ERR_ARG, "not an aggregation query");
+    *form = q->agg_form_ran;
     return IMM3_OK;
 }
 

@@ -443,6 +443,7 @@ void combine(MergedGroup &into, const MergedGroup &g, const int32_t *kinds, cons
             if (is_str[j]) into.vals[j] = (long long)std::max((unsigned long long)into.vals[j], (unsigned long long)g.vals[j]);
             else into.vals[j] = std::max(into.vals[j], g.vals[j]);
         } else if (kinds[j] == AGG_MIN) into.vals[j] = std::min(into.vals[j], g.vals[j]);
+        else if (kinds[j] == AGG_SUM) into.vals[j] += g.vals[j];
     }
 }
 
@@ -560,6 +561,7 @@ extern "C" int imm3_comm_merge_groups(imm3_comm *c, imm3_query *const *queries, 
                 long long *t = a.t_vals + (size_t)j * K;
                 if (kinds[j] == AGG_MAX) NCCLCHK(g_rccl.AllReduce(t, t, K, is_str[j] ? ncclUint64 : ncclInt64, ncclMax, c->nccl, s));
                 else if (kinds[j] == AGG_MIN) NCCLCHK(g_rccl.AllReduce(t, t, K, ncclInt64, ncclMin, c->nccl, s));
+                else if (kinds[j] == AGG_SUM) NCCLCHK(g_rccl.AllReduce(t, t, K, ncclInt64, ncclSum, c->nccl, s));
             }
         }
         std::vector<unsigned long long> h(words);

@@ -303,6 +303,7 @@ struct imm3_query {
     bool agg_fusable = false;          // the select chain is closed intervals over <= 2 dense int8 / int32 columns of one uniform segment (or empty): the aggregation kernel can evaluate it itself
     uint64_t limit_gather_gave_up = 0; // times settle_rows found k_limit_gather's give-up tag and gathered the rows again with k_scan + k_gather
     int32_t agg_first_form = imm3::AGG_FORM_LANES; // first kernel form to try: raised past the forms this query's keys overflowed
+    int32_t agg_form_ran = -1;         // diagnostics (imm3_query_agg_form): the AggForm the last aggregation launch ran, -1 before any
     // select-only runs: the count reduce goes to ctx->aux, fenced by these events
     hipEvent_t ev_filter_done = nullptr, ev_total_done = nullptr;
     bool total_on_aux = false;

@@ -368,7 +368,7 @@ struct LimitGatherArgs {
 // ---- group-by aggregation (imm3_agg.hip) ----
 constexpr int kMaxGroupCols = 4;
 constexpr int kMaxAggs = 4;
-enum AggKind : int32_t { AGG_COUNT = 0, AGG_MIN = 1, AGG_MAX = 2 };
+enum AggKind : int32_t { AGG_COUNT = 0, AGG_MIN = 1, AGG_MAX = 2, AGG_SUM = 3 }; // SUM: exact int64 over int32 / int8 columns
 // The kernel forms of the aggregation, fastest first (imm3_agg.hip).  A query starts at AGG_FORM_LANES; a form whose
 // per-work-group table cannot hold the query's keys raises the overflow word (3: a lanes form, 2: direct / tile) and the
 // host aggregates again from the next form, remembering it in the query handle.
@@ -429,13 +429,13 @@ struct AggArgs {
     long long *out_vals;
 };
 
-void launch_group_agg(const AggArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+int launch_group_agg(const AggArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // returns the AggForm it launched
 bool group_agg_fuses_select(const AggArgs &a); // would launch_group_agg run a form that evaluates a.fused[] itself (no select launch needed)?
 
 // ---- cross-segment / cross-GPU merge of group tables (ProjectAggregateQueueOp, ProjectAggregateQueue.scala:9-55) ----
 // Keys of <= 2 bytes index a DIRECT table (256 or 65 536 slots; one slot for no group column): every query's dense group
 // list is scattered into it with 64-bit atomics (counts add, first = min of segment << 32 | row, values max / min), and the
-// tables of the ranks then meet in element-wise all-reduces (imm3_comm.cpp).
+// tables of the ranks then meet in element-wise all-reduces (imm3_comm.cpp).  SUM columns add (64-bit atomics, ncclSum).
 struct MergeArgs {
     const unsigned long long *keys;   // one query's dense groups (k_group_collect's output)
     const uint32_t *first;

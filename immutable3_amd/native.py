@@ -49,6 +49,7 @@ DIAG_EXPORTS = [
     "imm3_ctx_timing_enable", "imm3_ctx_timing_reset", "imm3_ctx_timing_mask", "imm3_ctx_timing_collect", "imm3_ctx_set_tuning",
     "imm3_ctx_measure_read_gbps", "imm3_ctx_devclock_enable", "imm3_ctx_devclock_collect", "imm3_ctx_devclock_raw", "imm3_query_plan",
     "imm3_ctx_inject_fault", "imm3_ctx_debug_device_lock", "imm3_plan_predict", "imm3_comm_debug_standin", "imm3_plan_limit_scan",
+    "imm3_query_agg_form",
 ]
 COMM_ID_BYTES = 128
 
@@ -168,6 +169,7 @@ def load() -> C.CDLL:
     L.imm3_ctx_devclock_enable.argtypes = [vp, i32]
     L.imm3_ctx_devclock_collect.argtypes = [vp, vp, i32, P(i32)]
     L.imm3_query_plan.argtypes = [vp, vp, i32]
+    L.imm3_query_agg_form.argtypes = [vp, P(i32)]
     L.imm3_query_agg_shape.argtypes = [vp, P(i32), P(i32), P(i32)]
     L.imm3_ctx_inject_fault.argtypes = [vp, i32, i32, C.c_uint32]
     L.imm3_ctx_debug_device_lock.argtypes = [vp, u64, P(u64)]
@@ -452,7 +454,9 @@ class DeviceSegment:
             pass
 
 
-AGG_COUNT, AGG_MIN, AGG_MAX = 0, 1, 2
+AGG_COUNT, AGG_MIN, AGG_MAX, AGG_SUM = 0, 1, 2, 3
+# the aggregation's kernel forms (csrc/imm3_internal.h: AggForm; DeviceQuery.agg_form, tuning 100 + form)
+AGG_FORM_LANES, AGG_FORM_LANES_WIDE, AGG_FORM_DIRECT, AGG_FORM_TILE, AGG_FORM_GENERAL = 0, 1, 2, 3, 4
 
 
 class DeviceTable:
@@ -621,6 +625,12 @@ class DeviceQuery:
         return {"single_pass": bool(v[0]), "P": int(v[1]), "grid": int(v[2]), "spans": int(v[3]), "records": bool(v[4]),
                 "rec_dwords": int(v[5]), "ran_single_pass": bool(v[6]), "run_syncs": int(v[7]),
                 "abandoned_runs": int(v[8]), "busy_runs": int(v[9]), "limit_gather_gave_up": int(v[10])}
+
+    def agg_form(self) -> int:
+        """The kernel form (AGG_FORM_*) of this aggregation's last launch, -1 before the first (include/imm3_diag.h)."""
+        f = C.c_int32(-1)
+        _check(load().imm3_query_agg_form(self._h, C.byref(f)))
+        return f.value
 
     def device_ptr(self, which: int) -> int:
         p = C.c_void_p()

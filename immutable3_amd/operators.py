@@ -15,6 +15,7 @@ data goes through the C ABI (immutable3_amd/native.py -> libimm3.so); there is n
 """
 from __future__ import annotations
 
+import decimal
 from dataclasses import dataclass
 from typing import Callable, Dict, Iterator, List, Optional, Sequence, Tuple
 
@@ -466,6 +467,38 @@ class MinDoubleAggr(MaxDoubleAggr):  # :50-61
             self.value = float(v)
 
 
+class AvgDoubleAggr(Aggregator):     # :60-75
+    """State (sum, counter).  The reference's sum is a BigDecimal built from Double.toString of each value.toDouble of an Int /
+    Byte: an integer with scale 1, kept here as the exact int (the GPU's int64 SUM).  repr() is java.math.BigDecimal's
+    divide(counter, MathContext.DECIMAL128) -- 34 digits, HALF_EVEN, an exact quotient at the preferred scale 1 -- and its
+    toString (E-notation below an adjusted exponent of -6): Python's decimal implements the same arithmetic."""
+    kind = native.AGG_SUM
+    _DECIMAL128 = decimal.Context(prec=34, rounding=decimal.ROUND_HALF_EVEN)
+
+    def __init__(self, col, alias):
+        super().__init__(col, alias)
+        self.sum = 0
+        self.counter = 0
+
+    def add(self, v):
+        if float(v) != int(v):
+            raise ValueError(f"AvgDoubleAggr sums integral values (value.toDouble of an Int / Byte), got {v!r}")
+        self.sum += int(v)
+        self.counter += 1
+
+    def get(self):
+        return (self.sum, self.counter)
+
+    def combine(self, other):
+        s, c = other.get()
+        self.sum += s
+        self.counter += c
+        return self
+
+    def repr(self):
+        return str(self._DECIMAL128.divide(decimal.Decimal(f"{self.sum}.0"), decimal.Decimal(self.counter)))
+
+
 class MaxStringAggr(Aggregator):     # :79-91
     kind = native.AGG_MAX
 
@@ -572,6 +605,8 @@ class ProjectAggOp(Operator):
                 na = a.make()
                 if isinstance(na, CountAggr):
                     na.set(int(counts[g]))
+                elif isinstance(na, AvgDoubleAggr):  # the group's exact sum; every selected row added once to the counter
+                    na.sum, na.counter = int(vals[g, j]), int(counts[g])
                 elif isinstance(na, MaxStringAggr):
                     w = scan.cols[colnames.index(a.col)].width
                     na.value = int(vals[g, j]).to_bytes(8, "big", signed=True)[8 - w:].decode("utf-8", errors="replace")

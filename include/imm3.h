@@ -159,7 +159,7 @@ int imm3_segment_wait(imm3_segment *seg);
 int imm3_segment_destroy(imm3_segment *seg);
 int imm3_segment_bytes(const imm3_segment *seg, uint64_t *device_bytes);
 
-enum { IMM3_AGG_COUNT = 0, IMM3_AGG_MIN = 1, IMM3_AGG_MAX = 2 };
+enum { IMM3_AGG_COUNT = 0, IMM3_AGG_MIN = 1, IMM3_AGG_MAX = 2, IMM3_AGG_SUM = 3 };
 typedef struct {
     int32_t kind;
     int32_t column;
@@ -213,10 +213,13 @@ int imm3_query_create(imm3_ctx *ctx, const imm3_segment *seg,
 int imm3_query_destroy(imm3_query *q);
 
 /* ---- group-by aggregation: ProjectAggOp (engine/.../operator/ProjectAggregate.scala:115-227) over the rows the
- * SelectOps keep.  CountAggr / MinDoubleAggr / MaxDoubleAggr / MaxStringAggr (:22-112).
+ * SelectOps keep.  CountAggr / MinDoubleAggr / MaxDoubleAggr / MaxStringAggr (:22-112), and the sum that AvgDoubleAggr
+ * (:60-75) divides by its counter (the group's count).
  *   group_cols  indices into used_cols, in the order their values are joined into the group key (the reference
  *               joins them in batch-column order with "_", :151-156); total width <= 8 bytes on this path
- *   aggs        {kind, column (index into used_cols)}; MIN/MAX on INT/TINYINT, MAX on STRING (<= 8 bytes), COUNT on any
+ *   aggs        {kind, column (index into used_cols)}; MIN/MAX/SUM on INT/TINYINT (PFOR_INT included), MAX on STRING
+ *               (<= 8 bytes), COUNT on any.  MIN or SUM on a STRING column: IMM3_ERR_UNSUPPORTED_VECTOR "bad aggregator for
+ *               this data type" iff the segment has >= 1 batch (:205-214)
  * Groups come back in first-seen order (the reference's LinkedHashMap order): ascending first selected row. ---- */
 int imm3_query_create_agg(imm3_ctx *ctx, const imm3_segment *seg,
                           const int32_t *used_cols, int32_t n_used,
@@ -231,7 +234,8 @@ int imm3_query_group_count(imm3_query *q, uint32_t *n_groups);
 int imm3_query_agg_shape(const imm3_query *q, int32_t *n_group_cols, int32_t *n_aggs, int32_t *key_bytes);
 /* keys: the group columns' raw bytes packed little-endian in group_cols order; first_row: lowest selected row of
  * the group; counts: selected rows of the group; vals[g * n_aggs + j]: COUNT -> the count, MIN/MAX numeric -> the
- * int32 value sign-extended, MAX string -> the value's bytes packed big-endian.  Sorted by first_row. */
+ * int32 value sign-extended, SUM -> the exact int64 sum of the group's selected values (<= 2^32 rows x 2^31: no
+ * overflow), MAX string -> the value's bytes packed big-endian.  Sorted by first_row. */
 int imm3_query_fetch_groups(imm3_query *q, uint64_t *keys, uint32_t *first_row, uint64_t *counts, int64_t *vals,
                             uint32_t max_groups);
 

@@ -76,6 +76,11 @@ int imm3_plan_predict(int64_t n_rows, const int32_t *pred_width, const int32_t *
  * gathered the rows again with k_scan + k_gather.  n <= 11 values. */
 int imm3_query_plan(const imm3_query *q, int64_t *out, int32_t n);
 
+/* imm3_query_agg_form: the kernel form of an aggregation's last launch (csrc/imm3_internal.h's AggForm: 0 = lanes (63 keys), 1 = lanes
+ * (127 keys), 2 = direct, 3 = tile, 4 = general), after any re-run from a later form that a full per-work-group table forced; -1
+ * before the first run.  IMM3_ERR_ARG for a query that is not an aggregation. */
+int imm3_query_agg_form(const imm3_query *q, int32_t *form);
+
 /* ---- fault injection into the single-pass projection kernel (k_filter_project, csrc/imm3_project.hip) ----
  * The kernel's work-groups wait on each other; what happens when such a wait does not resolve must be exercised on a device.
  * imm3_ctx_inject_fault: in every later single-pass launch of this context, work-group `work_group` never announces its

@@ -1,0 +1,471 @@
+"""GPU suite: the exact int64 SUM of the group-by aggregation (IMM3_AGG_SUM: the sum that AvgDoubleAggr divides by its counter,
+ProjectAggregate.scala:60-75) in every kernel form, in the merges and at the operator level.  Expectations come from numpy:
+np.unique (first-seen order) and np.add.at in int64 -- oracle_np.project_agg knows no SUM."""
+import os
+import subprocess
+import sys
+from decimal import ROUND_HALF_EVEN, Context, Decimal
+
+import numpy as np
+import pytest
+
+from conftest import DENSE_INT, DENSE_STRING, DENSE_TINYINT, GT, LT, PforColumn, RawColumn, blocks_of
+from immutable3_amd import native, synth
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+CODES = [b"CA", b"NY", b"TX", b"WA", b"VA", b"DC", b"CT"]
+C, MN, MX, S = native.AGG_COUNT, native.AGG_MIN, native.AGG_MAX, native.AGG_SUM
+FORMS = [native.AGG_FORM_LANES, native.AGG_FORM_LANES_WIDE, native.AGG_FORM_DIRECT, native.AGG_FORM_TILE, native.AGG_FORM_GENERAL]
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = native.Context(0)
+    yield c
+    c.close()
+
+
+def raw_of(col):
+    """the column's values as the unsigned little-endian integers the group key packs"""
+    if col.codec == DENSE_STRING:
+        return col.values[:, 0].astype(np.uint64) | (col.values[:, 1].astype(np.uint64) << np.uint64(8))
+    return np.ascontiguousarray(col.values).view({1: np.uint8, 4: np.uint32}[col.width]).astype(np.uint64)
+
+
+def expect(cols, group, aggs, mask):
+    """(keys, first, counts, vals[g, j]) in first-seen order; vals: SUM exact int64, MIN / MAX, COUNT the count"""
+    key = np.zeros(mask.size, np.uint64)
+    shift = 0
+    for g in group:
+        key |= raw_of(cols[g]) << np.uint64(8 * shift)
+        shift += cols[g].width
+    sel = np.flatnonzero(mask)
+    uniq, idx, inv = np.unique(key[sel], return_index=True, return_inverse=True)
+    inv = inv.reshape(-1)
+    order = np.argsort(idx, kind="stable")
+    counts = np.bincount(inv, minlength=uniq.size).astype(np.int64)
+    vals = np.zeros((uniq.size, len(aggs)), np.int64)
+    for j, (kind, c) in enumerate(aggs):
+        v = np.asarray(cols[c].values, dtype=np.int64)[sel]
+        col = np.zeros(uniq.size, np.int64)
+        if kind == S:
+            np.add.at(col, inv, v)
+        elif kind == MX:
+            col[:] = np.iinfo(np.int64).min
+            np.maximum.at(col, inv, v)
+        elif kind == MN:
+            col[:] = np.iinfo(np.int64).max
+            np.minimum.at(col, inv, v)
+        else:
+            col = counts.copy()
+        vals[:, j] = col
+    return uniq[order], sel[idx[order]], counts[order], vals[order]
+
+
+def run_query(ctx, seg, used, sels, group, aggs, form=None, tuning=None):
+    """-> (form that ran, keys, first, counts, vals); form: the chain starts there (tuning 100 + form)"""
+    ctx.set_tuning(tuning if tuning is not None else (100 + form if form is not None else 0), 0)
+    try:
+        q = native.DeviceQuery(ctx, seg, used, sels, (), 0, 1024, group_cols=group, aggs=aggs)
+        q.run()
+        keys, first, counts, vals = q.fetch_groups()
+        ran = q.agg_form()
+        q.close()
+    finally:
+        ctx.set_tuning(0, 0)
+    return ran, keys, first, counts, vals
+
+
+def assert_same(got, want, what=None):
+    keys, first, counts, vals = got
+    wk, wf, wc, wv = want
+    assert keys.tolist() == wk.tolist(), what
+    assert first.tolist() == wf.tolist(), what
+    assert counts.tolist() == wc.tolist(), what
+    assert vals.tolist() == wv.tolist(), what
+
+
+def fallback(form, widths, aggs, cols):
+    """the form the planner lands on when the chain starts at `form` (imm3_agg.hip: launch_group_agg) for group columns of these
+    widths: the lanes forms take one 1- or 2-byte key column or two 1-byte ones and a sum as the one value aggregate, the direct form
+    keys of <= 2 bytes, the tile form int8 sums only"""
+    n_val = sum(1 for k, _ in aggs if k != C)
+    sums = [cols[c].width for k, c in aggs if k == S]
+    group_bytes = sum(widths)
+    if form <= native.AGG_FORM_LANES_WIDE:
+        if list(widths) in ([1], [2], [1, 1]) and n_val == 1:
+            return form
+        form = native.AGG_FORM_DIRECT
+    if form == native.AGG_FORM_DIRECT:
+        if group_bytes <= 2:
+            return form
+        form = native.AGG_FORM_TILE
+    if form == native.AGG_FORM_TILE and all(w == 1 for w in sums):
+        return form
+    return native.AGG_FORM_GENERAL
+
+
+# ---- random data: id int32, age int8, state 2-byte string, k8 int8 of 5 keys, k32 int32 of 40 keys ------------------------
+N = 300_000 + 77
+
+
+@pytest.fixture(scope="module")
+def data(ctx):
+    rng = np.random.default_rng(2024)
+    br = blocks_of(N, 1024)
+    cols = [RawColumn(DENSE_INT, 4, rng.integers(-2 ** 31, 2 ** 31, size=N).astype(np.int32), br),
+            RawColumn(DENSE_TINYINT, 1, rng.integers(-128, 128, size=N).astype(np.int8), br),
+            RawColumn(DENSE_STRING, 2, np.array([list(CODES[i]) for i in rng.integers(0, 7, size=N)], np.uint8), br),
+            RawColumn(DENSE_TINYINT, 1, rng.integers(-3, 2, size=N).astype(np.int8), br),
+            RawColumn(DENSE_INT, 4, rng.integers(0, 40, size=N).astype(np.int32) * 1000, br)]
+    seg = native.DeviceSegment(ctx, [c.native() for c in cols])
+    yield cols, seg
+    seg.close()
+
+
+SHAPES = [([3], [(S, 1)]), ([3], [(C, 0), (S, 0)]), ([2], [(S, 1), (C, 2)]), ([2], [(C, 0), (S, 0)]),   # 1- and 2-byte keys
+          ([3, 1], [(S, 0)]), ([1, 3], [(C, 1), (S, 1)]),                                      # two 1-byte columns (~1280 keys)
+          ([3, 2], [(C, 0), (S, 0), (MN, 1)]), ([2], [(C, 0), (S, 1), (MX, 0), (MN, 1)]),      # beside min / max
+          ([4], [(S, 1), (S, 0)]), ([], [(S, 0), (C, 2)])]                                     # a 4-byte key; no group column
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_sum_in_every_form_random(ctx, data, form):
+    cols, seg = data
+    for group, aggs in SHAPES:
+        want = expect(cols, group, aggs, np.ones(N, bool))
+        ran, *got = run_query(ctx, seg, [0, 1, 2, 3, 4], [], group, aggs, form=form)
+        widths = [cols[g].width for g in group]
+        # (a form whose per-work-group table overflows on these keys -- 1280 keys in a lanes form -- re-runs from a later one)
+        assert ran >= fallback(form, widths, aggs, cols), (form, group, aggs, ran)
+        if len(group) < 2:
+            assert ran == fallback(form, widths, aggs, cols), (form, group, aggs, ran)
+        assert_same(got, want, (form, group, aggs))
+
+
+def test_planner_picks_the_lanes_form_for_a_sum(ctx, data):
+    cols, seg = data
+    for aggs in ([(C, 0), (S, 1)], [(S, 0)], [(C, 1), (S, 0)]):
+        ran, *got = run_query(ctx, seg, [0, 1, 2, 3, 4], [], [2], aggs)
+        assert ran == native.AGG_FORM_LANES
+        assert_same(got, expect(cols, [2], aggs, np.ones(N, bool)))
+    # two value aggregates with a sum among them: not a lanes form, still exact
+    ran, *got = run_query(ctx, seg, [0, 1, 2, 3, 4], [], [2], [(S, 1), (MX, 1)])
+    assert ran == native.AGG_FORM_DIRECT
+    assert_same(got, expect(cols, [2], [(S, 1), (MX, 1)], np.ones(N, bool)))
+
+
+# ---- extremes: one group, every row the same extreme value, more rows than any 32-bit partial could hold ------------------
+NX = (1 << 24) + (1 << 20)   # 17.8 M rows: 255 x NX > 2^32 (a biased int8 partial), 127 x NX > 2^31
+
+
+@pytest.fixture(scope="module")
+def extremes(ctx):
+    br = blocks_of(NX, 1024)
+    cols = [RawColumn(DENSE_TINYINT, 1, np.zeros(NX, np.int8), br),
+            RawColumn(DENSE_TINYINT, 1, np.full(NX, 127, np.int8), br), RawColumn(DENSE_TINYINT, 1, np.full(NX, -128, np.int8), br),
+            RawColumn(DENSE_INT, 4, np.full(NX, 2 ** 31 - 1, np.int32), br), RawColumn(DENSE_INT, 4, np.full(NX, -2 ** 31, np.int32), br)]
+    seg = native.DeviceSegment(ctx, [c.native() for c in cols])
+    yield cols, seg
+    seg.close()
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_sum_extremes_never_wrap(ctx, extremes, form):
+    cols, seg = extremes
+    for c, v in ((1, 127), (2, -128), (3, 2 ** 31 - 1), (4, -2 ** 31)):
+        for aggs in ([(C, 0), (S, c)], [(S, c)]):
+            ran, keys, first, counts, vals = run_query(ctx, seg, [0, 1, 2, 3, 4], [], [0], aggs, form=form)
+            assert ran == fallback(form, [1], aggs, cols), (form, c, ran)
+            assert keys.tolist() == [0] and first.tolist() == [0] and counts.tolist() == [NX]
+            assert int(vals[0, len(aggs) - 1]) == NX * v, (form, c, int(vals[0, -1]), NX * v)
+    # behind a select chain: in the 63-key lanes form the fused instances (default) and the select launch (tuning 17)
+    for c, v in ((1, 127), (2, -128), (3, 2 ** 31 - 1), (4, -2 ** 31)):
+        sels = [(c, GT, float(v) - 1.0)] if v > 0 else [(c, LT, float(v) + 1.0)]
+        for tuning in ((0, 17) if form == native.AGG_FORM_LANES else (100 + form,)):
+            ran, keys, first, counts, vals = run_query(ctx, seg, [0, 1, 2, 3, 4], sels, [0], [(C, 0), (S, c)], tuning=tuning)
+            assert ran == fallback(form, [1], [(C, 0), (S, c)], cols)
+            assert counts.tolist() == [NX] and int(vals[0, 1]) == NX * v, (form, c, tuning)
+
+
+# ---- select chains: the fused lanes instances (default) and the separate select launch (tuning 17) ------------------------
+@pytest.mark.parametrize("tuning", [0, 17])
+def test_sum_with_select_chains(ctx, data, tuning):
+    cols, seg = data
+    age, ids = cols[1].values, cols[0].values
+    cases = [([(1, GT, 18.0), (1, LT, 30.0)], [(C, 0), (S, 1)], (age > 18) & (age < 30)),         # predicate on the summed column
+             ([(1, GT, 18.0), (1, LT, 30.0)], [(C, 0), (S, 0)], (age > 18) & (age < 30)),         # on another (int8) column
+             ([(0, GT, 0.0)], [(S, 0), (C, 1)], ids > 0),                                         # on the summed int32 column
+             ([(0, LT, -2.0e9), (1, GT, 100.0)], [(C, 0), (S, 1)], (ids < -2_000_000_000) & (age > 100))]
+    for sels, aggs, mask in cases:
+        ran, *got = run_query(ctx, seg, [0, 1, 2, 3, 4], sels, [2], aggs, tuning=tuning)
+        assert ran == native.AGG_FORM_LANES
+        assert_same(got, expect(cols, [2], aggs, mask), (sels, aggs))
+
+
+# ---- PFOR_INT and ragged segments -------------------------------------------------------------------------------------------
+def test_sum_over_pfor_and_ragged_segments(ctx):
+    rng = np.random.default_rng(5)
+    n = 150_001
+    br = blocks_of(n, 1024)
+    vals = rng.integers(-2 ** 31, 2 ** 31, size=n).astype(np.int32)
+    small = rng.integers(0, 1000, size=n).astype(np.int32)
+    st = np.array([list(CODES[i]) for i in rng.integers(0, 7, size=n)], np.uint8)
+    cols = [PforColumn(vals, br), PforColumn(small, br), RawColumn(DENSE_STRING, 2, st, br)]
+    seg = native.DeviceSegment(ctx, [c.native() for c in cols])
+    aggs = [(C, 0), (S, 0), (S, 1)]
+    for sels, mask in (([], np.ones(n, bool)), ([(1, GT, 499.0)], small > 499)):
+        for form in (None, native.AGG_FORM_GENERAL):
+            ran, *got = run_query(ctx, seg, [0, 1, 2], sels, [2], aggs, form=form)
+            assert_same(got, expect(cols, [2], aggs, mask), (sels, form))
+        ran, *got = run_query(ctx, seg, [0, 1, 2], sels, [2], [(C, 0), (S, 1)])   # one sum of a PFOR_INT column: a lanes form
+        assert ran == native.AGG_FORM_LANES
+        assert_same(got, expect(cols, [2], [(C, 0), (S, 1)], mask), sels)
+    seg.close()
+    # ragged layout: non-final blocks that are not multiples of 64 rows (the general kernel's per-word row bases)
+    br = [1000, 777, 3001] * 20 + [5]
+    n = sum(br)
+    cols = [RawColumn(DENSE_INT, 4, rng.integers(-2 ** 31, 2 ** 31, size=n).astype(np.int32), br),
+            RawColumn(DENSE_TINYINT, 1, rng.integers(-128, 128, size=n).astype(np.int8), br),
+            RawColumn(DENSE_STRING, 2, np.array([list(CODES[i]) for i in rng.integers(0, 7, size=n)], np.uint8), br)]
+    seg = native.DeviceSegment(ctx, [c.native() for c in cols])
+    aggs = [(S, 0), (C, 0), (S, 1)]
+    for sels, mask in (([], np.ones(n, bool)), ([(1, GT, 0.0)], cols[1].values > 0)):
+        ran, *got = run_query(ctx, seg, [0, 1, 2], sels, [2], aggs)
+        assert ran == native.AGG_FORM_GENERAL
+        assert_same(got, expect(cols, [2], aggs, mask), sels)
+    seg.close()
+
+
+# ---- table flavour: one query over several segments, groups spanning their boundaries ---------------------------------------
+def seg_cols(rng, n):
+    br = blocks_of(n, 1024)
+    return [RawColumn(DENSE_INT, 4, rng.integers(-2 ** 31, 2 ** 31, size=n).astype(np.int32), br),
+            RawColumn(DENSE_TINYINT, 1, rng.integers(-128, 128, size=n).astype(np.int8), br),
+            RawColumn(DENSE_STRING, 2, np.array([list(CODES[i]) for i in rng.integers(0, 7, size=n)], np.uint8), br)]
+
+
+def concat(per):
+    return [RawColumn(c.codec, c.width, np.concatenate([p[i].values for p in per]), [1]) for i, c in enumerate(per[0])]
+
+
+def test_sum_table_query_over_segments(ctx):
+    rng = np.random.default_rng(9)
+    sizes = [70_000, 1024, 33_333, 90_000, 5_000]
+    per = [seg_cols(rng, n) for n in sizes]
+    segs = [native.DeviceSegment(ctx, [c.native() for c in cols]) for cols in per]
+    cat = concat(per)
+    table = native.DeviceTable(ctx, segs)
+    age = cat[1].values
+    for group, aggs in (([2], [(C, 0), (S, 1)]), ([2], [(S, 0), (MX, 1)]), ([1], [(S, 0), (C, 2)]), ([], [(S, 0), (S, 1)])):
+        for sels, mask in (([], np.ones(age.size, bool)), ([(1, GT, 18.0), (1, LT, 30.0)], (age > 18) & (age < 30))):
+            wk, _, wc, wv = expect(cat, group, aggs, mask)
+            ran, keys, first, counts, vals = run_query(ctx, table, [0, 1, 2], sels, group, aggs)
+            assert keys.tolist() == wk.tolist() and counts.tolist() == wc.tolist() and vals.tolist() == wv.tolist(), (group, aggs, sels)
+    table.close()
+    for s in segs:
+        s.close()
+
+
+# ---- merges --------------------------------------------------------------------------------------------------------------
+def test_sum_merge_of_segment_queries(ctx):
+    rng = np.random.default_rng(13)
+    per = []
+    for n in (70_000, 1, 33_333, 120_000):
+        cols = seg_cols(rng, n)
+        cols[2] = RawColumn(DENSE_INT, 4, rng.integers(0, 3000, size=n).astype(np.int32) * 7, blocks_of(n, 1024))  # a wide key
+        per.append(cols)
+    segs = [native.DeviceSegment(ctx, [c.native() for c in cols]) for cols in per]
+    cat = concat(per)
+    aggs = [(C, 0), (S, 0), (S, 1), (MN, 0)]
+    for group in ([1], [2]):                                   # narrow key: direct merge table; wide key: hash merge table
+        queries = []
+        for s in segs:
+            q = native.DeviceQuery(ctx, s, [0, 1, 2], [], (), 0, 1024, group_cols=group, aggs=aggs)
+            q.run()
+            queries.append(q)
+        wk, _, wc, wv = expect(cat, group, aggs, np.ones(cat[0].values.size, bool))
+        (c0,) = native.Comm.create_all([ctx])
+        keys, first, counts, vals = native.Comm.merge_groups_all([c0], [queries], [[0, 1, 2, 3]])
+        assert keys.tolist() == wk.tolist() and counts.tolist() == wc.tolist() and vals.tolist() == wv.tolist(), group
+        c0.close()
+        comm = native.Comm(ctx, 1, 0, native.comm_unique_id())
+        k2, f2, n2, v2 = comm.merge_groups(queries, [0, 1, 2, 3])
+        assert k2.tolist() == wk.tolist() and v2.tolist() == wv.tolist(), group
+        comm.close()
+        for q in queries:
+            q.close()
+    for s in segs:
+        s.close()
+
+
+LOOPBACK_WORKER = r'''
+import sys, threading
+import numpy as np
+import torch  # noqa: F401  (its HIP runtime first: conftest.py says why)
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+from conftest import DENSE_INT, DENSE_TINYINT, RawColumn, blocks_of
+from immutable3_amd import native
+
+WORLD = 2
+ctxs = [native.Context(0) for _ in range(WORLD)]
+uid = native.comm_unique_id()
+comms = [None] * WORLD
+
+def both(fn):
+    out, err = [None] * WORLD, [None] * WORLD
+    def run(r):
+        try:
+            out[r] = fn(r)
+        except BaseException as e:      # noqa: BLE001
+            err[r] = e
+    ts = [threading.Thread(target=run, args=(r,)) for r in range(WORLD)]
+    for t in ts: t.start()
+    for t in ts: t.join(120)
+    assert not any(t.is_alive() for t in ts), "a rank is stuck in a collective"
+    return out, err
+
+def mk(r):
+    comms[r] = native.Comm(ctxs[r], WORLD, r, uid)
+out, err = both(mk)
+assert err == [None, None], err
+rng = np.random.default_rng(21)
+rows = [70_000, 50_001, 1024, 33_333]
+cols = []
+for n in rows:
+    br = blocks_of(n, 1024)
+    cols.append([RawColumn(DENSE_TINYINT, 1, rng.integers(-20, 20, size=n).astype(np.int8), br),
+                 RawColumn(DENSE_INT, 4, rng.integers(0, 3000, size=n).astype(np.int32) * 7, br),
+                 RawColumn(DENSE_INT, 4, rng.integers(-2 ** 31, 2 ** 31, size=n).astype(np.int32), br)])
+owner = [s % WORLD for s in range(len(rows))]
+segs = [native.DeviceSegment(ctxs[owner[s]], [c.native() for c in cols[s]]) for s in range(len(rows))]
+aggs = [(native.AGG_COUNT, 2), (native.AGG_SUM, 2), (native.AGG_SUM, 0)]
+for group in ([0], [1]):                   # narrow key: all-reduces (ncclSum on int64); wide key: all-gathered lists
+    key = np.concatenate([c[group[0]].values.astype(np.int64) for c in cols])
+    v2 = np.concatenate([c[2].values.astype(np.int64) for c in cols])
+    v0 = np.concatenate([c[0].values.astype(np.int64) for c in cols])
+    uniq, idx, inv = np.unique(key, return_index=True, return_inverse=True)
+    inv = inv.reshape(-1)
+    order = np.argsort(idx, kind="stable")
+    s2 = np.zeros(uniq.size, np.int64); np.add.at(s2, inv, v2)
+    s0 = np.zeros(uniq.size, np.int64); np.add.at(s0, inv, v0)
+    cnt = np.bincount(inv, minlength=uniq.size)
+    want = [[int(cnt[g]), int(s2[g]), int(s0[g])] for g in order]
+    queries, seg_idx = [[], []], [[], []]
+    for s in range(len(rows)):
+        q = native.DeviceQuery(ctxs[owner[s]], segs[s], [0, 1, 2], [], (), 0, 1024, group_cols=group, aggs=aggs)
+        q.run()
+        queries[owner[s]].append(q)
+        seg_idx[owner[s]].append(s)
+    out, err = both(lambda r: comms[r].merge_groups(queries[r], seg_idx[r]))
+    assert err == [None, None], err
+    for r in range(WORLD):
+        keys, first, counts, vals = out[r]
+        assert vals.tolist() == want, ("rank", r, group)
+    print("sum merge ok", group, len(want), flush=True)
+    for qs in queries:
+        for q in qs:
+            q.close()
+for c in comms: c.close()
+for s in segs: s.close()
+for c in ctxs: c.close()
+print("LOOPBACK-SUM-OK", flush=True)
+'''
+
+
+def test_sum_merge_of_two_ranks_over_the_loopback_transport(tmp_path):
+    """Two ranks (threads, one context each on device 0) through tests/native/loopback_rccl.cpp, as test_gpu_comm_loopback.py does."""
+    lib = tmp_path / "libloopback_rccl.so"
+    src = os.path.join(ROOT, "tests", "native", "loopback_rccl.cpp")
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "hip", "--offload-arch=gfx950", src, "-o", str(lib)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    script = tmp_path / "loopback_sum_worker.py"
+    script.write_text(LOOPBACK_WORKER)
+    env = dict(os.environ, IMM3_RCCL_LIB=str(lib))
+    r = subprocess.run([sys.executable, str(script), ROOT], env=env, capture_output=True, text=True, timeout=900)
+    sys.stdout.write(r.stdout[-4000:])
+    sys.stderr.write(r.stderr[-4000:])
+    assert r.returncode == 0 and "LOOPBACK-SUM-OK" in r.stdout
+
+
+# ---- graph capture ---------------------------------------------------------------------------------------------------------
+def test_sum_query_in_a_graph(ctx, data):
+    cols, seg = data
+    aggs = [(C, 0), (S, 0), (S, 1)]
+    want = expect(cols, [2], aggs, (cols[1].values > 18) & (cols[1].values < 30))
+    q = native.DeviceQuery(ctx, seg, [0, 1, 2, 3, 4], [(1, GT, 18.0), (1, LT, 30.0)], (), 0, 1024, group_cols=[2], aggs=aggs)
+    q.run()
+    assert_same(q.fetch_groups(), want)
+    with ctx.capture() as cap:
+        q.run()
+    for _ in range(2):
+        cap.graph.launch()
+        assert_same(q.fetch_groups(), want)
+    cap.graph.close()
+    q.close()
+
+
+# ---- operator level: ProjectAggOp with AvgDoubleAggr over the quirk_25 table on disk -----------------------------------------
+def java_avg(s, n):
+    return str(Context(prec=34, rounding=ROUND_HALF_EVEN).divide(Decimal(f"{s}.0"), Decimal(n)))
+
+
+def test_project_agg_op_avg_over_quirk_25():
+    from immutable3_amd.operators import AvgDoubleAggr, CountAggr, GpuSegmentManager, ProjectAggOp, ScanOp, SelectOp
+    from immutable3_amd.query import GT as QGT
+    from immutable3_amd.storage import SegmentManager
+    gsm = GpuSegmentManager(SegmentManager(GOLDEN))
+    t = gsm.getTable("quirk_25")
+    combined, all_rows = {}, []
+    for s in range(3):
+        ids = [int(v) for b in ScanOp(gsm, s, "quirk_25", [t.getColumn("id")]).iterator() for v in b.columnVectors[0].data[: b.size]]
+        rows = [(i, synth.CODES7[i % 7], (i * 5) % 11 - 5) for i in ids if i > 2]   # quirk_25: state CODES7[id % 7], age (id * 5) % 11 - 5
+        all_rows += rows
+        scan = ScanOp(gsm, s, "quirk_25", [t.getColumn("age"), t.getColumn("id"), t.getColumn("state")])
+        op = ProjectAggOp([AvgDoubleAggr("age", "age_avg"), CountAggr("id", "id_count")], SelectOp("id", QGT(2), scan), ["state"])
+        got = list(op.iterator())
+        order = []
+        for _, st, _ in rows:
+            if st not in order:
+                order.append(st)
+        assert [k for k, _ in got] == order
+        for k, aggs in got:
+            ages = [a for _, st, a in rows if st == k]
+            assert aggs["age_avg"].get() == (sum(ages), len(ages))
+            assert aggs["age_avg"].repr() == java_avg(sum(ages), len(ages))
+            assert aggs["id_count"].repr() == str(len(ages))
+            if k in combined:                                    # ProjectAggregateQueueOp: combine by key, first arrival first
+                for alias in aggs:
+                    combined[k][alias].combine(aggs[alias])
+            else:
+                combined[k] = aggs
+    assert len(all_rows) == 22
+    for k, aggs in combined.items():
+        ages = [a for _, st, a in all_rows if st == k]
+        assert aggs["age_avg"].get() == (sum(ages), len(ages))
+        assert aggs["age_avg"].repr() == java_avg(sum(ages), len(ages))
+        assert aggs["id_count"].get() == len(ages)
+    gsm.close()
+
+
+# ---- errors --------------------------------------------------------------------------------------------------------------
+def test_sum_errors(ctx, data):
+    cols, seg = data
+    with pytest.raises(native.Imm3Error) as e:
+        native.DeviceQuery(ctx, seg, [0, 1, 2], [], (), 0, 1024, group_cols=[0], aggs=[(S, 2)])
+    assert e.value.code == native.ERR_UNSUPPORTED_VECTOR and "bad aggregator for this data type" in str(e.value)
+    with pytest.raises(native.Imm3Error) as e:
+        native.DeviceQuery(ctx, seg, [0, 1, 2], [], (), 0, 1024, group_cols=[0], aggs=[(4, 0)])
+    assert e.value.code == native.ERR_ARG and "Unknown Aggregate type" in str(e.value)
+    # the Engine (Engine.resolveProjectOp, Engine.scala:130-156) still rejects Sum and Avg
+    from immutable3_amd import Avg, NoSelect, ProjectAgg, Query, Sum
+    from immutable3_amd.operators import Engine, GpuSegmentManager
+    from immutable3_amd.storage import SegmentManager
+    g = GpuSegmentManager(SegmentManager(GOLDEN))
+    for agg in (Sum("id"), Avg("age")):
+        with pytest.raises(Exception, match="Unknown Aggregate type"):
+            Engine(g).execute_agg(Query("quirk_25", NoSelect, ProjectAgg([agg], ["state"])))
+    g.close()
