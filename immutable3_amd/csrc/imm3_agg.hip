@@ -154,6 +154,48 @@ __device__ __forceinline__ void agg_fold(const AggArgs &a, const LdsTable &t, co
     }
 }
 
+// ---- string MAX wider than 8 bytes (AggCol::alive / chunks) ----
+// n (1 .. 8) bytes at p packed big-endian: integer order == byte-lexicographic order
+__device__ __forceinline__ unsigned long long be_bytes(const uint8_t *p, int n) {
+    if (n == 8 && ((uintptr_t)p & 7u) == 0) return __builtin_bswap64(*(const unsigned long long *)p);
+    unsigned long long v = 0;
+    for (int b = 0; b < n; ++b) v = (v << 8) | p[b];
+    return v;
+}
+
+// the bytes of virtual row `row` of a column (table queries: through the tile table)
+__device__ __forceinline__ const uint8_t *row_ptr(const void *data, const void *const *tile_ptrs, int64_t row, int width) {
+    if (tile_ptrs) return (const uint8_t *)as_global(tile_ptrs[row / kTileRows]) + (row % kTileRows) * (int64_t)width;
+    return (const uint8_t *)data + row * (int64_t)width;
+}
+
+// Fold the first 8 bytes of a wide string MAX into the row's group.  True when the row may hold the group's maximum: its prefix
+// is >= the running maximum it met there, and a running maximum never exceeds the final one -- so every row whose prefix equals
+// the final maximum is marked (and, with distinct prefixes, few others: the records of each work-group's row order).
+__device__ __forceinline__ bool agg_fold_prefix(const AggArgs &a, const LdsTable &t, const GroupRef &r, int j, unsigned long long v) {
+    if (r.slot >= 0) {
+        unsigned long long *p = (unsigned long long *)&t.vals[r.slot * kMaxAggs + j];
+        const unsigned long long cur = *p;
+        if (v > cur) atomicMax(p, v);
+        return v >= cur;
+    }
+    if (r.gslot == 0xFFFFFFFFu) return false;
+    return v >= atomicMax((unsigned long long *)&a.vals[(size_t)r.gslot * kMaxAggs + j], v);
+}
+
+// the slot of a key the aggregation launch has placed in the global table (read only); 0xFFFFFFFF: not there
+__device__ __forceinline__ uint32_t find_slot(const AggArgs &a, unsigned long long key) {
+    if (key == kEmptyKey) return a.mask + 1;
+    uint32_t g = hash_key(key) & a.mask;
+    for (uint32_t probes = 0; probes <= a.mask; ++probes) {
+        const unsigned long long cur = a.keys[g];
+        if (cur == key) return g;
+        if (cur == kEmptyKey) break;
+        g = (g + 1) & a.mask;
+    }
+    return 0xFFFFFFFFu;
+}
+
 __device__ __forceinline__ unsigned long long row_key(const AggArgs &a, int64_t row) {
     unsigned long long key = 0;
     for (int g = 0; g < a.n_group; ++g) key |= load_le(a.groups[g].data, row, a.groups[g].width) << (8 * a.groups[g].shift);
@@ -213,6 +255,9 @@ __device__ __forceinline__ long long agg_from_raw(const AggCol &a, unsigned long
 // Uniform layout: one wave step = 4 consecutive bitmap words = 256 rows; lane l owns rows 4l .. 4l+3 of the step
 // (bits = nibble l&15 of word l>>4) and loads them with one >= 4-byte load per column.  Steps without a survivor are
 // skipped before any column load.  Ragged layout: lane l <-> row base(word) + l, one word per step.
+// WIDE: the query has a string MAX wider than 8 bytes -- its prefix pass (the first 8 bytes of the selected rows only: 4 rows of a
+// wide column may reach past the column's slack), which also writes the rows that may hold the maximum into AggCol::alive.
+template <bool WIDE>
 __global__ __launch_bounds__(kAggThreads) void k_group_agg(const AggArgs a) {
     __shared__ unsigned long long s_keys[kLdsSlots + 1];      // 8 KiB
     __shared__ uint32_t s_first[kLdsSlots + 1];               // 4 KiB
@@ -268,6 +313,27 @@ __global__ __launch_bounds__(kAggThreads) void k_group_agg(const AggArgs a) {
             // then every aggregate column: one load for the 4 rows, fold, next column
             for (int q = 0; q < a.n_agg; ++q) {
                 if (a.aggs[q].kind == AGG_COUNT) continue;
+                if (WIDE && a.aggs[q].alive) {
+                    const int wd = a.aggs[q].width;
+                    uint32_t cand = 0; // bit k: row0 + k may hold its group's maximum
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if ((nib >> k) & 1u) {
+                            const uint8_t *p = a.aggs[q].tile_ptrs ? (const uint8_t *)as_global(a.aggs[q].tile_ptrs[tile]) + (in_tile + k) * (int64_t)wd
+                                                                  : (const uint8_t *)a.aggs[q].data + (row0 + k) * (int64_t)wd;
+                            if (agg_fold_prefix(a, tab, ref[k], q, be_bytes(p, 8))) cand |= 1u << k;
+                        }
+                    // the 16 lanes of one bitmap word OR their nibbles together; the word's first lane stores it
+                    const int sh = 4 * (lane & 7);
+                    uint32_t lo = (lane & 8) ? 0u : cand << sh, hi = (lane & 8) ? cand << sh : 0u;
+#pragma unroll
+                    for (int d = 1; d < 16; d <<= 1) {
+                        lo |= (uint32_t)__shfl_xor((int)lo, d);
+                        hi |= (uint32_t)__shfl_xor((int)hi, d);
+                    }
+                    if ((lane & 15) == 0 && (lo | hi) && w < a.n_words) a.aggs[q].alive[w] = ((uint64_t)hi << 32) | lo;
+                    continue;
+                }
                 unsigned long long raw[4];
                 if (a.aggs[q].tile_ptrs) load4_raw(as_global(a.aggs[q].tile_ptrs[tile]), in_tile, a.aggs[q].width, raw);
                 else load4_raw(a.aggs[q].data, row0, a.aggs[q].width, raw);
@@ -280,11 +346,22 @@ __global__ __launch_bounds__(kAggThreads) void k_group_agg(const AggArgs a) {
         for (int64_t w = (int64_t)blockIdx.x * kAggWaves + wave; w < a.n_words; w += stride) {
             const uint64_t word = a.bitmap[w];
             if (word == 0) continue; // wave-uniform
+            uint32_t cand = 0; // WIDE: bit q -- the row may hold aggregate q's maximum
             if ((word >> lane) & 1ULL) {
                 const int64_t row = (int64_t)a.word_row_base[w] + lane;
                 const GroupRef ref = agg_locate(a, tab, (uint32_t)row, row_key(a, row));
-                for (int q = 0; q < a.n_agg; ++q) agg_fold(a, tab, ref, q, agg_value(a.aggs[q], row));
+                for (int q = 0; q < a.n_agg; ++q) {
+                    if (WIDE && a.aggs[q].alive) {
+                        if (agg_fold_prefix(a, tab, ref, q, be_bytes((const uint8_t *)a.aggs[q].data + row * (int64_t)a.aggs[q].width, 8))) cand |= 1u << q;
+                    } else agg_fold(a, tab, ref, q, agg_value(a.aggs[q], row));
+                }
             }
+            if (WIDE)
+                for (int q = 0; q < a.n_agg; ++q) {
+                    if (!a.aggs[q].alive) continue;
+                    const uint64_t m = ballot64((cand >> q) & 1u);
+                    if (m && lane == 0) a.aggs[q].alive[w] = m;
+                }
         }
     }
     __syncthreads();
@@ -1483,8 +1560,105 @@ int launch_group_agg(const AggArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t
     }
     const int64_t want = ((a.n_words + 3) / 4 + kAggWaves - 1) / kAggWaves;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(want, 768)); // 512-thread work-groups, 48 KiB LDS: 3 per CU
-    IMM3_LAUNCH(k_group_agg, grid, kAggThreads, s, ev0, ev1, a);
+    bool wide = false; // (a string MAX wider than 8 bytes: only this form holds its 8-byte prefix -- the others decline in group_agg_fast_ok)
+    for (int q = 0; q < a.n_agg; ++q) wide |= a.aggs[q].alive != nullptr;
+    if (wide) IMM3_LAUNCH(k_group_agg<true>, grid, kAggThreads, s, ev0, ev1, a);
+    else IMM3_LAUNCH(k_group_agg<false>, grid, kAggThreads, s, ev0, ev1, a);
     return AGG_FORM_GENERAL;
+}
+
+// ---- string MAX wider than 8 bytes: refine passes ----
+__global__ __launch_bounds__(kBlockThreads) void k_strmax_init(const AggArgs a) {
+    const int64_t t0 = (int64_t)blockIdx.x * kBlockThreads + threadIdx.x, stride = (int64_t)gridDim.x * kBlockThreads;
+    const int64_t n = (int64_t)a.mask + 2;
+    for (int j = 0; j < a.n_agg; ++j) {
+        if (!a.aggs[j].alive) continue;
+        for (int64_t i = t0; i < a.n_words; i += stride) a.aggs[j].alive[i] = 0ULL;
+        const int64_t nc = (int64_t)((a.aggs[j].width + 7) / 8 - 1) * n;
+        for (int64_t i = t0; i < nc; i += stride) a.aggs[j].chunks[i] = 0ULL;
+    }
+}
+
+// Pass k of aggregate j: every row still alive whose chunk k - 1 (bytes 8 (k - 1) .. 8 k) equals its group's maximum of that chunk
+// (final: the previous launch completed it) folds chunk k into chunks[k - 1][slot] and stays alive while that chunk may be the
+// maximum (the prefix pass's argument).  A lane reads one bitmap word of 64: the wave skips the zero words with one ballot, then
+// takes the others one at a time, a lane per row.  A word belongs to one wave, which rewrites it in place.
+__global__ __launch_bounds__(kBlockThreads) void k_strmax_refine(const AggArgs a, const int j, const int k) {
+    const AggCol &c = a.aggs[j];
+    const int wd = c.width, nch = (wd + 7) / 8;
+    const size_t n = (size_t)a.mask + 2;
+    const unsigned long long *prev = c.chunks + (size_t)(k - 2) * n; // (k >= 2 only)
+    unsigned long long *cur = c.chunks + (size_t)(k - 1) * n;
+    const int len = wd - 8 * k < 8 ? wd - 8 * k : 8;
+    const bool last = k == nch - 1;
+    const int lane = threadIdx.x & 63;
+    for (int64_t base = (int64_t)blockIdx.x * kBlockThreads + (threadIdx.x & ~63); base < a.n_words; base += (int64_t)gridDim.x * kBlockThreads) {
+        const uint64_t mine = base + lane < a.n_words ? c.alive[base + lane] : 0ULL;
+        uint64_t todo = ballot64(mine != 0ULL);
+        while (todo) { // wave-uniform
+            const int b = __builtin_ctzll(todo);
+            todo &= todo - 1ULL;
+            const int64_t wi = base + b;
+            const uint64_t word = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(mine >> 32), b) << 32) | (uint32_t)__shfl((int)(uint32_t)mine, b);
+            bool keep = false;
+            if ((word >> lane) & 1ULL) {
+                const int64_t row = a.word_row_base ? (int64_t)a.word_row_base[wi] + lane : wi * 64 + lane;
+                unsigned long long key = 0;
+                for (int g = 0; g < a.n_group; ++g) {
+                    const uint8_t *kp = row_ptr(a.groups[g].data, a.groups[g].tile_ptrs, row, a.groups[g].width);
+                    unsigned long long v = 0;
+                    for (int x = 0; x < a.groups[g].width; ++x) v |= (unsigned long long)kp[x] << (8 * x);
+                    key |= v << (8 * a.groups[g].shift);
+                }
+                const uint32_t g = find_slot(a, key);
+                if (g != 0xFFFFFFFFu) {
+                    const uint8_t *p = row_ptr(c.data, c.tile_ptrs, row, wd);
+                    const unsigned long long want = k == 1 ? (unsigned long long)a.vals[(size_t)g * kMaxAggs + j] : prev[g];
+                    if (be_bytes(p + 8 * (k - 1), 8) == want) {
+                        const unsigned long long v = be_bytes(p + 8 * k, len);
+                        const unsigned long long seen = cur[g]; // (a running maximum: never above the final one)
+                        if (v > seen) atomicMax(cur + g, v);
+                        keep = v >= seen;
+                    }
+                }
+            }
+            const uint64_t next = ballot64(keep);
+            if (!last && lane == 0 && next != word) c.alive[wi] = next;
+        }
+    }
+}
+
+// the exact maximum of aggregate j for every dense group (k_group_collect's output): its chunks, `width` bytes
+__global__ __launch_bounds__(kBlockThreads) void k_strmax_collect(const AggArgs a, const int j, const uint32_t n_groups, uint8_t *out) {
+    const AggCol &c = a.aggs[j];
+    const int wd = c.width, nch = (wd + 7) / 8;
+    const size_t n = (size_t)a.mask + 2;
+    for (uint32_t o = blockIdx.x * kBlockThreads + threadIdx.x; o < n_groups; o += gridDim.x * kBlockThreads) {
+        const uint32_t g = find_slot(a, a.out_keys[o]);
+        uint8_t *dst = out + (size_t)o * wd;
+        for (int k = 0; k < nch; ++k) {
+            const int len = wd - 8 * k < 8 ? wd - 8 * k : 8;
+            const unsigned long long v = g == 0xFFFFFFFFu ? 0ULL : (k == 0 ? (unsigned long long)a.vals[(size_t)g * kMaxAggs + j] : c.chunks[(size_t)(k - 1) * n + g]);
+            for (int x = 0; x < len; ++x) dst[8 * k + x] = (uint8_t)(v >> (8 * (len - 1 - x)));
+        }
+    }
+}
+
+void launch_strmax_init(const AggArgs &a, hipStream_t s) {
+    int64_t most = a.n_words;
+    for (int j = 0; j < a.n_agg; ++j)
+        if (a.aggs[j].alive) most = std::max<int64_t>(most, (int64_t)((a.aggs[j].width + 7) / 8 - 1) * ((int64_t)a.mask + 2));
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((most + kBlockThreads - 1) / kBlockThreads, 2048));
+    hipLaunchKernelGGL(k_strmax_init, dim3(grid), dim3(kBlockThreads), 0, s, a);
+}
+void launch_strmax_refine(const AggArgs &a, int j, int k, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    const int64_t waves = (a.n_words + 63) / 64; // one bitmap word per lane
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + kBlockThreads / 64 - 1) / (kBlockThreads / 64), 2048));
+    IMM3_LAUNCH(k_strmax_refine, grid, kBlockThreads, s, ev0, ev1, a, j, k);
+}
+void launch_strmax_collect(const AggArgs &a, int j, uint32_t n_groups, uint8_t *out, hipStream_t s) {
+    const int grid = (int)std::max<uint32_t>(1u, std::min<uint32_t>((n_groups + kBlockThreads - 1) / kBlockThreads, 256u));
+    hipLaunchKernelGGL(k_strmax_collect, dim3(grid), dim3(kBlockThreads), 0, s, a, j, n_groups, out);
 }
 
 // ---- merge of group tables (imm3_comm_merge_groups): direct-indexed tables for keys of <= 2 bytes, a hash table for wider keys ----

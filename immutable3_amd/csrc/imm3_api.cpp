@@ -14,6 +14,7 @@
 #include <unordered_map>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -884,6 +885,7 @@ static void query_free(imm3_query *q) {
     pool_release(ctx, q->d_akeys); pool_release(ctx, q->d_acounts); pool_release(ctx, q->d_okeys); pool_release(ctx, q->d_ocounts);
     pool_release(ctx, q->d_afirst); pool_release(ctx, q->d_ofirst); pool_release(ctx, q->d_ameta);
     pool_release(ctx, q->d_avals); pool_release(ctx, q->d_ovals);
+    for (int j = 0; j < kMaxAggs; ++j) { pool_release(ctx, q->d_alive[j]); pool_release(ctx, q->d_chunks[j]); }
     if (q->ev_filter_done) (void)hipEventDestroy(q->ev_filter_done);
     if (q->ev_total_done) (void)hipEventDestroy(q->ev_total_done);
     // the query kept its inputs alive (imm3_handles.h, "Lifetimes")
@@ -2571,7 +2573,8 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
             return fail(IMM3_ERR_ARG, "Unknown Aggregate type");
         // ProjectAggregate.scala:176-220: a String vector only takes CountAggr / MaxStringAggr (AvgDoubleAggr's sum is numeric only)
         if (has_batches && is_str && (aggs[j].kind == IMM3_AGG_MIN || aggs[j].kind == IMM3_AGG_SUM)) return fail(IMM3_ERR_UNSUPPORTED_VECTOR, "bad aggregator for this data type");
-        if (is_str && aggs[j].kind == IMM3_AGG_MAX && sc.width > 8) return fail(IMM3_ERR_ARG, "MAX over strings wider than 8 bytes is not supported on the GPU path");
+        if (is_str && aggs[j].kind == IMM3_AGG_MAX && sc.width > kStrMaxWidth)
+            return fail(IMM3_ERR_ARG, "MAX over strings wider than " + std::to_string(kStrMaxWidth) + " bytes is not supported on the GPU path");
     }
     q->is_agg = true;
     q->group_cols.assign(group_cols, group_cols + n_group);
@@ -2598,6 +2601,12 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
     HIPCHK(pool_alloc(ctx, &p, n * sizeof(unsigned long long))); q->d_acounts = (unsigned long long *)p;
     HIPCHK(pool_alloc(ctx, &p, n * kMaxAggs * sizeof(long long))); q->d_avals = (long long *)p;
     HIPCHK(pool_alloc(ctx, &p, 2 * sizeof(uint32_t))); q->d_ameta = (uint32_t *)p;
+    for (int32_t j = 0; j < n_aggs; ++j) { // a string MAX wider than 8 bytes: the refine passes' bitmap and chunk table (no per-row buffer)
+        const SegCol &sc = seg->cols[(size_t)q->used[(size_t)aggs[j].column]];
+        if (sc.vcodec != IMM3_DENSE_STRING || aggs[j].kind != IMM3_AGG_MAX || sc.width <= 8) continue;
+        HIPCHK(pool_alloc(ctx, &p, (size_t)std::max<int64_t>(q->n_words, 1) * sizeof(uint64_t))); q->d_alive[j] = (uint64_t *)p;
+        HIPCHK(pool_alloc(ctx, &p, (size_t)((sc.width + 7) / 8 - 1) * n * sizeof(unsigned long long))); q->d_chunks[j] = (unsigned long long *)p;
+    }
     *out = guard.release();
     return IMM3_OK;
 }
@@ -2645,6 +2654,8 @@ static void fill_agg_args(const imm3_query *q, AggArgs &a) {
         a.aggs[j].width = sc.width;
         a.aggs[j].kind = q->aggs[j].kind;
         a.aggs[j].is_str = sc.vcodec == IMM3_DENSE_STRING;
+        a.aggs[j].chunks = q->d_chunks[j];
+        a.aggs[j].alive = q->d_alive[j];
     }
     a.n_agg = (int32_t)q->aggs.size();
     if (q->agg_fusable && q->ctx->filter_variant != TV_AGG_SELECT_LAUNCH) { // (filter launch + aggregation launch, as before round 5)
@@ -2700,14 +2711,37 @@ static int settle_agg_select(imm3_query *q) {
     return IMM3_OK;
 }
 
+// The aggregation launch (timed as kernel 4).  A string MAX wider than 8 bytes adds a zeroing launch before it and its refine passes
+// after it (kernel 6, one record per pass): a fixed sequence for the query, so a recorded run replays it whole.
+static int launch_agg(imm3_query *q, const AggArgs &a, hipStream_t s, bool timed) {
+    imm3_ctx *ctx = q->ctx;
+    bool wide = false;
+    for (int j = 0; j < a.n_agg; ++j) wide |= a.aggs[j].alive != nullptr;
+    if (wide) launch_strmax_init(a, s);
+    if (timed) {
+        LaunchTimer t(ctx, 4);
+        q->agg_form_ran = launch_group_agg(a, s, t.start, t.stop);
+    } else q->agg_form_ran = launch_group_agg(a, s, nullptr, nullptr);
+    for (int j = 0; j < a.n_agg; ++j) {
+        if (!a.aggs[j].alive) continue;
+        for (int k = 1; k < (a.aggs[j].width + 7) / 8; ++k) {
+            if (timed) {
+                LaunchTimer t(ctx, 6);
+                launch_strmax_refine(a, j, k, s, t.start, t.stop);
+            } else launch_strmax_refine(a, j, k, s, nullptr, nullptr);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return IMM3_OK;
+}
+
 static int run_agg(imm3_query *q) {
     imm3_ctx *ctx = q->ctx;
     AggArgs a;
     agg_launch_args(q, a);
     if (!q->run.agg_select_skipped) { a.n_fused = 0; a.fused_all = 0; } // (the select ran: the bitmap is what this launch reads)
-    LaunchTimer t(ctx, 4);
-    q->agg_form_ran = launch_group_agg(a, ctx->stream, t.start, t.stop);
-    HIPCHK(hipGetLastError());
+    const int rc = launch_agg(q, a, ctx->stream, true);
+    if (rc) return rc;
     q->run.ran_agg = true;
     return IMM3_OK;
 }
@@ -2740,8 +2774,8 @@ static int settle_groups(imm3_query *q, uint32_t *n_groups) {
                 g.n_fused = 0;
                 g.fused_all = 0;
             }
-            q->agg_form_ran = launch_group_agg(g, s, nullptr, nullptr);
-            HIPCHK(hipGetLastError());
+            const int lrc = launch_agg(q, g, s, false);
+            if (lrc) return lrc;
             continue;
         }
         if (meta[1]) return fail(IMM3_ERR_LAYOUT, "more distinct groups than the aggregation table holds (2^27)");
@@ -2809,6 +2843,54 @@ extern "C" int imm3_query_fetch_groups(imm3_query *q, uint64_t *keys, uint32_t *
         if (vals)
             for (size_t j = 0; j < na; ++j)
                 vals[(size_t)o * na + j] = q->aggs[j].kind == IMM3_AGG_COUNT ? (int64_t)hc[i] : (int64_t)hv[(size_t)i * kMaxAggs + j];
+    }
+    return IMM3_OK;
+}
+
+extern "C" int imm3_query_fetch_group_strings(imm3_query *q, int32_t agg, uint8_t *out, uint32_t max_groups) {
+    if (!q) return fail(IMM3_ERR_ARG, "query is null");
+    if (!q->is_agg) return fail(IMM3_ERR_ARG, "not an aggregation query");
+    if (agg < 0 || agg >= (int32_t)q->aggs.size()) return fail(IMM3_ERR_ARG, "aggregate index out of range");
+    const SegCol &sc = q->seg->cols[(size_t)q->used[(size_t)q->aggs[(size_t)agg].column]];
+    if (q->aggs[(size_t)agg].kind != IMM3_AGG_MAX || sc.vcodec != IMM3_DENSE_STRING) return fail(IMM3_ERR_ARG, "the aggregate is not a MAX over a STRING column");
+    if (!out && max_groups > 0) return fail(IMM3_ERR_ARG, "out is null");
+    CTX_LIVE(q->ctx);
+    uint32_t n = 0;
+    const int rc = settle_groups(q, &n);
+    if (rc) return rc;
+    imm3_ctx *ctx = q->ctx;
+    hipStream_t s = ctx->stream;
+    const size_t w = (size_t)sc.width;
+    const bool wide = q->d_chunks[agg] != nullptr;
+    std::vector<uint32_t> hf(n);
+    std::vector<long long> hv(wide ? 0 : (size_t)n * kMaxAggs);
+    std::vector<uint8_t> hb(wide ? (size_t)n * w : 0);
+    std::unique_ptr<void, std::function<void(void *)>> d(nullptr, [ctx](void *p) { pool_release(ctx, p); });
+    if (n) {
+        HIPCHK(hipMemcpyAsync(hf.data(), q->d_ofirst, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        if (wide) { // the exact values, assembled from the chunks on the device in the dense groups' order
+            void *p = nullptr;
+            HIPCHK(pool_alloc(ctx, &p, hb.size()));
+            d.reset(p);
+            AggArgs a;
+            fill_agg_args(q, a);
+            launch_strmax_collect(a, agg, n, (uint8_t *)p, s);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(hb.data(), p, hb.size(), hipMemcpyDeviceToHost, s));
+        } else HIPCHK(hipMemcpyAsync(hv.data(), q->d_ovals, hv.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return hf[x] < hf[y]; }); // imm3_query_fetch_groups' order
+    for (uint32_t o = 0; o < n && o < max_groups; ++o) {
+        const uint32_t i = order[o];
+        uint8_t *dst = out + (size_t)o * w;
+        if (wide) std::memcpy(dst, hb.data() + (size_t)i * w, w);
+        else { // (<= 8 bytes: the value packed big-endian)
+            const unsigned long long v = (unsigned long long)hv[(size_t)i * kMaxAggs + (size_t)agg];
+            for (size_t b = 0; b < w; ++b) dst[b] = (uint8_t)(v >> (8 * (w - 1 - b)));
+        }
     }
     return IMM3_OK;
 }

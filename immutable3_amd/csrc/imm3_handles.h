@@ -299,6 +299,9 @@ struct imm3_query {
     unsigned long long *d_akeys = nullptr, *d_acounts = nullptr, *d_okeys = nullptr, *d_ocounts = nullptr;
     uint32_t *d_afirst = nullptr, *d_ofirst = nullptr, *d_ameta = nullptr; // d_ameta: {n_groups, overflow}
     long long *d_avals = nullptr, *d_ovals = nullptr;
+    // per aggregate that is a string MAX wider than 8 bytes (else null): the refine passes' alive bitmap and chunk table (AggCol)
+    uint64_t *d_alive[imm3::kMaxAggs] = {nullptr, nullptr, nullptr, nullptr};
+    unsigned long long *d_chunks[imm3::kMaxAggs] = {nullptr, nullptr, nullptr, nullptr};
     uint32_t out_cap = 0;
     bool agg_fusable = false;          // the select chain is closed intervals over <= 2 dense int8 / int32 columns of one uniform segment (or empty): the aggregation kernel can evaluate it itself
     uint64_t limit_gather_gave_up = 0; // times settle_rows found k_limit_gather's give-up tag and gathered the rows again with k_scan + k_gather

@@ -389,7 +389,13 @@ struct AggCol {
     int32_t kind;                // AggKind
     int32_t is_str;              // AGG_MAX over a string column: values compared as big-endian-packed bytes
     int32_t pad;
+    // AGG_MAX over a string column wider than 8 bytes (else null): the aggregation launch folds the first 8 bytes and marks the
+    // rows that may hold the maximum in `alive` (a bitmap the size of the selection's); refine pass k = 1 .. ceil(width / 8) - 1
+    // keeps the rows whose chunk k - 1 equals the group's and folds chunk k into chunks[k - 1][slot] (mask + 2 slots per chunk)
+    unsigned long long *chunks;
+    uint64_t *alive;
 };
+constexpr int kStrMaxWidth = 256; // widest string MAX (IMM3_STRING_MAX_WIDTH)
 
 // SelectOp fused into the aggregation (k_group_agg_lanes' FUSED instances): ProjectAggIterator walks the selected positions of the
 // batch it is handed (ProjectAggregate.scala:158-177); with the predicates evaluated on the rows the aggregation kernel already holds
@@ -467,6 +473,12 @@ void launch_merge_scatter(const MergeArgs &a, hipStream_t s);
 void launch_merge_insert_list(const MergeArgs &a, hipStream_t s);
 void launch_merge_collect_list(const MergeArgs &a, hipStream_t s);
 void launch_group_collect(const AggArgs &a, hipStream_t s);
+// string MAX wider than 8 bytes (AggCol::chunks / alive): zero every such aggregate's alive bitmap and chunk table (before the
+// aggregation launch); refine pass k of aggregate j; the exact values of aggregate j's groups, `width` bytes per dense group
+// (k_group_collect's order: after it)
+void launch_strmax_init(const AggArgs &a, hipStream_t s);
+void launch_strmax_refine(const AggArgs &a, int j, int k, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+void launch_strmax_collect(const AggArgs &a, int j, uint32_t n_groups, uint8_t *out, hipStream_t s);
 
 constexpr int kSubTallies = 32;                       // in-kernel count reduce: sub-tallies (finish_add, imm3_device.h)
 constexpr int kFinishWords = 16 + kSubTallies * 16;   // u64 words of a query's `finish` block: header (9 used, padded to a 128-byte line) + one line per sub-tally

@@ -519,6 +519,14 @@ class ProjectAggOp : public Operator<AggMapTuple> {
         std::vector<uint32_t> first(n);
         std::vector<int64_t> vals((size_t)n * aggs.size());
         imm3Check(imm3_query_fetch_groups(h.q, keys.data(), first.data(), counts.data(), vals.data(), n));
+        // a MaxStringAggr over a column wider than 8 bytes: vals hold its first 8 bytes, the exact values come per aggregate
+        std::vector<std::vector<uint8_t>> wide(aggs.size());
+        for (size_t j = 0; j < aggs.size(); ++j) {
+            const int w = cols[(size_t)abi[j].column].width();
+            if (aggs[j].kind != Aggregator::MaxStringAggr || w <= 8) continue;
+            wide[j].resize((size_t)n * (size_t)w);
+            imm3Check(imm3_query_fetch_group_strings(h.q, (int32_t)j, wide[j].data(), n));
+        }
         std::vector<AggMapTuple> items;
         for (uint32_t g = 0; g < n; ++g) {
             std::string key;
@@ -544,7 +552,9 @@ class ProjectAggOp : public Operator<AggMapTuple> {
                 case Aggregator::MaxStringAggr: {
                     const int w = cols[(size_t)abi[j].column].width();
                     std::string sv((size_t)w, '\0');
-                    for (int b = 0; b < w; ++b) sv[(size_t)b] = (char)((uint64_t)x >> (8 * (w - 1 - b)));
+                    if (!wide[j].empty()) sv.assign((const char *)wide[j].data() + (size_t)g * (size_t)w, (size_t)w);
+                    else
+                        for (int b = 0; b < w; ++b) sv[(size_t)b] = (char)((uint64_t)x >> (8 * (w - 1 - b)));
                     m[j].svalue = sv;
                     break;
                 }

@@ -35,7 +35,7 @@ EXPORTS = [
     "imm3_table_create", "imm3_table_destroy", "imm3_query_create_table", "imm3_query_create_table_agg",
     "imm3_query_segment_starts", "imm3_query_locate_rows",
     "imm3_query_create", "imm3_query_create_agg", "imm3_query_group_count", "imm3_query_fetch_groups", "imm3_query_agg_shape",
-    "imm3_query_destroy", "imm3_query_reserve_rows",
+    "imm3_query_fetch_group_strings", "imm3_query_destroy", "imm3_query_reserve_rows",
     "imm3_query_run", "imm3_query_run_select", "imm3_query_run_count", "imm3_query_sync", "imm3_query_join_count", "imm3_query_log_counts",
     "imm3_query_layout", "imm3_query_batches", "imm3_query_count", "imm3_query_bitmap",
     "imm3_query_row_count", "imm3_query_fetch_rows", "imm3_query_device_ptr",
@@ -145,6 +145,7 @@ def load() -> C.CDLL:
     L.imm3_query_locate_rows.argtypes = [vp, vp, u64, vp, vp]
     L.imm3_query_group_count.argtypes = [vp, P(C.c_uint32)]
     L.imm3_query_fetch_groups.argtypes = [vp, vp, vp, vp, vp, C.c_uint32]
+    L.imm3_query_fetch_group_strings.argtypes = [vp, i32, vp, C.c_uint32]
     L.imm3_query_destroy.argtypes = [vp]
     L.imm3_query_reserve_rows.argtypes = [vp, u64]
     L.imm3_query_run.argtypes = [vp]
@@ -617,6 +618,17 @@ class DeviceQuery:
         vals = np.zeros((max(g, 1), na), np.int64)
         _check(load().imm3_query_fetch_groups(self._h, keys.ctypes.data, first.ctypes.data, counts.ctypes.data, vals.ctypes.data, g))
         return keys[:g], first[:g], counts[:g], vals[:g, : len(self.aggs or [])]
+
+    def fetch_group_strings(self, j: int) -> np.ndarray:
+        """The exact value of string MAX aggregate j per group: uint8[g, width], groups in fetch_groups' order."""
+        n = C.c_uint32(0)
+        _check(load().imm3_query_group_count(self._h, C.byref(n)))
+        g = n.value
+        col = self.aggs[j][1] if self.aggs is not None and 0 <= j < len(self.aggs) else 0
+        width = self.seg.widths[self.used_cols[col]] if 0 <= col < len(self.used_cols) else 1
+        out = np.zeros((max(g, 1), width), np.uint8)
+        _check(load().imm3_query_fetch_group_strings(self._h, j, out.ctypes.data, g))
+        return out[:g]
 
     def plan(self) -> dict:
         """How the library planned this query (include/imm3_diag.h: imm3_query_plan)."""

@@ -592,6 +592,10 @@ class ProjectAggOp(Operator):
                                group_cols=group_idx, aggs=[(a.kind, colnames.index(a.col)) for a in aggs])
         q.run()
         keys, first, counts, vals = q.fetch_groups()
+        # a MaxStringAggr over a column wider than 8 bytes: vals hold its first 8 bytes, the exact value comes from the device
+        wide = {j: q.fetch_group_strings(j) for j, a in enumerate(aggs)
+                if a.kind == native.AGG_MAX and scan.cols[colnames.index(a.col)].columnType == "STRING"
+                and scan.cols[colnames.index(a.col)].width > 8}
         q.close()
         widths = [scan.cols[i].width for i in group_idx]
         for g in range(keys.shape[0]):
@@ -607,6 +611,8 @@ class ProjectAggOp(Operator):
                     na.set(int(counts[g]))
                 elif isinstance(na, AvgDoubleAggr):  # the group's exact sum; every selected row added once to the counter
                     na.sum, na.counter = int(vals[g, j]), int(counts[g])
+                elif isinstance(na, MaxStringAggr) and j in wide:
+                    na.value = _value(wide[j][g])     # new String(bytes)
                 elif isinstance(na, MaxStringAggr):
                     w = scan.cols[colnames.index(a.col)].width
                     na.value = int(vals[g, j]).to_bytes(8, "big", signed=True)[8 - w:].decode("utf-8", errors="replace")

@@ -160,6 +160,8 @@ int imm3_segment_destroy(imm3_segment *seg);
 int imm3_segment_bytes(const imm3_segment *seg, uint64_t *device_bytes);
 
 enum { IMM3_AGG_COUNT = 0, IMM3_AGG_MIN = 1, IMM3_AGG_MAX = 2, IMM3_AGG_SUM = 3 };
+/* widest STRING column that IMM3_AGG_MAX takes on the GPU path (bytes) */
+#define IMM3_STRING_MAX_WIDTH 256
 typedef struct {
     int32_t kind;
     int32_t column;
@@ -218,7 +220,7 @@ int imm3_query_destroy(imm3_query *q);
  *   group_cols  indices into used_cols, in the order their values are joined into the group key (the reference
  *               joins them in batch-column order with "_", :151-156); total width <= 8 bytes on this path
  *   aggs        {kind, column (index into used_cols)}; MIN/MAX/SUM on INT/TINYINT (PFOR_INT included), MAX on STRING
- *               (<= 8 bytes), COUNT on any.  MIN or SUM on a STRING column: IMM3_ERR_UNSUPPORTED_VECTOR "bad aggregator for
+ *               (1 .. IMM3_STRING_MAX_WIDTH bytes; wider: IMM3_ERR_ARG), COUNT on any.  MIN or SUM on a STRING column: IMM3_ERR_UNSUPPORTED_VECTOR "bad aggregator for
  *               this data type" iff the segment has >= 1 batch (:205-214)
  * Groups come back in first-seen order (the reference's LinkedHashMap order): ascending first selected row. ---- */
 int imm3_query_create_agg(imm3_ctx *ctx, const imm3_segment *seg,
@@ -235,9 +237,15 @@ int imm3_query_agg_shape(const imm3_query *q, int32_t *n_group_cols, int32_t *n_
 /* keys: the group columns' raw bytes packed little-endian in group_cols order; first_row: lowest selected row of
  * the group; counts: selected rows of the group; vals[g * n_aggs + j]: COUNT -> the count, MIN/MAX numeric -> the
  * int32 value sign-extended, SUM -> the exact int64 sum of the group's selected values (<= 2^32 rows x 2^31: no
- * overflow), MAX string -> the value's bytes packed big-endian.  Sorted by first_row. */
+ * overflow), MAX string -> the value's bytes packed big-endian (a column wider than 8 bytes: its FIRST 8 bytes packed
+ * big-endian; the whole value comes from imm3_query_fetch_group_strings).  Sorted by first_row. */
 int imm3_query_fetch_groups(imm3_query *q, uint64_t *keys, uint32_t *first_row, uint64_t *counts, int64_t *vals,
                             uint32_t max_groups);
+/* The exact value of the string MAX aggregate `agg` (index into aggs) of every group: the column's width in bytes per group
+ * (out[g * width .. g * width + width)), the byte-lexicographic maximum (String.compareTo for ASCII).  Groups in the order of
+ * imm3_query_fetch_groups; any width, narrow columns included.  IMM3_ERR_ARG when `agg` is out of range or is not a MAX over
+ * a STRING column. */
+int imm3_query_fetch_group_strings(imm3_query *q, int32_t agg, uint8_t *out, uint32_t max_groups);
 
 /* Pre-size the projected-row buffers so that not even the FIRST imm3_query_run() has to wait for the count.  Without it an
  * unlimited projection sizes them once: a query whose SELECT list is predicate columns only (it runs as ONE launch that
@@ -362,6 +370,7 @@ int imm3_comm_allreduce_count_all(imm3_comm *const *comms, int32_t n_comms, imm3
  * device hash table per rank, exchanged as an ncclAllGather of the ranks' group lists and merged again on the device.  One rank:
  * the same merge over that rank's queries, no collective.
  *   keys / counts / vals as imm3_query_fetch_groups; first[g] = segment << 32 | first selected row of the group there.
+ * A query with a MAX over a STRING column wider than 8 bytes is refused (IMM3_ERR_ARG): such maxima are not merged.
  * Synchronous (the merged table is returned to the host). */
 int imm3_comm_merge_groups(imm3_comm *c, imm3_query *const *queries, const int32_t *segment_index, int32_t n_queries,
                            uint64_t *keys, uint64_t *first, uint64_t *counts, int64_t *vals, uint32_t max_groups, uint32_t *n_groups);

@@ -16,7 +16,7 @@ extern "C" {
 /* ---- live kernel timing (HIP events on the context's stream) ----
  * When enabled, every kernel launch of this context is bracketed by an event pair.
  * kernel ids: 0 = scan+select, 1 = offsets scan, 2 = compact+gather, 3 = count reduce, 4 = group-by aggregation,
- *             5 = PFOR_INT / snappy column decode. */
+ *             5 = PFOR_INT / snappy column decode, 6 = refine pass of a MAX over a string wider than 8 bytes (one per pass). */
 int imm3_ctx_timing_enable(imm3_ctx *ctx, int32_t max_records);
 int imm3_ctx_timing_reset(imm3_ctx *ctx);
 /* Only launches whose kernel id has its bit set in `kernel_mask` are bracketed (default: all). */
