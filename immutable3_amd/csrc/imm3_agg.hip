@@ -196,6 +196,136 @@ __device__ __forceinline__ uint32_t find_slot(const AggArgs &a, unsigned long lo
     return 0xFFFFFFFFu;
 }
 
+// ---- group keys wider than 8 bytes (AggArgs::wide_key) ----
+// A table slot holds a TAG, hash32 << 32 | rep_row: the key store is the group columns themselves, read at the representative row
+// whose insert claimed the slot.  Those bytes do not change while a kernel runs, so one CAS publishes hash and representative at
+// once and no CU ever reads key bytes that another CU wrote (the L2s of the XCDs are not coherent).  rep_row < 2^32 - 1: a tag is
+// never the empty marker.
+__device__ __forceinline__ uint32_t key_mix(uint32_t h, uint32_t v) {
+    h = (h ^ v) * 0x9E3779B1u; // one quarter-rate multiply per key dword (hash_key's argument); the finaliser below does the rest
+    return h ^ (h >> 15);
+}
+
+// hash32 of a row's key: the group columns' bytes, dword by dword as they stream in (no key held in registers)
+__device__ __forceinline__ uint32_t row_hash_wide(const AggArgs &a, int64_t row) {
+    uint32_t h = 0x811C9DC5u;
+    for (int g = 0; g < a.n_group; ++g) {
+        const int w = a.groups[g].width;
+        const uint8_t *p = row_ptr(a.groups[g].data, a.groups[g].tile_ptrs, row, w);
+        if ((w & 15) == 0)
+            for (int i = 0; i < w; i += 16) {
+                const uint4 v = *(const uint4 *)(p + i);
+                h = key_mix(key_mix(key_mix(key_mix(h, v.x), v.y), v.z), v.w);
+            }
+        else if ((w & 3) == 0)
+            for (int i = 0; i < w; i += 4) h = key_mix(h, *(const uint32_t *)(p + i));
+        else
+            for (int i = 0; i < w; i += 4) {
+                uint32_t v = 0;
+                for (int b = 0; b < 4 && i + b < w; ++b) v |= (uint32_t)p[i + b] << (8 * b);
+                h = key_mix(h, v);
+            }
+    }
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h & a.hash_mask;
+}
+
+// do rows r0 and r1 carry the same key?  (both read through the columns: the representative's bytes are L1 / L2-hot)
+__device__ __forceinline__ bool keys_equal_wide(const AggArgs &a, int64_t r0, int64_t r1) {
+    if (r0 == r1) return true;
+    for (int g = 0; g < a.n_group; ++g) {
+        const int w = a.groups[g].width;
+        const uint8_t *p = row_ptr(a.groups[g].data, a.groups[g].tile_ptrs, r0, w);
+        const uint8_t *q = row_ptr(a.groups[g].data, a.groups[g].tile_ptrs, r1, w);
+        if ((w & 15) == 0) {
+            for (int i = 0; i < w; i += 16) {
+                const uint4 x = *(const uint4 *)(p + i), y = *(const uint4 *)(q + i);
+                if (((x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w)) != 0u) return false;
+            }
+        } else if ((w & 3) == 0) {
+            for (int i = 0; i < w; i += 4)
+                if (*(const uint32_t *)(p + i) != *(const uint32_t *)(q + i)) return false;
+        } else
+            for (int i = 0; i < w; ++i)
+                if (p[i] != q[i]) return false;
+    }
+    return true;
+}
+
+// does the slot's tag `cur` name the group of the key with hash h at row `row`?
+__device__ __forceinline__ bool tag_matches(const AggArgs &a, unsigned long long cur, uint32_t h, int64_t row) {
+    return cur != kEmptyKey && (uint32_t)(cur >> 32) == h && keys_equal_wide(a, row, (int64_t)(uint32_t)cur);
+}
+
+// global_slot for a tag (an LDS entry's, or a row's own): the slot of its key, claimed with the tag itself when new
+__device__ __forceinline__ uint32_t global_slot_wide(const AggArgs &a, unsigned long long tag) {
+    const uint32_t h = (uint32_t)(tag >> 32);
+    const int64_t rep = (int64_t)(uint32_t)tag;
+    uint32_t g = h & a.mask;
+    for (uint32_t probes = 0; probes <= a.mask; ++probes) {
+        const unsigned long long prev = atomicCAS(&a.keys[g], kEmptyKey, tag);
+        if (prev == kEmptyKey || prev == tag || tag_matches(a, prev, h, rep)) return g;
+        g = (g + 1) & a.mask;
+    }
+    *a.overflow = 1;
+    return 0xFFFFFFFFu;
+}
+
+// find_slot for the wide keys: by row (its hash and bytes) or by tag (k_group_collect's out_keys), read only
+__device__ __forceinline__ uint32_t find_slot_row_wide(const AggArgs &a, int64_t row) {
+    const uint32_t h = row_hash_wide(a, row);
+    uint32_t g = h & a.mask;
+    for (uint32_t probes = 0; probes <= a.mask; ++probes) {
+        const unsigned long long cur = a.keys[g];
+        if (cur == kEmptyKey) break;
+        if (tag_matches(a, cur, h, row)) return g;
+        g = (g + 1) & a.mask;
+    }
+    return 0xFFFFFFFFu;
+}
+__device__ __forceinline__ uint32_t find_slot_tag_wide(const AggArgs &a, unsigned long long tag) {
+    uint32_t g = (uint32_t)(tag >> 32) & a.mask;
+    for (uint32_t probes = 0; probes <= a.mask; ++probes) {
+        const unsigned long long cur = a.keys[g];
+        if (cur == tag) return g;
+        if (cur == kEmptyKey) break;
+        g = (g + 1) & a.mask;
+    }
+    return 0xFFFFFFFFu;
+}
+
+// agg_locate for the wide keys: the LDS table's tags compare the same way
+__device__ __forceinline__ GroupRef agg_locate_wide(const AggArgs &a, const LdsTable &t, uint32_t row) {
+    GroupRef r{-1, 0xFFFFFFFFu};
+    const uint32_t h = row_hash_wide(a, row);
+    const unsigned long long tag = ((unsigned long long)h << 32) | row;
+    uint32_t s = h & (kLdsSlots - 1);
+    for (int probes = 0; probes < kMaxProbes; ++probes) {
+        unsigned long long cur = t.keys[s];
+        if (cur == kEmptyKey) {
+            cur = atomicCAS(&t.keys[s], kEmptyKey, tag);
+            if (cur == kEmptyKey) { r.slot = (int)s; break; }
+        }
+        if (tag_matches(a, cur, h, row)) { r.slot = (int)s; break; }
+        s = (s + 1) & (kLdsSlots - 1);
+    }
+    if (r.slot >= 0) {
+        if (row < t.first[r.slot]) atomicMin(&t.first[r.slot], row);
+        atomicAdd(&t.count[r.slot], 1u);
+    } else {
+        r.gslot = global_slot_wide(a, tag);
+        if (r.gslot != 0xFFFFFFFFu) {
+            atomicMin(&a.first[r.gslot], row);
+            atomicAdd(&a.counts[r.gslot], 1ULL);
+        }
+    }
+    return r;
+}
+
 __device__ __forceinline__ unsigned long long row_key(const AggArgs &a, int64_t row) {
     unsigned long long key = 0;
     for (int g = 0; g < a.n_group; ++g) key |= load_le(a.groups[g].data, row, a.groups[g].width) << (8 * a.groups[g].shift);
@@ -257,7 +387,9 @@ __device__ __forceinline__ long long agg_from_raw(const AggCol &a, unsigned long
 // skipped before any column load.  Ragged layout: lane l <-> row base(word) + l, one word per step.
 // WIDE: the query has a string MAX wider than 8 bytes -- its prefix pass (the first 8 bytes of the selected rows only: 4 rows of a
 // wide column may reach past the column's slack), which also writes the rows that may hold the maximum into AggCol::alive.
-template <bool WIDE>
+// KEYW: the group key is wider than 8 bytes (AggArgs::wide_key) -- tags instead of keys in both tables (agg_locate_wide), the key
+// bytes read at the selected rows only.
+template <bool WIDE, bool KEYW>
 __global__ __launch_bounds__(kAggThreads) void k_group_agg(const AggArgs a) {
     __shared__ unsigned long long s_keys[kLdsSlots + 1];      // 8 KiB
     __shared__ uint32_t s_first[kLdsSlots + 1];               // 4 KiB
@@ -291,6 +423,14 @@ __global__ __launch_bounds__(kAggThreads) void k_group_agg(const AggArgs a) {
             const int64_t row0 = st * 256 + 4 * lane;                 // (virtual) row of the lane's first row
             const int64_t tile = st >> 2;                              // table queries address columns through the tile table
             const int64_t in_tile = (st & 3) * 256 + 4 * lane;
+            GroupRef ref[4];
+            if constexpr (KEYW) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    ref[k] = GroupRef{-1, 0xFFFFFFFFu};
+                    if ((nib >> k) & 1u) ref[k] = agg_locate_wide(a, tab, (uint32_t)(row0 + k));
+                }
+            } else {
             // group key of the lane's 4 rows, one column at a time (keeps few registers live)
             unsigned long long key[4] = {0, 0, 0, 0};
             for (int g = 0; g < a.n_group; ++g) {
@@ -304,11 +444,11 @@ __global__ __launch_bounds__(kAggThreads) void k_group_agg(const AggArgs a) {
                 asm volatile("" ::"v"((uint32_t)key[0]), "v"((uint32_t)key[3]));
                 continue;
             }
-            GroupRef ref[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 ref[k] = GroupRef{-1, 0xFFFFFFFFu};
                 if ((nib >> k) & 1u) ref[k] = agg_locate(a, tab, (uint32_t)(row0 + k), key[k]);
+            }
             }
             // then every aggregate column: one load for the 4 rows, fold, next column
             for (int q = 0; q < a.n_agg; ++q) {
@@ -349,7 +489,7 @@ __global__ __launch_bounds__(kAggThreads) void k_group_agg(const AggArgs a) {
             uint32_t cand = 0; // WIDE: bit q -- the row may hold aggregate q's maximum
             if ((word >> lane) & 1ULL) {
                 const int64_t row = (int64_t)a.word_row_base[w] + lane;
-                const GroupRef ref = agg_locate(a, tab, (uint32_t)row, row_key(a, row));
+                const GroupRef ref = KEYW ? agg_locate_wide(a, tab, (uint32_t)row) : agg_locate(a, tab, (uint32_t)row, row_key(a, row));
                 for (int q = 0; q < a.n_agg; ++q) {
                     if (WIDE && a.aggs[q].alive) {
                         if (agg_fold_prefix(a, tab, ref, q, be_bytes((const uint8_t *)a.aggs[q].data + row * (int64_t)a.aggs[q].width, 8))) cand |= 1u << q;
@@ -370,7 +510,7 @@ __global__ __launch_bounds__(kAggThreads) void k_group_agg(const AggArgs a) {
     for (int i = t; i <= kLdsSlots; i += kAggThreads) {
         if (s_count[i] == 0) continue;
         const unsigned long long key = i == kLdsSlots ? kEmptyKey : s_keys[i];
-        const uint32_t g = global_slot(a, key);
+        const uint32_t g = KEYW ? global_slot_wide(a, key) : global_slot(a, key); // (KEYW: the entry's tag; slot kLdsSlots stays empty)
         if (g != 0xFFFFFFFFu) agg_update_global(a, g, s_first[i], (unsigned long long)s_count[i], &s_vals[i * kMaxAggs]);
     }
 }
@@ -1409,7 +1549,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_group_init(const AggArgs a) {
 
 // Can the fast form take this aggregation?  (uniform single segment; 32-bit keys and values)
 bool group_agg_fast_ok(const AggArgs &a) {
-    if (a.word_row_base || a.n_group > 2) return false;
+    if (a.word_row_base || a.n_group > 2 || a.wide_key) return false;
     int key_bytes = 0;
     for (int g = 0; g < a.n_group; ++g) {
         const int w = a.groups[g].width;
@@ -1562,8 +1702,11 @@ int launch_group_agg(const AggArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(want, 768)); // 512-thread work-groups, 48 KiB LDS: 3 per CU
     bool wide = false; // (a string MAX wider than 8 bytes: only this form holds its 8-byte prefix -- the others decline in group_agg_fast_ok)
     for (int q = 0; q < a.n_agg; ++q) wide |= a.aggs[q].alive != nullptr;
-    if (wide) IMM3_LAUNCH(k_group_agg<true>, grid, kAggThreads, s, ev0, ev1, a);
-    else IMM3_LAUNCH(k_group_agg<false>, grid, kAggThreads, s, ev0, ev1, a);
+    if (a.wide_key) { // (so does a group key wider than 8 bytes)
+        if (wide) IMM3_LAUNCH((k_group_agg<true, true>), grid, kAggThreads, s, ev0, ev1, a);
+        else IMM3_LAUNCH((k_group_agg<false, true>), grid, kAggThreads, s, ev0, ev1, a);
+    } else if (wide) IMM3_LAUNCH((k_group_agg<true, false>), grid, kAggThreads, s, ev0, ev1, a);
+    else IMM3_LAUNCH((k_group_agg<false, false>), grid, kAggThreads, s, ev0, ev1, a);
     return AGG_FORM_GENERAL;
 }
 
@@ -1583,6 +1726,8 @@ __global__ __launch_bounds__(kBlockThreads) void k_strmax_init(const AggArgs a) 
 // (final: the previous launch completed it) folds chunk k into chunks[k - 1][slot] and stays alive while that chunk may be the
 // maximum (the prefix pass's argument).  A lane reads one bitmap word of 64: the wave skips the zero words with one ballot, then
 // takes the others one at a time, a lane per row.  A word belongs to one wave, which rewrites it in place.
+// KEYW: the group key is wider than 8 bytes -- the row's slot is found by its hash and bytes (find_slot_row_wide)
+template <bool KEYW>
 __global__ __launch_bounds__(kBlockThreads) void k_strmax_refine(const AggArgs a, const int j, const int k) {
     const AggCol &c = a.aggs[j];
     const int wd = c.width, nch = (wd + 7) / 8;
@@ -1603,6 +1748,9 @@ __global__ __launch_bounds__(kBlockThreads) void k_strmax_refine(const AggArgs a
             bool keep = false;
             if ((word >> lane) & 1ULL) {
                 const int64_t row = a.word_row_base ? (int64_t)a.word_row_base[wi] + lane : wi * 64 + lane;
+                uint32_t g;
+                if constexpr (KEYW) g = find_slot_row_wide(a, row);
+                else {
                 unsigned long long key = 0;
                 for (int g = 0; g < a.n_group; ++g) {
                     const uint8_t *kp = row_ptr(a.groups[g].data, a.groups[g].tile_ptrs, row, a.groups[g].width);
@@ -1610,7 +1758,8 @@ __global__ __launch_bounds__(kBlockThreads) void k_strmax_refine(const AggArgs a
                     for (int x = 0; x < a.groups[g].width; ++x) v |= (unsigned long long)kp[x] << (8 * x);
                     key |= v << (8 * a.groups[g].shift);
                 }
-                const uint32_t g = find_slot(a, key);
+                g = find_slot(a, key);
+                }
                 if (g != 0xFFFFFFFFu) {
                     const uint8_t *p = row_ptr(c.data, c.tile_ptrs, row, wd);
                     const unsigned long long want = k == 1 ? (unsigned long long)a.vals[(size_t)g * kMaxAggs + j] : prev[g];
@@ -1629,12 +1778,14 @@ __global__ __launch_bounds__(kBlockThreads) void k_strmax_refine(const AggArgs a
 }
 
 // the exact maximum of aggregate j for every dense group (k_group_collect's output): its chunks, `width` bytes
+// (KEYW: out_keys holds the slots' tags)
+template <bool KEYW>
 __global__ __launch_bounds__(kBlockThreads) void k_strmax_collect(const AggArgs a, const int j, const uint32_t n_groups, uint8_t *out) {
     const AggCol &c = a.aggs[j];
     const int wd = c.width, nch = (wd + 7) / 8;
     const size_t n = (size_t)a.mask + 2;
     for (uint32_t o = blockIdx.x * kBlockThreads + threadIdx.x; o < n_groups; o += gridDim.x * kBlockThreads) {
-        const uint32_t g = find_slot(a, a.out_keys[o]);
+        const uint32_t g = KEYW ? find_slot_tag_wide(a, a.out_keys[o]) : find_slot(a, a.out_keys[o]);
         uint8_t *dst = out + (size_t)o * wd;
         for (int k = 0; k < nch; ++k) {
             const int len = wd - 8 * k < 8 ? wd - 8 * k : 8;
@@ -1654,11 +1805,29 @@ void launch_strmax_init(const AggArgs &a, hipStream_t s) {
 void launch_strmax_refine(const AggArgs &a, int j, int k, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     const int64_t waves = (a.n_words + 63) / 64; // one bitmap word per lane
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + kBlockThreads / 64 - 1) / (kBlockThreads / 64), 2048));
-    IMM3_LAUNCH(k_strmax_refine, grid, kBlockThreads, s, ev0, ev1, a, j, k);
+    if (a.wide_key) IMM3_LAUNCH(k_strmax_refine<true>, grid, kBlockThreads, s, ev0, ev1, a, j, k);
+    else IMM3_LAUNCH(k_strmax_refine<false>, grid, kBlockThreads, s, ev0, ev1, a, j, k);
 }
 void launch_strmax_collect(const AggArgs &a, int j, uint32_t n_groups, uint8_t *out, hipStream_t s) {
     const int grid = (int)std::max<uint32_t>(1u, std::min<uint32_t>((n_groups + kBlockThreads - 1) / kBlockThreads, 256u));
-    hipLaunchKernelGGL(k_strmax_collect, dim3(grid), dim3(kBlockThreads), 0, s, a, j, n_groups, out);
+    if (a.wide_key) hipLaunchKernelGGL(k_strmax_collect<true>, dim3(grid), dim3(kBlockThreads), 0, s, a, j, n_groups, out);
+    else hipLaunchKernelGGL(k_strmax_collect<false>, dim3(grid), dim3(kBlockThreads), 0, s, a, j, n_groups, out);
+}
+
+// wide keys: every dense group's key bytes, read at its first row (any row of the group carries its key)
+__global__ __launch_bounds__(kBlockThreads) void k_group_keys(const AggArgs a, const uint32_t n_groups, const int key_bytes, uint8_t *out) {
+    for (uint32_t o = blockIdx.x * kBlockThreads + threadIdx.x; o < n_groups; o += gridDim.x * kBlockThreads) {
+        const int64_t row = a.out_first[o];
+        uint8_t *dst = out + (size_t)o * key_bytes;
+        for (int g = 0, at = 0; g < a.n_group; at += a.groups[g].width, ++g) {
+            const uint8_t *p = row_ptr(a.groups[g].data, a.groups[g].tile_ptrs, row, a.groups[g].width);
+            for (int x = 0; x < a.groups[g].width && at + x < key_bytes; ++x) dst[at + x] = p[x];
+        }
+    }
+}
+void launch_group_keys(const AggArgs &a, uint32_t n_groups, int key_bytes, uint8_t *out, hipStream_t s) {
+    const int grid = (int)std::max<uint32_t>(1u, std::min<uint32_t>((n_groups + kBlockThreads - 1) / kBlockThreads, 256u));
+    hipLaunchKernelGGL(k_group_keys, dim3(grid), dim3(kBlockThreads), 0, s, a, n_groups, key_bytes, out);
 }
 
 // ---- merge of group tables (imm3_comm_merge_groups): direct-indexed tables for keys of <= 2 bytes, a hash table for wider keys ----

@@ -2547,7 +2547,7 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
                                  const imm3_select *sels, int32_t n_sels,
                                  const int32_t *group_cols, int32_t n_group,
                                  const imm3_aggregate *aggs, int32_t n_aggs,
-                                 int32_t table_block_size, imm3_query **out) {
+                                 int32_t table_block_size, imm3_query **out, bool wide_keys) {
     if (!out) return fail(IMM3_ERR_ARG, "out is null");
     *out = nullptr;
     if (n_group < 0 || n_group > kMaxGroupCols || (n_group > 0 && !group_cols)) return fail(IMM3_ERR_ARG, "0..4 group columns are supported on the GPU path");
@@ -2563,7 +2563,9 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
         if (group_cols[g] < 0 || group_cols[g] >= n_used) return fail(IMM3_ERR_ARG, "group column is not among the used columns");
         key_bytes += seg->cols[(size_t)q->used[(size_t)group_cols[g]]].width;
     }
-    if (key_bytes > 8) return fail(IMM3_ERR_ARG, "group key wider than 8 bytes is not supported on the GPU path");
+    if (!wide_keys && key_bytes > 8) return fail(IMM3_ERR_ARG, "group key wider than 8 bytes is not supported on the GPU path");
+    if (key_bytes > kGroupKeyMaxWidth)
+        return fail(IMM3_ERR_ARG, "group key wider than " + std::to_string(kGroupKeyMaxWidth) + " bytes is not supported on the GPU path");
     const bool has_batches = table ? !table->batch_size.empty() : !q->layout->size.empty();
     for (int32_t j = 0; j < n_aggs; ++j) {
         if (aggs[j].column < 0 || aggs[j].column >= n_used) return fail(IMM3_ERR_ARG, "aggregate column is not among the used columns");
@@ -2577,6 +2579,7 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
             return fail(IMM3_ERR_ARG, "MAX over strings wider than " + std::to_string(kStrMaxWidth) + " bytes is not supported on the GPU path");
     }
     q->is_agg = true;
+    q->agg_wide_key = key_bytes > 8;
     q->group_cols.assign(group_cols, group_cols + n_group);
     q->aggs.assign(aggs, aggs + n_aggs);
     {   // SelectOp fused into the aggregation launch (k_group_agg_lanes' FUSED instances; whether the lanes form takes the query is
@@ -2586,7 +2589,7 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
             ok = ok && !fp.pfor && (fp.kind == KIND_I8 || fp.kind == KIND_I32) && col_flat(seg->cols[(size_t)fp.seg_col]) != nullptr;
         q->agg_fusable = ok;
     }
-    // table capacity: twice the number of possible groups, bounded by the rows and by 2^27 slots
+    // table capacity: twice the number of possible groups, bounded by the rows and by 2^27 slots (a wide key's domain saturates)
     double domain = 1.0;
     for (int b = 0; b < key_bytes; ++b) domain *= 256.0;
     const double bound = std::min<double>(domain, (double)std::max<int64_t>(q->n_rows, 1));
@@ -2617,7 +2620,16 @@ extern "C" int imm3_query_create_agg(imm3_ctx *ctx, const imm3_segment *seg,
                                      const int32_t *group_cols, int32_t n_group,
                                      const imm3_aggregate *aggs, int32_t n_aggs,
                                      int32_t table_block_size, imm3_query **out) {
-    return query_create_agg_impl(ctx, seg, nullptr, used_cols, n_used, sels, n_sels, group_cols, n_group, aggs, n_aggs, table_block_size, out);
+    return query_create_agg_impl(ctx, seg, nullptr, used_cols, n_used, sels, n_sels, group_cols, n_group, aggs, n_aggs, table_block_size, out, false);
+}
+
+extern "C" int imm3_query_create_agg_wide(imm3_ctx *ctx, const imm3_segment *seg,
+                                          const int32_t *used_cols, int32_t n_used,
+                                          const imm3_select *sels, int32_t n_sels,
+                                          const int32_t *group_cols, int32_t n_group,
+                                          const imm3_aggregate *aggs, int32_t n_aggs,
+                                          int32_t table_block_size, imm3_query **out) {
+    return query_create_agg_impl(ctx, seg, nullptr, used_cols, n_used, sels, n_sels, group_cols, n_group, aggs, n_aggs, table_block_size, out, true);
 }
 
 extern "C" int imm3_query_create_table_agg(imm3_ctx *ctx, const imm3_table *table,
@@ -2627,7 +2639,17 @@ extern "C" int imm3_query_create_table_agg(imm3_ctx *ctx, const imm3_table *tabl
                                            const imm3_aggregate *aggs, int32_t n_aggs,
                                            int32_t table_block_size, imm3_query **out) {
     if (!table || table->segs.empty()) return fail(IMM3_ERR_ARG, "table is null or empty");
-    return query_create_agg_impl(ctx, table->segs[0], table, used_cols, n_used, sels, n_sels, group_cols, n_group, aggs, n_aggs, table_block_size, out);
+    return query_create_agg_impl(ctx, table->segs[0], table, used_cols, n_used, sels, n_sels, group_cols, n_group, aggs, n_aggs, table_block_size, out, false);
+}
+
+extern "C" int imm3_query_create_table_agg_wide(imm3_ctx *ctx, const imm3_table *table,
+                                                const int32_t *used_cols, int32_t n_used,
+                                                const imm3_select *sels, int32_t n_sels,
+                                                const int32_t *group_cols, int32_t n_group,
+                                                const imm3_aggregate *aggs, int32_t n_aggs,
+                                                int32_t table_block_size, imm3_query **out) {
+    if (!table || table->segs.empty()) return fail(IMM3_ERR_ARG, "table is null or empty");
+    return query_create_agg_impl(ctx, table->segs[0], table, used_cols, n_used, sels, n_sels, group_cols, n_group, aggs, n_aggs, table_block_size, out, true);
 }
 
 static void fill_agg_args(const imm3_query *q, AggArgs &a) {
@@ -2685,6 +2707,8 @@ static void fill_agg_args(const imm3_query *q, AggArgs &a) {
     a.out_first = q->d_ofirst;
     a.out_counts = q->d_ocounts;
     a.out_vals = q->d_ovals;
+    a.wide_key = q->agg_wide_key ? 1 : 0;
+    a.hash_mask = q->ctx->filter_variant == TV_AGG_WEAK_HASH ? 0x7u : 0xFFFFFFFFu;
 }
 
 static void agg_launch_args(const imm3_query *q, AggArgs &a) {
@@ -2796,16 +2820,19 @@ static int settle_groups(imm3_query *q, uint32_t *n_groups) {
 
 int imm3::query_groups(imm3_query *q, uint32_t *n_groups) { return settle_groups(q, n_groups); }
 
+// bytes of the packed group key: the group columns' widths
+static int32_t agg_key_bytes(const imm3_query *q) {
+    int32_t kb = 0;
+    for (int32_t g : q->group_cols) kb += q->seg->cols[(size_t)q->used[(size_t)g]].width;
+    return kb;
+}
+
 extern "C" int imm3_query_agg_shape(const imm3_query *q, int32_t *n_group_cols, int32_t *n_aggs, int32_t *key_bytes) {
     if (!q) return fail(IMM3_ERR_ARG, "query is null");
     if (!q->is_agg) return fail(IMM3_ERR_ARG, "not an aggregation query");
     if (n_group_cols) *n_group_cols = (int32_t)q->group_cols.size();
     if (n_aggs) *n_aggs = (int32_t)q->aggs.size();
-    if (key_bytes) {
-        int32_t kb = 0;
-        for (int32_t g : q->group_cols) kb += q->seg->cols[(size_t)q->used[(size_t)g]].width;
-        *key_bytes = kb;
-    }
+    if (key_bytes) *key_bytes = agg_key_bytes(q);
     return IMM3_OK;
 }
 
@@ -2814,12 +2841,36 @@ extern "C" int imm3_query_group_count(imm3_query *q, uint32_t *n_groups) {
     return settle_groups(q, n_groups);
 }
 
+// A wide-key query's packed key bytes of its n dense groups (k_group_collect's order), key_bytes each, gathered at their first rows
+static int gather_group_keys(imm3_query *q, uint32_t n, std::vector<uint8_t> &out) {
+    imm3_ctx *ctx = q->ctx;
+    const int32_t kb = agg_key_bytes(q);
+    out.assign((size_t)n * (size_t)kb, 0);
+    if (!n || !kb) return IMM3_OK;
+    std::unique_ptr<void, std::function<void(void *)>> d(nullptr, [ctx](void *p) { pool_release(ctx, p); });
+    void *p = nullptr;
+    HIPCHK(pool_alloc(ctx, &p, out.size()));
+    d.reset(p);
+    AggArgs a;
+    fill_agg_args(q, a);
+    launch_group_keys(a, n, kb, (uint8_t *)p, ctx->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out.data(), p, out.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return IMM3_OK;
+}
+
 extern "C" int imm3_query_fetch_groups(imm3_query *q, uint64_t *keys, uint32_t *first_row, uint64_t *counts, int64_t *vals, uint32_t max_groups) {
     if (!q) return fail(IMM3_ERR_ARG, "query is null");
     CTX_LIVE(q->ctx);
     uint32_t n = 0;
     const int rc = settle_groups(q, &n);
     if (rc) return rc;
+    std::vector<uint8_t> wk; // a wide key: its bytes (the table holds tags), keys[g] = the first 8 of them little-endian
+    if (q->agg_wide_key && keys) {
+        const int grc = gather_group_keys(q, n, wk);
+        if (grc) return grc;
+    }
     std::vector<unsigned long long> hk(n), hc(n);
     std::vector<uint32_t> hf(n);
     std::vector<long long> hv((size_t)n * kMaxAggs);
@@ -2837,7 +2888,12 @@ extern "C" int imm3_query_fetch_groups(imm3_query *q, uint64_t *keys, uint32_t *
     const size_t na = q->aggs.size();
     for (uint32_t o = 0; o < n && o < max_groups; ++o) {
         const uint32_t i = order[o];
-        if (keys) keys[o] = hk[i];
+        if (keys && q->agg_wide_key) {
+            const size_t kb = (size_t)agg_key_bytes(q);
+            uint64_t k = 0;
+            for (size_t b = 0; b < 8 && b < kb; ++b) k |= (uint64_t)wk[(size_t)i * kb + b] << (8 * b);
+            keys[o] = k;
+        } else if (keys) keys[o] = hk[i];
         if (first_row) first_row[o] = hf[i];
         if (counts) counts[o] = hc[i];
         if (vals)
@@ -2891,6 +2947,41 @@ extern "C" int imm3_query_fetch_group_strings(imm3_query *q, int32_t agg, uint8_
             const unsigned long long v = (unsigned long long)hv[(size_t)i * kMaxAggs + (size_t)agg];
             for (size_t b = 0; b < w; ++b) dst[b] = (uint8_t)(v >> (8 * (w - 1 - b)));
         }
+    }
+    return IMM3_OK;
+}
+
+extern "C" int imm3_query_fetch_group_keys(imm3_query *q, uint8_t *out, uint32_t max_groups) {
+    if (!q) return fail(IMM3_ERR_ARG, "query is null");
+    if (!q->is_agg) return fail(IMM3_ERR_ARG, "not an aggregation query");
+    if (!out && max_groups > 0) return fail(IMM3_ERR_ARG, "out is null");
+    CTX_LIVE(q->ctx);
+    uint32_t n = 0;
+    const int rc = settle_groups(q, &n);
+    if (rc) return rc;
+    hipStream_t s = q->ctx->stream;
+    const size_t kb = (size_t)agg_key_bytes(q);
+    std::vector<uint32_t> hf(n);
+    std::vector<unsigned long long> hk(q->agg_wide_key ? 0 : n);
+    std::vector<uint8_t> wk;
+    if (n) {
+        HIPCHK(hipMemcpyAsync(hf.data(), q->d_ofirst, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        if (!q->agg_wide_key) HIPCHK(hipMemcpyAsync(hk.data(), q->d_okeys, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    if (q->agg_wide_key) {
+        const int grc = gather_group_keys(q, n, wk);
+        if (grc) return grc;
+    }
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return hf[x] < hf[y]; }); // imm3_query_fetch_groups' order
+    for (uint32_t o = 0; o < n && o < max_groups; ++o) {
+        const uint32_t i = order[o];
+        uint8_t *dst = out + (size_t)o * kb;
+        if (q->agg_wide_key) std::memcpy(dst, wk.data() + (size_t)i * kb, kb);
+        else // (<= 8 bytes: the u64 key, little-endian)
+            for (size_t b = 0; b < kb; ++b) dst[b] = (uint8_t)(hk[i] >> (8 * b));
     }
     return IMM3_OK;
 }

@@ -484,6 +484,8 @@ extern "C" int imm3_comm_merge_groups(imm3_comm *c, imm3_query *const *queries, 
             kinds[j] = q0->aggs[j].kind;
             is_str[j] = q0->seg->cols[(size_t)q0->used[(size_t)q0->aggs[j].column]].vcodec == IMM3_DENSE_STRING;
         }
+        for (int32_t i = 0; i < n_queries && local_rc == IMM3_OK; ++i) // (... and u64 keys: never a wide key's prefix)
+            if (queries[i]->agg_wide_key) local_fail(IMM3_ERR_ARG, "a group key wider than 8 bytes cannot be merged (imm3_query_fetch_group_keys gives each query's keys)");
         for (int32_t i = 0; i < n_queries && local_rc == IMM3_OK; ++i) // (the tables below hold 8 bytes per value: never a wide value's prefix)
             for (int32_t j = 0; j < (int32_t)queries[i]->aggs.size(); ++j)
                 if (queries[i]->d_chunks[j]) {

@@ -71,6 +71,7 @@ enum TuningVariant : int {
     TV_LIMIT_NO_FUSED_GATHER = 15, // a small limit takes k_scan + k_gather instead of k_limit_gather
     TV_NO_CU_RESERVATION = 16,  // one-launch projections use every CU while a communicator is attached
     TV_AGG_SELECT_LAUNCH = 17,  // an aggregation's select chain runs as its own launch, not inside the aggregation launch
+    TV_AGG_WEAK_HASH = 18,      // group keys wider than 8 bytes hash to 3 bits: distinct keys collide by construction (tests of the key compare)
     TV_EAGER_BITMAP = 19,       // a projection through survivor records stores its bitmap in the staging launch
     TV_TILE_ABLATION = 20,      // 20 .. 22: k_filter_tile's ablation switches (tools' build only)
     TV_EMIT_ABLATION = 34,      // 34 .. 35: k_emit's ablation switches (tools' build only)
@@ -303,6 +304,7 @@ struct imm3_query {
     uint64_t *d_alive[imm3::kMaxAggs] = {nullptr, nullptr, nullptr, nullptr};
     unsigned long long *d_chunks[imm3::kMaxAggs] = {nullptr, nullptr, nullptr, nullptr};
     uint32_t out_cap = 0;
+    bool agg_wide_key = false;         // group key wider than 8 bytes (the _wide entry points): tables hold tags (AggArgs::wide_key)
     bool agg_fusable = false;          // the select chain is closed intervals over <= 2 dense int8 / int32 columns of one uniform segment (or empty): the aggregation kernel can evaluate it itself
     uint64_t limit_gather_gave_up = 0; // times settle_rows found k_limit_gather's give-up tag and gathered the rows again with k_scan + k_gather
     int32_t agg_first_form = imm3::AGG_FORM_LANES; // first kernel form to try: raised past the forms this query's keys overflowed

@@ -433,7 +433,12 @@ struct AggArgs {
     uint32_t *out_first;
     unsigned long long *out_counts;
     long long *out_vals;
+    // group key wider than 8 bytes (wide_key = 1; only the general kernel's KEYW instance): a table's u64 is a TAG, hash32 << 32 |
+    // rep_row, and the key bytes are read from the group columns at rep_row.  GroupCol::shift is not used then.
+    int32_t wide_key;
+    uint32_t hash_mask;          // hash32 &= hash_mask: all ones, or a few bits under TV_AGG_WEAK_HASH (collisions by construction)
 };
+constexpr int kGroupKeyMaxWidth = 256; // widest group key of the wide entry points (IMM3_GROUP_KEY_MAX_WIDTH)
 
 int launch_group_agg(const AggArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // returns the AggForm it launched
 bool group_agg_fuses_select(const AggArgs &a); // would launch_group_agg run a form that evaluates a.fused[] itself (no select launch needed)?
@@ -479,6 +484,9 @@ void launch_group_collect(const AggArgs &a, hipStream_t s);
 void launch_strmax_init(const AggArgs &a, hipStream_t s);
 void launch_strmax_refine(const AggArgs &a, int j, int k, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 void launch_strmax_collect(const AggArgs &a, int j, uint32_t n_groups, uint8_t *out, hipStream_t s);
+// wide keys: the packed key bytes (the group columns' raw bytes in order, key_bytes per group) of every dense group, read at its
+// first row (k_group_collect's order: after it)
+void launch_group_keys(const AggArgs &a, uint32_t n_groups, int key_bytes, uint8_t *out, hipStream_t s);
 
 constexpr int kSubTallies = 32;                       // in-kernel count reduce: sub-tallies (finish_add, imm3_device.h)
 constexpr int kFinishWords = 16 + kSubTallies * 16;   // u64 words of a query's `finish` block: header (9 used, padded to a 128-byte line) + one line per sub-tally

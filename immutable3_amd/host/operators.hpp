@@ -220,9 +220,11 @@ class ScanOp : public ColumnVectorOperator {
             sels[i].match_lens = lens[i].data();
             sels[i].n_match = (int32_t)lens[i].size();
         }
-        imm3Check(imm3_query_create_agg(sm_.ctx(), sm_.deviceSegment(tableName_, segIdx_), used.data(), (int32_t)used.size(),
-                                        sels.data(), (int32_t)sels.size(), group.data(), (int32_t)group.size(),
-                                        aggs.data(), (int32_t)aggs.size(), t.blockSize, &h.q));
+        int keyBytes = 0; // a group key wider than 8 bytes: the _wide entry point
+        for (int32_t g : group) keyBytes += cols_[(size_t)g].width();
+        imm3Check((keyBytes > 8 ? imm3_query_create_agg_wide : imm3_query_create_agg)(
+            sm_.ctx(), sm_.deviceSegment(tableName_, segIdx_), used.data(), (int32_t)used.size(), sels.data(), (int32_t)sels.size(),
+            group.data(), (int32_t)group.size(), aggs.data(), (int32_t)aggs.size(), t.blockSize, &h.q));
     }
 
     std::unique_ptr<Iterator<ColumnVectorBatch>> batches(const std::vector<Leaf> &leaves) const {
@@ -504,8 +506,11 @@ class ProjectAggOp : public Operator<AggMapTuple> {
         }
         auto scanOp = std::dynamic_pointer_cast<ScanOp>(op_);
         QueryHandle h;
-        imm3Check(imm3_query_create_table_agg(scanOp->manager().ctx(), table, usedIdx.data(), (int32_t)usedIdx.size(), sels.data(), (int32_t)sels.size(),
-                                              group.data(), (int32_t)group.size(), abi.data(), (int32_t)abi.size(), scanOp->table().blockSize, &h.q));
+        int keyBytes = 0; // a group key wider than 8 bytes: the _wide entry point
+        for (int32_t g : group) keyBytes += cols[(size_t)g].width();
+        imm3Check((keyBytes > 8 ? imm3_query_create_table_agg_wide : imm3_query_create_table_agg)(
+            scanOp->manager().ctx(), table, usedIdx.data(), (int32_t)usedIdx.size(), sels.data(), (int32_t)sels.size(),
+            group.data(), (int32_t)group.size(), abi.data(), (int32_t)abi.size(), scanOp->table().blockSize, &h.q));
         return decode(h, cols, group, aggs, abi);
     }
 
@@ -527,6 +532,14 @@ class ProjectAggOp : public Operator<AggMapTuple> {
             wide[j].resize((size_t)n * (size_t)w);
             imm3Check(imm3_query_fetch_group_strings(h.q, (int32_t)j, wide[j].data(), n));
         }
+        // the packed group keys: from the u64 keys, or (a key wider than 8 bytes) from the device
+        size_t keyBytes = 0;
+        for (int32_t gc : group) keyBytes += (size_t)cols[(size_t)gc].width();
+        std::vector<uint8_t> packed((size_t)n * keyBytes);
+        if (keyBytes > 8) imm3Check(imm3_query_fetch_group_keys(h.q, packed.data(), n));
+        else
+            for (uint32_t g = 0; g < n; ++g)
+                for (size_t b = 0; b < keyBytes; ++b) packed[(size_t)g * keyBytes + b] = (uint8_t)(keys[g] >> (8 * b));
         std::vector<AggMapTuple> items;
         for (uint32_t g = 0; g < n; ++g) {
             std::string key;
@@ -534,12 +547,10 @@ class ProjectAggOp : public Operator<AggMapTuple> {
             for (size_t k = 0; k < group.size(); ++k) {
                 const Column &c = cols[(size_t)group[k]];
                 const int w = c.width();
-                uint8_t raw[8] = {0};
-                for (int b = 0; b < w; ++b) raw[b] = (uint8_t)(keys[g] >> (8 * (off + b)));
                 ColumnVector v;
                 v.type = c.columnType;
                 v.width = w;
-                v.data = raw;
+                v.data = packed.data() + (size_t)g * keyBytes + (size_t)off;
                 if (k) key += "_";
                 key += v.value(0).toString(); // mkString("_"), ProjectAggregate.scala:144
                 off += w;

@@ -36,6 +36,7 @@ EXPORTS = [
     "imm3_query_segment_starts", "imm3_query_locate_rows",
     "imm3_query_create", "imm3_query_create_agg", "imm3_query_group_count", "imm3_query_fetch_groups", "imm3_query_agg_shape",
     "imm3_query_fetch_group_strings", "imm3_query_destroy", "imm3_query_reserve_rows",
+    "imm3_query_create_agg_wide", "imm3_query_create_table_agg_wide", "imm3_query_fetch_group_keys",
     "imm3_query_run", "imm3_query_run_select", "imm3_query_run_count", "imm3_query_sync", "imm3_query_join_count", "imm3_query_log_counts",
     "imm3_query_layout", "imm3_query_batches", "imm3_query_count", "imm3_query_bitmap",
     "imm3_query_row_count", "imm3_query_fetch_rows", "imm3_query_device_ptr",
@@ -146,6 +147,9 @@ def load() -> C.CDLL:
     L.imm3_query_group_count.argtypes = [vp, P(C.c_uint32)]
     L.imm3_query_fetch_groups.argtypes = [vp, vp, vp, vp, vp, C.c_uint32]
     L.imm3_query_fetch_group_strings.argtypes = [vp, i32, vp, C.c_uint32]
+    L.imm3_query_create_agg_wide.argtypes = [vp, vp, vp, i32, P(CSelect), i32, vp, i32, vp, i32, i32, P(vp)]
+    L.imm3_query_create_table_agg_wide.argtypes = [vp, vp, vp, i32, P(CSelect), i32, vp, i32, vp, i32, i32, P(vp)]
+    L.imm3_query_fetch_group_keys.argtypes = [vp, vp, C.c_uint32]
     L.imm3_query_destroy.argtypes = [vp]
     L.imm3_query_reserve_rows.argtypes = [vp, u64]
     L.imm3_query_run.argtypes = [vp]
@@ -458,6 +462,8 @@ class DeviceSegment:
 AGG_COUNT, AGG_MIN, AGG_MAX, AGG_SUM = 0, 1, 2, 3
 # the aggregation's kernel forms (csrc/imm3_internal.h: AggForm; DeviceQuery.agg_form, tuning 100 + form)
 AGG_FORM_LANES, AGG_FORM_LANES_WIDE, AGG_FORM_DIRECT, AGG_FORM_TILE, AGG_FORM_GENERAL = 0, 1, 2, 3, 4
+GROUP_KEY_MAX_WIDTH = 256  # include/imm3.h: IMM3_GROUP_KEY_MAX_WIDTH (DeviceQuery(..., wide_keys=True))
+TV_AGG_WEAK_HASH = 18      # tuning variant: wide group keys hash to 3 bits (csrc/imm3_handles.h)
 
 
 class DeviceTable:
@@ -488,7 +494,9 @@ class DeviceQuery:
 
     def __init__(self, ctx: Context, seg: DeviceSegment, used_cols: Sequence[int],
                  sels: Sequence[tuple], proj: Sequence[int] = (), limit: int = 0, table_block_size: int = 1024,
-                 group_cols: Optional[Sequence[int]] = None, aggs: Optional[Sequence[tuple]] = None):
+                 group_cols: Optional[Sequence[int]] = None, aggs: Optional[Sequence[tuple]] = None,
+                 wide_keys: bool = False):
+        """wide_keys: an aggregation through the _wide entry points (group keys of up to GROUP_KEY_MAX_WIDTH bytes)."""
         self.ctx, self.seg = ctx, seg
         self.used_cols = list(used_cols)
         self.proj = list(proj)
@@ -516,7 +524,10 @@ class DeviceQuery:
         self._h = C.c_void_p()
         self.is_table = isinstance(seg, DeviceTable)
         create = load().imm3_query_create_table if self.is_table else load().imm3_query_create
-        create_agg = load().imm3_query_create_table_agg if self.is_table else load().imm3_query_create_agg
+        if wide_keys:
+            create_agg = load().imm3_query_create_table_agg_wide if self.is_table else load().imm3_query_create_agg_wide
+        else:
+            create_agg = load().imm3_query_create_table_agg if self.is_table else load().imm3_query_create_agg
         if self.aggs is not None:
             gc = np.array(self.group_cols or [0], dtype=np.int32)
             ag = np.array([[k, c] for (k, c) in self.aggs] or [[0, 0]], dtype=np.int32)
@@ -629,6 +640,17 @@ class DeviceQuery:
         out = np.zeros((max(g, 1), width), np.uint8)
         _check(load().imm3_query_fetch_group_strings(self._h, j, out.ctypes.data, g))
         return out[:g]
+
+    def fetch_group_keys(self) -> np.ndarray:
+        """Every group's packed key bytes (the group columns' raw bytes in order): uint8[g, key_bytes], fetch_groups' order."""
+        n = C.c_uint32(0)
+        _check(load().imm3_query_group_count(self._h, C.byref(n)))
+        g = n.value
+        kb = C.c_int32(0)
+        _check(load().imm3_query_agg_shape(self._h, None, None, C.byref(kb)))
+        out = np.zeros((max(g, 1), max(kb.value, 1)), np.uint8)
+        _check(load().imm3_query_fetch_group_keys(self._h, out.ctypes.data, g))
+        return out[:g, : kb.value]
 
     def plan(self) -> dict:
         """How the library planned this query (include/imm3_diag.h: imm3_query_plan)."""

@@ -588,18 +588,21 @@ class ProjectAggOp(Operator):
             pass
         scan = _S()
         scan.cols = list(cols)
+        widths = [scan.cols[i].width for i in group_idx]
+        wide_key = sum(widths) > 8            # a key wider than 8 bytes: the _wide entry points, the key bytes from the device
         q = native.DeviceQuery(seg.ctx, seg, used_idx, sels, (), 0, block_size,
-                               group_cols=group_idx, aggs=[(a.kind, colnames.index(a.col)) for a in aggs])
+                               group_cols=group_idx, aggs=[(a.kind, colnames.index(a.col)) for a in aggs],
+                               wide_keys=wide_key)
         q.run()
         keys, first, counts, vals = q.fetch_groups()
+        key_bytes = q.fetch_group_keys() if wide_key else None
         # a MaxStringAggr over a column wider than 8 bytes: vals hold its first 8 bytes, the exact value comes from the device
         wide = {j: q.fetch_group_strings(j) for j, a in enumerate(aggs)
                 if a.kind == native.AGG_MAX and scan.cols[colnames.index(a.col)].columnType == "STRING"
                 and scan.cols[colnames.index(a.col)].width > 8}
         q.close()
-        widths = [scan.cols[i].width for i in group_idx]
         for g in range(keys.shape[0]):
-            raw = int(keys[g]).to_bytes(8, "little")
+            raw = bytes(key_bytes[g]) if wide_key else int(keys[g]).to_bytes(8, "little")
             parts, off = [], 0
             for i, w in zip(group_idx, widths):
                 parts.append(_key_part(scan.cols[i], raw[off: off + w]))

@@ -162,6 +162,8 @@ int imm3_segment_bytes(const imm3_segment *seg, uint64_t *device_bytes);
 enum { IMM3_AGG_COUNT = 0, IMM3_AGG_MIN = 1, IMM3_AGG_MAX = 2, IMM3_AGG_SUM = 3 };
 /* widest STRING column that IMM3_AGG_MAX takes on the GPU path (bytes) */
 #define IMM3_STRING_MAX_WIDTH 256
+/* widest group key (the sum of the group columns' widths) that the _wide aggregation entry points take (bytes) */
+#define IMM3_GROUP_KEY_MAX_WIDTH 256
 typedef struct {
     int32_t kind;
     int32_t column;
@@ -229,6 +231,22 @@ int imm3_query_create_agg(imm3_ctx *ctx, const imm3_segment *seg,
                           const int32_t *group_cols, int32_t n_group,
                           const imm3_aggregate *aggs, int32_t n_aggs,
                           int32_t table_block_size, imm3_query **out);
+/* The same with group keys of 0 .. IMM3_GROUP_KEY_MAX_WIDTH bytes (still at most 4 group columns; wider: IMM3_ERR_ARG).  The
+ * arguments are those of imm3_query_create_agg / imm3_query_create_table_agg.  A key of <= 8 bytes takes exactly the path of those
+ * (validation, plan, kernels, results).  A wider key is compared byte for byte on the device; imm3_query_fetch_groups then gives
+ * its first 8 bytes and imm3_query_fetch_group_keys the whole key.  The merges refuse a query with such a key. */
+int imm3_query_create_agg_wide(imm3_ctx *ctx, const imm3_segment *seg,
+                               const int32_t *used_cols, int32_t n_used,
+                               const imm3_select *sels, int32_t n_sels,
+                               const int32_t *group_cols, int32_t n_group,
+                               const imm3_aggregate *aggs, int32_t n_aggs,
+                               int32_t table_block_size, imm3_query **out);
+int imm3_query_create_table_agg_wide(imm3_ctx *ctx, const imm3_table *table,
+                                     const int32_t *used_cols, int32_t n_used,
+                                     const imm3_select *sels, int32_t n_sels,
+                                     const int32_t *group_cols, int32_t n_group,
+                                     const imm3_aggregate *aggs, int32_t n_aggs,
+                                     int32_t table_block_size, imm3_query **out);
 int imm3_query_group_count(imm3_query *q, uint32_t *n_groups);
 /* The shape of an aggregation query's result rows: group columns, aggregates (the stride of `vals` in imm3_query_fetch_groups and
  * imm3_comm_merge_groups[_all]), bytes of the packed group key.  A binding sizes its buffers from THIS, not from what its caller
@@ -238,7 +256,9 @@ int imm3_query_agg_shape(const imm3_query *q, int32_t *n_group_cols, int32_t *n_
  * the group; counts: selected rows of the group; vals[g * n_aggs + j]: COUNT -> the count, MIN/MAX numeric -> the
  * int32 value sign-extended, SUM -> the exact int64 sum of the group's selected values (<= 2^32 rows x 2^31: no
  * overflow), MAX string -> the value's bytes packed big-endian (a column wider than 8 bytes: its FIRST 8 bytes packed
- * big-endian; the whole value comes from imm3_query_fetch_group_strings).  Sorted by first_row. */
+ * big-endian; the whole value comes from imm3_query_fetch_group_strings).  Sorted by first_row.
+ * A group key wider than 8 bytes (the _wide entry points): keys[g] holds its FIRST 8 bytes little-endian -- the same packing as a
+ * narrow key's, so distinct groups may share keys[g]; the whole key comes from imm3_query_fetch_group_keys. */
 int imm3_query_fetch_groups(imm3_query *q, uint64_t *keys, uint32_t *first_row, uint64_t *counts, int64_t *vals,
                             uint32_t max_groups);
 /* The exact value of the string MAX aggregate `agg` (index into aggs) of every group: the column's width in bytes per group
@@ -246,6 +266,11 @@ int imm3_query_fetch_groups(imm3_query *q, uint64_t *keys, uint32_t *first_row, 
  * imm3_query_fetch_groups; any width, narrow columns included.  IMM3_ERR_ARG when `agg` is out of range or is not a MAX over
  * a STRING column. */
 int imm3_query_fetch_group_strings(imm3_query *q, int32_t agg, uint8_t *out, uint32_t max_groups);
+/* The packed group key of every group: the group columns' raw bytes in group_cols order, key_bytes (imm3_query_agg_shape) per group
+ * (out[g * key_bytes .. g * key_bytes + key_bytes)).  Groups in the order of imm3_query_fetch_groups; any key width, narrow keys
+ * included (there: byte for byte the u64 keys, little-endian).  IMM3_ERR_ARG for a query that is not an aggregation,
+ * IMM3_ERR_STATE before its first run. */
+int imm3_query_fetch_group_keys(imm3_query *q, uint8_t *out, uint32_t max_groups);
 
 /* Pre-size the projected-row buffers so that not even the FIRST imm3_query_run() has to wait for the count.  Without it an
  * unlimited projection sizes them once: a query whose SELECT list is predicate columns only (it runs as ONE launch that
@@ -370,7 +395,8 @@ int imm3_comm_allreduce_count_all(imm3_comm *const *comms, int32_t n_comms, imm3
  * device hash table per rank, exchanged as an ncclAllGather of the ranks' group lists and merged again on the device.  One rank:
  * the same merge over that rank's queries, no collective.
  *   keys / counts / vals as imm3_query_fetch_groups; first[g] = segment << 32 | first selected row of the group there.
- * A query with a MAX over a STRING column wider than 8 bytes is refused (IMM3_ERR_ARG): such maxima are not merged.
+ * A query with a MAX over a STRING column wider than 8 bytes, or with a group key wider than 8 bytes (imm3_query_create_agg_wide), is
+ * refused (IMM3_ERR_ARG): such maxima and keys are not merged.
  * Synchronous (the merged table is returned to the host). */
 int imm3_comm_merge_groups(imm3_comm *c, imm3_query *const *queries, const int32_t *segment_index, int32_t n_queries,
                            uint64_t *keys, uint64_t *first, uint64_t *counts, int64_t *vals, uint32_t max_groups, uint32_t *n_groups);

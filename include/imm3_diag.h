@@ -50,7 +50,8 @@ int imm3_ctx_measure_read_gbps(imm3_ctx *ctx, uint64_t bytes, int32_t iters, dou
  * 15 = a small limit behind a limit scan takes k_scan + k_gather instead of the one fused launch (k_limit_gather),
  * 16 = one-launch projections use every CU even while a communicator whose collectives launch kernels is attached (default: one
  * CU per XCD is left to the collective's kernel), 17 = an aggregation's select chain runs as its own launch instead of inside the
- * aggregation launch, 19 = a projection through survivor records stores its bitmap in the staging launch (default: the bitmap is
+ * aggregation launch, 18 = group keys wider than 8 bytes hash to 3 bits, so that distinct keys collide by construction (tests of
+ * the exactness of the key compare), 19 = a projection through survivor records stores its bitmap in the staging launch (default: the bitmap is
  * materialised when imm3_query_bitmap asks), 20 - 22 and 34 - 35 = ablation switches of k_filter_tile and k_emit (tools' build,
  * libimm3_ablate.so, only), 50 + mask = ablation mask of k_filter_project (tools' build), 100 + AggForm = the aggregation starts at
  * that kernel form, 140 and above = aggregation ablations (tools' build), 200 + P = fixed tiles per range.  The names of these
