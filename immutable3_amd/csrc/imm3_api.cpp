@@ -53,17 +53,6 @@ hipError_t imm3::pool_alloc(imm3_ctx *ctx, void **out, size_t bytes) { return (h
 void imm3::pool_release(imm3_ctx *ctx, void *p) { ctx->blocks.release(p); }
 static void pool_drain(imm3_ctx *ctx) { ctx->blocks.drain(); }
 
-// ---------------------------------------------------------------------------------------------
-// scalar rules shared with the reference (JVM d2i / i2b): Select.scala:65,73; SURVEY Appendix A.1 rule 5
-// ---------------------------------------------------------------------------------------------
-static int32_t jvm_d2i(double d) {
-    if (d != d) return 0;
-    if (d >= 2147483647.0) return INT32_MAX;
-    if (d <= -2147483648.0) return INT32_MIN;
-    return (int32_t)d;
-}
-static int32_t jvm_d2b(double d) { return (int32_t)(int8_t)(uint8_t)((uint32_t)jvm_d2i(d) & 0xFFu); }
-
 static const char *cond_name(int c) {
     switch (c) {
     case IMM3_MATCH: return "Match";
@@ -878,6 +867,10 @@ static void query_free(imm3_query *q) {
     pool_release(ctx, q->d_row_index);
     for (auto p : q->d_proj) pool_release(ctx, p);
     for (auto &p : q->preds) pool_release(ctx, p.d_blob);
+    for (auto &t : q->expr_terms)
+        for (auto &p : t) pool_release(ctx, p.d_blob);
+    pool_release(ctx, q->d_expr_preds);
+    pool_release(ctx, q->d_expr_term_start);
     pool_release(ctx, q->d_stage_rec);
     pool_release(ctx, q->d_tile_start);
     pool_release(ctx, q->d_desc);
@@ -1074,41 +1067,85 @@ static int fold_selects(imm3_query *q, const imm3_select *sels, int32_t n_sels) 
     for (int32_t i = 0; i < n_sels; ++i) {
         const int32_t sci = q->used[(size_t)sels[i].column];
         const SegCol &sc = q->seg->cols[(size_t)sci];
+        FoldedPred leaf; // (one leaf alone, then the conjunction with what the column has so far: imm3_expr_norm.cpp)
+        const int rc = leaf_pred(sci, sc.vcodec, sc.width, sels[i], leaf);
+        if (rc) return rc;
         FoldedPred *fp = pred_on(q->preds, sci);
-        const bool fresh = !fp;
-        if (fresh) {
-            q->preds.push_back(unfolded_pred(sci, sc.vcodec, sc.width));
-            fp = &q->preds.back();
-        }
-        if (fp->kind == KIND_STR) {
-            std::vector<std::string> vals;
-            int64_t off = 0;
-            for (int32_t m = 0; m < sels[i].n_match; ++m) {
-                const int32_t len = sels[i].match_lens[m];
-                if (len < 0) return fail(IMM3_ERR_ARG, "negative match length");
-                // String.equals can only hold for a value of exactly `width` bytes (DataType.scala:69-70)
-                if (len == sc.width) {
-                    std::string v((const char *)sels[i].match_bytes + off, (size_t)len);
-                    if (std::find(vals.begin(), vals.end(), v) == vals.end()) vals.push_back(v);
-                }
-                off += len;
-            }
-            if (fresh) fp->match = vals;
-            else {
-                std::vector<std::string> both;
-                for (auto &v : fp->match)
-                    if (std::find(vals.begin(), vals.end(), v) != vals.end()) both.push_back(v);
-                fp->match = both;
-            }
-        } else {
-            const int64_t t = fp->kind == KIND_I32 ? (int64_t)jvm_d2i(sels[i].value) : (int64_t)jvm_d2b(sels[i].value);
-            if (sels[i].cond == IMM3_GT) fp->lo = std::max(fp->lo, t + 1);      // strict >, Select.scala:68,76
-            else if (sels[i].cond == IMM3_LT) fp->hi = std::min(fp->hi, t - 1); // strict <, Select.scala:106,114
-            else { fp->lo = std::max(fp->lo, t); fp->hi = std::min(fp->hi, t); } // ==, Select.scala:144,152
-        }
+        if (!fp) q->preds.push_back(leaf);
+        else merge_pred(*fp, leaf);
     }
     for (const auto &p : q->preds)
         if (p.kind == KIND_STR ? p.match.empty() : p.lo > p.hi) q->always_false = true;
+    return IMM3_OK;
+}
+
+// Step 3 of a select tree with an OR in it (a segment with batches): its normal form (imm3_expr_norm.cpp) into q->expr_terms; q->preds
+// stays empty.  No term left: the tree selects nothing.
+static int fold_tree(imm3_query *q, const imm3_select *sels, int32_t n_sels, const int32_t *prog, int32_t n_prog) {
+    std::vector<ExprCol> leaf_cols;
+    for (int32_t i = 0; i < n_sels; ++i) {
+        const int32_t sci = q->used[(size_t)sels[i].column];
+        const SegCol &sc = q->seg->cols[(size_t)sci];
+        leaf_cols.push_back(ExprCol{sci, sc.vcodec, sc.width});
+    }
+    const int rc = expr_normalize(leaf_cols, sels, n_sels, prog, n_prog, q->expr_terms);
+    if (rc) return rc;
+    q->is_expr = true;
+    if (q->expr_terms.empty()) q->always_false = true;
+    return IMM3_OK;
+}
+
+static void fill_colpred(const imm3_query *q, const FoldedPred &fp, ColPred &cp);
+static int upload_match_blobs(imm3_query *q, std::vector<FoldedPred> &preds);
+
+// Step 5 of a select tree: which kernel form can take the terms, and the generic form's predicates on the device.  (Compressed
+// predicate columns have been decoded by now: place_compressed finds no folded predicate to fuse into k_filter_pfor.)
+static int expr_setup(imm3_query *q) {
+    if (q->always_false) return IMM3_OK;
+    for (auto &t : q->expr_terms) {
+        const int rc = upload_match_blobs(q, t);
+        if (rc) return rc;
+    }
+    // tile form: <= kMaxExprTerms terms, every predicate of a tile kind, <= 3 distinct columns that make an instantiated combination
+    bool ok = !q->ragged && !q->table && q->expr_terms.size() <= (size_t)kMaxExprTerms;
+    std::vector<std::pair<int32_t, int32_t>> cols; // (tile kind, segment column), in first-seen order
+    for (const auto &t : q->expr_terms)
+        for (const auto &p : t) {
+            const int tk = tile_kind(p);
+            ok = ok && tk != TK_NONE;
+            bool seen = false;
+            for (auto &c : cols) seen = seen || c.second == p.seg_col;
+            if (!seen) cols.emplace_back(tk, p.seg_col);
+        }
+    ok = ok && cols.size() <= (size_t)kMaxTileCols;
+    if (ok) {
+        std::stable_sort(cols.begin(), cols.end(), [](const std::pair<int32_t, int32_t> &x, const std::pair<int32_t, int32_t> &y) { return x.first < y.first; });
+        int n_s2 = 0;
+        for (size_t k = 0; k < cols.size(); ++k) {
+            q->expr_kinds[k] = cols[k].first;
+            q->expr_seg_col[k] = cols[k].second;
+            n_s2 += cols[k].first == TK_S2;
+        }
+        ok = n_s2 <= 1 && filter_tile_group(q->expr_kinds) > 0; // (k_filter_expr is instantiated for k_filter_tile's combinations)
+    }
+    q->expr_tile_ok = ok;
+    // generic form (also what TV_GENERIC_ONLY runs): the predicates term after term
+    q->h_expr_term_start.assign(1, 0);
+    for (const auto &t : q->expr_terms) {
+        for (const auto &p : t) {
+            ColPred cp;
+            fill_colpred(q, p, cp);
+            q->h_expr_preds.push_back(cp);
+        }
+        q->h_expr_term_start.push_back((int32_t)q->h_expr_preds.size());
+    }
+    void *d = nullptr;
+    HIPCHK(pool_alloc(q->ctx, &d, q->h_expr_preds.size() * sizeof(ColPred)));
+    q->d_expr_preds = (ColPred *)d;
+    HIPCHK(pool_alloc(q->ctx, &d, q->h_expr_term_start.size() * sizeof(int32_t)));
+    q->d_expr_term_start = (int32_t *)d;
+    HIPCHK(hipMemcpyAsync(q->d_expr_preds, q->h_expr_preds.data(), q->h_expr_preds.size() * sizeof(ColPred), hipMemcpyHostToDevice, q->ctx->stream));
+    HIPCHK(hipMemcpyAsync(q->d_expr_term_start, q->h_expr_term_start.data(), q->h_expr_term_start.size() * sizeof(int32_t), hipMemcpyHostToDevice, q->ctx->stream));
     return IMM3_OK;
 }
 
@@ -1139,8 +1176,8 @@ static int place_compressed(imm3_query *q, bool have_batches, const std::vector<
 }
 
 // Step 5: IN-lists too long for the kernel arguments go to the device.
-static int upload_match_blobs(imm3_query *q) {
-    for (auto &p : q->preds) {
+static int upload_match_blobs(imm3_query *q, std::vector<FoldedPred> &preds) {
+    for (auto &p : preds) {
         if (p.kind != KIND_STR || p.match.empty() || (p.width <= 8 && p.match.size() <= (size_t)kMaxMatch)) continue;
         std::string blob;
         for (auto &v : p.match) blob += v;
@@ -1217,12 +1254,27 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
                                  const int32_t *used_cols, int32_t n_used,
                                  const imm3_select *sels, int32_t n_sels,
                                  const int32_t *proj, int32_t n_proj, int64_t limit,
-                                 int32_t table_block_size, const std::vector<int32_t> &row_cols, imm3_query **out) {
+                                 int32_t table_block_size, const std::vector<int32_t> &row_cols, imm3_query **out,
+                                 const int32_t *prog = nullptr, int32_t n_prog = 0, bool tree = false) {
     if (!seg || !out) return fail(IMM3_ERR_ARG, "null argument");
     *out = nullptr;
     CTX_LIVE(ctx); // (the context's gate is held until creation returns)
     int rc = check_create_args(ctx, seg, table, used_cols, n_used, sels, n_sels, proj, n_proj);
     if (rc) return rc;
+    // A select tree (imm3_query_create_expr): the leaves have passed the checks of a flat list; now the program.  Without an OR it
+    // IS a flat list -- the leaves in program order go through the steps below exactly as imm3_query_create's do.
+    std::vector<imm3_select> flat;
+    bool has_or = false;
+    if (tree) {
+        rc = expr_check_program(prog, n_prog, n_sels, &has_or);
+        if (rc) return rc;
+        if (!has_or) {
+            for (int32_t i = 0; i < n_prog; ++i)
+                if (prog[i] >= 0) flat.push_back(sels[prog[i]]);
+            sels = flat.data();
+            n_sels = (int32_t)flat.size();
+        }
+    }
 
     std::unique_ptr<imm3_query, void (*)(imm3_query *)> q(new imm3_query(), query_free);
     q->ctx = ctx;
@@ -1238,9 +1290,11 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
 
     int32_t nb = 0;
     rc = scan_layout(q.get(), sels, n_sels, nb); if (rc) return rc;
-    if (nb >= 1) { rc = fold_selects(q.get(), sels, n_sels); if (rc) return rc; }
+    if (nb >= 1 && has_or) { rc = fold_tree(q.get(), sels, n_sels, prog, n_prog); if (rc) return rc; }
+    else if (nb >= 1) { rc = fold_selects(q.get(), sels, n_sels); if (rc) return rc; }
     rc = place_compressed(q.get(), nb >= 1, row_cols); if (rc) return rc;
-    rc = upload_match_blobs(q.get()); if (rc) return rc;
+    rc = upload_match_blobs(q.get(), q->preds); if (rc) return rc;
+    if (q->is_expr) { rc = expr_setup(q.get()); if (rc) return rc; }
     rc = alloc_buffers(q.get()); if (rc) return rc;
     rc = plan_projection(q.get()); if (rc) return rc;
     *out = q.release();
@@ -1253,6 +1307,14 @@ extern "C" int imm3_query_create(imm3_ctx *ctx, const imm3_segment *seg,
                                  const int32_t *proj, int32_t n_proj, int64_t limit,
                                  int32_t table_block_size, imm3_query **out) {
     return query_create_impl(ctx, seg, nullptr, used_cols, n_used, sels, n_sels, proj, n_proj, limit, table_block_size, {}, out);
+}
+
+extern "C" int imm3_query_create_expr(imm3_ctx *ctx, const imm3_segment *seg,
+                                      const int32_t *used_cols, int32_t n_used,
+                                      const imm3_select *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog,
+                                      const int32_t *proj, int32_t n_proj, int64_t limit,
+                                      int32_t table_block_size, imm3_query **out) {
+    return query_create_impl(ctx, seg, nullptr, used_cols, n_used, leaves, n_leaves, proj, n_proj, limit, table_block_size, {}, out, prog, n_prog, true);
 }
 
 extern "C" int imm3_query_create_table(imm3_ctx *ctx, const imm3_table *table,
@@ -1527,7 +1589,7 @@ static int run_select(imm3_query *q, unsigned mode) {
         return IMM3_OK;
     }
     // (planned on every run: the tuning variant may have changed since creation)
-    const SelectChain chain = plan_select_chain(q);
+    const SelectChain chain = q->is_expr ? SelectChain() : plan_select_chain(q); // (a select tree is ONE launch of its own: no chain)
     if (q->table && !chain.generic.empty()) return fail(IMM3_ERR_ARG, "table queries support int32 / int8 / 2-byte string predicates (<= 8 IN-list values); use per-segment queries");
     const int fv = ctx->filter_variant;
     int pass = 0;
@@ -1538,7 +1600,8 @@ static int run_select(imm3_query *q, unsigned mode) {
     q->run.ran_single_pass = false;
     // exactly ONE launch in the whole select chain: only then may that launch publish the count (and append to the count
     // log) itself, and only then are the survivors' values staged
-    const bool skip_bitmap = count_only && chain.single_tile_pass && !q->table && !overlap_total && fv != TV_COUNT_BY_K_TOTAL;
+    const bool expr_tile = q->is_expr && q->expr_tile_ok && fv != TV_GENERIC_ONLY;
+    const bool skip_bitmap = count_only && (chain.single_tile_pass || expr_tile) && !q->table && !overlap_total && fv != TV_COUNT_BY_K_TOTAL;
     q->run.bitmap_valid = !skip_bitmap;
     // `limit` stops the scan (Project.scala:73-80; Engine.scala:166,253-258: the reference's workers stall on the full queue once the
     // consumer has its rows): a projection with a limit whose select chain is one tile launch over one uniform segment runs that
@@ -1557,6 +1620,59 @@ static int run_select(imm3_query *q, unsigned mode) {
     li.filter_variant = fv;
     li.n_tiles = q->n_tiles;
     const bool chunked = limit_scan_applies(li);
+    if (q->is_expr) { // the tree's terms, one launch (imm3_expr.hip); `limit` is the gather's to honour
+        LaunchTimer t(ctx, 0);
+        if (expr_tile) {
+            ExprTileArgs a;
+            std::memset(&a, 0, sizeof(a));
+            bool any_i32 = false;
+            int narrow_bytes = 0;
+            for (int k = 0; k < kMaxTileCols; ++k) {
+                a.kinds[k] = q->expr_kinds[k];
+                any_i32 |= a.kinds[k] == TK_I32;
+                narrow_bytes += a.kinds[k] == TK_I8 ? 1 : (a.kinds[k] == TK_S2 ? 2 : 0);
+            }
+            a.n_terms = (int32_t)q->expr_terms.size();
+            for (int ti = 0; ti < a.n_terms; ++ti)
+                for (int k = 0; k < kMaxTileCols && a.kinds[k] != TK_NONE; ++k) {
+                    const FoldedPred *fp = pred_on(q->expr_terms[(size_t)ti], q->expr_seg_col[k]);
+                    if (fp) {
+                        fill_tile_col(q, *fp, a.cols[ti][k], a.kinds[k]);
+                        a.use[ti] |= 1u << k;
+                    } else a.cols[ti][k].data = col_flat(q->seg->cols[(size_t)q->expr_seg_col[k]]); // (not tested in this term)
+                }
+            a.n_rows = q->n_rows;
+            a.n_words = q->n_words;
+            a.n_tiles = q->n_tiles;
+            a.bitmap = skip_bitmap ? nullptr : q->d_bitmap;
+            a.block_partials = q->d_block_partials;
+            grid = filter_grid(q->n_tiles, false, any_i32, ctx->grid_blocks, narrow_bytes);
+            if (!overlap_total && fv != TV_COUNT_BY_K_TOTAL && (grid <= 512 || fv != TV_COUNT_SMALL_GRID)) {
+                a.finish = q->d_total;
+                count_done = true;
+            }
+            if (!launch_filter_expr(a, grid, s, t.start, t.stop)) return fail(IMM3_ERR_ARG, "internal: no tree kernel for this column combination");
+            q->expr_form_ran = 0;
+        } else {
+            ExprGenericArgs a;
+            std::memset(&a, 0, sizeof(a));
+            a.preds = q->d_expr_preds;
+            a.term_start = q->d_expr_term_start;
+            a.n_terms = (int32_t)q->expr_terms.size();
+            a.n_rows = q->n_rows;
+            a.n_words = q->n_words;
+            a.n_tiles = q->n_tiles;
+            a.bitmap = q->d_bitmap;
+            a.block_partials = q->d_block_partials;
+            a.word_row_base = q->d_word_row_base;
+            a.word_nvalid = q->d_word_nvalid;
+            grid = filter_grid(q->n_words, true, false, ctx->grid_blocks);
+            launch_filter_expr_generic(a, grid, s, t.start, t.stop);
+            q->expr_form_ran = 1;
+        }
+        HIPCHK(hipGetLastError());
+        ++pass;
+    }
     for (const auto &take : chain.tile_passes) {
         TileArgs a;
         std::memset(&a, 0, sizeof(a));
@@ -2547,7 +2663,8 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
                                  const imm3_select *sels, int32_t n_sels,
                                  const int32_t *group_cols, int32_t n_group,
                                  const imm3_aggregate *aggs, int32_t n_aggs,
-                                 int32_t table_block_size, imm3_query **out, bool wide_keys) {
+                                 int32_t table_block_size, imm3_query **out, bool wide_keys,
+                                 const int32_t *prog = nullptr, int32_t n_prog = 0, bool tree = false) {
     if (!out) return fail(IMM3_ERR_ARG, "out is null");
     *out = nullptr;
     if (n_group < 0 || n_group > kMaxGroupCols || (n_group > 0 && !group_cols)) return fail(IMM3_ERR_ARG, "0..4 group columns are supported on the GPU path");
@@ -2555,7 +2672,7 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
     imm3_query *q = nullptr;
     std::vector<int32_t> row_cols(group_cols, group_cols + n_group); // read row by row: PFOR_INT ones through their decoded form
     for (int32_t j = 0; j < n_aggs; ++j) row_cols.push_back(aggs[j].column);
-    int rc = query_create_impl(ctx, seg, table, used_cols, n_used, sels, n_sels, nullptr, 0, 0, table_block_size, row_cols, &q);
+    int rc = query_create_impl(ctx, seg, table, used_cols, n_used, sels, n_sels, nullptr, 0, 0, table_block_size, row_cols, &q, prog, n_prog, tree);
     if (rc) return rc;
     std::unique_ptr<imm3_query, void (*)(imm3_query *)> guard(q, query_free);
     int key_bytes = 0;
@@ -2584,7 +2701,8 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
     q->aggs.assign(aggs, aggs + n_aggs);
     {   // SelectOp fused into the aggregation launch (k_group_agg_lanes' FUSED instances; whether the lanes form takes the query is
         // the launcher's call at run time)
-        bool ok = !table && !q->ragged && !q->always_false && has_batches && q->n_rows > 0 && q->preds.size() <= (size_t)kMaxAggPreds;
+        bool ok = !table && !q->ragged && !q->always_false && has_batches && q->n_rows > 0 && q->preds.size() <= (size_t)kMaxAggPreds &&
+                  !q->is_expr; // (a select tree's launch writes the bitmap, the aggregation reads it)
         for (const auto &fp : q->preds)
             ok = ok && !fp.pfor && (fp.kind == KIND_I8 || fp.kind == KIND_I32) && col_flat(seg->cols[(size_t)fp.seg_col]) != nullptr;
         q->agg_fusable = ok;
@@ -2630,6 +2748,15 @@ extern "C" int imm3_query_create_agg_wide(imm3_ctx *ctx, const imm3_segment *seg
                                           const imm3_aggregate *aggs, int32_t n_aggs,
                                           int32_t table_block_size, imm3_query **out) {
     return query_create_agg_impl(ctx, seg, nullptr, used_cols, n_used, sels, n_sels, group_cols, n_group, aggs, n_aggs, table_block_size, out, true);
+}
+
+extern "C" int imm3_query_create_agg_expr(imm3_ctx *ctx, const imm3_segment *seg,
+                                          const int32_t *used_cols, int32_t n_used,
+                                          const imm3_select *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog,
+                                          const int32_t *group_cols, int32_t n_group,
+                                          const imm3_aggregate *aggs, int32_t n_aggs,
+                                          int32_t table_block_size, imm3_query **out) {
+    return query_create_agg_impl(ctx, seg, nullptr, used_cols, n_used, leaves, n_leaves, group_cols, n_group, aggs, n_aggs, table_block_size, out, true, prog, n_prog, true);
 }
 
 extern "C" int imm3_query_create_table_agg(imm3_ctx *ctx, const imm3_table *table,
@@ -2996,6 +3123,12 @@ extern "C" int imm3_query_agg_form(const imm3_query *q, int32_t *form) {
 // ---------------------------------------------------------------------------------------------
 // write side of the PFOR_INT codec (host only; host/codec.hpp)
 // ---------------------------------------------------------------------------------------------
+extern "C" int imm3_query_expr_form(const imm3_query *q, int32_t *form) {
+    if (!q || !form) return fail(IMM3_ERR_ARG, "null argument");
+    *form = q->expr_form_ran;
+    return IMM3_OK;
+}
+
 extern "C" uint64_t imm3_pfor_encode_bound(int32_t n_values) {
     return n_values < 0 ? 0 : (uint64_t)immutabledb::codec::pforEncodeBound(n_values);
 }

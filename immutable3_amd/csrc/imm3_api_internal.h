@@ -12,6 +12,25 @@ void pool_release(imm3_ctx *ctx, void *p);
 void graphs_mark_stale(imm3_ctx *ctx, const imm3_query *q);          // recorded graphs that replay this query point at buffers that are about to move
 void fill_tile_col(const imm3_query *q, const FoldedPred &fp, TileCol &c, int kind);
 
+// scalar rules shared with the reference (JVM d2i / i2b): Select.scala:65,73; SURVEY Appendix A.1 rule 5
+inline int32_t jvm_d2i(double d) {
+    if (d != d) return 0;
+    if (d >= 2147483647.0) return INT32_MAX;
+    if (d <= -2147483648.0) return INT32_MIN;
+    return (int32_t)d;
+}
+inline int32_t jvm_d2b(double d) { return (int32_t)(int8_t)(uint8_t)((uint32_t)jvm_d2i(d) & 0xFFu); }
+
+// ---- imm3_expr_norm.cpp: select trees (imm3_query_create_expr) ----
+struct ExprCol { int32_t seg_col, vcodec, width; };   // the column a leaf is on: segment column, its DENSE_* value codec, bytes per value
+typedef std::vector<FoldedPred> ExprTerm;             // a conjunction: at most one folded predicate per column
+int leaf_pred(int32_t seg_col, int32_t vcodec, int32_t width, const imm3_select &leaf, FoldedPred &out); // one leaf alone
+void merge_pred(FoldedPred &into, const FoldedPred &other);                                             // ... AND another on the same column
+bool pred_empty(const FoldedPred &p);                                                                    // no value passes
+int expr_check_program(const int32_t *prog, int32_t n_prog, int32_t n_leaves, bool *has_or);             // IMM3_ERR_ARG: malformed
+int expr_normalize(const std::vector<ExprCol> &leaf_cols, const imm3_select *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog,
+                   std::vector<ExprTerm> &terms);
+
 // ---- imm3_planner.cpp ----
 constexpr int kSampleChunks = 8;                                      // the sample a plan is made on: eight chunks of 64 tiles spread over the segment / table
 constexpr int64_t kSampleChunkTiles = 64;

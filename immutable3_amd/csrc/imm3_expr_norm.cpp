@@ -1,0 +1,208 @@
+// imm3_expr_norm.cpp -- select trees on the host: one leaf as a folded predicate, the postfix program's checks, and the normal form
+// the kernels of imm3_expr.hip evaluate -- a disjunction of TERMS, each a conjunction with at most one folded predicate per column
+// (one closed interval, or one intersected IN-list: what fold_selects makes of a flat select list).  No device is touched here.
+#include "../../include/imm3.h"
+#include "../../include/imm3_diag.h"
+#include "imm3_handles.h"
+#include "imm3_api_internal.h"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace imm3 {
+
+// One SelectOp leaf on a column of DENSE_* codec `vcodec`: GT / LT / EQ narrow the column type's full interval (threshold narrowed
+// per leaf: d.toInt / d.toByte, Select.scala:65,73), Match keeps the values of exactly `width` bytes, each once.
+int leaf_pred(int32_t seg_col, int32_t vcodec, int32_t width, const imm3_select &leaf, FoldedPred &out) {
+    out = unfolded_pred(seg_col, vcodec, width);
+    if (out.kind == KIND_STR) {
+        int64_t off = 0;
+        for (int32_t m = 0; m < leaf.n_match; ++m) {
+            const int32_t len = leaf.match_lens[m];
+            if (len < 0) return fail(IMM3_ERR_ARG, "negative match length");
+            // String.equals can only hold for a value of exactly `width` bytes (DataType.scala:69-70)
+            if (len == width) {
+                std::string v((const char *)leaf.match_bytes + off, (size_t)len);
+                if (std::find(out.match.begin(), out.match.end(), v) == out.match.end()) out.match.push_back(v);
+            }
+            off += len;
+        }
+    } else {
+        const int64_t t = out.kind == KIND_I32 ? (int64_t)jvm_d2i(leaf.value) : (int64_t)jvm_d2b(leaf.value);
+        if (leaf.cond == IMM3_GT) out.lo = std::max(out.lo, t + 1);      // strict >, Select.scala:68,76
+        else if (leaf.cond == IMM3_LT) out.hi = std::min(out.hi, t - 1); // strict <, Select.scala:106,114
+        else { out.lo = std::max(out.lo, t); out.hi = std::min(out.hi, t); } // ==, Select.scala:144,152
+    }
+    return IMM3_OK;
+}
+
+// the conjunction of two predicates on the same column: intervals intersect, IN-lists intersect (the first one's order stays)
+void merge_pred(FoldedPred &into, const FoldedPred &other) {
+    if (into.kind == KIND_STR) {
+        std::vector<std::string> both;
+        for (auto &v : into.match)
+            if (std::find(other.match.begin(), other.match.end(), v) != other.match.end()) both.push_back(v);
+        into.match = both;
+    } else {
+        into.lo = std::max(into.lo, other.lo);
+        into.hi = std::min(into.hi, other.hi);
+    }
+}
+
+bool pred_empty(const FoldedPred &p) { return p.kind == KIND_STR ? p.match.empty() : p.lo > p.hi; }
+
+int expr_check_program(const int32_t *prog, int32_t n_prog, int32_t n_leaves, bool *has_or) {
+    if (has_or) *has_or = false;
+    if (n_prog < 0 || (n_prog > 0 && !prog)) return fail(IMM3_ERR_ARG, "bad select program");
+    if (n_prog == 0) return n_leaves == 0 ? IMM3_OK : fail(IMM3_ERR_ARG, "select program: empty, but leaves were given");
+    int64_t depth = 0;
+    for (int32_t i = 0; i < n_prog; ++i) {
+        const int32_t op = prog[i];
+        if (op >= 0) {
+            if (op >= n_leaves) return fail(IMM3_ERR_ARG, "select program: leaf index out of range");
+            ++depth;
+        } else if (op == IMM3_EXPR_AND || op == IMM3_EXPR_OR) {
+            if (depth < 2) return fail(IMM3_ERR_ARG, "select program: stack underflow");
+            --depth;
+            if (op == IMM3_EXPR_OR && has_or) *has_or = true;
+        } else return fail(IMM3_ERR_ARG, "select program: unknown operator");
+    }
+    if (depth != 1) return fail(IMM3_ERR_ARG, "select program: more than one result");
+    return IMM3_OK;
+}
+
+namespace {
+bool same_pred(const FoldedPred &a, const FoldedPred &b) {
+    if (a.seg_col != b.seg_col) return false;
+    if (a.kind != KIND_STR) return a.lo == b.lo && a.hi == b.hi;
+    if (a.match.size() != b.match.size()) return false;
+    for (auto &v : a.match)
+        if (std::find(b.match.begin(), b.match.end(), v) == b.match.end()) return false;
+    return true;
+}
+bool same_term(const ExprTerm &a, const ExprTerm &b) {
+    if (a.size() != b.size()) return false;
+    for (const auto &p : a) {
+        bool found = false;
+        for (const auto &r : b) found = found || same_pred(p, r);
+        if (!found) return false;
+    }
+    return true;
+}
+void add_term(std::vector<ExprTerm> &dnf, const ExprTerm &t) {
+    for (const auto &p : t)
+        if (pred_empty(p)) return; // selects nothing
+    for (const auto &have : dnf)
+        if (same_term(have, t)) return;
+    dnf.push_back(t);
+}
+constexpr size_t kMaxWorkTerms = 4096; // terms of an intermediate result (the final bound is the kernels': kMaxExprGenericTerms)
+} // namespace
+
+// The tree as a disjunction of terms.  AND distributes over OR (every pair of terms, merged per column), terms that select nothing
+// and duplicates are dropped; no term left = the tree selects nothing.  A term keeps its columns in the order the program first
+// names them: a tree without OR gives the one term whose predicates are fold_selects' of the same leaves in program order.
+int expr_normalize(const std::vector<ExprCol> &leaf_cols, const imm3_select *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog,
+                   std::vector<ExprTerm> &terms) {
+    terms.clear();
+    const int crc = expr_check_program(prog, n_prog, n_leaves, nullptr);
+    if (crc) return crc;
+    std::vector<std::vector<ExprTerm>> stack;
+    for (int32_t i = 0; i < n_prog; ++i) {
+        const int32_t op = prog[i];
+        if (op >= 0) {
+            const ExprCol &c = leaf_cols[(size_t)op];
+            FoldedPred fp;
+            const int lrc = leaf_pred(c.seg_col, c.vcodec, c.width, leaves[op], fp);
+            if (lrc) return lrc;
+            std::vector<ExprTerm> dnf;
+            add_term(dnf, ExprTerm{fp});
+            stack.push_back(std::move(dnf));
+            continue;
+        }
+        std::vector<ExprTerm> b = std::move(stack.back());
+        stack.pop_back();
+        std::vector<ExprTerm> a = std::move(stack.back());
+        stack.pop_back();
+        std::vector<ExprTerm> r;
+        if (op == IMM3_EXPR_OR) {
+            r = std::move(a);
+            for (const auto &t : b) add_term(r, t);
+        } else {
+            for (const auto &x : a)
+                for (const auto &y : b) {
+                    ExprTerm t = x;
+                    for (const auto &p : y) {
+                        FoldedPred *mine = pred_on(t, p.seg_col);
+                        if (mine) merge_pred(*mine, p);
+                        else t.push_back(p);
+                    }
+                    add_term(r, t);
+                    if (r.size() > kMaxWorkTerms) return fail(IMM3_ERR_ARG, "select tree: too many terms");
+                }
+        }
+        if (r.size() > kMaxWorkTerms) return fail(IMM3_ERR_ARG, "select tree: too many terms");
+        stack.push_back(std::move(r));
+    }
+    if (!stack.empty()) terms = std::move(stack.back());
+    if (terms.size() > (size_t)kMaxExprGenericTerms)
+        return fail(IMM3_ERR_ARG, "select tree: its normal form has " + std::to_string(terms.size()) + " terms, more than " + std::to_string(kMaxExprGenericTerms));
+    return IMM3_OK;
+}
+
+} // namespace imm3
+
+using namespace imm3;
+
+// diagnostics: the normaliser without a device (tests hold the terms' truth table against the tree's)
+extern "C" int imm3_expr_normalize(const int32_t *col_codec, const int32_t *col_width, int32_t n_cols, const imm3_select *leaves, int32_t n_leaves,
+                                   const int32_t *prog, int32_t n_prog, char *json_out, int64_t cap, int64_t *needed) {
+    if (n_cols < 0 || (n_cols > 0 && (!col_codec || !col_width)) || n_leaves < 0 || (n_leaves > 0 && !leaves) || cap < 0 || (cap > 0 && !json_out))
+        return fail(IMM3_ERR_ARG, "bad argument");
+    std::vector<ExprCol> leaf_cols;
+    for (int32_t i = 0; i < n_leaves; ++i) {
+        const int32_t c = leaves[i].column, cond = leaves[i].cond;
+        if (c < 0 || c >= n_cols) return fail(IMM3_ERR_ARG, "select column is not among the columns");
+        if (cond != IMM3_MATCH && cond != IMM3_GT && cond != IMM3_LT && cond != IMM3_EQ) return fail(IMM3_ERR_UNSUPPORTED_CONDITION, "Unsupported condition");
+        const int32_t vc = value_codec(col_codec[c]);
+        if (vc != IMM3_DENSE_INT && vc != IMM3_DENSE_TINYINT && vc != IMM3_DENSE_STRING) return fail(IMM3_ERR_NO_CODEC, "No implementation for codec " + std::to_string(col_codec[c]));
+        if ((cond == IMM3_MATCH) != (vc == IMM3_DENSE_STRING)) return fail(IMM3_ERR_UNSUPPORTED_VECTOR, "Unsupported column vector");
+        if (cond == IMM3_MATCH && leaves[i].n_match > 0 && (!leaves[i].match_bytes || !leaves[i].match_lens)) return fail(IMM3_ERR_ARG, "Match without values");
+        leaf_cols.push_back(ExprCol{c, vc, col_width[c]});
+    }
+    std::vector<ExprTerm> terms;
+    const int rc = expr_normalize(leaf_cols, leaves, n_leaves, prog, n_prog, terms);
+    if (rc) return rc;
+    std::string js = "[";
+    for (size_t t = 0; t < terms.size(); ++t) {
+        js += t ? ",[" : "[";
+        for (size_t k = 0; k < terms[t].size(); ++k) {
+            const FoldedPred &p = terms[t][k];
+            js += k ? ",{" : "{";
+            js += "\"col\":" + std::to_string(p.seg_col);
+            if (p.kind == KIND_STR) {
+                js += ",\"match\":[";
+                for (size_t m = 0; m < p.match.size(); ++m) {
+                    js += m ? ",\"" : "\"";
+                    char hex[3];
+                    for (unsigned char ch : p.match[m]) {
+                        std::snprintf(hex, sizeof(hex), "%02x", ch);
+                        js += hex;
+                    }
+                    js += "\"";
+                }
+                js += "]";
+            } else js += ",\"lo\":" + std::to_string(p.lo) + ",\"hi\":" + std::to_string(p.hi);
+            js += "}";
+        }
+        js += "]";
+    }
+    js += "]";
+    if (needed) *needed = (int64_t)js.size() + 1;
+    if ((int64_t)js.size() + 1 > cap) return cap == 0 ? IMM3_OK : fail(IMM3_ERR_ARG, "json_out is too small");
+    std::memcpy(json_out, js.c_str(), js.size() + 1);
+    return IMM3_OK;
+}

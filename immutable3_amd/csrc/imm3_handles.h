@@ -347,6 +347,18 @@ struct imm3_query {
     unsigned long long *d_desc = nullptr;   // per-span descriptors of the chained scan
     size_t sp_trash_off = 0;                // byte offset of the writers' trash lines in d_desc's allocation
     imm3::ProjectTile *d_tile_desc = nullptr; // table queries: one descriptor per tile of the table for the launch's columns (k_filter_project's TABLE instances)
+    // select tree (imm3_query_create_expr, an OR in it): the selection is the OR of these terms, ONE launch of imm3_expr.hip's tile or
+    // generic kernel; q->preds stays empty, the projection takes the bitmap path and an aggregation reads the bitmap
+    bool is_expr = false;
+    std::vector<std::vector<FoldedPred>> expr_terms;
+    bool expr_tile_ok = false;              // the tile form can take the terms (uniform layout, <= 8 terms over <= 3 tile columns of an instantiated kind combination)
+    int32_t expr_kinds[imm3::kMaxTileCols] = {imm3::TK_NONE, imm3::TK_NONE, imm3::TK_NONE}; // of the tile launch, sorted
+    int32_t expr_seg_col[imm3::kMaxTileCols] = {-1, -1, -1};                                  // segment column of each
+    std::vector<imm3::ColPred> h_expr_preds; // generic form: host images of the terms' predicates and their starts (copied asynchronously: live with the query)
+    std::vector<int32_t> h_expr_term_start;
+    imm3::ColPred *d_expr_preds = nullptr;
+    int32_t *d_expr_term_start = nullptr;
+    int32_t expr_form_ran = -1;             // diagnostics (imm3_query_expr_form): 0 = tile, 1 = generic, -1 before any launch
     bool count_log_on = false;              // imm3_query_log_counts is installed: every run logs the segment's count (a limit query then scans whole)
     uint32_t sp_abandoned_runs = 0, sp_busy_runs = 0; // single-pass runs whose rows were gathered from the bitmap instead: a prefix never came / the device was busy (imm3_query_plan)
 };

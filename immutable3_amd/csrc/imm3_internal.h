@@ -296,6 +296,40 @@ struct FilterArgs {
     const uint8_t *word_nvalid;
 };
 
+// ---- select trees (imm3_expr.hip): AND / OR over the leaves, as a disjunction of TERMS ----
+// The host rewrites a tree into terms (imm3_expr_norm.cpp): each term is a conjunction with at most one folded predicate per column --
+// exactly what a flat select list folds to -- and the selection is the OR of the terms.
+constexpr int kMaxExprTerms = 8;         // terms the tile form carries in its kernel arguments
+constexpr int kMaxExprGenericTerms = 64; // terms the generic form takes (its predicates sit in device memory)
+
+// k_filter_expr<K0, K1, K2>: k_filter_tile's geometry (one wave per 1024-row tile, one 128-byte bitmap line per tile); the columns
+// are loaded once per tile and tested once per term.  ~1.4 KB of kernel arguments.
+struct ExprTileArgs {
+    TileCol cols[kMaxExprTerms][kMaxTileCols]; // [t][k]: term t's predicate on tile column k (data: the same column in every term)
+    uint32_t use[kMaxExprTerms];               // bit k: term t constrains tile column k (an unconstrained column is not tested)
+    int32_t kinds[kMaxTileCols];               // sorted ascending, TK_NONE last (selects the template instance)
+    int32_t n_terms;
+    int64_t n_rows, n_words, n_tiles;
+    uint64_t *bitmap;                          // null: count-only run -- no bitmap line is stored
+    uint32_t *block_partials;
+    unsigned long long *finish;                // the query's finish block: the count is reduced in the kernel; null = k_total does
+};
+
+// k_filter_expr_generic: any column kind, any layout, up to kMaxExprGenericTerms terms; one wave per bitmap word per iteration.
+struct ExprGenericArgs {
+    const ColPred *preds;          // device memory: the terms' predicates, term after term
+    const int32_t *term_start;     // device memory: n_terms + 1 indices into preds
+    int32_t n_terms;
+    int32_t pad;
+    int64_t n_rows, n_words, n_tiles;
+    uint64_t *bitmap;
+    uint32_t *block_partials;
+    const uint32_t *word_row_base; // ragged layout only (as FilterArgs)
+    const uint8_t *word_nvalid;
+};
+bool launch_filter_expr(const ExprTileArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // false: no instance for these kinds
+void launch_filter_expr_generic(const ExprGenericArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+
 struct TotalArgs {               // k_total: sum of the filter launch's per-workgroup partials
     const uint32_t *block_partials;
     int32_t n_partials;

@@ -463,40 +463,6 @@ __global__ __launch_bounds__(kBlockThreads, tile_min_waves(K0, K1, STAGE)) void 
 //   batch's BitSet starts on a fresh word, word w covers rows [base[w], base[w] + nvalid[w]).
 // ---------------------------------------------------------------------------------------------
 
-// SelectIteratorMatch (Select.scala:25-51): keep the row iff its `width` raw bytes equal one IN-list value.
-__device__ __forceinline__ bool match_row(const ColPred &c, int64_t row) {
-    const uint8_t *p = (const uint8_t *)c.data + row * (int64_t)c.width;
-    bool found = false;
-    if (c.match_in_args) {
-        uint64_t v = 0;
-        switch (c.width) {
-        case 1: v = *p; break;
-        case 2: v = *(const uint16_t *)p; break;
-        case 4: v = *(const uint32_t *)p; break;
-        case 8: v = *(const uint64_t *)p; break;
-        default:
-            for (int b = 0; b < c.width; ++b) v |= (uint64_t)p[b] << (8 * b);
-        }
-        for (int m = 0; m < c.n_match; ++m) found |= (v == c.match[m]);
-    } else {
-        for (int m = 0; m < c.n_match; ++m) {
-            const uint8_t *q = c.match_blob + (int64_t)m * c.width;
-            bool eq = true;
-            for (int b = 0; b < c.width; ++b) eq &= (p[b] == q[b]);
-            found |= eq;
-        }
-    }
-    return found;
-}
-
-__device__ __forceinline__ bool eval_row(const ColPred &c, int64_t row) {
-    switch (c.kind) {
-    case KIND_I32: return in_closed(((const int32_t *)c.data)[row], c.lo, c.hi);
-    case KIND_I8: return in_closed((int32_t)((const int8_t *)c.data)[row], c.lo, c.hi);
-    default: return match_row(c, row);
-    }
-}
-
 __global__ __launch_bounds__(kBlockThreads) void k_filter_generic(const FilterArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;

@@ -649,6 +649,7 @@ static int plan_one_tile_pass(imm3_query *q, const std::vector<const FoldedPred 
 }
 
 int plan_projection(imm3_query *q) {
+    if (q->is_expr) return IMM3_OK; // a select tree: the bitmap path (k_scan + k_gather) -- no records, no one launch, no sample
     // (anything but an unlimited projection whose select chain is ONE tile launch takes the bitmap path, which needs no set-up)
     if (!q->proj.empty() && q->limit <= 0 && !q->always_false && q->n_rows > 0 && q->ctx->filter_variant != TV_NO_RECORDS &&
         q->proj.size() <= (size_t)kMaxProj) {

@@ -2,6 +2,8 @@
 //   imm3_sql -q "select id, age from test_100 where (age > 18 and age < 30) limit 10" -d <dataDir> [--device n]
 // Prints one `Row(...)` per line, like `println(it.next)` (SqlCli.scala:72).
 //   --parse-only   print the parsed Query ADT and the planner's column order / leaves; no GPU needed.
+//   --honour-and-or  run an `or` of the where clause as a disjunction (default off: the reference executes every Or as an And,
+//                  Engine.scala:236-245).  With --parse-only it also prints the tree's postfix program.
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -37,7 +39,7 @@ static std::string showQuery(const Query &q) {
 int main(int argc, char **argv) {
     std::string query, dataDir;
     int device = 0, repeat = 0;
-    bool parseOnly = false;
+    bool parseOnly = false, honourAndOr = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if ((a == "-q" || a == "--query") && i + 1 < argc) query = argv[++i];
@@ -45,11 +47,12 @@ int main(int argc, char **argv) {
         else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (a == "--cpu-count" && i + 1 < argc) ++i; // accepted for SqlCli compatibility; segments run on the GPU
         else if (a == "--parse-only") parseOnly = true;
+        else if (a == "--honour-and-or") honourAndOr = true;
         else if (a == "--repeat" && i + 1 < argc) repeat = std::atoi(argv[++i]); // re-run the query N times on the resident table, time to stderr
         else { std::fprintf(stderr, "Error parsing arguments: %s\n", a.c_str()); return 2; }
     }
     if (query.empty() || (dataDir.empty() && !parseOnly)) {
-        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only]\n");
+        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only] [--honour-and-or]\n");
         return 2;
     }
     try {
@@ -65,11 +68,19 @@ int main(int argc, char **argv) {
                 for (const auto &l : Engine::resolveSelectOps(q)) std::cout << " " << l.col << ":" << l.cond.toString();
                 std::cout << "\n";
             }
+            if (honourAndOr && SelectTreeOp::hasOr(*q.select)) { // leaf index | AND | OR, post-order (include/imm3.h: select trees)
+                std::vector<Leaf> leaves;
+                std::vector<int32_t> prog;
+                SelectTreeOp::program(*q.select, leaves, prog);
+                std::cout << "program:";
+                for (int32_t op : prog) std::cout << " " << (op == IMM3_EXPR_AND ? std::string("AND") : op == IMM3_EXPR_OR ? std::string("OR") : std::to_string(op));
+                std::cout << "\n";
+            }
             return 0;
         }
         SegmentManager sm(dataDir);
         GpuSegmentManager gsm(sm, device);
-        Engine engine(gsm);
+        Engine engine(gsm, honourAndOr);
         for (const Row &r : engine.execute(q)) std::cout << r.toString() << "\n";
         for (int k = 0; k < repeat; ++k) { // segments are resident now: this is the steady-state query time
             const auto t0 = std::chrono::steady_clock::now();

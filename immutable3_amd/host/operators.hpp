@@ -167,8 +167,9 @@ class ScanOp : public ColumnVectorOperator {
     const Table &table() const { return sm_.sm.getTable(tableName_); }
     GpuSegmentManager &manager() const { return sm_; }
 
-    // builds the fused query: leaves in application order, optional projection
-    void makeQuery(const std::vector<Leaf> &leaves, const std::vector<std::string> &projNames, int limit, QueryHandle &h) const {
+    // builds the fused query: leaves in application order, optional projection.  `prog`: the leaves are those of a select TREE and
+    // this is its postfix program (include/imm3.h: imm3_query_create_expr), AND / OR honoured; null: the leaves are a conjunction
+    void makeQuery(const std::vector<Leaf> &leaves, const std::vector<std::string> &projNames, int limit, QueryHandle &h, const std::vector<int32_t> *prog = nullptr) const {
         const Table &t = table();
         std::vector<int32_t> used;
         for (const auto &c : cols_) used.push_back(t.columnIndex(c.name));
@@ -197,11 +198,16 @@ class ScanOp : public ColumnVectorOperator {
                 if (cols_[i].name == n) { proj.push_back((int32_t)i); found = true; }
             if (!found) throw Exception("NoSuchElementException: key not found: " + n); // vecCols(col), Project.scala:56
         }
+        if (prog)
+            imm3Check(imm3_query_create_expr(sm_.ctx(), sm_.deviceSegment(tableName_, segIdx_), used.data(), (int32_t)used.size(), sels.data(), (int32_t)sels.size(),
+                                             prog->data(), (int32_t)prog->size(), proj.data(), (int32_t)proj.size(), limit, t.blockSize, &h.q));
+        else
         imm3Check(imm3_query_create(sm_.ctx(), sm_.deviceSegment(tableName_, segIdx_), used.data(), (int32_t)used.size(),
                                     sels.data(), (int32_t)sels.size(), proj.data(), (int32_t)proj.size(), limit, t.blockSize, &h.q));
     }
 
-    void makeAggQuery(const std::vector<Leaf> &leaves, const std::vector<int32_t> &group, const std::vector<imm3_aggregate> &aggs, QueryHandle &h) const {
+    void makeAggQuery(const std::vector<Leaf> &leaves, const std::vector<int32_t> &group, const std::vector<imm3_aggregate> &aggs, QueryHandle &h,
+                      const std::vector<int32_t> *prog = nullptr) const {
         const Table &t = table();
         std::vector<int32_t> used;
         for (const auto &c : cols_) used.push_back(t.columnIndex(c.name));
@@ -222,14 +228,19 @@ class ScanOp : public ColumnVectorOperator {
         }
         int keyBytes = 0; // a group key wider than 8 bytes: the _wide entry point
         for (int32_t g : group) keyBytes += cols_[(size_t)g].width();
+        if (prog) { // (one entry point for narrow and wide keys)
+            imm3Check(imm3_query_create_agg_expr(sm_.ctx(), sm_.deviceSegment(tableName_, segIdx_), used.data(), (int32_t)used.size(), sels.data(), (int32_t)sels.size(),
+                                                 prog->data(), (int32_t)prog->size(), group.data(), (int32_t)group.size(), aggs.data(), (int32_t)aggs.size(), t.blockSize, &h.q));
+            return;
+        }
         imm3Check((keyBytes > 8 ? imm3_query_create_agg_wide : imm3_query_create_agg)(
             sm_.ctx(), sm_.deviceSegment(tableName_, segIdx_), used.data(), (int32_t)used.size(), sels.data(), (int32_t)sels.size(),
             group.data(), (int32_t)group.size(), aggs.data(), (int32_t)aggs.size(), t.blockSize, &h.q));
     }
 
-    std::unique_ptr<Iterator<ColumnVectorBatch>> batches(const std::vector<Leaf> &leaves) const {
+    std::unique_ptr<Iterator<ColumnVectorBatch>> batches(const std::vector<Leaf> &leaves, const std::vector<int32_t> *prog = nullptr) const {
         QueryHandle h;
-        makeQuery(leaves, {}, 0, h);
+        makeQuery(leaves, {}, 0, h, prog);
         imm3Check(imm3_query_run_select(h.q));
         int32_t nb = 0;
         int64_t nwords = 0, nrows = 0;
@@ -324,6 +335,46 @@ class SelectOp : public ColumnVectorOperator {
     std::shared_ptr<ColumnVectorOperator> op_;
 };
 
+// ---- SelectTreeOp: a whole SelectADT over a ScanOp with its AND / OR tags HONOURED -- what the reference announces and does not do
+// (Engine.scala:236,266: "TODO: use AND/OR operators").  Fuses with ScanOp / ProjectOp / ProjectAggOp like a SelectOp chain does. ----
+class SelectTreeOp : public ColumnVectorOperator {
+  public:
+    SelectTreeOp(std::shared_ptr<SelectADT> select, std::shared_ptr<ColumnVectorOperator> op) : select_(std::move(select)), op_(std::move(op)) {}
+    // the tree as leaves + postfix program, post-order (a NoSelect side adds nothing: the other side stands alone)
+    static void program(const SelectADT &s, std::vector<Leaf> &leaves, std::vector<int32_t> &prog) {
+        if (s.kind == SelectADT::And || s.kind == SelectADT::Or) {
+            const size_t before = prog.size();
+            program(*s.op1, leaves, prog);
+            const size_t mid = prog.size();
+            program(*s.op2, leaves, prog);
+            if (mid > before && prog.size() > mid) prog.push_back(s.kind == SelectADT::And ? IMM3_EXPR_AND : IMM3_EXPR_OR);
+        } else if (s.kind == SelectADT::Select) {
+            prog.push_back((int32_t)leaves.size());
+            leaves.push_back(Leaf{s.col, s.cond});
+        }
+    }
+    static bool hasOr(const SelectADT &s) {
+        return s.kind == SelectADT::Or || (s.kind == SelectADT::And && (hasOr(*s.op1) || hasOr(*s.op2)));
+    }
+    std::shared_ptr<ScanOp> chain(std::vector<Leaf> &leaves, std::vector<int32_t> &prog) const {
+        auto scan = std::dynamic_pointer_cast<ScanOp>(op_);
+        if (!scan) throw Exception("SelectTreeOp must sit on a ScanOp for the fused GPU path");
+        program(*select_, leaves, prog);
+        return scan;
+    }
+    std::unique_ptr<Iterator<ColumnVectorBatch>> iterator() override {
+        std::vector<Leaf> leaves;
+        std::vector<int32_t> prog;
+        auto scan = chain(leaves, prog);
+        SelectOp::checkConditions(leaves);
+        return scan->batches(leaves, &prog);
+    }
+
+  private:
+    std::shared_ptr<SelectADT> select_;
+    std::shared_ptr<ColumnVectorOperator> op_;
+};
+
 // ---- ProjectOp (Project.scala:17) ----
 class ProjectOp : public ProjectionOperator {
   public:
@@ -333,13 +384,16 @@ class ProjectOp : public ProjectionOperator {
     }
     std::unique_ptr<Iterator<Row>> iterator() override {
         std::vector<Leaf> leaves;
+        std::vector<int32_t> prog;
+        const std::vector<int32_t> *progp = nullptr;
         std::shared_ptr<ScanOp> scan;
         if (auto sel = std::dynamic_pointer_cast<SelectOp>(op_)) scan = sel->chain(leaves);
+        else if (auto tree = std::dynamic_pointer_cast<SelectTreeOp>(op_)) { scan = tree->chain(leaves, prog); progp = &prog; }
         else scan = std::dynamic_pointer_cast<ScanOp>(op_);
         if (!scan) return hostIterator();
         SelectOp::checkConditions(leaves);
         QueryHandle h;
-        scan->makeQuery(leaves, cols_, limit_, h);
+        scan->makeQuery(leaves, cols_, limit_, h, progp);
         imm3Check(imm3_query_run(h.q));
         uint64_t n = 0;
         imm3Check(imm3_query_row_count(h.q, &n));
@@ -456,8 +510,11 @@ class ProjectAggOp : public Operator<AggMapTuple> {
         : aggs_(std::move(aggs)), op_(std::move(op)), groupBy_(std::move(groupBy)) {}
     std::unique_ptr<Iterator<AggMapTuple>> iterator() override {
         std::vector<Leaf> leaves;
+        std::vector<int32_t> prog;
+        const std::vector<int32_t> *progp = nullptr;
         std::shared_ptr<ScanOp> scan;
         if (auto sel = std::dynamic_pointer_cast<SelectOp>(op_)) scan = sel->chain(leaves);
+        else if (auto tree = std::dynamic_pointer_cast<SelectTreeOp>(op_)) { scan = tree->chain(leaves, prog); progp = &prog; }
         else scan = std::dynamic_pointer_cast<ScanOp>(op_);
         if (!scan) throw Exception("ProjectAggOp must sit on a ScanOp / SelectOp chain for the fused GPU path");
         SelectOp::checkConditions(leaves);
@@ -480,7 +537,7 @@ class ProjectAggOp : public Operator<AggMapTuple> {
         std::vector<imm3_aggregate> abi(aggs.size());
         for (size_t j = 0; j < aggs.size(); ++j) { abi[j].kind = aggs[j].abiKind(); abi[j].column = usedIndex(aggs[j].col); }
         QueryHandle h;
-        scan->makeAggQuery(leaves, group, abi, h);
+        scan->makeAggQuery(leaves, group, abi, h, progp);
         auto it = std::make_unique<VectorIterator<AggMapTuple>>();
         it->items = decode(h, cols, group, aggs, abi);
         return it;
@@ -585,7 +642,16 @@ class ProjectAggOp : public Operator<AggMapTuple> {
 // ---- Engine (Engine.scala:81-197) ----
 class Engine {
   public:
-    explicit Engine(GpuSegmentManager &sm) : sm_(sm) {}
+    // honourAndOr: a query whose select tree holds an Or runs it as a disjunction (one SelectTreeOp per segment) instead of the
+    // reference's conjunction.  Off (the default) nothing changes; a tree without Or is the same either way.
+    explicit Engine(GpuSegmentManager &sm, bool honourAndOr = false) : sm_(sm), honourAndOr_(honourAndOr) {}
+    bool asTree(const Query &q) const { return honourAndOr_ && SelectTreeOp::hasOr(*q.select); }
+    // the operators between ScanOp and the projection: the reference's SelectOp chain, or one SelectTreeOp
+    std::shared_ptr<ColumnVectorOperator> selectOps(const Query &q, const std::vector<Leaf> &leaves, std::shared_ptr<ColumnVectorOperator> op) const {
+        if (asTree(q)) return std::make_shared<SelectTreeOp>(q.select, op);
+        for (const auto &l : leaves) op = SelectOp::mkSelectOp(l.col, l.cond)(op);
+        return op;
+    }
 
     // Engine.getColumns (:85-106): (rec(query.select).toList ++ projectColumns).toSet.toList.  Scala's Set1..Set4 keep
     // insertion order, so for <= 4 distinct columns this is first-seen order (SURVEY A.1 rule 3); from the fifth distinct
@@ -630,6 +696,7 @@ class Engine {
     // fills `p` and returns true when the whole table can run as one fused launch
     bool tablePlan(const Query &q, TablePlan &p) {
         const Table &table = sm_.sm.getTable(q.table);
+        if (asTree(q)) return false; // a table takes no select tree: per-segment queries
         p.table = sm_.deviceTable(q.table);
         if (!p.table) return false;
         p.used = getColumns(q, table);
@@ -697,7 +764,7 @@ class Engine {
         const int nseg = sm_.sm.getTableSegmentCount(table.name);
         for (int seg = 0; seg < nseg; ++seg) {
             std::shared_ptr<ColumnVectorOperator> op = mkScan(used, seg);
-            for (const auto &l : leaves) op = SelectOp::mkSelectOp(l.col, l.cond)(op);
+            op = selectOps(q, leaves, op);
             ProjectAggOp agg(aggs, op, q.project.groupBy);
             auto it = agg.iterator();
             while (it->hasNext()) {
@@ -775,7 +842,7 @@ class Engine {
         for (int seg = 0; seg < nseg; ++seg) {
             if (q.project.limit > 0 && (int)rows.size() >= q.project.limit) break;
             std::shared_ptr<ColumnVectorOperator> op = mkScan(used, seg);
-            for (const auto &l : leaves) op = SelectOp::mkSelectOp(l.col, l.cond)(op);
+            op = selectOps(q, leaves, op);
             auto it = mkProj(op)->iterator();
             while (it->hasNext() && !(q.project.limit > 0 && (int)rows.size() >= q.project.limit)) rows.push_back(it->next());
         }
@@ -784,6 +851,7 @@ class Engine {
 
   private:
     GpuSegmentManager &sm_;
+    bool honourAndOr_ = false;
 };
 
 } // namespace immutabledb

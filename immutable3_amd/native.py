@@ -22,6 +22,9 @@ SNAPPY_INT, SNAPPY_TINYINT, SNAPPY_STRING = 16, 17, 18   # extension: blocks as 
 INT_CODECS, TINYINT_CODECS = (DENSE_INT, PFOR_INT, SNAPPY_INT), (DENSE_TINYINT, SNAPPY_TINYINT)
 # SelectCondition (core/src/main/scala/immutabledb/Query.scala:3-9)
 MATCH, NOTMATCH, EQ, GT, LT, NOOP = 0, 1, 2, 3, 4, 5
+# operators of a select tree's postfix program (include/imm3.h: IMM3_EXPR_AND / IMM3_EXPR_OR); values >= 0 are leaf indices
+EXPR_AND, EXPR_OR = -1, -2
+EXPR_FORM_TILE, EXPR_FORM_GENERIC = 0, 1
 
 OK = 0
 ERR_UNSUPPORTED_CONDITION, ERR_UNSUPPORTED_VECTOR, ERR_NO_CODEC, ERR_LAYOUT, ERR_ARG, ERR_DEVICE, ERR_STATE = 1, 2, 3, 4, 5, 6, 7
@@ -37,6 +40,7 @@ EXPORTS = [
     "imm3_query_create", "imm3_query_create_agg", "imm3_query_group_count", "imm3_query_fetch_groups", "imm3_query_agg_shape",
     "imm3_query_fetch_group_strings", "imm3_query_destroy", "imm3_query_reserve_rows",
     "imm3_query_create_agg_wide", "imm3_query_create_table_agg_wide", "imm3_query_fetch_group_keys",
+    "imm3_query_create_expr", "imm3_query_create_agg_expr",
     "imm3_query_run", "imm3_query_run_select", "imm3_query_run_count", "imm3_query_sync", "imm3_query_join_count", "imm3_query_log_counts",
     "imm3_query_layout", "imm3_query_batches", "imm3_query_count", "imm3_query_bitmap",
     "imm3_query_row_count", "imm3_query_fetch_rows", "imm3_query_device_ptr",
@@ -50,7 +54,7 @@ DIAG_EXPORTS = [
     "imm3_ctx_timing_enable", "imm3_ctx_timing_reset", "imm3_ctx_timing_mask", "imm3_ctx_timing_collect", "imm3_ctx_set_tuning",
     "imm3_ctx_measure_read_gbps", "imm3_ctx_devclock_enable", "imm3_ctx_devclock_collect", "imm3_ctx_devclock_raw", "imm3_query_plan",
     "imm3_ctx_inject_fault", "imm3_ctx_debug_device_lock", "imm3_plan_predict", "imm3_comm_debug_standin", "imm3_plan_limit_scan",
-    "imm3_query_agg_form",
+    "imm3_query_agg_form", "imm3_query_expr_form", "imm3_expr_normalize",
 ]
 COMM_ID_BYTES = 128
 
@@ -150,6 +154,10 @@ def load() -> C.CDLL:
     L.imm3_query_create_agg_wide.argtypes = [vp, vp, vp, i32, P(CSelect), i32, vp, i32, vp, i32, i32, P(vp)]
     L.imm3_query_create_table_agg_wide.argtypes = [vp, vp, vp, i32, P(CSelect), i32, vp, i32, vp, i32, i32, P(vp)]
     L.imm3_query_fetch_group_keys.argtypes = [vp, vp, C.c_uint32]
+    L.imm3_query_create_expr.argtypes = [vp, vp, vp, i32, P(CSelect), i32, vp, i32, vp, i32, i64, i32, P(vp)]
+    L.imm3_query_create_agg_expr.argtypes = [vp, vp, vp, i32, P(CSelect), i32, vp, i32, vp, i32, vp, i32, i32, P(vp)]
+    L.imm3_query_expr_form.argtypes = [vp, P(i32)]
+    L.imm3_expr_normalize.argtypes = [vp, vp, i32, P(CSelect), i32, vp, i32, vp, i64, P(i64)]
     L.imm3_query_destroy.argtypes = [vp]
     L.imm3_query_reserve_rows.argtypes = [vp, u64]
     L.imm3_query_run.argtypes = [vp]
@@ -489,40 +497,86 @@ class DeviceTable:
             pass
 
 
+def _cselects(sels):
+    """(CSelect array, the numpy buffers it points into) for [(column, cond, operand)]"""
+    cs = (CSelect * max(1, len(sels)))()
+    keep = []
+    for i, (col, cond, operand) in enumerate(sels):
+        cs[i].column = col
+        cs[i].cond = cond
+        cs[i].value = 0.0
+        cs[i].n_match = 0
+        if cond in (MATCH, NOTMATCH):
+            vals = [bytes(v) for v in (operand or [])]
+            blob = np.frombuffer(b"".join(vals) or b"\0", dtype=np.uint8).copy()
+            lens = np.array([len(v) for v in vals] or [0], dtype=np.int32)
+            keep += [blob, lens]
+            cs[i].match_bytes = blob.ctypes.data
+            cs[i].match_lens = lens.ctypes.data
+            cs[i].n_match = len(vals)
+        elif operand is not None:
+            cs[i].value = float(operand)
+    return cs, keep
+
+
+def expr_normalize(col_codecs: Sequence[int], col_widths: Sequence[int], leaves: Sequence[tuple], prog: Sequence[int]):
+    """The normal form of a select tree (include/imm3_diag.h: imm3_expr_normalize), no device needed: a list of terms, each a list
+    of {"col", "lo", "hi"} / {"col", "match": [bytes]} -- the selection is the OR of the terms, a term the AND of its predicates."""
+    import json
+    cs, keep = _cselects(leaves)
+    cc = np.array(list(col_codecs) or [0], dtype=np.int32)
+    cw = np.array(list(col_widths) or [0], dtype=np.int32)
+    pg = np.array(list(prog) or [0], dtype=np.int32)
+    need = C.c_int64(0)
+    args = (cc.ctypes.data, cw.ctypes.data, len(col_codecs), cs, len(leaves), pg.ctypes.data, len(prog))
+    _check(load().imm3_expr_normalize(*args, None, 0, C.byref(need)))
+    buf = C.create_string_buffer(need.value)
+    _check(load().imm3_expr_normalize(*args, C.cast(buf, C.c_void_p), need.value, None))
+    terms = json.loads(buf.value.decode())
+    for t in terms:
+        for p in t:
+            if "match" in p:
+                p["match"] = [bytes.fromhex(h) for h in p["match"]]
+    return terms
+
+
 class DeviceQuery:
     """imm3_query: ScanOp -> SelectOp* -> ProjectOp (or ProjectAggOp when `aggs` is given) over one device segment."""
 
     def __init__(self, ctx: Context, seg: DeviceSegment, used_cols: Sequence[int],
                  sels: Sequence[tuple], proj: Sequence[int] = (), limit: int = 0, table_block_size: int = 1024,
                  group_cols: Optional[Sequence[int]] = None, aggs: Optional[Sequence[tuple]] = None,
-                 wide_keys: bool = False):
-        """wide_keys: an aggregation through the _wide entry points (group keys of up to GROUP_KEY_MAX_WIDTH bytes)."""
+                 wide_keys: bool = False, expr: Optional[Sequence[int]] = None):
+        """wide_keys: an aggregation through the _wide entry points (group keys of up to GROUP_KEY_MAX_WIDTH bytes).
+        expr: a select TREE -- `sels` are its leaves and `expr` the postfix program over them (leaf indices, EXPR_AND, EXPR_OR):
+        the _expr entry points, which honour OR.  Without it `sels` is a conjunction."""
         self.ctx, self.seg = ctx, seg
         self.used_cols = list(used_cols)
         self.proj = list(proj)
         self.group_cols = list(group_cols or [])
         self.aggs = list(aggs) if aggs is not None else None
+        self.expr = list(expr) if expr is not None else None
         used = np.array(self.used_cols or [0], dtype=np.int32)
         pj = np.array(self.proj or [0], dtype=np.int32)
-        cs = (CSelect * max(1, len(sels)))()
-        keep = []
-        for i, (col, cond, operand) in enumerate(sels):
-            cs[i].column = col
-            cs[i].cond = cond
-            cs[i].value = 0.0
-            cs[i].n_match = 0
-            if cond in (MATCH, NOTMATCH):
-                vals = [bytes(v) for v in (operand or [])]
-                blob = np.frombuffer(b"".join(vals) or b"\0", dtype=np.uint8).copy()
-                lens = np.array([len(v) for v in vals] or [0], dtype=np.int32)
-                keep += [blob, lens]
-                cs[i].match_bytes = blob.ctypes.data
-                cs[i].match_lens = lens.ctypes.data
-                cs[i].n_match = len(vals)
-            elif operand is not None:
-                cs[i].value = float(operand)
+        cs, keep = _cselects(sels)
         self._h = C.c_void_p()
         self.is_table = isinstance(seg, DeviceTable)
+        if self.expr is not None:
+            if self.is_table:
+                raise Imm3Error(ERR_ARG, "a table query takes no select tree: run per-segment queries")
+            pg = np.array(self.expr or [0], dtype=np.int32)
+            if self.aggs is not None:
+                gc = np.array(self.group_cols or [0], dtype=np.int32)
+                ag = np.array([[k, c] for (k, c) in self.aggs] or [[0, 0]], dtype=np.int32)
+                _check(load().imm3_query_create_agg_expr(ctx._h, seg._h, used.ctypes.data, len(self.used_cols), cs, len(sels),
+                                                         pg.ctypes.data, len(self.expr), gc.ctypes.data, len(self.group_cols),
+                                                         ag.ctypes.data, len(self.aggs), table_block_size, C.byref(self._h)))
+            else:
+                _check(load().imm3_query_create_expr(ctx._h, seg._h, used.ctypes.data, len(self.used_cols), cs, len(sels),
+                                                     pg.ctypes.data, len(self.expr), pj.ctypes.data, len(self.proj), limit,
+                                                     table_block_size, C.byref(self._h)))
+            self._finish_init(ctx, seg)
+            return
         create = load().imm3_query_create_table if self.is_table else load().imm3_query_create
         if wide_keys:
             create_agg = load().imm3_query_create_table_agg_wide if self.is_table else load().imm3_query_create_agg_wide
@@ -537,6 +591,9 @@ class DeviceQuery:
         else:
             _check(create(ctx._h, seg._h, used.ctypes.data, len(self.used_cols), cs, len(sels),
                           pj.ctypes.data, len(self.proj), limit, table_block_size, C.byref(self._h)))
+        self._finish_init(ctx, seg)
+
+    def _finish_init(self, ctx, seg):
         ctx._adopt(self)
         nb, tw, nr = C.c_int32(0), C.c_int64(0), C.c_int64(0)
         _check(load().imm3_query_layout(self._h, C.byref(nb), C.byref(tw), C.byref(nr)))
@@ -664,6 +721,12 @@ class DeviceQuery:
         """The kernel form (AGG_FORM_*) of this aggregation's last launch, -1 before the first (include/imm3_diag.h)."""
         f = C.c_int32(-1)
         _check(load().imm3_query_agg_form(self._h, C.byref(f)))
+        return f.value
+
+    def expr_form(self) -> int:
+        """The kernel form of a select tree's last select launch: EXPR_FORM_TILE, EXPR_FORM_GENERIC, -1 when none ran."""
+        f = C.c_int32(-1)
+        _check(load().imm3_query_expr_form(self._h, C.byref(f)))
         return f.value
 
     def device_ptr(self, which: int) -> int:

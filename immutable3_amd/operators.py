@@ -230,7 +230,7 @@ class ScanOp(ColumnVectorOperator):
         names = [c.name for c in t.columns]
         return [names.index(c.name) for c in self.cols]
 
-    def _query(self, leaves, proj_names: Sequence[str] = (), limit: int = 0) -> native.DeviceQuery:
+    def _query(self, leaves, proj_names: Sequence[str] = (), limit: int = 0, expr=None) -> native.DeviceQuery:
         t = self._table()
         colnames = [c.name for c in self.cols]
         sels = []
@@ -247,7 +247,7 @@ class ScanOp(ColumnVectorOperator):
                 raise Exception(f"NoSuchElementException: key not found: {name}")
             proj.append(colnames.index(name))
         seg = self.sm.device_segment(self.tableName, self.segIdx)
-        return native.DeviceQuery(seg.ctx, seg, self._used_indices(), sels, proj, limit, t.blockSize)
+        return native.DeviceQuery(seg.ctx, seg, self._used_indices(), sels, proj, limit, t.blockSize, expr=expr)
 
     def _pfor_decoded(self, c: Column) -> np.ndarray:
         """PFOR_INT column of this segment as the GPU decodes it (one projection without predicates), cached."""
@@ -280,8 +280,8 @@ class ScanOp(ColumnVectorOperator):
             out.append(_decode_view(c, np.asarray(dat[start_row * c.width: (start_row + size) * c.width])))
         return out
 
-    def _batches(self, leaves) -> Iterator[FilledColumnVectorBatch]:
-        q = self._query(leaves)
+    def _batches(self, leaves, expr=None) -> Iterator[FilledColumnVectorBatch]:
+        q = self._query(leaves, expr=expr)
         q.run_select()
         size, oid, woff = q.batches()
         words = q.bitmap()
@@ -330,6 +330,63 @@ class SelectOp(ColumnVectorOperator):
         return scan._batches(leaves)
 
 
+def select_program(select: SelectADT):
+    """A SelectADT (Query.scala:11-15) as the leaves and the postfix program of include/imm3.h's select trees, post-order:
+    ([(col, cond)], [leaf index | native.EXPR_AND | native.EXPR_OR]).  NoSelect adds nothing."""
+    leaves, prog = [], []
+
+    def rec(sel):
+        if isinstance(sel, (And, Or)):
+            before = len(prog)
+            rec(sel.op1)
+            mid = len(prog)
+            rec(sel.op2)
+            if mid > before and len(prog) > mid:          # (a NoSelect side adds nothing: the other side stands alone)
+                prog.append(native.EXPR_AND if isinstance(sel, And) else native.EXPR_OR)
+        elif isinstance(sel, Select):
+            prog.append(len(leaves))
+            leaves.append((sel.col, sel.cond))
+    rec(select)
+    return leaves, prog
+
+
+def has_or(select: SelectADT) -> bool:
+    return isinstance(select, Or) or (isinstance(select, And) and (has_or(select.op1) or has_or(select.op2)))
+
+
+class SelectTreeOp(ColumnVectorOperator):
+    """A whole SelectADT over a ScanOp with its AND / OR tags HONOURED -- what the reference announces and does not do
+    (Engine.scala:236,266: "TODO: use AND/OR operators"; its runOps applies the leaves one after the other).  Fuses with ScanOp /
+    ProjectOp / ProjectAggOp like a SelectOp chain does: one imm3 query per segment (imm3_query_create_expr)."""
+
+    def __init__(self, select: SelectADT, op: ColumnVectorOperator):
+        self.select, self.op = select, op
+        self.program: List[int] = []
+
+    @staticmethod
+    def mkSelectTreeOp(select: SelectADT):
+        return lambda op: SelectTreeOp(select, op)
+
+    def _chain(self):
+        """-> (ScanOp, [(col, cond)] in program order); the program itself is left in self.program"""
+        if not isinstance(self.op, ScanOp):
+            raise Exception("SelectTreeOp must sit on a ScanOp for the fused GPU path")
+        leaves, self.program = select_program(self.select)
+        return self.op, leaves
+
+    def iterator(self):
+        scan, leaves = self._chain()
+        for (_, cond) in leaves:
+            if not isinstance(cond, (Match, GT, LT, EQ)):
+                raise Exception(f"Unsupported condition: {cond}")   # Select.scala:22
+        return scan._batches(leaves, self.program)
+
+
+def _expr_of(op):
+    """the program a fused launch passes on: a SelectTreeOp's (after its _chain()), None for a SelectOp chain"""
+    return op.program if isinstance(op, SelectTreeOp) else None
+
+
 class ProjectOp(ProjectionOperator):
     """Project.scala:17: ProjectOp(cols, op, limit = 0)."""
 
@@ -343,7 +400,7 @@ class ProjectOp(ProjectionOperator):
     def _fused(self):
         if isinstance(self.op, ScanOp):
             return self.op, []
-        if isinstance(self.op, SelectOp):
+        if isinstance(self.op, (SelectOp, SelectTreeOp)):
             return self.op._chain()
         return None
 
@@ -353,7 +410,7 @@ class ProjectOp(ProjectionOperator):
         for (_, cond) in leaves:
             if not isinstance(cond, (Match, GT, LT, EQ)):
                 raise Exception(f"Unsupported condition: {cond}")
-        q = scan._query(leaves, self.cols, self.limit)
+        q = scan._query(leaves, self.cols, self.limit, _expr_of(self.op))
         q.run()
         idx, cols = q.fetch_rows()
         out = []
@@ -573,9 +630,9 @@ class ProjectAggOp(Operator):
             code, operand = _cond_spec(cond)
             sels.append((colnames.index(col), code, operand))
         seg = scan.sm.device_segment(scan.tableName, scan.segIdx)
-        yield from self._run(seg, scan.cols, scan._used_indices(), sels, t.blockSize)
+        yield from self._run(seg, scan.cols, scan._used_indices(), sels, t.blockSize, _expr_of(self.op))
 
-    def _run(self, seg, cols, used_idx, sels, block_size):
+    def _run(self, seg, cols, used_idx, sels, block_size, expr=None):
         """seg: a DeviceSegment or a DeviceTable (then the groups are already merged across segments)."""
         colnames = [c.name for c in cols]
         group_idx = [i for i, n in enumerate(colnames) if n in self.groupBy]
@@ -592,7 +649,7 @@ class ProjectAggOp(Operator):
         wide_key = sum(widths) > 8            # a key wider than 8 bytes: the _wide entry points, the key bytes from the device
         q = native.DeviceQuery(seg.ctx, seg, used_idx, sels, (), 0, block_size,
                                group_cols=group_idx, aggs=[(a.kind, colnames.index(a.col)) for a in aggs],
-                               wide_keys=wide_key)
+                               wide_keys=wide_key, expr=expr)
         q.run()
         keys, first, counts, vals = q.fetch_groups()
         key_bytes = q.fetch_group_keys() if wide_key else None
@@ -705,13 +762,23 @@ class Engine:
     reference: one PipelineThread per segment, :176-180); output order across segments is unspecified in
     the reference (queue interleaving, :255) and defined here as ascending segment index."""
 
-    def __init__(self, sm: GpuSegmentManager):
+    def __init__(self, sm: GpuSegmentManager, honour_and_or: bool = False):
+        """honour_and_or: a query whose select tree holds an Or runs it as a disjunction (SelectTreeOp, per segment) instead of the
+        reference's conjunction.  Off (the default) nothing changes; a tree without Or is the same either way."""
         self.sm = sm
+        self.honour_and_or = honour_and_or
+
+    def _as_tree(self, query: Query) -> bool:
+        return self.honour_and_or and has_or(query.select)
+
+    def _select_ops(self, query: Query):
+        """the operators between ScanOp and the projection: the reference's SelectOp chain, or one SelectTreeOp"""
+        return [SelectTreeOp.mkSelectTreeOp(query.select)] if self._as_tree(query) else resolveSelectOps(query)
 
     def pipelines(self, query: Query):
         table = self.sm.getTable(query.table)
         used = getColumns(query, table)
-        leaves = resolveSelectOps(query)
+        leaves = self._select_ops(query)
         mk_scan = ScanOp.mkScanOp(self.sm, query.table)
         mk_proj = ProjectOp.mkProjectOp(list(query.project.cols), query.project.limit)
         for segIdx in range(self.sm.getTableSegmentCount(table.name)):
@@ -725,6 +792,8 @@ class Engine:
     def _table_plan(self, query: Query):
         """(DeviceTable, used columns, select specs) when the whole table can run as ONE fused launch, else None."""
         table = self.sm.getTable(query.table)
+        if self._as_tree(query):
+            return None                          # a table takes no select tree: per-segment queries
         dt = self.sm.device_table(query.table)
         if dt is None:
             return None
@@ -754,7 +823,7 @@ class Engine:
             agg_op = resolveProjectOp(query.project, table)(ScanOp(self.sm, 0, query.table, used))
             return dict(agg_op._run(dt, used, used_idx, sels, table.blockSize))
         used = getColumns(query, table)
-        leaves = resolveSelectOps(query)
+        leaves = self._select_ops(query)
         mk_scan = ScanOp.mkScanOp(self.sm, query.table)
         mk_agg = resolveProjectOp(query.project, table)
         result = {}

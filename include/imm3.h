@@ -96,7 +96,9 @@ typedef struct {
 
 /* One SelectOp leaf (engine/.../operator/Select.scala:14-23).  Leaves are applied in array order,
  * which is the order PipelineThread.runOps composes them (Engine.scala:237-245); the AND/OR tag is
- * ignored there, so every tree is a conjunction. */
+ * ignored there, so a flat list of leaves is a CONJUNCTION -- through every entry point that takes `sels`, whatever tree the
+ * leaves came from.  A tree whose AND / OR tags are honoured is described by the leaves plus a program: see the select trees
+ * below (the _expr entry points). */
 typedef struct {
     int32_t column;             /* index into the query's used-column list                           */
     int32_t cond;               /* IMM3_GT / IMM3_LT / IMM3_EQ / IMM3_MATCH (others -> error)         */
@@ -215,6 +217,43 @@ int imm3_query_create(imm3_ctx *ctx, const imm3_segment *seg,
                       const int32_t *proj, int32_t n_proj, int64_t limit,
                       int32_t table_block_size, imm3_query **out);
 int imm3_query_destroy(imm3_query *q);
+
+/* ---- select trees: a SelectADT (core/Query.scala:11-15: Select | And(l, r) | Or(l, r) | NoSelect) with its tags HONOURED.
+ * The reference announces this and does not do it ("TODO: use AND/OR operators", Engine.scala:236,266): its runOps, and
+ * every entry point above, execute an Or as an And.  Here the tree is the `leaves` array plus a POSTFIX program of int32:
+ *   value >= 0         push leaf `value`
+ *   IMM3_EXPR_AND      pop two, push their conjunction
+ *   IMM3_EXPR_OR       pop two, push their disjunction
+ * exactly one result must remain; (age < 18 or age > 65) and state = 'CA' is leaves {LT 18, GT 65, Match CA}, program
+ * {0, 1, IMM3_EXPR_OR, 2, IMM3_EXPR_AND}.  An empty program (and no leaves) is NoSelect.
+ * Checks, in this order: the leaves, as imm3_query_create checks its list (NotMatch / NoOp: "Unsupported condition" always; a
+ * leaf on the wrong vector type "Unsupported column vector" and an unknown codec "No implementation for ..." iff the segment
+ * has >= 1 batch; thresholds narrowed per leaf); then the program -- stack underflow, more than one result, an unknown operator
+ * or a leaf index out of range: IMM3_ERR_ARG.
+ * A program WITHOUT IMM3_EXPR_OR is the flat list of its leaves in program order and takes exactly imm3_query_create's path
+ * (same folded predicates, same plan, same kernels).  With one, the library rewrites the tree into a disjunction of TERMS, each
+ * a conjunction with at most one interval / IN-list per column (terms that select nothing and duplicates are dropped), and the
+ * whole select is ONE launch: up to 8 terms over up to 3 int32 / int8 / 2-byte-string columns (IN-lists of <= 8 values) of a
+ * uniform segment through a tile kernel, anything else -- ragged layouts, other string widths, longer IN-lists, more columns,
+ * 9 .. 64 terms -- through a row-per-lane kernel; more than 64 terms: IMM3_ERR_ARG.  PFOR_INT / snappy predicate columns are
+ * read in their decoded form.  The projection goes scan -> offsets scan -> gather (imm3_query_plan reports no one launch and no
+ * records; `limit` bounds the rows emitted, the select covers the whole segment); an aggregation reads the bitmap the select
+ * launch wrote.  Every run call, getter, imm3_query_log_counts and graph capture works as for any query.
+ * Single-segment queries only: an imm3_table takes no tree (out of scope; run per-segment queries and merge). ---- */
+enum { IMM3_EXPR_AND = -1, IMM3_EXPR_OR = -2 };
+int imm3_query_create_expr(imm3_ctx *ctx, const imm3_segment *seg,
+                           const int32_t *used_cols, int32_t n_used,
+                           const imm3_select *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog,
+                           const int32_t *proj, int32_t n_proj, int64_t limit,
+                           int32_t table_block_size, imm3_query **out);
+/* Group-by aggregation under a select tree: the arguments of imm3_query_create_agg_wide (group keys of 0 ..
+ * IMM3_GROUP_KEY_MAX_WIDTH bytes; a key of <= 8 bytes behaves as through imm3_query_create_agg) with the tree in place of `sels`. */
+int imm3_query_create_agg_expr(imm3_ctx *ctx, const imm3_segment *seg,
+                               const int32_t *used_cols, int32_t n_used,
+                               const imm3_select *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog,
+                               const int32_t *group_cols, int32_t n_group,
+                               const imm3_aggregate *aggs, int32_t n_aggs,
+                               int32_t table_block_size, imm3_query **out);
 
 /* ---- group-by aggregation: ProjectAggOp (engine/.../operator/ProjectAggregate.scala:115-227) over the rows the
  * SelectOps keep.  CountAggr / MinDoubleAggr / MaxDoubleAggr / MaxStringAggr (:22-112), and the sum that AvgDoubleAggr

@@ -82,6 +82,19 @@ int imm3_query_plan(const imm3_query *q, int64_t *out, int32_t n);
  * before the first run.  IMM3_ERR_ARG for a query that is not an aggregation. */
 int imm3_query_agg_form(const imm3_query *q, int32_t *form);
 
+/* imm3_query_expr_form: which kernel the last select launch of a select-tree query (an IMM3_EXPR_OR in its program) ran: 0 = the tile
+ * form (k_filter_expr), 1 = the generic form (k_filter_expr_generic); -1 before the first launch, for a tree that selects nothing
+ * (no launch at all) and for every other query. */
+int imm3_query_expr_form(const imm3_query *q, int32_t *form);
+
+/* imm3_expr_normalize: the normal form of a select tree, without a device or a handle (tests hold the terms' truth table against the
+ * tree's).  Columns are given by codec and width; a leaf's `column` indexes them.  json_out receives, NUL-terminated,
+ *   [[{"col":c,"lo":l,"hi":h} | {"col":c,"match":["<hex bytes>", ...]}, ...], ...]     one inner list per term
+ * `needed` (may be NULL) the bytes that takes; cap = 0 only asks for `needed`.  Errors as at query creation; a normal form of
+ * more than 64 terms is IMM3_ERR_ARG. */
+int imm3_expr_normalize(const int32_t *col_codec, const int32_t *col_width, int32_t n_cols, const imm3_select *leaves, int32_t n_leaves,
+                        const int32_t *prog, int32_t n_prog, char *json_out, int64_t cap, int64_t *needed);
+
 /* ---- fault injection into the single-pass projection kernel (k_filter_project, csrc/imm3_project.hip) ----
  * The kernel's work-groups wait on each other; what happens when such a wait does not resolve must be exercised on a device.
  * imm3_ctx_inject_fault: in every later single-pass launch of this context, work-group `work_group` never announces its
