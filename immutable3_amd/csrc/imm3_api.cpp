@@ -1102,12 +1102,36 @@ static int upload_match_blobs(imm3_query *q, std::vector<FoldedPred> &preds);
 // predicate columns have been decoded by now: place_compressed finds no folded predicate to fuse into k_filter_pfor.)
 static int expr_setup(imm3_query *q) {
     if (q->always_false) return IMM3_OK;
-    for (auto &t : q->expr_terms) {
-        const int rc = upload_match_blobs(q, t);
-        if (rc) return rc;
+    // a table has no row-per-lane kernel: the tree fits the tile form or the query is refused, each bound by name.  Every refusal
+    // starts with IMM3_TABLE_TREE_REFUSED: that prefix is what sends a caller to per-segment queries (imm3.h).
+    const auto refuse = [](const std::string &bound) {
+        return fail(IMM3_ERR_ARG, std::string(IMM3_TABLE_TREE_REFUSED) + bound + "; use per-segment queries");
+    };
+    const auto n = [](size_t v) { return std::to_string(v); };
+    if (q->table) {
+        std::vector<int32_t> seen;
+        for (const auto &t : q->expr_terms)
+            for (const auto &p : t) {
+                if (p.kind == KIND_STR && p.width != 2)
+                    return refuse("string predicates on 2-byte columns only (column width " + n((size_t)p.width) + ")");
+                if (p.kind == KIND_STR && p.match.size() > (size_t)kMaxTileMatch)
+                    return refuse("IN-lists of at most " + n((size_t)kMaxTileMatch) + " values (got " + n(p.match.size()) + ")");
+                if (tile_kind(p) == TK_NONE)
+                    return refuse("predicates on int32, int8 and 2-byte string columns only (column " + n((size_t)p.seg_col) + " is none of them)");
+                if (std::find(seen.begin(), seen.end(), p.seg_col) == seen.end()) seen.push_back(p.seg_col);
+            }
+        if (q->expr_terms.size() > (size_t)kMaxExprTerms)
+            return refuse("at most " + n((size_t)kMaxExprTerms) + " terms (this one normalises to " + n(q->expr_terms.size()) + ")");
+        if (seen.size() > (size_t)kMaxTileCols)
+            return refuse("at most " + n((size_t)kMaxTileCols) + " predicate columns (got " + n(seen.size()) + ")");
+    } else {
+        for (auto &t : q->expr_terms) {
+            const int rc = upload_match_blobs(q, t);
+            if (rc) return rc;
+        }
     }
     // tile form: <= kMaxExprTerms terms, every predicate of a tile kind, <= 3 distinct columns that make an instantiated combination
-    bool ok = !q->ragged && !q->table && q->expr_terms.size() <= (size_t)kMaxExprTerms;
+    bool ok = !q->ragged && q->expr_terms.size() <= (size_t)kMaxExprTerms;
     std::vector<std::pair<int32_t, int32_t>> cols; // (tile kind, segment column), in first-seen order
     for (const auto &t : q->expr_terms)
         for (const auto &p : t) {
@@ -1129,6 +1153,12 @@ static int expr_setup(imm3_query *q) {
         ok = n_s2 <= 1 && filter_tile_group(q->expr_kinds) > 0; // (k_filter_expr is instantiated for k_filter_tile's combinations)
     }
     q->expr_tile_ok = ok;
+    if (q->table) { // (no generic form: nothing to upload)
+        if (!ok)
+            return refuse("at most one 2-byte string column among its predicate columns, in a uniform block layout "
+                          "(no kernel for this column-kind combination)");
+        return IMM3_OK;
+    }
     // generic form (also what TV_GENERIC_ONLY runs): the predicates term after term
     q->h_expr_term_start.assign(1, 0);
     for (const auto &t : q->expr_terms) {
@@ -1263,18 +1293,22 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
     if (rc) return rc;
     // A select tree (imm3_query_create_expr): the leaves have passed the checks of a flat list; now the program.  Without an OR it
     // IS a flat list -- the leaves in program order go through the steps below exactly as imm3_query_create's do.
+    // A table's tree (imm3_query_create_table_expr) has ALL its leaves through imm3_query_create_table's checks first, the ones that
+    // need the batches (scan_layout) included, and its program checked behind them.
     std::vector<imm3_select> flat;
     bool has_or = false;
-    if (tree) {
-        rc = expr_check_program(prog, n_prog, n_sels, &has_or);
-        if (rc) return rc;
+    auto check_program = [&]() -> int {
+        const int prc = expr_check_program(prog, n_prog, n_sels, &has_or);
+        if (prc) return prc;
         if (!has_or) {
             for (int32_t i = 0; i < n_prog; ++i)
                 if (prog[i] >= 0) flat.push_back(sels[prog[i]]);
             sels = flat.data();
             n_sels = (int32_t)flat.size();
         }
-    }
+        return IMM3_OK;
+    };
+    if (tree && !table) { rc = check_program(); if (rc) return rc; }
 
     std::unique_ptr<imm3_query, void (*)(imm3_query *)> q(new imm3_query(), query_free);
     q->ctx = ctx;
@@ -1290,6 +1324,7 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
 
     int32_t nb = 0;
     rc = scan_layout(q.get(), sels, n_sels, nb); if (rc) return rc;
+    if (tree && table) { rc = check_program(); if (rc) return rc; }
     if (nb >= 1 && has_or) { rc = fold_tree(q.get(), sels, n_sels, prog, n_prog); if (rc) return rc; }
     else if (nb >= 1) { rc = fold_selects(q.get(), sels, n_sels); if (rc) return rc; }
     rc = place_compressed(q.get(), nb >= 1, row_cols); if (rc) return rc;
@@ -1315,6 +1350,15 @@ extern "C" int imm3_query_create_expr(imm3_ctx *ctx, const imm3_segment *seg,
                                       const int32_t *proj, int32_t n_proj, int64_t limit,
                                       int32_t table_block_size, imm3_query **out) {
     return query_create_impl(ctx, seg, nullptr, used_cols, n_used, leaves, n_leaves, proj, n_proj, limit, table_block_size, {}, out, prog, n_prog, true);
+}
+
+extern "C" int imm3_query_create_table_expr(imm3_ctx *ctx, const imm3_table *table,
+                                            const int32_t *used_cols, int32_t n_used,
+                                            const imm3_select *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog,
+                                            const int32_t *proj, int32_t n_proj, int64_t limit,
+                                            int32_t table_block_size, imm3_query **out) {
+    if (!table || table->segs.empty()) return fail(IMM3_ERR_ARG, "table is null or empty");
+    return query_create_impl(ctx, table->segs[0], table, used_cols, n_used, leaves, n_leaves, proj, n_proj, limit, table_block_size, {}, out, prog, n_prog, true);
 }
 
 extern "C" int imm3_query_create_table(imm3_ctx *ctx, const imm3_table *table,
@@ -1601,6 +1645,10 @@ static int run_select(imm3_query *q, unsigned mode) {
     // exactly ONE launch in the whole select chain: only then may that launch publish the count (and append to the count
     // log) itself, and only then are the survivors' values staged
     const bool expr_tile = q->is_expr && q->expr_tile_ok && fv != TV_GENERIC_ONLY;
+    // (a table has no generic kernel, so the tools' TV_GENERIC_ONLY tuning variant has nothing to run for a table tree: imm3_diag.h)
+    if (q->is_expr && q->table && !expr_tile)
+        return fail(IMM3_ERR_ARG, "a select tree over a table runs through the tile kernel only (the generic-only tuning variant "
+                                  "does not apply to a table); use per-segment queries");
     const bool skip_bitmap = count_only && (chain.single_tile_pass || expr_tile) && !q->table && !overlap_total && fv != TV_COUNT_BY_K_TOTAL;
     q->run.bitmap_valid = !skip_bitmap;
     // `limit` stops the scan (Project.scala:73-80; Engine.scala:166,253-258: the reference's workers stall on the full queue once the
@@ -1641,6 +1689,10 @@ static int run_select(imm3_query *q, unsigned mode) {
                         a.use[ti] |= 1u << k;
                     } else a.cols[ti][k].data = col_flat(q->seg->cols[(size_t)q->expr_seg_col[k]]); // (not tested in this term)
                 }
+            if (q->table) { // address the columns through the tile table (cols[..].data is not read)
+                a.tile_rows = q->table->d_tile_rows;
+                for (int k = 0; k < kMaxTileCols && a.kinds[k] != TK_NONE; ++k) a.tile_ptrs[k] = (const void *const *)q->table->d_tile_ptrs[(size_t)q->expr_seg_col[k]];
+            }
             a.n_rows = q->n_rows;
             a.n_words = q->n_words;
             a.n_tiles = q->n_tiles;
@@ -2777,6 +2829,16 @@ extern "C" int imm3_query_create_table_agg_wide(imm3_ctx *ctx, const imm3_table 
                                                 int32_t table_block_size, imm3_query **out) {
     if (!table || table->segs.empty()) return fail(IMM3_ERR_ARG, "table is null or empty");
     return query_create_agg_impl(ctx, table->segs[0], table, used_cols, n_used, sels, n_sels, group_cols, n_group, aggs, n_aggs, table_block_size, out, true);
+}
+
+extern "C" int imm3_query_create_table_agg_expr(imm3_ctx *ctx, const imm3_table *table,
+                                                const int32_t *used_cols, int32_t n_used,
+                                                const imm3_select *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog,
+                                                const int32_t *group_cols, int32_t n_group,
+                                                const imm3_aggregate *aggs, int32_t n_aggs,
+                                                int32_t table_block_size, imm3_query **out) {
+    if (!table || table->segs.empty()) return fail(IMM3_ERR_ARG, "table is null or empty");
+    return query_create_agg_impl(ctx, table->segs[0], table, used_cols, n_used, leaves, n_leaves, group_cols, n_group, aggs, n_aggs, table_block_size, out, true, prog, n_prog, true);
 }
 
 static void fill_agg_args(const imm3_query *q, AggArgs &a) {

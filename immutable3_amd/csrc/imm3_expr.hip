@@ -14,12 +14,15 @@
 //                               accumulators OR into the tile's words (s_or_b64).  The narrow-only kinds evaluate in the lane, as
 //                               k_filter_tile's do: one 16-bit mask per term and column, AND / OR in the vector unit, and the same
 //                               DPP assembly of the bitmap word.
+//                               Its TABLE instances walk an imm3_table's tile table as k_filter_tile's do (one tile per step, the
+//                               partial tile that ends each segment rolled): the select tree over ALL segments is one launch.
 //   k_filter_expr_generic       any column kind, any layout, up to 64 terms: one row per lane, one bitmap word per wave and step,
-//                               the terms' ColPreds read from device memory.
+//                               the terms' ColPreds read from device memory.  One segment only.
 #include "imm3_internal.h"
 #include "imm3_device.h"
 #include "imm3_tile.h"
 #include <hip/hip_ext.h>
+#include <type_traits>
 
 namespace imm3 {
 
@@ -39,7 +42,7 @@ __device__ __forceinline__ void expr_load(ColRegs<K> &c, const void *data, int64
 
 // the in-lane kinds: OR over the terms of the AND of the constrained columns' masks (wave-uniform control flow: `use` is scalar)
 template <int K0, int K1, int K2>
-__device__ __forceinline__ uint32_t expr_lane_mask(const ExprTileArgs &a, const ColRegs<K0> &c0, const ColRegs<K1> &c1, const ColRegs<K2> &c2) {
+__device__ __forceinline__ uint32_t expr_lane_mask(const ExprTermArgs &a, const ColRegs<K0> &c0, const ColRegs<K1> &c1, const ColRegs<K2> &c2) {
     uint32_t m = 0;
     for (int t = 0; t < a.n_terms; ++t) {
         const uint32_t u = a.use[t];
@@ -55,7 +58,7 @@ __device__ __forceinline__ uint32_t expr_lane_mask(const ExprTileArgs &a, const 
 // One full tile whose columns are in registers -> its bitmap line (unless count-only); returns the lane's share of the survivors
 // (whichever lanes count: every lane, the word owners, or lane 0 -- the caller sums over the wave).
 template <int K0, int K1, int K2>
-__device__ __forceinline__ uint32_t expr_full_tile(const ExprTileArgs &a, int64_t tile, int lane, ColRegs<K0> &c0, ColRegs<K1> &c1, ColRegs<K2> &c2, uint8_t *xp) {
+__device__ __forceinline__ uint32_t expr_full_tile(const ExprTermArgs &a, int64_t tile, int lane, ColRegs<K0> &c0, ColRegs<K1> &c1, ColRegs<K2> &c2, uint8_t *xp) {
     constexpr int kLane = expr_lane_tile(K0, K1, K2);
     if constexpr (kLane == 2) {
         const uint32_t m = expr_lane_mask<K0, K1, K2>(a, c0, c1, c2); // byte 0: rows 8 lane .. + 7, byte 1: 512 + 8 lane .. + 7
@@ -119,12 +122,12 @@ __device__ __forceinline__ uint32_t expr_full_tile(const ExprTileArgs &a, int64_
     }
 }
 
-// A tile with fewer than 1024 valid rows (the end of the segment): rolled, bounds-checked, row-at-a-time.
+// A tile with fewer than 1024 valid rows (the end of a segment): rolled, bounds-checked, row-at-a-time.
+// `valid_rows` rows starting at element `row0` of each column pointer.
 template <int K0, int K1, int K2>
-__device__ __forceinline__ uint32_t expr_partial_tile(const ExprTileArgs &a, int64_t tile, int lane, int64_t row0, int64_t valid_rows, ColRegs<K0> &c0, ColRegs<K1> &c1,
-                                                      ColRegs<K2> &c2) {
+__device__ __forceinline__ uint32_t expr_partial_tile(const ExprTermArgs &a, int64_t tile, int lane, const void *d0, const void *d1, const void *d2, int64_t row0,
+                                                      int64_t valid_rows, ColRegs<K0> &c0, ColRegs<K1> &c1, ColRegs<K2> &c2) {
     const int64_t w = tile * kTileWords + lane;
-    const void *d0 = a.cols[0][0].data, *d1 = a.cols[0][1].data, *d2 = a.cols[0][2].data;
     uint64_t mine = 0ULL;
 #pragma unroll 1
     for (int j = 0; j < kTileWords; ++j) {
@@ -151,8 +154,10 @@ __device__ __forceinline__ uint32_t expr_partial_tile(const ExprTileArgs &a, int
 
 // T = tiles per wave iteration (narrow columns take several tiles at once so that every wave keeps >= 4 KiB of loads in flight),
 // the same values as k_filter_tile's instances.
-template <int K0, int K1, int K2, int T>
-__global__ __launch_bounds__(kBlockThreads) void k_filter_expr(const ExprTileArgs a) {
+// TABLE selects the tile-table walk (table queries) at compile time, as in k_filter_tile: the single-segment kernel carries none of
+// it, not even the tile table's words in its argument block (ExprTermArgs, imm3_internal.h).
+template <int K0, int K1, int K2, int T, bool TABLE>
+__global__ __launch_bounds__(kBlockThreads) void k_filter_expr(const std::conditional_t<TABLE, ExprTileArgs, ExprTermArgs> a) {
     constexpr int kLane = expr_lane_tile(K0, K1, K2);
     constexpr bool kXpose = kLane == 0 && (K0 == TK_I8 || K0 == TK_S2 || K1 == TK_I8 || K1 == TK_S2 || K2 == TK_I8 || K2 == TK_S2);
     // narrow-only kinds spend longer on a tile than its loads take to issue: the next group's loads go out BEFORE the current group
@@ -162,10 +167,36 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_expr(const ExprTileArg
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     uint8_t *xp = s_xpose[wave];
-    const void *d0 = a.cols[0][0].data, *d1 = a.cols[0][1].data, *d2 = a.cols[0][2].data;
+    const void *d0 = a.cols[0][0].data, *d1 = a.cols[0][1].data, *d2 = a.cols[0][2].data; // (one segment; a table's come from its tile table)
     uint32_t lane_total = 0;
     const int64_t wave_id = (int64_t)blockIdx.x * kWavesPerBlock + wave;
     const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+
+    if constexpr (TABLE) { // table query: tiles come from the tile table (one partial tile per segment), one tile per step
+        static_assert(T == 1, "the table walk takes one tile per step");
+        for (int64_t tile = wave_id; tile < a.n_tiles; tile += n_waves) {
+            const uint32_t rows_here = a.tile_rows[tile];
+            const void *t0 = K0 != TK_NONE ? as_global(a.tile_ptrs[0][tile]) : nullptr; // (as_global: no flat loads through a pointer read from memory)
+            const void *t1 = K1 != TK_NONE ? as_global(a.tile_ptrs[1][tile]) : nullptr;
+            const void *t2 = K2 != TK_NONE ? as_global(a.tile_ptrs[2][tile]) : nullptr;
+            ColRegs<K0> c0;
+            ColRegs<K1> c1;
+            ColRegs<K2> c2;
+            if (rows_here == kTileRows) {
+                expr_load<kLane>(c0, t0, 0, lane);
+                expr_load<kLane>(c1, t1, 0, lane);
+                expr_load<kLane>(c2, t2, 0, lane);
+                lane_total += expr_full_tile<K0, K1, K2>(a, tile, lane, c0, c1, c2, xp);
+            } else {
+                lane_total += expr_partial_tile<K0, K1, K2>(a, tile, lane, t0, t1, t2, 0, rows_here, c0, c1, c2);
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) lane_total += __shfl_xor(lane_total, d);
+        if (a.finish) block_partial_finish(a.finish, lane_total, lane, wave);
+        else block_partial_store(a.block_partials, lane_total, lane, wave);
+        return;
+    } else {
     const int64_t n_full = a.n_rows / kTileRows;
     const int64_t n_groups = n_full / T;
 
@@ -215,13 +246,14 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_expr(const ExprTileArg
             expr_load<kLane>(c2, d2, row0, lane);
             lane_total += expr_full_tile<K0, K1, K2>(a, tile, lane, c0, c1, c2, xp);
         } else {
-            lane_total += expr_partial_tile<K0, K1, K2>(a, tile, lane, row0, a.n_rows - row0, c0, c1, c2);
+            lane_total += expr_partial_tile<K0, K1, K2>(a, tile, lane, d0, d1, d2, row0, a.n_rows - row0, c0, c1, c2);
         }
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) lane_total += __shfl_xor(lane_total, d);
     if (a.finish) block_partial_finish(a.finish, lane_total, lane, wave);
     else block_partial_store(a.block_partials, lane_total, lane, wave);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -259,7 +291,13 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_expr_generic(const Exp
 
 #define IMM3_EXPR_CASE(k0, k1, k2, T)                                                                  \
     if (a.kinds[0] == k0 && a.kinds[1] == k1 && a.kinds[2] == k2) {                                    \
-        IMM3_LAUNCH((k_filter_expr<k0, k1, k2, T>), grid, kBlockThreads, s, ev0, ev1, a);              \
+        IMM3_LAUNCH((k_filter_expr<k0, k1, k2, T, false>), grid, kBlockThreads, s, ev0, ev1, seg);     \
+        return true;                                                                                   \
+    }
+// the table instances: one tile per step whatever the kinds
+#define IMM3_EXPR_TABLE_CASE(k0, k1, k2, T)                                                            \
+    if (a.kinds[0] == k0 && a.kinds[1] == k1 && a.kinds[2] == k2) {                                    \
+        IMM3_LAUNCH((k_filter_expr<k0, k1, k2, 1, true>), grid, kBlockThreads, s, ev0, ev1, a);        \
         return true;                                                                                   \
     }
 // k_filter_tile's column-kind combinations (and tiles per iteration), except the one without any column: a tree has leaves
@@ -271,6 +309,11 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_expr_generic(const Exp
     X(TK_I8, TK_I8, TK_I8, 2) X(TK_I32, TK_I32, TK_S2, 1) X(TK_I32, TK_I8, TK_S2, 1) X(TK_I8, TK_I8, TK_S2, 1)
 
 bool launch_filter_expr(const ExprTileArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    if (a.tile_rows) { // a table query: the tile table replaces cols[..].data / n_rows
+        IMM3_EXPR_KINDS(IMM3_EXPR_TABLE_CASE)
+        return false;
+    }
+    const ExprTermArgs &seg = a; // (one segment: the kernel takes the terms alone)
     IMM3_EXPR_KINDS(IMM3_EXPR_CASE)
     return false;
 }

@@ -347,8 +347,8 @@ struct imm3_query {
     unsigned long long *d_desc = nullptr;   // per-span descriptors of the chained scan
     size_t sp_trash_off = 0;                // byte offset of the writers' trash lines in d_desc's allocation
     imm3::ProjectTile *d_tile_desc = nullptr; // table queries: one descriptor per tile of the table for the launch's columns (k_filter_project's TABLE instances)
-    // select tree (imm3_query_create_expr, an OR in it): the selection is the OR of these terms, ONE launch of imm3_expr.hip's tile or
-    // generic kernel; q->preds stays empty, the projection takes the bitmap path and an aggregation reads the bitmap
+    // select tree (imm3_query_create_expr / _table_expr, an OR in it): the selection is the OR of these terms, ONE launch of imm3_expr.hip's
+    // tile or generic kernel (a table: the tile kernel's TABLE instance, or the query is refused); q->preds stays empty, the projection takes the bitmap path and an aggregation reads the bitmap
     bool is_expr = false;
     std::vector<std::vector<FoldedPred>> expr_terms;
     bool expr_tile_ok = false;              // the tile form can take the terms (uniform layout, <= 8 terms over <= 3 tile columns of an instantiated kind combination)

@@ -304,7 +304,10 @@ constexpr int kMaxExprGenericTerms = 64; // terms the generic form takes (its pr
 
 // k_filter_expr<K0, K1, K2>: k_filter_tile's geometry (one wave per 1024-row tile, one 128-byte bitmap line per tile); the columns
 // are loaded once per tile and tested once per term.  ~1.4 KB of kernel arguments.
-struct ExprTileArgs {
+// ExprTermArgs is what the single-segment instances take as their kernel arguments -- the terms and where the results go --
+// and ExprTileArgs, what the host fills, adds the tile table the TABLE instances walk: the segment instances' argument block (and
+// with it their code, down to the offsets of the implicit arguments behind it) does not know that tables exist.
+struct ExprTermArgs {
     TileCol cols[kMaxExprTerms][kMaxTileCols]; // [t][k]: term t's predicate on tile column k (data: the same column in every term)
     uint32_t use[kMaxExprTerms];               // bit k: term t constrains tile column k (an unconstrained column is not tested)
     int32_t kinds[kMaxTileCols];               // sorted ascending, TK_NONE last (selects the template instance)
@@ -314,6 +317,13 @@ struct ExprTileArgs {
     uint32_t *block_partials;
     unsigned long long *finish;                // the query's finish block: the count is reduced in the kernel; null = k_total does
 };
+struct ExprTileArgs : ExprTermArgs {
+    // table queries (imm3_table; the TABLE instances): the tile table replaces cols[t][k].data / n_rows, exactly as in TileArgs.  Tile t
+    // holds tile_rows[t] valid rows (1024 except the last tile of each segment) starting at tile_ptrs[k][t] in column k.  Null for one segment.
+    const uint32_t *tile_rows;
+    const void *const *tile_ptrs[kMaxTileCols];
+};
+static_assert(sizeof(ExprTileArgs) <= 2048, "ExprTileArgs travels as kernel arguments: keep it well under the 4 KiB limit");
 
 // k_filter_expr_generic: any column kind, any layout, up to kMaxExprGenericTerms terms; one wave per bitmap word per iteration.
 struct ExprGenericArgs {

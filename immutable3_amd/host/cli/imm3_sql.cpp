@@ -4,6 +4,7 @@
 //   --parse-only   print the parsed Query ADT and the planner's column order / leaves; no GPU needed.
 //   --honour-and-or  run an `or` of the where clause as a disjunction (default off: the reference executes every Or as an And,
 //                  Engine.scala:236-245).  With --parse-only it also prints the tree's postfix program.
+//   --explain      after the rows, one line on stderr: whether the query ran as one table query or per segment ("path: ...").
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -39,7 +40,7 @@ static std::string showQuery(const Query &q) {
 int main(int argc, char **argv) {
     std::string query, dataDir;
     int device = 0, repeat = 0;
-    bool parseOnly = false, honourAndOr = false;
+    bool parseOnly = false, honourAndOr = false, explain = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if ((a == "-q" || a == "--query") && i + 1 < argc) query = argv[++i];
@@ -48,11 +49,12 @@ int main(int argc, char **argv) {
         else if (a == "--cpu-count" && i + 1 < argc) ++i; // accepted for SqlCli compatibility; segments run on the GPU
         else if (a == "--parse-only") parseOnly = true;
         else if (a == "--honour-and-or") honourAndOr = true;
+        else if (a == "--explain") explain = true;
         else if (a == "--repeat" && i + 1 < argc) repeat = std::atoi(argv[++i]); // re-run the query N times on the resident table, time to stderr
         else { std::fprintf(stderr, "Error parsing arguments: %s\n", a.c_str()); return 2; }
     }
     if (query.empty() || (dataDir.empty() && !parseOnly)) {
-        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only] [--honour-and-or]\n");
+        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only] [--honour-and-or] [--explain]\n");
         return 2;
     }
     try {
@@ -82,6 +84,7 @@ int main(int argc, char **argv) {
         GpuSegmentManager gsm(sm, device);
         Engine engine(gsm, honourAndOr);
         for (const Row &r : engine.execute(q)) std::cout << r.toString() << "\n";
+        if (explain) std::fprintf(stderr, "path: %s\n", engine.lastPath().c_str());
         for (int k = 0; k < repeat; ++k) { // segments are resident now: this is the steady-state query time
             const auto t0 = std::chrono::steady_clock::now();
             const size_t n = engine.execute(q).size();

@@ -12,10 +12,12 @@
 // into one imm3_query.  Everything that touches data goes through the C ABI; there is no CPU evaluation path.
 #pragma once
 
+#include <cstring>
 #include <functional>
 #include <memory>
 
 #include "../../include/imm3.h"
+#include "../../include/imm3_diag.h" // (imm3_query_expr_form, for Engine::lastPath)
 #include "storage.hpp"
 #include "scala_sets.hpp"
 
@@ -23,6 +25,11 @@ namespace immutabledb {
 
 inline void imm3Check(int rc) {
     if (rc != IMM3_OK) throw Exception(imm3_last_error());
+}
+// an _table_expr entry point refused a select tree because it does not fit the one table launch (imm3.h: the message prefix is the
+// contract) -- the one creation error that per-segment queries answer; any other IMM3_ERR_ARG is a real argument error
+inline bool tableTreeRefused(int rc) {
+    return rc == IMM3_ERR_ARG && std::strncmp(imm3_last_error(), IMM3_TABLE_TREE_REFUSED, sizeof(IMM3_TABLE_TREE_REFUSED) - 1) == 0;
 }
 
 // ---- vectors (DataVector.scala) ----
@@ -543,8 +550,11 @@ class ProjectAggOp : public Operator<AggMapTuple> {
         return it;
     }
 
-    // the same aggregation as ONE table-level query (imm3_table): groups merged across segments on the GPU
-    std::vector<AggMapTuple> runOn(imm3_table *table, const std::vector<Column> &cols, const std::vector<int32_t> &usedIdx, const std::vector<imm3_select> &sels) {
+    // the same aggregation as ONE table-level query (imm3_table): groups merged across segments on the GPU.  `prog`: `sels` are the
+    // leaves of a select TREE and this is its postfix program (imm3_query_create_table_agg_expr); false: the table refused the tree
+    // (IMM3_ERR_ARG: it does not fit the one launch) and the caller runs per-segment queries.
+    bool runOn(imm3_table *table, const std::vector<Column> &cols, const std::vector<int32_t> &usedIdx, const std::vector<imm3_select> &sels,
+               const std::vector<int32_t> *prog, std::vector<AggMapTuple> &out) {
         std::vector<int32_t> group;
         for (size_t i = 0; i < cols.size(); ++i)
             for (const auto &g : groupBy_) if (cols[i].name == g) { group.push_back((int32_t)i); break; }
@@ -565,10 +575,18 @@ class ProjectAggOp : public Operator<AggMapTuple> {
         QueryHandle h;
         int keyBytes = 0; // a group key wider than 8 bytes: the _wide entry point
         for (int32_t g : group) keyBytes += cols[(size_t)g].width();
+        if (prog) { // (one entry point for narrow and wide keys)
+            const int rc = imm3_query_create_table_agg_expr(scanOp->manager().ctx(), table, usedIdx.data(), (int32_t)usedIdx.size(), sels.data(), (int32_t)sels.size(),
+                                                            prog->data(), (int32_t)prog->size(), group.data(), (int32_t)group.size(), abi.data(), (int32_t)abi.size(),
+                                                            scanOp->table().blockSize, &h.q);
+            if (tableTreeRefused(rc)) return false;
+            imm3Check(rc);
+        } else
         imm3Check((keyBytes > 8 ? imm3_query_create_table_agg_wide : imm3_query_create_table_agg)(
             scanOp->manager().ctx(), table, usedIdx.data(), (int32_t)usedIdx.size(), sels.data(), (int32_t)sels.size(),
             group.data(), (int32_t)group.size(), abi.data(), (int32_t)abi.size(), scanOp->table().blockSize, &h.q));
-        return decode(h, cols, group, aggs, abi);
+        out = decode(h, cols, group, aggs, abi);
+        return true;
     }
 
   private:
@@ -642,8 +660,8 @@ class ProjectAggOp : public Operator<AggMapTuple> {
 // ---- Engine (Engine.scala:81-197) ----
 class Engine {
   public:
-    // honourAndOr: a query whose select tree holds an Or runs it as a disjunction (one SelectTreeOp per segment) instead of the
-    // reference's conjunction.  Off (the default) nothing changes; a tree without Or is the same either way.
+    // honourAndOr: a query whose select tree holds an Or runs it as a disjunction (one table launch when the table takes the tree, else
+    // one SelectTreeOp per segment) instead of the reference's conjunction.  Off (the default) nothing changes; a tree without Or is the same either way.
     explicit Engine(GpuSegmentManager &sm, bool honourAndOr = false) : sm_(sm), honourAndOr_(honourAndOr) {}
     bool asTree(const Query &q) const { return honourAndOr_ && SelectTreeOp::hasOr(*q.select); }
     // the operators between ScanOp and the projection: the reference's SelectOp chain, or one SelectTreeOp
@@ -692,16 +710,20 @@ class Engine {
         std::vector<imm3_select> sels;
         std::vector<std::string> blobs;
         std::vector<std::vector<int32_t>> lens;
+        bool tree = false;         // `sels` are the leaves of a select tree with an Or (honourAndOr) and `prog` its postfix program:
+        std::vector<int32_t> prog; // the _table_expr entry points, which may still refuse it (IMM3_ERR_ARG: per-segment queries)
     };
     // fills `p` and returns true when the whole table can run as one fused launch
     bool tablePlan(const Query &q, TablePlan &p) {
         const Table &table = sm_.sm.getTable(q.table);
-        if (asTree(q)) return false; // a table takes no select tree: per-segment queries
         p.table = sm_.deviceTable(q.table);
         if (!p.table) return false;
         p.used = getColumns(q, table);
         for (const auto &c : p.used) p.usedIdx.push_back(table.columnIndex(c.name));
-        const std::vector<Leaf> leaves = resolveSelectOps(q);
+        p.tree = asTree(q);
+        std::vector<Leaf> leaves;
+        if (p.tree) SelectTreeOp::program(*q.select, leaves, p.prog);
+        else leaves = resolveSelectOps(q);
         SelectOp::checkConditions(leaves);
         p.sels.resize(leaves.size());
         p.blobs.resize(leaves.size());
@@ -751,12 +773,18 @@ class Engine {
         const std::vector<Column> used = getColumns(q, table);
         const std::vector<Leaf> leaves = resolveSelectOps(q);
         const std::vector<Aggregator> aggs = resolveProjectOp(q.project, table);
+        path_ = "per-segment queries";
         {   // one table-level aggregation query: groups come back already merged in (segment, row) first-seen order
             TablePlan p;
             if (tablePlan(q, p)) {
                 auto scan = std::make_shared<ScanOp>(sm_, 0, q.table, p.used);
                 ProjectAggOp op(aggs, scan, q.project.groupBy);
-                return op.runOn(p.table, p.used, p.usedIdx, p.sels);
+                std::vector<AggMapTuple> merged;
+                if (op.runOn(p.table, p.used, p.usedIdx, p.sels, p.tree ? &p.prog : nullptr, merged)) {
+                    path_ = p.tree ? "one table query: select tree" : "one table query";
+                    return merged;
+                }
+                path_ = std::string("per-segment queries: ") + imm3_last_error();
             }
         }
         auto mkScan = ScanOp::mkScanOp(sm_, q.table);
@@ -792,21 +820,38 @@ class Engine {
             return rows;
         }
         if (q.project.kind != ProjectADT::Project) throw Exception("NoProject");
+        path_ = "per-segment queries";
         {   // the whole table in ONE fused launch when it qualifies
             TablePlan p;
-            if (tablePlan(q, p)) {
-                std::vector<int32_t> proj;
-                std::vector<Column> pcols;
+            bool planned = tablePlan(q, p);
+            QueryHandle h;
+            std::vector<int32_t> proj;
+            std::vector<Column> pcols;
+            if (planned) {
                 for (const auto &name : q.project.cols) {
                     bool found = false;
                     for (size_t k = 0; k < p.used.size() && !found; ++k)
                         if (p.used[k].name == name) { proj.push_back((int32_t)k); pcols.push_back(p.used[k]); found = true; }
                     if (!found) throw Exception("NoSuchElementException: key not found: " + name);
                 }
-                QueryHandle h;
+                if (p.tree) {
+                    const int rc = imm3_query_create_table_expr(sm_.ctx(), p.table, p.usedIdx.data(), (int32_t)p.usedIdx.size(), p.sels.data(), (int32_t)p.sels.size(),
+                                                                p.prog.data(), (int32_t)p.prog.size(), proj.data(), (int32_t)proj.size(), q.project.limit,
+                                                                sm_.sm.getTable(q.table).blockSize, &h.q);
+                    if (tableTreeRefused(rc)) { planned = false; path_ = std::string("per-segment queries: ") + imm3_last_error(); }
+                    else imm3Check(rc);
+                } else
                 imm3Check(imm3_query_create_table(sm_.ctx(), p.table, p.usedIdx.data(), (int32_t)p.usedIdx.size(), p.sels.data(), (int32_t)p.sels.size(),
                                                   proj.data(), (int32_t)proj.size(), q.project.limit, sm_.sm.getTable(q.table).blockSize, &h.q));
+            }
+            if (planned) {
                 imm3Check(imm3_query_run(h.q));
+                path_ = "one table query";
+                if (p.tree) { // the tree's one launch over all segments: say which kernel the library ran (imm3_diag.h)
+                    int32_t form = -1;
+                    imm3Check(imm3_query_expr_form(h.q, &form));
+                    path_ += ": select tree, " + std::string(form == 0 ? "tile form" : form == 1 ? "generic form" : "no launch (selects nothing)");
+                }
                 uint64_t n = 0;
                 imm3Check(imm3_query_row_count(h.q, &n));
                 std::vector<std::vector<uint8_t>> bufs(pcols.size());
@@ -849,9 +894,14 @@ class Engine {
         return rows;
     }
 
+    // which way the last execute / executeAgg went: "one table query[: select tree, <kernel form>]", or "per-segment queries[: <the
+    // library's refusal of the tree>]" (imm3_sql --explain prints it)
+    const std::string &lastPath() const { return path_; }
+
   private:
     GpuSegmentManager &sm_;
     bool honourAndOr_ = false;
+    std::string path_;
 };
 
 } // namespace immutabledb

@@ -25,6 +25,8 @@ MATCH, NOTMATCH, EQ, GT, LT, NOOP = 0, 1, 2, 3, 4, 5
 # operators of a select tree's postfix program (include/imm3.h: IMM3_EXPR_AND / IMM3_EXPR_OR); values >= 0 are leaf indices
 EXPR_AND, EXPR_OR = -1, -2
 EXPR_FORM_TILE, EXPR_FORM_GENERIC = 0, 1
+# how every "this tree does not fit a table" refusal of the _table_expr entry points begins (include/imm3.h: IMM3_TABLE_TREE_REFUSED)
+TABLE_TREE_REFUSED = "a select tree over a table takes "
 
 OK = 0
 ERR_UNSUPPORTED_CONDITION, ERR_UNSUPPORTED_VECTOR, ERR_NO_CODEC, ERR_LAYOUT, ERR_ARG, ERR_DEVICE, ERR_STATE = 1, 2, 3, 4, 5, 6, 7
@@ -40,7 +42,7 @@ EXPORTS = [
     "imm3_query_create", "imm3_query_create_agg", "imm3_query_group_count", "imm3_query_fetch_groups", "imm3_query_agg_shape",
     "imm3_query_fetch_group_strings", "imm3_query_destroy", "imm3_query_reserve_rows",
     "imm3_query_create_agg_wide", "imm3_query_create_table_agg_wide", "imm3_query_fetch_group_keys",
-    "imm3_query_create_expr", "imm3_query_create_agg_expr",
+    "imm3_query_create_expr", "imm3_query_create_agg_expr", "imm3_query_create_table_expr", "imm3_query_create_table_agg_expr",
     "imm3_query_run", "imm3_query_run_select", "imm3_query_run_count", "imm3_query_sync", "imm3_query_join_count", "imm3_query_log_counts",
     "imm3_query_layout", "imm3_query_batches", "imm3_query_count", "imm3_query_bitmap",
     "imm3_query_row_count", "imm3_query_fetch_rows", "imm3_query_device_ptr",
@@ -156,6 +158,8 @@ def load() -> C.CDLL:
     L.imm3_query_fetch_group_keys.argtypes = [vp, vp, C.c_uint32]
     L.imm3_query_create_expr.argtypes = [vp, vp, vp, i32, P(CSelect), i32, vp, i32, vp, i32, i64, i32, P(vp)]
     L.imm3_query_create_agg_expr.argtypes = [vp, vp, vp, i32, P(CSelect), i32, vp, i32, vp, i32, vp, i32, i32, P(vp)]
+    L.imm3_query_create_table_expr.argtypes = L.imm3_query_create_expr.argtypes
+    L.imm3_query_create_table_agg_expr.argtypes = L.imm3_query_create_agg_expr.argtypes
     L.imm3_query_expr_form.argtypes = [vp, P(i32)]
     L.imm3_expr_normalize.argtypes = [vp, vp, i32, P(CSelect), i32, vp, i32, vp, i64, P(i64)]
     L.imm3_query_destroy.argtypes = [vp]
@@ -549,7 +553,8 @@ class DeviceQuery:
                  wide_keys: bool = False, expr: Optional[Sequence[int]] = None):
         """wide_keys: an aggregation through the _wide entry points (group keys of up to GROUP_KEY_MAX_WIDTH bytes).
         expr: a select TREE -- `sels` are its leaves and `expr` the postfix program over them (leaf indices, EXPR_AND, EXPR_OR):
-        the _expr entry points, which honour OR.  Without it `sels` is a conjunction."""
+        the _expr entry points, which honour OR (a DeviceTable: the _table_expr ones -- ERR_ARG when the tree does not fit the one
+        table launch).  Without it `sels` is a conjunction."""
         self.ctx, self.seg = ctx, seg
         self.used_cols = list(used_cols)
         self.proj = list(proj)
@@ -562,19 +567,19 @@ class DeviceQuery:
         self._h = C.c_void_p()
         self.is_table = isinstance(seg, DeviceTable)
         if self.expr is not None:
-            if self.is_table:
-                raise Imm3Error(ERR_ARG, "a table query takes no select tree: run per-segment queries")
+            create = load().imm3_query_create_table_expr if self.is_table else load().imm3_query_create_expr
+            create_agg = load().imm3_query_create_table_agg_expr if self.is_table else load().imm3_query_create_agg_expr
             pg = np.array(self.expr or [0], dtype=np.int32)
             if self.aggs is not None:
                 gc = np.array(self.group_cols or [0], dtype=np.int32)
                 ag = np.array([[k, c] for (k, c) in self.aggs] or [[0, 0]], dtype=np.int32)
-                _check(load().imm3_query_create_agg_expr(ctx._h, seg._h, used.ctypes.data, len(self.used_cols), cs, len(sels),
-                                                         pg.ctypes.data, len(self.expr), gc.ctypes.data, len(self.group_cols),
-                                                         ag.ctypes.data, len(self.aggs), table_block_size, C.byref(self._h)))
+                _check(create_agg(ctx._h, seg._h, used.ctypes.data, len(self.used_cols), cs, len(sels),
+                                  pg.ctypes.data, len(self.expr), gc.ctypes.data, len(self.group_cols),
+                                  ag.ctypes.data, len(self.aggs), table_block_size, C.byref(self._h)))
             else:
-                _check(load().imm3_query_create_expr(ctx._h, seg._h, used.ctypes.data, len(self.used_cols), cs, len(sels),
-                                                     pg.ctypes.data, len(self.expr), pj.ctypes.data, len(self.proj), limit,
-                                                     table_block_size, C.byref(self._h)))
+                _check(create(ctx._h, seg._h, used.ctypes.data, len(self.used_cols), cs, len(sels),
+                              pg.ctypes.data, len(self.expr), pj.ctypes.data, len(self.proj), limit,
+                              table_block_size, C.byref(self._h)))
             self._finish_init(ctx, seg)
             return
         create = load().imm3_query_create_table if self.is_table else load().imm3_query_create

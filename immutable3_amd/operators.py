@@ -763,8 +763,8 @@ class Engine:
     the reference (queue interleaving, :255) and defined here as ascending segment index."""
 
     def __init__(self, sm: GpuSegmentManager, honour_and_or: bool = False):
-        """honour_and_or: a query whose select tree holds an Or runs it as a disjunction (SelectTreeOp, per segment) instead of the
-        reference's conjunction.  Off (the default) nothing changes; a tree without Or is the same either way."""
+        """honour_and_or: a query whose select tree holds an Or runs it as a disjunction (one table launch when the table takes the
+        tree, else SelectTreeOp per segment) instead of the reference's conjunction.  Off (the default) nothing changes; a tree without Or is the same either way."""
         self.sm = sm
         self.honour_and_or = honour_and_or
 
@@ -790,27 +790,36 @@ class Engine:
             yield segIdx, mk_proj(op)
 
     def _table_plan(self, query: Query):
-        """(DeviceTable, used columns, select specs) when the whole table can run as ONE fused launch, else None."""
+        """(DeviceTable, used columns, their table indices, select specs, program) when the whole table can run as ONE fused launch,
+        else None.  program: None for the reference's conjunction; for a tree with an Or under honour_and_or the postfix program over
+        the select specs (imm3_query_create_table_expr), which the library may still refuse (ERR_ARG: _table_tree_refused)."""
         table = self.sm.getTable(query.table)
-        if self._as_tree(query):
-            return None                          # a table takes no select tree: per-segment queries
         dt = self.sm.device_table(query.table)
         if dt is None:
             return None
         used = getColumns(query, table)
         names = [c.name for c in used]
+        if self._as_tree(query):
+            leaves, prog = select_program(query.select)
+        else:
+            leaves, prog = [(op.col, op.cond) for op in (leaf(None) for leaf in resolveSelectOps(query))], None
         sels = []
-        for leaf in resolveSelectOps(query):
-            op = leaf(None)
-            if not isinstance(op.cond, (Match, GT, LT, EQ)):
-                raise Exception(f"Unsupported condition: {op.cond}")
-            code, operand = _cond_spec(op.cond)
-            col = used[names.index(op.col)]
+        for (name, cond) in leaves:
+            if not isinstance(cond, (Match, GT, LT, EQ)):
+                raise Exception(f"Unsupported condition: {cond}")
+            code, operand = _cond_spec(cond)
+            col = used[names.index(name)]
             if code == native.MATCH and (col.codec not in CodecType.STRING_CODECS or col.width != 2 or not (0 < len(operand) <= 8)):
                 return None                      # the tile kernels take 2-byte strings with <= 8 IN-list values
-            sels.append((names.index(op.col), code, operand))
+            sels.append((names.index(name), code, operand))
         tnames = [c.name for c in table.columns]
-        return dt, used, [tnames.index(n) for n in names], sels
+        return dt, used, [tnames.index(n) for n in names], sels, prog
+
+    @staticmethod
+    def _table_tree_refused(e: native.Imm3Error, prog) -> bool:
+        """the table refused a select TREE because it does not fit its one launch (more terms or predicate columns than it carries:
+        the message prefix is the C ABI's contract, imm3.h): per-segment queries.  Any other ERR_ARG is a real argument error."""
+        return prog is not None and e.code == native.ERR_ARG and e.msg.startswith(native.TABLE_TREE_REFUSED)
 
     def execute_agg(self, query: Query):
         """ProjectAgg queries: per-segment ProjectAggOp, then ProjectAggregateQueueOp's combine by group key
@@ -819,9 +828,13 @@ class Engine:
         table = self.sm.getTable(query.table)
         plan = self._table_plan(query)
         if plan is not None:
-            dt, used, used_idx, sels = plan
+            dt, used, used_idx, sels, prog = plan
             agg_op = resolveProjectOp(query.project, table)(ScanOp(self.sm, 0, query.table, used))
-            return dict(agg_op._run(dt, used, used_idx, sels, table.blockSize))
+            try:
+                return dict(agg_op._run(dt, used, used_idx, sels, table.blockSize, prog))
+            except native.Imm3Error as e:
+                if not self._table_tree_refused(e, prog):
+                    raise
         used = getColumns(query, table)
         leaves = self._select_ops(query)
         mk_scan = ScanOp.mkScanOp(self.sm, query.table)
@@ -848,10 +861,15 @@ class Engine:
         plan = self._table_plan(query)
         if plan is None:
             return None
-        dt, used, used_idx, sels = plan
+        dt, used, used_idx, sels, prog = plan
         names = [c.name for c in used]
         proj = [names.index(n) for n in query.project.cols]
-        q = native.DeviceQuery(dt.ctx, dt, used_idx, sels, proj, query.project.limit, self.sm.getTable(query.table).blockSize)
+        try:
+            q = native.DeviceQuery(dt.ctx, dt, used_idx, sels, proj, query.project.limit, self.sm.getTable(query.table).blockSize, expr=prog)
+        except native.Imm3Error as e:
+            if self._table_tree_refused(e, prog):
+                return None
+            raise
         q.run()
         idx, cols = q.fetch_rows()
         seg, row = q.locate_rows(idx)

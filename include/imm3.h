@@ -239,7 +239,7 @@ int imm3_query_destroy(imm3_query *q);
  * read in their decoded form.  The projection goes scan -> offsets scan -> gather (imm3_query_plan reports no one launch and no
  * records; `limit` bounds the rows emitted, the select covers the whole segment); an aggregation reads the bitmap the select
  * launch wrote.  Every run call, getter, imm3_query_log_counts and graph capture works as for any query.
- * Single-segment queries only: an imm3_table takes no tree (out of scope; run per-segment queries and merge). ---- */
+ * An imm3_table takes a tree through imm3_query_create_table_expr / _table_agg_expr below. ---- */
 enum { IMM3_EXPR_AND = -1, IMM3_EXPR_OR = -2 };
 int imm3_query_create_expr(imm3_ctx *ctx, const imm3_segment *seg,
                            const int32_t *used_cols, int32_t n_used,
@@ -254,6 +254,36 @@ int imm3_query_create_agg_expr(imm3_ctx *ctx, const imm3_segment *seg,
                                const int32_t *group_cols, int32_t n_group,
                                const imm3_aggregate *aggs, int32_t n_aggs,
                                int32_t table_block_size, imm3_query **out);
+
+/* Select trees over an imm3_table: the arguments of imm3_query_create_expr / imm3_query_create_agg_expr with `seg` replaced by
+ * `table` (the aggregation takes wide keys, as _agg_expr does).  Checks, in this order: the leaves, exactly as
+ * imm3_query_create_table checks its list (every leaf, whether or not the program mentions it; the vector-type and codec checks
+ * that need a batch included); then the program, with imm3_query_create_expr's errors.
+ * A program WITHOUT IMM3_EXPR_OR takes exactly the path of imm3_query_create_table / _table_agg_wide: same imm3_query_plan, same
+ * kernels, same results.  With one, the tree is normalised as for a segment and must fit the tile form -- at most 8 terms, at
+ * most 3 predicate columns of int32 / int8 / 2-byte string (at most one of them a string), IN-lists of at most 8 values: the
+ * select over ALL segments is then ONE launch (imm3_query_expr_form reports the tile form, 0).  A tree that does not fit is
+ * refused at creation with IMM3_ERR_ARG and a message that names the bound exceeded -- a table has no row-per-lane kernel, the
+ * rule imm3_query_create_table applies to strings of other widths and longer IN-lists -- and the caller runs per-segment tree
+ * queries and merges.  Every such refusal's message begins with IMM3_TABLE_TREE_REFUSED (part of the contract): that prefix, not
+ * the status alone, tells "this tree does not fit a table" from a genuine argument error, which falling back would only repeat.
+ * A tree that normalises to no term selects nothing.  PFOR_INT / snappy predicate columns are read in the
+ * decoded form the table holds.  The projection takes the table's bitmap plan (offsets scan, then gather: imm3_query_plan reports
+ * no one launch and no records); `limit` bounds the rows emitted, in ascending (segment, row) order.  An aggregation reads the
+ * bitmap (never fused).  imm3_query_segment_starts, imm3_query_locate_rows, imm3_query_run_count (a table run always stores its
+ * bitmap), imm3_query_log_counts, graph capture and replay and every getter work as for any table query. */
+#define IMM3_TABLE_TREE_REFUSED "a select tree over a table takes "
+int imm3_query_create_table_expr(imm3_ctx *ctx, const imm3_table *table,
+                                 const int32_t *used_cols, int32_t n_used,
+                                 const imm3_select *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog,
+                                 const int32_t *proj, int32_t n_proj, int64_t limit,
+                                 int32_t table_block_size, imm3_query **out);
+int imm3_query_create_table_agg_expr(imm3_ctx *ctx, const imm3_table *table,
+                                     const int32_t *used_cols, int32_t n_used,
+                                     const imm3_select *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog,
+                                     const int32_t *group_cols, int32_t n_group,
+                                     const imm3_aggregate *aggs, int32_t n_aggs,
+                                     int32_t table_block_size, imm3_query **out);
 
 /* ---- group-by aggregation: ProjectAggOp (engine/.../operator/ProjectAggregate.scala:115-227) over the rows the
  * SelectOps keep.  CountAggr / MinDoubleAggr / MaxDoubleAggr / MaxStringAggr (:22-112), and the sum that AvgDoubleAggr

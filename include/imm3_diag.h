@@ -38,7 +38,8 @@ int imm3_ctx_devclock_raw(imm3_ctx *ctx, int32_t launch, uint64_t *out, int32_t 
 int imm3_ctx_measure_read_gbps(imm3_ctx *ctx, uint64_t bytes, int32_t iters, double *gbps);
 
 /* Tuning knobs (0 = default): filter variant, grid size in workgroups.  For experiments/bench.
- * variant 1 = word-at-a-time kernel only, 2 = count reduce on the aux stream, 3 = no survivor staging,
+ * variant 1 = word-at-a-time kernel only (a select tree over an imm3_table has no such kernel: under variant 1 its run calls
+ * answer IMM3_ERR_ARG), 2 = count reduce on the aux stream, 3 = no survivor staging,
  * 4 = stage int32 columns only, 5 = PFOR_INT predicates read the decoded column instead of the compressed blocks,
  * 7 = reduce the count with a separate k_total launch instead of inside the filter kernel,
  * 6 = projections never use the one-launch kernel, 8 = they use it with gathered SELECT-list columns too, 9 = gathered int32
