@@ -1655,6 +1655,7 @@ static int run_select(imm3_query *q, unsigned mode) {
     // consumer has its rows): a projection with a limit whose select chain is one tile launch over one uniform segment runs that
     // launch as chunks of growing size; every chunk first looks at the rows selected so far (a device word) and leaves at once when
     // the limit has been reached -- nothing is read, no bitmap line written.  Enqueued blindly: no host wait.  TV_NO_LIMIT_CHUNKS: off.
+    // (Over a table the limit stops the scan inside one launch instead: table_limit_applies, in the tile pass below.)
     LimitScanInputs li;
     li.whole = mode & SEL_WHOLE;
     li.count_log_on = q->count_log_on;
@@ -1795,7 +1796,36 @@ static int run_select(imm3_query *q, unsigned mode) {
                 stamped = true;
             }
         }
-        (void)stamped;
+        // A table query with a limit: ONE launch whose work-groups claim runs of tiles in ascending order and stop claiming once the
+        // finished runs hold `limit` rows (k_filter_table_limit); it publishes count, rows to emit and the scanned prefix itself.
+        TableLimitInputs ti;
+        ti.table = q->table != nullptr;
+        ti.tree = q->is_expr;
+        ti.limit = q->limit;
+        ti.count_in_scan = count_in_scan;
+        ti.single_tile_pass = chain.single_tile_pass;
+        ti.whole = mode & SEL_WHOLE;
+        ti.count_log_on = q->count_log_on;
+        ti.count_only = count_only;
+        ti.filter_variant = fv;
+        ti.n_tiles = q->n_tiles;
+        ti.grid = std::min(grid, kTableLimitMaxGrid); // (narrow columns like 1536 work-groups for a whole scan; here they would claim half of a 100 M-row table before the first run is done)
+        if (table_limit_applies(ti)) {
+            grid = ti.grid;
+            if (stamped) { // (diagnostics: the stamps of this launch are this grid's)
+                std::lock_guard<std::mutex> lk(ctx->mu);
+                if (!ctx->stamp_grids.empty()) ctx->stamp_grids.back() = grid;
+            }
+            a.finish = q->d_total;
+            a.defer_lines = 0;
+            LaunchTimer t(ctx, 0);
+            if (!launch_filter_table_limit(a, grid, s, t.start, t.stop)) return fail(IMM3_ERR_ARG, "internal: no tile kernel for this column combination");
+            HIPCHK(hipGetLastError());
+            count_done = true;
+            q->run.select_partial = true; // (the offsets scan and the gather stop at finish[kFinishLimitTiles]; the getters' whole select: settle_whole_select)
+            ++pass;
+            continue;
+        }
         if (chunked) { // the limit scan: this launch in chunks that end at tiles 1024, 8192, 32 768, ...; each adds to the running count and scanned-tile words
             int widths[kMaxTileCols] = {0, 0, 0};
             for (int k = 0; k < kMaxTileCols; ++k) widths[k] = a.kinds[k] == TK_I32 ? 4 : (a.kinds[k] == TK_S2 ? 2 : (a.kinds[k] == TK_I8 ? 1 : 0));

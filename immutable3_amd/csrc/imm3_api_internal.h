@@ -71,4 +71,13 @@ struct LimitScanInputs {
 };
 bool limit_scan_applies(const LimitScanInputs &in);
 
+// A projection with a `limit` over a TABLE: one limit-aware launch whose work-groups claim runs of tiles and stop claiming at the
+// limit (k_filter_table_limit), or the whole select as before?
+struct TableLimitInputs {
+    bool table = false, tree = false, count_in_scan = false, single_tile_pass = false, whole = false, count_log_on = false, count_only = false;
+    int64_t limit = 0, n_tiles = 0;
+    int filter_variant = 0, grid = 0; // grid: work-groups of the launch
+};
+bool table_limit_applies(const TableLimitInputs &in);
+
 } // namespace imm3

@@ -67,7 +67,7 @@ enum TuningVariant : int {
     TV_RECORDS_ALWAYS = 11,     // survivor records even when no predicate column is projected; the cost model drops neither them nor the one launch
     TV_PLAN_PINNED = 12,        // the plan made at creation stands whatever the cost model says (P still adapts); also: no bitmap lines parked in LDS
     TV_COUNT_SMALL_GRID = 13,   // a one-launch select chain reduces its count in the kernel only at <= 512 work-groups
-    TV_NO_LIMIT_CHUNKS = 14,    // a `limit` query scans the whole segment in one launch
+    TV_NO_LIMIT_CHUNKS = 14,    // a `limit` query scans the whole segment in one launch (a table query: the whole table)
     TV_LIMIT_NO_FUSED_GATHER = 15, // a small limit takes k_scan + k_gather instead of k_limit_gather
     TV_NO_CU_RESERVATION = 16,  // one-launch projections use every CU while a communicator is attached
     TV_AGG_SELECT_LAUNCH = 17,  // an aggregation's select chain runs as its own launch, not inside the aggregation launch

@@ -235,6 +235,17 @@ constexpr int kFinishDense = 9;         // finish[9]: single-pass projection: ra
 constexpr int kFinishLimitRows = 11;    // finish[11]: rows selected by the chunks of this run so far
 constexpr int kFinishLimitTiles = 12;   // finish[12]: tiles those chunks scanned (the offsets scan and the gather stop there)
 constexpr int kFinishLimitGaveUp = 13;  // finish[13]: k_limit_gather's look-back ran into its poll cap in the run with this tag: gather with k_scan + k_gather
+// A TABLE query's limit stops the scan inside ONE launch (k_filter_table_limit, imm3_kernels.hip): its work-groups claim runs of
+// kTableLimitClaimTiles consecutive virtual tiles from a ticket counter, in ascending order, and stop claiming once the runs that are
+// done have selected `limit` rows (finish[kFinishLimitRows]); the launch's last work-group turns the tickets into finish[kFinishLimitTiles]
+// and sets the ticket counter and the rows word back to zero for the next run (no memset, nothing for a recorded graph to miss).
+// The ticket counter sits on a 128-byte line of its own, away from the header line that holds the rows word (every claim is one
+// returning atomic on the ticket and one access to the rows word; on ONE line they queue behind each other): a spare word of the
+// last sub-tally's line, which the tally touches once per work-group, at its exit.
+constexpr int kFinishLimitTicketLineWord = 8; // (word 0 of a sub-tally's line is the sub-tally)
+constexpr int kTableLimitMaxGrid = 512; // work-groups of the limit-aware launch at most (2 per CU): what they claim at once is what a `limit 10` scans at least
+constexpr int kTableLimitClaimTiles = 32; // tiles per claim: eight per wave.  A multiple of kSpanTiles: the gather walks whole spans of the scanned prefix
+static_assert(kTableLimitClaimTiles % kSpanTiles == 0 && kTableLimitClaimTiles % kWavesPerBlock == 0, "the scanned prefix ends on a span boundary; a claim splits evenly over the waves");
 constexpr int kDescValueBits = 36, kDescFlagShift = 36, kDescEpochShift = 38;
 constexpr unsigned long long kDescValueMask = (1ULL << kDescValueBits) - 1;
 constexpr unsigned long long kDescEpochMask = (1ULL << (64 - kDescEpochShift)) - 1;
@@ -534,6 +545,8 @@ void launch_group_keys(const AggArgs &a, uint32_t n_groups, int key_bytes, uint8
 
 constexpr int kSubTallies = 32;                       // in-kernel count reduce: sub-tallies (finish_add, imm3_device.h)
 constexpr int kFinishWords = 16 + kSubTallies * 16;   // u64 words of a query's `finish` block: header (9 used, padded to a 128-byte line) + one line per sub-tally
+constexpr int kFinishLimitTicket = 16 + 16 * (kSubTallies - 1) + kFinishLimitTicketLineWord; // finish[520]: claims handed out so far in this launch (zero between runs)
+static_assert(kFinishLimitTicket < kFinishWords && kFinishLimitTicketLineWord > 0 && kFinishLimitTicketLineWord < 16, "the ticket word lies inside the finish block, beside the last sub-tally");
 constexpr int kMaxFilterGrid = 4096; // capacity of block_partials
 int filter_grid(int64_t units, bool generic, bool any_i32, int grid_blocks, int narrow_row_bytes = 0); // narrow_row_bytes: bytes per row of a launch without an int32 column
 // ev0/ev1: optional events stamped with the kernel's own start/end (hipExtLaunchKernelGGL), else null
@@ -584,6 +597,7 @@ struct SumCountsArgs {
 void launch_sum_counts(const SumCountsArgs &a, hipStream_t s);
 
 bool launch_filter_tile(const TileArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+bool launch_filter_table_limit(const TileArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // a.tile_rows, a.bitmap and a.finish set; false: no instance for these kinds
 int filter_tile_group(const int32_t *kinds); // tiles per wave iteration of the instance for these kinds (0: none)
 void launch_filter_generic(const FilterArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 void launch_total(const TotalArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);

@@ -456,6 +456,98 @@ __global__ __launch_bounds__(kBlockThreads, tile_min_waves(K0, K1, STAGE)) void 
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_filter_table_limit<K0, K1, K2>: k_filter_tile's TABLE walk for a projection with a `limit` (Project.scala:73-80: ProjectIterator
+// stops at the limit; Engine.scala:166,253-258: the workers of the segments behind it stall on the full queue).  One launch that scans
+// AND stops: the work-groups do not walk the tile table grid-stride, each CLAIMS the next run of kTableLimitClaimTiles consecutive
+// virtual tiles from one ticket counter (finish[kFinishLimitTicket]), one returning device-scope atomic per claim.  Tickets go out in
+// ascending order, so the claimed tiles are always a prefix [0, T) of the table.  Before every claim the work-group looks at the rows
+// the finished runs have selected (finish[kFinishLimitRows]) and leaves when they have reached the limit; after a run it adds the
+// run's survivors to that word (one atomic per claim; its returned value is the look before the next claim).  Check first, then
+// claim: every ticket handed out is evaluated to its end, so when the rows word reaches the limit every run it counted lies inside
+// the claimed prefix, the final prefix is complete and holds at least `limit` survivors -- the first `limit` survivors of the table
+// in (segment, row) order are in it.  No work-group waits for another: no look-back, no poll, no residency requirement.
+// Both words are touched with device-scope atomics only (the XCDs' L2s are not coherent).  The launch's last work-group (the finish
+// block's tally says which) publishes count and rows to emit of the prefix, writes finish[kFinishLimitTiles] = min(tickets x claim,
+// n_tiles) -- where the offsets scan and the gather stop; bitmap lines behind it are never written -- and zeroes both words for the
+// next run.  A run is evaluated like any table tile: full tiles on the fast path, each segment's partial tile rolled, one 128-byte
+// bitmap line per tile at its usual place.  Wave w of the work-group takes tiles w, w + 4, ... of the run.
+// ---------------------------------------------------------------------------------------------
+template <int K0, int K1, int K2>
+__global__ __launch_bounds__(kBlockThreads) void k_filter_table_limit(const TileArgs a) {
+    constexpr int kLane = lane_tile(K0, K1, K2, false);
+    constexpr bool kXpose = kLane == 0 && (K0 == TK_I8 || K0 == TK_S2 || K1 == TK_I8 || K1 == TK_S2 || K2 == TK_I8 || K2 == TK_S2);
+    __shared__ __attribute__((aligned(16))) uint8_t s_xpose[kWavesPerBlock][kXpose ? kXposeBytes : 16];
+    __shared__ long long s_first;               // first tile of the run the work-group holds, -1: none (it leaves)
+    __shared__ uint32_t s_run[kWavesPerBlock];  // the waves' survivors of that run
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    uint8_t *xp = s_xpose[wave];
+    if (a.stamps && threadIdx.x == 0) a.stamps[2 * blockIdx.x] = wall_clock64(); // instrumented pass of bench.py only
+    Arena A; // (no records here: the staging arguments of the tile helpers stay unused)
+    const int64_t wave_id = (int64_t)blockIdx.x * kWavesPerBlock + wave;
+    unsigned long long *rows_word = a.finish + kFinishLimitRows, *ticket_word = a.finish + kFinishLimitTicket;
+    const unsigned long long limit = a.finish[3]; // (written at creation)
+    const unsigned long long n_claims = (unsigned long long)((a.n_tiles + kTableLimitClaimTiles - 1) / kTableLimitClaimTiles);
+    unsigned long long seen = 0, block_total = 0; // thread 0: the rows word as last seen; survivors of this work-group's runs
+    if (threadIdx.x == 0) seen = __hip_atomic_load(rows_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (;;) {
+        if (threadIdx.x == 0) {
+            long long first = -1;
+            if (seen < limit) { // check first, then claim
+                const unsigned long long ticket = __hip_atomic_fetch_add(ticket_word, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (ticket < n_claims) first = (long long)(ticket * (unsigned long long)kTableLimitClaimTiles); // (a ticket past the table's end: nothing is left)
+            }
+            s_first = first;
+        }
+        __syncthreads();
+        const int64_t first = s_first;
+        if (first < 0) break; // block-uniform
+        const int64_t end = first + kTableLimitClaimTiles < a.n_tiles ? first + kTableLimitClaimTiles : a.n_tiles;
+        uint32_t lane_total = 0;
+        for (int64_t tile = first + wave; tile < end; tile += kWavesPerBlock) {
+            const uint32_t rows_here = a.tile_rows[tile];
+            const void *d0 = K0 != TK_NONE ? as_global(a.tile_ptrs[0][tile]) : nullptr; // (as_global: no flat loads through a pointer read from memory)
+            const void *d1 = K1 != TK_NONE ? as_global(a.tile_ptrs[1][tile]) : nullptr;
+            const void *d2 = K2 != TK_NONE ? as_global(a.tile_ptrs[2][tile]) : nullptr;
+            ColRegs<K0> c0;
+            ColRegs<K1> c1;
+            ColRegs<K2> c2;
+            if (rows_here == kTileRows) {
+                tile_load<kLane>(c0, d0, 0, lane);
+                tile_load<kLane>(c1, d1, 0, lane);
+                tile_load<kLane>(c2, d2, 0, lane);
+                lane_total += finish_full_tile<K0, K1, K2, false>(a, tile, lane, c0, c1, c2, xp, nullptr, nullptr, A, wave_id);
+            } else {
+                lane_total += partial_tile<K0, K1, K2, false>(a, tile, lane, d0, d1, d2, 0, rows_here, c0, c1, c2, nullptr, nullptr, A, wave_id);
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) lane_total += __shfl_xor(lane_total, d); // (whichever lanes counted: 0..15, every fourth, or all)
+        if (lane == 0) s_run[wave] = lane_total;
+        __syncthreads(); // (also: every wave has read s_first before thread 0 writes the next one)
+        if (threadIdx.x == 0) {
+            unsigned long long t = 0;
+#pragma unroll
+            for (int i = 0; i < kWavesPerBlock; ++i) t += s_run[i];
+            block_total += t;
+            // returning, and its value used: the add has been performed before this thread arrives at the tally below, so the
+            // last work-group's reset of the word cannot be overtaken by it
+            seen = t ? __hip_atomic_fetch_add(rows_word, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + t
+                     : __hip_atomic_load(rows_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if (threadIdx.x == 0) {
+        if (finish_add(a.finish, block_total)) { // the launch's last work-group: count and rows to emit of the prefix are published
+            const unsigned long long claimed = __hip_atomic_load(ticket_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * (unsigned long long)kTableLimitClaimTiles;
+            a.finish[kFinishLimitTiles] = claimed < (unsigned long long)a.n_tiles ? claimed : (unsigned long long)a.n_tiles;
+            __hip_atomic_store(ticket_word, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // ready for the next run
+            __hip_atomic_store(rows_word, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (a.stamps) a.stamps[2 * blockIdx.x + 1] = wall_clock64();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // k_filter_generic: any column kind (any string width, long IN-lists), any layout; one wave per bitmap
 // word per iteration.
 //   uniform layout (word_row_base == null): word w covers rows [64w, min(64w+64, n_rows))
@@ -1032,6 +1124,19 @@ int filter_grid(int64_t units, bool generic, bool any_i32, int grid_blocks, int 
 
 bool launch_filter_tile(const TileArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     IMM3_TILE_KINDS(IMM3_TILE_CASE)
+    return false;
+}
+
+// the limit-aware table launch: the same column-kind combinations, one instance each (no deferred lines, no records)
+bool launch_filter_table_limit(const TileArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    if (!a.tile_rows || !a.bitmap || !a.finish || a.and_existing || a.stage_rec) return false;
+#define IMM3_TABLE_LIMIT_CASE(k0, k1, k2, T)                                                    \
+    if (a.kinds[0] == k0 && a.kinds[1] == k1 && a.kinds[2] == k2) {                             \
+        IMM3_LAUNCH((k_filter_table_limit<k0, k1, k2>), grid, kBlockThreads, s, ev0, ev1, a);   \
+        return true;                                                                            \
+    }
+    IMM3_TILE_KINDS(IMM3_TABLE_LIMIT_CASE)
+#undef IMM3_TABLE_LIMIT_CASE
     return false;
 }
 

@@ -5,7 +5,7 @@
 //   * the cost model's decisions between the one launch, survivor records and the bitmap path (imm3_plan.h) on an estimate --
 //     the sample at creation, a reservation -- or on a run's count (single_pass_stream_columns, records_drop_if_narrow,
 //     single_pass_drop_if_narrow, single_pass_restore);
-//   * whether a projection with a `limit` scans in chunks (limit_scan_applies);
+//   * whether a projection with a `limit` scans in chunks (limit_scan_applies) or, over a table, in one launch that stops (table_limit_applies);
 //   * the select chain's passes (plan_select_chain) and the plan query creation makes for a projection (plan_projection).
 // The reference has no planner to mirror: its Engine builds ScanOp -> SelectOp* -> ProjectOp per segment unconditionally
 // (engine/src/main/scala/immutabledb/engine/Engine.scala:158-196); these are choices between equivalent executions of that chain.
@@ -36,6 +36,19 @@ bool limit_scan_applies(const LimitScanInputs &in) {
     if (in.table || in.records || in.skip_bitmap || in.overlap_total) return false;
     if (in.filter_variant == TV_COUNT_BY_K_TOTAL || in.filter_variant == TV_NO_LIMIT_CHUNKS) return false;
     return in.n_tiles > kLimitFirstChunkTiles;
+}
+
+// The same over a TABLE (all segments a GPU owns: what both Engines build for a multi-segment table) is ONE launch that stops itself
+// (k_filter_table_limit, imm3_kernels.hip: runs of kTableLimitClaimTiles tiles claimed in ascending order until the runs that are
+// done have selected `limit` rows).  A flat query only (a select tree with an OR runs k_filter_expr), with a projection behind it
+// (count_in_scan), a select chain of one tile launch, not for a getter's whole select, a count log or a count-only run, not under
+// the tuning variants that pin the old launches (7, 14: the whole select stays reachable for comparison) -- and only when the table
+// has more tiles than the launch's work-groups claim at once: below that every tile is claimed before the first run is done.
+bool table_limit_applies(const TableLimitInputs &in) {
+    if (!in.table || in.tree || !(in.limit > 0) || !in.count_in_scan || !in.single_tile_pass) return false;
+    if (in.whole || in.count_log_on || in.count_only) return false;
+    if (in.filter_variant == TV_COUNT_BY_K_TOTAL || in.filter_variant == TV_NO_LIMIT_CHUNKS) return false;
+    return in.grid > 0 && in.n_tiles > (int64_t)in.grid * kTableLimitClaimTiles;
 }
 
 int tile_kind(const FoldedPred &fp) {
@@ -718,4 +731,22 @@ extern "C" int imm3_plan_limit_scan(int32_t whole, int32_t count_log_on, int32_t
     in.filter_variant = filter_variant;
     in.n_tiles = n_tiles;
     return limit_scan_applies(in) ? 1 : 0;
+}
+
+// diagnostics: the same for the limit-aware table launch (table_limit_applies; tests/test_table_limit_host.py walks it)
+extern "C" int imm3_plan_table_limit(int32_t table, int32_t tree, int64_t limit, int32_t count_in_scan, int32_t single_tile_pass, int32_t whole, int32_t count_log_on,
+                                     int32_t count_only, int32_t filter_variant, int64_t n_tiles, int32_t grid) {
+    TableLimitInputs in;
+    in.table = table != 0;
+    in.tree = tree != 0;
+    in.limit = limit;
+    in.count_in_scan = count_in_scan != 0;
+    in.single_tile_pass = single_tile_pass != 0;
+    in.whole = whole != 0;
+    in.count_log_on = count_log_on != 0;
+    in.count_only = count_only != 0;
+    in.filter_variant = filter_variant;
+    in.n_tiles = n_tiles;
+    in.grid = grid;
+    return table_limit_applies(in) ? 1 : 0;
 }

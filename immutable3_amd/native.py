@@ -56,6 +56,7 @@ DIAG_EXPORTS = [
     "imm3_ctx_timing_enable", "imm3_ctx_timing_reset", "imm3_ctx_timing_mask", "imm3_ctx_timing_collect", "imm3_ctx_set_tuning",
     "imm3_ctx_measure_read_gbps", "imm3_ctx_devclock_enable", "imm3_ctx_devclock_collect", "imm3_ctx_devclock_raw", "imm3_query_plan",
     "imm3_ctx_inject_fault", "imm3_ctx_debug_device_lock", "imm3_plan_predict", "imm3_comm_debug_standin", "imm3_plan_limit_scan",
+    "imm3_plan_table_limit",
     "imm3_query_agg_form", "imm3_query_expr_form", "imm3_expr_normalize",
 ]
 COMM_ID_BYTES = 128
@@ -476,6 +477,12 @@ AGG_COUNT, AGG_MIN, AGG_MAX, AGG_SUM = 0, 1, 2, 3
 AGG_FORM_LANES, AGG_FORM_LANES_WIDE, AGG_FORM_DIRECT, AGG_FORM_TILE, AGG_FORM_GENERAL = 0, 1, 2, 3, 4
 GROUP_KEY_MAX_WIDTH = 256  # include/imm3.h: IMM3_GROUP_KEY_MAX_WIDTH (DeviceQuery(..., wide_keys=True))
 TV_AGG_WEAK_HASH = 18      # tuning variant: wide group keys hash to 3 bits (csrc/imm3_handles.h)
+TV_NO_LIMIT_CHUNKS = 14    # tuning variant: a `limit` never stops the scan -- the whole segment / table in one launch (csrc/imm3_handles.h)
+# csrc/imm3_internal.h: kTableLimitClaimTiles -- a table query with a limit scans in runs of this many virtual tiles, claimed in
+# ascending order by the work-groups of one launch, until the finished runs hold `limit` rows; kFinishLimitTiles -- the word of the
+# finish block (DeviceQuery.device_ptr(1), u64 words) that then says how many tiles were scanned
+TABLE_LIMIT_CLAIM_TILES = 32
+FINISH_LIMIT_TILES = 12
 
 
 class DeviceTable:
@@ -521,6 +528,16 @@ def _cselects(sels):
         elif operand is not None:
             cs[i].value = float(operand)
     return cs, keep
+
+
+def plan_table_limit(table=1, tree=0, limit=10, count_in_scan=1, single_tile_pass=1, whole=0, count_log_on=0, count_only=0,
+                     filter_variant=0, n_tiles=1 << 20, grid=512) -> int:
+    """include/imm3_diag.h: imm3_plan_table_limit -- the library's own decision whether a table query with a limit runs the one
+    launch that stops at the limit (1) or the whole select (0); a pure function, no device needed."""
+    L = load()
+    L.imm3_plan_table_limit.argtypes = [C.c_int32, C.c_int32, C.c_int64] + [C.c_int32] * 6 + [C.c_int64, C.c_int32]
+    return int(L.imm3_plan_table_limit(table, tree, limit, count_in_scan, single_tile_pass, whole, count_log_on, count_only,
+                                       filter_variant, n_tiles, grid))
 
 
 def expr_normalize(col_codecs: Sequence[int], col_widths: Sequence[int], leaves: Sequence[tuple], prog: Sequence[int]):

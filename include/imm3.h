@@ -184,7 +184,15 @@ int imm3_table_create(imm3_ctx *ctx, const imm3_segment *const *segs, int32_t n_
 int imm3_table_destroy(imm3_table *t);
 /* Table flavours of imm3_query_create / imm3_query_create_agg (same arguments, `seg` replaced by `table`).
  * Layout getters cover all segments in order (batches of segment 0, then segment 1, ...; oid restarts per segment);
- * imm3_query_segment_starts gives, per segment, its first batch and its first word in the bitmap. */
+ * imm3_query_segment_starts gives, per segment, its first batch and its first word in the bitmap.
+ * `limit` > 0 STOPS THE SCAN of a table projection too (Project.scala:73-80; Engine.scala:166,253-258: the workers of the segments
+ * behind the limit stall on the full queue): when the select is one tile launch over a table of more tiles than that launch's
+ * work-groups claim at once, the work-groups take runs of 32 virtual tiles in ascending order and stop once the finished runs
+ * hold `limit` rows.  The getters then answer exactly as behind a segment's stopped scan: imm3_query_row_count and
+ * imm3_query_fetch_rows give the first `limit` survivors in (segment, row) order; imm3_query_count, imm3_query_bitmap,
+ * imm3_query_join_count and a count log give the WHOLE table's figures (the whole select runs first; a logged query never stops);
+ * imm3_query_segment_starts and imm3_query_locate_rows are unchanged.  Behind imm3_query_run the device-side bitmap and count
+ * (imm3_query_device_ptr 0, 1) cover the scanned prefix only.  A select tree with an IMM3_EXPR_OR scans the whole table. */
 int imm3_query_create_table(imm3_ctx *ctx, const imm3_table *table,
                             const int32_t *used_cols, int32_t n_used,
                             const imm3_select *sels, int32_t n_sels,

@@ -47,7 +47,7 @@ int imm3_ctx_measure_read_gbps(imm3_ctx *ctx, uint64_t bytes, int32_t iters, dou
  * then adapts from the first run's count on), 11 = survivor records are staged even when no predicate column is projected,
  * 12 = the plan made at creation stands whatever the cost model predicts (tests of one plan's kernels; P still adapts) and no
  * bitmap lines are parked in LDS, 13 = a one-launch select chain reduces its count inside the filter kernel only at <= 512
- * work-groups (default: at every grid), 14 = a `limit` query scans the whole segment in one launch instead of in chunks behind a limit-reached word (decided per run),
+ * work-groups (default: at every grid), 14 = a `limit` query scans the whole segment in one launch instead of in chunks behind a limit-reached word, and the whole table instead of stopping at the limit (decided per run),
  * 15 = a small limit behind a limit scan takes k_scan + k_gather instead of the one fused launch (k_limit_gather),
  * 16 = one-launch projections use every CU even while a communicator whose collectives launch kernels is attached (default: one
  * CU per XCD is left to the collective's kernel), 17 = an aggregation's select chain runs as its own launch instead of inside the
@@ -117,6 +117,14 @@ int imm3_expr_normalize(const int32_t *col_codec, const int32_t *col_width, int3
  * no handle: tests walk it. */
 int imm3_plan_limit_scan(int32_t whole, int32_t count_log_on, int32_t count_in_scan, int64_t limit, int32_t single_tile_pass, int32_t table, int32_t records,
                          int32_t skip_bitmap, int32_t overlap_total, int32_t filter_variant, int64_t n_tiles);
+/* imm3_plan_table_limit: does a projection with a `limit` over an imm3_table run its select as the one launch that stops at the limit
+ * (1: k_filter_table_limit -- work-groups claim runs of 32 virtual tiles in ascending order and stop claiming once the finished runs
+ * have selected `limit` rows) or as the whole select (0)?  csrc/imm3_planner.cpp: table_limit_applies, pure like the decision above.
+ * 1 needs: a table; a flat query (tree = 0: no IMM3_EXPR_OR); limit > 0; a projection behind the select (count_in_scan); a select chain
+ * of one tile launch; not a getter's whole select; no count log; not a count-only run; not tuning variant 7 or 14; and
+ * n_tiles > grid * 32, `grid` being the launch's work-groups. */
+int imm3_plan_table_limit(int32_t table, int32_t tree, int64_t limit, int32_t count_in_scan, int32_t single_tile_pass, int32_t whole, int32_t count_log_on,
+                          int32_t count_only, int32_t filter_variant, int64_t n_tiles, int32_t grid);
 struct imm3_comm;
 int imm3_comm_debug_standin(struct imm3_comm *comm, int32_t work_groups, uint32_t spin_us);
 int imm3_ctx_inject_fault(imm3_ctx *ctx, int32_t work_group, int32_t span, uint32_t max_polls);
