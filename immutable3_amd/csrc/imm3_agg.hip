@@ -1926,6 +1926,151 @@ void launch_merge_collect_list(const MergeArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(k_merge_collect_list, dim3(grid < 1 ? 1 : grid), dim3(kBlockThreads), 0, s, a);
 }
 
+// ---- merge by byte key (imm3_comm_merge_groups_wide; MergeWideArgs in imm3_internal.h) ----
+// Lanes: ONE LANE PER RECORD, a word loop over the key.  A record is 64 .. 560 bytes of its own cache lines, so a lane that walks its
+// record wastes no fetched byte, and the work per record is the probe (a dependent chain of atomics), not the read: a lane group per
+// record would spend cross-lane reductions inside a divergent probe loop to shorten a compare that ends at the first differing word.
+
+// one query's dense groups as records
+__global__ __launch_bounds__(kBlockThreads) void k_mergew_pack(const MergeWideArgs a) {
+    for (uint32_t g = blockIdx.x * kBlockThreads + threadIdx.x; g < a.n_groups; g += gridDim.x * kBlockThreads) {
+        unsigned long long *w = a.rec_out + (size_t)g * a.rec_words;
+        w[0] = a.seg_hi | (unsigned long long)a.q_first[g];
+        w[1] = a.q_counts[g];
+        for (int j = 0; j < kMaxAggs; ++j) w[2 + j] = j < a.n_agg ? (unsigned long long)a.q_vals[(size_t)g * kMaxAggs + j] : 0ULL;
+        if (a.q_key_bytes) {
+            const uint8_t *src = a.q_key_bytes + (size_t)g * a.key_bytes;
+            for (int k = 0; k < a.key_words; ++k) {
+                unsigned long long v = 0;
+                for (int x = 0; x < 8 && 8 * k + x < a.key_bytes; ++x) v |= (unsigned long long)src[8 * k + x] << (8 * x);
+                w[kMergeWideHead + k] = v;
+            }
+        } else if (a.key_words) w[kMergeWideHead] = a.q_keys[g]; // (the u64 key IS its bytes little-endian)
+        for (int j = 0; j < a.n_agg; ++j) {
+            if (!a.str_off[j]) continue;
+            const uint8_t *src = a.q_str[j] + (size_t)g * a.str_width[j];
+            for (int k = 0; k < a.str_words[j]; ++k) {
+                unsigned long long v = 0;
+                for (int x = 0; x < 8 && 8 * k + x < a.str_width[j]; ++x) v |= (unsigned long long)src[8 * k + x] << (8 * x);
+                w[a.str_off[j] + k] = v;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlockThreads) void k_mergew_init(const MergeWideArgs a) {
+    for (uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x; i < a.slots; i += gridDim.x * kBlockThreads) {
+        a.t_claim[i] = kMergeWideEmpty;
+        a.t_counts[i] = 0ULL;
+        a.t_first[i] = ~0ULL;
+        for (int j = 0; j < kMaxAggs; ++j) {
+            const int kind = j < a.n_agg ? a.kinds[j] : AGG_COUNT;
+            a.t_vals[(size_t)j * a.slots + i] = kind == AGG_MIN ? INT64_MAX : ((kind == AGG_SUM || (j < a.n_agg && a.is_str[j])) ? 0 : INT64_MIN);
+            if (j < a.n_agg && a.best_plane[j] >= 0) a.t_best[(size_t)a.best_plane[j] * a.slots + i] = kMergeWideEmpty;
+        }
+    }
+    if (a.out_n && blockIdx.x == 0 && threadIdx.x == 0) *a.out_n = 0ULL;
+}
+
+__device__ __forceinline__ uint32_t mergew_hash(const unsigned long long *key, int words) {
+    unsigned long long h = 0x9E3779B97F4A7C15ULL;
+    for (int k = 0; k < words; ++k) {
+        h = (h ^ key[k]) * 0xD6E8FEB86659FD93ULL;
+        h ^= h >> 32;
+    }
+    return (uint32_t)h;
+}
+// the byte-lexicographic order of two zero-padded strings of `words` words: < 0, 0, > 0
+__device__ __forceinline__ int mergew_strcmp(const unsigned long long *x, const unsigned long long *y, int words) {
+    for (int k = 0; k < words; ++k) {
+        if (x[k] == y[k]) continue;
+        return __builtin_bswap64(x[k]) < __builtin_bswap64(y[k]) ? -1 : 1;
+    }
+    return 0;
+}
+
+__global__ __launch_bounds__(kBlockThreads) void k_mergew_insert(const MergeWideArgs a) {
+    for (uint32_t me = blockIdx.x * kBlockThreads + threadIdx.x; me < a.n_recs; me += gridDim.x * kBlockThreads) {
+        const unsigned long long *w = a.recs + (size_t)me * a.rec_words;
+        if (!w[1]) continue; // padding
+        const unsigned long long *key = w + kMergeWideHead;
+        // the key's slot: the first one from its hash on that this record claims or whose claimant's record carries the same key
+        uint32_t g = mergew_hash(key, a.key_words) & a.mask, slot = kMergeWideEmpty;
+        for (uint32_t probes = 0; probes <= a.mask; ++probes) {
+            const uint32_t prev = atomicCAS(&a.t_claim[g], kMergeWideEmpty, me);
+            if (prev == kMergeWideEmpty || prev == me) { slot = g; break; }
+            const unsigned long long *other = a.recs + (size_t)prev * a.rec_words + kMergeWideHead;
+            bool same = true;
+            for (int k = 0; k < a.key_words && same; ++k) same = other[k] == key[k];
+            if (same) { slot = g; break; }
+            g = (g + 1) & a.mask;
+        }
+        if (slot == kMergeWideEmpty) continue; // (cannot happen: the table holds twice the records)
+        atomicAdd(a.t_counts + slot, w[1]);
+        atomicMin(a.t_first + slot, w[0]);
+        for (int j = 0; j < a.n_agg; ++j) {
+            const long long v = (long long)w[2 + j];
+            long long *t = a.t_vals + (size_t)j * a.slots + slot;
+            if (a.kinds[j] == AGG_MAX) {
+                if (a.is_str[j]) atomicMax((unsigned long long *)t, (unsigned long long)v);
+                else atomicMax(t, v);
+            } else if (a.kinds[j] == AGG_MIN) atomicMin(t, v);
+            else if (a.kinds[j] == AGG_SUM) atomicAdd((unsigned long long *)t, (unsigned long long)v);
+            if (a.best_plane[j] < 0) continue;
+            // wide string MAX: the slot's best record moves to this one while this one's string is greater (equal strings: the lower
+            // index, so the walk is a strict order and ends); both strings are read from records, never from the table
+            uint32_t *b = a.t_best + (size_t)a.best_plane[j] * a.slots + slot;
+            uint32_t cur = __hip_atomic_load(b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (;;) {
+                if (cur != kMergeWideEmpty) {
+                    const int c = mergew_strcmp(w + a.str_off[j], a.recs + (size_t)cur * a.rec_words + a.str_off[j], a.str_words[j]);
+                    if (c < 0 || (c == 0 && cur <= me)) break;
+                }
+                const uint32_t prev = atomicCAS(b, cur, me);
+                if (prev == cur) break;
+                cur = prev;
+            }
+        }
+    }
+}
+
+// the occupied slots as records (order irrelevant: the host sorts by first arrival): numbers from the table, key bytes from the
+// claimant's record, string bytes from the best record
+__global__ __launch_bounds__(kBlockThreads) void k_mergew_collect(const MergeWideArgs a) {
+    const int lane = threadIdx.x & 63;
+    for (uint32_t base = blockIdx.x * kBlockThreads + (threadIdx.x & ~63u); base < a.slots; base += gridDim.x * kBlockThreads) {
+        const uint32_t i = base + (uint32_t)lane;
+        const uint32_t claim = i < a.slots ? a.t_claim[i] : kMergeWideEmpty;
+        const bool occ = claim != kMergeWideEmpty;
+        const uint64_t m = (uint64_t)__ballot(occ);
+        if (!m) continue;
+        unsigned long long start = 0;
+        if (lane == 0) start = atomicAdd(a.out_n, (unsigned long long)__popcll(m));
+        start = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(start >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)start);
+        const unsigned long long o = start + (unsigned long long)__popcll(m & ((1ULL << lane) - 1ULL));
+        if (occ && o < a.out_cap) {
+            unsigned long long *w = a.out_recs + o * (size_t)a.rec_words;
+            const unsigned long long *src = a.recs + (size_t)claim * a.rec_words;
+            w[0] = a.t_first[i];
+            w[1] = a.t_counts[i];
+            for (int j = 0; j < kMaxAggs; ++j) w[2 + j] = (unsigned long long)a.t_vals[(size_t)j * a.slots + i];
+            for (int k = 0; k < a.key_words; ++k) w[kMergeWideHead + k] = src[kMergeWideHead + k];
+            for (int j = 0; j < a.n_agg; ++j) {
+                if (a.best_plane[j] < 0) continue;
+                const uint32_t best = a.t_best[(size_t)a.best_plane[j] * a.slots + i]; // (set by every record that reached the slot: never empty here)
+                const unsigned long long *bs = a.recs + (size_t)(best == kMergeWideEmpty ? claim : best) * a.rec_words;
+                for (int k = 0; k < a.str_words[j]; ++k) w[a.str_off[j] + k] = bs[a.str_off[j] + k];
+            }
+        }
+    }
+}
+
+static int mergew_grid(uint32_t n) { return (int)std::max<uint32_t>(1u, std::min<uint32_t>((n + kBlockThreads - 1) / kBlockThreads, 1024u)); }
+void launch_mergew_pack(const MergeWideArgs &a, hipStream_t s) { hipLaunchKernelGGL(k_mergew_pack, dim3(mergew_grid(a.n_groups)), dim3(kBlockThreads), 0, s, a); }
+void launch_mergew_init(const MergeWideArgs &a, hipStream_t s) { hipLaunchKernelGGL(k_mergew_init, dim3(mergew_grid(a.slots)), dim3(kBlockThreads), 0, s, a); }
+void launch_mergew_insert(const MergeWideArgs &a, hipStream_t s) { hipLaunchKernelGGL(k_mergew_insert, dim3(mergew_grid(a.n_recs)), dim3(kBlockThreads), 0, s, a); }
+void launch_mergew_collect(const MergeWideArgs &a, hipStream_t s) { hipLaunchKernelGGL(k_mergew_collect, dim3(mergew_grid(a.slots)), dim3(kBlockThreads), 0, s, a); }
+
 void launch_group_collect(const AggArgs &a, hipStream_t s) {
     const int64_t n = (int64_t)a.mask + 2;
     const int grid = (int)std::min<int64_t>((n + kBlockThreads - 1) / kBlockThreads, 2048);

@@ -3038,6 +3038,7 @@ static int settle_groups(imm3_query *q, uint32_t *n_groups) {
 }
 
 int imm3::query_groups(imm3_query *q, uint32_t *n_groups) { return settle_groups(q, n_groups); }
+void imm3::query_agg_args(const imm3_query *q, AggArgs &a) { fill_agg_args(q, a); }
 
 // bytes of the packed group key: the group columns' widths
 static int32_t agg_key_bytes(const imm3_query *q) {

@@ -788,3 +788,373 @@ extern "C" int imm3_comm_merge_groups_all(imm3_comm *const *comms, int32_t n_com
     }
     return IMM3_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The same merge by BYTE key: group keys of 0 .. IMM3_GROUP_KEY_MAX_WIDTH bytes and string maxima of any width
+// (imm3_comm_merge_groups_wide).  Every (query, group) becomes one immutable record (MergeWideArgs, imm3_internal.h); the records go
+// through a device hash table whose slots hold the index of the record that claimed them, the occupied slots come out as records
+// again, and with more than one rank those lists are exchanged with ncclAllGather -- fixed-size slots, sized by an all-reduce(max)
+// of the list lengths -- and go through the same table once more.  The protocol around the collectives is that of
+// imm3_comm_merge_groups: everything that can fail on one rank alone happens before the first collective and travels with the
+// shape vote, so every rank takes the same exit.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+struct WideSpec {
+    int key_bytes = 0, n_agg = 0;
+    int32_t kinds[kMaxAggs] = {0, 0, 0, 0}, is_str[kMaxAggs] = {0, 0, 0, 0};
+    int32_t str_width[kMaxAggs] = {0, 0, 0, 0}; // of every MAX over a STRING column, narrow ones included; 0: another aggregate
+    bool operator==(const WideSpec &o) const {
+        if (key_bytes != o.key_bytes || n_agg != o.n_agg) return false;
+        for (int j = 0; j < kMaxAggs; ++j)
+            if (kinds[j] != o.kinds[j] || is_str[j] != o.is_str[j] || str_width[j] != o.str_width[j]) return false;
+        return true;
+    }
+    // what the ranks vote on: {key width, aggregates, their kinds, which are strings}, {the string widths}
+    unsigned long long vote(int word) const {
+        unsigned long long v = 0;
+        if (word == 0) {
+            v = (unsigned long long)key_bytes | (unsigned long long)n_agg << 16;
+            for (int j = 0; j < kMaxAggs; ++j) v |= (unsigned long long)(kinds[j] & 3) << (24 + 2 * j) | (unsigned long long)(is_str[j] & 1) << (32 + j);
+        } else
+            for (int j = 0; j < kMaxAggs; ++j) v |= (unsigned long long)str_width[j] << (16 * j);
+        return v;
+    }
+};
+
+WideSpec wide_spec_of(const imm3_query *q) {
+    WideSpec sp;
+    for (int32_t g : q->group_cols) sp.key_bytes += q->seg->cols[(size_t)q->used[(size_t)g]].width;
+    sp.n_agg = (int)q->aggs.size();
+    for (int j = 0; j < sp.n_agg; ++j) {
+        const SegCol &sc = q->seg->cols[(size_t)q->used[(size_t)q->aggs[(size_t)j].column]];
+        sp.kinds[j] = q->aggs[(size_t)j].kind;
+        sp.is_str[j] = sc.vcodec == IMM3_DENSE_STRING;
+        if (sp.kinds[j] == AGG_MAX && sp.is_str[j]) sp.str_width[j] = sc.width;
+    }
+    return sp;
+}
+
+// the record geometry of a spec (the table and list pointers stay null)
+MergeWideArgs wide_geometry(const WideSpec &sp) {
+    MergeWideArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.key_bytes = sp.key_bytes;
+    a.key_words = (sp.key_bytes + 7) / 8;
+    a.n_agg = sp.n_agg;
+    int off = kMergeWideHead + a.key_words, planes = 0;
+    for (int j = 0; j < kMaxAggs; ++j) {
+        a.kinds[j] = sp.kinds[j];
+        a.is_str[j] = sp.is_str[j];
+        a.best_plane[j] = -1;
+        if (sp.str_width[j] > 8) {
+            a.str_off[j] = off;
+            a.str_words[j] = (sp.str_width[j] + 7) / 8;
+            a.str_width[j] = sp.str_width[j];
+            a.best_plane[j] = planes++;
+            off += a.str_words[j];
+        }
+    }
+    a.rec_words = off;
+    return a;
+}
+int wide_planes(const MergeWideArgs &a) {
+    int n = 0;
+    for (int j = 0; j < kMaxAggs; ++j) n += a.best_plane[j] >= 0;
+    return n;
+}
+
+// one allocation: {counts, first, vals[kMaxAggs]} x slots, the collected list and its counter, then the 32-bit planes {claim, best ...}
+size_t wide_table_bytes(const MergeWideArgs &geo, unsigned long long slots, unsigned long long list_cap) {
+    return (size_t)((slots * (2 + kMaxAggs) + list_cap * (unsigned long long)geo.rec_words + 8) * sizeof(unsigned long long) +
+                    slots * (unsigned long long)(1 + wide_planes(geo)) * sizeof(uint32_t));
+}
+void wide_bind(MergeWideArgs &a, void *p, unsigned long long slots, unsigned long long list_cap) {
+    a.slots = (uint32_t)slots;
+    a.mask = (uint32_t)(slots - 1);
+    unsigned long long *w = (unsigned long long *)p;
+    a.t_counts = w;
+    a.t_first = a.t_counts + slots;
+    a.t_vals = (long long *)(a.t_first + slots);
+    a.out_recs = (unsigned long long *)(a.t_vals + (size_t)kMaxAggs * slots);
+    a.out_n = a.out_recs + list_cap * (unsigned long long)a.rec_words;
+    a.out_cap = (uint32_t)list_cap;
+    a.t_claim = (uint32_t *)(a.out_n + 8);
+    a.t_best = a.t_claim + slots;
+}
+
+void combine_wide(unsigned long long *into, const unsigned long long *g, const MergeWideArgs &geo) {
+    into[0] = std::min(into[0], g[0]);
+    into[1] += g[1];
+    for (int j = 0; j < geo.n_agg; ++j) {
+        unsigned long long &t = into[2 + j];
+        const unsigned long long v = g[2 + j];
+        if (geo.kinds[j] == AGG_MAX) t = geo.is_str[j] ? std::max(t, v) : (unsigned long long)std::max((long long)t, (long long)v);
+        else if (geo.kinds[j] == AGG_MIN) t = (unsigned long long)std::min((long long)t, (long long)v);
+        else if (geo.kinds[j] == AGG_SUM) t += v;
+        if (geo.str_off[j] && std::memcmp(g + geo.str_off[j], into + geo.str_off[j], (size_t)geo.str_width[j]) > 0)
+            std::memcpy(into + geo.str_off[j], g + geo.str_off[j], (size_t)geo.str_words[j] * sizeof(unsigned long long));
+    }
+}
+
+// records (any order) -> the caller's arrays, ascending first arrival
+void unpack_wide(const std::vector<unsigned long long> &recs, const WideSpec &sp, const MergeWideArgs &geo, uint8_t *key_bytes_out, uint64_t *first,
+                 uint64_t *counts, int64_t *vals, uint8_t *const *str_out, uint32_t max_groups, uint32_t *n_groups) {
+    const size_t R = (size_t)geo.rec_words, n = recs.size() / R;
+    std::vector<const unsigned long long *> order(n);
+    for (size_t i = 0; i < n; ++i) order[i] = recs.data() + i * R;
+    std::sort(order.begin(), order.end(), [](const unsigned long long *x, const unsigned long long *y) { return x[0] < y[0]; }); // first arrival first
+    *n_groups = (uint32_t)n;
+    for (size_t o = 0; o < n && o < max_groups; ++o) {
+        const unsigned long long *w = order[o];
+        if (key_bytes_out && sp.key_bytes) std::memcpy(key_bytes_out + o * (size_t)sp.key_bytes, w + kMergeWideHead, (size_t)sp.key_bytes);
+        if (first) first[o] = w[0];
+        if (counts) counts[o] = w[1];
+        for (int j = 0; j < sp.n_agg; ++j) {
+            if (vals) vals[o * (size_t)sp.n_agg + (size_t)j] = sp.kinds[j] == AGG_COUNT ? (int64_t)w[1] : (int64_t)w[2 + j];
+            if (!str_out || !str_out[j]) continue;
+            const size_t wd = (size_t)sp.str_width[j];
+            uint8_t *dst = str_out[j] + o * wd;
+            if (geo.str_off[j]) std::memcpy(dst, w + geo.str_off[j], wd);
+            else // (<= 8 bytes: the value packed big-endian)
+                for (size_t b = 0; b < wd; ++b) dst[b] = (uint8_t)(w[2 + j] >> (8 * (wd - 1 - b)));
+        }
+    }
+}
+
+// The merged records of this communicator's ranks (every rank gets all of them), in no particular order.
+int merge_wide_records(imm3_comm *c, imm3_query *const *queries, const int32_t *segment_index, int32_t n_queries, uint8_t *const *str_out,
+                       WideSpec &sp, std::vector<unsigned long long> &out) {
+    imm3_ctx *ctx = c->ctx;
+    imm3::GateScope gate(&ctx->gate);
+    if (ctx->closed) return fail(IMM3_ERR_STATE, "the context of this communicator has been destroyed");
+    if (ctx->capture) return fail(IMM3_ERR_STATE, "a graph capture is open on this context");
+    HIPCHK(hipSetDevice(ctx->device));
+    // ---- everything this rank can get wrong on its own, before the first collective ----
+    int local_rc = IMM3_OK;
+    std::string local_why;
+    auto local_fail = [&](int code, const std::string &msg) {
+        if (local_rc == IMM3_OK) { local_rc = code; local_why = msg; }
+    };
+    {
+        const char *why = "";
+        const int src = same_spec(queries, n_queries, &why);
+        if (src) local_fail(src, why);
+        else if (n_queries == 0) local_fail(IMM3_ERR_ARG, "a rank joins the merge with at least one aggregation query (the aggregates' kinds come from it)");
+    }
+    std::vector<uint32_t> n_local((size_t)std::max(n_queries, 0), 0u);
+    if (local_rc == IMM3_OK) {
+        sp = wide_spec_of(queries[0]);
+        for (int32_t i = 1; i < n_queries && local_rc == IMM3_OK; ++i) {
+            const WideSpec si = wide_spec_of(queries[i]);
+            if (si.key_bytes != sp.key_bytes) local_fail(IMM3_ERR_ARG, "the queries' group keys differ in width");
+            else if (!(si == sp)) local_fail(IMM3_ERR_ARG, "the queries aggregate differently (kinds, or the widths of their string MAX columns)");
+        }
+        for (int j = 0; j < kMaxAggs && local_rc == IMM3_OK && str_out; ++j)
+            if (j < sp.n_agg && str_out[j] && !sp.str_width[j]) local_fail(IMM3_ERR_ARG, "str_out[" + std::to_string(j) + "] is set, but that aggregate is not a MAX over a STRING column");
+        for (int32_t i = 0; i < n_queries && local_rc == IMM3_OK; ++i) {
+            if (queries[i]->ctx != ctx) { local_fail(IMM3_ERR_ARG, "the query runs on another context than the communicator"); break; }
+            const int grc = query_groups(queries[i], &n_local[(size_t)i]);
+            if (grc) local_fail(grc, imm3_last_error());
+        }
+    }
+    constexpr unsigned long long kMaxMergeEntries = 1ULL << 30; // (the table's slot fields and record indices are 32 bits; 0xFFFFFFFF is the empty marker)
+    unsigned long long total_local = 0;
+    uint32_t most_local = 0;
+    for (int32_t i = 0; i < n_queries; ++i) { total_local += n_local[(size_t)i]; most_local = std::max(most_local, n_local[(size_t)i]); }
+    if (local_rc == IMM3_OK && total_local > kMaxMergeEntries) local_fail(IMM3_ERR_ARG, "too many groups to merge");
+    hipStream_t s = ctx->stream;
+    if (c->world > 1) {
+        const int rrc = rccl_ready();
+        if (rrc) return rrc; // (no RCCL in this process: no rank of this process can be inside the collective either)
+        if (c->in_flight) HIPCHK(hipStreamWaitEvent(s, c->ev_done, 0));
+        unsigned long long shape[5] = {sp.vote(0), sp.vote(1), ~sp.vote(0), ~sp.vote(1), local_rc == IMM3_OK ? 0ULL : 1ULL};
+        if (local_rc != IMM3_OK) shape[0] = shape[1] = shape[2] = shape[3] = 0ULL; // (a failed rank does not vote on the shape)
+        HIPCHK(hipMemcpyAsync(c->d_slot, shape, sizeof(shape), hipMemcpyHostToDevice, s));
+        NCCLCHK(g_rccl.AllReduce(c->d_slot, c->d_slot, 5, ncclUint64, ncclMax, c->nccl, s));
+        HIPCHK(hipMemcpyAsync(shape, c->d_slot, sizeof(shape), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (local_rc != IMM3_OK) return fail(local_rc, local_why);
+        if (shape[4]) return fail(IMM3_ERR_STATE, "another rank failed before the merge (its call says why); no rank has merged anything");
+        if (shape[0] != ~shape[2] || shape[1] != ~shape[3]) // (max != min: every rank sees it and leaves here)
+            return fail(IMM3_ERR_ARG, "the ranks' aggregation queries differ in key width, aggregates or string MAX widths");
+    } else if (local_rc != IMM3_OK) return fail(local_rc, local_why);
+    const MergeWideArgs geo = wide_geometry(sp);
+    const size_t R = (size_t)geo.rec_words;
+    auto pow2_at_least = [](unsigned long long v) { unsigned long long p = 1024; while (p < v) p <<= 1; return p; };
+    auto round8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
+    // ---- this rank's records and their merge: {records, key bytes of one query, string bytes of one query per wide MAX, table} ----
+    const unsigned long long n1 = std::max<unsigned long long>(total_local, 1), slots1 = pow2_at_least(2 * n1);
+    const size_t rec_bytes = (size_t)n1 * R * sizeof(unsigned long long);
+    const size_t keyb_bytes = sp.key_bytes > 8 ? round8((size_t)most_local * (size_t)sp.key_bytes) : 0;
+    size_t strb_bytes[kMaxAggs], tmp_bytes = keyb_bytes;
+    for (int j = 0; j < kMaxAggs; ++j) { strb_bytes[j] = geo.str_off[j] ? round8((size_t)most_local * (size_t)geo.str_width[j]) : 0; tmp_bytes += strb_bytes[j]; }
+    void *p1 = nullptr;
+    {
+        const hipError_t e = hipMalloc(&p1, rec_bytes + tmp_bytes + wide_table_bytes(geo, slots1, n1));
+        if (e != hipSuccess) { (void)hipGetLastError(); p1 = nullptr; }
+    }
+    std::unique_ptr<void, void (*)(void *)> g1(p1, [](void *q) { (void)hipFree(q); });
+    std::string p1_why = "hipMalloc of the merge table failed";
+    unsigned long long mine = 0;
+    MergeWideArgs a1 = geo;
+    if (p1) {
+        // device work of THIS rank between two collectives: a failure clears p1 instead of returning (the rank then says ~0 in the
+        // list-length all-reduce and every rank leaves together)
+        auto local_step = [&](hipError_t e, const char *what) {
+            if (e == hipSuccess || !p1) return;
+            (void)hipGetLastError();
+            p1_why = std::string(what) + ": " + hipGetErrorString(e);
+            p1 = nullptr;
+        };
+        unsigned long long *d_recs = (unsigned long long *)p1;
+        uint8_t *d_tmp = (uint8_t *)p1 + rec_bytes;
+        uint8_t *d_keyb = d_tmp, *d_strb[kMaxAggs];
+        d_tmp += keyb_bytes;
+        for (int j = 0; j < kMaxAggs; ++j) { d_strb[j] = d_tmp; d_tmp += strb_bytes[j]; }
+        wide_bind(a1, d_tmp, slots1, n1);
+        launch_mergew_init(a1, s);
+        local_step(hipGetLastError(), "merge table init");
+        size_t at = 0;
+        for (int32_t i = 0; i < n_queries && p1; ++i) {
+            imm3_query *q = queries[i];
+            const uint32_t ng = n_local[(size_t)i];
+            if (!ng) continue;
+            AggArgs qa;
+            query_agg_args(q, qa);
+            a1.q_keys = q->d_okeys;
+            a1.q_key_bytes = nullptr;
+            if (sp.key_bytes > 8) { // (the table holds tags: the bytes are read at each group's first row)
+                launch_group_keys(qa, ng, sp.key_bytes, d_keyb, s);
+                a1.q_key_bytes = d_keyb;
+            }
+            for (int j = 0; j < kMaxAggs; ++j) {
+                a1.q_str[j] = nullptr;
+                if (!geo.str_off[j]) continue;
+                launch_strmax_collect(qa, j, ng, d_strb[j], s);
+                a1.q_str[j] = d_strb[j];
+            }
+            a1.q_first = q->d_ofirst;
+            a1.q_counts = q->d_ocounts;
+            a1.q_vals = q->d_ovals;
+            a1.n_groups = ng;
+            a1.seg_hi = (unsigned long long)(uint32_t)segment_index[i] << 32;
+            a1.rec_out = d_recs + at * R;
+            launch_mergew_pack(a1, s); // (the next query's gathers overwrite d_keyb / d_strb behind this launch: same stream)
+            local_step(hipGetLastError(), "merge pack");
+            at += ng;
+        }
+        if (p1) {
+            a1.recs = d_recs;
+            a1.n_recs = (uint32_t)total_local;
+            if (total_local) launch_mergew_insert(a1, s);
+            launch_mergew_collect(a1, s);
+            local_step(hipGetLastError(), "merge insert / collect");
+        }
+        if (p1) local_step(hipMemcpyAsync(&mine, a1.out_n, sizeof(mine), hipMemcpyDeviceToHost, s), "merge list length");
+        if (p1) local_step(hipStreamSynchronize(s), "merge list length");
+    }
+    auto take_list = [&](const unsigned long long *d_list, unsigned long long n) -> int {
+        out.assign((size_t)n * R, 0ULL);
+        if (n) HIPCHK(hipMemcpyAsync(out.data(), d_list, out.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return IMM3_OK;
+    };
+    if (c->world == 1) {
+        if (!p1) return fail(IMM3_ERR_DEVICE, p1_why);
+        return take_list(a1.out_recs, mine);
+    }
+    // list lengths -> the common slot count (a rank whose table could not be built says so with ~0: every rank leaves)
+    unsigned long long word = p1 ? mine : ~0ULL, most = 0;
+    HIPCHK(hipMemcpyAsync(c->d_slot, &word, sizeof(word), hipMemcpyHostToDevice, s));
+    NCCLCHK(g_rccl.AllReduce(c->d_slot, c->d_slot, 1, ncclUint64, ncclMax, c->nccl, s));
+    HIPCHK(hipMemcpyAsync(&most, c->d_slot, sizeof(most), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (most == ~0ULL) return fail(IMM3_ERR_DEVICE, p1 ? std::string("a rank could not build its merge table; no rank has merged anything") : p1_why + "; no rank has merged anything");
+    out.clear();
+    const size_t per_rank = (size_t)most * R;
+    if (!per_rank) return IMM3_OK;
+    const unsigned long long entries = most * (unsigned long long)c->world;
+    if (entries > kMaxMergeEntries) return fail(IMM3_ERR_ARG, "too many groups to merge"); // (the same figure on every rank: every rank leaves here)
+    const unsigned long long slots2 = pow2_at_least(2 * entries);
+    void *p = nullptr;
+    // (sizes are the same on every rank: an allocation failure here is reported through one more flag exchange)
+    hipError_t e = hipMalloc(&p, (per_rank + per_rank * (size_t)c->world) * sizeof(unsigned long long) + wide_table_bytes(geo, slots2, entries));
+    if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
+    std::unique_ptr<void, void (*)(void *)> guard(p, [](void *q) { (void)hipFree(q); });
+    unsigned long long ok = p ? 0ULL : 1ULL, any = 0;
+    HIPCHK(hipMemcpyAsync(c->d_slot, &ok, sizeof(ok), hipMemcpyHostToDevice, s));
+    NCCLCHK(g_rccl.AllReduce(c->d_slot, c->d_slot, 1, ncclUint64, ncclMax, c->nccl, s));
+    HIPCHK(hipMemcpyAsync(&any, c->d_slot, sizeof(any), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (any) return fail(IMM3_ERR_DEVICE, "a rank could not allocate the exchange buffers of the merge; no rank has merged anything");
+    unsigned long long *d_send = (unsigned long long *)p, *d_recv = d_send + per_rank;
+    HIPCHK(hipMemsetAsync(d_send, 0, per_rank * sizeof(unsigned long long), s)); // (padding records: count 0)
+    if (mine) HIPCHK(hipMemcpyAsync(d_send, a1.out_recs, (size_t)mine * R * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    NCCLCHK(g_rccl.AllGather(d_send, d_recv, per_rank, ncclUint64, c->nccl, s));
+    MergeWideArgs a2 = geo;
+    wide_bind(a2, d_recv + per_rank * (size_t)c->world, slots2, entries);
+    launch_mergew_init(a2, s);
+    HIPCHK(hipGetLastError());
+    a2.recs = d_recv;
+    a2.n_recs = (uint32_t)entries;
+    launch_mergew_insert(a2, s);
+    HIPCHK(hipGetLastError());
+    launch_mergew_collect(a2, s);
+    HIPCHK(hipGetLastError());
+    unsigned long long n2 = 0;
+    HIPCHK(hipMemcpyAsync(&n2, a2.out_n, sizeof(n2), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return take_list(a2.out_recs, n2);
+}
+
+} // namespace
+
+extern "C" int imm3_comm_merge_groups_wide(imm3_comm *c, imm3_query *const *queries, const int32_t *segment_index, int32_t n_queries,
+                                           uint8_t *key_bytes_out, uint64_t *first, uint64_t *counts, int64_t *vals,
+                                           uint8_t *const *str_out, uint32_t max_groups, uint32_t *n_groups) {
+    if (!c || !n_groups || n_queries < 0 || (n_queries > 0 && (!queries || !segment_index))) return fail(IMM3_ERR_ARG, "bad argument");
+    WideSpec sp;
+    std::vector<unsigned long long> recs;
+    const int rc = merge_wide_records(c, queries, segment_index, n_queries, str_out, sp, recs);
+    if (rc) return rc;
+    unpack_wide(recs, sp, wide_geometry(sp), key_bytes_out, first, counts, vals, str_out, max_groups, n_groups);
+    return IMM3_OK;
+}
+
+// Single-process flavour (comms from imm3_comm_create_all): per device the world-of-one merge above, then one merge by byte key on
+// the host.
+extern "C" int imm3_comm_merge_groups_wide_all(imm3_comm *const *comms, int32_t n_comms, imm3_query *const *const *queries,
+                                               const int32_t *const *segment_index, const int32_t *n_queries,
+                                               uint8_t *key_bytes_out, uint64_t *first, uint64_t *counts, int64_t *vals,
+                                               uint8_t *const *str_out, uint32_t max_groups, uint32_t *n_groups) {
+    if (!comms || n_comms < 1 || !queries || !segment_index || !n_queries || !n_groups) return fail(IMM3_ERR_ARG, "bad argument");
+    bool have = false;
+    WideSpec sp;
+    MergeWideArgs geo = wide_geometry(sp);
+    std::map<std::string, std::vector<unsigned long long>> all;
+    for (int32_t i = 0; i < n_comms; ++i) {
+        if (!comms[i] || n_queries[i] < 0 || (n_queries[i] > 0 && (!queries[i] || !segment_index[i]))) return fail(IMM3_ERR_ARG, "bad argument");
+        if (n_queries[i] == 0) continue;
+        imm3_comm one = *comms[i]; // the same communicator seen as a world of one: its device's queries merged without a collective
+        one.world = 1;
+        WideSpec si;
+        std::vector<unsigned long long> recs;
+        const int rc = merge_wide_records(&one, queries[i], segment_index[i], n_queries[i], str_out, si, recs);
+        if (rc) return rc;
+        if (!have) { sp = si; geo = wide_geometry(sp); have = true; }
+        else if (!(si == sp)) return fail(IMM3_ERR_ARG, "the devices' aggregation queries differ in key width, aggregates or string MAX widths");
+        const size_t R = (size_t)geo.rec_words;
+        for (size_t g = 0; g < recs.size() / R; ++g) {
+            const unsigned long long *w = recs.data() + g * R;
+            std::string key((const char *)(w + kMergeWideHead), (size_t)sp.key_bytes);
+            auto it = all.find(key);
+            if (it == all.end()) all.emplace(std::move(key), std::vector<unsigned long long>(w, w + R));
+            else combine_wide(it->second.data(), w, geo);
+        }
+    }
+    std::vector<unsigned long long> merged;
+    for (auto &kv : all) merged.insert(merged.end(), kv.second.begin(), kv.second.end());
+    unpack_wide(merged, sp, geo, key_bytes_out, first, counts, vals, str_out, max_groups, n_groups);
+    return IMM3_OK;
+}

@@ -370,4 +370,5 @@ void ctx_retain(imm3_ctx *c);
 void ctx_release(imm3_ctx *c);
 int join_query_count(imm3_query *q); // settle the query's count word for device-side consumers on the context's stream (enqueued, no host wait)
 int query_groups(imm3_query *q, uint32_t *n_groups);  // the aggregation's dense group list is complete in q->d_o* (synchronises)
+void query_agg_args(const imm3_query *q, AggArgs &a); // the kernels' view of an aggregation query (launch_group_keys / launch_strmax_collect behind query_groups)
 }

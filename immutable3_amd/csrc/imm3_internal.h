@@ -532,6 +532,53 @@ void launch_merge_init(const MergeArgs &a, hipStream_t s);
 void launch_merge_scatter(const MergeArgs &a, hipStream_t s);
 void launch_merge_insert_list(const MergeArgs &a, hipStream_t s);
 void launch_merge_collect_list(const MergeArgs &a, hipStream_t s);
+// ---- the merge by BYTE key (imm3_comm_merge_groups_wide): group keys of 0 .. kGroupKeyMaxWidth bytes, string maxima of any width ----
+// One fixed-stride RECORD of u64 words per (query, group), written once by k_mergew_pack and never changed:
+//   [0] segment << 32 | first row   [1] count (0 = padding)   [2 .. 2 + kMaxAggs) values
+//   [kMergeWideHead .. + key_words) the key bytes, zero-padded to 8   then, per string MAX wider than 8 bytes, its bytes zero-padded to 8
+// The records are the hash table's input, the ncclAllGather payload and the collect kernel's output.  A table slot holds the INDEX
+// of the record that claimed it (32-bit compare-and-swap from kMergeWideEmpty, which no index can be: entries <= 2^30); a later
+// arrival compares its key with the claimant's record -- immutable input, so there is no half-published key to read and no key value
+// is reserved.  Per wide string MAX a slot holds the index of the record with the greatest string so far (compare-and-swap loop).
+constexpr int kMergeWideHead = 2 + kMaxAggs;
+constexpr uint32_t kMergeWideEmpty = 0xFFFFFFFFu;
+struct MergeWideArgs {
+    int32_t rec_words, key_words, key_bytes, n_agg;
+    int32_t kinds[kMaxAggs];           // AggKind
+    int32_t is_str[kMaxAggs];          // MAX over strings: values[j] compares unsigned (the first <= 8 bytes packed big-endian)
+    int32_t str_off[kMaxAggs];         // word offset of aggregate j's wide string in the record, 0: none
+    int32_t str_words[kMaxAggs];       // its words
+    int32_t str_width[kMaxAggs];       // its bytes
+    int32_t best_plane[kMaxAggs];      // which plane of t_best is aggregate j's, -1: none
+    // k_mergew_pack: one query's dense groups (k_group_collect's output) -> n_groups records at rec_out
+    const unsigned long long *q_keys;  // the u64 keys (a key of <= 8 bytes; else q_key_bytes)
+    const uint8_t *q_key_bytes;        // launch_group_keys' output, key_bytes per group (a key wider than 8 bytes)
+    const uint32_t *q_first;
+    const unsigned long long *q_counts;
+    const long long *q_vals;           // kMaxAggs per group
+    const uint8_t *q_str[kMaxAggs];    // launch_strmax_collect's output, str_width[j] per group (wide string maxima)
+    uint32_t n_groups;
+    unsigned long long seg_hi;         // the query's segment index << 32
+    unsigned long long *rec_out;
+    // the table: slots = mask + 1, a power of two >= 2 x the records that can arrive
+    uint32_t *t_claim;                 // [slots] record index of the slot's key, kMergeWideEmpty = free
+    unsigned long long *t_counts;      // [slots]
+    unsigned long long *t_first;       // [slots]
+    long long *t_vals;                 // [kMaxAggs][slots]
+    uint32_t *t_best;                  // [planes][slots] record index of the greatest wide string so far, kMergeWideEmpty = none
+    uint32_t slots, mask;
+    // k_mergew_insert: n_recs records at recs (count 0: padding of the all-gather slots, skipped)
+    const unsigned long long *recs;
+    uint32_t n_recs;
+    // k_mergew_collect: the occupied slots as records, in no particular order, and how many (starts at 0)
+    unsigned long long *out_recs;
+    unsigned long long *out_n;
+    uint32_t out_cap;
+};
+void launch_mergew_pack(const MergeWideArgs &a, hipStream_t s);
+void launch_mergew_init(const MergeWideArgs &a, hipStream_t s);
+void launch_mergew_insert(const MergeWideArgs &a, hipStream_t s);
+void launch_mergew_collect(const MergeWideArgs &a, hipStream_t s);
 void launch_group_collect(const AggArgs &a, hipStream_t s);
 // string MAX wider than 8 bytes (AggCol::chunks / alive): zero every such aggregate's alive bitmap and chunk table (before the
 // aggregation launch); refine pass k of aggregate j; the exact values of aggregate j's groups, `width` bytes per dense group

@@ -48,6 +48,7 @@ EXPORTS = [
     "imm3_query_row_count", "imm3_query_fetch_rows", "imm3_query_device_ptr",
     "imm3_comm_unique_id", "imm3_comm_create", "imm3_comm_create_all", "imm3_comm_destroy", "imm3_comm_info",
     "imm3_comm_sync", "imm3_comm_join", "imm3_comm_allreduce_u64", "imm3_comm_allreduce_count", "imm3_comm_allreduce_count_all", "imm3_comm_merge_groups", "imm3_comm_merge_groups_all",
+    "imm3_comm_merge_groups_wide", "imm3_comm_merge_groups_wide_all",
     "imm3_pfor_encode_bound", "imm3_pfor_encode_block", "imm3_pfor_encode_column",
     "imm3_snappy_encode_bound", "imm3_snappy_encode_block",
 ]
@@ -205,6 +206,8 @@ def load() -> C.CDLL:
     L.imm3_comm_allreduce_count_all.argtypes = [P(vp), i32, P(P(vp)), P(i32), P(u64)]
     L.imm3_comm_merge_groups.argtypes = [vp, P(vp), vp, i32, vp, vp, vp, vp, C.c_uint32, P(C.c_uint32)]
     L.imm3_comm_merge_groups_all.argtypes = [P(vp), i32, P(P(vp)), P(vp), P(i32), vp, vp, vp, vp, C.c_uint32, P(C.c_uint32)]
+    L.imm3_comm_merge_groups_wide.argtypes = [vp, P(vp), vp, i32, vp, vp, vp, vp, P(vp), C.c_uint32, P(C.c_uint32)]
+    L.imm3_comm_merge_groups_wide_all.argtypes = [P(vp), i32, P(P(vp)), P(vp), P(i32), vp, vp, vp, vp, P(vp), C.c_uint32, P(C.c_uint32)]
     for name in EXPORTS + DIAG_EXPORTS:
         fn = getattr(L, name)
         if name not in ("imm3_last_error", "imm3_pfor_encode_bound", "imm3_snappy_encode_bound"):
@@ -870,6 +873,57 @@ class Comm:
         vals = np.zeros((max(m, 1), na), np.int64)
         _check(load().imm3_comm_merge_groups_all(carr, n, qq, ss, nq, keys.ctypes.data, first.ctypes.data, counts.ctypes.data, vals.ctypes.data, m, C.byref(g)))
         return keys[:m], first[:m], counts[:m], vals[:m]
+
+    @staticmethod
+    def _wide_buffers(q0: "DeviceQuery", g: int):
+        """Result buffers of a merge by byte key, sized from imm3_query_agg_shape: (key bytes, first, counts, vals, {j: string bytes},
+        the str_out pointer array)."""
+        na, kb = C.c_int32(0), C.c_int32(0)
+        _check(load().imm3_query_agg_shape(q0._h, None, C.byref(na), C.byref(kb)))
+        n = max(g, 1)
+        keys = np.zeros((n, max(kb.value, 1)), np.uint8)
+        first, counts = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        vals = np.zeros((n, max(na.value, 1)), np.int64)
+        strs = {}
+        for j, (kind, col) in enumerate(q0.aggs or []):
+            if kind == AGG_MAX and q0.seg.codecs[q0.used_cols[col]] in (DENSE_STRING, SNAPPY_STRING):
+                strs[j] = np.zeros((n, q0.seg.widths[q0.used_cols[col]]), np.uint8)
+        ptrs = (C.c_void_p * max(1, na.value))(*[strs[j].ctypes.data if j in strs else None for j in range(na.value)])
+        return keys, first, counts, vals, strs, ptrs, na.value, kb.value
+
+    def merge_groups_wide(self, queries: Sequence["DeviceQuery"], segment_index: Sequence[int], max_groups: Optional[int] = None):
+        """merge_groups by byte key: any key width, string maxima of any width.  (key_bytes uint8[g, key_bytes], first uint64[g] =
+        segment << 32 | row, counts uint64[g], vals int64[g, n_aggs], {j: uint8[g, width]} for every MAX over STRING aggregate j) in
+        first-seen order; every rank gets the whole table.  max_groups: fetch only that many (the total is then the sixth item)."""
+        qs = (C.c_void_p * max(1, len(queries)))(*[q._h for q in queries])
+        seg = np.ascontiguousarray(segment_index, dtype=np.int32)
+        n = C.c_uint32(0)
+        _check(load().imm3_comm_merge_groups_wide(self._h, qs, seg.ctypes.data, len(queries), None, None, None, None, None, 0, C.byref(n)))
+        g = n.value if max_groups is None else min(n.value, max_groups)
+        keys, first, counts, vals, strs, ptrs, na, kb = self._wide_buffers(queries[0], g)
+        _check(load().imm3_comm_merge_groups_wide(self._h, qs, seg.ctypes.data, len(queries), keys.ctypes.data, first.ctypes.data, counts.ctypes.data,
+                                                  vals.ctypes.data, ptrs, g, C.byref(n)))
+        out = (keys[:g, :kb], first[:g], counts[:g], vals[:g, :na], {j: b[:g] for j, b in strs.items()})
+        return out if max_groups is None else out + (n.value,)
+
+    @staticmethod
+    def merge_groups_wide_all(comms: Sequence["Comm"], queries_per_comm: Sequence[Sequence["DeviceQuery"]], segments_per_comm: Sequence[Sequence[int]]):
+        """Single-process flavour of merge_groups_wide: one Comm per device (create_all), each with its queries and their segment indices."""
+        n = len(comms)
+        carr = (C.c_void_p * n)(*[c._h for c in comms])
+        qarrs = [(C.c_void_p * max(1, len(qs)))(*[q._h for q in qs]) for qs in queries_per_comm]
+        qq = (C.POINTER(C.c_void_p) * n)(*[C.cast(a, C.POINTER(C.c_void_p)) for a in qarrs])
+        segs = [np.ascontiguousarray(s, dtype=np.int32) for s in segments_per_comm]
+        ss = (C.c_void_p * n)(*[s.ctypes.data if s.size else None for s in segs])
+        nq = (C.c_int32 * n)(*[len(qs) for qs in queries_per_comm])
+        q0 = next(q for qs in queries_per_comm for q in qs)
+        g = C.c_uint32(0)
+        _check(load().imm3_comm_merge_groups_wide_all(carr, n, qq, ss, nq, None, None, None, None, None, 0, C.byref(g)))
+        m = g.value
+        keys, first, counts, vals, strs, ptrs, na, kb = Comm._wide_buffers(q0, m)
+        _check(load().imm3_comm_merge_groups_wide_all(carr, n, qq, ss, nq, keys.ctypes.data, first.ctypes.data, counts.ctypes.data, vals.ctypes.data,
+                                                      ptrs, m, C.byref(g)))
+        return keys[:m, :kb], first[:m], counts[:m], vals[:m, :na], {j: b[:m] for j, b in strs.items()}
 
     @staticmethod
     def allreduce_count_all(comms: Sequence["Comm"], queries_per_comm: Sequence[Sequence["DeviceQuery"]]) -> int:

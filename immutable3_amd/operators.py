@@ -609,7 +609,8 @@ class ProjectAggOp(Operator):
     def make(aggs, groupBy):           # ProjectAggregate.scala:116-122
         return lambda op: ProjectAggOp(aggs, op, groupBy)
 
-    def iterator(self):
+    def _segment_args(self):
+        """_run's arguments for this operator's own segment"""
         if isinstance(self.op, ScanOp):
             scan, leaves = self.op, []
         else:
@@ -630,36 +631,56 @@ class ProjectAggOp(Operator):
             code, operand = _cond_spec(cond)
             sels.append((colnames.index(col), code, operand))
         seg = scan.sm.device_segment(scan.tableName, scan.segIdx)
-        yield from self._run(seg, scan.cols, scan._used_indices(), sels, t.blockSize, _expr_of(self.op))
+        return seg, scan.cols, scan._used_indices(), sels, t.blockSize, _expr_of(self.op)
 
-    def _run(self, seg, cols, used_idx, sels, block_size, expr=None):
-        """seg: a DeviceSegment or a DeviceTable (then the groups are already merged across segments)."""
+    def iterator(self):
+        yield from self._run(*self._segment_args())
+
+    def _shape(self, cols):
+        """(column names, group column indices, aggregators, group widths, key wider than 8 bytes, indices of the MaxStringAggr
+        over a column wider than 8 bytes) of this operator over the batch columns `cols`"""
         colnames = [c.name for c in cols]
         group_idx = [i for i, n in enumerate(colnames) if n in self.groupBy]
         by_alias = {}
         for a in self.aggs:
             by_alias[a.alias] = a
         aggs = list(by_alias.values())
+        widths = [cols[i].width for i in group_idx]
+        wide_strs = [j for j, a in enumerate(aggs)
+                     if a.kind == native.AGG_MAX and cols[colnames.index(a.col)].columnType == "STRING" and cols[colnames.index(a.col)].width > 8]
+        return colnames, group_idx, aggs, widths, sum(widths) > 8, wide_strs
+
+    def _open(self, seg, cols, used_idx, sels, block_size, expr=None) -> native.DeviceQuery:
+        """The aggregation query over seg, run and left open (the caller fetches or merges its groups, then closes it)."""
+        colnames, group_idx, aggs, _, wide_key, _ = self._shape(list(cols))
+        q = native.DeviceQuery(seg.ctx, seg, used_idx, sels, (), 0, block_size,
+                               group_cols=group_idx, aggs=[(a.kind, colnames.index(a.col)) for a in aggs],
+                               wide_keys=wide_key, expr=expr)   # a key wider than 8 bytes: the _wide entry points, the key bytes from the device
+        q.run()
+        return q
+
+    def _run(self, seg, cols, used_idx, sels, block_size, expr=None):
+        """seg: a DeviceSegment or a DeviceTable (then the groups are already merged across segments)."""
+        _, _, _, _, wide_key, wide_strs = self._shape(list(cols))
+        q = self._open(seg, cols, used_idx, sels, block_size, expr)
+        keys, first, counts, vals = q.fetch_groups()
+        key_bytes = q.fetch_group_keys() if wide_key else None
+        # a MaxStringAggr over a column wider than 8 bytes: vals hold its first 8 bytes, the exact value comes from the device
+        wide = {j: q.fetch_group_strings(j) for j in wide_strs}
+        q.close()
+        yield from self._groups(cols, keys, key_bytes, counts, vals, wide)
+
+    def _groups(self, cols, keys, key_bytes, counts, vals, wide):
+        """(groupKey, {alias: Aggregator}) per group of the fetched (or merged) arrays: keys uint64[g] or, when key_bytes is given,
+        the packed key bytes uint8[g, key width]; wide: {j: uint8[g, width]} for the string maxima wider than 8 bytes."""
+        colnames, group_idx, aggs, widths, _, _ = self._shape(list(cols))
 
         class _S:                             # the per-row decoding below only needs `cols`
             pass
         scan = _S()
         scan.cols = list(cols)
-        widths = [scan.cols[i].width for i in group_idx]
-        wide_key = sum(widths) > 8            # a key wider than 8 bytes: the _wide entry points, the key bytes from the device
-        q = native.DeviceQuery(seg.ctx, seg, used_idx, sels, (), 0, block_size,
-                               group_cols=group_idx, aggs=[(a.kind, colnames.index(a.col)) for a in aggs],
-                               wide_keys=wide_key, expr=expr)
-        q.run()
-        keys, first, counts, vals = q.fetch_groups()
-        key_bytes = q.fetch_group_keys() if wide_key else None
-        # a MaxStringAggr over a column wider than 8 bytes: vals hold its first 8 bytes, the exact value comes from the device
-        wide = {j: q.fetch_group_strings(j) for j, a in enumerate(aggs)
-                if a.kind == native.AGG_MAX and scan.cols[colnames.index(a.col)].columnType == "STRING"
-                and scan.cols[colnames.index(a.col)].width > 8}
-        q.close()
-        for g in range(keys.shape[0]):
-            raw = bytes(key_bytes[g]) if wide_key else int(keys[g]).to_bytes(8, "little")
+        for g in range(counts.shape[0]):
+            raw = bytes(key_bytes[g]) if key_bytes is not None else int(keys[g]).to_bytes(8, "little")
             parts, off = [], 0
             for i, w in zip(group_idx, widths):
                 parts.append(_key_part(scan.cols[i], raw[off: off + w]))
@@ -762,11 +783,14 @@ class Engine:
     reference: one PipelineThread per segment, :176-180); output order across segments is unspecified in
     the reference (queue interleaving, :255) and defined here as ascending segment index."""
 
-    def __init__(self, sm: GpuSegmentManager, honour_and_or: bool = False):
+    def __init__(self, sm: GpuSegmentManager, honour_and_or: bool = False, device_merge: bool = False):
         """honour_and_or: a query whose select tree holds an Or runs it as a disjunction (one table launch when the table takes the
-        tree, else SelectTreeOp per segment) instead of the reference's conjunction.  Off (the default) nothing changes; a tree without Or is the same either way."""
+        tree, else SelectTreeOp per segment) instead of the reference's conjunction.  Off (the default) nothing changes; a tree without Or is the same either way.
+        device_merge: the per-segment branch of execute_agg merges its queries' groups on the GPU (one imm3_comm_merge_groups_wide
+        over a one-rank communicator per context) instead of combining dicts on the host.  Off (the default) nothing changes."""
         self.sm = sm
         self.honour_and_or = honour_and_or
+        self.device_merge = device_merge
 
     def _as_tree(self, query: Query) -> bool:
         return self.honour_and_or and has_or(query.select)
@@ -839,6 +863,8 @@ class Engine:
         leaves = self._select_ops(query)
         mk_scan = ScanOp.mkScanOp(self.sm, query.table)
         mk_agg = resolveProjectOp(query.project, table)
+        if self.device_merge:
+            return self._execute_agg_device_merge(table, used, leaves, mk_scan, mk_agg)
         result = {}
         for segIdx in range(self.sm.getTableSegmentCount(table.name)):
             if not self.sm.owns(table.name, segIdx):
@@ -854,6 +880,47 @@ class Engine:
                     for alias, agg in aggmap.items():
                         cur[alias] = cur[alias].combine(agg) if alias in cur else agg
         return result
+
+    def _execute_agg_device_merge(self, table, used, leaves, mk_scan, mk_agg):
+        """execute_agg's per-segment branch with the combine on the GPU: every owned segment's aggregation query stays open, one
+        merge by byte key brings their groups together (first arrival first: ascending segment, then first row), and the merged
+        arrays are decoded into the same dict the host combine builds."""
+        queries: Dict[int, list] = {}          # by index of the segment's context
+        seg_ids: Dict[int, list] = {}
+        agg_op = None
+        try:
+            for segIdx in range(self.sm.getTableSegmentCount(table.name)):
+                if not self.sm.owns(table.name, segIdx):
+                    continue
+                op = mk_scan(used, segIdx)
+                for leaf in leaves:
+                    op = leaf(op)
+                agg_op = mk_agg(op)
+                ci = segIdx % len(self.sm.ctxs)
+                queries.setdefault(ci, []).append(agg_op._open(*agg_op._segment_args()))
+                seg_ids.setdefault(ci, []).append(segIdx)
+            if agg_op is None:
+                return {}
+            order = sorted(queries)
+            if len(order) == 1:
+                comm = native.Comm(self.sm.ctxs[order[0]], 1, 0, native.comm_unique_id())
+                try:
+                    key_bytes, _, counts, vals, strs = comm.merge_groups_wide(queries[order[0]], seg_ids[order[0]])
+                finally:
+                    comm.close()
+            else:
+                comms = native.Comm.create_all([self.sm.ctxs[ci] for ci in order])
+                try:
+                    key_bytes, _, counts, vals, strs = native.Comm.merge_groups_wide_all(comms, [queries[ci] for ci in order], [seg_ids[ci] for ci in order])
+                finally:
+                    for c in comms:
+                        c.close()
+        finally:
+            for qs in queries.values():
+                for q in qs:
+                    q.close()
+        wide = {j: strs[j] for j in agg_op._shape(list(used))[5]}
+        return dict(agg_op._groups(used, None, key_bytes, counts, vals, wide))
 
     def execute_table_columns(self, query: Query):
         """Project query over the whole table as ONE fused launch: (segment uint32[n], row uint32[n], [column arrays])

@@ -311,7 +311,8 @@ int imm3_query_create_agg(imm3_ctx *ctx, const imm3_segment *seg,
 /* The same with group keys of 0 .. IMM3_GROUP_KEY_MAX_WIDTH bytes (still at most 4 group columns; wider: IMM3_ERR_ARG).  The
  * arguments are those of imm3_query_create_agg / imm3_query_create_table_agg.  A key of <= 8 bytes takes exactly the path of those
  * (validation, plan, kernels, results).  A wider key is compared byte for byte on the device; imm3_query_fetch_groups then gives
- * its first 8 bytes and imm3_query_fetch_group_keys the whole key.  The merges refuse a query with such a key. */
+ * its first 8 bytes and imm3_query_fetch_group_keys the whole key.  The merges refuse a query with such a key; see
+ * imm3_comm_merge_groups_wide. */
 int imm3_query_create_agg_wide(imm3_ctx *ctx, const imm3_segment *seg,
                                const int32_t *used_cols, int32_t n_used,
                                const imm3_select *sels, int32_t n_sels,
@@ -473,7 +474,7 @@ int imm3_comm_allreduce_count_all(imm3_comm *const *comms, int32_t n_comms, imm3
  * the same merge over that rank's queries, no collective.
  *   keys / counts / vals as imm3_query_fetch_groups; first[g] = segment << 32 | first selected row of the group there.
  * A query with a MAX over a STRING column wider than 8 bytes, or with a group key wider than 8 bytes (imm3_query_create_agg_wide), is
- * refused (IMM3_ERR_ARG): such maxima and keys are not merged.
+ * refused (IMM3_ERR_ARG): such maxima and keys are not merged here; see imm3_comm_merge_groups_wide.
  * Synchronous (the merged table is returned to the host). */
 int imm3_comm_merge_groups(imm3_comm *c, imm3_query *const *queries, const int32_t *segment_index, int32_t n_queries,
                            uint64_t *keys, uint64_t *first, uint64_t *counts, int64_t *vals, uint32_t max_groups, uint32_t *n_groups);
@@ -482,6 +483,34 @@ int imm3_comm_merge_groups(imm3_comm *c, imm3_query *const *queries, const int32
 int imm3_comm_merge_groups_all(imm3_comm *const *comms, int32_t n_comms, imm3_query *const *const *queries,
                                const int32_t *const *segment_index, const int32_t *n_queries,
                                uint64_t *keys, uint64_t *first, uint64_t *counts, int64_t *vals, uint32_t max_groups, uint32_t *n_groups);
+
+/* ---- multi-GPU: the group-by merge by BYTE key.  The same merge for any aggregation query that has been run: a group key of
+ * 0 .. IMM3_GROUP_KEY_MAX_WIDTH bytes (narrow or wide entry points), any mix of COUNT / MIN / MAX / SUM, MAX over a STRING column of
+ * 1 .. IMM3_STRING_MAX_WIDTH bytes; queries over a segment and over a table may be mixed.  Every (query, group) becomes one record
+ * on the device, the records are merged in a hash table keyed by the key's bytes, and with more than one rank the ranks' merged
+ * lists are exchanged with ncclAllGather and merged again.
+ *   key_bytes_out[g * key_bytes ..) the whole packed key as imm3_query_fetch_group_keys lays it out (key_bytes from
+ *                                   imm3_query_agg_shape; a key of <= 8 bytes: the u64 key little-endian)
+ *   first[g]                        segment << 32 | first selected row of the group there
+ *   counts[g], vals[g * n_aggs + j] as imm3_query_fetch_groups (a string MAX wider than 8 bytes: its first 8 bytes big-endian)
+ *   str_out                         NULL, or n_aggs pointers: str_out[j] receives `width` bytes per group when aggregate j is a MAX
+ *                                   over a STRING column (any width) and must be NULL for every other aggregate
+ * Any output pointer may be NULL.  *n_groups is the total even when max_groups is smaller; max_groups groups are written, in
+ * ascending `first` (segment, then first row) -- the order of imm3_comm_merge_groups, whose result this equals for queries that one
+ * accepts.  Counts and SUM add, numeric MIN / MAX combine as signed int64, a string MAX is the byte-lexicographic maximum over the
+ * whole width.  IMM3_ERR_ARG: a null query, one that is not an aggregation, queries (of this rank or of different ranks) that differ
+ * in key_bytes, in the number or kind of their aggregates or in the width of a string MAX column, a non-NULL str_out[j] for another
+ * aggregate; IMM3_ERR_STATE: a query that has not been run.  All of these are found before the first collective and reach every
+ * rank: no rank is left waiting.  At most 2^30 groups enter a merge.  Synchronous. */
+int imm3_comm_merge_groups_wide(imm3_comm *c, imm3_query *const *queries, const int32_t *segment_index, int32_t n_queries,
+                                uint8_t *key_bytes_out, uint64_t *first, uint64_t *counts, int64_t *vals,
+                                uint8_t *const *str_out, uint32_t max_groups, uint32_t *n_groups);
+/* Single-process flavour (comms from imm3_comm_create_all), as imm3_comm_merge_groups_all: per device the one-rank merge, then one
+ * merge by byte key inside this process. */
+int imm3_comm_merge_groups_wide_all(imm3_comm *const *comms, int32_t n_comms, imm3_query *const *const *queries,
+                                    const int32_t *const *segment_index, const int32_t *n_queries,
+                                    uint8_t *key_bytes_out, uint64_t *first, uint64_t *counts, int64_t *vals,
+                                    uint8_t *const *str_out, uint32_t max_groups, uint32_t *n_groups);
 
 /* ---- write side of the PFOR_INT codec (host code, no device involved) ----
  * PFORCodecInt.encode (core/codec/PFORCodec.scala:19-31), which SegmentWriter.flush applies to each block of a PFOR_INT
