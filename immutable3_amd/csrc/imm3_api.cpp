@@ -1095,6 +1095,12 @@ static int fold_tree(imm3_query *q, const imm3_select *sels, int32_t n_sels, con
     return IMM3_OK;
 }
 
+// A table has no word-at-a-time kernel: the predicates that would need it are refused when the query is created.
+static const char *const kTableGenericRefusal =
+    "table queries take int32 / int8 predicates, Match on 2-byte string columns with at most 8 IN-list values, and Match on string "
+    "columns whose width is a multiple of 4 (4 .. 256 bytes, any IN-list); still refused: string columns of any other width and "
+    "2-byte string columns with more than 8 values; use per-segment queries";
+
 static void fill_colpred(const imm3_query *q, const FoldedPred &fp, ColPred &cp);
 static int upload_match_blobs(imm3_query *q, std::vector<FoldedPred> &preds);
 
@@ -1328,6 +1334,9 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
     if (nb >= 1 && has_or) { rc = fold_tree(q.get(), sels, n_sels, prog, n_prog); if (rc) return rc; }
     else if (nb >= 1) { rc = fold_selects(q.get(), sels, n_sels); if (rc) return rc; }
     rc = place_compressed(q.get(), nb >= 1, row_cols); if (rc) return rc;
+    if (table) // (a flat select list; a tree's terms are checked by expr_setup)
+        for (const FoldedPred &p : q->preds)
+            if (pred_route(p) == 2 && !p.match.empty()) return fail(IMM3_ERR_ARG, kTableGenericRefusal);
     rc = upload_match_blobs(q.get(), q->preds); if (rc) return rc;
     if (q->is_expr) { rc = expr_setup(q.get()); if (rc) return rc; }
     rc = alloc_buffers(q.get()); if (rc) return rc;
@@ -1634,7 +1643,9 @@ static int run_select(imm3_query *q, unsigned mode) {
     }
     // (planned on every run: the tuning variant may have changed since creation)
     const SelectChain chain = q->is_expr ? SelectChain() : plan_select_chain(q); // (a select tree is ONE launch of its own: no chain)
-    if (q->table && !chain.generic.empty()) return fail(IMM3_ERR_ARG, "table queries support int32 / int8 / 2-byte string predicates (<= 8 IN-list values); use per-segment queries");
+    // (a table has no word-at-a-time kernel.  Creation has refused the predicates that need it; what is left here is the tools'
+    // TV_GENERIC_ONLY tuning variant, which sends every predicate there)
+    if (q->table && !chain.generic.empty()) return fail(IMM3_ERR_ARG, kTableGenericRefusal);
     const int fv = ctx->filter_variant;
     int pass = 0;
     int grid = 1;
@@ -1884,6 +1895,34 @@ static int run_select(imm3_query *q, unsigned mode) {
         {
             LaunchTimer t(ctx, 0);
             launch_filter_pfor(a, grid, s, t.start, t.stop);
+        }
+        HIPCHK(hipGetLastError());
+        ++pass;
+    }
+    // string passes (k_filter_str_rows): one column whose width is a multiple of 4 per launch, a segment or a table's tile table
+    for (const FoldedPred *fp : chain.str_passes) {
+        StrRowsArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.data = col_flat(q->seg->cols[(size_t)fp->seg_col]);
+        a.width = fp->width;
+        a.n_match = (int32_t)fp->match.size();
+        a.values = (const uint32_t *)fp->d_blob;
+        if (!a.values) // (upload_match_blobs: width <= 8 and <= kMaxMatch values)
+            for (size_t m = 0; m < fp->match.size() && m < (size_t)kMaxMatch; ++m) std::memcpy(a.inl[m], fp->match[m].data(), std::min<size_t>((size_t)fp->width, sizeof(a.inl[m])));
+        a.and_existing = pass > 0;
+        a.n_rows = q->n_rows;
+        a.n_words = q->n_words;
+        a.n_tiles = q->n_tiles;
+        a.bitmap = q->d_bitmap;
+        a.block_partials = q->d_block_partials;
+        if (q->table) {
+            a.tile_rows = q->table->d_tile_rows;
+            a.tile_ptrs = (const void *const *)q->table->d_tile_ptrs[(size_t)fp->seg_col];
+        }
+        grid = str_rows_grid(q->n_tiles, ctx->grid_blocks);
+        {
+            LaunchTimer t(ctx, 0);
+            if (!launch_filter_str_rows(a, grid, s, t.start, t.stop)) return fail(IMM3_ERR_ARG, "internal: no string kernel for this column width");
         }
         HIPCHK(hipGetLastError());
         ++pass;

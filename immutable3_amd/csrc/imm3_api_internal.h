@@ -38,6 +38,8 @@ constexpr int kSampleTiles = kSampleChunks * (int)kSampleChunkTiles;
 constexpr int64_t kLimitFirstChunkTiles = 1024;                       // a limit scan's first chunk (the next ones are 8 x, 4 x, 4 x ... larger)
 
 int tile_kind(const FoldedPred &fp);
+bool str_rows_pred(const FoldedPred &fp);
+int pred_route(const FoldedPred &fp);
 int32_t single_pass_run_grid(const imm3_query *q);
 bool single_pass_reserves(const imm3_query *q);
 void single_pass_set_P(imm3_query *q, int32_t P);
@@ -55,10 +57,11 @@ int single_pass_restore(imm3_query *q, uint64_t survivors);
 
 // The select chain's passes as run_select enqueues them, from the query's folded predicates and the tuning variant read NOW: tile passes
 // of up to kMaxTileCols columns (numeric kinds first, at most one 2-byte string each; a query without predicates is one tile pass
-// with zero columns), then one k_filter_pfor pass per fused PFOR_INT predicate, then the word-at-a-time passes.
+// with zero columns), then one k_filter_pfor pass per fused PFOR_INT predicate, then one k_filter_str_rows pass per string predicate
+// on a column whose width is a multiple of 4, then the word-at-a-time passes.
 struct SelectChain {
     std::vector<std::vector<const FoldedPred *>> tile_passes;
-    std::vector<const FoldedPred *> pfor, generic;
+    std::vector<const FoldedPred *> pfor, str_passes, generic;
     bool single_tile_pass = false; // exactly ONE launch in the whole chain: its column order is the records' and the one launch's
 };
 SelectChain plan_select_chain(const imm3_query *q);

@@ -307,6 +307,28 @@ struct FilterArgs {
     const uint8_t *word_nvalid;
 };
 
+// ---- k_filter_str_rows (imm3_strmatch.hip): Match on one string column whose width is a whole number of dwords ----
+// One wave per 1024-row tile, lane l on row 64 j + l; the tile's 16 bitmap words leave as one 128-byte line.
+constexpr int kStrPrefixDwords = 4;  // dwords of a row compared first; the rest only for the rows that pass (widths above 16 bytes)
+struct StrRowsArgs {
+    const void *data;                // flat (decoded) column in HBM, 16-byte aligned
+    int32_t width;                   // bytes per row: a multiple of 4, 4 .. 256
+    int32_t n_match;                 // IN-list size
+    int32_t and_existing;            // 1: AND into the bitmap already in memory
+    int32_t pad;
+    uint32_t inl[kMaxMatch][2];      // values == null (width <= 8 and n_match <= kMaxMatch): the values' dwords, little-endian
+    const uint32_t *values;          // else: n_match * width bytes in device memory (FoldedPred::d_blob)
+    int64_t n_rows, n_words, n_tiles;
+    uint64_t *bitmap;                // allocated in whole tiles
+    uint32_t *block_partials;
+    // table queries: tile t holds tile_rows[t] valid rows starting at tile_ptrs[t] (as TileArgs); null for one segment
+    const uint32_t *tile_rows;
+    const void *const *tile_ptrs;
+};
+bool str_rows_width_ok(int32_t width);            // a multiple of 4 in 4 .. 256
+int str_rows_grid(int64_t n_tiles, int grid_blocks);
+bool launch_filter_str_rows(const StrRowsArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // false: no instance for this width
+
 // ---- select trees (imm3_expr.hip): AND / OR over the leaves, as a disjunction of TERMS ----
 // The host rewrites a tree into terms (imm3_expr_norm.cpp): each term is a conjunction with at most one folded predicate per column --
 // exactly what a flat select list folds to -- and the selection is the OR of the terms.

@@ -58,16 +58,30 @@ int tile_kind(const FoldedPred &fp) {
     return TK_NONE;
 }
 
+// A string predicate k_filter_str_rows takes (imm3_strmatch.hip): a row is a whole number of dwords, 4 .. 256 bytes; any IN-list.
+bool str_rows_pred(const FoldedPred &fp) {
+    return fp.kind == KIND_STR && !fp.pfor && str_rows_width_ok(fp.width) && !fp.match.empty();
+}
+
+// Which kernel a folded predicate goes to on a uniform layout: 0 the tile kernel, 1 k_filter_str_rows, 2 the word-at-a-time kernel
+// (the only one a table does not have).
+int pred_route(const FoldedPred &fp) {
+    if (tile_kind(fp) != TK_NONE) return 0;
+    return str_rows_pred(fp) ? 1 : 2;
+}
+
 SelectChain plan_select_chain(const imm3_query *q) {
-    // Uniform layouts: numeric and 2-byte-string predicates go through the tile kernel; everything else -- other string widths, long
-    // IN-lists, ragged layouts -- through the word-at-a-time kernel, up to 4 columns per launch.  Every pass after the first ANDs
-    // into the bitmap in memory.
+    // Uniform layouts: numeric and 2-byte-string predicates go through the tile kernel, string predicates on columns whose width is
+    // a multiple of 4 through k_filter_str_rows (one column per launch); everything else -- other string widths, long IN-lists on
+    // 2-byte columns, ragged layouts -- through the word-at-a-time kernel, up to 4 columns per launch.  Every pass after the first
+    // ANDs into the bitmap in memory.
     const bool tiles = !q->ragged && q->ctx->filter_variant != TV_GENERIC_ONLY;
     SelectChain c;
     std::vector<const FoldedPred *> tile_preds;
     for (const auto &p : q->preds) {
         if (p.pfor) c.pfor.push_back(&p);
-        else if (tiles && tile_kind(p) != TK_NONE) tile_preds.push_back(&p);
+        else if (tiles && pred_route(p) == 0) tile_preds.push_back(&p);
+        else if (tiles && pred_route(p) == 1) c.str_passes.push_back(&p);
         else c.generic.push_back(&p);
     }
     std::stable_sort(tile_preds.begin(), tile_preds.end(),
@@ -87,7 +101,7 @@ SelectChain plan_select_chain(const imm3_query *q) {
         c.tile_passes.push_back(take);
     }
     if (q->preds.empty() && tiles) c.tile_passes.emplace_back();
-    c.single_tile_pass = c.generic.empty() && c.pfor.empty() && c.tile_passes.size() == 1;
+    c.single_tile_pass = c.generic.empty() && c.pfor.empty() && c.str_passes.empty() && c.tile_passes.size() == 1; // (a string pass: the bitmap path, as with a generic pass)
     return c;
 }
 
@@ -749,4 +763,15 @@ extern "C" int imm3_plan_table_limit(int32_t table, int32_t tree, int64_t limit,
     in.n_tiles = n_tiles;
     in.grid = grid;
     return table_limit_applies(in) ? 1 : 0;
+}
+
+// diagnostics: which kernel a string Match goes to (pred_route; tests/test_str_rows_host.py walks it): 0 the tile kernel (2-byte
+// strings, <= 8 values), 1 k_filter_str_rows (a width that is a multiple of 4), 2 the word-at-a-time kernel (what a table refuses)
+extern "C" int imm3_plan_string_route(int32_t width, int32_t n_match) {
+    if (width < 1 || width > IMM3_STRING_MAX_WIDTH || n_match < 1) return -1;
+    FoldedPred fp;
+    fp.kind = KIND_STR;
+    fp.width = width;
+    fp.match.assign((size_t)n_match, std::string((size_t)width, 'x'));
+    return pred_route(fp);
 }

@@ -733,9 +733,15 @@ class Engine {
             for (size_t k = 0; k < p.used.size(); ++k) if (p.used[k].name == leaves[i].col) { ci = (int32_t)k; break; }
             if (ci < 0) throw Exception("NoSuchElementException: next on empty iterator");
             const Column &c = p.used[(size_t)ci];
-            if (leaves[i].cond.kind == SelectCondition::Match &&
-                (c.columnType != ColumnType::STRING || c.width() != 2 || leaves[i].cond.values.empty() || leaves[i].cond.values.size() > 8))
-                return false; // the tile kernels take 2-byte strings with <= 8 IN-list values
+            if (leaves[i].cond.kind == SelectCondition::Match) {
+                // the tile kernels take 2-byte strings with <= 8 IN-list values; a flat select list also takes any non-empty IN-list
+                // on a string column whose width is a multiple of 4 (k_filter_str_rows); a tree keeps the tile kinds
+                const bool isStr = c.columnType == ColumnType::STRING;
+                const size_t nv = leaves[i].cond.values.size();
+                const bool tile = isStr && c.width() == 2 && nv > 0 && nv <= 8;
+                const bool rows = isStr && !p.tree && c.width() % 4 == 0 && c.width() >= 4 && c.width() <= 256 && nv > 0;
+                if (!tile && !rows) return false;
+            }
             p.sels[i] = imm3_select{};
             p.sels[i].column = ci;
             p.sels[i].cond = (int32_t)leaves[i].cond.kind;

@@ -57,7 +57,7 @@ DIAG_EXPORTS = [
     "imm3_ctx_timing_enable", "imm3_ctx_timing_reset", "imm3_ctx_timing_mask", "imm3_ctx_timing_collect", "imm3_ctx_set_tuning",
     "imm3_ctx_measure_read_gbps", "imm3_ctx_devclock_enable", "imm3_ctx_devclock_collect", "imm3_ctx_devclock_raw", "imm3_query_plan",
     "imm3_ctx_inject_fault", "imm3_ctx_debug_device_lock", "imm3_plan_predict", "imm3_comm_debug_standin", "imm3_plan_limit_scan",
-    "imm3_plan_table_limit",
+    "imm3_plan_table_limit", "imm3_plan_string_route",
     "imm3_query_agg_form", "imm3_query_expr_form", "imm3_expr_normalize",
 ]
 COMM_ID_BYTES = 128
@@ -541,6 +541,14 @@ def plan_table_limit(table=1, tree=0, limit=10, count_in_scan=1, single_tile_pas
     L.imm3_plan_table_limit.argtypes = [C.c_int32, C.c_int32, C.c_int64] + [C.c_int32] * 6 + [C.c_int64, C.c_int32]
     return int(L.imm3_plan_table_limit(table, tree, limit, count_in_scan, single_tile_pass, whole, count_log_on, count_only,
                                        filter_variant, n_tiles, grid))
+
+
+def plan_string_route(width: int, n_match: int = 1) -> int:
+    """include/imm3_diag.h: imm3_plan_string_route -- the kernel a string Match goes to on a uniform layout: 0 the tile kernel,
+    1 k_filter_str_rows, 2 the word-at-a-time kernel (what a table refuses); a pure function, no device needed."""
+    L = load()
+    L.imm3_plan_string_route.argtypes = [C.c_int32, C.c_int32]
+    return int(L.imm3_plan_string_route(width, n_match))
 
 
 def expr_normalize(col_codecs: Sequence[int], col_widths: Sequence[int], leaves: Sequence[tuple], prog: Sequence[int]):

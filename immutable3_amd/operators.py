@@ -833,8 +833,14 @@ class Engine:
                 raise Exception(f"Unsupported condition: {cond}")
             code, operand = _cond_spec(cond)
             col = used[names.index(name)]
-            if code == native.MATCH and (col.codec not in CodecType.STRING_CODECS or col.width != 2 or not (0 < len(operand) <= 8)):
-                return None                      # the tile kernels take 2-byte strings with <= 8 IN-list values
+            if code == native.MATCH:
+                # the tile kernels take 2-byte strings with <= 8 IN-list values; a flat select list also takes any non-empty
+                # IN-list on a string column whose width is a multiple of 4 (k_filter_str_rows); a tree keeps the tile kinds
+                is_str = col.codec in CodecType.STRING_CODECS
+                tile = is_str and col.width == 2 and 0 < len(operand) <= 8
+                rows = is_str and prog is None and col.width % 4 == 0 and 4 <= col.width <= 256 and len(operand) > 0
+                if not (tile or rows):
+                    return None
             sels.append((names.index(name), code, operand))
         tnames = [c.name for c in table.columns]
         return dt, used, [tnames.index(n) for n in names], sels, prog

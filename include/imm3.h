@@ -192,7 +192,13 @@ int imm3_table_destroy(imm3_table *t);
  * imm3_query_fetch_rows give the first `limit` survivors in (segment, row) order; imm3_query_count, imm3_query_bitmap,
  * imm3_query_join_count and a count log give the WHOLE table's figures (the whole select runs first; a logged query never stops);
  * imm3_query_segment_starts and imm3_query_locate_rows are unchanged.  Behind imm3_query_run the device-side bitmap and count
- * (imm3_query_device_ptr 0, 1) cover the scanned prefix only.  A select tree with an IMM3_EXPR_OR scans the whole table. */
+ * (imm3_query_device_ptr 0, 1) cover the scanned prefix only.  A select tree with an IMM3_EXPR_OR scans the whole table.
+ * PREDICATES A TABLE TAKES: GT / LT / EQ on int32 and int8 columns; Match on a 2-byte string column with at most 8 IN-list values
+ * (the tile kernel); Match on a string column whose width is a multiple of 4, 4 .. IMM3_STRING_MAX_WIDTH bytes, with an IN-list of
+ * any length (one more launch per such column over the tile table, ANDed into the bitmap; a query with one takes the bitmap plan:
+ * offsets scan then gather, no stop at a `limit`, an aggregation reads the bitmap).  STILL REFUSED, at creation, with IMM3_ERR_ARG
+ * and a message that says so: Match on a string column of any other width (1, 3, 5, ...) and on a 2-byte column with more than 8
+ * values -- a table has no word-at-a-time kernel; the caller runs per-segment queries. */
 int imm3_query_create_table(imm3_ctx *ctx, const imm3_table *table,
                             const int32_t *used_cols, int32_t n_used,
                             const imm3_select *sels, int32_t n_sels,
@@ -242,8 +248,9 @@ int imm3_query_destroy(imm3_query *q);
  * (same folded predicates, same plan, same kernels).  With one, the library rewrites the tree into a disjunction of TERMS, each
  * a conjunction with at most one interval / IN-list per column (terms that select nothing and duplicates are dropped), and the
  * whole select is ONE launch: up to 8 terms over up to 3 int32 / int8 / 2-byte-string columns (IN-lists of <= 8 values) of a
- * uniform segment through a tile kernel, anything else -- ragged layouts, other string widths, longer IN-lists, more columns,
- * 9 .. 64 terms -- through a row-per-lane kernel; more than 64 terms: IMM3_ERR_ARG.  PFOR_INT / snappy predicate columns are
+ * uniform segment through a tile kernel, anything else -- ragged layouts, other string widths (the dword-multiple widths a flat
+ * select list runs through its string kernel included: a tree keeps the row-per-lane form for them), longer IN-lists, more
+ * columns, 9 .. 64 terms -- through a row-per-lane kernel; more than 64 terms: IMM3_ERR_ARG.  PFOR_INT / snappy predicate columns are
  * read in their decoded form.  The projection goes scan -> offsets scan -> gather (imm3_query_plan reports no one launch and no
  * records; `limit` bounds the rows emitted, the select covers the whole segment); an aggregation reads the bitmap the select
  * launch wrote.  Every run call, getter, imm3_query_log_counts and graph capture works as for any query.
@@ -271,9 +278,9 @@ int imm3_query_create_agg_expr(imm3_ctx *ctx, const imm3_segment *seg,
  * kernels, same results.  With one, the tree is normalised as for a segment and must fit the tile form -- at most 8 terms, at
  * most 3 predicate columns of int32 / int8 / 2-byte string (at most one of them a string), IN-lists of at most 8 values: the
  * select over ALL segments is then ONE launch (imm3_query_expr_form reports the tile form, 0).  A tree that does not fit is
- * refused at creation with IMM3_ERR_ARG and a message that names the bound exceeded -- a table has no row-per-lane kernel, the
- * rule imm3_query_create_table applies to strings of other widths and longer IN-lists -- and the caller runs per-segment tree
- * queries and merges.  Every such refusal's message begins with IMM3_TABLE_TREE_REFUSED (part of the contract): that prefix, not
+ * refused at creation with IMM3_ERR_ARG and a message that names the bound exceeded -- a table has no row-per-lane kernel.  That
+ * includes a tree with an IMM3_EXPR_OR over a string column of 4, 8, ... bytes, which imm3_query_create_table's flat list takes:
+ * a tree's string predicates are 2-byte columns only -- and the caller runs per-segment tree queries and merges.  Every such refusal's message begins with IMM3_TABLE_TREE_REFUSED (part of the contract): that prefix, not
  * the status alone, tells "this tree does not fit a table" from a genuine argument error, which falling back would only repeat.
  * A tree that normalises to no term selects nothing.  PFOR_INT / snappy predicate columns are read in the
  * decoded form the table holds.  The projection takes the table's bitmap plan (offsets scan, then gather: imm3_query_plan reports

@@ -125,6 +125,11 @@ int imm3_plan_limit_scan(int32_t whole, int32_t count_log_on, int32_t count_in_s
  * n_tiles > grid * 32, `grid` being the launch's work-groups. */
 int imm3_plan_table_limit(int32_t table, int32_t tree, int64_t limit, int32_t count_in_scan, int32_t single_tile_pass, int32_t whole, int32_t count_log_on,
                           int32_t count_only, int32_t filter_variant, int64_t n_tiles, int32_t grid);
+/* imm3_plan_string_route: which kernel a Match on a string column of `width` bytes with `n_match` IN-list values goes to on a uniform
+ * layout (csrc/imm3_planner.cpp: pred_route, pure): 0 = the tile kernel (2-byte columns, at most 8 values), 1 = k_filter_str_rows (a
+ * width that is a multiple of 4, 4 .. 256, any IN-list), 2 = the word-at-a-time kernel -- the one an imm3_table does not have, so
+ * 2 is what a table query refuses at creation.  -1: width outside 1 .. IMM3_STRING_MAX_WIDTH or an empty list. */
+int imm3_plan_string_route(int32_t width, int32_t n_match);
 struct imm3_comm;
 int imm3_comm_debug_standin(struct imm3_comm *comm, int32_t work_groups, uint32_t spin_us);
 int imm3_ctx_inject_fault(imm3_ctx *ctx, int32_t work_group, int32_t span, uint32_t max_polls);
