@@ -1,5 +1,7 @@
-// imm3_api.cpp -- the C ABI of include/imm3.h: host-side planning (validation that mirrors the reference's
-// exceptions, predicate folding, batch layout) and launch orchestration of the HIP kernels.
+// imm3_api.cpp -- the C ABI of include/imm3.h but for the run calls: contexts, segments, tables, query creation (validation that
+// mirrors the reference's exceptions, predicate folding, batch layout), the getters and what they settle of the last run, and
+// aggregation.  The run itself -- imm3_query_run / _run_select / _run_count and the launches they enqueue -- is imm3_run.cpp; which
+// plan a projection takes is imm3_planner.cpp.
 // Compiled with hipcc for gfx950.  There is NO CPU fallback: without a HIP device every entry point that
 // touches data fails with IMM3_ERR_DEVICE.
 #include "../../include/imm3.h"
@@ -20,7 +22,7 @@
 #include <vector>
 
 #include "imm3_handles.h"
-#include "imm3_api_internal.h" // (shared with the planner, imm3_planner.cpp: which plan a projection takes, and at what P / grid)
+#include "imm3_api_internal.h" // (shared with the run, imm3_run.cpp, and the planner, imm3_planner.cpp)
 
 using namespace imm3;
 
@@ -33,18 +35,6 @@ int imm3::fail(int code, const std::string &msg) {
     g_err = msg;
     return code;
 }
-
-// Entry into a context (imm3_sync.h): the call passes the context's capture gate -- shared, so calls of any number of
-// threads run side by side; while ANOTHER thread has a graph capture open it waits here until that capture ends.
-// (Declares a scope guard: one use per function scope.)
-#define CTX_LIVE_RUN(c)                                                                           \
-    if (!(c)) return fail(IMM3_ERR_ARG, "ctx is null");                                           \
-    imm3::GateScope imm3_gate_scope_(&(c)->gate);                                                 \
-    if ((c)->closed) return fail(IMM3_ERR_STATE, "the context of this handle has been destroyed")
-// every entry point but the run calls: not while THIS thread's graph capture is open (most of them synchronise or allocate)
-#define CTX_LIVE(c)                                                                               \
-    CTX_LIVE_RUN(c);                                                                              \
-    if ((c)->capture) return fail(IMM3_ERR_STATE, "a graph capture is open on this context: only imm3_query_run / imm3_query_run_select and imm3_ctx_capture_end are accepted")
 
 // ---------------------------------------------------------------------------------------------
 // context-level caching allocator (imm3_sync.h: BlockPool, one per context, thread-safe)
@@ -289,10 +279,6 @@ extern "C" int imm3_ctx_inject_fault(imm3_ctx *ctx, int32_t work_group, int32_t 
     return IMM3_OK;
 }
 
-#ifdef IMM3_ABLATE
-static int single_pass_lock_word(int device, unsigned long long **out);
-#endif
-
 // The device's ticket word of the single-pass kernel (0 = free).  Tests put a foreign ticket there to make every launch find the
 // device busy, deterministically; imm3_project.hip and run_single_pass say what the word is for.
 extern "C" int imm3_ctx_debug_device_lock(imm3_ctx *ctx, uint64_t value, uint64_t *previous) {
@@ -452,24 +438,6 @@ extern "C" int imm3_ctx_timing_collect(imm3_ctx *ctx, int32_t kernel_id, float *
     *n_out = n;
     return IMM3_OK;
 }
-
-namespace {
-// Hands out one event pair per launch when timing is on; the launcher stamps it with the kernel's own
-// start and end (hipExtLaunchKernelGGL), so elapsed time == kernel duration as rocprofv3 reports it.
-struct LaunchTimer {
-    hipEvent_t start = nullptr, stop = nullptr;
-    LaunchTimer(imm3_ctx *ctx, int32_t id) {
-        if (!ctx->timing.load(std::memory_order_relaxed) || ctx->capture || !((ctx->timing_mask.load(std::memory_order_relaxed) >> id) & 1u)) return;
-        std::lock_guard<std::mutex> lk(ctx->mu); // (diagnostics only: the lock is taken when timing is on)
-        if (ctx->used < ctx->pool.size()) {
-            TimingRecord &rec = ctx->pool[ctx->used++];
-            rec.kernel_id = id;
-            start = rec.start;
-            stop = rec.stop;
-        }
-    }
-};
-} // namespace
 
 // ---------------------------------------------------------------------------------------------
 // segment
@@ -888,7 +856,7 @@ static void query_free(imm3_query *q) {
     delete q;
 }
 
-static int ensure_row_capacity(imm3_query *q, uint64_t rows) {
+int imm3::ensure_row_capacity(imm3_query *q, uint64_t rows) {
     if (rows <= q->cap_rows && q->d_row_index) return IMM3_OK;
     if (rows < 1) rows = 1;
     imm3_ctx *ctx = q->ctx;
@@ -1096,12 +1064,11 @@ static int fold_tree(imm3_query *q, const imm3_select *sels, int32_t n_sels, con
 }
 
 // A table has no word-at-a-time kernel: the predicates that would need it are refused when the query is created.
-static const char *const kTableGenericRefusal =
+const char *const imm3::kTableGenericRefusal =
     "table queries take int32 / int8 predicates, Match on 2-byte string columns with at most 8 IN-list values, and Match on string "
     "columns whose width is a multiple of 4 (4 .. 256 bytes, any IN-list); still refused: string columns of any other width and "
     "2-byte string columns with more than 8 values; use per-segment queries";
 
-static void fill_colpred(const imm3_query *q, const FoldedPred &fp, ColPred &cp);
 static int upload_match_blobs(imm3_query *q, std::vector<FoldedPred> &preds);
 
 // Step 5 of a select tree: which kernel form can take the terms, and the generic form's predicates on the device.  (Compressed
@@ -1573,922 +1540,6 @@ extern "C" int imm3_query_reserve_rows(imm3_query *q, uint64_t rows) {
         if (src) return src;
     }
     if (rows < (uint64_t)q->n_rows) single_pass_adapt(q, rows, -1); // (the reservation bounds the survivors)
-    return IMM3_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// execution
-// ---------------------------------------------------------------------------------------------
-static void fill_colpred(const imm3_query *q, const FoldedPred &fp, ColPred &cp) {
-    std::memset(&cp, 0, sizeof(cp));
-    const SegCol &sc = q->seg->cols[(size_t)fp.seg_col];
-    cp.data = col_flat(sc);
-    cp.kind = fp.kind;
-    cp.width = fp.width;
-    cp.lo = (int32_t)fp.lo;
-    cp.hi = (int32_t)fp.hi;
-    cp.n_match = (int32_t)fp.match.size();
-    cp.match_in_args = (fp.kind == KIND_STR && !fp.d_blob) ? 1 : 0;
-    cp.match_blob = fp.d_blob;
-    if (cp.match_in_args) {
-        for (size_t m = 0; m < fp.match.size(); ++m) {
-            uint64_t v = 0;
-            for (int b = 0; b < fp.width; ++b) v |= (uint64_t)(uint8_t)fp.match[m][(size_t)b] << (8 * b);
-            cp.match[m] = v;
-        }
-    }
-}
-
-// join: make `s` wait for this query's count reduce on the aux stream (no-op when it ran on the main stream)
-static int join_total(imm3_query *q, hipStream_t s) {
-    if (q->total_on_aux) HIPCHK(hipStreamWaitEvent(s, q->ev_total_done, 0));
-    return IMM3_OK;
-}
-
-// What a caller of run_select wants, OR-ed together; SEL_DEFAULT: store the bitmap, reduce the count on the main stream.
-enum SelectMode : unsigned {
-    SEL_DEFAULT = 0,
-    SEL_OVERLAP_TOTAL = 1u << 0, // nothing on the main stream needs the count: reduce it on the aux stream (TV_COUNT_ON_AUX)
-    SEL_COUNT_IN_SCAN = 1u << 1, // a projection follows on the same stream; its offsets scan publishes the count (no k_total launch)
-    SEL_COUNT_ONLY = 1u << 2,    // the caller wants selected.size alone -- a chain that is ONE tile launch then stores no bitmap
-    SEL_WHOLE = 1u << 3,         // never in chunks (the getters' full select)
-    SEL_PLAIN = 1u << 4,         // stage no survivor records: the bitmap is what the caller wants (settle_lazy_bitmap)
-};
-// Chunks of a limit scan: they end at tiles 1024, 8192, 32 768, 131 072, ... (x 4) and at the segment's end -- four launches for
-// 100 M rows.  A `limit 10` is usually met in the first megarow: the chunks behind it cost their dispatch only (1 - 4 us each, which
-// is why there are few of them); a limit met at 5 % of the segment stops at 8 %; one met in the second half scans everything, as a
-// whole select would.  Multiples of kChunkTiles (the offsets scan's unit).
-static constexpr int64_t kLimitSecondEndTiles = 8192; // (kLimitFirstChunkTiles: imm3_api_internal.h)
-
-static int run_select(imm3_query *q, unsigned mode) {
-    const bool overlap_total = mode & SEL_OVERLAP_TOTAL, count_in_scan = mode & SEL_COUNT_IN_SCAN, count_only = mode & SEL_COUNT_ONLY;
-    imm3_ctx *ctx = q->ctx;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    {   // the previous run's reduce may still be reading block_partials / writing total on the aux stream
-        const int jrc = join_total(q, s);
-        if (jrc) return jrc;
-        q->total_on_aux = false;
-    }
-    q->run.offsets_valid = false; // (a new bitmap)
-    q->run.select_partial = false;
-    if (q->always_false || q->n_tiles == 0) {
-        // an empty interval / empty IN-list clears every bit; nothing to read
-        HIPCHK(hipMemsetAsync(q->d_total, 0, 2 * sizeof(unsigned long long), s)); // (an always-false query logs nothing)
-        HIPCHK(hipMemsetAsync(q->d_bitmap, 0, (size_t)std::max<int64_t>(q->n_tiles * kTileWords, 1) * sizeof(uint64_t), s));
-        q->run.ran_select = true;
-        q->run.bitmap_valid = true;
-        q->run.ran_single_pass = false;
-        return IMM3_OK;
-    }
-    // (planned on every run: the tuning variant may have changed since creation)
-    const SelectChain chain = q->is_expr ? SelectChain() : plan_select_chain(q); // (a select tree is ONE launch of its own: no chain)
-    // (a table has no word-at-a-time kernel.  Creation has refused the predicates that need it; what is left here is the tools'
-    // TV_GENERIC_ONLY tuning variant, which sends every predicate there)
-    if (q->table && !chain.generic.empty()) return fail(IMM3_ERR_ARG, kTableGenericRefusal);
-    const int fv = ctx->filter_variant;
-    int pass = 0;
-    int grid = 1;
-    bool count_done = false; // the filter kernel's last work-group has written total / n_emit
-    q->run.stage_written = false;
-    q->run.bitmap_lazy = false;
-    q->run.ran_single_pass = false;
-    // exactly ONE launch in the whole select chain: only then may that launch publish the count (and append to the count
-    // log) itself, and only then are the survivors' values staged
-    const bool expr_tile = q->is_expr && q->expr_tile_ok && fv != TV_GENERIC_ONLY;
-    // (a table has no generic kernel, so the tools' TV_GENERIC_ONLY tuning variant has nothing to run for a table tree: imm3_diag.h)
-    if (q->is_expr && q->table && !expr_tile)
-        return fail(IMM3_ERR_ARG, "a select tree over a table runs through the tile kernel only (the generic-only tuning variant "
-                                  "does not apply to a table); use per-segment queries");
-    const bool skip_bitmap = count_only && (chain.single_tile_pass || expr_tile) && !q->table && !overlap_total && fv != TV_COUNT_BY_K_TOTAL;
-    q->run.bitmap_valid = !skip_bitmap;
-    // `limit` stops the scan (Project.scala:73-80; Engine.scala:166,253-258: the reference's workers stall on the full queue once the
-    // consumer has its rows): a projection with a limit whose select chain is one tile launch over one uniform segment runs that
-    // launch as chunks of growing size; every chunk first looks at the rows selected so far (a device word) and leaves at once when
-    // the limit has been reached -- nothing is read, no bitmap line written.  Enqueued blindly: no host wait.  TV_NO_LIMIT_CHUNKS: off.
-    // (Over a table the limit stops the scan inside one launch instead: table_limit_applies, in the tile pass below.)
-    LimitScanInputs li;
-    li.whole = mode & SEL_WHOLE;
-    li.count_log_on = q->count_log_on;
-    li.count_in_scan = count_in_scan;
-    li.limit = q->limit;
-    li.single_tile_pass = chain.single_tile_pass;
-    li.table = q->table != nullptr;
-    li.records = q->d_stage_rec != nullptr;
-    li.skip_bitmap = skip_bitmap;
-    li.overlap_total = overlap_total;
-    li.filter_variant = fv;
-    li.n_tiles = q->n_tiles;
-    const bool chunked = limit_scan_applies(li);
-    if (q->is_expr) { // the tree's terms, one launch (imm3_expr.hip); `limit` is the gather's to honour
-        LaunchTimer t(ctx, 0);
-        if (expr_tile) {
-            ExprTileArgs a;
-            std::memset(&a, 0, sizeof(a));
-            bool any_i32 = false;
-            int narrow_bytes = 0;
-            for (int k = 0; k < kMaxTileCols; ++k) {
-                a.kinds[k] = q->expr_kinds[k];
-                any_i32 |= a.kinds[k] == TK_I32;
-                narrow_bytes += a.kinds[k] == TK_I8 ? 1 : (a.kinds[k] == TK_S2 ? 2 : 0);
-            }
-            a.n_terms = (int32_t)q->expr_terms.size();
-            for (int ti = 0; ti < a.n_terms; ++ti)
-                for (int k = 0; k < kMaxTileCols && a.kinds[k] != TK_NONE; ++k) {
-                    const FoldedPred *fp = pred_on(q->expr_terms[(size_t)ti], q->expr_seg_col[k]);
-                    if (fp) {
-                        fill_tile_col(q, *fp, a.cols[ti][k], a.kinds[k]);
-                        a.use[ti] |= 1u << k;
-                    } else a.cols[ti][k].data = col_flat(q->seg->cols[(size_t)q->expr_seg_col[k]]); // (not tested in this term)
-                }
-            if (q->table) { // address the columns through the tile table (cols[..].data is not read)
-                a.tile_rows = q->table->d_tile_rows;
-                for (int k = 0; k < kMaxTileCols && a.kinds[k] != TK_NONE; ++k) a.tile_ptrs[k] = (const void *const *)q->table->d_tile_ptrs[(size_t)q->expr_seg_col[k]];
-            }
-            a.n_rows = q->n_rows;
-            a.n_words = q->n_words;
-            a.n_tiles = q->n_tiles;
-            a.bitmap = skip_bitmap ? nullptr : q->d_bitmap;
-            a.block_partials = q->d_block_partials;
-            grid = filter_grid(q->n_tiles, false, any_i32, ctx->grid_blocks, narrow_bytes);
-            if (!overlap_total && fv != TV_COUNT_BY_K_TOTAL && (grid <= 512 || fv != TV_COUNT_SMALL_GRID)) {
-                a.finish = q->d_total;
-                count_done = true;
-            }
-            if (!launch_filter_expr(a, grid, s, t.start, t.stop)) return fail(IMM3_ERR_ARG, "internal: no tree kernel for this column combination");
-            q->expr_form_ran = 0;
-        } else {
-            ExprGenericArgs a;
-            std::memset(&a, 0, sizeof(a));
-            a.preds = q->d_expr_preds;
-            a.term_start = q->d_expr_term_start;
-            a.n_terms = (int32_t)q->expr_terms.size();
-            a.n_rows = q->n_rows;
-            a.n_words = q->n_words;
-            a.n_tiles = q->n_tiles;
-            a.bitmap = q->d_bitmap;
-            a.block_partials = q->d_block_partials;
-            a.word_row_base = q->d_word_row_base;
-            a.word_nvalid = q->d_word_nvalid;
-            grid = filter_grid(q->n_words, true, false, ctx->grid_blocks);
-            launch_filter_expr_generic(a, grid, s, t.start, t.stop);
-            q->expr_form_ran = 1;
-        }
-        HIPCHK(hipGetLastError());
-        ++pass;
-    }
-    for (const auto &take : chain.tile_passes) {
-        TileArgs a;
-        std::memset(&a, 0, sizeof(a));
-        const int n = (int)take.size();
-        for (int k = 0; k < kMaxTileCols; ++k) a.kinds[k] = TK_NONE;
-        for (int k = 0; k < n; ++k) {
-            const FoldedPred &fp = *take[(size_t)k];
-            if (q->table) a.tile_ptrs[k] = (const void *const *)q->table->d_tile_ptrs[(size_t)fp.seg_col];
-            a.kinds[k] = tile_kind(fp);
-            fill_tile_col(q, fp, a.cols[k], a.kinds[k]);
-        }
-        if (chain.single_tile_pass && q->d_stage_rec && !skip_bitmap && !(mode & SEL_PLAIN)) { // the columns are in the order the records were laid out for (same sort)
-            bool same = true;
-            for (int k = 0; k < kMaxTileCols; ++k) same = same && a.kinds[k] == q->stage_kinds[k] && (k >= n || take[(size_t)k]->seg_col == q->stage_seg_col[k]);
-            if (!same) return fail(IMM3_ERR_ARG, "internal: staged record layout does not match the tile launch");
-            a.stage_rec = q->d_stage_rec;
-            a.tile_start = q->d_tile_start;
-            a.wave_cap = q->stage_wave_cap;
-            a.max_slots = q->stage_max_slots;
-            q->run.stage_written = true;
-        }
-        a.ablate = tile_ablation(fv); // (tools' build only)
-        a.and_existing = pass > 0;
-        a.n_rows = q->n_rows;
-        a.n_words = q->n_words;
-        a.n_tiles = q->n_tiles;
-        a.bitmap = q->d_bitmap;
-        // A records run whose offsets scan follows (imm3_query_run of a projection) stores NO bitmap: the records carry the positions
-        // and the scan takes the tiles' counts from the arenas (round 5: 12.5 MB of 128-byte line stores in between the streaming
-        // loads, and 12.5 MB read back by k_scan -- C4 107 -> 100 us).  imm3_query_bitmap materialises it on demand.  TV_EAGER_BITMAP: off.
-        q->run.bitmap_lazy = q->run.stage_written && count_in_scan && !q->count_log_on && fv != TV_EAGER_BITMAP;
-        if (q->run.bitmap_lazy) {
-            a.bitmap = nullptr;
-            q->run.bitmap_valid = false;
-        }
-        a.block_partials = q->d_block_partials;
-        a.tile_rows = q->table ? q->table->d_tile_rows : nullptr; // table query: address the columns through the tile table
-        bool any_i32 = false;
-        int narrow_bytes = 0;
-        for (int k = 0; k < kMaxTileCols; ++k) {
-            any_i32 |= (a.kinds[k] == TK_I32);
-            narrow_bytes += a.kinds[k] == TK_I8 ? 1 : (a.kinds[k] == TK_S2 ? 2 : 0);
-        }
-        bool stamped = false;
-        grid = filter_grid(q->n_tiles, false, any_i32, ctx->grid_blocks, narrow_bytes); // (no column at all: the store-only kernel also likes 1536 groups, 9.9 vs 17.2 us)
-        if (q->run.stage_written) grid = q->stage_grid; // fixed at creation: the arena layout depends on it
-        // A select chain that is ONE tile pass also reduces its count in the kernel (one relaxed atomic per work-group into a
-        // two-level tally, finish_add): no k_total launch.  TV_COUNT_BY_K_TOTAL = never; TV_COUNT_SMALL_GRID = only at <= 512 work-groups (what
-        // round 1 did: with a single tally the 1536 atomics of a narrow-column launch cost more than the launch they saved).
-        if (chain.single_tile_pass && !overlap_total && fv != TV_COUNT_BY_K_TOTAL && (grid <= 512 || fv != TV_COUNT_SMALL_GRID)) {
-            a.finish = q->d_total;
-            count_done = true;
-        }
-        // bitmap lines parked in LDS and stored in bursts: no staging (whose LDS and 2048 work-groups
-        // leave no room for 32 KiB more per group); TV_PLAN_PINNED switches it off
-        // (64 lines = 32 KiB per work-group at <= 4 groups per CU; 16 lines = 8 KiB for the 1536-group narrow-column kernels)
-        a.defer_lines = (fv == TV_PLAN_PINNED || q->run.bitmap_lazy) ? 0 : (q->run.stage_written ? 16 : (grid <= 1024 ? kDeferLines : 16)); // (no bitmap, no lines to park)
-        if (skip_bitmap) { // count-only: the kernel instance that stores nothing (the count is reduced in the kernel)
-            a.bitmap = nullptr;
-            a.defer_lines = 0;
-        }
-        if (ctx->d_stamps) { // (diagnostics: bench.py's instrumented pass)
-            std::lock_guard<std::mutex> lk(ctx->mu);
-            if (ctx->d_stamps && ctx->stamp_used < ctx->stamp_slots) {
-                a.stamps = ctx->d_stamps + (size_t)ctx->stamp_used * kMaxFilterGrid * 2;
-                ctx->stamp_grids.push_back(grid);
-                ++ctx->stamp_used;
-                stamped = true;
-            }
-        }
-        // A table query with a limit: ONE launch whose work-groups claim runs of tiles in ascending order and stop claiming once the
-        // finished runs hold `limit` rows (k_filter_table_limit); it publishes count, rows to emit and the scanned prefix itself.
-        TableLimitInputs ti;
-        ti.table = q->table != nullptr;
-        ti.tree = q->is_expr;
-        ti.limit = q->limit;
-        ti.count_in_scan = count_in_scan;
-        ti.single_tile_pass = chain.single_tile_pass;
-        ti.whole = mode & SEL_WHOLE;
-        ti.count_log_on = q->count_log_on;
-        ti.count_only = count_only;
-        ti.filter_variant = fv;
-        ti.n_tiles = q->n_tiles;
-        ti.grid = std::min(grid, kTableLimitMaxGrid); // (narrow columns like 1536 work-groups for a whole scan; here they would claim half of a 100 M-row table before the first run is done)
-        if (table_limit_applies(ti)) {
-            grid = ti.grid;
-            if (stamped) { // (diagnostics: the stamps of this launch are this grid's)
-                std::lock_guard<std::mutex> lk(ctx->mu);
-                if (!ctx->stamp_grids.empty()) ctx->stamp_grids.back() = grid;
-            }
-            a.finish = q->d_total;
-            a.defer_lines = 0;
-            LaunchTimer t(ctx, 0);
-            if (!launch_filter_table_limit(a, grid, s, t.start, t.stop)) return fail(IMM3_ERR_ARG, "internal: no tile kernel for this column combination");
-            HIPCHK(hipGetLastError());
-            count_done = true;
-            q->run.select_partial = true; // (the offsets scan and the gather stop at finish[kFinishLimitTiles]; the getters' whole select: settle_whole_select)
-            ++pass;
-            continue;
-        }
-        if (chunked) { // the limit scan: this launch in chunks that end at tiles 1024, 8192, 32 768, ...; each adds to the running count and scanned-tile words
-            int widths[kMaxTileCols] = {0, 0, 0};
-            for (int k = 0; k < kMaxTileCols; ++k) widths[k] = a.kinds[k] == TK_I32 ? 4 : (a.kinds[k] == TK_S2 ? 2 : (a.kinds[k] == TK_I8 ? 1 : 0));
-            int64_t tile0 = 0, len = kLimitFirstChunkTiles;
-            while (tile0 < q->n_tiles) {
-                const int64_t tiles = std::min<int64_t>(len, q->n_tiles - tile0);
-                TileArgs c = a;
-                for (int k = 0; k < kMaxTileCols; ++k)
-                    if (c.kinds[k] != TK_NONE) c.cols[k].data = (const uint8_t *)a.cols[k].data + tile0 * kTileRows * widths[k];
-                c.bitmap = a.bitmap + tile0 * kTileWords;
-                c.n_rows = std::min<int64_t>(tiles * kTileRows, q->n_rows - tile0 * kTileRows);
-                c.n_words = (c.n_rows + 63) / 64;
-                c.n_tiles = (c.n_words + kTileWords - 1) / kTileWords;
-                c.finish = q->d_total;
-                c.chunked = tile0 == 0 ? 2 : 1; // (the first chunk starts the running words over)
-                c.stamps = nullptr;
-                const int cgrid = filter_grid(c.n_tiles, false, any_i32, ctx->grid_blocks, narrow_bytes);
-                c.defer_lines = fv == TV_PLAN_PINNED ? 0 : (cgrid <= 1024 ? kDeferLines : 16);
-                LaunchTimer t(ctx, 0);
-                if (!launch_filter_tile(c, cgrid, s, t.start, t.stop)) return fail(IMM3_ERR_ARG, "internal: no tile kernel for this column combination");
-                HIPCHK(hipGetLastError());
-                tile0 += tiles;
-                len = tile0 == kLimitFirstChunkTiles ? kLimitSecondEndTiles - tile0 : tile0 * 3; // (the next chunk ends at 4 x this one's end)
-            }
-            count_done = true;
-            q->run.select_partial = true;
-            ++pass;
-            continue;
-        }
-        LaunchTimer t(ctx, 0);
-        if (!launch_filter_tile(a, grid, s, t.start, t.stop)) return fail(IMM3_ERR_ARG, "internal: no tile kernel for this column combination");
-        HIPCHK(hipGetLastError());
-        ++pass;
-    }
-    // PFOR_INT passes: one compressed column per launch, decoded in LDS and compared in registers
-    q->run.has_pfor_pass = !chain.pfor.empty();
-    for (const FoldedPred *fp : chain.pfor) {
-        const SegCol &sc = q->seg->cols[(size_t)fp->seg_col];
-        PforArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.data = sc.d_data;
-        a.block_off = sc.d_block_off;
-        a.n_blocks = (int64_t)sc.block_rows.size();
-        a.lo = (int32_t)fp->lo;
-        a.hi = (int32_t)fp->hi;
-        a.and_existing = pass > 0;
-        a.n_rows = q->n_rows;
-        a.n_words = q->n_words;
-        a.n_tiles = q->n_tiles;
-        a.bitmap = q->d_bitmap;
-        a.block_partials = q->d_block_partials;
-        a.status = (uint32_t *)(q->d_total + 2);
-        // VALU/LDS-latency bound, 5 waves per SIMD resident: the finest grid balances best (measured 83 us at 2048
-        // work-groups, 76 us at 4096, 100 M rows)
-        grid = filter_grid(q->n_tiles, true, false, ctx->grid_blocks > 0 ? ctx->grid_blocks.load() : kMaxFilterGrid);
-        {
-            LaunchTimer t(ctx, 0);
-            launch_filter_pfor(a, grid, s, t.start, t.stop);
-        }
-        HIPCHK(hipGetLastError());
-        ++pass;
-    }
-    // string passes (k_filter_str_rows): one column whose width is a multiple of 4 per launch, a segment or a table's tile table
-    for (const FoldedPred *fp : chain.str_passes) {
-        StrRowsArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.data = col_flat(q->seg->cols[(size_t)fp->seg_col]);
-        a.width = fp->width;
-        a.n_match = (int32_t)fp->match.size();
-        a.values = (const uint32_t *)fp->d_blob;
-        if (!a.values) // (upload_match_blobs: width <= 8 and <= kMaxMatch values)
-            for (size_t m = 0; m < fp->match.size() && m < (size_t)kMaxMatch; ++m) std::memcpy(a.inl[m], fp->match[m].data(), std::min<size_t>((size_t)fp->width, sizeof(a.inl[m])));
-        a.and_existing = pass > 0;
-        a.n_rows = q->n_rows;
-        a.n_words = q->n_words;
-        a.n_tiles = q->n_tiles;
-        a.bitmap = q->d_bitmap;
-        a.block_partials = q->d_block_partials;
-        if (q->table) {
-            a.tile_rows = q->table->d_tile_rows;
-            a.tile_ptrs = (const void *const *)q->table->d_tile_ptrs[(size_t)fp->seg_col];
-        }
-        grid = str_rows_grid(q->n_tiles, ctx->grid_blocks);
-        {
-            LaunchTimer t(ctx, 0);
-            if (!launch_filter_str_rows(a, grid, s, t.start, t.stop)) return fail(IMM3_ERR_ARG, "internal: no string kernel for this column width");
-        }
-        HIPCHK(hipGetLastError());
-        ++pass;
-    }
-    // generic passes
-    size_t gi = 0;
-    const bool need_empty_generic = q->preds.empty() && pass == 0;
-    while (gi < chain.generic.size() || (need_empty_generic && pass == 0)) {
-        FilterArgs a;
-        std::memset(&a, 0, sizeof(a));
-        const size_t take = std::min<size_t>(kMaxPredCols, chain.generic.size() - gi);
-        for (size_t i = 0; i < take; ++i) fill_colpred(q, *chain.generic[gi + i], a.cols[i]);
-        a.ncols = (int32_t)take;
-        a.and_existing = pass > 0;
-        a.n_rows = q->n_rows;
-        a.n_words = q->n_words;
-        a.n_tiles = q->n_tiles;
-        a.bitmap = q->d_bitmap;
-        a.block_partials = q->d_block_partials;
-        a.word_row_base = q->d_word_row_base;
-        a.word_nvalid = q->d_word_nvalid;
-        grid = filter_grid(q->n_words, true, false, ctx->grid_blocks);
-        {
-            LaunchTimer t(ctx, 0);
-            launch_filter_generic(a, grid, s, t.start, t.stop);
-        }
-        HIPCHK(hipGetLastError());
-        gi += take;
-        ++pass;
-    }
-    q->run.count_pending_scan = !count_done && count_in_scan;
-    if (!count_done && !count_in_scan) { // the last pass's per-workgroup partials -> selected-row count (+ rows ProjectOp will emit)
-        TotalArgs ta;
-        std::memset(&ta, 0, sizeof(ta));
-        ta.block_partials = q->d_block_partials;
-        ta.n_partials = grid;
-        ta.total = q->d_total;
-        ta.n_emit = q->d_n_emit;
-        ta.limit = q->limit;
-        hipStream_t ts = s;
-        if (overlap_total) {
-            // nothing downstream on the main stream needs the count: reduce it on the aux stream so the next scan
-            // starts right behind this one (saves the reduce kernel and two dependent-launch gaps per step)
-            {
-                std::lock_guard<std::mutex> lk(ctx->mu);
-                if (!ctx->aux) HIPCHK(hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking));
-            }
-            if (!q->ev_filter_done) {
-                HIPCHK(hipEventCreateWithFlags(&q->ev_filter_done, hipEventDisableTiming));
-                HIPCHK(hipEventCreateWithFlags(&q->ev_total_done, hipEventDisableTiming));
-            }
-            HIPCHK(hipEventRecord(q->ev_filter_done, s));
-            HIPCHK(hipStreamWaitEvent(ctx->aux, q->ev_filter_done, 0));
-            ts = ctx->aux;
-        }
-        {
-            LaunchTimer t(ctx, 3);
-            launch_total(ta, ts, t.start, t.stop);
-        }
-        if (overlap_total) {
-            HIPCHK(hipEventRecord(q->ev_total_done, ctx->aux));
-            q->total_on_aux = true;
-        }
-    }
-    HIPCHK(hipGetLastError());
-    q->run.ran_select = true;
-    return IMM3_OK;
-}
-
-// the SELECT-list columns as the unpacking kernels take them: gathered columns first, then the ones the record carries
-// (every mention of a staged column reads the record; the plan counts only the first as riding in it: proj_rides_in_records)
-static int fill_emit_cols(const imm3_query *q, EmitCol *out, int &n_out) {
-    std::vector<EmitCol> gathered, staged;
-    for (size_t j = 0; j < q->proj.size(); ++j) {
-        const int32_t sci = q->used[(size_t)q->proj[j]];
-        const SegCol &sc = q->seg->cols[(size_t)sci];
-        EmitCol c;
-        std::memset(&c, 0, sizeof(c));
-        c.dst = q->d_proj[j];
-        c.width = sc.width;
-        c.rec_dword = -1;
-        for (int k = 0; k < kMaxTileCols; ++k)
-            if (q->stage_seg_col[k] == sci) {
-                const RecField f = rec_layout(q->stage_kinds, k);
-                c.rec_dword = f.dword;
-                c.rec_shift = f.shift;
-            }
-        if (c.rec_dword < 0) { c.src = col_flat(sc); gathered.push_back(c); }
-        else staged.push_back(c);
-    }
-    int n = 0;
-    for (const auto &c : gathered) out[n++] = c;
-    for (const auto &c : staged) out[n++] = c;
-    n_out = n;
-    return (int)gathered.size();
-}
-
-void imm3::fill_tile_col(const imm3_query *q, const FoldedPred &fp, TileCol &c, int kind) {
-    c.data = col_flat(q->seg->cols[(size_t)fp.seg_col]);
-    c.lo = (int32_t)fp.lo;
-    c.hi = (int32_t)fp.hi;
-    if (kind == TK_S2) {
-        c.n_match = (int32_t)fp.match.size();
-        for (size_t m = 0; m < fp.match.size(); ++m)
-            c.match[m] = (uint32_t)(uint8_t)fp.match[m][0] | ((uint32_t)(uint8_t)fp.match[m][1] << 8);
-    }
-}
-
-// Per-device state of the single-pass projection kernel, whose work-groups wait on each other and therefore must own the
-// device while they run (imm3_project.hip): launches of all contexts of a device are chained through one event -- each
-// starts behind the previous one, stream side, no host wait -- and a device word holds the running launch's ticket for
-// whatever the host cannot order (graph replays, other processes on the same GPU).  Internal synchronisation state, guarded
-// by its mutex; it lives as long as the process.
-namespace {
-struct SinglePassDevice {
-    std::mutex mu;
-    hipEvent_t last = nullptr;            // recorded behind the last launch
-    unsigned long long *d_lock = nullptr; // the ticket word
-};
-SinglePassDevice g_single_pass[kMaxDevices];
-} // namespace
-
-static int single_pass_device(int device, SinglePassDevice **out) {
-    if (device < 0 || device >= kMaxDevices) return fail(IMM3_ERR_ARG, "device index out of range");
-    SinglePassDevice &d = g_single_pass[device];
-    std::lock_guard<std::mutex> lk(d.mu);
-    if (!d.d_lock) {
-        void *p = nullptr;
-        HIPCHK(hipMalloc(&p, 64));
-        HIPCHK(hipMemset(p, 0, 64));
-        d.d_lock = (unsigned long long *)p;
-        HIPCHK(hipEventCreateWithFlags(&d.last, hipEventDisableTiming));
-    }
-    *out = &d;
-    return IMM3_OK;
-}
-
-#ifdef IMM3_ABLATE
-static int single_pass_lock_word(int device, unsigned long long **out) {
-    SinglePassDevice *dev = nullptr;
-    const int rc = single_pass_device(device, &dev);
-    if (rc) return rc;
-    *out = dev->d_lock;
-    return IMM3_OK;
-}
-#endif
-
-// ScanOp -> SelectOp* -> ProjectOp in one launch (k_filter_project): bitmap, count and the projected rows
-static int run_single_pass(imm3_query *q) {
-    imm3_ctx *ctx = q->ctx;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    {
-        const int jrc = join_total(q, s);
-        if (jrc) return jrc;
-        q->total_on_aux = false;
-    }
-    // The rows are written by the filter kernel itself, so their arrays exist before the count does: the caller's
-    // reservation, else room for every row of the segment (pooled: allocated once).  A reservation that turns out too
-    // small is answered from the bitmap when the rows are fetched (settle_rows).
-    if (!q->reserved && q->cap_rows < (uint64_t)q->n_rows) {
-        const int rc = ensure_row_capacity(q, (uint64_t)q->n_rows);
-        if (rc) return rc;
-    }
-    ProjectArgs a;
-    std::memset(&a, 0, sizeof(a));
-    for (int k = 0; k < kMaxTileCols; ++k) {
-        a.kinds[k] = q->stage_kinds[k];
-        if (a.kinds[k] == TK_NONE) continue;
-        const FoldedPred *fp = nullptr;
-        for (const auto &p : q->preds)
-            if (p.seg_col == q->stage_seg_col[k]) fp = &p;
-        for (const auto &p : q->sp_pass) // (a streamed SELECT-list column: every value passes)
-            if (p.seg_col == q->stage_seg_col[k]) fp = &p;
-        if (!fp) return fail(IMM3_ERR_ARG, "internal: single-pass plan lost a predicate column");
-        fill_tile_col(q, *fp, a.cols[k], a.kinds[k]);
-    }
-    {   // a communicator may have been attached or destroyed since the plan was made: the grid follows, and so does the planned P
-        // (a P the host has lowered for dense survivors stays: it is below either plan)
-        const int32_t want_plan = q->sp_P_plan_for[single_pass_reserves(q) ? 1 : 0];
-        if (!q->sp_P_fixed && !ctx->capture && want_plan > 0 && want_plan != q->sp_P_plan) {
-            const bool at_plan = q->sp_P == q->sp_P_plan;
-            q->sp_P_plan = want_plan;
-            if (at_plan || q->sp_P > want_plan) {
-                if (hipMemsetAsync(q->d_desc, 0, q->sp_trash_off, s) == hipSuccess) single_pass_set_P(q, want_plan); // (hygiene, as in single_pass_pick_P)
-                else (void)hipGetLastError();
-            }
-        }
-        q->sp_grid = single_pass_run_grid(q);
-    }
-    a.P = q->sp_P;
-    a.n_rows = q->n_rows;
-    if (q->table) {
-        if (!q->d_tile_desc) return fail(IMM3_ERR_STATE, "internal: table query planned as one launch without its tile descriptors");
-        a.tile_desc = q->d_tile_desc;
-        a.n_rows = q->n_tiles * kTileRows; // (virtual rows: what the tiles span; the kernel takes a tile's valid rows from its descriptor)
-    }
-    a.n_tiles = q->n_tiles;
-    a.n_spans = q->sp_spans;
-    a.n_rounds = (q->sp_spans + q->sp_grid - 1) / q->sp_grid;
-    a.bitmap = q->d_bitmap;
-    a.finish = q->d_total;
-    a.desc = (unsigned long long *)((uint8_t *)q->d_desc + q->sp_desc_off);
-    a.round_total = q->d_desc;
-    a.round_ctr = (uint32_t *)(q->d_desc + q->sp_rounds_max);
-    a.trash = (uint8_t *)q->d_desc + q->sp_trash_off;
-    a.cap_rows = q->cap_rows;
-    a.row_index = q->d_row_index;
-    {   // SELECT-list columns: the first mention of a predicate column comes out of the records, everything else is gathered
-        int ng = 0;
-        for (size_t j = 0; j < q->proj.size(); ++j) {
-            const int32_t sci = q->used[(size_t)q->proj[j]];
-            const SegCol &sc = q->seg->cols[(size_t)sci];
-            int k_pred = -1;
-            for (int k = 0; k < kMaxTileCols; ++k)
-                if (q->stage_seg_col[k] == sci && !a.pred_dst[k]) { k_pred = k; break; }
-            if (k_pred >= 0) a.pred_dst[k_pred] = q->d_proj[j];
-            else {
-                if (ng >= kMaxEmitGather || q->table) return fail(IMM3_ERR_ARG, "internal: single-pass plan has too many gathered columns");
-                a.gather[ng].dst = q->d_proj[j];
-                a.gather[ng].src = col_flat(sc);
-                a.gather[ng].width = sc.width;
-                ++ng;
-            }
-        }
-        a.n_gather = ng;
-    }
-    a.ablate = project_ablation(ctx->filter_variant); // (tools' build only: a mask -- 1 no unpack, 2 no chained scan, 4 no records, 16 no output stores, 32 plain instead of non-temporal stores in the straight copy of fully surviving dense ranges)
-    a.max_polls = ctx->fault_max_polls; // (tools' build only: imm3_ctx_inject_fault)
-    a.fault_wg = ctx->fault_wg;
-    a.fault_span = ctx->fault_span;
-    if (ctx->d_stamps) {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (ctx->d_stamps && ctx->stamp_used < ctx->stamp_slots) {
-            a.stamps = ctx->d_stamps + (size_t)ctx->stamp_used * kMaxFilterGrid * 2;
-            ctx->stamp_grids.push_back(q->sp_grid);
-            ++ctx->stamp_used;
-        }
-    }
-    SinglePassDevice *dev = nullptr;
-    {
-        const int drc = single_pass_device(ctx->device, &dev);
-        if (drc) return drc;
-    }
-    a.device_lock = dev->d_lock;
-    {
-        std::lock_guard<std::mutex> lk(dev->mu); // (wait - launch - record is one step: the next launcher waits for THIS launch)
-        const bool chained = !ctx->capture;      // (a capture cannot depend on an event recorded outside it: the device lock covers replays)
-        if (chained) HIPCHK(hipStreamWaitEvent(s, dev->last, 0));
-        {
-            LaunchTimer t(ctx, 0);
-            const bool launched = q->table ? launch_filter_project_table(a, q->sp_grid, s, t.start, t.stop) : launch_filter_project(a, q->sp_grid, s, t.start, t.stop);
-            if (!launched) return fail(IMM3_ERR_ARG, "internal: no single-pass kernel for this column combination");
-        }
-        HIPCHK(hipGetLastError());
-        if (chained) HIPCHK(hipEventRecord(dev->last, s));
-    }
-    q->run.stage_written = false;
-    q->run.count_pending_scan = false;
-    q->run.has_pfor_pass = false;
-    q->run.ran_select = true;
-    q->run.bitmap_valid = true;
-    q->run.ran_project = true;
-    q->run.ran_single_pass = true;
-    q->run.sp_verified = false;
-    q->run.offsets_valid = false;
-    return IMM3_OK;
-}
-
-// ProjectOp from the survivor records the select launch staged
-static int launch_emit_records(imm3_query *q) {
-    imm3_ctx *ctx = q->ctx;
-    EmitArgs e;
-    std::memset(&e, 0, sizeof(e));
-    e.stage = q->d_stage_rec;
-    e.tile_start = q->d_tile_start;
-    e.wave_cap = q->stage_wave_cap;
-    e.n_waves = (int64_t)q->stage_grid * kWavesPerBlock;
-    e.main_tiles = q->stage_main_tiles;
-    e.max_slots = q->stage_max_slots;
-    e.T = q->stage_T;
-    e.ablate = emit_ablation(ctx->filter_variant); // (tools' build only)
-    e.tile_offsets = q->d_tile_offsets;
-    e.chunk_sums = q->d_chunk_sums;
-    e.n_tiles = q->n_tiles;
-    e.cap_rows = q->cap_rows;
-    e.row_index = q->d_row_index;
-    e.R = rec_layout(q->stage_kinds, -1).dwords;
-    int n_cols = 0;
-    const int n_gather = fill_emit_cols(q, e.cols, n_cols);
-    e.n_cols = n_cols;
-    LaunchTimer t(ctx, 2);
-    launch_emit(e, n_gather, 0, ctx->stream, t.start, t.stop);
-    HIPCHK(hipGetLastError());
-    return IMM3_OK;
-}
-
-static int launch_project(imm3_query *q) {
-    imm3_ctx *ctx = q->ctx;
-    hipStream_t s = ctx->stream;
-    if (q->run.stage_written) return launch_emit_records(q);
-    GatherArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.bitmap = q->d_bitmap;
-    g.tile_offsets = q->d_tile_offsets;
-    g.chunk_sums = q->d_chunk_sums;
-    g.n_tiles = q->n_tiles;
-    g.n_words = q->n_words;
-    g.limit = q->limit;
-    g.cap_rows = q->cap_rows;
-    g.n_staged_tiles = 0;
-    g.word_row_base = q->d_word_row_base;
-    g.tile_rows = q->table ? q->table->d_tile_rows : nullptr;
-    g.scanned_tiles = q->run.select_partial ? q->d_total + kFinishLimitTiles : nullptr;
-    // more SELECT-list columns than one launch carries: gather in groups (row indices written by the first)
-    size_t done = 0;
-    const size_t np = q->proj.size();
-    do {
-        const size_t take = std::min<size_t>(kMaxProj, np - done);
-        g.row_index = done == 0 ? q->d_row_index : nullptr;
-        g.n_proj = (int32_t)take;
-        for (size_t j = 0; j < take; ++j) {
-            const SegCol &sc = q->seg->cols[(size_t)q->used[(size_t)q->proj[done + j]]];
-            g.proj[j].src = col_flat(sc);
-            g.proj[j].tile_ptrs = q->table ? (const void *const *)q->table->d_tile_ptrs[(size_t)q->used[(size_t)q->proj[done + j]]] : nullptr;
-            g.proj[j].dst = q->d_proj[done + j];
-            g.proj[j].width = sc.width;
-            g.proj[j].staged = nullptr;
-        }
-        {
-            LaunchTimer t(ctx, 2);
-            launch_gather(g, 0, s, t.start, t.stop);
-        }
-        HIPCHK(hipGetLastError());
-        done += take;
-    } while (done < np);
-    return IMM3_OK;
-}
-
-// A small limit behind a limit scan: the offsets scan and the gather in ONE launch over the scanned tiles (k_limit_gather).
-// `select id ... limit 10`: 7 + 9 us of k_scan + k_gather -> ~5.  TV_LIMIT_NO_FUSED_GATHER: off.
-constexpr int kLimitGatherGrid = 256;
-static bool limit_gather_applies(const imm3_query *q) {
-    if (!q->run.select_partial || !(q->limit > 0) || q->limit > kLimitGatherMaxRows || q->table || q->d_word_row_base || q->run.stage_written || q->ctx->filter_variant == TV_LIMIT_NO_FUSED_GATHER) return false;
-    if (q->n_chunks > (int64_t)kLimitGatherGrid * kLimitGatherMaxChunks || q->proj.size() > (size_t)kMaxProj || !q->d_limit_state) return false;
-    for (int32_t pj : q->proj) {
-        const SegCol &sc = q->seg->cols[(size_t)q->used[(size_t)pj]];
-        if (!col_flat(sc) || (sc.width != 1 && sc.width != 2 && sc.width != 4)) return false;
-    }
-    return true;
-}
-static int launch_limit_gather_for(imm3_query *q) {
-    imm3_ctx *ctx = q->ctx;
-    LimitGatherArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.bitmap = q->d_bitmap;
-    g.finish = q->d_total;
-    g.wg_state = q->d_limit_state;
-    g.n_tiles = q->n_tiles;
-    g.limit = q->limit;
-    g.cap_rows = q->cap_rows;
-    g.row_index = q->d_row_index;
-    g.n_proj = (int32_t)q->proj.size();
-    g.fault_wg = ctx->fault_wg;        // (tools' build only: imm3_ctx_inject_fault)
-    g.max_polls = ctx->fault_max_polls;
-    for (size_t j = 0; j < q->proj.size(); ++j) {
-        const SegCol &sc = q->seg->cols[(size_t)q->used[(size_t)q->proj[j]]];
-        g.proj[j].src = col_flat(sc);
-        g.proj[j].dst = q->d_proj[j];
-        g.proj[j].width = sc.width;
-    }
-    LaunchTimer t(ctx, 2);
-    launch_limit_gather(g, (int)std::min<int64_t>(kLimitGatherGrid, std::max<int64_t>(q->n_chunks, 1)), ctx->stream, t.start, t.stop);
-    HIPCHK(hipGetLastError());
-    return IMM3_OK;
-}
-
-static int run_project(imm3_query *q) {
-    imm3_ctx *ctx = q->ctx;
-    hipStream_t s = ctx->stream;
-    if (q->n_tiles > 0 && limit_gather_applies(q)) {
-        if (!q->d_row_index) {
-            const int rc = ensure_row_capacity(q, 1);
-            if (rc) return rc;
-        }
-        const int rc = launch_limit_gather_for(q);
-        if (rc) return rc;
-        q->run.offsets_valid = false; // (no offsets scan has run on this bitmap)
-        q->run.ran_project = true;
-        q->run.limit_gather_ran = true;
-        return IMM3_OK;
-    }
-    q->run.limit_gather_ran = false;
-    if (q->n_tiles > 0) {
-        ScanArgs sa;
-        std::memset(&sa, 0, sizeof(sa));
-        sa.bitmap = q->d_bitmap;
-        sa.tile_offsets = q->d_tile_offsets;
-        sa.chunk_sums = q->d_chunk_sums;
-        sa.n_tiles = q->n_tiles;
-        sa.finish = q->run.count_pending_scan ? q->d_total : nullptr;
-        sa.scanned_tiles = q->run.select_partial ? q->d_total + kFinishLimitTiles : nullptr;
-        if (q->run.stage_written && q->run.bitmap_lazy) { // no bitmap was stored: the tiles' counts come from the records' start table
-            sa.rec_tile_start = q->d_tile_start;
-            sa.rec_n_waves = (int64_t)q->stage_grid * kWavesPerBlock;
-            sa.rec_main_tiles = q->stage_main_tiles;
-            sa.rec_max_slots = q->stage_max_slots;
-            sa.rec_T = q->stage_T;
-        }
-        {
-            LaunchTimer t(ctx, 1);
-            launch_scan(sa, s, t.start, t.stop);
-        }
-        HIPCHK(hipGetLastError());
-        q->run.offsets_valid = true;
-    }
-    if (!(q->limit > 0) && !q->reserved && !q->d_row_index) {
-        // Unlimited projection, no reservation, FIRST run: the output size is the count -> one synchronisation.  The arrays get
-        // an eighth of headroom and every later run of the query writes into them without asking: a steady-state projecting
-        // query never synchronises (a run that outgrows them is detected when its rows are fetched, and emitted again).
-        unsigned long long total = 0;
-        HIPCHK(hipMemcpyAsync(&total, q->d_total, sizeof(total), hipMemcpyDeviceToHost, s));
-        // ... and, for the cost model, where the survivors are: the offsets scan's per-chunk counts (256 tiles each; 1.5 KB for 100 M
-        // rows) say how densely they sit where they sit and how many of them in fully surviving chunks -- the whole segment, where
-        // the sample at creation saw 0.5 % of it (a range of a sorted key between two sample chunks showed it nothing)
-        std::vector<uint32_t> chunk_counts;
-        if (!q->plan_pinned && !q->table && q->n_chunks > 0 && q->n_chunks <= (1 << 20) && q->run.offsets_valid) {
-            chunk_counts.resize((size_t)q->n_chunks);
-            HIPCHK(hipMemcpyAsync(chunk_counts.data(), q->d_chunk_sums, chunk_counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
-        ++q->run_syncs;
-        if (!chunk_counts.empty() && total > 0) {
-            const double chunk_rows = (double)kChunkTiles * kTileRows;
-            double sum = 0.0, sum_sq = 0.0, sum_full = 0.0;
-            for (size_t i = 0; i < chunk_counts.size(); ++i) {
-                const double c = (double)chunk_counts[i];
-                sum += c;
-                sum_sq += c * c;
-                if (c >= chunk_rows) sum_full += c;
-            }
-            if (sum > 0.0) {
-                q->plan_density.sigma = (double)total / (double)std::max<int64_t>(q->n_rows, 1);
-                q->plan_density.sloc = std::min(1.0, std::max(q->plan_density.sigma, sum_sq / (sum * chunk_rows)));
-                q->plan_density.full = sum_full / sum;
-                q->plan_have_density = true;
-            }
-        }
-        {   // enough survivors for the gathered columns to be streamed instead?  Then this run is done again as one launch
-            const int src = single_pass_stream_columns(q, total);
-            if (src) return src;
-            if (q->single_pass) return run_single_pass(q);
-            if (single_pass_restore_wanted(q, total)) {
-                q->sp_restore_pending = true; // (from the next run on)
-                q->sp_restore_survivors = total;
-            }
-            records_drop_if_narrow(q, total); // (this run's rows then come from the bitmap)
-            if (!q->d_stage_rec && q->run.bitmap_lazy) { // ... which the staging launch did not store: the select chain runs once more, plainly (the offsets stand: same counts)
-                const int prc = run_select(q, SEL_WHOLE);
-                if (prc) return prc;
-                q->run.offsets_valid = true;
-            }
-        }
-        const unsigned long long want = std::min<unsigned long long>((unsigned long long)std::max<int64_t>(q->n_rows, 1), total + total / 8 + 1024);
-        const int rc = ensure_row_capacity(q, want);
-        if (rc) return rc;
-    } else if (!q->d_row_index) {
-        const int rc = ensure_row_capacity(q, 1);
-        if (rc) return rc;
-    }
-    if (q->n_tiles > 0) {
-        const int rc = launch_project(q);
-        if (rc) return rc;
-    }
-    q->run.ran_project = true;
-    return IMM3_OK;
-}
-
-static int run_agg(imm3_query *q);
-static bool agg_run_fuses(const imm3_query *q);
-
-// a run recorded into an open capture: nothing in it may synchronise, allocate or use a second stream
-static int capture_admit(imm3_query *q) {
-    imm3_ctx *ctx = q->ctx;
-    if (!ctx->capture) return IMM3_OK;
-    if (ctx->filter_variant == TV_COUNT_ON_AUX) return fail(IMM3_ERR_STATE, "tuning variant 2 (count reduce on the aux stream) cannot be captured");
-    const bool sp = q->single_pass && !q->proj.empty() && !q->always_false && q->n_tiles > 0; // (writes its rows without knowing the count)
-    if (!q->proj.empty() && !(q->limit > 0) && !q->reserved && !sp && !q->d_row_index)
-        return fail(IMM3_ERR_STATE, "an unlimited projection sizes its output from the count on its first run (a synchronisation): run it once, or call imm3_query_reserve_rows, before capturing it");
-    if (sp && !q->reserved && q->cap_rows < (uint64_t)q->n_rows)
-        return fail(IMM3_ERR_STATE, "run the query once (or reserve rows) before capturing it: its output buffers are allocated on first use");
-    if (!q->proj.empty() && !q->d_row_index) return fail(IMM3_ERR_STATE, "run the query once (or reserve rows) before capturing it: its output buffers are allocated on first use");
-    auto &qs = ctx->capture->queries;
-    if (std::find(qs.begin(), qs.end(), q) == qs.end()) {
-        qs.push_back(q);
-        ctx->capture->states.emplace_back();
-    }
-    return IMM3_OK;
-}
-
-// the run has been recorded: what it leaves in the handle is what every replay of the graph leaves (imm3_graph_launch)
-static int capture_note(imm3_query *q, int rc) {
-    imm3_ctx *ctx = q->ctx;
-    if (rc || !ctx->capture) return rc;
-    auto &qs = ctx->capture->queries;
-    const auto it = std::find(qs.begin(), qs.end(), q);
-    if (it == qs.end()) return rc;
-    ctx->capture->states[(size_t)(it - qs.begin())] = q->run;
-    return rc;
-}
-
-// The three run calls: the context's capture gate held for the whole run, the run admitted into an open capture and noted there
-// (capture_note); `plan` is what the call launches.
-static int run_entry(imm3_query *q, int (*plan)(imm3_query *)) {
-    if (!q) return fail(IMM3_ERR_ARG, "query is null");
-    CTX_LIVE_RUN(q->ctx);
-    const int ca = capture_admit(q);
-    if (ca) return ca;
-    q->run.ran_project = false;
-    return capture_note(q, plan(q));
-}
-
-extern "C" int imm3_query_run_select(imm3_query *q) {
-    return run_entry(q, [](imm3_query *r) { return run_select(r, r->ctx->filter_variant == TV_COUNT_ON_AUX ? SEL_OVERLAP_TOTAL : SEL_DEFAULT); });
-}
-
-extern "C" int imm3_query_run_count(imm3_query *q) {
-    return run_entry(q, [](imm3_query *r) { return run_select(r, SEL_COUNT_ONLY); });
-}
-
-extern "C" int imm3_query_join_count(imm3_query *q) {
-    if (!q) return fail(IMM3_ERR_ARG, "query is null");
-    CTX_LIVE(q->ctx);
-    HIPCHK(hipSetDevice(q->ctx->device));
-    return imm3::join_query_count(q);
-}
-
-static int run_query(imm3_query *q) {
-    // Reducing the count on the aux stream (TV_COUNT_ON_AUX) measured SLOWER on MI355X / ROCm 7.2 (75.6 vs 67.1 us
-    // per step: the cross-queue event packets cost more than the two same-queue launch gaps they remove), so the
-    // default keeps the reduce on the main stream.
-    if (q->sp_restore_pending && !q->ctx->capture) {
-        const int rrc = single_pass_restore(q, q->sp_restore_survivors);
-        if (rrc) return rrc;
-    }
-    if (q->single_pass && !q->proj.empty() && !q->always_false && q->n_tiles > 0) return run_single_pass(q);
-    const bool select_only = q->proj.empty() && !q->is_agg && q->ctx->filter_variant == TV_COUNT_ON_AUX;
-    const bool count_in_scan = !q->proj.empty() && q->n_tiles > 0 && !q->always_false && q->ctx->filter_variant != TV_COUNT_BY_K_TOTAL;
-    int rc = IMM3_OK;
-    q->run.agg_select_skipped = agg_run_fuses(q);
-    if (q->run.agg_select_skipped) q->run.ran_select = true; // (bitmap and count on demand: settle_agg_select)
-    else rc = run_select(q, (select_only ? SEL_OVERLAP_TOTAL : SEL_DEFAULT) | (count_in_scan ? SEL_COUNT_IN_SCAN : SEL_DEFAULT));
-    if (rc) return rc;
-    if (!q->proj.empty()) rc = run_project(q);
-    if (!rc && q->is_agg) rc = run_agg(q);
-    return rc;
-}
-
-extern "C" int imm3_query_run(imm3_query *q) { return run_entry(q, run_query); }
-
-extern "C" int imm3_query_sync(imm3_query *q) {
-    if (!q) return fail(IMM3_ERR_ARG, "query is null");
-    CTX_LIVE(q->ctx);
-    HIPCHK(hipSetDevice(q->ctx->device));
-    HIPCHK(hipStreamSynchronize(q->ctx->stream));
-    if (q->ctx->aux) HIPCHK(hipStreamSynchronize(q->ctx->aux));
     return IMM3_OK;
 }
 
@@ -2977,7 +2028,7 @@ static void agg_launch_args(const imm3_query *q, AggArgs &a) {
     a.ablate = agg_ablation(fv);
 }
 // will this run's aggregation launch evaluate the select chain itself?  (then no select launch precedes it)
-static bool agg_run_fuses(const imm3_query *q) {
+bool imm3::agg_run_fuses(const imm3_query *q) {
     if (!q->is_agg || !q->agg_fusable || q->count_log_on) return false; // (a count log wants every run's count on the device: the select launch produces it)
     AggArgs a;
     agg_launch_args(q, a);
@@ -3017,7 +2068,7 @@ static int launch_agg(imm3_query *q, const AggArgs &a, hipStream_t s, bool timed
     return IMM3_OK;
 }
 
-static int run_agg(imm3_query *q) {
+int imm3::run_agg(imm3_query *q) {
     imm3_ctx *ctx = q->ctx;
     AggArgs a;
     agg_launch_args(q, a);

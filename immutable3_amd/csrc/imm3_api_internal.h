@@ -1,8 +1,21 @@
-// imm3_api_internal.h -- what imm3_api.cpp (the C ABI: validation, launches, getters) and imm3_planner.cpp (plans and their
-// geometry) share.  Internal to libimm3: nothing here is part of include/imm3.h.
+// imm3_api_internal.h -- what imm3_api.cpp (the C ABI but for the run calls: validation, creation, getters, aggregation), imm3_run.cpp
+// (the run calls and their launches), imm3_planner.cpp (plans and their geometry) and imm3_expr_norm.cpp (select trees) share: only
+// what crosses between them.  Internal to libimm3: nothing here is part of include/imm3.h.
 #pragma once
 
 #include "imm3_handles.h"
+
+// Entry into a context (imm3_sync.h): the call passes the context's capture gate -- shared, so calls of any number of
+// threads run side by side; while ANOTHER thread has a graph capture open it waits here until that capture ends.
+// (Declares a scope guard: one use per function scope.)
+#define CTX_LIVE_RUN(c)                                                                           \
+    if (!(c)) return fail(IMM3_ERR_ARG, "ctx is null");                                           \
+    imm3::GateScope imm3_gate_scope_(&(c)->gate);                                                 \
+    if ((c)->closed) return fail(IMM3_ERR_STATE, "the context of this handle has been destroyed")
+// every entry point but the run calls: not while THIS thread's graph capture is open (most of them synchronise or allocate)
+#define CTX_LIVE(c)                                                                               \
+    CTX_LIVE_RUN(c);                                                                              \
+    if ((c)->capture) return fail(IMM3_ERR_STATE, "a graph capture is open on this context: only imm3_query_run / imm3_query_run_select and imm3_ctx_capture_end are accepted")
 
 namespace imm3 {
 
@@ -10,7 +23,45 @@ namespace imm3 {
 hipError_t pool_alloc(imm3_ctx *ctx, void **out, size_t bytes);      // the context's caching allocator (stream-ordered reuse)
 void pool_release(imm3_ctx *ctx, void *p);
 void graphs_mark_stale(imm3_ctx *ctx, const imm3_query *q);          // recorded graphs that replay this query point at buffers that are about to move
+int ensure_row_capacity(imm3_query *q, uint64_t rows);               // the projection's output arrays, for at least `rows` rows
+extern const char *const kTableGenericRefusal;                       // a table has no word-at-a-time kernel: the refusal's text, at creation and at a run
+int run_agg(imm3_query *q);                                          // ProjectAggOp behind (or fused with) the select: the aggregation launch
+bool agg_run_fuses(const imm3_query *q);                             // ... which evaluates the select chain itself: no run_select
+
+// Hands out one event pair per launch when timing is on; the launcher stamps it with the kernel's own
+// start and end (hipExtLaunchKernelGGL), so elapsed time == kernel duration as rocprofv3 reports it.
+struct LaunchTimer {
+    hipEvent_t start = nullptr, stop = nullptr;
+    LaunchTimer(imm3_ctx *ctx, int32_t id) {
+        if (!ctx->timing.load(std::memory_order_relaxed) || ctx->capture || !((ctx->timing_mask.load(std::memory_order_relaxed) >> id) & 1u)) return;
+        std::lock_guard<std::mutex> lk(ctx->mu); // (diagnostics only: the lock is taken when timing is on)
+        if (ctx->used < ctx->pool.size()) {
+            TimingRecord &rec = ctx->pool[ctx->used++];
+            rec.kernel_id = id;
+            start = rec.start;
+            stop = rec.stop;
+        }
+    }
+};
+
+// ---- imm3_run.cpp ----
+// What a caller of run_select wants, OR-ed together; SEL_DEFAULT: store the bitmap, reduce the count on the main stream.
+enum SelectMode : unsigned {
+    SEL_DEFAULT = 0,
+    SEL_OVERLAP_TOTAL = 1u << 0, // nothing on the main stream needs the count: reduce it on the aux stream (TV_COUNT_ON_AUX)
+    SEL_COUNT_IN_SCAN = 1u << 1, // a projection follows on the same stream; its offsets scan publishes the count (no k_total launch)
+    SEL_COUNT_ONLY = 1u << 2,    // the caller wants selected.size alone -- a chain that is ONE tile launch then stores no bitmap
+    SEL_WHOLE = 1u << 3,         // never in chunks (the getters' full select)
+    SEL_PLAIN = 1u << 4,         // stage no survivor records: the bitmap is what the caller wants (settle_lazy_bitmap)
+};
+int run_select(imm3_query *q, unsigned mode);                        // ScanOp -> SelectOp*: bitmap and count; mode: SelectMode bits
+int launch_project(imm3_query *q);                                   // the gather behind an offsets scan: from the records a run staged, else from the bitmap
+int join_total(imm3_query *q, hipStream_t s);                        // make `s` wait for the count reduce on the aux stream
+void fill_colpred(const imm3_query *q, const FoldedPred &fp, ColPred &cp);
 void fill_tile_col(const imm3_query *q, const FoldedPred &fp, TileCol &c, int kind);
+#ifdef IMM3_ABLATE
+int single_pass_lock_word(int device, unsigned long long **out);     // the device's ticket word of the single-pass kernel (imm3_ctx_debug_device_lock)
+#endif
 
 // scalar rules shared with the reference (JVM d2i / i2b): Select.scala:65,73; SURVEY Appendix A.1 rule 5
 inline int32_t jvm_d2i(double d) {
@@ -35,7 +86,9 @@ int expr_normalize(const std::vector<ExprCol> &leaf_cols, const imm3_select *lea
 constexpr int kSampleChunks = 8;                                      // the sample a plan is made on: eight chunks of 64 tiles spread over the segment / table
 constexpr int64_t kSampleChunkTiles = 64;
 constexpr int kSampleTiles = kSampleChunks * (int)kSampleChunkTiles;
-constexpr int64_t kLimitFirstChunkTiles = 1024;                       // a limit scan's first chunk (the next ones are 8 x, 4 x, 4 x ... larger)
+constexpr int64_t kLimitFirstChunkTiles = 1024;                       // a limit scan's first chunk ends here, the second at
+constexpr int64_t kLimitSecondEndTiles = 8192;                        // ... this tile, every later one at 4 x the end before it
+constexpr int kLimitMaxChunks = 32;                                   // (27 such ends fit an int64_t)
 
 int tile_kind(const FoldedPred &fp);
 bool str_rows_pred(const FoldedPred &fp);
@@ -55,7 +108,7 @@ void single_pass_drop_if_narrow(imm3_query *q, uint64_t survivors);
 bool single_pass_restore_wanted(const imm3_query *q, uint64_t survivors);
 int single_pass_restore(imm3_query *q, uint64_t survivors);
 
-// The select chain's passes as run_select enqueues them, from the query's folded predicates and the tuning variant read NOW: tile passes
+// The select chain's passes as run_select (imm3_run.cpp) enqueues them, from the query's folded predicates and the tuning variant read NOW: tile passes
 // of up to kMaxTileCols columns (numeric kinds first, at most one 2-byte string each; a query without predicates is one tile pass
 // with zero columns), then one k_filter_pfor pass per fused PFOR_INT predicate, then one k_filter_str_rows pass per string predicate
 // on a column whose width is a multiple of 4, then the word-at-a-time passes.
@@ -73,6 +126,11 @@ struct LimitScanInputs {
     int filter_variant = 0;
 };
 bool limit_scan_applies(const LimitScanInputs &in);
+struct LimitChunks {
+    int n = 0;                        // chunks; end[0 .. n) ascending, end[n - 1] == n_tiles
+    int64_t end[kLimitMaxChunks] = {}; // the tile a chunk ends before (the next chunk's first tile)
+};
+LimitChunks limit_chunk_ends(int64_t n_tiles); // a limit scan's chunks over a segment of n_tiles tiles (none for an empty one)
 
 // A projection with a `limit` over a TABLE: one limit-aware launch whose work-groups claim runs of tiles and stop claiming at the
 // limit (k_filter_table_limit), or the whole select as before?

@@ -110,7 +110,7 @@ struct imm3_comm {
 };
 
 // A communicator whose collectives put KERNELS on the device -- more than one rank (a one-rank all-reduce launches none), or the
-// tools' stand-in -- makes the one-launch plans of its context leave a CU per XCD free (imm3_api.cpp: single_pass_run_grid).
+// tools' stand-in -- makes the one-launch plans of its context leave a CU per XCD free (imm3_planner.cpp: single_pass_run_grid).
 static void comm_reserve(imm3_comm *c, bool on) {
     if (on == c->reserves) return;
     c->reserves = on;

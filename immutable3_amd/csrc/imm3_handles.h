@@ -1,5 +1,5 @@
 // imm3_handles.h -- the handle structs behind include/imm3.h, shared by the translation units of the C ABI
-// (imm3_api.cpp: planning + launches; imm3_comm.cpp: the RCCL count reduce).  Private to csrc/.
+// (imm3_api.cpp: creation + getters; imm3_run.cpp: the run and its launches; imm3_planner.cpp: plans; imm3_comm.cpp: the RCCL count reduce).  Private to csrc/.
 #pragma once
 
 #include "../../include/imm3.h"
@@ -117,7 +117,7 @@ struct imm3_ctx {
     imm3_graph *capture = nullptr;  // open stream capture (imm3_ctx_capture_begin .. _end), else null; owned by the capturing thread (gate)
     std::vector<imm3_graph *> graphs; // graphs recorded on this context that have not been destroyed yet (mu)
     // fault injection into k_filter_project (imm3_ctx_inject_fault, imm3_diag.h): read by the tools' build of the kernel only
-    std::atomic<int> comms_attached{0}; // communicators created on this context and not yet destroyed: one-launch plans leave CUs for their kernels (imm3_api.cpp: single_pass_run_grid)
+    std::atomic<int> comms_attached{0}; // communicators created on this context and not yet destroyed: one-launch plans leave CUs for their kernels (imm3_planner.cpp: single_pass_run_grid)
     std::atomic<int> fault_wg{-1}, fault_span{-1};
     std::atomic<uint32_t> fault_max_polls{0};
 };
@@ -225,7 +225,7 @@ struct imm3_table { // all segments of one table as one scan unit: the tile tabl
     int64_t n_tiles = 0, n_rows = 0;
     uint32_t *d_tile_rows = nullptr;   // valid rows per tile
     std::vector<void **> d_tile_ptrs;  // per column: device array of per-tile pointers
-    // the sample a query's plan is made on (single_pass_sample, imm3_api.cpp): eight chunks of 64 tiles spread over the table
+    // the sample a query's plan is made on (single_pass_sample, imm3_planner.cpp): eight chunks of 64 tiles spread over the table
     uint32_t *d_sample_rows = nullptr;     // valid rows of the sampled tiles (null: the table is too small to sample)
     std::vector<void **> d_sample_ptrs;    // per column: the sampled tiles' pointers
     // batches of all segments (every column shares one block layout: checked at creation), built once: a query over 98

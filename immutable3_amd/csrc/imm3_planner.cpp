@@ -1,11 +1,13 @@
 // imm3_planner.cpp -- which plan a projection takes and with what geometry (round 5: split off imm3_api.cpp, which keeps the C
-// ABI's validation, launches and getters).  Everything here is host arithmetic plus the one sampling launch at query creation:
+// ABI's validation and getters; the launches of a run are imm3_run.cpp).  Everything here is host arithmetic plus the one sampling
+// launch at query creation:
 //   * the one-launch projection's geometry: tiles per wave and span (P) per grid, the grid a run may use while a communicator
 //     is attached, the descriptor allocation (single_pass_setup, single_pass_run_grid, single_pass_adapt);
 //   * the cost model's decisions between the one launch, survivor records and the bitmap path (imm3_plan.h) on an estimate --
 //     the sample at creation, a reservation -- or on a run's count (single_pass_stream_columns, records_drop_if_narrow,
 //     single_pass_drop_if_narrow, single_pass_restore);
-//   * whether a projection with a `limit` scans in chunks (limit_scan_applies) or, over a table, in one launch that stops (table_limit_applies);
+//   * whether a projection with a `limit` scans in chunks (limit_scan_applies) and where the chunks end (limit_chunk_ends) or, over a
+//     table, in one launch that stops (table_limit_applies);
 //   * the select chain's passes (plan_select_chain) and the plan query creation makes for a projection (plan_projection).
 // The reference has no planner to mirror: its Engine builds ScanOp -> SelectOp* -> ProjectOp per segment unconditionally
 // (engine/src/main/scala/immutabledb/engine/Engine.scala:158-196); these are choices between equivalent executions of that chain.
@@ -15,6 +17,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -27,7 +30,7 @@
 namespace imm3 {
 
 // `limit` stops the scan (Project.scala:73-80; Engine.scala:166,253-258): a projection with a limit whose select chain is ONE tile
-// launch over one uniform segment runs that launch as chunks of growing size (run_select, imm3_api.cpp).  Not when the caller wants
+// launch over one uniform segment runs that launch as chunks of growing size (launch_tile_chunks, imm3_run.cpp).  Not when the caller wants
 // the whole segment's count anyway (`whole`: a getter settling a partial scan; a count log), not for a select-only run
 // (count_in_scan false: no projection follows), not for tables, records plans or count-only runs, not under the tuning variants that
 // pin the old launches (7: k_total, 14: no chunks), and not for segments the first chunk already covers.
@@ -36,6 +39,21 @@ bool limit_scan_applies(const LimitScanInputs &in) {
     if (in.table || in.records || in.skip_bitmap || in.overlap_total) return false;
     if (in.filter_variant == TV_COUNT_BY_K_TOTAL || in.filter_variant == TV_NO_LIMIT_CHUNKS) return false;
     return in.n_tiles > kLimitFirstChunkTiles;
+}
+
+// Chunks of a limit scan: they end at tiles 1024, 8192, 32 768, 131 072, ... (x 4) and at the segment's end -- four launches for
+// 100 M rows.  A `limit 10` is usually met in the first megarow: the chunks behind it cost their dispatch only (1 - 4 us each, which
+// is why there are few of them); a limit met at 5 % of the segment stops at 8 %; one met in the second half scans everything, as a
+// whole select would.  Multiples of kChunkTiles (the offsets scan's unit), but for the last end.
+LimitChunks limit_chunk_ends(int64_t n_tiles) {
+    static_assert(kLimitFirstChunkTiles % kChunkTiles == 0 && kLimitSecondEndTiles % kChunkTiles == 0, "a chunk of the limit scan ends where a chunk of the offsets scan does");
+    LimitChunks c;
+    for (int64_t end = kLimitFirstChunkTiles; end < n_tiles; end = end == kLimitFirstChunkTiles ? kLimitSecondEndTiles : end * 4) {
+        c.end[c.n++] = end;
+        if (end > INT64_MAX / 4) break; // (no further end fits an int64_t: 27 entries at the most)
+    }
+    if (n_tiles > 0) c.end[c.n++] = n_tiles;
+    return c;
 }
 
 // The same over a TABLE (all segments a GPU owns: what both Engines build for a multi-segment table) is ONE launch that stops itself
@@ -571,7 +589,7 @@ static int single_pass_sample(imm3_query *q) {
 
 // ---- the plan query creation makes for a projection ----
 // The SELECT-list entries whose values ride in the records (and in the one launch's): the first mention of each predicate column;
-// every other entry is gathered.  (fill_emit_cols, imm3_api.cpp, lets a later mention of a staged column read the record too: the
+// every other entry is gathered.  (fill_emit_cols, imm3_run.cpp, lets a later mention of a staged column read the record too: the
 // plan counts it as gathered -- one rule for both would change which launches run.)
 static std::vector<bool> proj_rides_in_records(imm3_query *q) {
     std::vector<bool> rides(q->proj.size(), false);
@@ -745,6 +763,13 @@ extern "C" int imm3_plan_limit_scan(int32_t whole, int32_t count_log_on, int32_t
     in.filter_variant = filter_variant;
     in.n_tiles = n_tiles;
     return limit_scan_applies(in) ? 1 : 0;
+}
+
+// diagnostics: the chunk ends of a limit scan over n_tiles tiles (limit_chunk_ends; tests/test_limit_chunks_host.py walks them)
+extern "C" int imm3_plan_limit_chunks(int64_t n_tiles, int64_t *ends_out, int32_t cap) {
+    const LimitChunks c = limit_chunk_ends(n_tiles);
+    for (int i = 0; i < c.n && i < cap && ends_out; ++i) ends_out[i] = c.end[i];
+    return c.n;
 }
 
 // diagnostics: the same for the limit-aware table launch (table_limit_applies; tests/test_table_limit_host.py walks it)

@@ -57,7 +57,7 @@ DIAG_EXPORTS = [
     "imm3_ctx_timing_enable", "imm3_ctx_timing_reset", "imm3_ctx_timing_mask", "imm3_ctx_timing_collect", "imm3_ctx_set_tuning",
     "imm3_ctx_measure_read_gbps", "imm3_ctx_devclock_enable", "imm3_ctx_devclock_collect", "imm3_ctx_devclock_raw", "imm3_query_plan",
     "imm3_ctx_inject_fault", "imm3_ctx_debug_device_lock", "imm3_plan_predict", "imm3_comm_debug_standin", "imm3_plan_limit_scan",
-    "imm3_plan_table_limit", "imm3_plan_string_route",
+    "imm3_plan_table_limit", "imm3_plan_string_route", "imm3_plan_limit_chunks",
     "imm3_query_agg_form", "imm3_query_expr_form", "imm3_expr_normalize",
 ]
 COMM_ID_BYTES = 128
@@ -541,6 +541,16 @@ def plan_table_limit(table=1, tree=0, limit=10, count_in_scan=1, single_tile_pas
     L.imm3_plan_table_limit.argtypes = [C.c_int32, C.c_int32, C.c_int64] + [C.c_int32] * 6 + [C.c_int64, C.c_int32]
     return int(L.imm3_plan_table_limit(table, tree, limit, count_in_scan, single_tile_pass, whole, count_log_on, count_only,
                                        filter_variant, n_tiles, grid))
+
+
+def plan_limit_chunks(n_tiles: int) -> list:
+    """include/imm3_diag.h: imm3_plan_limit_chunks -- the chunk ends (in tiles, ascending, the last one n_tiles) of a limit scan over
+    a segment of n_tiles tiles; a pure function, no device needed."""
+    L = load()
+    L.imm3_plan_limit_chunks.argtypes = [C.c_int64, C.c_void_p, C.c_int32]
+    ends = np.zeros(32, dtype=np.int64)
+    n = int(L.imm3_plan_limit_chunks(n_tiles, ends.ctypes.data, 32))
+    return [int(e) for e in ends[:n]]
 
 
 def plan_string_route(width: int, n_match: int = 1) -> int:

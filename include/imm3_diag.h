@@ -117,6 +117,10 @@ int imm3_expr_normalize(const int32_t *col_codec, const int32_t *col_width, int3
  * no handle: tests walk it. */
 int imm3_plan_limit_scan(int32_t whole, int32_t count_log_on, int32_t count_in_scan, int64_t limit, int32_t single_tile_pass, int32_t table, int32_t records,
                          int32_t skip_bitmap, int32_t overlap_total, int32_t filter_variant, int64_t n_tiles);
+/* imm3_plan_limit_chunks: the chunks such a scan runs as over a segment of n_tiles tiles (csrc/imm3_planner.cpp: limit_chunk_ends,
+ * pure): returns their number (at most 32) and writes the first `cap` chunk ends -- the tile a chunk stops before -- to ends_out,
+ * ascending: 1024, 8192, 32 768, ... (x 4) while below n_tiles, then n_tiles itself.  n_tiles <= 0: no chunk. */
+int imm3_plan_limit_chunks(int64_t n_tiles, int64_t *ends_out, int32_t cap);
 /* imm3_plan_table_limit: does a projection with a `limit` over an imm3_table run its select as the one launch that stops at the limit
  * (1: k_filter_table_limit -- work-groups claim runs of 32 virtual tiles in ascending order and stop claiming once the finished runs
  * have selected `limit` rows) or as the whole select (0)?  csrc/imm3_planner.cpp: table_limit_applies, pure like the decision above.

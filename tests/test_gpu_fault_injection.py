@@ -268,7 +268,7 @@ print("table ok", flush=True)
 
 # ---- 6. a co-resident kernel on the communicator's stream (the G > 1 shape: one launch per pass + one collective per pass).  The
 # stand-in has the footprint of RCCL's all-reduce kernel and cannot share a CU with a work-group of the one-launch projection; while a
-# communicator is attached the projection leaves one CU per XCD free for it (imm3_api.cpp: single_pass_run_grid).  Passes under
+# communicator is attached the projection leaves one CU per XCD free for it (imm3_planner.cpp: single_pass_run_grid).  Passes under
 # it: exact counts on the device, exact rows, no abandoned and no busy run -- with the reservation and (tuning 16) without it.
 import torch
 PASSES = 40

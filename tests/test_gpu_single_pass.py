@@ -635,7 +635,7 @@ def test_survivors_between_the_sample_points(ctx, big):
     n, data, seg = big
     a, b, c, d, s2 = data
     n_full = n // 1024
-    centres = [(2 * i + 1) * n_full // 16 for i in range(8)]          # the sample's chunks: 64 tiles around each (imm3_api.cpp: sample_tile_ptrs)
+    centres = [(2 * i + 1) * n_full // 16 for i in range(8)]          # the sample's chunks: 64 tiles around each (imm3_planner.cpp: sample_tile_ptrs)
     lo_tile, hi_tile = centres[0] + 100, centres[1] - 100
     assert hi_tile - lo_tile > 1000
     lo, hi = lo_tile * 1024 + 7, hi_tile * 1024 - 9

@@ -20,7 +20,7 @@ def test_the_base_case_takes_the_stopping_launch():
     assert call() == 1
     assert call(limit=1) == 1 and call(limit=10 ** 12) == 1
     assert call(filter_variant=12) == 1 and call(filter_variant=15) == 1      # variants that pin other things
-    assert call(grid=1536) == 1                         # (run_select hands in the grid it launches: at most 512 work-groups)
+    assert call(grid=1536) == 1                         # (the tile pass of run_select hands in the grid it launches: at most 512 work-groups)
 
 
 def test_every_veto_keeps_the_whole_select():
