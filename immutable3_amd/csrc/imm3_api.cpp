@@ -1047,8 +1047,10 @@ static int fold_selects(imm3_query *q, const imm3_select *sels, int32_t n_sels) 
     return IMM3_OK;
 }
 
-// Step 3 of a select tree with an OR in it (a segment with batches): its normal form (imm3_expr_norm.cpp) into q->expr_terms; q->preds
-// stays empty.  No term left: the tree selects nothing.
+// Step 3 of a select tree with an OR or a NOT in it (a segment with batches): its normal form (imm3_expr_norm.cpp) into q->expr_terms;
+// q->preds stays empty.  No term left: the tree selects nothing.  The one term without a predicate: it selects EVERY row, and the
+// query is from here on the NoSelect form -- no tree, no predicate, the scan every query without select leaves runs (the tree
+// kernels have no instance without a column).
 static int fold_tree(imm3_query *q, const imm3_select *sels, int32_t n_sels, const int32_t *prog, int32_t n_prog) {
     std::vector<ExprCol> leaf_cols;
     for (int32_t i = 0; i < n_sels; ++i) {
@@ -1058,6 +1060,11 @@ static int fold_tree(imm3_query *q, const imm3_select *sels, int32_t n_sels, con
     }
     const int rc = expr_normalize(leaf_cols, sels, n_sels, prog, n_prog, q->expr_terms);
     if (rc) return rc;
+    if (q->expr_terms.size() == 1 && q->expr_terms[0].empty()) {
+        q->expr_terms.clear();
+        q->expr_universal = true;
+        return IMM3_OK;
+    }
     q->is_expr = true;
     if (q->expr_terms.empty()) q->always_false = true;
     return IMM3_OK;
@@ -1088,7 +1095,7 @@ static int expr_setup(imm3_query *q) {
                 if (p.kind == KIND_STR && p.width != 2)
                     return refuse("string predicates on 2-byte columns only (column width " + n((size_t)p.width) + ")");
                 if (p.kind == KIND_STR && p.match.size() > (size_t)kMaxTileMatch)
-                    return refuse("IN-lists of at most " + n((size_t)kMaxTileMatch) + " values (got " + n(p.match.size()) + ")");
+                    return refuse(std::string(p.negated ? "IN-lists and exclusion lists" : "IN-lists") + " of at most " + n((size_t)kMaxTileMatch) + " values (got " + n(p.match.size()) + ")");
                 if (tile_kind(p) == TK_NONE)
                     return refuse("predicates on int32, int8 and 2-byte string columns only (column " + n((size_t)p.seg_col) + " is none of them)");
                 if (std::find(seen.begin(), seen.end(), p.seg_col) == seen.end()) seen.push_back(p.seg_col);
@@ -1264,16 +1271,16 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
     CTX_LIVE(ctx); // (the context's gate is held until creation returns)
     int rc = check_create_args(ctx, seg, table, used_cols, n_used, sels, n_sels, proj, n_proj);
     if (rc) return rc;
-    // A select tree (imm3_query_create_expr): the leaves have passed the checks of a flat list; now the program.  Without an OR it
-    // IS a flat list -- the leaves in program order go through the steps below exactly as imm3_query_create's do.
+    // A select tree (imm3_query_create_expr): the leaves have passed the checks of a flat list; now the program.  Without an OR and
+    // without a NOT it IS a flat list -- the leaves in program order go through the steps below exactly as imm3_query_create's do.
     // A table's tree (imm3_query_create_table_expr) has ALL its leaves through imm3_query_create_table's checks first, the ones that
     // need the batches (scan_layout) included, and its program checked behind them.
     std::vector<imm3_select> flat;
-    bool has_or = false;
+    bool has_or = false, has_not = false;
     auto check_program = [&]() -> int {
-        const int prc = expr_check_program(prog, n_prog, n_sels, &has_or);
+        const int prc = expr_check_program(prog, n_prog, n_sels, &has_or, &has_not);
         if (prc) return prc;
-        if (!has_or) {
+        if (!has_or && !has_not) {
             for (int32_t i = 0; i < n_prog; ++i)
                 if (prog[i] >= 0) flat.push_back(sels[prog[i]]);
             sels = flat.data();
@@ -1298,7 +1305,7 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
     int32_t nb = 0;
     rc = scan_layout(q.get(), sels, n_sels, nb); if (rc) return rc;
     if (tree && table) { rc = check_program(); if (rc) return rc; }
-    if (nb >= 1 && has_or) { rc = fold_tree(q.get(), sels, n_sels, prog, n_prog); if (rc) return rc; }
+    if (nb >= 1 && (has_or || has_not)) { rc = fold_tree(q.get(), sels, n_sels, prog, n_prog); if (rc) return rc; }
     else if (nb >= 1) { rc = fold_selects(q.get(), sels, n_sels); if (rc) return rc; }
     rc = place_compressed(q.get(), nb >= 1, row_cols); if (rc) return rc;
     if (table) // (a flat select list; a tree's terms are checked by expr_setup)

@@ -78,7 +78,7 @@ typedef std::vector<FoldedPred> ExprTerm;             // a conjunction: at most 
 int leaf_pred(int32_t seg_col, int32_t vcodec, int32_t width, const imm3_select &leaf, FoldedPred &out); // one leaf alone
 void merge_pred(FoldedPred &into, const FoldedPred &other);                                             // ... AND another on the same column
 bool pred_empty(const FoldedPred &p);                                                                    // no value passes
-int expr_check_program(const int32_t *prog, int32_t n_prog, int32_t n_leaves, bool *has_or);             // IMM3_ERR_ARG: malformed
+int expr_check_program(const int32_t *prog, int32_t n_prog, int32_t n_leaves, bool *has_or, bool *has_not); // IMM3_ERR_ARG: malformed; the out-flags (may be null): an IMM3_EXPR_OR / an IMM3_EXPR_NOT in it
 int expr_normalize(const std::vector<ExprCol> &leaf_cols, const imm3_select *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog,
                    std::vector<ExprTerm> &terms);
 

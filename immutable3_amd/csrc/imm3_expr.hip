@@ -1,4 +1,4 @@
-// imm3_expr.hip -- the scan+select kernels of a select TREE (AND / OR over SelectOp leaves), gfx950, wave64.
+// imm3_expr.hip -- the scan+select kernels of a select TREE (AND / OR / NOT over SelectOp leaves), gfx950, wave64.
 //
 // The reference's PipelineThread.runOps applies every SelectOp of a SelectADT one after the other whatever the node's tag says
 // (engine/Engine.scala:236-245, "TODO: use AND/OR operators"): every tree is a conjunction there, and so it is through
@@ -16,6 +16,8 @@
 //                               DPP assembly of the bitmap word.
 //                               Its TABLE instances walk an imm3_table's tile table as k_filter_tile's do (one tile per step, the
 //                               partial tile that ends each segment rolled): the select tree over ALL segments is one launch.
+//                               A term's string predicate may be a NEGATED list (a complemented Match under IMM3_EXPR_NOT): the
+//                               flag travels with the list and turns the match around where it is taken, inside every bounds check.
 //   k_filter_expr_generic       any column kind, any layout, up to 64 terms: one row per lane, one bitmap word per wave and step,
 //                               the terms' ColPreds read from device memory.  One segment only.
 #include "imm3_internal.h"
@@ -40,16 +42,50 @@ __device__ __forceinline__ void expr_load(ColRegs<K> &c, const void *data, int64
     else c.load(data, row0, lane);
 }
 
+// A string predicate of a tree may be NEGATED (a complemented Match: TileCol::negated, wave-uniform, read from the kernel arguments
+// with the list): keep the rows that equal NONE of the values.  Only a 2-byte string column has a list, and only the NEG instances
+// of the kernels look at the flag: the host launches them for a tree that carries a negated list (launch_filter_expr) and the
+// plain instances for every other tree, which therefore run the code they ran before NOT existed -- the test of the flag inside the
+// term loops of ONE instance cost the trees without NOT 3 - 13 % (more SGPR spills around the row-strided kinds' 32 word pairs).
+// Within a NEG instance the flag is one scalar test per term and string column.
+// in-lane: the term's 16-bit match mask XORed with the lane's all-rows mask (full tiles only: every one of the 16 rows exists)
+template <bool NEG, int K>
+__device__ __forceinline__ uint32_t expr_col_lane_mask(const ColRegs<K> &c, const TileCol &col) {
+    uint32_t m = c.lane_mask(col);
+    if constexpr (NEG && K == TK_S2) {
+        if (col.negated) m ^= 0xFFFFu;
+    }
+    return m;
+}
+// row-strided: the ballot of "not matched"
+template <bool NEG, int K>
+__device__ __forceinline__ void expr_col_test(ColRegs<K> &c, const TileCol &col, uint64_t (&ta)[kTileWords]) {
+    if constexpr (NEG && K == TK_S2) {
+        if (col.negated) {
+            c.test_not(col, ta);
+            return;
+        }
+    }
+    c.test(col, ta);
+}
+// one row of the rolled partial tile (the caller has it inside its bounds check: a row that does not exist is never evaluated as "not matched")
+template <bool NEG, int K>
+__device__ __forceinline__ bool expr_col_row(ColRegs<K> &c, const void *data, const TileCol &col, int64_t r) {
+    const bool hit = c.row(data, col, r);
+    if constexpr (NEG && K == TK_S2) return hit != (col.negated != 0);
+    else return hit;
+}
+
 // the in-lane kinds: OR over the terms of the AND of the constrained columns' masks (wave-uniform control flow: `use` is scalar)
-template <int K0, int K1, int K2>
+template <int K0, int K1, int K2, bool NEG>
 __device__ __forceinline__ uint32_t expr_lane_mask(const ExprTermArgs &a, const ColRegs<K0> &c0, const ColRegs<K1> &c1, const ColRegs<K2> &c2) {
     uint32_t m = 0;
     for (int t = 0; t < a.n_terms; ++t) {
         const uint32_t u = a.use[t];
         uint32_t tm = 0xFFFFu;
-        if (K0 != TK_NONE && (u & 1u)) tm &= c0.lane_mask(a.cols[t][0]);
-        if (K1 != TK_NONE && (u & 2u)) tm &= c1.lane_mask(a.cols[t][1]);
-        if (K2 != TK_NONE && (u & 4u)) tm &= c2.lane_mask(a.cols[t][2]);
+        if (K0 != TK_NONE && (u & 1u)) tm &= expr_col_lane_mask<NEG>(c0, a.cols[t][0]);
+        if (K1 != TK_NONE && (u & 2u)) tm &= expr_col_lane_mask<NEG>(c1, a.cols[t][1]);
+        if (K2 != TK_NONE && (u & 4u)) tm &= expr_col_lane_mask<NEG>(c2, a.cols[t][2]);
         m |= tm;
     }
     return m;
@@ -57,11 +93,11 @@ __device__ __forceinline__ uint32_t expr_lane_mask(const ExprTermArgs &a, const 
 
 // One full tile whose columns are in registers -> its bitmap line (unless count-only); returns the lane's share of the survivors
 // (whichever lanes count: every lane, the word owners, or lane 0 -- the caller sums over the wave).
-template <int K0, int K1, int K2>
+template <int K0, int K1, int K2, bool NEG>
 __device__ __forceinline__ uint32_t expr_full_tile(const ExprTermArgs &a, int64_t tile, int lane, ColRegs<K0> &c0, ColRegs<K1> &c1, ColRegs<K2> &c2, uint8_t *xp) {
     constexpr int kLane = expr_lane_tile(K0, K1, K2);
     if constexpr (kLane == 2) {
-        const uint32_t m = expr_lane_mask<K0, K1, K2>(a, c0, c1, c2); // byte 0: rows 8 lane .. + 7, byte 1: 512 + 8 lane .. + 7
+        const uint32_t m = expr_lane_mask<K0, K1, K2, NEG>(a, c0, c1, c2); // byte 0: rows 8 lane .. + 7, byte 1: 512 + 8 lane .. + 7
         if (!a.bitmap) return (uint32_t)__popc(m);
         // eight lanes' bytes -> one word, for both runs at once (k_filter_tile's assembly: pairs, quads, then the upper quad's half)
         const uint32_t odd = (uint32_t)__builtin_amdgcn_mov_dpp((int)m, 0xF5, 0xF, 0xF, true);      // quad_perm [1,1,3,3]
@@ -80,7 +116,7 @@ __device__ __forceinline__ uint32_t expr_full_tile(const ExprTermArgs &a, int64_
         }
         return (uint32_t)(__popcll(word_a) + __popcll(word_b));
     } else if constexpr (kLane == 1) {
-        const uint32_t m = expr_lane_mask<K0, K1, K2>(a, c0, c1, c2); // rows 16 lane .. 16 lane + 15
+        const uint32_t m = expr_lane_mask<K0, K1, K2, NEG>(a, c0, c1, c2); // rows 16 lane .. 16 lane + 15
         if (!a.bitmap) return (uint32_t)__popc(m);
         const uint32_t odd = (uint32_t)__builtin_amdgcn_mov_dpp((int)m, 0xF5, 0xF, 0xF, true);       // quad_perm [1,1,3,3]
         const uint32_t pair = m | (odd << 16);
@@ -103,9 +139,9 @@ __device__ __forceinline__ uint32_t expr_full_tile(const ExprTermArgs &a, int64_
             uint64_t ta[kTileWords];
 #pragma unroll
             for (int j = 0; j < kTileWords; ++j) ta[j] = ~0ULL;
-            if (K0 != TK_NONE && (u & 1u)) c0.test(a.cols[t][0], ta);
-            if (K1 != TK_NONE && (u & 2u)) c1.test(a.cols[t][1], ta);
-            if (K2 != TK_NONE && (u & 4u)) c2.test(a.cols[t][2], ta);
+            if (K0 != TK_NONE && (u & 1u)) expr_col_test<NEG>(c0, a.cols[t][0], ta);
+            if (K1 != TK_NONE && (u & 2u)) expr_col_test<NEG>(c1, a.cols[t][1], ta);
+            if (K2 != TK_NONE && (u & 4u)) expr_col_test<NEG>(c2, a.cols[t][2], ta);
 #pragma unroll
             for (int j = 0; j < kTileWords; ++j) acc[j] |= ta[j];
         }
@@ -124,7 +160,7 @@ __device__ __forceinline__ uint32_t expr_full_tile(const ExprTermArgs &a, int64_
 
 // A tile with fewer than 1024 valid rows (the end of a segment): rolled, bounds-checked, row-at-a-time.
 // `valid_rows` rows starting at element `row0` of each column pointer.
-template <int K0, int K1, int K2>
+template <int K0, int K1, int K2, bool NEG>
 __device__ __forceinline__ uint32_t expr_partial_tile(const ExprTermArgs &a, int64_t tile, int lane, const void *d0, const void *d1, const void *d2, int64_t row0,
                                                       int64_t valid_rows, ColRegs<K0> &c0, ColRegs<K1> &c1, ColRegs<K2> &c2) {
     const int64_t w = tile * kTileWords + lane;
@@ -137,10 +173,10 @@ __device__ __forceinline__ uint32_t expr_partial_tile(const ExprTermArgs &a, int
         bool keep = false;
         for (int t = 0; t < a.n_terms; ++t) {
             const uint32_t u = a.use[t];
-            bool k = valid;
-            if (K0 != TK_NONE && (u & 1u)) k = k && c0.row(d0, a.cols[t][0], r);
-            if (K1 != TK_NONE && (u & 2u)) k = k && c1.row(d1, a.cols[t][1], r);
-            if (K2 != TK_NONE && (u & 4u)) k = k && c2.row(d2, a.cols[t][2], r);
+            bool k = valid; // (the bounds check FIRST: a negated list keeps "no match", and a row past valid_rows matches nothing)
+            if (K0 != TK_NONE && (u & 1u)) k = k && expr_col_row<NEG>(c0, d0, a.cols[t][0], r);
+            if (K1 != TK_NONE && (u & 2u)) k = k && expr_col_row<NEG>(c1, d1, a.cols[t][1], r);
+            if (K2 != TK_NONE && (u & 4u)) k = k && expr_col_row<NEG>(c2, d2, a.cols[t][2], r);
             keep = keep || k;
         }
         const uint64_t m = ballot64(keep);
@@ -156,7 +192,8 @@ __device__ __forceinline__ uint32_t expr_partial_tile(const ExprTermArgs &a, int
 // the same values as k_filter_tile's instances.
 // TABLE selects the tile-table walk (table queries) at compile time, as in k_filter_tile: the single-segment kernel carries none of
 // it, not even the tile table's words in its argument block (ExprTermArgs, imm3_internal.h).
-template <int K0, int K1, int K2, int T, bool TABLE>
+// NEG: the instance that honours TileCol::negated (only kinds with a 2-byte string column have one)
+template <int K0, int K1, int K2, int T, bool TABLE, bool NEG = false>
 __global__ __launch_bounds__(kBlockThreads) void k_filter_expr(const std::conditional_t<TABLE, ExprTileArgs, ExprTermArgs> a) {
     constexpr int kLane = expr_lane_tile(K0, K1, K2);
     constexpr bool kXpose = kLane == 0 && (K0 == TK_I8 || K0 == TK_S2 || K1 == TK_I8 || K1 == TK_S2 || K2 == TK_I8 || K2 == TK_S2);
@@ -186,9 +223,9 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_expr(const std::condit
                 expr_load<kLane>(c0, t0, 0, lane);
                 expr_load<kLane>(c1, t1, 0, lane);
                 expr_load<kLane>(c2, t2, 0, lane);
-                lane_total += expr_full_tile<K0, K1, K2>(a, tile, lane, c0, c1, c2, xp);
+                lane_total += expr_full_tile<K0, K1, K2, NEG>(a, tile, lane, c0, c1, c2, xp);
             } else {
-                lane_total += expr_partial_tile<K0, K1, K2>(a, tile, lane, t0, t1, t2, 0, rows_here, c0, c1, c2);
+                lane_total += expr_partial_tile<K0, K1, K2, NEG>(a, tile, lane, t0, t1, t2, 0, rows_here, c0, c1, c2);
             }
         }
 #pragma unroll
@@ -232,7 +269,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_expr(const std::condit
             load_group(c0, c1, c2, grp);
         }
 #pragma unroll
-        for (int t = 0; t < T; ++t) lane_total += expr_full_tile<K0, K1, K2>(a, grp * T + t, lane, c0[t], c1[t], c2[t], xp);
+        for (int t = 0; t < T; ++t) lane_total += expr_full_tile<K0, K1, K2, NEG>(a, grp * T + t, lane, c0[t], c1[t], c2[t], xp);
     }
     // leftovers: fewer than T full tiles, then the one partial tile at the end of the segment
     for (int64_t tile = n_groups * T + wave_id; tile < a.n_tiles; tile += n_waves) {
@@ -244,9 +281,9 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_expr(const std::condit
             expr_load<kLane>(c0, d0, row0, lane);
             expr_load<kLane>(c1, d1, row0, lane);
             expr_load<kLane>(c2, d2, row0, lane);
-            lane_total += expr_full_tile<K0, K1, K2>(a, tile, lane, c0, c1, c2, xp);
+            lane_total += expr_full_tile<K0, K1, K2, NEG>(a, tile, lane, c0, c1, c2, xp);
         } else {
-            lane_total += expr_partial_tile<K0, K1, K2>(a, tile, lane, d0, d1, d2, row0, a.n_rows - row0, c0, c1, c2);
+            lane_total += expr_partial_tile<K0, K1, K2, NEG>(a, tile, lane, d0, d1, d2, row0, a.n_rows - row0, c0, c1, c2);
         }
     }
 #pragma unroll
@@ -259,6 +296,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_expr(const std::condit
 // ---------------------------------------------------------------------------------------------
 // k_filter_expr_generic: k_filter_generic's walk (uniform or ragged layout, one bitmap word per wave and step) over the terms.
 // ---------------------------------------------------------------------------------------------
+template <bool NEG> // NEG: the instance that honours ColPred::negated (launched for a tree that carries a negated list)
 __global__ __launch_bounds__(kBlockThreads) void k_filter_expr_generic(const ExprGenericArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -279,7 +317,12 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_expr_generic(const Exp
         uint64_t acc = 0ULL;
         for (int t = 0; t < a.n_terms; ++t) {
             uint64_t ta = ~0ULL;
-            for (int p = a.term_start[t]; p < a.term_start[t + 1] && ta; ++p) ta &= ballot64(valid && eval_row(a.preds[p], row)); // (wave-uniform exit: no row of the word is left in the term)
+            // (wave-uniform exit: no row of the word is left in the term.  A NEGATED list -- ColPred::negated, set on string predicates
+            // only -- keeps the rows that match none of its values, INSIDE the bounds check: a lane past word_nvalid sets no bit)
+            for (int p = a.term_start[t]; p < a.term_start[t + 1] && ta; ++p) {
+                if constexpr (NEG) ta &= ballot64(valid && (eval_row(a.preds[p], row) != (a.preds[p].negated != 0)));
+                else ta &= ballot64(valid && eval_row(a.preds[p], row));
+            }
             acc |= ta;
         }
         acc &= low_mask(nv);
@@ -291,13 +334,17 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_expr_generic(const Exp
 
 #define IMM3_EXPR_CASE(k0, k1, k2, T)                                                                  \
     if (a.kinds[0] == k0 && a.kinds[1] == k1 && a.kinds[2] == k2) {                                    \
-        IMM3_LAUNCH((k_filter_expr<k0, k1, k2, T, false>), grid, kBlockThreads, s, ev0, ev1, seg);     \
+        constexpr bool has_s2 = k0 == TK_S2 || k1 == TK_S2 || k2 == TK_S2;                             \
+        if (has_s2 && neg) IMM3_LAUNCH((k_filter_expr<k0, k1, k2, T, false, has_s2>), grid, kBlockThreads, s, ev0, ev1, seg); \
+        else IMM3_LAUNCH((k_filter_expr<k0, k1, k2, T, false>), grid, kBlockThreads, s, ev0, ev1, seg); \
         return true;                                                                                   \
     }
 // the table instances: one tile per step whatever the kinds
 #define IMM3_EXPR_TABLE_CASE(k0, k1, k2, T)                                                            \
     if (a.kinds[0] == k0 && a.kinds[1] == k1 && a.kinds[2] == k2) {                                    \
-        IMM3_LAUNCH((k_filter_expr<k0, k1, k2, 1, true>), grid, kBlockThreads, s, ev0, ev1, a);        \
+        constexpr bool has_s2 = k0 == TK_S2 || k1 == TK_S2 || k2 == TK_S2;                             \
+        if (has_s2 && neg) IMM3_LAUNCH((k_filter_expr<k0, k1, k2, 1, true, has_s2>), grid, kBlockThreads, s, ev0, ev1, a); \
+        else IMM3_LAUNCH((k_filter_expr<k0, k1, k2, 1, true>), grid, kBlockThreads, s, ev0, ev1, a);   \
         return true;                                                                                   \
     }
 // k_filter_tile's column-kind combinations (and tiles per iteration), except the one without any column: a tree has leaves
@@ -309,6 +356,9 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_expr_generic(const Exp
     X(TK_I8, TK_I8, TK_I8, 2) X(TK_I32, TK_I32, TK_S2, 1) X(TK_I32, TK_I8, TK_S2, 1) X(TK_I8, TK_I8, TK_S2, 1)
 
 bool launch_filter_expr(const ExprTileArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    bool neg = false; // a negated list among the terms' predicates: the NEG instance
+    for (int t = 0; t < a.n_terms; ++t)
+        for (int k = 0; k < kMaxTileCols; ++k) neg = neg || ((a.use[t] >> k & 1u) && a.cols[t][k].negated);
     if (a.tile_rows) { // a table query: the tile table replaces cols[..].data / n_rows
         IMM3_EXPR_KINDS(IMM3_EXPR_TABLE_CASE)
         return false;
@@ -318,8 +368,9 @@ bool launch_filter_expr(const ExprTileArgs &a, int grid, hipStream_t s, hipEvent
     return false;
 }
 
-void launch_filter_expr_generic(const ExprGenericArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    IMM3_LAUNCH(k_filter_expr_generic, grid, kBlockThreads, s, ev0, ev1, a);
+void launch_filter_expr_generic(const ExprGenericArgs &a, bool negated, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    if (negated) IMM3_LAUNCH(k_filter_expr_generic<true>, grid, kBlockThreads, s, ev0, ev1, a);
+    else IMM3_LAUNCH(k_filter_expr_generic<false>, grid, kBlockThreads, s, ev0, ev1, a);
 }
 
 } // namespace imm3

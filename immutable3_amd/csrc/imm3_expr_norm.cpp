@@ -1,6 +1,7 @@
 // imm3_expr_norm.cpp -- select trees on the host: one leaf as a folded predicate, the postfix program's checks, and the normal form
 // the kernels of imm3_expr.hip evaluate -- a disjunction of TERMS, each a conjunction with at most one folded predicate per column
-// (one closed interval, or one intersected IN-list: what fold_selects makes of a flat select list).  No device is touched here.
+// (one closed interval, or one intersected IN-list: what fold_selects makes of a flat select list; under an IMM3_EXPR_NOT also a
+// NEGATED IN-list, the exclusions of a complemented Match).  No device is touched here.
 #include "../../include/imm3.h"
 #include "../../include/imm3_diag.h"
 #include "imm3_handles.h"
@@ -39,23 +40,42 @@ int leaf_pred(int32_t seg_col, int32_t vcodec, int32_t width, const imm3_select 
     return IMM3_OK;
 }
 
-// the conjunction of two predicates on the same column: intervals intersect, IN-lists intersect (the first one's order stays)
+// the conjunction of two predicates on the same column: intervals intersect, IN-lists intersect (the first one's order stays);
+// IN and NOT-IN: the IN-list minus the exclusions (still an IN-list, maybe empty); NOT-IN and NOT-IN: the union of the exclusions,
+// first seen first
 void merge_pred(FoldedPred &into, const FoldedPred &other) {
     if (into.kind == KIND_STR) {
-        std::vector<std::string> both;
-        for (auto &v : into.match)
-            if (std::find(other.match.begin(), other.match.end(), v) != other.match.end()) both.push_back(v);
-        into.match = both;
+        const auto has = [](const std::vector<std::string> &l, const std::string &v) { return std::find(l.begin(), l.end(), v) != l.end(); };
+        if (into.negated && other.negated) {
+            for (auto &v : other.match)
+                if (!has(into.match, v)) into.match.push_back(v);
+            return;
+        }
+        const std::vector<std::string> &in = into.negated ? other.match : into.match, &cut = into.negated ? into.match : other.match;
+        const bool keep_common = !into.negated && !other.negated; // IN and IN: what both hold; else: what the exclusions leave
+        std::vector<std::string> left;
+        for (auto &v : in)
+            if (has(cut, v) == keep_common) left.push_back(v);
+        into.match = left;
+        into.negated = false;
     } else {
         into.lo = std::max(into.lo, other.lo);
         into.hi = std::min(into.hi, other.hi);
     }
 }
 
-bool pred_empty(const FoldedPred &p) { return p.kind == KIND_STR ? p.match.empty() : p.lo > p.hi; }
+bool pred_empty(const FoldedPred &p) { return p.kind == KIND_STR ? (!p.negated && p.match.empty()) : p.lo > p.hi; } // (a NOT-IN is never empty)
 
-int expr_check_program(const int32_t *prog, int32_t n_prog, int32_t n_leaves, bool *has_or) {
+// every value passes: the column type's full interval, or a NOT-IN without exclusions (only a complement makes one)
+bool pred_unconstrained(const FoldedPred &p) {
+    if (p.kind == KIND_STR) return p.negated && p.match.empty();
+    const FoldedPred full = unfolded_pred(p.seg_col, p.kind == KIND_I32 ? IMM3_DENSE_INT : IMM3_DENSE_TINYINT, p.width);
+    return p.lo <= full.lo && p.hi >= full.hi;
+}
+
+int expr_check_program(const int32_t *prog, int32_t n_prog, int32_t n_leaves, bool *has_or, bool *has_not) {
     if (has_or) *has_or = false;
+    if (has_not) *has_not = false;
     if (n_prog < 0 || (n_prog > 0 && !prog)) return fail(IMM3_ERR_ARG, "bad select program");
     if (n_prog == 0) return n_leaves == 0 ? IMM3_OK : fail(IMM3_ERR_ARG, "select program: empty, but leaves were given");
     int64_t depth = 0;
@@ -68,6 +88,9 @@ int expr_check_program(const int32_t *prog, int32_t n_prog, int32_t n_leaves, bo
             if (depth < 2) return fail(IMM3_ERR_ARG, "select program: stack underflow");
             --depth;
             if (op == IMM3_EXPR_OR && has_or) *has_or = true;
+        } else if (op == IMM3_EXPR_NOT) {
+            if (depth < 1) return fail(IMM3_ERR_ARG, "select program: stack underflow");
+            if (has_not) *has_not = true;
         } else return fail(IMM3_ERR_ARG, "select program: unknown operator");
     }
     if (depth != 1) return fail(IMM3_ERR_ARG, "select program: more than one result");
@@ -78,7 +101,7 @@ namespace {
 bool same_pred(const FoldedPred &a, const FoldedPred &b) {
     if (a.seg_col != b.seg_col) return false;
     if (a.kind != KIND_STR) return a.lo == b.lo && a.hi == b.hi;
-    if (a.match.size() != b.match.size()) return false;
+    if (a.negated != b.negated || a.match.size() != b.match.size()) return false;
     for (auto &v : a.match)
         if (std::find(b.match.begin(), b.match.end(), v) == b.match.end()) return false;
     return true;
@@ -92,37 +115,134 @@ bool same_term(const ExprTerm &a, const ExprTerm &b) {
     }
     return true;
 }
-void add_term(std::vector<ExprTerm> &dnf, const ExprTerm &t) {
+// The disjunction of two predicates on one column as ONE predicate, where a complement makes that possible: intervals that overlap
+// or touch, and a string list with a NOT-IN (IN or NOT-IN: the exclusions the IN-list does not give back; NOT-IN or NOT-IN: the
+// exclusions both hold).  Two IN-lists stay two terms, as in a tree without NOT.
+bool union_pred(const FoldedPred &a, const FoldedPred &b, FoldedPred &out) {
+    out = a;
+    if (a.kind != KIND_STR) {
+        if (a.lo > b.hi + 1 || b.lo > a.hi + 1) return false;
+        out.lo = std::min(a.lo, b.lo);
+        out.hi = std::max(a.hi, b.hi);
+        return true;
+    }
+    if (!a.negated && !b.negated) return false;
+    const FoldedPred &neg = a.negated ? a : b, &other = a.negated ? b : a;
+    out = neg;
+    out.match.clear();
+    for (auto &v : neg.match) {
+        const bool in_other = std::find(other.match.begin(), other.match.end(), v) != other.match.end();
+        if (in_other == other.negated) out.match.push_back(v); // still excluded: by both NOT-INs / not given back by the IN-list
+    }
+    return true;
+}
+// `complemented` (the tree holds a negation that did not cancel): the result sheds predicates every value passes -- a term without
+// any is UNIVERSAL and absorbs all others -- and a term that differs from one already there in ONE column, where the two predicates
+// are one (union_pred), replaces it: `x or not x` comes out as the universal term, not as two halves.  A tree without NOT never
+// holds such a predicate and keeps its terms exactly as they were before NOT existed.
+void add_term(std::vector<ExprTerm> &dnf, ExprTerm t, bool complemented) {
     for (const auto &p : t)
         if (pred_empty(p)) return; // selects nothing
+    if (complemented) {
+        if (dnf.size() == 1 && dnf[0].empty()) return; // (universal already)
+        t.erase(std::remove_if(t.begin(), t.end(), pred_unconstrained), t.end());
+        if (t.empty()) {
+            dnf.assign(1, t);
+            return;
+        }
+        for (size_t h = 0; h < dnf.size(); ++h) {
+            const ExprTerm &have = dnf[h];
+            if (have.size() != t.size()) continue;
+            const FoldedPred *mine = nullptr, *theirs = nullptr;
+            int differ = 0;
+            for (const auto &p : t) {
+                const FoldedPred *r = nullptr;
+                for (const auto &c : have)
+                    if (c.seg_col == p.seg_col) r = &c;
+                if (!r) { differ = 2; break; }
+                if (!same_pred(p, *r)) { ++differ; mine = &p; theirs = r; }
+            }
+            FoldedPred u;
+            if (differ != 1 || !union_pred(*theirs, *mine, u)) continue;
+            ExprTerm merged;
+            for (const auto &c : have) merged.push_back(c.seg_col == u.seg_col ? u : c);
+            dnf.erase(dnf.begin() + (std::ptrdiff_t)h);
+            add_term(dnf, merged, true); // (it may now meet a third term the same way)
+            return;
+        }
+    }
     for (const auto &have : dnf)
         if (same_term(have, t)) return;
     dnf.push_back(t);
 }
 constexpr size_t kMaxWorkTerms = 4096; // terms of an intermediate result (the final bound is the kernels': kMaxExprGenericTerms)
+
+// The complement of one leaf as terms, in int64 so nothing overflows at the type's ends: NOT GT t = [MIN, t], NOT LT t = [t, MAX],
+// NOT EQ t = [MIN, t - 1] or [t + 1, MAX] (an empty piece dropped), NOT Match = the NEGATED IN-list of the values of the column's
+// width (the others never matched: they are no exclusions either).
+void complement_leaf(const FoldedPred &full, const FoldedPred &leaf, int32_t cond, std::vector<ExprTerm> &dnf) {
+    FoldedPred c = full;
+    if (leaf.kind == KIND_STR) {
+        c.match = leaf.match;
+        c.negated = true;
+        add_term(dnf, ExprTerm{c}, true);
+        return;
+    }
+    if (cond == IMM3_GT) c.hi = leaf.lo - 1;        // leaf: [t + 1, MAX]
+    else if (cond == IMM3_LT) c.lo = leaf.hi + 1;   // leaf: [MIN, t - 1]
+    else {                                          // leaf: [t, t]
+        FoldedPred below = full;
+        below.hi = leaf.lo - 1;
+        add_term(dnf, ExprTerm{below}, true);
+        c.lo = leaf.lo + 1;
+    }
+    add_term(dnf, ExprTerm{c}, true);
+}
 } // namespace
 
-// The tree as a disjunction of terms.  AND distributes over OR (every pair of terms, merged per column), terms that select nothing
-// and duplicates are dropped; no term left = the tree selects nothing.  A term keeps its columns in the order the program first
-// names them: a tree without OR gives the one term whose predicates are fold_selects' of the same leaves in program order.
+// The tree as a disjunction of terms.  IMM3_EXPR_NOT is pushed down to the leaves first (De Morgan over AND / OR, a double NOT
+// cancels): one walk over the program from its end tells every leaf whether it stands complemented and every AND / OR whether it
+// trades places with the other.  Then AND distributes over OR (every pair of terms, merged per column), terms that select nothing
+// and duplicates are dropped; no term left = the tree selects nothing, the one term without a predicate = it selects every row.
+// A term keeps its columns in the order the program first names them: a tree without OR and NOT gives the one term whose predicates
+// are fold_selects' of the same leaves in program order.
 int expr_normalize(const std::vector<ExprCol> &leaf_cols, const imm3_select *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog,
                    std::vector<ExprTerm> &terms) {
     terms.clear();
-    const int crc = expr_check_program(prog, n_prog, n_leaves, nullptr);
+    const int crc = expr_check_program(prog, n_prog, n_leaves, nullptr, nullptr);
     if (crc) return crc;
+    std::vector<uint8_t> flipped((size_t)n_prog, 0); // leaf: complemented; AND / OR: the other one
+    bool complemented = false;
+    {
+        std::vector<uint8_t> pending(1, 0); // the parity each subtree still to come (walking backwards) stands under
+        for (int32_t i = n_prog - 1; i >= 0; --i) {
+            const uint8_t par = pending.back();
+            pending.pop_back();
+            const int32_t op = prog[i];
+            if (op == IMM3_EXPR_NOT) pending.push_back(par ^ 1);
+            else {
+                flipped[(size_t)i] = par;
+                complemented = complemented || par;
+                if (op < 0) pending.insert(pending.end(), 2, par);
+            }
+        }
+    }
     std::vector<std::vector<ExprTerm>> stack;
     for (int32_t i = 0; i < n_prog; ++i) {
-        const int32_t op = prog[i];
+        int32_t op = prog[i];
+        if (op == IMM3_EXPR_NOT) continue; // (it has reached its leaves)
         if (op >= 0) {
             const ExprCol &c = leaf_cols[(size_t)op];
             FoldedPred fp;
             const int lrc = leaf_pred(c.seg_col, c.vcodec, c.width, leaves[op], fp);
             if (lrc) return lrc;
             std::vector<ExprTerm> dnf;
-            add_term(dnf, ExprTerm{fp});
+            if (flipped[(size_t)i]) complement_leaf(unfolded_pred(c.seg_col, c.vcodec, c.width), fp, leaves[op].cond, dnf);
+            else add_term(dnf, ExprTerm{fp}, complemented);
             stack.push_back(std::move(dnf));
             continue;
         }
+        if (flipped[(size_t)i]) op = op == IMM3_EXPR_OR ? IMM3_EXPR_AND : IMM3_EXPR_OR;
         std::vector<ExprTerm> b = std::move(stack.back());
         stack.pop_back();
         std::vector<ExprTerm> a = std::move(stack.back());
@@ -130,7 +250,7 @@ int expr_normalize(const std::vector<ExprCol> &leaf_cols, const imm3_select *lea
         std::vector<ExprTerm> r;
         if (op == IMM3_EXPR_OR) {
             r = std::move(a);
-            for (const auto &t : b) add_term(r, t);
+            for (const auto &t : b) add_term(r, t, complemented);
         } else {
             for (const auto &x : a)
                 for (const auto &y : b) {
@@ -140,7 +260,7 @@ int expr_normalize(const std::vector<ExprCol> &leaf_cols, const imm3_select *lea
                         if (mine) merge_pred(*mine, p);
                         else t.push_back(p);
                     }
-                    add_term(r, t);
+                    add_term(r, t, complemented);
                     if (r.size() > kMaxWorkTerms) return fail(IMM3_ERR_ARG, "select tree: too many terms");
                 }
         }
@@ -184,7 +304,7 @@ extern "C" int imm3_expr_normalize(const int32_t *col_codec, const int32_t *col_
             js += k ? ",{" : "{";
             js += "\"col\":" + std::to_string(p.seg_col);
             if (p.kind == KIND_STR) {
-                js += ",\"match\":[";
+                js += p.negated ? ",\"not_match\":[" : ",\"match\":[";
                 for (size_t m = 0; m < p.match.size(); ++m) {
                     js += m ? ",\"" : "\"";
                     char hex[3];

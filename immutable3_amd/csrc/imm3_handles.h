@@ -241,6 +241,7 @@ struct FoldedPred { // all SelectOp leaves on one segment column, folded
     int32_t kind = 0, width = 0;
     int64_t lo = 0, hi = 0;                // numeric closed interval
     std::vector<std::string> match;        // string: surviving IN-list values (each exactly width bytes)
+    bool negated = false;                  // string, select trees only: `match` are EXCLUSIONS -- every value but these passes (a complemented Match)
     uint8_t *d_blob = nullptr;             // device copy when it does not fit the kernel arguments
     bool pfor = false;                     // PFOR_INT column evaluated on its compressed blocks (k_filter_pfor)
 };
@@ -347,7 +348,7 @@ struct imm3_query {
     unsigned long long *d_desc = nullptr;   // per-span descriptors of the chained scan
     size_t sp_trash_off = 0;                // byte offset of the writers' trash lines in d_desc's allocation
     imm3::ProjectTile *d_tile_desc = nullptr; // table queries: one descriptor per tile of the table for the launch's columns (k_filter_project's TABLE instances)
-    // select tree (imm3_query_create_expr / _table_expr, an OR in it): the selection is the OR of these terms, ONE launch of imm3_expr.hip's
+    // select tree (imm3_query_create_expr / _table_expr, an OR or a NOT in it): the selection is the OR of these terms, ONE launch of imm3_expr.hip's
     // tile or generic kernel (a table: the tile kernel's TABLE instance, or the query is refused); q->preds stays empty, the projection takes the bitmap path and an aggregation reads the bitmap
     bool is_expr = false;
     std::vector<std::vector<FoldedPred>> expr_terms;
@@ -359,6 +360,7 @@ struct imm3_query {
     imm3::ColPred *d_expr_preds = nullptr;
     int32_t *d_expr_term_start = nullptr;
     int32_t expr_form_ran = -1;             // diagnostics (imm3_query_expr_form): 0 = tile, 1 = generic, -1 before any launch
+    bool expr_universal = false;            // the tree's normal form is the one term without a predicate: every row -- the query is the NoSelect form (is_expr stays false)
     bool count_log_on = false;              // imm3_query_log_counts is installed: every run logs the segment's count (a limit query then scans whole)
     uint32_t sp_abandoned_runs = 0, sp_busy_runs = 0; // single-pass runs whose rows were gathered from the bitmap instead: a prefix never came / the device was busy (imm3_query_plan)
 };

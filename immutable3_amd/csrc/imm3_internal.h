@@ -46,6 +46,8 @@ struct ColPred {
     int32_t lo, hi;              // numeric closed interval (int8 values sign-extended)
     int32_t n_match;             // string: IN-list size
     int32_t match_in_args;       // 1: width <= 8 and n_match <= kMaxMatch -> values packed in match[]
+    int32_t negated;             // string, select trees only (k_filter_expr_generic): 1 = keep the rows that equal NONE of the values
+    int32_t pad;
     uint64_t match[kMaxMatch];   // value bytes packed little-endian (byte 0 = first character)
     const uint8_t *match_blob;   // otherwise: n_match * width bytes in device memory
 };
@@ -61,7 +63,7 @@ struct TileCol {
     const void *data;               // flat column in HBM, 16-byte aligned
     int32_t lo, hi;                 // TK_I32 / TK_I8: closed interval
     int32_t n_match;                // TK_S2: IN-list size (1..kMaxTileMatch)
-    int32_t pad;
+    int32_t negated;                // TK_S2, select trees only (k_filter_expr): 1 = keep the rows that equal NONE of the values
     uint32_t match[kMaxTileMatch];  // TK_S2: the two value bytes, little-endian
 };
 
@@ -371,7 +373,7 @@ struct ExprGenericArgs {
     const uint8_t *word_nvalid;
 };
 bool launch_filter_expr(const ExprTileArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // false: no instance for these kinds
-void launch_filter_expr_generic(const ExprGenericArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+void launch_filter_expr_generic(const ExprGenericArgs &a, bool negated, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // negated: a predicate with ColPred::negated among them
 
 struct TotalArgs {               // k_total: sum of the filter launch's per-workgroup partials
     const uint32_t *block_partials;

@@ -58,7 +58,7 @@ LimitChunks limit_chunk_ends(int64_t n_tiles) {
 
 // The same over a TABLE (all segments a GPU owns: what both Engines build for a multi-segment table) is ONE launch that stops itself
 // (k_filter_table_limit, imm3_kernels.hip: runs of kTableLimitClaimTiles tiles claimed in ascending order until the runs that are
-// done have selected `limit` rows).  A flat query only (a select tree with an OR runs k_filter_expr), with a projection behind it
+// done have selected `limit` rows).  A flat query only (a select tree with an OR or a NOT runs k_filter_expr), with a projection behind it
 // (count_in_scan), a select chain of one tile launch, not for a getter's whole select, a count log or a count-only run, not under
 // the tuning variants that pin the old launches (7, 14: the whole select stays reachable for comparison) -- and only when the table
 // has more tiles than the launch's work-groups claim at once: below that every tile is claimed before the first run is done.

@@ -30,6 +30,7 @@ void imm3::fill_colpred(const imm3_query *q, const FoldedPred &fp, ColPred &cp) 
     cp.lo = (int32_t)fp.lo;
     cp.hi = (int32_t)fp.hi;
     cp.n_match = (int32_t)fp.match.size();
+    cp.negated = fp.negated ? 1 : 0;
     cp.match_in_args = (fp.kind == KIND_STR && !fp.d_blob) ? 1 : 0;
     cp.match_blob = fp.d_blob;
     if (cp.match_in_args) {
@@ -182,7 +183,9 @@ static int launch_tree_generic(imm3_query *q, SelectRun &run) {
     a.word_nvalid = q->d_word_nvalid;
     run.grid = filter_grid(q->n_words, true, false, ctx->grid_blocks);
     LaunchTimer t(ctx, 0);
-    launch_filter_expr_generic(a, run.grid, run.s, t.start, t.stop);
+    bool negated = false;
+    for (const ColPred &cp : q->h_expr_preds) negated = negated || cp.negated;
+    launch_filter_expr_generic(a, negated, run.grid, run.s, t.start, t.stop);
     q->expr_form_ran = 1;
     return IMM3_OK;
 }
@@ -464,6 +467,7 @@ int imm3::run_select(imm3_query *q, unsigned mode) {
     }
     // (planned on every run: the tuning variant may have changed since creation)
     if (!q->is_expr) run.chain = plan_select_chain(q); // (a select tree is ONE launch of its own: no chain)
+    if (q->expr_universal) q->expr_form_ran = run.chain.tile_passes.empty() ? 1 : 0; // (a tree that selects every row: the NoSelect scan, tile or word at a time)
     // (a table has no word-at-a-time kernel.  Creation has refused the predicates that need it; what is left here is the tools'
     // TV_GENERIC_ONLY tuning variant, which sends every predicate there)
     if (q->table && !run.chain.generic.empty()) return fail(IMM3_ERR_ARG, kTableGenericRefusal);
@@ -533,6 +537,7 @@ void imm3::fill_tile_col(const imm3_query *q, const FoldedPred &fp, TileCol &c, 
     c.hi = (int32_t)fp.hi;
     if (kind == TK_S2) {
         c.n_match = (int32_t)fp.match.size();
+        c.negated = fp.negated ? 1 : 0;
         for (size_t m = 0; m < fp.match.size(); ++m)
             c.match[m] = (uint32_t)(uint8_t)fp.match[m][0] | ((uint32_t)(uint8_t)fp.match[m][1] << 8);
     }

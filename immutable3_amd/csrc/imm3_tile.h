@@ -234,6 +234,15 @@ struct ColRegs<TK_S2> {
             }
         }
     }
+    // test() of a NEGATED list (select trees, k_filter_expr): the ballot is taken of "equals none of the values" -- per value an
+    // s_andn2_b64 where test() has an s_or_b64 / s_and_b64, nothing more
+    __device__ __forceinline__ void test_not(const TileCol &c, uint64_t (&acc)[kTileWords]) {
+        for (int m = 0; m < c.n_match; ++m) {
+            const uint32_t mm = c.match[m];
+#pragma unroll
+            for (int j = 0; j < kTileWords; ++j) acc[j] &= ~ballot64(v[j] == mm);
+        }
+    }
     __device__ __forceinline__ bool row(const void *data, const TileCol &c, int64_t r) { return hit(c, ((const IMM3_GLOBAL uint16_t *)data)[r]); }
     __device__ __forceinline__ uint32_t value(int j) const { return v[j]; }
     __device__ __forceinline__ uint32_t rowval(const void *data, int64_t r) const { return ((const IMM3_GLOBAL uint16_t *)data)[r]; }

@@ -343,30 +343,40 @@ class SelectOp : public ColumnVectorOperator {
 };
 
 // ---- SelectTreeOp: a whole SelectADT over a ScanOp with its AND / OR tags HONOURED -- what the reference announces and does not do
-// (Engine.scala:236,266: "TODO: use AND/OR operators").  Fuses with ScanOp / ProjectOp / ProjectAggOp like a SelectOp chain does. ----
+// (Engine.scala:236,266: "TODO: use AND/OR operators").  Fuses with ScanOp / ProjectOp / ProjectAggOp like a SelectOp chain does.
+// honourNotMatch: a NotMatch(values) leaf -- which the reference's SelectOp throws on (Select.scala:22) -- is emitted as Match(values)
+// followed by IMM3_EXPR_NOT, the complement of its Match; off, the leaf stays what checkConditions rejects. ----
 class SelectTreeOp : public ColumnVectorOperator {
   public:
-    SelectTreeOp(std::shared_ptr<SelectADT> select, std::shared_ptr<ColumnVectorOperator> op) : select_(std::move(select)), op_(std::move(op)) {}
+    SelectTreeOp(std::shared_ptr<SelectADT> select, std::shared_ptr<ColumnVectorOperator> op, bool honourNotMatch = false)
+        : select_(std::move(select)), op_(std::move(op)), honourNotMatch_(honourNotMatch) {}
     // the tree as leaves + postfix program, post-order (a NoSelect side adds nothing: the other side stands alone)
-    static void program(const SelectADT &s, std::vector<Leaf> &leaves, std::vector<int32_t> &prog) {
+    static void program(const SelectADT &s, std::vector<Leaf> &leaves, std::vector<int32_t> &prog, bool honourNotMatch = false) {
         if (s.kind == SelectADT::And || s.kind == SelectADT::Or) {
             const size_t before = prog.size();
-            program(*s.op1, leaves, prog);
+            program(*s.op1, leaves, prog, honourNotMatch);
             const size_t mid = prog.size();
-            program(*s.op2, leaves, prog);
+            program(*s.op2, leaves, prog, honourNotMatch);
             if (mid > before && prog.size() > mid) prog.push_back(s.kind == SelectADT::And ? IMM3_EXPR_AND : IMM3_EXPR_OR);
         } else if (s.kind == SelectADT::Select) {
             prog.push_back((int32_t)leaves.size());
-            leaves.push_back(Leaf{s.col, s.cond});
+            if (honourNotMatch && s.cond.kind == SelectCondition::NotMatch) {
+                leaves.push_back(Leaf{s.col, SelectCondition::match(s.cond.values)});
+                prog.push_back(IMM3_EXPR_NOT);
+            } else leaves.push_back(Leaf{s.col, s.cond});
         }
     }
     static bool hasOr(const SelectADT &s) {
         return s.kind == SelectADT::Or || (s.kind == SelectADT::And && (hasOr(*s.op1) || hasOr(*s.op2)));
     }
+    static bool hasNotMatch(const SelectADT &s) {
+        if (s.kind == SelectADT::And || s.kind == SelectADT::Or) return hasNotMatch(*s.op1) || hasNotMatch(*s.op2);
+        return s.kind == SelectADT::Select && s.cond.kind == SelectCondition::NotMatch;
+    }
     std::shared_ptr<ScanOp> chain(std::vector<Leaf> &leaves, std::vector<int32_t> &prog) const {
         auto scan = std::dynamic_pointer_cast<ScanOp>(op_);
         if (!scan) throw Exception("SelectTreeOp must sit on a ScanOp for the fused GPU path");
-        program(*select_, leaves, prog);
+        program(*select_, leaves, prog, honourNotMatch_);
         return scan;
     }
     std::unique_ptr<Iterator<ColumnVectorBatch>> iterator() override {
@@ -380,6 +390,7 @@ class SelectTreeOp : public ColumnVectorOperator {
   private:
     std::shared_ptr<SelectADT> select_;
     std::shared_ptr<ColumnVectorOperator> op_;
+    bool honourNotMatch_ = false;
 };
 
 // ---- ProjectOp (Project.scala:17) ----
@@ -662,11 +673,15 @@ class Engine {
   public:
     // honourAndOr: a query whose select tree holds an Or runs it as a disjunction (one table launch when the table takes the tree, else
     // one SelectTreeOp per segment) instead of the reference's conjunction.  Off (the default) nothing changes; a tree without Or is the same either way.
-    explicit Engine(GpuSegmentManager &sm, bool honourAndOr = false) : sm_(sm), honourAndOr_(honourAndOr) {}
-    bool asTree(const Query &q) const { return honourAndOr_ && SelectTreeOp::hasOr(*q.select); }
+    // honourNotMatch: a query whose select tree holds a NotMatch leaf runs as a tree, whether or not it has an Or: the leaf is the
+    // complement of its Match (IMM3_EXPR_NOT), and the And / Or tags of THAT query are then honoured too.  Off (the default) nothing
+    // changes: the leaf throws "Unsupported condition", as in the reference.
+    explicit Engine(GpuSegmentManager &sm, bool honourAndOr = false, bool honourNotMatch = false) : sm_(sm), honourAndOr_(honourAndOr), honourNotMatch_(honourNotMatch) {}
+    bool notTree(const Query &q) const { return honourNotMatch_ && SelectTreeOp::hasNotMatch(*q.select); }
+    bool asTree(const Query &q) const { return (honourAndOr_ && SelectTreeOp::hasOr(*q.select)) || notTree(q); }
     // the operators between ScanOp and the projection: the reference's SelectOp chain, or one SelectTreeOp
     std::shared_ptr<ColumnVectorOperator> selectOps(const Query &q, const std::vector<Leaf> &leaves, std::shared_ptr<ColumnVectorOperator> op) const {
-        if (asTree(q)) return std::make_shared<SelectTreeOp>(q.select, op);
+        if (asTree(q)) return std::make_shared<SelectTreeOp>(q.select, op, notTree(q));
         for (const auto &l : leaves) op = SelectOp::mkSelectOp(l.col, l.cond)(op);
         return op;
     }
@@ -710,7 +725,7 @@ class Engine {
         std::vector<imm3_select> sels;
         std::vector<std::string> blobs;
         std::vector<std::vector<int32_t>> lens;
-        bool tree = false;         // `sels` are the leaves of a select tree with an Or (honourAndOr) and `prog` its postfix program:
+        bool tree = false;         // `sels` are the leaves of a select tree with an Or (honourAndOr) or a NotMatch (honourNotMatch) and `prog` its postfix program:
         std::vector<int32_t> prog; // the _table_expr entry points, which may still refuse it (IMM3_ERR_ARG: per-segment queries)
     };
     // fills `p` and returns true when the whole table can run as one fused launch
@@ -722,7 +737,7 @@ class Engine {
         for (const auto &c : p.used) p.usedIdx.push_back(table.columnIndex(c.name));
         p.tree = asTree(q);
         std::vector<Leaf> leaves;
-        if (p.tree) SelectTreeOp::program(*q.select, leaves, p.prog);
+        if (p.tree) SelectTreeOp::program(*q.select, leaves, p.prog, notTree(q));
         else leaves = resolveSelectOps(q);
         SelectOp::checkConditions(leaves);
         p.sels.resize(leaves.size());
@@ -906,7 +921,7 @@ class Engine {
 
   private:
     GpuSegmentManager &sm_;
-    bool honourAndOr_ = false;
+    bool honourAndOr_ = false, honourNotMatch_ = false;
     std::string path_;
 };
 

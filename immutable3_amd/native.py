@@ -22,8 +22,9 @@ SNAPPY_INT, SNAPPY_TINYINT, SNAPPY_STRING = 16, 17, 18   # extension: blocks as 
 INT_CODECS, TINYINT_CODECS = (DENSE_INT, PFOR_INT, SNAPPY_INT), (DENSE_TINYINT, SNAPPY_TINYINT)
 # SelectCondition (core/src/main/scala/immutabledb/Query.scala:3-9)
 MATCH, NOTMATCH, EQ, GT, LT, NOOP = 0, 1, 2, 3, 4, 5
-# operators of a select tree's postfix program (include/imm3.h: IMM3_EXPR_AND / IMM3_EXPR_OR); values >= 0 are leaf indices
-EXPR_AND, EXPR_OR = -1, -2
+# operators of a select tree's postfix program (include/imm3.h: IMM3_EXPR_AND / IMM3_EXPR_OR / IMM3_EXPR_NOT); values >= 0 are leaf
+# indices.  NOT pops one operand and pushes its complement (-4: -3 stays the unknown operator it has always been)
+EXPR_AND, EXPR_OR, EXPR_NOT = -1, -2, -4
 EXPR_FORM_TILE, EXPR_FORM_GENERIC = 0, 1
 # how every "this tree does not fit a table" refusal of the _table_expr entry points begins (include/imm3.h: IMM3_TABLE_TREE_REFUSED)
 TABLE_TREE_REFUSED = "a select tree over a table takes "
@@ -563,7 +564,8 @@ def plan_string_route(width: int, n_match: int = 1) -> int:
 
 def expr_normalize(col_codecs: Sequence[int], col_widths: Sequence[int], leaves: Sequence[tuple], prog: Sequence[int]):
     """The normal form of a select tree (include/imm3_diag.h: imm3_expr_normalize), no device needed: a list of terms, each a list
-    of {"col", "lo", "hi"} / {"col", "match": [bytes]} -- the selection is the OR of the terms, a term the AND of its predicates."""
+    of {"col", "lo", "hi"} / {"col", "match": [bytes]} / {"col", "not_match": [bytes]} (a negated IN-list: every value but these)
+    -- the selection is the OR of the terms, a term the AND of its predicates; [[]] selects every row, [] none."""
     import json
     cs, keep = _cselects(leaves)
     cc = np.array(list(col_codecs) or [0], dtype=np.int32)
@@ -577,8 +579,9 @@ def expr_normalize(col_codecs: Sequence[int], col_widths: Sequence[int], leaves:
     terms = json.loads(buf.value.decode())
     for t in terms:
         for p in t:
-            if "match" in p:
-                p["match"] = [bytes.fromhex(h) for h in p["match"]]
+            for key in ("match", "not_match"):
+                if key in p:
+                    p[key] = [bytes.fromhex(h) for h in p[key]]
     return terms
 
 
@@ -590,8 +593,8 @@ class DeviceQuery:
                  group_cols: Optional[Sequence[int]] = None, aggs: Optional[Sequence[tuple]] = None,
                  wide_keys: bool = False, expr: Optional[Sequence[int]] = None):
         """wide_keys: an aggregation through the _wide entry points (group keys of up to GROUP_KEY_MAX_WIDTH bytes).
-        expr: a select TREE -- `sels` are its leaves and `expr` the postfix program over them (leaf indices, EXPR_AND, EXPR_OR):
-        the _expr entry points, which honour OR (a DeviceTable: the _table_expr ones -- ERR_ARG when the tree does not fit the one
+        expr: a select TREE -- `sels` are its leaves and `expr` the postfix program over them (leaf indices, EXPR_AND, EXPR_OR,
+        EXPR_NOT): the _expr entry points, which honour OR and NOT (a DeviceTable: the _table_expr ones -- ERR_ARG when the tree does not fit the one
         table launch).  Without it `sels` is a conjunction."""
         self.ctx, self.seg = ctx, seg
         self.used_cols = list(used_cols)

@@ -330,9 +330,11 @@ class SelectOp(ColumnVectorOperator):
         return scan._batches(leaves)
 
 
-def select_program(select: SelectADT):
+def select_program(select: SelectADT, honour_not_match: bool = False):
     """A SelectADT (Query.scala:11-15) as the leaves and the postfix program of include/imm3.h's select trees, post-order:
-    ([(col, cond)], [leaf index | native.EXPR_AND | native.EXPR_OR]).  NoSelect adds nothing."""
+    ([(col, cond)], [leaf index | native.EXPR_AND | native.EXPR_OR | native.EXPR_NOT]).  NoSelect adds nothing.
+    honour_not_match: a NotMatch(values) leaf is emitted as Match(values) followed by EXPR_NOT; off, it stays the NotMatch leaf
+    every consumer rejects ("Unsupported condition", Select.scala:22)."""
     leaves, prog = [], []
 
     def rec(sel):
@@ -345,7 +347,11 @@ def select_program(select: SelectADT):
                 prog.append(native.EXPR_AND if isinstance(sel, And) else native.EXPR_OR)
         elif isinstance(sel, Select):
             prog.append(len(leaves))
-            leaves.append((sel.col, sel.cond))
+            if honour_not_match and isinstance(sel.cond, NotMatch):
+                leaves.append((sel.col, Match(list(sel.cond.values))))
+                prog.append(native.EXPR_NOT)
+            else:
+                leaves.append((sel.col, sel.cond))
     rec(select)
     return leaves, prog
 
@@ -354,24 +360,31 @@ def has_or(select: SelectADT) -> bool:
     return isinstance(select, Or) or (isinstance(select, And) and (has_or(select.op1) or has_or(select.op2)))
 
 
+def has_not_match(select: SelectADT) -> bool:
+    if isinstance(select, (And, Or)):
+        return has_not_match(select.op1) or has_not_match(select.op2)
+    return isinstance(select, Select) and isinstance(select.cond, NotMatch)
+
+
 class SelectTreeOp(ColumnVectorOperator):
     """A whole SelectADT over a ScanOp with its AND / OR tags HONOURED -- what the reference announces and does not do
     (Engine.scala:236,266: "TODO: use AND/OR operators"; its runOps applies the leaves one after the other).  Fuses with ScanOp /
-    ProjectOp / ProjectAggOp like a SelectOp chain does: one imm3 query per segment (imm3_query_create_expr)."""
+    ProjectOp / ProjectAggOp like a SelectOp chain does: one imm3 query per segment (imm3_query_create_expr).
+    honour_not_match: a NotMatch leaf runs as the complement of its Match (select_program); off, it raises as in the reference."""
 
-    def __init__(self, select: SelectADT, op: ColumnVectorOperator):
-        self.select, self.op = select, op
+    def __init__(self, select: SelectADT, op: ColumnVectorOperator, honour_not_match: bool = False):
+        self.select, self.op, self.honour_not_match = select, op, honour_not_match
         self.program: List[int] = []
 
     @staticmethod
-    def mkSelectTreeOp(select: SelectADT):
-        return lambda op: SelectTreeOp(select, op)
+    def mkSelectTreeOp(select: SelectADT, honour_not_match: bool = False):
+        return lambda op: SelectTreeOp(select, op, honour_not_match)
 
     def _chain(self):
         """-> (ScanOp, [(col, cond)] in program order); the program itself is left in self.program"""
         if not isinstance(self.op, ScanOp):
             raise Exception("SelectTreeOp must sit on a ScanOp for the fused GPU path")
-        leaves, self.program = select_program(self.select)
+        leaves, self.program = select_program(self.select, self.honour_not_match)
         return self.op, leaves
 
     def iterator(self):
@@ -783,21 +796,29 @@ class Engine:
     reference: one PipelineThread per segment, :176-180); output order across segments is unspecified in
     the reference (queue interleaving, :255) and defined here as ascending segment index."""
 
-    def __init__(self, sm: GpuSegmentManager, honour_and_or: bool = False, device_merge: bool = False):
+    def __init__(self, sm: GpuSegmentManager, honour_and_or: bool = False, device_merge: bool = False, honour_not_match: bool = False):
         """honour_and_or: a query whose select tree holds an Or runs it as a disjunction (one table launch when the table takes the
         tree, else SelectTreeOp per segment) instead of the reference's conjunction.  Off (the default) nothing changes; a tree without Or is the same either way.
         device_merge: the per-segment branch of execute_agg merges its queries' groups on the GPU (one imm3_comm_merge_groups_wide
-        over a one-rank communicator per context) instead of combining dicts on the host.  Off (the default) nothing changes."""
+        over a one-rank communicator per context) instead of combining dicts on the host.  Off (the default) nothing changes.
+        honour_not_match: a query whose select tree holds a NotMatch leaf -- which the reference's SelectOp throws on -- runs as a
+        tree, whether or not it has an Or: the leaf is the complement of its Match (IMM3_EXPR_NOT), and the And / Or tags of THAT
+        query are then honoured too, whatever honour_and_or says (a complement under a conjunction-for-everything has no meaning
+        to preserve).  Off (the default) nothing changes: a NotMatch leaf raises "Unsupported condition", as in the reference."""
         self.sm = sm
         self.honour_and_or = honour_and_or
         self.device_merge = device_merge
+        self.honour_not_match = honour_not_match
+
+    def _not_tree(self, query: Query) -> bool:
+        return self.honour_not_match and has_not_match(query.select)
 
     def _as_tree(self, query: Query) -> bool:
-        return self.honour_and_or and has_or(query.select)
+        return (self.honour_and_or and has_or(query.select)) or self._not_tree(query)
 
     def _select_ops(self, query: Query):
         """the operators between ScanOp and the projection: the reference's SelectOp chain, or one SelectTreeOp"""
-        return [SelectTreeOp.mkSelectTreeOp(query.select)] if self._as_tree(query) else resolveSelectOps(query)
+        return [SelectTreeOp.mkSelectTreeOp(query.select, self._not_tree(query))] if self._as_tree(query) else resolveSelectOps(query)
 
     def pipelines(self, query: Query):
         table = self.sm.getTable(query.table)
@@ -815,7 +836,7 @@ class Engine:
 
     def _table_plan(self, query: Query):
         """(DeviceTable, used columns, their table indices, select specs, program) when the whole table can run as ONE fused launch,
-        else None.  program: None for the reference's conjunction; for a tree with an Or under honour_and_or the postfix program over
+        else None.  program: None for the reference's conjunction; for a tree with an Or under honour_and_or, or with a NotMatch under honour_not_match, the postfix program over
         the select specs (imm3_query_create_table_expr), which the library may still refuse (ERR_ARG: _table_tree_refused)."""
         table = self.sm.getTable(query.table)
         dt = self.sm.device_table(query.table)
@@ -824,7 +845,7 @@ class Engine:
         used = getColumns(query, table)
         names = [c.name for c in used]
         if self._as_tree(query):
-            leaves, prog = select_program(query.select)
+            leaves, prog = select_program(query.select, self._not_tree(query))
         else:
             leaves, prog = [(op.col, op.cond) for op in (leaf(None) for leaf in resolveSelectOps(query))], None
         sels = []

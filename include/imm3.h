@@ -192,7 +192,7 @@ int imm3_table_destroy(imm3_table *t);
  * imm3_query_fetch_rows give the first `limit` survivors in (segment, row) order; imm3_query_count, imm3_query_bitmap,
  * imm3_query_join_count and a count log give the WHOLE table's figures (the whole select runs first; a logged query never stops);
  * imm3_query_segment_starts and imm3_query_locate_rows are unchanged.  Behind imm3_query_run the device-side bitmap and count
- * (imm3_query_device_ptr 0, 1) cover the scanned prefix only.  A select tree with an IMM3_EXPR_OR scans the whole table.
+ * (imm3_query_device_ptr 0, 1) cover the scanned prefix only.  A select tree with an IMM3_EXPR_OR or IMM3_EXPR_NOT scans the whole table.
  * PREDICATES A TABLE TAKES: GT / LT / EQ on int32 and int8 columns; Match on a 2-byte string column with at most 8 IN-list values
  * (the tile kernel); Match on a string column whose width is a multiple of 4, 4 .. IMM3_STRING_MAX_WIDTH bytes, with an IN-list of
  * any length (one more launch per such column over the tile table, ANDed into the bitmap; a query with one takes the bitmap plan:
@@ -238,24 +238,38 @@ int imm3_query_destroy(imm3_query *q);
  *   value >= 0         push leaf `value`
  *   IMM3_EXPR_AND      pop two, push their conjunction
  *   IMM3_EXPR_OR       pop two, push their disjunction
+ *   IMM3_EXPR_NOT      pop ONE, push its complement: exactly the rows of the segment (or table) the operand does not select
  * exactly one result must remain; (age < 18 or age > 65) and state = 'CA' is leaves {LT 18, GT 65, Match CA}, program
  * {0, 1, IMM3_EXPR_OR, 2, IMM3_EXPR_AND}.  An empty program (and no leaves) is NoSelect.
+ * IMM3_EXPR_NOT is what the reference's query ADT calls NotMatch (core/Query.scala) and its SelectOp throws on (Select.scala:22):
+ * NotMatch(values) is written {Match leaf, IMM3_EXPR_NOT}; `state not in ('CA','NY')`, `not (age > 18 and age < 30)` and `id != 7`
+ * ({EQ 7, IMM3_EXPR_NOT}) are trees like any other.  There are no null semantics, because the reference has none: Int.MinValue
+ * and "\\N" are ordinary values, and the complement of a leaf holds every row the leaf does not.  A LEAF with cond IMM3_NOTMATCH or
+ * IMM3_NOOP stays "Unsupported condition", always.  The operator's value is -4 on purpose: -3 has been fed to these entry points
+ * as "an unknown operator" since they exist, and stays one.
  * Checks, in this order: the leaves, as imm3_query_create checks its list (NotMatch / NoOp: "Unsupported condition" always; a
  * leaf on the wrong vector type "Unsupported column vector" and an unknown codec "No implementation for ..." iff the segment
  * has >= 1 batch; thresholds narrowed per leaf); then the program -- stack underflow, more than one result, an unknown operator
- * or a leaf index out of range: IMM3_ERR_ARG.
- * A program WITHOUT IMM3_EXPR_OR is the flat list of its leaves in program order and takes exactly imm3_query_create's path
- * (same folded predicates, same plan, same kernels).  With one, the library rewrites the tree into a disjunction of TERMS, each
- * a conjunction with at most one interval / IN-list per column (terms that select nothing and duplicates are dropped), and the
- * whole select is ONE launch: up to 8 terms over up to 3 int32 / int8 / 2-byte-string columns (IN-lists of <= 8 values) of a
- * uniform segment through a tile kernel, anything else -- ragged layouts, other string widths (the dword-multiple widths a flat
- * select list runs through its string kernel included: a tree keeps the row-per-lane form for them), longer IN-lists, more
- * columns, 9 .. 64 terms -- through a row-per-lane kernel; more than 64 terms: IMM3_ERR_ARG.  PFOR_INT / snappy predicate columns are
- * read in their decoded form.  The projection goes scan -> offsets scan -> gather (imm3_query_plan reports no one launch and no
+ * or a leaf index out of range: IMM3_ERR_ARG (an IMM3_EXPR_NOT on an empty stack is a stack underflow).
+ * A program with NEITHER IMM3_EXPR_OR NOR IMM3_EXPR_NOT is the flat list of its leaves in program order and takes exactly
+ * imm3_query_create's path (same folded predicates, same plan, same kernels).  With either, the library rewrites the tree into a
+ * disjunction of TERMS: NOT is pushed down to the leaves first (De Morgan over AND / OR, a double NOT cancels; NOT GT t is the
+ * interval up to t, NOT LT t the one from t, NOT EQ t the two intervals around t -- two terms, an empty one dropped -- and NOT Match
+ * a NEGATED IN-list, the values of the column's width as exclusions), then AND distributes over OR.  Each term is a conjunction
+ * with at most one interval / IN-list / exclusion list per column (on one column IN and NOT-IN fold to the IN-list minus the
+ * exclusions, two NOT-INs to the union of their exclusions; terms that select nothing and duplicates are dropped; a predicate
+ * every value passes leaves its term).  A tree whose normal form is the one term WITHOUT any predicate -- `x or not x`, NOT GT
+ * 1e12, NOT Match of values of the wrong length only -- selects every row and runs as the query's NoSelect form: the scan, plan
+ * and kernels of a query without select leaves.
+ * Any other tree's whole select is ONE launch: up to 8 terms over up to 3 int32 / int8 / 2-byte-string columns (IN-lists and
+ * exclusion lists of <= 8 values) of a uniform segment through a tile kernel, anything else -- ragged layouts, other string widths
+ * (the dword-multiple widths a flat select list runs through its string kernel included: a tree keeps the row-per-lane form for
+ * them), longer IN-lists, more columns, 9 .. 64 terms -- through a row-per-lane kernel; more than 64 terms: IMM3_ERR_ARG.
+ * PFOR_INT / snappy predicate columns are read in their decoded form.  The projection goes scan -> offsets scan -> gather (imm3_query_plan reports no one launch and no
  * records; `limit` bounds the rows emitted, the select covers the whole segment); an aggregation reads the bitmap the select
  * launch wrote.  Every run call, getter, imm3_query_log_counts and graph capture works as for any query.
  * An imm3_table takes a tree through imm3_query_create_table_expr / _table_agg_expr below. ---- */
-enum { IMM3_EXPR_AND = -1, IMM3_EXPR_OR = -2 };
+enum { IMM3_EXPR_AND = -1, IMM3_EXPR_OR = -2, IMM3_EXPR_NOT = -4 };
 int imm3_query_create_expr(imm3_ctx *ctx, const imm3_segment *seg,
                            const int32_t *used_cols, int32_t n_used,
                            const imm3_select *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog,
@@ -274,14 +288,17 @@ int imm3_query_create_agg_expr(imm3_ctx *ctx, const imm3_segment *seg,
  * `table` (the aggregation takes wide keys, as _agg_expr does).  Checks, in this order: the leaves, exactly as
  * imm3_query_create_table checks its list (every leaf, whether or not the program mentions it; the vector-type and codec checks
  * that need a batch included); then the program, with imm3_query_create_expr's errors.
- * A program WITHOUT IMM3_EXPR_OR takes exactly the path of imm3_query_create_table / _table_agg_wide: same imm3_query_plan, same
- * kernels, same results.  With one, the tree is normalised as for a segment and must fit the tile form -- at most 8 terms, at
- * most 3 predicate columns of int32 / int8 / 2-byte string (at most one of them a string), IN-lists of at most 8 values: the
- * select over ALL segments is then ONE launch (imm3_query_expr_form reports the tile form, 0).  A tree that does not fit is
- * refused at creation with IMM3_ERR_ARG and a message that names the bound exceeded -- a table has no row-per-lane kernel.  That
- * includes a tree with an IMM3_EXPR_OR over a string column of 4, 8, ... bytes, which imm3_query_create_table's flat list takes:
- * a tree's string predicates are 2-byte columns only -- and the caller runs per-segment tree queries and merges.  Every such refusal's message begins with IMM3_TABLE_TREE_REFUSED (part of the contract): that prefix, not
- * the status alone, tells "this tree does not fit a table" from a genuine argument error, which falling back would only repeat.
+ * A program with neither IMM3_EXPR_OR nor IMM3_EXPR_NOT takes exactly the path of imm3_query_create_table / _table_agg_wide: same
+ * imm3_query_plan, same kernels, same results.  With either, the tree is normalised as for a segment (a tree that selects every
+ * row: the table's NoSelect form) and must fit the tile form, the rules applied to the normal form AFTER negation -- at most 8 terms
+ * (a complemented EQ counts as two), at most 3 predicate columns of int32 / int8 / 2-byte string (at most one of them a string),
+ * IN-lists and exclusion lists of at most 8 values (a union of exclusions that grew past 8 included; NOT over a 4-byte string
+ * column is "2-byte columns only").  The select over ALL segments is then ONE launch (imm3_query_expr_form reports the tile form,
+ * 0).  A tree that does not fit is refused at creation with IMM3_ERR_ARG and a message that names the bound exceeded -- a table
+ * has no row-per-lane kernel.  That includes a tree with an IMM3_EXPR_OR over a string column of 4, 8, ... bytes, which
+ * imm3_query_create_table's flat list takes: a tree's string predicates are 2-byte columns only -- and the caller runs
+ * per-segment tree queries and merges.  Every such refusal's message begins with IMM3_TABLE_TREE_REFUSED (part of the contract):
+ * that prefix, not the status alone, tells "this tree does not fit a table" from a genuine argument error, which falling back would only repeat.
  * A tree that normalises to no term selects nothing.  PFOR_INT / snappy predicate columns are read in the
  * decoded form the table holds.  The projection takes the table's bitmap plan (offsets scan, then gather: imm3_query_plan reports
  * no one launch and no records); `limit` bounds the rows emitted, in ascending (segment, row) order.  An aggregation reads the

@@ -83,14 +83,16 @@ int imm3_query_plan(const imm3_query *q, int64_t *out, int32_t n);
  * before the first run.  IMM3_ERR_ARG for a query that is not an aggregation. */
 int imm3_query_agg_form(const imm3_query *q, int32_t *form);
 
-/* imm3_query_expr_form: which kernel the last select launch of a select-tree query (an IMM3_EXPR_OR in its program) ran: 0 = the tile
+/* imm3_query_expr_form: which kernel the last select launch of a select-tree query (an IMM3_EXPR_OR or IMM3_EXPR_NOT in its program) ran: 0 = the tile
  * form (k_filter_expr), 1 = the generic form (k_filter_expr_generic); -1 before the first launch, for a tree that selects nothing
- * (no launch at all) and for every other query. */
+ * (no launch at all) and for every other query.  A tree that selects EVERY row runs the NoSelect scan: 0 when that is the tile
+ * kernel's launch, 1 when it is the word-at-a-time kernel's (ragged layouts). */
 int imm3_query_expr_form(const imm3_query *q, int32_t *form);
 
 /* imm3_expr_normalize: the normal form of a select tree, without a device or a handle (tests hold the terms' truth table against the
  * tree's).  Columns are given by codec and width; a leaf's `column` indexes them.  json_out receives, NUL-terminated,
- *   [[{"col":c,"lo":l,"hi":h} | {"col":c,"match":["<hex bytes>", ...]}, ...], ...]     one inner list per term
+ *   [[{"col":c,"lo":l,"hi":h} | {"col":c,"match":["<hex bytes>", ...]} | {"col":c,"not_match":[...]}, ...], ...]     one inner list per term
+ * ("not_match": a negated IN-list, the exclusions of a complemented Match; a tree that selects every row is [[]], one that selects nothing [])
  * `needed` (may be NULL) the bytes that takes; cap = 0 only asks for `needed`.  Errors as at query creation; a normal form of
  * more than 64 terms is IMM3_ERR_ARG. */
 int imm3_expr_normalize(const int32_t *col_codec, const int32_t *col_width, int32_t n_cols, const imm3_select *leaves, int32_t n_leaves,
@@ -124,7 +126,7 @@ int imm3_plan_limit_chunks(int64_t n_tiles, int64_t *ends_out, int32_t cap);
 /* imm3_plan_table_limit: does a projection with a `limit` over an imm3_table run its select as the one launch that stops at the limit
  * (1: k_filter_table_limit -- work-groups claim runs of 32 virtual tiles in ascending order and stop claiming once the finished runs
  * have selected `limit` rows) or as the whole select (0)?  csrc/imm3_planner.cpp: table_limit_applies, pure like the decision above.
- * 1 needs: a table; a flat query (tree = 0: no IMM3_EXPR_OR); limit > 0; a projection behind the select (count_in_scan); a select chain
+ * 1 needs: a table; a flat query (tree = 0: no IMM3_EXPR_OR / IMM3_EXPR_NOT); limit > 0; a projection behind the select (count_in_scan); a select chain
  * of one tile launch; not a getter's whole select; no count log; not a count-only run; not tuning variant 7 or 14; and
  * n_tiles > grid * 32, `grid` being the launch's work-groups. */
 int imm3_plan_table_limit(int32_t table, int32_t tree, int64_t limit, int32_t count_in_scan, int32_t single_tile_pass, int32_t whole, int32_t count_log_on,
