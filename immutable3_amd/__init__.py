@@ -5,6 +5,7 @@ native.py    ctypes binding of that ABI (the only road to the GPU; no CPU fallba
 operators.py ScanOp / SelectOp / ProjectOp / Engine mirrors of the reference's operator interface
 storage.py   the reference's on-disk format: SegmentManager (reader) and SegmentWriter / loader (writer)
 schema.py, query.py   Column / Table / Row and the Query ADT
+sql.py       SQLParser: the reference's SQL subset (the mirror of host/sql.hpp), `order by` behind a flag
 synth.py     seeded synthetic tables of BASELINE.json's configs
 """
 from .query import (EQ, GT, LT, And, Avg, Count, Match, Max, Min, NoOp, NoSelect, NotMatch, Or, Project,  # noqa: F401

@@ -834,6 +834,10 @@ static void query_free(imm3_query *q) {
     pool_release(ctx, q->d_word_nvalid);
     pool_release(ctx, q->d_row_index);
     for (auto p : q->d_proj) pool_release(ctx, p);
+    for (int b = 0; b < 2; ++b) { pool_release(ctx, q->d_order_keys[b]); pool_release(ctx, q->d_order_perm[b]); }
+    pool_release(ctx, q->d_order_state); pool_release(ctx, q->d_order_counts); pool_release(ctx, q->d_order_diff); pool_release(ctx, q->d_order_tally);
+    pool_release(ctx, q->d_order_row_index);
+    for (auto p : q->d_order_proj) pool_release(ctx, p);
     for (auto &p : q->preds) pool_release(ctx, p.d_blob);
     for (auto &t : q->expr_terms)
         for (auto &p : t) pool_release(ctx, p.d_blob);
@@ -877,7 +881,75 @@ int imm3::ensure_row_capacity(imm3_query *q, uint64_t rows) {
         q->d_proj[j] = (uint8_t *)p;
     }
     q->cap_rows = rows;
+    return q->ordered ? ensure_order_buffers(q) : IMM3_OK;
+}
+
+// An ordered query's buffers (imm3_order.hip): two (key, permutation) buffers and the ordered arrays for as many rows as the row
+// arrays hold, from the same pool; the fixed-size tables once.
+int imm3::ensure_order_buffers(imm3_query *q) {
+    if (!q->ordered || !q->d_row_index) return IMM3_OK;
+    imm3_ctx *ctx = q->ctx;
+    void *p = nullptr;
+    if (!q->d_order_state) {
+        HIPCHK(pool_alloc(ctx, &p, OW_WORDS * sizeof(uint32_t)));
+        q->d_order_state = (uint32_t *)p;
+        HIPCHK(hipMemsetAsync(p, 0, OW_WORDS * sizeof(uint32_t), ctx->stream));
+        HIPCHK(pool_alloc(ctx, &p, (size_t)256 * kOrderWaves * sizeof(uint32_t)));
+        q->d_order_counts = (uint32_t *)p;
+        HIPCHK(pool_alloc(ctx, &p, (size_t)kOrderWaves * kOrderKeyWords * sizeof(uint32_t)));
+        q->d_order_diff = (uint32_t *)p;
+        HIPCHK(pool_alloc(ctx, &p, (size_t)kOrderWaves * 2 * sizeof(uint32_t)));
+        q->d_order_tally = (uint32_t *)p;
+    }
+    if (q->order_cap_rows == q->cap_rows && q->d_order_row_index) return IMM3_OK;
+    const uint64_t rows = q->cap_rows;
+    const uint64_t key_words = (uint64_t)(q->order_key_bytes + 3) / 4;
+    for (int b = 0; b < 2; ++b) {
+        pool_release(ctx, q->d_order_keys[b]);
+        pool_release(ctx, q->d_order_perm[b]);
+        q->d_order_keys[b] = q->d_order_perm[b] = nullptr;
+    }
+    pool_release(ctx, q->d_order_row_index);
+    q->d_order_row_index = nullptr;
+    for (auto &c : q->d_order_proj) {
+        pool_release(ctx, c);
+        c = nullptr;
+    }
+    for (int b = 0; b < 2; ++b) {
+        HIPCHK(pool_alloc(ctx, &p, rows * key_words * sizeof(uint32_t)));
+        q->d_order_keys[b] = (uint32_t *)p;
+        HIPCHK(pool_alloc(ctx, &p, rows * sizeof(uint32_t)));
+        q->d_order_perm[b] = (uint32_t *)p;
+    }
+    HIPCHK(pool_alloc(ctx, &p, rows * sizeof(uint32_t)));
+    q->d_order_row_index = (uint32_t *)p;
+    q->d_order_proj.assign(q->proj.size(), nullptr);
+    for (size_t j = 0; j < q->proj.size(); ++j) {
+        const SegCol &sc = q->seg->cols[(size_t)q->used[(size_t)q->proj[j]]];
+        HIPCHK(pool_alloc(ctx, &p, rows * (uint64_t)sc.width));
+        q->d_order_proj[j] = (uint8_t *)p;
+    }
+    q->order_cap_rows = rows;
     return IMM3_OK;
+}
+
+extern "C" int imm3_query_set_order(imm3_query *q, const imm3_order_key *keys, int32_t n_keys, int64_t limit) {
+    if (!q) return fail(IMM3_ERR_ARG, "query is null");
+    CTX_LIVE(q->ctx);
+    std::vector<int32_t> widths;
+    for (int32_t pj : q->proj) widths.push_back(q->seg->cols[(size_t)q->used[(size_t)pj]].width);
+    int32_t key_bytes = 0;
+    const int rc = imm3::order_check_args(q->is_agg, (int32_t)q->proj.size(), widths.data(), q->limit, q->run.ran_select || q->run.ran_project || q->run.ran_agg,
+                                          keys, n_keys, limit, &key_bytes);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(q->ctx->device));
+    q->order_keys.assign(keys, keys + n_keys);
+    q->order_limit = limit > 0 ? limit : 0;
+    if (q->ordered && key_bytes != q->order_key_bytes) q->order_cap_rows = 0; // (set again with wider keys: the key buffers are sized anew)
+    q->order_key_bytes = key_bytes;
+    q->ordered = true;
+    q->run.order_valid = false;
+    return ensure_order_buffers(q); // (rows reserved before this call: the order's buffers follow now)
 }
 
 // Batches of ONE segment as ScanOp yields them: the FIRST used column defines them (Scan.scala:55,72); BlockIterator
@@ -1779,6 +1851,26 @@ static int settle_rows(imm3_query *q, uint64_t *rows) {
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(q->ctx->stream));
     }
+    if (q->ordered) {
+        // the one place that emits rows again is also the one that orders them again: whatever happened above (a single-pass run that
+        // gave up on its rows, arrays that were outgrown) went through launch_project, which cleared order_valid
+        if (q->n_tiles <= 0) emit = 0;
+        else {
+            if (!q->run.order_valid) {
+                const int rc = run_order(q);
+                if (rc) return rc;
+            }
+            uint32_t st[OW_WORDS];
+            HIPCHK(hipMemcpyAsync(st, q->d_order_state, sizeof(st), hipMemcpyDeviceToHost, q->ctx->stream));
+            HIPCHK(hipStreamSynchronize(q->ctx->stream));
+            emit = st[OW_N_OUT];
+            if (q->order_counted != q->order_launches) { // (each enqueued order is counted once, by the path the device took)
+                q->order_counted = q->order_launches;
+                if (st[OW_SELECT]) ++q->order_select_runs;
+                else ++q->order_full_runs;
+            }
+        }
+    }
     *rows = emit;
     return IMM3_OK;
 }
@@ -1797,11 +1889,12 @@ extern "C" int imm3_query_fetch_rows(imm3_query *q, uint32_t *row_index_out, voi
     const uint64_t n = std::min(rows, max_rows);
     hipStream_t s = q->ctx->stream;
     if (n) {
-        if (row_index_out) HIPCHK(hipMemcpyAsync(row_index_out, q->d_row_index, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        // (an ordered query: the ordered arrays -- the unordered projection stays where it was)
+        if (row_index_out) HIPCHK(hipMemcpyAsync(row_index_out, q->ordered ? q->d_order_row_index : q->d_row_index, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         for (size_t j = 0; j < q->proj.size(); ++j) {
             if (!col_out || !col_out[j]) continue;
             const SegCol &sc = q->seg->cols[(size_t)q->used[(size_t)q->proj[j]]];
-            HIPCHK(hipMemcpyAsync(col_out[j], q->d_proj[j], n * (uint64_t)sc.width, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(col_out[j], q->ordered ? q->d_order_proj[j] : q->d_proj[j], n * (uint64_t)sc.width, hipMemcpyDeviceToHost, s));
         }
     }
     HIPCHK(hipStreamSynchronize(s));
@@ -1817,6 +1910,14 @@ extern "C" int imm3_query_device_ptr(imm3_query *q, int32_t which, void **ptr) {
     case 3: *ptr = q->d_n_emit; return IMM3_OK;
     case 4: *ptr = q->d_total + kFinishStatus; return IMM3_OK; // the status word (imm3.h: which device-side consumers must look at it)
     default:
+        // an ORDERED query's arrays sit at a base of their own, far from 16+j (a SELECT list has no bound: 16+j runs on)
+        if (q->ordered && which == IMM3_PTR_ORDER_ROW_INDEX) { *ptr = q->d_order_row_index; return IMM3_OK; }
+        if (q->ordered && which == IMM3_PTR_ORDER_ROW_COUNT) { *ptr = q->d_order_state ? q->d_order_state + OW_N_OUT : nullptr; return IMM3_OK; }
+        if (q->ordered && which >= IMM3_PTR_ORDER_COLUMN && (size_t)(which - IMM3_PTR_ORDER_COLUMN) < q->proj.size()) {
+            const size_t j = (size_t)(which - IMM3_PTR_ORDER_COLUMN);
+            *ptr = j < q->d_order_proj.size() ? q->d_order_proj[j] : nullptr;
+            return IMM3_OK;
+        }
         if (which >= 16 && (size_t)(which - 16) < q->d_proj.size()) {
             *ptr = q->d_proj[(size_t)(which - 16)];
             return IMM3_OK;
@@ -1827,10 +1928,11 @@ extern "C" int imm3_query_device_ptr(imm3_query *q, int32_t which, void **ptr) {
 
 extern "C" int imm3_query_plan(const imm3_query *q, int64_t *out, int32_t n) {
     if (!q || !out) return fail(IMM3_ERR_ARG, "null argument");
-    const int64_t v[11] = {q->single_pass ? 1 : 0, q->sp_P, q->sp_grid, q->sp_spans, q->d_stage_rec ? 1 : 0,
+    const int64_t v[14] = {q->single_pass ? 1 : 0, q->sp_P, q->sp_grid, q->sp_spans, q->d_stage_rec ? 1 : 0,
                            (q->single_pass || q->d_stage_rec) ? rec_layout(q->stage_kinds, -1).dwords : 0, q->run.ran_single_pass ? 1 : 0, (int64_t)q->run_syncs,
-                           (int64_t)q->sp_abandoned_runs, (int64_t)q->sp_busy_runs, (int64_t)q->limit_gather_gave_up};
-    for (int32_t i = 0; i < n && i < 11; ++i) out[i] = v[i];
+                           (int64_t)q->sp_abandoned_runs, (int64_t)q->sp_busy_runs, (int64_t)q->limit_gather_gave_up,
+                           (int64_t)q->order_select_runs, (int64_t)q->order_full_runs, (int64_t)q->order_launches};
+    for (int32_t i = 0; i < n && i < 14; ++i) out[i] = v[i];
     return IMM3_OK;
 }
 

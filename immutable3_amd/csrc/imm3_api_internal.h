@@ -56,6 +56,7 @@ enum SelectMode : unsigned {
 };
 int run_select(imm3_query *q, unsigned mode);                        // ScanOp -> SelectOp*: bitmap and count; mode: SelectMode bits
 int launch_project(imm3_query *q);                                   // the gather behind an offsets scan: from the records a run staged, else from the bitmap
+int run_order(imm3_query *q);                                        // an ordered query: key build, select / sort, apply behind the rows as last emitted (enqueued, no host wait)
 int join_total(imm3_query *q, hipStream_t s);                        // make `s` wait for the count reduce on the aux stream
 void fill_colpred(const imm3_query *q, const FoldedPred &fp, ColPred &cp);
 void fill_tile_col(const imm3_query *q, const FoldedPred &fp, TileCol &c, int kind);
@@ -81,6 +82,10 @@ bool pred_empty(const FoldedPred &p);                                           
 int expr_check_program(const int32_t *prog, int32_t n_prog, int32_t n_leaves, bool *has_or, bool *has_not); // IMM3_ERR_ARG: malformed; the out-flags (may be null): an IMM3_EXPR_OR / an IMM3_EXPR_NOT in it
 int expr_normalize(const std::vector<ExprCol> &leaf_cols, const imm3_select *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog,
                    std::vector<ExprTerm> &terms);
+
+// ---- imm3_order_args.cpp: the argument checks of imm3_query_set_order, over plain values ----
+int order_check_args(bool is_agg, int32_t n_proj, const int32_t *proj_widths, int64_t create_limit, bool has_run,
+                     const imm3_order_key *keys, int32_t n_keys, int64_t limit, int32_t *key_bytes_out);
 
 // ---- imm3_planner.cpp ----
 constexpr int kSampleChunks = 8;                                      // the sample a plan is made on: eight chunks of 64 tiles spread over the segment / table

@@ -73,6 +73,8 @@ enum TuningVariant : int {
     TV_AGG_SELECT_LAUNCH = 17,  // an aggregation's select chain runs as its own launch, not inside the aggregation launch
     TV_AGG_WEAK_HASH = 18,      // group keys wider than 8 bytes hash to 3 bits: distinct keys collide by construction (tests of the key compare)
     TV_EAGER_BITMAP = 19,       // a projection through survivor records stores its bitmap in the staging launch
+    TV_ORDER_FULL_SORT = 23,    // an ordered query with a limit sorts every row: no radix select in front of the sort
+    TV_ORDER_SELECT_ALWAYS = 24, // ... takes the radix select whenever the limit is below the survivors (the threshold sweep of tools/order_bench.py)
     TV_TILE_ABLATION = 20,      // 20 .. 22: k_filter_tile's ablation switches (tools' build only)
     TV_EMIT_ABLATION = 34,      // 34 .. 35: k_emit's ablation switches (tools' build only)
     TV_PROJECT_ABLATION = 50,   // 50 + mask (mask <= 255): k_filter_project's ablation mask (tools' build only)
@@ -142,6 +144,7 @@ struct QueryRunState {
     bool limit_gather_ran = false;   // the last projection was k_limit_gather's one launch: settle_rows looks at its give-up tag
     bool ran_single_pass = false;    // the last run went through k_filter_project ...
     bool sp_verified = false;        // ... and its status word has been read since (rows complete, or gathered again from the bitmap)
+    bool order_valid = false;        // an ordered query (imm3_query_set_order): the ordered arrays hold the order of the rows as last emitted (every re-emit clears it: launch_project)
 };
 
 // A recorded sequence of query runs (hipGraph): launching it enqueues every kernel of those runs with one call.
@@ -362,6 +365,17 @@ struct imm3_query {
     int32_t expr_form_ran = -1;             // diagnostics (imm3_query_expr_form): 0 = tile, 1 = generic, -1 before any launch
     bool expr_universal = false;            // the tree's normal form is the one term without a predicate: every row -- the query is the NoSelect form (is_expr stays false)
     bool count_log_on = false;              // imm3_query_log_counts is installed: every run logs the segment's count (a limit query then scans whole)
+    // ORDER BY (imm3_query_set_order; imm3_order.hip): the projected rows ordered behind every emit, into arrays of their own
+    bool ordered = false;
+    std::vector<imm3_order_key> order_keys;   // proj: index into `proj`
+    int64_t order_limit = 0;                  // <= 0: every row
+    int32_t order_key_bytes = 0;
+    uint32_t *d_order_keys[2] = {nullptr, nullptr}, *d_order_perm[2] = {nullptr, nullptr}; // ping-pong, sized with the row arrays
+    uint32_t *d_order_state = nullptr, *d_order_counts = nullptr, *d_order_diff = nullptr, *d_order_tally = nullptr;
+    uint32_t *d_order_row_index = nullptr;
+    std::vector<uint8_t *> d_order_proj;
+    uint64_t order_cap_rows = 0;              // rows the order's buffers were sized for
+    uint64_t order_select_runs = 0, order_full_runs = 0, order_launches = 0, order_counted = 0; // settled ordered runs that took the radix select / sorted every row; times the order was enqueued (imm3_query_plan)
     uint32_t sp_abandoned_runs = 0, sp_busy_runs = 0; // single-pass runs whose rows were gathered from the bitmap instead: a prefix never came / the device was busy (imm3_query_plan)
 };
 
@@ -372,5 +386,6 @@ void ctx_retain(imm3_ctx *c);
 void ctx_release(imm3_ctx *c);
 int join_query_count(imm3_query *q); // settle the query's count word for device-side consumers on the context's stream (enqueued, no host wait)
 int query_groups(imm3_query *q, uint32_t *n_groups);  // the aggregation's dense group list is complete in q->d_o* (synchronises)
+int ensure_order_buffers(imm3_query *q);              // an ordered query's buffers, for the capacity of its row arrays
 void query_agg_args(const imm3_query *q, AggArgs &a); // the kernels' view of an aggregation query (launch_group_keys / launch_strmax_collect behind query_groups)
 }

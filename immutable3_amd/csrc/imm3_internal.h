@@ -677,6 +677,68 @@ void launch_scan(const ScanArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev
 void launch_gather(const GatherArgs &a, int grid_blocks, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 void launch_limit_gather(const LimitGatherArgs &a, int grid_blocks, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 
+// ---- ORDER BY (imm3_order.hip): a stable LSD radix sort of (normalised key, permutation) behind the projection, with an exact
+// radix select in front of it for a top-k.  Every launch has the same fixed geometry -- kOrderWaves waves, each owning ONE contiguous
+// piece of the rows -- and takes the row count from a device word, so the host enqueues the whole order without knowing it. ----
+constexpr int kOrderMaxKeys = 4;
+constexpr int kOrderKeyMaxBytes = 16;
+constexpr int kOrderKeyWords = kOrderKeyMaxBytes / 4;
+constexpr int kOrderWaves = 1024;                       // waves of every order launch = "blocks" of the (digit, block) count table
+constexpr int kOrderBlockThreads = 256;
+constexpr int kOrderGrid = kOrderWaves * 64 / kOrderBlockThreads;
+constexpr int64_t kOrderSweepRows = (int64_t)kOrderWaves * 64; // rows one step of all waves covers: above it a wave walks its piece in several steps
+constexpr int kOrderSelectFactor = 4;                   // the select runs when survivors >= this x limit
+// the order's device words (uint32): written by k_order_plan and k_order_find, read by every launch behind them
+enum OrderWord : int {
+    OW_N = 0,        // rows the projection emitted (clamped to the arrays' capacity)
+    OW_N_SORT = 1,   // rows the sort passes move: OW_N, or `limit` behind the select
+    OW_N_OUT = 2,    // rows of the ordered result, min(OW_N, limit); OW_N_OUT + 1 stays 0: the pair reads as one uint64
+    OW_ACTIVE = 4,   // bit p set: key byte p (0 = most significant) differs between rows -- its pass moves something
+    OW_SELECT = 5,   // 1: the radix select compacts the candidates first
+    OW_NEED = 6,     // select: rows still wanted among those that match the threshold's bytes found so far
+    OW_THR = 8,      // 4 words: the threshold key, found byte by byte
+    OW_KEY0 = 12,    // 4 words: the first row's key (what a byte position that never differs holds)
+    OW_WORDS = 16,
+};
+struct OrderKeyCol {
+    const uint8_t *src;  // the projected (unordered) column, width bytes per row
+    int32_t width;
+    int32_t kind;        // KIND_I32 / KIND_I8 / KIND_STR
+    int32_t descending;
+    int32_t pad;
+};
+struct OrderArgs {
+    const unsigned long long *n_emit; // the projection's row-count word
+    uint64_t cap_rows;                // capacity of the row arrays (a run that outgrew them is ordered again once settled)
+    int64_t limit;                    // <= 0: none
+    OrderKeyCol cols[kOrderMaxKeys];
+    int32_t n_cols, key_bytes, key_words, force_full;
+    uint32_t *keys[2];                // ping-pong: key word w of row i at keys[b][w * cap_rows + i], word 0 most significant
+    uint32_t *perm[2];
+    uint32_t *state;                  // OrderWord
+    uint32_t *counts;                 // 256 x kOrderWaves: [digit][wave] counts, scanned in place to first positions
+    uint32_t *diff;                   // kOrderWaves x 4: OR of key ^ first key per wave
+    uint32_t *tally;                  // kOrderWaves x 2: select: {rows below the threshold, rows equal to it} per wave; then {first output, equal rows before}
+    int32_t byte_pos, pad;            // the key byte this launch works on
+};
+struct OrderApplyCol {
+    const uint8_t *src;
+    uint8_t *dst;
+    int32_t width, pad;
+};
+struct OrderApplyArgs {
+    const uint32_t *perm[2];
+    const uint32_t *state;
+    int32_t key_bytes, n_cols;
+    const uint32_t *row_index;        // null: the columns only (a later group of a wide SELECT list)
+    uint32_t *row_index_out;
+    OrderApplyCol cols[kMaxProj];
+};
+void launch_order_keys(const OrderArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);   // k_order_keys + k_order_plan
+void launch_order_select(const OrderArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // the radix select: per key byte count + find, then offsets, compact
+void launch_order_pass(const OrderArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);   // one LSD pass on a.byte_pos: count, scan, scatter
+void launch_order_apply(const OrderApplyArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+
 } // namespace imm3
 
 #ifdef __HIPCC__

@@ -743,6 +743,7 @@ static int launch_emit_records(imm3_query *q) {
 int imm3::launch_project(imm3_query *q) {
     imm3_ctx *ctx = q->ctx;
     hipStream_t s = ctx->stream;
+    q->run.order_valid = false; // (the rows are emitted again: whoever does that orders them again -- run_query, settle_rows)
     if (q->run.stage_written) return launch_emit_records(q);
     GatherArgs g;
     std::memset(&g, 0, sizeof(g));
@@ -933,10 +934,85 @@ static int run_project(imm3_query *q) {
     return IMM3_OK;
 }
 
+// ORDER BY behind the rows as last emitted (imm3_order.hip): key build, the radix select when a limit is set, one LSD pass per key
+// byte, apply.  Every launch reads the row count and what the launches before it decided from device words: enqueued blindly.
+int imm3::run_order(imm3_query *q) {
+    imm3_ctx *ctx = q->ctx;
+    hipStream_t s = ctx->stream;
+    if (!q->ordered) return IMM3_OK;
+    if (q->n_tiles <= 0) { // (nothing was emitted and no row-count word was written: the ordered result is empty)
+        q->run.order_valid = true;
+        return IMM3_OK;
+    }
+    {
+        const int rc = ensure_order_buffers(q);
+        if (rc) return rc;
+    }
+    OrderArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.n_emit = q->d_n_emit;
+    a.cap_rows = q->cap_rows;
+    a.limit = q->order_limit;
+    a.n_cols = (int32_t)q->order_keys.size();
+    for (int c = 0; c < a.n_cols; ++c) {
+        const imm3_order_key &k = q->order_keys[(size_t)c];
+        const SegCol &sc = q->seg->cols[(size_t)q->used[(size_t)q->proj[(size_t)k.proj]]];
+        a.cols[c].src = q->d_proj[(size_t)k.proj];
+        a.cols[c].width = sc.width;
+        a.cols[c].kind = sc.vcodec == IMM3_DENSE_INT ? KIND_I32 : (sc.vcodec == IMM3_DENSE_TINYINT ? KIND_I8 : KIND_STR);
+        a.cols[c].descending = k.descending ? 1 : 0;
+    }
+    a.key_bytes = q->order_key_bytes;
+    a.key_words = (q->order_key_bytes + 3) / 4;
+    a.force_full = ctx->filter_variant == TV_ORDER_FULL_SORT ? 1 : (ctx->filter_variant == TV_ORDER_SELECT_ALWAYS ? 2 : 0); // (0: the device decides)
+    for (int b = 0; b < 2; ++b) {
+        a.keys[b] = q->d_order_keys[b];
+        a.perm[b] = q->d_order_perm[b];
+    }
+    a.state = q->d_order_state;
+    a.counts = q->d_order_counts;
+    a.diff = q->d_order_diff;
+    a.tally = q->d_order_tally;
+    LaunchTimer t(ctx, 7); // (one record for the whole order: from its first kernel's start to its last one's end)
+    launch_order_keys(a, s, t.start, nullptr);
+    if (q->order_limit > 0) launch_order_select(a, s, nullptr, nullptr);
+    for (int p = a.key_bytes - 1; p >= 0; --p) { // least significant byte first
+        a.byte_pos = p;
+        launch_order_pass(a, s, nullptr, nullptr);
+    }
+    HIPCHK(hipGetLastError());
+    OrderApplyArgs ap;
+    std::memset(&ap, 0, sizeof(ap));
+    ap.perm[0] = q->d_order_perm[0];
+    ap.perm[1] = q->d_order_perm[1];
+    ap.state = q->d_order_state;
+    ap.key_bytes = a.key_bytes;
+    const size_t np = q->proj.size();
+    size_t done = 0;
+    do { // more SELECT-list columns than one launch carries: in groups, as the gather (the row indices with the first)
+        const size_t take = std::min<size_t>(kMaxProj, np - done);
+        ap.row_index = done == 0 ? q->d_row_index : nullptr;
+        ap.row_index_out = q->d_order_row_index;
+        ap.n_cols = (int32_t)take;
+        for (size_t j = 0; j < take; ++j) {
+            ap.cols[j].src = q->d_proj[done + j];
+            ap.cols[j].dst = q->d_order_proj[done + j];
+            ap.cols[j].width = q->seg->cols[(size_t)q->used[(size_t)q->proj[done + j]]].width;
+        }
+        done += take;
+        launch_order_apply(ap, s, nullptr, done >= np ? t.stop : nullptr);
+    } while (done < np);
+    HIPCHK(hipGetLastError());
+    ++q->order_launches;
+    q->run.order_valid = true;
+    return IMM3_OK;
+}
+
 // a run recorded into an open capture: nothing in it may synchronise, allocate or use a second stream
 static int capture_admit(imm3_query *q) {
     imm3_ctx *ctx = q->ctx;
     if (!ctx->capture) return IMM3_OK;
+    if (q->ordered) return fail(IMM3_ERR_STATE, "an ordered query (imm3_query_set_order) cannot be run inside a graph capture: graph replay of ordered queries is not supported");
     if (ctx->filter_variant == TV_COUNT_ON_AUX) return fail(IMM3_ERR_STATE, "tuning variant 2 (count reduce on the aux stream) cannot be captured");
     const bool sp = q->single_pass && !q->proj.empty() && !q->always_false && q->n_tiles > 0; // (writes its rows without knowing the count)
     if (!q->proj.empty() && !(q->limit > 0) && !q->reserved && !sp && !q->d_row_index)
@@ -997,7 +1073,10 @@ static int run_query(imm3_query *q) {
         const int rrc = single_pass_restore(q, q->sp_restore_survivors);
         if (rrc) return rrc;
     }
-    if (q->single_pass && !q->proj.empty() && !q->always_false && q->n_tiles > 0) return run_single_pass(q);
+    if (q->single_pass && !q->proj.empty() && !q->always_false && q->n_tiles > 0) {
+        const int src = run_single_pass(q);
+        return src ? src : run_order(q);
+    }
     const bool select_only = q->proj.empty() && !q->is_agg && q->ctx->filter_variant == TV_COUNT_ON_AUX;
     const bool count_in_scan = !q->proj.empty() && q->n_tiles > 0 && !q->always_false && q->ctx->filter_variant != TV_COUNT_BY_K_TOTAL;
     int rc = IMM3_OK;
@@ -1006,6 +1085,7 @@ static int run_query(imm3_query *q) {
     else rc = run_select(q, (select_only ? SEL_OVERLAP_TOTAL : SEL_DEFAULT) | (count_in_scan ? SEL_COUNT_IN_SCAN : SEL_DEFAULT));
     if (rc) return rc;
     if (!q->proj.empty()) rc = run_project(q);
+    if (!rc && q->ordered) rc = run_order(q);
     if (!rc && q->is_agg) rc = run_agg(q);
     return rc;
 }

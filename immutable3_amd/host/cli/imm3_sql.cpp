@@ -4,6 +4,8 @@
 //   --parse-only   print the parsed Query ADT and the planner's column order / leaves; no GPU needed.
 //   --honour-and-or  run an `or` of the where clause as a disjunction (default off: the reference executes every Or as an And,
 //                  Engine.scala:236-245).  With --parse-only it also prints the tree's postfix program.
+//   --order-by     accept `order by f [asc|desc] {, f [asc|desc]}` between the where clause and `limit` (default off: the reference's
+//                  grammar, in which such a statement does not parse); the rows come back sorted on the GPU, `limit` applied behind the order.
 //   --explain      after the rows, one line on stderr: whether the query ran as one table query or per segment ("path: ...").
 #include <chrono>
 #include <cstdio>
@@ -27,7 +29,15 @@ static std::string showSelect(const SelectADT &s) {
 static std::string showQuery(const Query &q) {
     std::string p;
     auto list = [](const std::vector<std::string> &v) { std::string s = "List("; for (size_t i = 0; i < v.size(); ++i) { if (i) s += ", "; s += v[i]; } return s + ")"; };
-    if (q.project.kind == ProjectADT::Project) p = "Project(" + list(q.project.cols) + "," + std::to_string(q.project.limit) + ")";
+    if (q.project.kind == ProjectADT::Project) {
+        p = "Project(" + list(q.project.cols) + "," + std::to_string(q.project.limit);
+        if (!q.project.orderBy.empty()) { // (only under --order-by: the reference's Project has two fields)
+            p += ",List(";
+            for (size_t i = 0; i < q.project.orderBy.size(); ++i) p += std::string(i ? ", " : "") + "(" + q.project.orderBy[i].first + "," + (q.project.orderBy[i].second ? "desc" : "asc") + ")";
+            p += ")";
+        }
+        p += ")";
+    }
     else {
         static const char *names[] = {"Sum", "Avg", "Min", "Max", "Count"};
         p = "ProjectAgg(List(";
@@ -40,7 +50,7 @@ static std::string showQuery(const Query &q) {
 int main(int argc, char **argv) {
     std::string query, dataDir;
     int device = 0, repeat = 0;
-    bool parseOnly = false, honourAndOr = false, explain = false;
+    bool parseOnly = false, honourAndOr = false, explain = false, orderBy = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if ((a == "-q" || a == "--query") && i + 1 < argc) query = argv[++i];
@@ -49,16 +59,17 @@ int main(int argc, char **argv) {
         else if (a == "--cpu-count" && i + 1 < argc) ++i; // accepted for SqlCli compatibility; segments run on the GPU
         else if (a == "--parse-only") parseOnly = true;
         else if (a == "--honour-and-or") honourAndOr = true;
+        else if (a == "--order-by") orderBy = true;
         else if (a == "--explain") explain = true;
         else if (a == "--repeat" && i + 1 < argc) repeat = std::atoi(argv[++i]); // re-run the query N times on the resident table, time to stderr
         else { std::fprintf(stderr, "Error parsing arguments: %s\n", a.c_str()); return 2; }
     }
     if (query.empty() || (dataDir.empty() && !parseOnly)) {
-        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only] [--honour-and-or] [--explain]\n");
+        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only] [--honour-and-or] [--order-by] [--explain]\n");
         return 2;
     }
     try {
-        const Query q = SQLParser::parseAll(query);
+        const Query q = SQLParser::parseAll(query, orderBy);
         if (parseOnly) {
             std::cout << showQuery(q) << "\n";
             if (!dataDir.empty()) {

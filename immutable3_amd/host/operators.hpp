@@ -12,6 +12,7 @@
 // into one imm3_query.  Everything that touches data goes through the C ABI; there is no CPU evaluation path.
 #pragma once
 
+#include <algorithm>
 #include <cstring>
 #include <functional>
 #include <memory>
@@ -396,9 +397,19 @@ class SelectTreeOp : public ColumnVectorOperator {
 // ---- ProjectOp (Project.scala:17) ----
 class ProjectOp : public ProjectionOperator {
   public:
-    ProjectOp(std::vector<std::string> cols, std::shared_ptr<ColumnVectorOperator> op, int limit = 0) : cols_(std::move(cols)), op_(std::move(op)), limit_(limit) {}
-    static std::function<std::shared_ptr<ProjectOp>(std::shared_ptr<ColumnVectorOperator>)> mkProjectOp(const std::vector<std::string> &cols, int limit = 0) {
-        return [cols, limit](std::shared_ptr<ColumnVectorOperator> op) { return std::make_shared<ProjectOp>(cols, op, limit); };
+    // orderBy: (column of `cols`, descending), most significant first -- the rows come back in that order, `limit` applied behind it
+    // (imm3_query_set_order: sorted on the device); empty: the reference's ProjectOp
+    ProjectOp(std::vector<std::string> cols, std::shared_ptr<ColumnVectorOperator> op, int limit = 0, std::vector<std::pair<std::string, bool>> orderBy = {})
+        : cols_(std::move(cols)), op_(std::move(op)), limit_(limit), orderKeys_(orderKeys(cols_, orderBy)) {}
+    static std::function<std::shared_ptr<ProjectOp>(std::shared_ptr<ColumnVectorOperator>)> mkProjectOp(const std::vector<std::string> &cols, int limit = 0,
+                                                                                                          const std::vector<std::pair<std::string, bool>> &orderBy = {}) {
+        return [cols, limit, orderBy](std::shared_ptr<ColumnVectorOperator> op) { return std::make_shared<ProjectOp>(cols, op, limit, orderBy); };
+    }
+    // the one call an ordered query adds between its creation and its first run
+    static void setOrder(imm3_query *q, const std::vector<std::pair<int, bool>> &keys, int limit) {
+        std::vector<imm3_order_key> ks;
+        for (const auto &k : keys) ks.push_back(imm3_order_key{(int32_t)k.first, k.second ? 1 : 0});
+        imm3Check(imm3_query_set_order(q, ks.data(), (int32_t)ks.size(), limit));
     }
     std::unique_ptr<Iterator<Row>> iterator() override {
         std::vector<Leaf> leaves;
@@ -411,7 +422,8 @@ class ProjectOp : public ProjectionOperator {
         if (!scan) return hostIterator();
         SelectOp::checkConditions(leaves);
         QueryHandle h;
-        scan->makeQuery(leaves, cols_, limit_, h, progp);
+        scan->makeQuery(leaves, cols_, orderKeys_.empty() ? limit_ : 0, h, progp); // (an order's limit is applied behind the order: no creation-time limit)
+        if (!orderKeys_.empty()) setOrder(h.q, orderKeys_, limit_);
         imm3Check(imm3_query_run(h.q));
         uint64_t n = 0;
         imm3Check(imm3_query_row_count(h.q, &n));
@@ -449,7 +461,8 @@ class ProjectOp : public ProjectionOperator {
         auto it = std::make_unique<VectorIterator<Row>>();
         auto in = op_->iterator();
         int total = 0;
-        while (in->hasNext() && !(limit_ > 0 && total >= limit_)) {
+        const int limit = orderKeys_.empty() ? limit_ : 0; // (ordered: every row, sorted below)
+        while (in->hasNext() && !(limit > 0 && total >= limit)) {
             ColumnVectorBatch vec = in->next();
             std::vector<int> vecCols;
             for (const auto &name : cols_) {
@@ -460,18 +473,23 @@ class ProjectOp : public ProjectionOperator {
                 vecCols.push_back(idx);
             }
             for (int pos : vec.selected.toList()) {
-                if (limit_ > 0 && total >= limit_) break;
+                if (limit > 0 && total >= limit) break;
                 std::vector<Value> xs;
                 for (int ci : vecCols) xs.push_back(vec.columnVectors[(size_t)ci].value(pos));
                 it->items.push_back(Row::fromSeq(std::move(xs)));
                 ++total;
             }
         }
+        if (!orderKeys_.empty()) {
+            std::stable_sort(it->items.begin(), it->items.end(), [this](const Row &a, const Row &b) { return rowBefore(a, b, orderKeys_); });
+            if (limit_ > 0 && it->items.size() > (size_t)limit_) it->items.resize((size_t)limit_);
+        }
         return it;
     }
     std::vector<std::string> cols_;
     std::shared_ptr<ColumnVectorOperator> op_;
     int limit_;
+    std::vector<std::pair<int, bool>> orderKeys_;
 };
 
 
@@ -841,6 +859,9 @@ class Engine {
             return rows;
         }
         if (q.project.kind != ProjectADT::Project) throw Exception("NoProject");
+        const std::vector<std::pair<int, bool>> okeys = orderKeys(q.project.cols, q.project.orderBy); // (throws for a key outside the SELECT list)
+        const bool ordered = !okeys.empty();
+        const int createLimit = ordered ? 0 : q.project.limit; // an order's limit is applied behind the order (imm3_query_set_order)
         path_ = "per-segment queries";
         {   // the whole table in ONE fused launch when it qualifies
             TablePlan p;
@@ -857,15 +878,16 @@ class Engine {
                 }
                 if (p.tree) {
                     const int rc = imm3_query_create_table_expr(sm_.ctx(), p.table, p.usedIdx.data(), (int32_t)p.usedIdx.size(), p.sels.data(), (int32_t)p.sels.size(),
-                                                                p.prog.data(), (int32_t)p.prog.size(), proj.data(), (int32_t)proj.size(), q.project.limit,
+                                                                p.prog.data(), (int32_t)p.prog.size(), proj.data(), (int32_t)proj.size(), createLimit,
                                                                 sm_.sm.getTable(q.table).blockSize, &h.q);
                     if (tableTreeRefused(rc)) { planned = false; path_ = std::string("per-segment queries: ") + imm3_last_error(); }
                     else imm3Check(rc);
                 } else
                 imm3Check(imm3_query_create_table(sm_.ctx(), p.table, p.usedIdx.data(), (int32_t)p.usedIdx.size(), p.sels.data(), (int32_t)p.sels.size(),
-                                                  proj.data(), (int32_t)proj.size(), q.project.limit, sm_.sm.getTable(q.table).blockSize, &h.q));
+                                                  proj.data(), (int32_t)proj.size(), createLimit, sm_.sm.getTable(q.table).blockSize, &h.q));
             }
             if (planned) {
+                if (ordered) ProjectOp::setOrder(h.q, okeys, q.project.limit); // ONE ordered table query: sorted on the device
                 imm3Check(imm3_query_run(h.q));
                 path_ = "one table query";
                 if (p.tree) { // the tree's one launch over all segments: say which kernel the library ran (imm3_diag.h)
@@ -902,9 +924,22 @@ class Engine {
         const std::vector<Column> used = getColumns(q, table);
         const std::vector<Leaf> leaves = resolveSelectOps(q);
         auto mkScan = ScanOp::mkScanOp(sm_, q.table);
-        auto mkProj = ProjectOp::mkProjectOp(q.project.cols, q.project.limit);
+        auto mkProj = ProjectOp::mkProjectOp(q.project.cols, q.project.limit, q.project.orderBy);
         std::vector<Row> rows;
         const int nseg = sm_.sm.getTableSegmentCount(table.name);
+        if (ordered) {
+            // per-segment ordered queries, each with the limit (no segment can contribute more), then a stable merge: the segments'
+            // results are appended in segment order, each in (keys, row) order, so a stable sort by the keys is by (keys, segment, row)
+            for (int seg = 0; seg < nseg; ++seg) {
+                std::shared_ptr<ColumnVectorOperator> op = mkScan(used, seg);
+                op = selectOps(q, leaves, op);
+                auto it = mkProj(op)->iterator();
+                while (it->hasNext()) rows.push_back(it->next());
+            }
+            std::stable_sort(rows.begin(), rows.end(), [&okeys](const Row &a, const Row &b) { return rowBefore(a, b, okeys); });
+            if (q.project.limit > 0 && rows.size() > (size_t)q.project.limit) rows.resize((size_t)q.project.limit);
+            return rows;
+        }
         for (int seg = 0; seg < nseg; ++seg) {
             if (q.project.limit > 0 && (int)rows.size() >= q.project.limit) break;
             std::shared_ptr<ColumnVectorOperator> op = mkScan(used, seg);

@@ -276,9 +276,34 @@ struct ProjectADT {
     enum Kind { Project, ProjectAgg, NoProject } kind = NoProject;
     std::vector<std::string> cols; // Project
     int limit = 0;
+    std::vector<std::pair<std::string, bool>> orderBy; // Project: (column, descending), most significant first -- the "sort" Query.scala:27 announces; empty: none
     std::vector<Aggregate> aggs;   // ProjectAgg
     std::vector<std::string> groupBy;
 };
+
+// ORDER BY keys as places in the SELECT list: (index into cols, descending).  A key that is not a SELECT-list column is refused.
+inline std::vector<std::pair<int, bool>> orderKeys(const std::vector<std::string> &cols, const std::vector<std::pair<std::string, bool>> &orderBy) {
+    std::vector<std::pair<int, bool>> out;
+    for (const auto &k : orderBy) {
+        int idx = -1;
+        for (size_t j = 0; j < cols.size() && idx < 0; ++j)
+            if (cols[j] == k.first) idx = (int)j;
+        if (idx < 0) throw Exception("order by column `" + k.first + "' is not in the SELECT list");
+        out.push_back({idx, k.second});
+    }
+    return out;
+}
+// rows ordered by such keys: Int / Byte values as signed integers, strings byte-wise unsigned; stable (equal keys keep their order)
+inline bool rowBefore(const Row &a, const Row &b, const std::vector<std::pair<int, bool>> &keys) {
+    for (const auto &k : keys) {
+        const Value &x = a.xs.at((size_t)k.first), &y = b.xs.at((size_t)k.first);
+        int c = 0;
+        if (x.kind == Value::String) c = x.s.compare(y.s);
+        else c = x.i < y.i ? -1 : (x.i > y.i ? 1 : 0);
+        if (c != 0) return k.second ? c > 0 : c < 0;
+    }
+    return false;
+}
 
 struct Query {
     std::string table;

@@ -10,6 +10,10 @@
 //   filter           := "(" repsep(filter,"and") ")" | "(" repsep(filter,"or") ")"
 //                     | ident "=" value | ident "=" "'" value "'" | ident ">" value | ident "<" value   (:56-96)
 //   limit            := opt("limit" digits)                                                  (:37)
+// EXTENSION, only when the parser is asked for it (parseAll(sql, true); imm3_sql --order-by) -- the "sort" core/Query.scala:27 announces:
+//   queryProject     := "select" repsep(ident, ",") "from" ident where orderBy limit
+//   orderBy          := opt("order" "by" rep1sep(ident opt("asc" | "desc"), ","))
+// With the flag off the grammar is the reference's, and such a statement fails to parse as it always has.
 //   ident = [\w#]+   value = [\w0-9#]+  (no sign, no decimal point)                          (:119-121)
 #pragma once
 
@@ -23,8 +27,9 @@ namespace immutabledb {
 
 class SQLParser {
   public:
-    static Query parseAll(const std::string &input) {
+    static Query parseAll(const std::string &input, bool orderBy = false) {
         SQLParser p(input);
+        p.orderBy_ = orderBy;
         Query q;
         size_t end = 0;
         if (p.query(0, q, end)) {
@@ -39,6 +44,7 @@ class SQLParser {
     explicit SQLParser(const std::string &s) : s_(s) {}
     const std::string &s_;
     size_t furthest_ = 0;
+    bool orderBy_ = false;
     std::string expected_ = "`select'";
 
     size_t skipWs(size_t i) const {
@@ -162,6 +168,30 @@ class SQLParser {
         end = p;
         return true;
     }
+    // opt("order" ~ "by" ~> rep1sep(ident ~ opt("asc" | "desc"), ",")): the position behind the clause, or i when there is none
+    size_t orderByClause(size_t i, std::vector<std::pair<std::string, bool>> &out) {
+        size_t p, q;
+        if (!lit(i, "order", p) || !lit(p, "by", q)) return i;
+        std::vector<std::pair<std::string, bool>> keys;
+        for (;;) {
+            std::string f;
+            size_t r, t;
+            if (!ident(q, f, r)) break;
+            bool desc = false;
+            if (lit(r, "desc", t)) { desc = true; r = t; }
+            else if (lit(r, "asc", t)) r = t;
+            keys.push_back({f, desc});
+            q = r;
+            if (!lit(q, ",", t)) break;
+            std::string g;
+            size_t u;
+            if (!ident(t, g, u)) break; // (rep1sep backtracks over a dangling separator)
+            q = t;
+        }
+        if (keys.empty()) return i;
+        out = keys;
+        return q;
+    }
     bool agg(size_t i, Aggregate &a, size_t &end) { // aggSumP | aggMinP | aggMaxP | aggCountP (:103-117)
         static const struct { const char *kw; Aggregate::Kind k; } kinds[] = {
             {"sum", Aggregate::Sum}, {"min", Aggregate::Min}, {"max", Aggregate::Max}, {"count", Aggregate::Count}};
@@ -228,6 +258,7 @@ class SQLParser {
                 p.kind = ProjectADT::Project;
                 p.cols = cols;
                 size_t e;
+                if (orderBy_) d = orderByClause(d, p.orderBy);
                 if (lit(d, "limit", e)) {
                     size_t k = skipWs(e), j = k;
                     while (j < s_.size() && std::isdigit((unsigned char)s_[j])) ++j;

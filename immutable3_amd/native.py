@@ -41,7 +41,7 @@ EXPORTS = [
     "imm3_table_create", "imm3_table_destroy", "imm3_query_create_table", "imm3_query_create_table_agg",
     "imm3_query_segment_starts", "imm3_query_locate_rows",
     "imm3_query_create", "imm3_query_create_agg", "imm3_query_group_count", "imm3_query_fetch_groups", "imm3_query_agg_shape",
-    "imm3_query_fetch_group_strings", "imm3_query_destroy", "imm3_query_reserve_rows",
+    "imm3_query_fetch_group_strings", "imm3_query_destroy", "imm3_query_reserve_rows", "imm3_query_set_order",
     "imm3_query_create_agg_wide", "imm3_query_create_table_agg_wide", "imm3_query_fetch_group_keys",
     "imm3_query_create_expr", "imm3_query_create_agg_expr", "imm3_query_create_table_expr", "imm3_query_create_table_agg_expr",
     "imm3_query_run", "imm3_query_run_select", "imm3_query_run_count", "imm3_query_sync", "imm3_query_join_count", "imm3_query_log_counts",
@@ -62,6 +62,9 @@ DIAG_EXPORTS = [
     "imm3_query_agg_form", "imm3_query_expr_form", "imm3_expr_normalize",
 ]
 COMM_ID_BYTES = 128
+# imm3_query_device_ptr ids of an ordered query's arrays (include/imm3.h)
+PTR_ORDER_ROW_INDEX, PTR_ORDER_ROW_COUNT, PTR_ORDER_COLUMN = 0x1000, 0x1001, 0x2000
+TV_ORDER_FULL_SORT, TV_ORDER_SELECT_ALWAYS = 23, 24   # tuning variants (csrc/imm3_handles.h): an ordered query with a limit always sorts every row / always selects
 
 
 class Imm3Error(Exception):
@@ -167,6 +170,7 @@ def load() -> C.CDLL:
     L.imm3_expr_normalize.argtypes = [vp, vp, i32, P(CSelect), i32, vp, i32, vp, i64, P(i64)]
     L.imm3_query_destroy.argtypes = [vp]
     L.imm3_query_reserve_rows.argtypes = [vp, u64]
+    L.imm3_query_set_order.argtypes = [vp, vp, i32, i64]
     L.imm3_query_run.argtypes = [vp]
     L.imm3_query_run_select.argtypes = [vp]
     L.imm3_query_run_count.argtypes = [vp]
@@ -675,6 +679,12 @@ class DeviceQuery:
     def reserve_rows(self, rows: int):
         _check(load().imm3_query_reserve_rows(self._h, rows))
 
+    def set_order(self, keys: Sequence[tuple], limit: int = 0):
+        """ORDER BY (imm3_query_set_order): keys = [(index into the SELECT list, descending)], most significant first; limit > 0: the
+        first `limit` rows of the ordered result.  Before the first run; row_count / fetch_rows then answer in that order."""
+        ks = np.array([[int(p), 1 if d else 0] for (p, d) in keys] or [[0, 0]], dtype=np.int32)
+        _check(load().imm3_query_set_order(self._h, ks.ctypes.data, len(keys), int(limit)))
+
     def run(self):
         _check(load().imm3_query_run(self._h))
 
@@ -757,11 +767,12 @@ class DeviceQuery:
 
     def plan(self) -> dict:
         """How the library planned this query (include/imm3_diag.h: imm3_query_plan)."""
-        v = np.zeros(11, np.int64)
-        _check(load().imm3_query_plan(self._h, v.ctypes.data, 11))
+        v = np.zeros(14, np.int64)
+        _check(load().imm3_query_plan(self._h, v.ctypes.data, 14))
         return {"single_pass": bool(v[0]), "P": int(v[1]), "grid": int(v[2]), "spans": int(v[3]), "records": bool(v[4]),
                 "rec_dwords": int(v[5]), "ran_single_pass": bool(v[6]), "run_syncs": int(v[7]),
-                "abandoned_runs": int(v[8]), "busy_runs": int(v[9]), "limit_gather_gave_up": int(v[10])}
+                "abandoned_runs": int(v[8]), "busy_runs": int(v[9]), "limit_gather_gave_up": int(v[10]),
+                "order_select_runs": int(v[11]), "order_full_runs": int(v[12]), "order_launches": int(v[13])}
 
     def agg_form(self) -> int:
         """The kernel form (AGG_FORM_*) of this aggregation's last launch, -1 before the first (include/imm3_diag.h)."""

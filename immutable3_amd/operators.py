@@ -24,7 +24,7 @@ import numpy as np
 from . import native
 from .native import Imm3Error
 from .query import (EQ, GT, LT, And, Avg, Count, Match, Max, Min, NoOp, NoSelect, NotMatch, Or, Project, ProjectAgg,
-                    Query, Select, SelectADT, SelectCondition, Sum)
+                    Query, Select, SelectADT, SelectCondition, Sum, order_keys)
 from .schema import CodecType, Column, Row, Table
 from .storage import SegmentManager
 
@@ -400,15 +400,44 @@ def _expr_of(op):
     return op.program if isinstance(op, SelectTreeOp) else None
 
 
-class ProjectOp(ProjectionOperator):
-    """Project.scala:17: ProjectOp(cols, op, limit = 0)."""
+def merge_ordered(parts, keys, limit: int = 0):
+    """The host merge of per-segment ordered results: parts = [(segIdx, row_index, [typed column arrays])], keys = [(index into the
+    columns, descending)].  Returns (segment int64[n], row int64[n], [column arrays]) ordered by (keys, segment, row) -- int columns as
+    signed integers, string columns (uint8[n, width]) byte-wise unsigned -- and cut to `limit` rows when limit > 0."""
+    parts = list(parts)
+    if not parts:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), []
+    seg = np.concatenate([np.full(np.asarray(ri).size, s, np.int64) for (s, ri, _) in parts])
+    row = np.concatenate([np.asarray(ri).astype(np.int64) for (_, ri, _) in parts])
+    cols = [np.concatenate([p[2][j] for p in parts]) for j in range(len(parts[0][2]))]
+    sort_keys = []                                              # most significant first
+    for (j, desc) in keys:
+        c = cols[j]
+        if c.ndim == 2:                                         # a string column: one key per byte
+            b = c.astype(np.int16)
+            sort_keys += [(255 - b[:, k]) if desc else b[:, k] for k in range(b.shape[1])]
+        else:
+            v = c.astype(np.int64)
+            sort_keys.append(-v if desc else v)
+    perm = np.lexsort(tuple([row, seg] + sort_keys[::-1]))
+    if limit > 0:
+        perm = perm[:limit]
+    return seg[perm], row[perm], [c[perm] for c in cols]
 
-    def __init__(self, cols: Sequence[str], op: ColumnVectorOperator, limit: int = 0):
+
+class ProjectOp(ProjectionOperator):
+    """Project.scala:17: ProjectOp(cols, op, limit = 0).  order_by -- entries (col, descending) over `cols`, most significant first -- is
+    the sort the reference announces and does not have (Query.scala:27): the rows come back in that order, sorted on the device
+    (imm3_query_set_order), and `limit` is applied after it."""
+
+    def __init__(self, cols: Sequence[str], op: ColumnVectorOperator, limit: int = 0, order_by=()):
         self.cols, self.op, self.limit = list(cols), op, limit
+        self.order_by = tuple(order_by)
+        self.order_keys = order_keys(self.cols, self.order_by)   # (ValueError: a key outside the SELECT list)
 
     @staticmethod
-    def mkProjectOp(cols: Sequence[str], limit: int = 0):       # Project.scala:8-15
-        return lambda op: ProjectOp(cols, op, limit)
+    def mkProjectOp(cols: Sequence[str], limit: int = 0, order_by=()):       # Project.scala:8-15
+        return lambda op: ProjectOp(cols, op, limit, order_by)
 
     def _fused(self):
         if isinstance(self.op, ScanOp):
@@ -423,7 +452,9 @@ class ProjectOp(ProjectionOperator):
         for (_, cond) in leaves:
             if not isinstance(cond, (Match, GT, LT, EQ)):
                 raise Exception(f"Unsupported condition: {cond}")
-        q = scan._query(leaves, self.cols, self.limit, _expr_of(self.op))
+        q = scan._query(leaves, self.cols, 0 if self.order_keys else self.limit, _expr_of(self.op))
+        if self.order_keys:
+            q.set_order(self.order_keys, self.limit)               # (the limit is applied behind the order: no creation-time limit)
         q.run()
         idx, cols = q.fetch_rows()
         out = []
@@ -447,6 +478,9 @@ class ProjectOp(ProjectionOperator):
         """ProjectIterator over batches from a non-fusable upstream (e.g. a queue of batches from several
         segments, Engine.scala:190-191).  Row materialisation is Project.scala:50-63; batches without
         survivors are skipped (the reference faults on them)."""
+        if self.order_keys:
+            yield from self._host_ordered()
+            return
         total = 0
         for vec in self.op.iterator():
             names = [c.name for c in vec.columns]
@@ -458,6 +492,36 @@ class ProjectOp(ProjectionOperator):
                 total += 1
             if self.limit > 0 and total >= self.limit:
                 return
+
+
+    def _host_ordered(self) -> Iterator[Row]:
+        """the same over a non-fusable upstream with an order: every row, then a stable sort by the keys"""
+        rows = []
+        for vec in self.op.iterator():
+            names = [c.name for c in vec.columns]
+            vec_cols = [names.index(c) for c in self.cols]
+            for pos in vec.selected.toList():
+                rows.append([vec.columnVectors[j].data[pos] for j in vec_cols])     # (raw: a string's bytes order it, not its decoding)
+        rows = _stable_by_keys(rows, self.order_keys)
+        for r in rows[: self.limit] if self.limit > 0 else rows:
+            yield Row(*[_value(x) for x in r])
+
+
+def _stable_by_keys(rows, keys):
+    """rows (lists of raw values: numpy ints, uint8 arrays for strings) in (keys, arrival) order: ints compare as signed integers,
+    strings byte-wise unsigned"""
+    import functools
+
+    def val(v):
+        return bytes(v) if isinstance(v, np.ndarray) else int(v)
+
+    def cmp(a, b):
+        for (j, desc) in keys:
+            x, y = val(a[1][j]), val(b[1][j])
+            if x != y:
+                return (1 if x < y else -1) if desc else (-1 if x < y else 1)
+        return a[0] - b[0]
+    return [r for (_, r) in sorted(enumerate(rows), key=functools.cmp_to_key(cmp))]
 
 
 # ------------------------------------------------------------------------------------------
@@ -825,7 +889,7 @@ class Engine:
         used = getColumns(query, table)
         leaves = self._select_ops(query)
         mk_scan = ScanOp.mkScanOp(self.sm, query.table)
-        mk_proj = ProjectOp.mkProjectOp(list(query.project.cols), query.project.limit)
+        mk_proj = ProjectOp.mkProjectOp(list(query.project.cols), query.project.limit, getattr(query.project, "order_by", ()))
         for segIdx in range(self.sm.getTableSegmentCount(table.name)):
             if not self.sm.owns(table.name, segIdx):
                 continue
@@ -958,12 +1022,15 @@ class Engine:
         dt, used, used_idx, sels, prog = plan
         names = [c.name for c in used]
         proj = [names.index(n) for n in query.project.cols]
+        okeys = order_keys(query.project.cols, getattr(query.project, "order_by", ()))
         try:
-            q = native.DeviceQuery(dt.ctx, dt, used_idx, sels, proj, query.project.limit, self.sm.getTable(query.table).blockSize, expr=prog)
+            q = native.DeviceQuery(dt.ctx, dt, used_idx, sels, proj, 0 if okeys else query.project.limit, self.sm.getTable(query.table).blockSize, expr=prog)
         except native.Imm3Error as e:
             if self._table_tree_refused(e, prog):
                 return None
             raise
+        if okeys:
+            q.set_order(okeys, query.project.limit)                 # ONE ordered table query: (keys, segment, row) order, then the limit
         q.run()
         idx, cols = q.fetch_rows()
         seg, row = q.locate_rows(idx)
@@ -987,6 +1054,13 @@ class Engine:
             yield from _rows_from_columns(fused[2])
             return
         limit = query.project.limit
+        okeys = order_keys(query.project.cols, getattr(query.project, "order_by", ()))
+        if okeys:
+            # per-segment ordered queries, each with the limit (no segment contributes more), then a stable host merge by
+            # (keys, segment, row)
+            _, _, cols = merge_ordered(self.execute_columns(query), okeys, limit)
+            yield from _rows_from_columns(cols)
+            return
         total = 0
         for _, proj in self.pipelines(query):
             for row in proj.iterator():

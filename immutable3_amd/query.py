@@ -82,14 +82,29 @@ class ProjectADT:
     pass
 
 
+def order_keys(cols, order_by):
+    """ORDER BY entries (col, descending) as places in the SELECT list `cols`: [(index, descending)].  A key that is not a
+    SELECT-list column raises ValueError naming it (order keys outside the SELECT list are out of scope: include/imm3.h)."""
+    cols = list(cols)
+    out = []
+    for (col, desc) in order_by:
+        if col not in cols:
+            raise ValueError(f"order by column {col!r} is not in the SELECT list {cols}")
+        out.append((cols.index(col), bool(desc)))
+    return out
+
+
 @dataclass(frozen=True)
-class Project(ProjectADT):         # Query.scala:29
+class Project(ProjectADT):         # Query.scala:29; order_by is the "sort" the reference announces above ProjectADT (Query.scala:27)
     cols: tuple
     limit: int = 0
+    order_by: tuple = ()           # entries (col, descending), most significant first; with it `limit` is applied AFTER the order
 
-    def __init__(self, cols, limit: int = 0):
+    def __init__(self, cols, limit: int = 0, order_by=()):
         object.__setattr__(self, "cols", tuple(cols))
         object.__setattr__(self, "limit", int(limit))
+        object.__setattr__(self, "order_by", tuple((str(c), bool(d)) for (c, d) in order_by))
+        order_keys(self.cols, self.order_by)
 
 
 @dataclass(frozen=True)

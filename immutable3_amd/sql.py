@@ -1,0 +1,254 @@
+"""SQLParser -- the SQL subset of engine/src/main/scala/immutabledb/sql/SQLParser.scala:8-129 as a backtracking recursive-descent
+parser with the semantics of scala-parser-combinators' JavaTokenParsers (the Python mirror of host/sql.hpp): whitespace is skipped
+before every literal / regex, literals match as PREFIXES (no word boundary), alternatives are tried in order with backtracking,
+parseAll must consume the whole input.
+
+  query            := queryProjectAgg | queryProjectAggNoGroup | queryProject
+  queryProject     := "select" repsep(ident, ",") "from" ident where limit
+  queryProjectAgg  := "select" rep1sep(agg, ",") "from" ident where ["group" "by" rep1sep(ident, ",")]
+  where            := opt("where" filter)
+  filter           := "(" repsep(filter,"and") ")" | "(" repsep(filter,"or") ")"
+                    | ident "=" value | ident "=" "'" value "'" | ident ">" value | ident "<" value
+  limit            := opt("limit" digits)
+  ident = [\\w#]+   value = [\\w0-9#]+
+
+EXTENSION, only when the parser is asked for it -- parseAll(sql, order_by=True) -- the "sort" core/Query.scala:27 announces:
+  queryProject     := "select" repsep(ident, ",") "from" ident where orderBy limit
+  orderBy          := opt("order" "by" rep1sep(ident opt("asc" | "desc"), ","))
+With the flag off the grammar is the reference's, and such a statement fails to parse."""
+from __future__ import annotations
+
+import re
+
+from . import query as Q
+
+_WORD = re.compile(r"[A-Za-z0-9_#]+")
+_DIGITS = re.compile(r"[0-9]+")
+
+
+class ParseError(Exception):
+    pass
+
+
+class SQLParser:
+    def __init__(self, s: str, order_by: bool = False):
+        self.s, self.order_by = s, order_by
+        self.furthest, self.expected = 0, "`select'"
+
+    @staticmethod
+    def parseAll(sql: str, order_by: bool = False) -> Q.Query:
+        p = SQLParser(sql, order_by)
+        r = p._query(0)
+        if r is not None:
+            q, end = r
+            end = p._ws(end)
+            if end == len(sql):
+                return q
+            raise ParseError(f"[1.{end + 1}] failure: end of input expected\n\n{sql}")
+        raise ParseError(f"[1.{p.furthest + 1}] failure: {p.expected} expected\n\n{sql}")
+
+    # ---- tokens ----
+    def _ws(self, i):
+        while i < len(self.s) and self.s[i].isspace():
+            i += 1
+        return i
+
+    def _note(self, at, what):
+        if at >= self.furthest:
+            self.furthest, self.expected = at, what
+
+    def _lit(self, i, word):
+        i = self._ws(i)
+        if self.s.startswith(word, i):
+            return i + len(word)
+        self._note(i, f"`{word}'")
+        return None
+
+    def _ident(self, i):
+        i = self._ws(i)
+        m = _WORD.match(self.s, i)
+        if not m:
+            self._note(i, "string matching regex `[\\w\\#]+'")
+            return None
+        return m.group(0), m.end()
+
+    @staticmethod
+    def _to_double(v: str) -> float:
+        try:
+            if v[-1:] in "dDfF" and v[:-1]:
+                return float(v[:-1])
+            return float(v)
+        except ValueError:
+            raise ParseError(f'NumberFormatException: For input string: "{v}"')
+
+    # ---- filters ----
+    def _filter_list(self, i, sep, is_and):
+        p = self._lit(i, "(")
+        if p is None:
+            return None
+        xs = []
+        r = self._filter(p)
+        if r is not None:
+            xs.append(r[0])
+            p = r[1]
+            while True:
+                t = self._lit(p, sep)
+                if t is None:
+                    break
+                r = self._filter(t)
+                if r is None:
+                    break
+                xs.append(r[0])
+                p = r[1]
+        q = self._lit(p, ")")
+        if q is None:
+            return None
+        if not xs:
+            raise ParseError("UnsupportedOperationException: tail of empty list")
+        acc = xs[0]
+        for x in xs[1:]:
+            acc = Q.And(acc, x) if is_and else Q.Or(acc, x)
+        return acc, q
+
+    def _cmp(self, i, op):
+        a = self._ident(i)
+        if a is None:
+            return None
+        q = self._lit(a[1], op)
+        if q is None:
+            return None
+        return a[0], q
+
+    def _filter(self, i):
+        for sep, is_and in (("and", True), ("or", False)):
+            r = self._filter_list(i, sep, is_and)
+            if r is not None:
+                return r
+        c = self._cmp(i, "=")
+        if c is not None:
+            v = self._ident(c[1])
+            if v is not None:
+                return Q.Select(c[0], Q.EQ(self._to_double(v[0]))), v[1]
+            t = self._lit(c[1], "'")
+            if t is not None:
+                v = self._ident(t)
+                if v is not None:
+                    u = self._lit(v[1], "'")
+                    if u is not None:
+                        return Q.Select(c[0], Q.Match([v[0]])), u
+        for op, mk in ((">", Q.GT), ("<", Q.LT)):
+            c = self._cmp(i, op)
+            if c is not None:
+                v = self._ident(c[1])
+                if v is not None:
+                    return Q.Select(c[0], mk(self._to_double(v[0]))), v[1]
+        return None
+
+    def _where(self, i):
+        p = self._lit(i, "where")
+        if p is not None:
+            r = self._filter(p)
+            if r is not None:
+                return r
+        return Q.NoSelect, i
+
+    def _from(self, i):
+        p = self._lit(i, "from")
+        return None if p is None else self._ident(p)
+
+    def _ident_list(self, i, at_least_one):
+        r = self._ident(i)
+        if r is None:
+            return None if at_least_one else ([], i)
+        out, p = [r[0]], r[1]
+        while True:
+            q = self._lit(p, ",")
+            r = self._ident(q) if q is not None else None
+            if r is None:
+                break
+            out.append(r[0])
+            p = r[1]
+        return out, p
+
+    def _agg(self, i):
+        for kw, mk in (("sum", Q.Sum), ("min", Q.Min), ("max", Q.Max), ("count", Q.Count)):
+            p = self._lit(i, kw)
+            q = self._lit(p, "(") if p is not None else None
+            r = self._ident(q) if q is not None else None
+            t = self._lit(r[1], ")") if r is not None else None
+            if t is not None:
+                return mk(r[0]), t
+        return None
+
+    def _select_agg(self, i):
+        q = self._lit(i, "select")
+        r = self._agg(q) if q is not None else None
+        if r is None:
+            return None
+        aggs, p = [r[0]], r[1]
+        while True:
+            c = self._lit(p, ",")
+            r = self._agg(c) if c is not None else None
+            if r is None:
+                break
+            aggs.append(r[0])
+            p = r[1]
+        return aggs, p
+
+    def _order_by(self, i):
+        """opt("order" "by" rep1sep(ident opt("asc" | "desc"), ",")): (keys, position behind the clause); no clause: ([], i)"""
+        p = self._lit(i, "order")
+        q = self._lit(p, "by") if p is not None else None
+        if q is None:
+            return [], i
+        keys = []
+        while True:
+            r = self._ident(q)
+            if r is None:
+                break
+            name, e = r
+            desc = False
+            t = self._lit(e, "desc")
+            if t is not None:
+                desc, e = True, t
+            else:
+                t = self._lit(e, "asc")
+                if t is not None:
+                    e = t
+            keys.append((name, desc))
+            q = e
+            t = self._lit(q, ",")
+            if t is None or self._ident(t) is None:      # (rep1sep backtracks over a dangling separator)
+                break
+            q = t
+        return (keys, q) if keys else ([], i)
+
+    def _query(self, i):
+        a = self._select_agg(i)
+        if a is not None:
+            t = self._from(a[1])
+            if t is not None:
+                w = self._where(t[1])
+                d = self._lit(w[1], "group")
+                e = self._lit(d, "by") if d is not None else None
+                g = self._ident_list(e, True) if e is not None else None
+                if g is not None:
+                    return Q.Query(t[0], w[0], Q.ProjectAgg(a[0], g[0])), g[1]
+                return Q.Query(t[0], w[0], Q.ProjectAgg(a[0])), w[1]
+        p = self._lit(i, "select")
+        if p is None:
+            return None
+        cols = self._ident_list(p, False)
+        t = self._from(cols[1])
+        if t is None:
+            return None
+        w = self._where(t[1])
+        d, order, limit = w[1], [], 0
+        if self.order_by:
+            order, d = self._order_by(d)
+        e = self._lit(d, "limit")
+        if e is not None:
+            m = _DIGITS.match(self.s, self._ws(e))
+            if m:
+                limit, d = int(m.group(0)), m.end()
+        return Q.Query(t[0], w[0], Q.Project(cols[0], limit, order)), d

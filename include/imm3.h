@@ -381,6 +381,35 @@ int imm3_query_fetch_group_keys(imm3_query *q, uint8_t *out, uint32_t max_groups
  * synchronises.  A run that outgrows the arrays, reserved or not, is detected when its rows are fetched and emitted again. */
 int imm3_query_reserve_rows(imm3_query *q, uint64_t rows);
 
+/* ---- ORDER BY: the "sort" core/Query.scala:27 announces above ProjectADT ("// add sort") and the reference does not have.
+ * Called on a PROJECTING query from any of the four creators (imm3_query_create, _create_expr, _create_table, _create_table_expr),
+ * before that query's first run; every later run then orders its projected rows on the device, behind the projection on the
+ * context's stream (no host synchronisation beyond the projection's own), and the row getters answer in that order.
+ *   keys    1 .. IMM3_ORDER_MAX_KEYS entries, keys[0] most significant; proj = index into the query's SELECT list (`proj` of the
+ *           creator), descending != 0 reverses THAT key only.  The key columns' widths sum to at most IMM3_ORDER_KEY_MAX_WIDTH bytes.
+ *   limit   > 0: the first `limit` rows of the ordered result (applied AFTER the order); <= 0: every row.
+ * Order: lexicographic over the keys.  int32 and int8 columns compare as signed integers (PFOR_INT / snappy columns are projected
+ * decoded: the same); STRING columns byte-wise unsigned, first byte most significant (String.compareTo for ASCII: the rule of the
+ * string MAX aggregate).  Rows whose keys are ALL equal stay in ascending row order -- (segment, row) of a table, i.e. the virtual
+ * row index -- under descending keys too: the result is a pure function of the data, bit-exact from run to run.  No null semantics:
+ * Int.MinValue and "\\N" are ordinary values.
+ * Getters of an ordered query: imm3_query_row_count = min(survivors, limit); imm3_query_fetch_rows = the ordered rows (row index
+ * and every SELECT-list column, permuted together).  imm3_query_count, _bitmap, _join_count, _segment_starts and _locate_rows are
+ * untouched: they describe the select, not the order.  The ordered rows live in arrays of their own (imm3_query_device_ptr
+ * IMM3_PTR_ORDER_*); ids 2, 3 and 16+j keep meaning the unordered projection.
+ * Errors: IMM3_ERR_ARG -- n_keys outside 1 .. 4, a `proj` out of range or repeated, key columns wider than 16 bytes together, a
+ * query without a SELECT list or an aggregation, a query that was CREATED with a limit > 0 (a creation-time limit stops the scan
+ * -- the reference's unordered Project.scala:73-80 -- and an order over the prefix it happened to emit has no meaning: create the
+ * query with limit <= 0 and pass the limit here; the message says so);
+ * IMM3_ERR_STATE -- the query has already run.  imm3_query_run of an ordered query inside imm3_ctx_capture_begin .. _end:
+ * IMM3_ERR_STATE (graph replay of ordered queries is not supported).
+ * OUT OF SCOPE: merging ordered results across ranks (imm3_comm_*), ordering aggregation results, order keys outside the SELECT
+ * list, graph capture of ordered runs. ---- */
+typedef struct { int32_t proj; int32_t descending; } imm3_order_key;   /* proj: index into the query's SELECT list */
+#define IMM3_ORDER_MAX_KEYS 4
+#define IMM3_ORDER_KEY_MAX_WIDTH 16   /* sum of the key columns' widths, bytes */
+int imm3_query_set_order(imm3_query *q, const imm3_order_key *keys, int32_t n_keys, int64_t limit);
+
 /* Enqueue the whole pipeline on the context's stream.  n_proj == 0: the scan+select kernel (selection bitmap + count).
  * Unlimited projection whose SELECT list is predicate columns only (one of them an int32 column, or >= 30 % of the rows
  * surviving), one uniform segment: ONE launch -- scan + select +
@@ -429,6 +458,11 @@ int imm3_query_fetch_rows(imm3_query *q, uint32_t *row_index_out, void *const *c
 /* Device-resident results for callers that stay on the GPU (RCCL count reduce, chained kernels).
  * which: 0 = bitmap (uint64 words), 1 = total count (one uint64), 2 = row indices (uint32),
  *        3 = emitted row count (one uint64), 4 = status word (one uint64), 16+j = projected column j.
+ *        Ordered queries (imm3_query_set_order) only -- on any other query these ids are what they always were (an unknown id, or
+ *        16+j of a very long SELECT list) --, null before the first run: IMM3_PTR_ORDER_ROW_INDEX (0x1000) = ordered row indices
+ *        (uint32), IMM3_PTR_ORDER_ROW_COUNT (0x1001) = ordered row count, min(survivors, limit) (one uint64), IMM3_PTR_ORDER_COLUMN
+ *        (0x2000) + j = ordered projected column j; complete behind every imm3_query_run whose unordered rows (2, 16+j) are -- after
+ *        a run that outgrew its arrays or gave up on its rows, imm3_query_row_count orders again.
  * What a device-side consumer may rely on behind a run, without any host getter in between:
  *   - bitmap (0), count (1) and emitted row count (3) are exact after EVERY run.  In particular the one-launch projection
  *     (csrc/imm3_project.hip), whose work-groups wait on each other, degrades to "count + bitmap" when such a wait does not
@@ -450,6 +484,9 @@ int imm3_query_fetch_rows(imm3_query *q, uint32_t *row_index_out, void *const *c
  *     and an aggregation whose select chain rides in the aggregation launch.  imm3_query_bitmap materialises it on demand (the
  *     select chain runs once more); a DEVICE consumer of pointer 0 calls imm3_query_run_select.  The COUNT (1) is exact behind
  *     every imm3_query_run -- except for such an aggregation, where imm3_query_join_count / imm3_query_count produce it. */
+#define IMM3_PTR_ORDER_ROW_INDEX 0x1000
+#define IMM3_PTR_ORDER_ROW_COUNT 0x1001
+#define IMM3_PTR_ORDER_COLUMN 0x2000
 int imm3_query_device_ptr(imm3_query *q, int32_t which, void **ptr);
 
 /* ---- multi-GPU: the count reduce.  Segments shard one per GPU -- segment s belongs to GPU s mod G -- and

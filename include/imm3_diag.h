@@ -16,7 +16,8 @@ extern "C" {
 /* ---- live kernel timing (HIP events on the context's stream) ----
  * When enabled, every kernel launch of this context is bracketed by an event pair.
  * kernel ids: 0 = scan+select, 1 = offsets scan, 2 = compact+gather, 3 = count reduce, 4 = group-by aggregation,
- *             5 = PFOR_INT / snappy column decode, 6 = refine pass of a MAX over a string wider than 8 bytes (one per pass). */
+ *             5 = PFOR_INT / snappy column decode, 6 = refine pass of a MAX over a string wider than 8 bytes (one per pass),
+ *             7 = ORDER BY of an ordered query: ONE record per order, from its first kernel's start to its last one's end. */
 int imm3_ctx_timing_enable(imm3_ctx *ctx, int32_t max_records);
 int imm3_ctx_timing_reset(imm3_ctx *ctx);
 /* Only launches whose kernel id has its bit set in `kernel_mask` are bracketed (default: all). */
@@ -53,7 +54,8 @@ int imm3_ctx_measure_read_gbps(imm3_ctx *ctx, uint64_t bytes, int32_t iters, dou
  * CU per XCD is left to the collective's kernel), 17 = an aggregation's select chain runs as its own launch instead of inside the
  * aggregation launch, 18 = group keys wider than 8 bytes hash to 3 bits, so that distinct keys collide by construction (tests of
  * the exactness of the key compare), 19 = a projection through survivor records stores its bitmap in the staging launch (default: the bitmap is
- * materialised when imm3_query_bitmap asks), 20 - 22 and 34 - 35 = ablation switches of k_filter_tile and k_emit (tools' build,
+ * materialised when imm3_query_bitmap asks), 23 = an ordered query with a limit sorts every row (no radix select: the
+ * yardstick of tests/test_gpu_zz_perf_order.py), 24 = it takes the radix select whenever the limit is below the survivors, 20 - 22 and 34 - 35 = ablation switches of k_filter_tile and k_emit (tools' build,
  * libimm3_ablate.so, only), 50 + mask = ablation mask of k_filter_project (tools' build), 100 + AggForm = the aggregation starts at
  * that kernel form, 140 and above = aggregation ablations (tools' build), 200 + P = fixed tiles per range.  The names of these
  * numbers are csrc/imm3_handles.h's TuningVariant. */
@@ -75,7 +77,10 @@ int imm3_plan_predict(int64_t n_rows, const int32_t *pred_width, const int32_t *
  * out[8] / out[9] = single-pass runs of this query whose rows a getter had to gather from the bitmap because the launch gave up on
  * them: a look-back wait timed out (the query keeps the bitmap path from then on) / another launch of the kernel owned the device
  * (that run only); out[10] = runs whose small-limit gather (k_limit_gather) ran into its look-back poll cap, so that a getter
- * gathered the rows again with k_scan + k_gather.  n <= 11 values. */
+ * gathered the rows again with k_scan + k_gather.
+ * Ordered queries (imm3_query_set_order), the tail: out[11] / out[12] = ordered runs, as far as a row getter has settled them, that
+ * took the radix select in front of the sort (0 < limit, survivors >= 4 x limit) / that sorted every row; out[13] = times the order
+ * has been enqueued (once per run, once more whenever a getter had to emit the rows again).  n <= 14 values. */
 int imm3_query_plan(const imm3_query *q, int64_t *out, int32_t n);
 
 /* imm3_query_agg_form: the kernel form of an aggregation's last launch (csrc/imm3_internal.h's AggForm: 0 = lanes (63 keys), 1 = lanes
