@@ -46,6 +46,7 @@ static void pool_drain(imm3_ctx *ctx) { ctx->blocks.drain(); }
 static const char *cond_name(int c) {
     switch (c) {
     case IMM3_MATCH: return "Match";
+    case IMM3_STR_RANGE: return "StrRange";
     case IMM3_NOTMATCH: return "NotMatch";
     case IMM3_EQ: return "EQ";
     case IMM3_GT: return "GT";
@@ -1050,10 +1051,15 @@ static int check_create_args(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
     // whether or not the segment has any block.
     for (int32_t i = 0; i < n_sels; ++i) {
         const int c = sels[i].cond;
-        if (c != IMM3_MATCH && c != IMM3_GT && c != IMM3_LT && c != IMM3_EQ)
+        if (c != IMM3_MATCH && c != IMM3_GT && c != IMM3_LT && c != IMM3_EQ && c != IMM3_STR_RANGE)
             return fail(IMM3_ERR_UNSUPPORTED_CONDITION, std::string("Unsupported condition: ") + cond_name(c));
         if (c == IMM3_MATCH && sels[i].n_match > 0 && (!sels[i].match_bytes || !sels[i].match_lens))
             return fail(IMM3_ERR_ARG, "Match without values");
+        if (c == IMM3_STR_RANGE) { // (the bounds' lengths are held against a STRING column's width; any other column fails scan_layout's vector check)
+            const SegCol &sc = seg->cols[(size_t)used_cols[sels[i].column]];
+            const int rrc = str_range_check_leaf(sels[i].n_match, sels[i].match_bytes, sels[i].match_lens, sc.vcodec == IMM3_DENSE_STRING ? sc.width : 0);
+            if (rrc) return rrc;
+        }
     }
     return IMM3_OK;
 }
@@ -1096,7 +1102,7 @@ static int scan_layout(imm3_query *q, const imm3_select *sels, int32_t n_sels, i
     for (int32_t i = 0; i < n_sels; ++i) {
         const SegCol &sc = q->seg->cols[(size_t)q->used[(size_t)sels[i].column]];
         const bool is_str = sc.vcodec == IMM3_DENSE_STRING;
-        if ((sels[i].cond == IMM3_MATCH) != is_str) return fail(IMM3_ERR_UNSUPPORTED_VECTOR, "Unsupported column vector");
+        if ((sels[i].cond == IMM3_MATCH || sels[i].cond == IMM3_STR_RANGE) != is_str) return fail(IMM3_ERR_UNSUPPORTED_VECTOR, "Unsupported column vector");
     }
     return IMM3_OK;
 }
@@ -1115,7 +1121,9 @@ static int fold_selects(imm3_query *q, const imm3_select *sels, int32_t n_sels) 
         else merge_pred(*fp, leaf);
     }
     for (const auto &p : q->preds)
-        if (p.kind == KIND_STR ? p.match.empty() : p.lo > p.hi) q->always_false = true;
+        if (p.has_range ? pred_empty(p) : (p.kind == KIND_STR ? p.match.empty() : p.lo > p.hi)) q->always_false = true;
+    // a range every row passes leaves its column: a query left without predicates is the NoSelect form
+    q->preds.erase(std::remove_if(q->preds.begin(), q->preds.end(), [](const FoldedPred &p) { return p.has_range && pred_unconstrained(p); }), q->preds.end());
     return IMM3_OK;
 }
 
@@ -1147,6 +1155,14 @@ const char *const imm3::kTableGenericRefusal =
     "table queries take int32 / int8 predicates, Match on 2-byte string columns with at most 8 IN-list values, and Match on string "
     "columns whose width is a multiple of 4 (4 .. 256 bytes, any IN-list); still refused: string columns of any other width and "
     "2-byte string columns with more than 8 values; use per-segment queries";
+
+// ... and a range (IMM3_STR_RANGE) goes through its string pass or not at all
+const char *const imm3::kTableRangeRefusal =
+    "table queries take a string range (IMM3_STR_RANGE) on string columns whose width is a multiple of 4 (4 .. 256 bytes) only: a table "
+    "has no word-at-a-time kernel for the other widths; use per-segment queries";
+static const char *const kTreeRangeRefusal =
+    "a select program with an IMM3_EXPR_OR or an IMM3_EXPR_NOT does not take IMM3_STR_RANGE leaves (its normal form would need "
+    "complemented ranges and ranges with exclusions); a program of IMM3_EXPR_AND alone does";
 
 static int upload_match_blobs(imm3_query *q, std::vector<FoldedPred> &preds);
 
@@ -1260,9 +1276,14 @@ static int place_compressed(imm3_query *q, bool have_batches, const std::vector<
 // Step 5: IN-lists too long for the kernel arguments go to the device.
 static int upload_match_blobs(imm3_query *q, std::vector<FoldedPred> &preds) {
     for (auto &p : preds) {
-        if (p.kind != KIND_STR || p.match.empty() || (p.width <= 8 && p.match.size() <= (size_t)kMaxMatch)) continue;
+        if (p.kind != KIND_STR || (!p.has_range && (p.match.empty() || (p.width <= 8 && p.match.size() <= (size_t)kMaxMatch)))) continue;
         std::string blob;
         for (auto &v : p.match) blob += v;
+        if (p.has_range) { // (always on the device: the bounds byte for byte, then dword-swapped for the string pass's tails)
+            std::vector<uint8_t> packed;
+            str_range_pack(p.range_lo, p.range_hi, packed, p.range_lo4, p.range_hi4);
+            blob.assign(packed.begin(), packed.end());
+        }
         void *d = nullptr;
         HIPCHK(pool_alloc(q->ctx, &d, blob.size()));
         p.d_blob = (uint8_t *)d;
@@ -1352,6 +1373,9 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
     auto check_program = [&]() -> int {
         const int prc = expr_check_program(prog, n_prog, n_sels, &has_or, &has_not);
         if (prc) return prc;
+        if (has_or || has_not)
+            for (int32_t i = 0; i < n_sels; ++i)
+                if (sels[i].cond == IMM3_STR_RANGE) return fail(IMM3_ERR_ARG, kTreeRangeRefusal);
         if (!has_or && !has_not) {
             for (int32_t i = 0; i < n_prog; ++i)
                 if (prog[i] >= 0) flat.push_back(sels[prog[i]]);
@@ -1382,7 +1406,7 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
     rc = place_compressed(q.get(), nb >= 1, row_cols); if (rc) return rc;
     if (table) // (a flat select list; a tree's terms are checked by expr_setup)
         for (const FoldedPred &p : q->preds)
-            if (pred_route(p) == 2 && !p.match.empty()) return fail(IMM3_ERR_ARG, kTableGenericRefusal);
+            if (pred_route(p) == 2 && (p.has_range ? !q->always_false : !p.match.empty())) return fail(IMM3_ERR_ARG, p.has_range ? kTableRangeRefusal : kTableGenericRefusal);
     rc = upload_match_blobs(q.get(), q->preds); if (rc) return rc;
     if (q->is_expr) { rc = expr_setup(q.get()); if (rc) return rc; }
     rc = alloc_buffers(q.get()); if (rc) return rc;

@@ -79,6 +79,7 @@ typedef std::vector<FoldedPred> ExprTerm;             // a conjunction: at most 
 int leaf_pred(int32_t seg_col, int32_t vcodec, int32_t width, const imm3_select &leaf, FoldedPred &out); // one leaf alone
 void merge_pred(FoldedPred &into, const FoldedPred &other);                                             // ... AND another on the same column
 bool pred_empty(const FoldedPred &p);                                                                    // no value passes
+bool pred_unconstrained(const FoldedPred &p);                                                            // every value passes
 int expr_check_program(const int32_t *prog, int32_t n_prog, int32_t n_leaves, bool *has_or, bool *has_not); // IMM3_ERR_ARG: malformed; the out-flags (may be null): an IMM3_EXPR_OR / an IMM3_EXPR_NOT in it
 int expr_normalize(const std::vector<ExprCol> &leaf_cols, const imm3_select *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog,
                    std::vector<ExprTerm> &terms);
@@ -86,6 +87,20 @@ int expr_normalize(const std::vector<ExprCol> &leaf_cols, const imm3_select *lea
 // ---- imm3_order_args.cpp: the argument checks of imm3_query_set_order, over plain values ----
 int order_check_args(bool is_agg, int32_t n_proj, const int32_t *proj_widths, int64_t create_limit, bool has_run,
                      const imm3_order_key *keys, int32_t n_keys, int64_t limit, int32_t *key_bytes_out);
+
+// ---- imm3_str_range.cpp: IMM3_STR_RANGE over plain values ----
+int str_range_check_leaf(int32_t n_match, const uint8_t *bytes, const int32_t *lens, int32_t width);   // the leaf's own checks (width <= 0: not held against a column)
+void str_range_pad(const uint8_t *lo, int32_t lo_len, const uint8_t *hi, int32_t hi_len, int32_t width, std::string &lo_out, std::string &hi_out);
+bool str_range_empty(const std::string &lo, const std::string &hi);                                      // lo' > hi'
+bool str_range_full(const std::string &lo, const std::string &hi);                                       // every row passes
+bool str_range_holds(const std::string &lo, const std::string &hi, const std::string &v);
+void str_range_intersect(std::string &lo, std::string &hi, const std::string &lo2, const std::string &hi2);
+void str_range_filter_match(const std::string &lo, const std::string &hi, std::vector<std::string> &match);
+bool str_range_successor(std::string &v);
+bool str_range_predecessor(std::string &v);
+int str_range_route(int32_t width);
+void str_range_pack(const std::string &lo, const std::string &hi, std::vector<uint8_t> &blob, uint32_t lo4[4], uint32_t hi4[4]);
+extern const char *const kTableRangeRefusal;                          // a table has no word-at-a-time kernel: a range on a width the string pass does not take
 
 // ---- imm3_planner.cpp ----
 constexpr int kSampleChunks = 8;                                      // the sample a plan is made on: eight chunks of 64 tiles spread over the segment / table

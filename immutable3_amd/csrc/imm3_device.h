@@ -166,6 +166,17 @@ __device__ __forceinline__ void block_partial_finish(unsigned long long *finish,
 // SelectIteratorMatch (Select.scala:25-51): keep the row iff its `width` raw bytes equal one IN-list value.
 __device__ __forceinline__ bool match_row(const ColPred &c, int64_t row) {
     const uint8_t *p = (const uint8_t *)c.data + row * (int64_t)c.width;
+    if (c.range) { // IMM3_STR_RANGE: lo' <= row <= hi' in unsigned byte order -- against each bound the first byte that differs decides
+        const uint8_t *lo = c.match_blob, *hi = lo + c.width;
+        bool tie_lo = true, tie_hi = true, in = true;
+        for (int b = 0; b < c.width; ++b) {
+            const uint32_t x = p[b], l = lo[b], h = hi[b];
+            in = in && !(tie_lo && x < l) && !(tie_hi && x > h);
+            tie_lo = tie_lo && x == l;
+            tie_hi = tie_hi && x == h;
+        }
+        return in;
+    }
     bool found = false;
     if (c.match_in_args) {
         uint64_t v = 0;

@@ -15,11 +15,26 @@
 
 namespace imm3 {
 
+// The range logic is a unit of its own (imm3_str_range.cpp) and a WEAK reference from this file: the normaliser is also built
+// without it (tests/native/expr_not_asan.cpp links this file alone), where a range leaf is refused instead of folded.
+__attribute__((weak)) int str_range_check_leaf(int32_t n_match, const uint8_t *bytes, const int32_t *lens, int32_t width);
+__attribute__((weak)) void str_range_pad(const uint8_t *lo, int32_t lo_len, const uint8_t *hi, int32_t hi_len, int32_t width, std::string &lo_out, std::string &hi_out);
+__attribute__((weak)) bool str_range_empty(const std::string &lo, const std::string &hi);
+__attribute__((weak)) bool str_range_full(const std::string &lo, const std::string &hi);
+__attribute__((weak)) void str_range_intersect(std::string &lo, std::string &hi, const std::string &lo2, const std::string &hi2);
+__attribute__((weak)) void str_range_filter_match(const std::string &lo, const std::string &hi, std::vector<std::string> &match);
+
 // One SelectOp leaf on a column of DENSE_* codec `vcodec`: GT / LT / EQ narrow the column type's full interval (threshold narrowed
 // per leaf: d.toInt / d.toByte, Select.scala:65,73), Match keeps the values of exactly `width` bytes, each once.
 int leaf_pred(int32_t seg_col, int32_t vcodec, int32_t width, const imm3_select &leaf, FoldedPred &out) {
     out = unfolded_pred(seg_col, vcodec, width);
-    if (out.kind == KIND_STR) {
+    if (out.kind == KIND_STR && leaf.cond == IMM3_STR_RANGE) { // lo' <= row <= hi' (imm3_str_range.cpp)
+        if (!str_range_check_leaf || !str_range_pad) return fail(IMM3_ERR_ARG, "IMM3_STR_RANGE: this build holds no range logic");
+        const int rc = str_range_check_leaf(leaf.n_match, leaf.match_bytes, leaf.match_lens, width);
+        if (rc) return rc;
+        out.has_range = true;
+        str_range_pad(leaf.match_bytes, leaf.match_lens[0], leaf.match_bytes + leaf.match_lens[0], leaf.match_lens[1], width, out.range_lo, out.range_hi);
+    } else if (out.kind == KIND_STR) {
         int64_t off = 0;
         for (int32_t m = 0; m < leaf.n_match; ++m) {
             const int32_t len = leaf.match_lens[m];
@@ -44,7 +59,20 @@ int leaf_pred(int32_t seg_col, int32_t vcodec, int32_t width, const imm3_select 
 // IN and NOT-IN: the IN-list minus the exclusions (still an IN-list, maybe empty); NOT-IN and NOT-IN: the union of the exclusions,
 // first seen first
 void merge_pred(FoldedPred &into, const FoldedPred &other) {
-    if (into.kind == KIND_STR) {
+    if (into.kind == KIND_STR && (into.has_range || other.has_range)) {
+        // two ranges: their intersection; a range and an IN-list: the list's values inside the range -- an ordinary Match from here on
+        // (a program with an OR or a NOT takes no range: neither side is negated)
+        if (into.has_range && other.has_range) str_range_intersect(into.range_lo, into.range_hi, other.range_lo, other.range_hi);
+        else {
+            const FoldedPred &r = into.has_range ? into : other;
+            std::vector<std::string> list = into.has_range ? other.match : into.match;
+            str_range_filter_match(r.range_lo, r.range_hi, list);
+            into.match = list;
+            into.has_range = false;
+            into.range_lo.clear();
+            into.range_hi.clear();
+        }
+    } else if (into.kind == KIND_STR) {
         const auto has = [](const std::vector<std::string> &l, const std::string &v) { return std::find(l.begin(), l.end(), v) != l.end(); };
         if (into.negated && other.negated) {
             for (auto &v : other.match)
@@ -64,10 +92,14 @@ void merge_pred(FoldedPred &into, const FoldedPred &other) {
     }
 }
 
-bool pred_empty(const FoldedPred &p) { return p.kind == KIND_STR ? (!p.negated && p.match.empty()) : p.lo > p.hi; } // (a NOT-IN is never empty)
+bool pred_empty(const FoldedPred &p) { // (a NOT-IN is never empty)
+    if (p.kind == KIND_STR && p.has_range) return str_range_empty(p.range_lo, p.range_hi);
+    return p.kind == KIND_STR ? (!p.negated && p.match.empty()) : p.lo > p.hi;
+}
 
 // every value passes: the column type's full interval, or a NOT-IN without exclusions (only a complement makes one)
 bool pred_unconstrained(const FoldedPred &p) {
+    if (p.kind == KIND_STR && p.has_range) return str_range_full(p.range_lo, p.range_hi);
     if (p.kind == KIND_STR) return p.negated && p.match.empty();
     const FoldedPred full = unfolded_pred(p.seg_col, p.kind == KIND_I32 ? IMM3_DENSE_INT : IMM3_DENSE_TINYINT, p.width);
     return p.lo <= full.lo && p.hi >= full.hi;

@@ -245,6 +245,9 @@ struct FoldedPred { // all SelectOp leaves on one segment column, folded
     int64_t lo = 0, hi = 0;                // numeric closed interval
     std::vector<std::string> match;        // string: surviving IN-list values (each exactly width bytes)
     bool negated = false;                  // string, select trees only: `match` are EXCLUSIONS -- every value but these passes (a complemented Match)
+    bool has_range = false;                // string: a byte-order range INSTEAD of an IN-list (IMM3_STR_RANGE; `match` is empty, never negated):
+    std::string range_lo, range_hi;        // ... the padded bounds, `width` bytes each, lo' <= row <= hi' (imm3_str_range.cpp)
+    uint32_t range_lo4[4] = {0, 0, 0, 0}, range_hi4[4] = {0, 0, 0, 0}; // ... their first 16 bytes as the string pass's kernel arguments (str_range_pack)
     uint8_t *d_blob = nullptr;             // device copy when it does not fit the kernel arguments
     bool pfor = false;                     // PFOR_INT column evaluated on its compressed blocks (k_filter_pfor)
 };

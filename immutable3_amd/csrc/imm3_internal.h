@@ -47,7 +47,8 @@ struct ColPred {
     int32_t n_match;             // string: IN-list size
     int32_t match_in_args;       // 1: width <= 8 and n_match <= kMaxMatch -> values packed in match[]
     int32_t negated;             // string, select trees only (k_filter_expr_generic): 1 = keep the rows that equal NONE of the values
-    int32_t pad;
+    int32_t range;               // string: 1 = a byte-order range (IMM3_STR_RANGE): keep the rows with lo' <= row <= hi', the bounds (width bytes each,
+                                 // lo' then hi') at match_blob; n_match is 0
     uint64_t match[kMaxMatch];   // value bytes packed little-endian (byte 0 = first character)
     const uint8_t *match_blob;   // otherwise: n_match * width bytes in device memory
 };
@@ -330,6 +331,21 @@ struct StrRowsArgs {
 bool str_rows_width_ok(int32_t width);            // a multiple of 4 in 4 .. 256
 int str_rows_grid(int64_t n_tiles, int grid_blocks);
 bool launch_filter_str_rows(const StrRowsArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // false: no instance for this width
+// ---- k_filter_str_range (imm3_strmatch.hip): lo' <= row <= hi' in byte order on one such column; k_filter_str_rows' geometry and grid ----
+struct StrRangeArgs {
+    const void *data;                // flat (decoded) column in HBM, 16-byte aligned
+    int32_t width;                   // bytes per row: a multiple of 4, 4 .. 256
+    int32_t and_existing;            // 1: AND into the bitmap already in memory
+    uint32_t lo[kStrPrefixDwords];   // the first min(width, 16) bytes of lo' and hi', each dword's bytes swapped (its first byte most
+    uint32_t hi[kStrPrefixDwords];   // significant): unsigned dword order is then byte order
+    const uint32_t *tails;           // device memory: all width / 4 swapped dwords of lo', then of hi' (read for widths above 16 bytes only)
+    int64_t n_rows, n_words, n_tiles;
+    uint64_t *bitmap;                // allocated in whole tiles
+    uint32_t *block_partials;
+    const uint32_t *tile_rows;       // table queries, as StrRowsArgs
+    const void *const *tile_ptrs;
+};
+bool launch_filter_str_range(const StrRangeArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // false: no instance for this width
 
 // ---- select trees (imm3_expr.hip): AND / OR over the leaves, as a disjunction of TERMS ----
 // The host rewrites a tree into terms (imm3_expr_norm.cpp): each term is a conjunction with at most one folded predicate per column --

@@ -76,8 +76,10 @@ int tile_kind(const FoldedPred &fp) {
     return TK_NONE;
 }
 
-// A string predicate k_filter_str_rows takes (imm3_strmatch.hip): a row is a whole number of dwords, 4 .. 256 bytes; any IN-list.
+// A string predicate the string pass takes (imm3_strmatch.hip): a row is a whole number of dwords, 4 .. 256 bytes; any IN-list
+// (k_filter_str_rows) or a byte-order range (k_filter_str_range; str_range_route says the same of the width).
 bool str_rows_pred(const FoldedPred &fp) {
+    if (fp.kind == KIND_STR && fp.has_range) return !fp.pfor && str_range_route(fp.width) == 1;
     return fp.kind == KIND_STR && !fp.pfor && str_rows_width_ok(fp.width) && !fp.match.empty();
 }
 

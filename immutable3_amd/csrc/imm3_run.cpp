@@ -33,6 +33,11 @@ void imm3::fill_colpred(const imm3_query *q, const FoldedPred &fp, ColPred &cp) 
     cp.negated = fp.negated ? 1 : 0;
     cp.match_in_args = (fp.kind == KIND_STR && !fp.d_blob) ? 1 : 0;
     cp.match_blob = fp.d_blob;
+    if (fp.has_range) { // the bounds, byte for byte, on the device: lo' then hi' (upload_match_blobs)
+        cp.range = 1;
+        cp.match_in_args = 0;
+        cp.n_match = 0;
+    }
     if (cp.match_in_args) {
         for (size_t m = 0; m < fp.match.size(); ++m) {
             uint64_t v = 0;
@@ -354,8 +359,35 @@ static int launch_pfor_pass(imm3_query *q, SelectRun &run, const FoldedPred &fp)
     return IMM3_OK;
 }
 
+// The string pass of a range (k_filter_str_range): the geometry, grid and tile table of k_filter_str_rows
+static int launch_str_range_pass(imm3_query *q, SelectRun &run, const FoldedPred &fp) {
+    imm3_ctx *ctx = q->ctx;
+    StrRangeArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.data = col_flat(q->seg->cols[(size_t)fp.seg_col]);
+    a.width = fp.width;
+    std::memcpy(a.lo, fp.range_lo4, sizeof(a.lo));
+    std::memcpy(a.hi, fp.range_hi4, sizeof(a.hi));
+    if (!fp.d_blob) return fail(IMM3_ERR_ARG, "internal: a string range without its bounds on the device");
+    a.tails = (const uint32_t *)(fp.d_blob + 2 * (size_t)fp.width); // (behind the byte-for-byte bounds: str_range_pack)
+    fill_pass_tail(q, run, a);
+    if (q->table) {
+        a.tile_rows = q->table->d_tile_rows;
+        a.tile_ptrs = (const void *const *)q->table->d_tile_ptrs[(size_t)fp.seg_col];
+    }
+    run.grid = str_rows_grid(q->n_tiles, ctx->grid_blocks);
+    {
+        LaunchTimer t(ctx, 0);
+        if (!launch_filter_str_range(a, run.grid, run.s, t.start, t.stop)) return fail(IMM3_ERR_ARG, "internal: no string range kernel for this column width");
+    }
+    HIPCHK(hipGetLastError());
+    ++run.pass;
+    return IMM3_OK;
+}
+
 // A string pass (k_filter_str_rows): one column whose width is a multiple of 4 per launch, a segment or a table's tile table
 static int launch_str_rows_pass(imm3_query *q, SelectRun &run, const FoldedPred &fp) {
+    if (fp.has_range) return launch_str_range_pass(q, run, fp);
     imm3_ctx *ctx = q->ctx;
     StrRowsArgs a;
     std::memset(&a, 0, sizeof(a));

@@ -6,6 +6,9 @@
 //                  Engine.scala:236-245).  With --parse-only it also prints the tree's postfix program.
 //   --order-by     accept `order by f [asc|desc] {, f [asc|desc]}` between the where clause and `limit` (default off: the reference's
 //                  grammar, in which such a statement does not parse); the rows come back sorted on the GPU, `limit` applied behind the order.
+//   --string-ranges  accept `f like 'value%'`, `f > 'value'` and `f < 'value'` on string columns (default off: the reference's grammar, in
+//                  which such a statement does not parse): byte-order prefix / range predicates, run on the GPU.  With --parse-only and a
+//                  data directory, the leaves of such conditions are also printed as the bytes the library gets ("leafbytes:").
 //   --explain      after the rows, one line on stderr: whether the query ran as one table query or per segment ("path: ...").
 #include <chrono>
 #include <cstdio>
@@ -50,7 +53,7 @@ static std::string showQuery(const Query &q) {
 int main(int argc, char **argv) {
     std::string query, dataDir;
     int device = 0, repeat = 0;
-    bool parseOnly = false, honourAndOr = false, explain = false, orderBy = false;
+    bool parseOnly = false, honourAndOr = false, explain = false, orderBy = false, stringRanges = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if ((a == "-q" || a == "--query") && i + 1 < argc) query = argv[++i];
@@ -60,16 +63,17 @@ int main(int argc, char **argv) {
         else if (a == "--parse-only") parseOnly = true;
         else if (a == "--honour-and-or") honourAndOr = true;
         else if (a == "--order-by") orderBy = true;
+        else if (a == "--string-ranges") stringRanges = true;
         else if (a == "--explain") explain = true;
         else if (a == "--repeat" && i + 1 < argc) repeat = std::atoi(argv[++i]); // re-run the query N times on the resident table, time to stderr
         else { std::fprintf(stderr, "Error parsing arguments: %s\n", a.c_str()); return 2; }
     }
     if (query.empty() || (dataDir.empty() && !parseOnly)) {
-        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only] [--honour-and-or] [--order-by] [--explain]\n");
+        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only] [--honour-and-or] [--order-by] [--string-ranges] [--explain]\n");
         return 2;
     }
     try {
-        const Query q = SQLParser::parseAll(query, orderBy);
+        const Query q = SQLParser::parseAll(query, orderBy, stringRanges);
         if (parseOnly) {
             std::cout << showQuery(q) << "\n";
             if (!dataDir.empty()) {
@@ -80,6 +84,16 @@ int main(int argc, char **argv) {
                 std::cout << "\nleaves:";
                 for (const auto &l : Engine::resolveSelectOps(q)) std::cout << " " << l.col << ":" << l.cond.toString();
                 std::cout << "\n";
+                if (stringRanges) { // the range leaves as the C ABI gets them: column:lo:hi, the bounds in hex
+                    auto hex = [](const std::string &b) { static const char *d = "0123456789abcdef"; std::string h; for (unsigned char ch : b) { h += d[ch >> 4]; h += d[ch & 15]; } return h; };
+                    std::cout << "leafbytes:";
+                    for (const auto &l : Engine::resolveSelectOps(q))
+                        if (l.cond.isStrRange()) {
+                            const auto b = l.cond.abiValues(t.getColumn(l.col).width());
+                            std::cout << " " << l.col << ":" << hex(b[0]) << ":" << hex(b[1]);
+                        }
+                    std::cout << "\n";
+                }
             }
             if (honourAndOr && SelectTreeOp::hasOr(*q.select)) { // leaf index | AND | OR, post-order (include/imm3.h: select trees)
                 std::vector<Leaf> leaves;

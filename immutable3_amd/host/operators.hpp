@@ -192,9 +192,9 @@ class ScanOp : public ColumnVectorOperator {
         for (size_t i = 0; i < leaves.size(); ++i) {
             sels[i] = imm3_select{};
             sels[i].column = usedIndex(leaves[i].col);
-            sels[i].cond = (int32_t)leaves[i].cond.kind;
+            sels[i].cond = leaves[i].cond.abiCond();
             sels[i].value = leaves[i].cond.value;
-            for (const auto &v : leaves[i].cond.values) { blobs[i] += v; lens[i].push_back((int32_t)v.size()); }
+            for (const auto &v : leaves[i].cond.abiValues(cols_[(size_t)sels[i].column].width())) { blobs[i] += v; lens[i].push_back((int32_t)v.size()); }
             sels[i].match_bytes = (const uint8_t *)blobs[i].data();
             sels[i].match_lens = lens[i].data();
             sels[i].n_match = (int32_t)lens[i].size();
@@ -227,9 +227,9 @@ class ScanOp : public ColumnVectorOperator {
             sels[i].column = -1;
             for (size_t k = 0; k < cols_.size(); ++k) if (cols_[k].name == leaves[i].col) { sels[i].column = (int32_t)k; break; }
             if (sels[i].column < 0) throw Exception("NoSuchElementException: next on empty iterator");
-            sels[i].cond = (int32_t)leaves[i].cond.kind;
+            sels[i].cond = leaves[i].cond.abiCond();
             sels[i].value = leaves[i].cond.value;
-            for (const auto &v : leaves[i].cond.values) { blobs[i] += v; lens[i].push_back((int32_t)v.size()); }
+            for (const auto &v : leaves[i].cond.abiValues(cols_[(size_t)sels[i].column].width())) { blobs[i] += v; lens[i].push_back((int32_t)v.size()); }
             sels[i].match_bytes = (const uint8_t *)blobs[i].data();
             sels[i].match_lens = lens[i].data();
             sels[i].n_match = (int32_t)lens[i].size();
@@ -775,11 +775,13 @@ class Engine {
                 const bool rows = isStr && !p.tree && c.width() % 4 == 0 && c.width() >= 4 && c.width() <= 256 && nv > 0;
                 if (!tile && !rows) return false;
             }
+            // a table takes a range on a string column whose width is a multiple of 4, in a flat select list only
+            if (leaves[i].cond.isStrRange() && !(c.columnType == ColumnType::STRING && !p.tree && c.width() % 4 == 0 && c.width() >= 4 && c.width() <= 256)) return false;
             p.sels[i] = imm3_select{};
             p.sels[i].column = ci;
-            p.sels[i].cond = (int32_t)leaves[i].cond.kind;
+            p.sels[i].cond = leaves[i].cond.abiCond();
             p.sels[i].value = leaves[i].cond.value;
-            for (const auto &v : leaves[i].cond.values) { p.blobs[i] += v; p.lens[i].push_back((int32_t)v.size()); }
+            for (const auto &v : leaves[i].cond.abiValues(c.width())) { p.blobs[i] += v; p.lens[i].push_back((int32_t)v.size()); }
             p.sels[i].match_bytes = (const uint8_t *)p.blobs[i].data();
             p.sels[i].match_lens = p.lens[i].data();
             p.sels[i].n_match = (int32_t)p.lens[i].size();

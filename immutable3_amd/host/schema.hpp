@@ -232,9 +232,45 @@ struct Row {
 
 // ---- Query ADT (Query.scala:3-46) ----
 struct SelectCondition {
-    enum Kind { Match, NotMatch, EQ, GT, LT, NoOp } kind = NoOp; // same order as IMM3_MATCH .. IMM3_NOOP
+    // Match .. NoOp: same order as IMM3_MATCH .. IMM3_NOOP.  EXTENSION, behind them: byte-order ranges on a string column (include/imm3.h:
+    // IMM3_STR_RANGE; the order of ORDER BY and the string MAX aggregate -- unsigned, byte-wise, from the first byte).  StrRange(lo, hi)
+    // is closed, lo padded to the column's width with 0x00 and hi with 0xFF; Prefix(p) = StrRange(p, p); StrGT(v) / StrLT(v) are strict,
+    // relative to v padded with 0x00.
+    enum Kind { Match, NotMatch, EQ, GT, LT, NoOp, StrRange, Prefix, StrGT, StrLT } kind = NoOp;
     double value = 0;                 // EQ / GT / LT
-    std::vector<std::string> values;  // Match / NotMatch
+    std::vector<std::string> values;  // Match / NotMatch; StrRange: {lo, hi}; Prefix / StrGT / StrLT: {the value}
+    static SelectCondition strRange(std::string lo, std::string hi) { SelectCondition c; c.kind = StrRange; c.values = {std::move(lo), std::move(hi)}; return c; }
+    static SelectCondition prefix(std::string p) { SelectCondition c; c.kind = Prefix; c.values = {std::move(p)}; return c; }
+    static SelectCondition strGT(std::string v) { SelectCondition c; c.kind = StrGT; c.values = {std::move(v)}; return c; }
+    static SelectCondition strLT(std::string v) { SelectCondition c; c.kind = StrLT; c.values = {std::move(v)}; return c; }
+    bool isStrRange() const { return kind >= StrRange; }
+    // what the C ABI's leaf carries: the condition code (a range form: 6, IMM3_STR_RANGE) and the values -- of a range form the leaf's
+    // {lo, hi} on a string column of `width` bytes.  StrGT(v) is from the successor of v padded with 0x00 on, StrLT(v) up to its
+    // predecessor (big-endian arithmetic over the column's width); where there is none the leaf is one no row passes (lo 01, hi 00:
+    // 01 00 00 .. > 00 FF FF ..).  A bound longer than the column throws (the library refuses it too).
+    int32_t abiCond() const { return isStrRange() ? 6 : (int32_t)kind; }
+    std::vector<std::string> abiValues(int width) const {
+        if (!isStrRange()) return values;
+        for (const auto &b : values)
+            if ((int)b.size() > width) throw Exception("string bound '" + b + "' is longer than the column's " + std::to_string(width) + " bytes");
+        if (kind == StrRange) return values;
+        if (kind == Prefix) return {values[0], values[0]};
+        std::string v = values[0];
+        v.resize((size_t)std::max(width, 0), '\0');
+        size_t i = v.size();
+        if (kind == StrGT) {
+            while (i > 0 && (unsigned char)v[i - 1] == 0xFF) --i;
+            if (i == 0) return {std::string("\x01"), std::string(1, '\0')};
+            v[i - 1] = (char)((unsigned char)v[i - 1] + 1);
+            for (size_t k = i; k < v.size(); ++k) v[k] = '\0';
+            return {v, std::string()};
+        }
+        while (i > 0 && (unsigned char)v[i - 1] == 0x00) --i;
+        if (i == 0) return {std::string("\x01"), std::string(1, '\0')};
+        v[i - 1] = (char)((unsigned char)v[i - 1] - 1);
+        for (size_t k = i; k < v.size(); ++k) v[k] = (char)0xFF;
+        return {std::string(), v};
+    }
     static SelectCondition match(std::vector<std::string> v) { SelectCondition c; c.kind = Match; c.values = std::move(v); return c; }
     static SelectCondition notMatch(std::vector<std::string> v) { SelectCondition c; c.kind = NotMatch; c.values = std::move(v); return c; }
     static SelectCondition eq(double d) { SelectCondition c; c.kind = EQ; c.value = d; return c; }
@@ -250,6 +286,10 @@ struct SelectCondition {
         case EQ: return "EQ(" + d.str() + ")";
         case GT: return "GT(" + d.str() + ")";
         case LT: return "LT(" + d.str() + ")";
+        case StrRange: return "StrRange(" + values[0] + "," + values[1] + ")";
+        case Prefix: return "Prefix(" + values[0] + ")";
+        case StrGT: return "StrGT(" + values[0] + ")";
+        case StrLT: return "StrLT(" + values[0] + ")";
         default: return "NoOp";
         }
     }

@@ -14,6 +14,10 @@
 //   queryProject     := "select" repsep(ident, ",") "from" ident where orderBy limit
 //   orderBy          := opt("order" "by" rep1sep(ident opt("asc" | "desc"), ","))
 // With the flag off the grammar is the reference's, and such a statement fails to parse as it always has.
+// EXTENSION, only when asked for (parseAll(sql, orderBy, true); imm3_sql --string-ranges) -- byte-order ranges on string columns
+// (SelectCondition::prefix / strGT / strLT), tried behind the reference's alternatives:
+//   filter           := ... | ident ">" "'" value "'" | ident "<" "'" value "'" | ident "like" "'" value "%" "'"
+// With the flag off those statements fail to parse with the message they have always given.
 //   ident = [\w#]+   value = [\w0-9#]+  (no sign, no decimal point)                          (:119-121)
 #pragma once
 
@@ -27,9 +31,10 @@ namespace immutabledb {
 
 class SQLParser {
   public:
-    static Query parseAll(const std::string &input, bool orderBy = false) {
+    static Query parseAll(const std::string &input, bool orderBy = false, bool stringRanges = false) {
         SQLParser p(input);
         p.orderBy_ = orderBy;
+        p.stringRanges_ = stringRanges;
         Query q;
         size_t end = 0;
         if (p.query(0, q, end)) {
@@ -44,7 +49,7 @@ class SQLParser {
     explicit SQLParser(const std::string &s) : s_(s) {}
     const std::string &s_;
     size_t furthest_ = 0;
-    bool orderBy_ = false;
+    bool orderBy_ = false, stringRanges_ = false;
     std::string expected_ = "`select'";
 
     size_t skipWs(size_t i) const {
@@ -138,6 +143,18 @@ class SQLParser {
             out = SelectADT::mkSelect(f, SelectCondition::lt(toDouble(v)));
             end = r;
             return true;
+        }
+        if (stringRanges_) { // filterGTString | filterLTString | filterLike
+            static const struct { const char *op; int kind; const char *tail; } forms[] = {{">", 0, ""}, {"<", 1, ""}, {"like", 2, "%"}};
+            for (const auto &fm : forms) {
+                size_t u = 0;
+                if (!(ident(i, f, p) && lit(p, fm.op, q) && lit(q, "'", r) && ident(r, v, t))) continue;
+                if (*fm.tail && !lit(t, fm.tail, t)) continue;
+                if (!lit(t, "'", u)) continue;
+                out = SelectADT::mkSelect(f, fm.kind == 0 ? SelectCondition::strGT(v) : fm.kind == 1 ? SelectCondition::strLT(v) : SelectCondition::prefix(v));
+                end = u;
+                return true;
+            }
         }
         return false;
     }

@@ -22,6 +22,9 @@ SNAPPY_INT, SNAPPY_TINYINT, SNAPPY_STRING = 16, 17, 18   # extension: blocks as 
 INT_CODECS, TINYINT_CODECS = (DENSE_INT, PFOR_INT, SNAPPY_INT), (DENSE_TINYINT, SNAPPY_TINYINT)
 # SelectCondition (core/src/main/scala/immutabledb/Query.scala:3-9)
 MATCH, NOTMATCH, EQ, GT, LT, NOOP = 0, 1, 2, 3, 4, 5
+# extension (include/imm3.h: IMM3_STR_RANGE): a closed byte-order range on a string column; operand (lo, hi), each 0 .. width bytes,
+# lo padded with 0x00 and hi with 0xFF
+STR_RANGE = 6
 # operators of a select tree's postfix program (include/imm3.h: IMM3_EXPR_AND / IMM3_EXPR_OR / IMM3_EXPR_NOT); values >= 0 are leaf
 # indices.  NOT pops one operand and pushes its complement (-4: -3 stays the unknown operator it has always been)
 EXPR_AND, EXPR_OR, EXPR_NOT = -1, -2, -4
@@ -58,7 +61,7 @@ DIAG_EXPORTS = [
     "imm3_ctx_timing_enable", "imm3_ctx_timing_reset", "imm3_ctx_timing_mask", "imm3_ctx_timing_collect", "imm3_ctx_set_tuning",
     "imm3_ctx_measure_read_gbps", "imm3_ctx_devclock_enable", "imm3_ctx_devclock_collect", "imm3_ctx_devclock_raw", "imm3_query_plan",
     "imm3_ctx_inject_fault", "imm3_ctx_debug_device_lock", "imm3_plan_predict", "imm3_comm_debug_standin", "imm3_plan_limit_scan",
-    "imm3_plan_table_limit", "imm3_plan_string_route", "imm3_plan_limit_chunks",
+    "imm3_plan_table_limit", "imm3_plan_string_route", "imm3_plan_string_range_route", "imm3_plan_limit_chunks",
     "imm3_query_agg_form", "imm3_query_expr_form", "imm3_expr_normalize",
 ]
 COMM_ID_BYTES = 128
@@ -525,7 +528,7 @@ def _cselects(sels):
         cs[i].cond = cond
         cs[i].value = 0.0
         cs[i].n_match = 0
-        if cond in (MATCH, NOTMATCH):
+        if cond in (MATCH, NOTMATCH, STR_RANGE):   # (STR_RANGE: the two bounds travel as Match's values do)
             vals = [bytes(v) for v in (operand or [])]
             blob = np.frombuffer(b"".join(vals) or b"\0", dtype=np.uint8).copy()
             lens = np.array([len(v) for v in vals] or [0], dtype=np.int32)
@@ -564,6 +567,14 @@ def plan_string_route(width: int, n_match: int = 1) -> int:
     L = load()
     L.imm3_plan_string_route.argtypes = [C.c_int32, C.c_int32]
     return int(L.imm3_plan_string_route(width, n_match))
+
+
+def plan_string_range_route(width: int) -> int:
+    """include/imm3_diag.h: imm3_plan_string_range_route -- the kernel a STR_RANGE leaf goes to on a uniform layout: 1 the string
+    pass (k_filter_str_range: widths 4, 8, ... 256), 2 the word-at-a-time kernel (what a table refuses), -1 outside 1 .. 256."""
+    L = load()
+    L.imm3_plan_string_range_route.argtypes = [C.c_int32]
+    return int(L.imm3_plan_string_range_route(width))
 
 
 def expr_normalize(col_codecs: Sequence[int], col_widths: Sequence[int], leaves: Sequence[tuple], prog: Sequence[int]):

@@ -23,6 +23,7 @@ import numpy as np
 
 from . import native
 from .native import Imm3Error
+from .query import (STR_RANGE_CONDS, str_range_bounds)
 from .query import (EQ, GT, LT, And, Avg, Count, Match, Max, Min, NoOp, NoSelect, NotMatch, Or, Project, ProjectAgg,
                     Query, Select, SelectADT, SelectCondition, Sum, order_keys)
 from .schema import CodecType, Column, Row, Table
@@ -197,7 +198,13 @@ class ProjectionOperator(Operator):    # Operator.scala:26-28
     pass
 
 
-def _cond_spec(cond: SelectCondition):
+SUPPORTED_CONDS = (Match, GT, LT, EQ) + STR_RANGE_CONDS      # what SelectOp.iterator lets through (Select.scala:17-23, and the range extension)
+
+
+def _cond_spec(cond: SelectCondition, width: int = 0):
+    """(native cond, operand) of one leaf; width: bytes of the leaf's column (the range forms are made for it)"""
+    if isinstance(cond, STR_RANGE_CONDS):
+        return native.STR_RANGE, list(str_range_bounds(cond, width))
     if isinstance(cond, Match):
         return native.MATCH, [v.encode("utf-8") if isinstance(v, str) else bytes(v) for v in cond.values]
     if isinstance(cond, NotMatch):
@@ -238,7 +245,7 @@ class ScanOp(ColumnVectorOperator):
             # `vec.columns...filter(_.name == col).head` (Select.scala:60): first used column of that name
             if col not in colnames:
                 raise Exception("NoSuchElementException: next on empty iterator")
-            code, operand = _cond_spec(cond)
+            code, operand = _cond_spec(cond, self.cols[colnames.index(col)].width)
             sels.append((colnames.index(col), code, operand))
         # Project.scala:32-35: vecCols maps each SELECT-list name to its position among the batch columns
         proj = []
@@ -325,7 +332,7 @@ class SelectOp(ColumnVectorOperator):
     def iterator(self):
         scan, leaves = self._chain()
         for (_, cond) in leaves:
-            if not isinstance(cond, (Match, GT, LT, EQ)):
+            if not isinstance(cond, SUPPORTED_CONDS):
                 raise Exception(f"Unsupported condition: {cond}")   # Select.scala:22
         return scan._batches(leaves)
 
@@ -390,7 +397,7 @@ class SelectTreeOp(ColumnVectorOperator):
     def iterator(self):
         scan, leaves = self._chain()
         for (_, cond) in leaves:
-            if not isinstance(cond, (Match, GT, LT, EQ)):
+            if not isinstance(cond, SUPPORTED_CONDS):
                 raise Exception(f"Unsupported condition: {cond}")   # Select.scala:22
         return scan._batches(leaves, self.program)
 
@@ -450,7 +457,7 @@ class ProjectOp(ProjectionOperator):
         """Fused execution; returns (row_index uint32[n], [typed numpy array per SELECT-list column])."""
         scan, leaves = self._fused()
         for (_, cond) in leaves:
-            if not isinstance(cond, (Match, GT, LT, EQ)):
+            if not isinstance(cond, SUPPORTED_CONDS):
                 raise Exception(f"Unsupported condition: {cond}")
         q = scan._query(leaves, self.cols, 0 if self.order_keys else self.limit, _expr_of(self.op))
         if self.order_keys:
@@ -693,7 +700,7 @@ class ProjectAggOp(Operator):
         else:
             scan, leaves = self.op._chain()
         for (_, cond) in leaves:
-            if not isinstance(cond, (Match, GT, LT, EQ)):
+            if not isinstance(cond, SUPPORTED_CONDS):
                 raise Exception(f"Unsupported condition: {cond}")
         colnames = [c.name for c in scan.cols]
         # groupCols filters the BATCH columns by membership in groupBy (:135-140): batch-column order
@@ -705,7 +712,7 @@ class ProjectAggOp(Operator):
         t = scan._table()
         sels = []
         for (col, cond) in leaves:
-            code, operand = _cond_spec(cond)
+            code, operand = _cond_spec(cond, scan.cols[colnames.index(col)].width)
             sels.append((colnames.index(col), code, operand))
         seg = scan.sm.device_segment(scan.tableName, scan.segIdx)
         return seg, scan.cols, scan._used_indices(), sels, t.blockSize, _expr_of(self.op)
@@ -914,10 +921,14 @@ class Engine:
             leaves, prog = [(op.col, op.cond) for op in (leaf(None) for leaf in resolveSelectOps(query))], None
         sels = []
         for (name, cond) in leaves:
-            if not isinstance(cond, (Match, GT, LT, EQ)):
+            if not isinstance(cond, SUPPORTED_CONDS):
                 raise Exception(f"Unsupported condition: {cond}")
-            code, operand = _cond_spec(cond)
             col = used[names.index(name)]
+            code, operand = _cond_spec(cond, col.width)
+            if code == native.STR_RANGE:
+                # a table takes a range on a string column whose width is a multiple of 4, in a flat select list only
+                if not (col.codec in CodecType.STRING_CODECS and prog is None and col.width % 4 == 0 and 4 <= col.width <= 256):
+                    return None
             if code == native.MATCH:
                 # the tile kernels take 2-byte strings with <= 8 IN-list values; a flat select list also takes any non-empty
                 # IN-list on a string column whose width is a multiple of 4 (k_filter_str_rows); a tree keeps the tile kinds

@@ -40,6 +40,80 @@ class LT(SelectCondition):         # Query.scala:8
     lt: float
 
 
+# ---- EXTENSION: byte-order ranges on a string column (include/imm3.h: IMM3_STR_RANGE).  The order is the one ORDER BY sorts by and
+# the string MAX aggregate maximises by: unsigned, byte-wise, from the first byte.  Bounds are str (UTF-8) or bytes. ----
+def _bytes(v) -> bytes:
+    return v.encode("utf-8") if isinstance(v, str) else bytes(v)
+
+
+@dataclass(frozen=True)
+class StrRange(SelectCondition):   # closed: lo padded to the column's width with 0x00 <= row <= hi padded with 0xFF
+    lo: bytes
+    hi: bytes
+
+    def __init__(self, lo, hi):
+        object.__setattr__(self, "lo", _bytes(lo))
+        object.__setattr__(self, "hi", _bytes(hi))
+
+
+@dataclass(frozen=True)
+class Prefix(SelectCondition):     # the rows that start with p: StrRange(p, p)
+    p: bytes
+
+    def __init__(self, p):
+        object.__setattr__(self, "p", _bytes(p))
+
+
+@dataclass(frozen=True)
+class StrGT(SelectCondition):      # strict: row > v padded to the column's width with 0x00
+    v: bytes
+
+    def __init__(self, v):
+        object.__setattr__(self, "v", _bytes(v))
+
+
+@dataclass(frozen=True)
+class StrLT(SelectCondition):      # strict: row < v padded to the column's width with 0x00
+    v: bytes
+
+    def __init__(self, v):
+        object.__setattr__(self, "v", _bytes(v))
+
+
+STR_RANGE_CONDS = (StrRange, Prefix, StrGT, StrLT)
+STR_RANGE_NONE = (b"\x01", b"\x00")   # a leaf no row passes: 01 00 00 .. > 00 FF FF ..
+
+
+def str_successor(v: bytes):
+    """the next value of len(v) bytes in byte order (big-endian arithmetic over all the bytes), or None behind FF .. FF"""
+    n = int.from_bytes(v, "big") + 1
+    return None if not v or n >> (8 * len(v)) else n.to_bytes(len(v), "big")
+
+
+def str_predecessor(v: bytes):
+    """the value before v, or None before 00 .. 00"""
+    n = int.from_bytes(v, "big")
+    return None if not v or n == 0 else (n - 1).to_bytes(len(v), "big")
+
+
+def str_range_bounds(cond: SelectCondition, width: int):
+    """(lo, hi) of the IMM3_STR_RANGE leaf a range condition becomes on a string column of `width` bytes; the library pads lo with
+    0x00 and hi with 0xFF.  StrGT(v) is from the successor of v padded with 0x00 on, StrLT(v) up to its predecessor; where there is
+    none the leaf is STR_RANGE_NONE.  A bound longer than the column raises ValueError (the library refuses it too)."""
+    given = {StrRange: lambda c: (c.lo, c.hi), Prefix: lambda c: (c.p, c.p), StrGT: lambda c: (c.v,), StrLT: lambda c: (c.v,)}[type(cond)](cond)
+    for b in given:
+        if len(b) > width:
+            raise ValueError(f"string bound {b!r} is longer than the column's {width} bytes")
+    if isinstance(cond, (StrRange, Prefix)):
+        return given
+    padded = cond.v + b"\x00" * (width - len(cond.v))
+    if isinstance(cond, StrGT):
+        lo = str_successor(padded)
+        return STR_RANGE_NONE if lo is None else (lo, b"")
+    hi = str_predecessor(padded)
+    return STR_RANGE_NONE if hi is None else (b"", hi)
+
+
 @dataclass(frozen=True)
 class _NoOp(SelectCondition):      # Query.scala:9
     pass

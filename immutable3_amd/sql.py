@@ -15,7 +15,12 @@ parseAll must consume the whole input.
 EXTENSION, only when the parser is asked for it -- parseAll(sql, order_by=True) -- the "sort" core/Query.scala:27 announces:
   queryProject     := "select" repsep(ident, ",") "from" ident where orderBy limit
   orderBy          := opt("order" "by" rep1sep(ident opt("asc" | "desc"), ","))
-With the flag off the grammar is the reference's, and such a statement fails to parse."""
+With the flag off the grammar is the reference's, and such a statement fails to parse.
+
+EXTENSION, only when asked for -- parseAll(sql, string_ranges=True) -- byte-order ranges on string columns (query.Prefix / StrGT / StrLT),
+tried behind the reference's alternatives:
+  filter           := ... | ident ">" "'" value "'" | ident "<" "'" value "'" | ident "like" "'" value "%" "'"
+With the flag off those statements fail to parse with the message they have always given."""
 from __future__ import annotations
 
 import re
@@ -31,13 +36,13 @@ class ParseError(Exception):
 
 
 class SQLParser:
-    def __init__(self, s: str, order_by: bool = False):
-        self.s, self.order_by = s, order_by
+    def __init__(self, s: str, order_by: bool = False, string_ranges: bool = False):
+        self.s, self.order_by, self.string_ranges = s, order_by, string_ranges
         self.furthest, self.expected = 0, "`select'"
 
     @staticmethod
-    def parseAll(sql: str, order_by: bool = False) -> Q.Query:
-        p = SQLParser(sql, order_by)
+    def parseAll(sql: str, order_by: bool = False, string_ranges: bool = False) -> Q.Query:
+        p = SQLParser(sql, order_by, string_ranges)
         r = p._query(0)
         if r is not None:
             q, end = r
@@ -142,6 +147,15 @@ class SQLParser:
                 v = self._ident(c[1])
                 if v is not None:
                     return Q.Select(c[0], mk(self._to_double(v[0]))), v[1]
+        if self.string_ranges:
+            for op, mk, tail in ((">", Q.StrGT, ""), ("<", Q.StrLT, ""), ("like", Q.Prefix, "%")):
+                c = self._cmp(i, op)
+                t = self._lit(c[1], "'") if c is not None else None
+                v = self._ident(t) if t is not None else None
+                u = (self._lit(v[1], tail) if tail else v[1]) if v is not None else None
+                u = self._lit(u, "'") if u is not None else None
+                if u is not None:
+                    return Q.Select(c[0], mk(v[0])), u
         return None
 
     def _where(self, i):

@@ -63,6 +63,22 @@ enum { IMM3_SNAPPY_INT = 16, IMM3_SNAPPY_TINYINT = 17, IMM3_SNAPPY_STRING = 18 }
 
 /* SelectCondition (core/Query.scala:3-9) */
 enum { IMM3_MATCH = 0, IMM3_NOTMATCH = 1, IMM3_EQ = 2, IMM3_GT = 3, IMM3_LT = 4, IMM3_NOOP = 5 };
+/* EXTENSION (not a SelectCondition value): a closed byte-order range on a STRING column, the order ORDER BY sorts by and the string
+ * MAX aggregate maximises by -- unsigned, byte-wise, from the first byte.  A leaf with this cond has n_match == 2: match_bytes holds
+ * `lo` followed by `hi`, match_lens their lengths, each 0 .. width.  It selects the rows whose `width` bytes r satisfy
+ * lo' <= r <= hi', where lo' is lo padded to `width` with 0x00 and hi' is hi padded with 0xFF: {lo = "Jo", hi = "Jo"} is the prefix
+ * test, {lo = "M", hi = ""} is "from M on", {"", ""} selects every row, lo' > hi' selects none.  No null semantics, no collation.
+ * Errors: n_match != 2, null pointers or a bound longer than the column: IMM3_ERR_ARG, the message says which; a leaf on an int32 /
+ * int8 column: "Unsupported column vector" iff the segment has >= 1 batch, as for Match on such a column.
+ * Every creator that takes `sels` or `leaves` accepts the leaf.  Leaves on one column fold: two ranges to their intersection, a range
+ * and a Match to the IN-list's values inside the range (an ordinary Match from there on).  Uniform layouts run a range on a column of
+ * 4, 8, ... IMM3_STRING_MAX_WIDTH bytes through a string pass of its own (k_filter_str_range, beside Match's; a table too), any
+ * other width, ragged layouts and the generic-only tuning variant through the word-at-a-time kernel; a TABLE refuses a range on
+ * those other widths at creation (IMM3_ERR_ARG, a message of its own).
+ * OUT OF SCOPE: a select-tree program that has an IMM3_EXPR_OR or an IMM3_EXPR_NOT *and* an IMM3_STR_RANGE leaf is refused at creation
+ * with IMM3_ERR_ARG (segment and table alike; not an IMM3_TABLE_TREE_REFUSED refusal: per-segment queries would be refused the same
+ * way) -- the normal form would need complemented ranges and ranges with exclusions. */
+enum { IMM3_STR_RANGE = 6 };
 
 /* status codes */
 enum {
@@ -101,12 +117,12 @@ typedef struct {
  * below (the _expr entry points). */
 typedef struct {
     int32_t column;             /* index into the query's used-column list                           */
-    int32_t cond;               /* IMM3_GT / IMM3_LT / IMM3_EQ / IMM3_MATCH (others -> error)         */
+    int32_t cond;               /* IMM3_GT / IMM3_LT / IMM3_EQ / IMM3_MATCH / IMM3_STR_RANGE (others -> error) */
     double value;               /* GT/LT/EQ operand as the Query ADT carries it (core/Query.scala:6-8);
                                    narrowed per column type INSIDE the library: Int column d.toInt,
                                    TinyInt column d.toByte (Select.scala:65,73)                      */
-    const uint8_t *match_bytes; /* MATCH: the IN-list values, concatenated                            */
-    const int32_t *match_lens;  /* MATCH: byte length of each value                                   */
+    const uint8_t *match_bytes; /* MATCH: the IN-list values, concatenated; STR_RANGE: lo, then hi     */
+    const int32_t *match_lens;  /* MATCH: byte length of each value; STR_RANGE: of lo and of hi       */
     int32_t n_match;
 } imm3_select;
 

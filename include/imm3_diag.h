@@ -141,6 +141,10 @@ int imm3_plan_table_limit(int32_t table, int32_t tree, int64_t limit, int32_t co
  * width that is a multiple of 4, 4 .. 256, any IN-list), 2 = the word-at-a-time kernel -- the one an imm3_table does not have, so
  * 2 is what a table query refuses at creation.  -1: width outside 1 .. IMM3_STRING_MAX_WIDTH or an empty list. */
 int imm3_plan_string_route(int32_t width, int32_t n_match);
+/* imm3_plan_string_range_route: the same for an IMM3_STR_RANGE leaf (neither empty nor full) on a string column of `width` bytes:
+ * 1 = the string pass (k_filter_str_range: widths 4, 8, ... 256), 2 = the word-at-a-time kernel (every other width in 1 .. 256: what
+ * a table refuses), -1 outside. */
+int imm3_plan_string_range_route(int32_t width);
 struct imm3_comm;
 int imm3_comm_debug_standin(struct imm3_comm *comm, int32_t work_groups, uint32_t spin_us);
 int imm3_ctx_inject_fault(imm3_ctx *ctx, int32_t work_group, int32_t span, uint32_t max_polls);
