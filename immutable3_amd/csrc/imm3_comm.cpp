@@ -8,6 +8,7 @@
 // need the library, and a host that already carries it (PyTorch-ROCm ships its own copy under the same soname) gets
 // that copy instead of a second one.
 #include "imm3_handles.h"
+#include "imm3_merge_order.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h> // types and enums only; every call goes through the table below
@@ -1156,5 +1157,353 @@ extern "C" int imm3_comm_merge_groups_wide_all(imm3_comm *const *comms, int32_t 
     std::vector<unsigned long long> merged;
     for (auto &kv : all) merged.insert(merged.end(), kv.second.begin(), kv.second.end());
     unpack_wide(merged, sp, geo, key_bytes_out, first, counts, vals, str_out, max_groups, n_groups);
+    return IMM3_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Merging ORDERED results (imm3_comm_merge_ordered; DESIGN.md section 21, "Merging ordered results").  Every (query, ordered row)
+// becomes one record whose first six words are its sort key (imm3_merge_order.h); this rank's lists -- one per query, already in
+// order -- are merged by k_merge_order_rank and cut to the limit, and with more than one rank those lists are exchanged with
+// ncclAllGather -- fixed-size slots, sized by an all-reduce(max) of the list lengths -- and merged by the same kernel.  The
+// protocol around the collectives is that of merge_wide_records: everything that can fail on one rank alone happens before the
+// first collective and travels with the shape vote, so every rank takes the same exit.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+MergeOrderSpec order_spec_of(const imm3_query *q) {
+    MergeOrderSpec sp;
+    for (int32_t p : q->proj) {
+        const SegCol &sc = q->seg->cols[(size_t)q->used[(size_t)p]];
+        sp.widths.push_back(sc.width);
+        sp.kinds.push_back(sc.vcodec == IMM3_DENSE_INT ? KIND_I32 : (sc.vcodec == IMM3_DENSE_TINYINT ? KIND_I8 : KIND_STR));
+    }
+    for (const imm3_order_key &k : q->order_keys) {
+        sp.key_proj.push_back(k.proj);
+        sp.key_desc.push_back(k.descending ? 1 : 0);
+    }
+    return sp;
+}
+
+// The merged records of this communicator's ranks, in order, cut to `limit` (every rank gets all of them); *total: their number.
+int merge_ordered_records(imm3_comm *c, imm3_query *const *queries, const int32_t *segment_index, int32_t n_queries, int64_t limit,
+                          MergeOrderSpec &sp, std::vector<uint32_t> &out, uint64_t *total) {
+    imm3_ctx *ctx = c->ctx;
+    imm3::GateScope gate(&ctx->gate);
+    if (ctx->closed) return fail(IMM3_ERR_STATE, "the context of this communicator has been destroyed");
+    if (ctx->capture) return fail(IMM3_ERR_STATE, "a graph capture is open on this context");
+    HIPCHK(hipSetDevice(ctx->device));
+    out.clear();
+    *total = 0;
+    // ---- everything this rank can get wrong on its own, before the first collective ----
+    int local_rc = IMM3_OK;
+    std::string local_why;
+    auto local_fail = [&](int code, const std::string &msg) {
+        if (local_rc == IMM3_OK) { local_rc = code; local_why = msg; }
+    };
+    if (n_queries == 0) local_fail(IMM3_ERR_ARG, "a rank joins the merge with at least one ordered query (the SELECT list and the keys come from it)");
+    for (int32_t i = 0; i < n_queries && local_rc == IMM3_OK; ++i) {
+        const imm3_query *q = queries[i];
+        if (!q) local_fail(IMM3_ERR_ARG, "query is null");
+        else if (q->is_agg || q->proj.empty() || !q->ordered) local_fail(IMM3_ERR_ARG, "not an ordered projection (imm3_query_set_order on a projecting query)");
+        else if (q->ctx != ctx) local_fail(IMM3_ERR_ARG, "the query runs on another context than the communicator");
+    }
+    for (int32_t i = 0; i < n_queries && local_rc == IMM3_OK; ++i)
+        if (!queries[i]->run.ran_project) local_fail(IMM3_ERR_STATE, "imm3_query_run has not been called");
+    std::vector<int32_t> n_entries((size_t)std::max(n_queries, 0), 1);
+    std::vector<size_t> entry_at((size_t)std::max(n_queries, 0), 0);
+    std::vector<uint64_t> n_local((size_t)std::max(n_queries, 0), 0);
+    std::vector<char> split((size_t)std::max(n_queries, 0), 0); // a table query whose global indices are not ascending
+    unsigned long long total_local = 0;
+    if (local_rc == IMM3_OK) {
+        sp = order_spec_of(queries[0]);
+        for (int32_t i = 1; i < n_queries && local_rc == IMM3_OK; ++i)
+            if (!(order_spec_of(queries[i]) == sp)) local_fail(IMM3_ERR_ARG, "the queries differ in their SELECT lists (columns, widths, kinds) or in their order keys");
+    }
+    if (local_rc == IMM3_OK) {
+        std::vector<int64_t> own((size_t)n_queries);
+        size_t at = 0;
+        for (int32_t i = 0; i < n_queries; ++i) {
+            own[(size_t)i] = queries[i]->order_limit;
+            n_entries[(size_t)i] = queries[i]->table ? (int32_t)queries[i]->table->segs.size() : 1;
+            entry_at[(size_t)i] = at;
+            at += (size_t)n_entries[(size_t)i];
+        }
+        std::string why;
+        if (!merge_order_check(limit, own.data(), n_entries.data(), n_queries, segment_index, &why)) local_fail(IMM3_ERR_ARG, why);
+        for (int32_t i = 0; i < n_queries && local_rc == IMM3_OK; ++i)
+            for (int32_t e = 1; e < n_entries[(size_t)i]; ++e)
+                if (segment_index[entry_at[(size_t)i] + (size_t)e] < segment_index[entry_at[(size_t)i] + (size_t)e - 1]) split[(size_t)i] = 1;
+    }
+    for (int32_t i = 0; i < n_queries && local_rc == IMM3_OK; ++i) { // (waits for the run; orders again when the arrays were outgrown)
+        const int rrc = imm3_query_row_count(queries[i], &n_local[(size_t)i]);
+        if (rrc) local_fail(rrc, imm3_last_error());
+        total_local += n_local[(size_t)i];
+    }
+    if (local_rc == IMM3_OK && total_local > kMergeOrderMaxRows) local_fail(IMM3_ERR_ARG, "too many rows to merge (more than 2^30 enter the merge)");
+    hipStream_t s = ctx->stream;
+    if (c->world > 1) {
+        const int rrc = rccl_ready();
+        if (rrc) return rrc; // (no RCCL in this process: no rank of this process can be inside the collective either)
+        if (c->in_flight) HIPCHK(hipStreamWaitEvent(s, c->ev_done, 0));
+        unsigned long long shape[5] = {sp.vote(0, limit), sp.vote(1, limit), ~sp.vote(0, limit), ~sp.vote(1, limit), local_rc == IMM3_OK ? 0ULL : 1ULL};
+        if (local_rc != IMM3_OK) shape[0] = shape[1] = shape[2] = shape[3] = 0ULL; // (a failed rank does not vote on the shape)
+        HIPCHK(hipMemcpyAsync(c->d_slot, shape, sizeof(shape), hipMemcpyHostToDevice, s));
+        NCCLCHK(g_rccl.AllReduce(c->d_slot, c->d_slot, 5, ncclUint64, ncclMax, c->nccl, s));
+        HIPCHK(hipMemcpyAsync(shape, c->d_slot, sizeof(shape), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (local_rc != IMM3_OK) return fail(local_rc, local_why);
+        if (shape[4]) return fail(IMM3_ERR_STATE, "another rank failed before the merge (its call says why); no rank has merged anything");
+        if (shape[0] != ~shape[2] || shape[1] != ~shape[3]) // (max != min: every rank sees it and leaves here)
+            return fail(IMM3_ERR_ARG, "the ranks' ordered queries differ in SELECT list, order keys or the merge's limit");
+    } else if (local_rc != IMM3_OK) return fail(local_rc, local_why);
+    const MergeOrderGeometry geo = merge_order_geometry(sp.widths);
+    const size_t R = (size_t)geo.rec_words;
+    const uint64_t ulimit = limit > 0 ? (uint64_t)limit : 0;
+    auto cut_of = [&](unsigned long long n) { return ulimit && ulimit < n ? (unsigned long long)ulimit : n; };
+    // ---- this rank's lists and their merge.  One allocation: {input records, a split query's records in its own order, merged
+    // records, total word, list table, per table query: tile starts + global indices, a split query's per-segment counts} ----
+    int32_t n_lists = 0;
+    unsigned long long list_cap = 0, split_rows = 0, split_segs = 0, meta_u32 = 0;
+    for (int32_t i = 0; i < n_queries; ++i) {
+        n_lists += split[(size_t)i] ? n_entries[(size_t)i] : 1;
+        list_cap = std::max<unsigned long long>(list_cap, n_local[(size_t)i]);
+        if (split[(size_t)i]) { split_rows = std::max<unsigned long long>(split_rows, n_local[(size_t)i]); split_segs = std::max<unsigned long long>(split_segs, (unsigned long long)n_entries[(size_t)i]); }
+        if (queries[i]->table) meta_u32 += 2ULL * (unsigned long long)n_entries[(size_t)i] + 2ULL;
+    }
+    auto even = [](unsigned long long v) { return (v + 1ULL) & ~1ULL; };
+    const unsigned long long mine = cut_of(total_local);
+    const unsigned long long in_words = total_local * R, tmp_words = split_rows * R, out_words = mine * R;
+    const unsigned long long w_in = 0, w_tmp = w_in + in_words, w_out = w_tmp + tmp_words, w_total = w_out + out_words, w_lists = w_total + 2,
+                             w_meta = w_lists + 4ULL * (unsigned long long)n_lists, w_counts = w_meta + even(meta_u32), w_end = w_counts + even(split_segs);
+    const unsigned long long rank_waves = (unsigned long long)n_lists * ((list_cap + 63ULL) / 64ULL);
+    void *p1 = nullptr;
+    std::string p1_why = "hipMalloc of the ordered merge's buffers failed";
+    if (rank_waves / 4ULL >= 0x7FFFFFFFULL) p1_why = "too many lists of too many rows to merge in one launch";
+    else {
+        const hipError_t e = hipMalloc(&p1, (size_t)w_end * sizeof(uint32_t));
+        if (e != hipSuccess) { (void)hipGetLastError(); p1 = nullptr; }
+    }
+    std::unique_ptr<void, void (*)(void *)> g1(p1, [](void *q) { (void)hipFree(q); });
+    uint32_t *const d1 = (uint32_t *)p1;
+    std::vector<uint32_t> h_meta;              // host images: live until the stream has been synchronised below
+    std::vector<unsigned long long> h_lists;
+    if (p1) {
+        // device work of THIS rank between two collectives: a failure clears p1 instead of returning (the rank then says ~0 in the
+        // list-length all-reduce and every rank leaves together)
+        auto local_step = [&](hipError_t e, const char *what) {
+            if (e == hipSuccess || !p1) return;
+            (void)hipGetLastError();
+            p1_why = std::string(what) + ": " + hipGetErrorString(e);
+            p1 = nullptr;
+        };
+        local_step(hipMemsetAsync(d1, 0, (size_t)w_end * sizeof(uint32_t), s), "merge buffer clear"); // (pad words: records are bit-exact images)
+        // the list table and the tables' lookups
+        h_lists.assign(2 * (size_t)n_lists, 0ULL);
+        h_meta.assign((size_t)even(meta_u32), 0u);
+        std::vector<size_t> meta_at((size_t)n_queries, 0), list_at((size_t)n_queries, 0);
+        {
+            size_t m = 0, l = 0;
+            unsigned long long rec_at = 0;
+            for (int32_t i = 0; i < n_queries; ++i) {
+                const imm3_query *q = queries[i];
+                list_at[(size_t)i] = l;
+                if (!split[(size_t)i]) { // (a split query's entries are written by its move launch)
+                    h_lists[2 * l] = w_in + rec_at * R;
+                    h_lists[2 * l + 1] = n_local[(size_t)i];
+                }
+                l += split[(size_t)i] ? (size_t)n_entries[(size_t)i] : 1;
+                rec_at += n_local[(size_t)i];
+                if (!q->table) continue;
+                meta_at[(size_t)i] = m;
+                const int32_t ns = n_entries[(size_t)i];
+                for (int32_t t = 0; t <= ns; ++t) h_meta[m + (size_t)t] = (uint32_t)q->table->tile_start[(size_t)t];
+                for (int32_t t = 0; t < ns; ++t) h_meta[m + (size_t)ns + 1 + (size_t)t] = (uint32_t)segment_index[entry_at[(size_t)i] + (size_t)t];
+                m += 2 * (size_t)ns + 2;
+            }
+        }
+        local_step(hipMemcpyAsync(d1 + w_lists, h_lists.data(), h_lists.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, s), "merge list table");
+        if (!h_meta.empty()) local_step(hipMemcpyAsync(d1 + w_meta, h_meta.data(), h_meta.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s), "merge table lookups");
+        unsigned long long rec_at = 0;
+        for (int32_t i = 0; i < n_queries && p1; ++i) {
+            imm3_query *q = queries[i];
+            const uint64_t n = n_local[(size_t)i];
+            if (!n) continue;
+            MergeOrderPackArgs pa;
+            std::memset(&pa, 0, sizeof(pa));
+            pa.n_keys = (int32_t)q->order_keys.size();
+            pa.key_bytes = q->order_key_bytes;
+            for (int k = 0; k < pa.n_keys; ++k) {
+                const int32_t pj = q->order_keys[(size_t)k].proj;
+                pa.keys[k].src = q->d_order_proj[(size_t)pj];
+                pa.keys[k].width = sp.widths[(size_t)pj];
+                pa.keys[k].kind = sp.kinds[(size_t)pj];
+                pa.keys[k].descending = q->order_keys[(size_t)k].descending ? 1 : 0;
+            }
+            pa.row_index = q->d_order_row_index;
+            pa.n_rows = (uint32_t)n;
+            pa.rec_words = (int32_t)R;
+            pa.recs = d1 + (split[(size_t)i] ? w_tmp : w_in + rec_at * R);
+            if (q->table) {
+                pa.n_tsegs = n_entries[(size_t)i];
+                pa.tile_start = d1 + w_meta + meta_at[(size_t)i];
+                pa.global_index = pa.tile_start + pa.n_tsegs + 1;
+            } else pa.segment = (uint32_t)segment_index[entry_at[(size_t)i]];
+            const size_t np = q->proj.size();
+            for (size_t done = 0; done < np && p1;) { // more SELECT-list columns than one launch carries: in groups (the key with the first)
+                const size_t take = std::min<size_t>(kMaxProj, np - done);
+                pa.with_key = done == 0;
+                pa.n_cols = (int32_t)take;
+                for (size_t j = 0; j < take; ++j) {
+                    pa.cols[j].src = q->d_order_proj[done + j];
+                    pa.cols[j].width = sp.widths[done + j];
+                    pa.cols[j].rec_off = geo.col_off[done + j];
+                }
+                done += take;
+                launch_merge_order_pack(pa, s);
+                local_step(hipGetLastError(), "merge pack");
+            }
+            if (split[(size_t)i] && p1) {
+                MergeOrderSplitArgs sa;
+                std::memset(&sa, 0, sizeof(sa));
+                sa.src = d1 + w_tmp;
+                sa.dst = d1;
+                sa.dst_word = w_in + rec_at * R;
+                sa.n_rows = (uint32_t)n;
+                sa.n_tsegs = n_entries[(size_t)i];
+                sa.rec_words = (int32_t)R;
+                sa.global_index = pa.global_index;
+                sa.counts = d1 + w_counts;
+                sa.lists = (unsigned long long *)(d1 + w_lists) + 2 * list_at[(size_t)i];
+                launch_merge_order_split(sa, s); // (the next split query reuses the records behind this launch: same stream)
+                local_step(hipGetLastError(), "merge split");
+            }
+            rec_at += n;
+        }
+        if (p1 && total_local) {
+            MergeOrderArgs ma;
+            std::memset(&ma, 0, sizeof(ma));
+            ma.recs = d1;
+            ma.buf_words = w_tmp; // (the input records only)
+            ma.lists = (const unsigned long long *)(d1 + w_lists);
+            ma.n_lists = n_lists;
+            ma.rec_words = (int32_t)R;
+            ma.list_cap = (uint32_t)list_cap;
+            ma.cut = (uint32_t)mine;
+            ma.out = d1 + w_out;
+            ma.out_total = (unsigned long long *)(d1 + w_total);
+            launch_merge_order_rank(ma, s);
+            local_step(hipGetLastError(), "merge rank");
+        }
+        if (p1) local_step(hipStreamSynchronize(s), "merge of this rank's lists");
+    }
+    if (c->world == 1) {
+        if (!p1) return fail(IMM3_ERR_DEVICE, p1_why);
+        out.assign((size_t)out_words, 0u);
+        if (out_words) HIPCHK(hipMemcpyAsync(out.data(), d1 + w_out, (size_t)out_words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        *total = mine;
+        return IMM3_OK;
+    }
+    // list lengths -> the common slot size (a rank whose lists could not be merged says so with ~0: every rank leaves)
+    unsigned long long word = p1 ? mine : ~0ULL, most = 0;
+    HIPCHK(hipMemcpyAsync(c->d_slot, &word, sizeof(word), hipMemcpyHostToDevice, s));
+    NCCLCHK(g_rccl.AllReduce(c->d_slot, c->d_slot, 1, ncclUint64, ncclMax, c->nccl, s));
+    HIPCHK(hipMemcpyAsync(&most, c->d_slot, sizeof(most), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (most == ~0ULL) return fail(IMM3_ERR_DEVICE, p1 ? std::string("a rank could not merge its own lists; no rank has merged anything") : p1_why + "; no rank has merged anything");
+    if (!most) return IMM3_OK; // (every rank's list is empty)
+    const unsigned long long entries = most * (unsigned long long)c->world;
+    if (entries > kMergeOrderMaxRows) return fail(IMM3_ERR_ARG, "too many rows to merge (more than 2^30 enter the merge)"); // (the same figure on every rank: every rank leaves here)
+    const unsigned long long slot_words = 2ULL + most * R, cut2 = cut_of(entries);
+    // {send slot, the ranks' slots, total word, merged records}; sizes are the same on every rank: an allocation failure is reported
+    // through one more flag exchange
+    const unsigned long long x_recv = slot_words, x_total = x_recv + slot_words * (unsigned long long)c->world, x_out = x_total + 2, x_end = x_out + cut2 * R;
+    void *p = nullptr;
+    hipError_t e = hipMalloc(&p, (size_t)x_end * sizeof(uint32_t));
+    if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
+    std::unique_ptr<void, void (*)(void *)> guard(p, [](void *q) { (void)hipFree(q); });
+    unsigned long long ok = p ? 0ULL : 1ULL, any = 0;
+    HIPCHK(hipMemcpyAsync(c->d_slot, &ok, sizeof(ok), hipMemcpyHostToDevice, s));
+    NCCLCHK(g_rccl.AllReduce(c->d_slot, c->d_slot, 1, ncclUint64, ncclMax, c->nccl, s));
+    HIPCHK(hipMemcpyAsync(&any, c->d_slot, sizeof(any), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (any) return fail(IMM3_ERR_DEVICE, "a rank could not allocate the exchange buffers of the merge; no rank has merged anything");
+    uint32_t *const dx = (uint32_t *)p;
+    HIPCHK(hipMemsetAsync(dx, 0, (size_t)slot_words * sizeof(uint32_t), s)); // (the slot's tail behind this rank's records)
+    HIPCHK(hipMemcpyAsync(dx, &mine, sizeof(mine), hipMemcpyHostToDevice, s)); // the slot's length word
+    if (mine) HIPCHK(hipMemcpyAsync(dx + 2, d1 + w_out, (size_t)out_words * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    NCCLCHK(g_rccl.AllGather(dx, dx + x_recv, (size_t)(slot_words / 2), ncclUint64, c->nccl, s));
+    MergeOrderArgs ma;
+    std::memset(&ma, 0, sizeof(ma));
+    ma.recs = dx + x_recv;
+    ma.buf_words = slot_words * (unsigned long long)c->world;
+    ma.slot_words = slot_words;
+    ma.n_lists = c->world;
+    ma.rec_words = (int32_t)R;
+    ma.list_cap = (uint32_t)most;
+    ma.cut = (uint32_t)cut2;
+    ma.out = dx + x_out;
+    ma.out_total = (unsigned long long *)(dx + x_total);
+    launch_merge_order_rank(ma, s);
+    HIPCHK(hipGetLastError());
+    std::vector<uint32_t> h((size_t)(2 + cut2 * R)); // one copy: the total word and the records behind it
+    HIPCHK(hipMemcpyAsync(h.data(), dx + x_total, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    unsigned long long all = 0;
+    std::memcpy(&all, h.data(), sizeof(all));
+    *total = std::min(all, cut2);
+    out.assign(h.begin() + 2, h.begin() + 2 + (size_t)(*total * R));
+    return IMM3_OK;
+}
+
+} // namespace
+
+extern "C" int imm3_comm_merge_ordered(imm3_comm *c, imm3_query *const *queries, const int32_t *segment_index, int32_t n_queries,
+                                       int64_t limit, uint32_t *segment_out, uint32_t *row_out, void *const *col_out,
+                                       uint64_t max_rows, uint64_t *n_rows) {
+    if (!c || !n_rows || n_queries < 0 || (n_queries > 0 && (!queries || !segment_index))) return fail(IMM3_ERR_ARG, "bad argument");
+    MergeOrderSpec sp;
+    std::vector<uint32_t> recs;
+    uint64_t total = 0;
+    const int rc = merge_ordered_records(c, queries, segment_index, n_queries, limit, sp, recs, &total);
+    if (rc) return rc;
+    *n_rows = total;
+    merge_order_unpack(recs.data(), total, merge_order_geometry(sp.widths), sp.widths, segment_out, row_out, col_out, max_rows);
+    return IMM3_OK;
+}
+
+// Single-process flavour (comms from imm3_comm_create_all): per device the world-of-one merge above, cut to the limit, then one
+// k-way merge of the devices' lists on the host.
+extern "C" int imm3_comm_merge_ordered_all(imm3_comm *const *comms, int32_t n_comms, imm3_query *const *const *queries,
+                                           const int32_t *const *segment_index, const int32_t *n_queries,
+                                           int64_t limit, uint32_t *segment_out, uint32_t *row_out, void *const *col_out,
+                                           uint64_t max_rows, uint64_t *n_rows) {
+    if (!comms || n_comms < 1 || !queries || !segment_index || !n_queries || !n_rows) return fail(IMM3_ERR_ARG, "bad argument");
+    bool have = false;
+    MergeOrderSpec sp;
+    std::vector<std::vector<uint32_t>> lists;
+    std::vector<uint64_t> lens;
+    for (int32_t i = 0; i < n_comms; ++i) {
+        if (!comms[i] || n_queries[i] < 0 || (n_queries[i] > 0 && (!queries[i] || !segment_index[i]))) return fail(IMM3_ERR_ARG, "bad argument");
+        if (n_queries[i] == 0) continue;
+        imm3_comm one = *comms[i]; // the same communicator seen as a world of one: its device's queries merged without a collective
+        one.world = 1;
+        MergeOrderSpec si;
+        std::vector<uint32_t> recs;
+        uint64_t n = 0;
+        const int rc = merge_ordered_records(&one, queries[i], segment_index[i], n_queries[i], limit, si, recs, &n);
+        if (rc) return rc;
+        if (!have) { sp = si; have = true; }
+        else if (!(si == sp)) return fail(IMM3_ERR_ARG, "the devices' ordered queries differ in SELECT list or order keys");
+        lists.push_back(std::move(recs));
+        lens.push_back(n);
+    }
+    const MergeOrderGeometry geo = merge_order_geometry(sp.widths);
+    std::vector<const uint32_t *> ptrs;
+    for (auto &l : lists) ptrs.push_back(l.data());
+    std::vector<uint32_t> merged;
+    merge_order_host(ptrs.data(), lens.data(), (int32_t)lists.size(), geo.rec_words, limit > 0 ? (uint64_t)limit : 0, merged);
+    *n_rows = merged.size() / (size_t)geo.rec_words;
+    merge_order_unpack(merged.data(), *n_rows, geo, sp.widths, segment_out, row_out, col_out, max_rows);
     return IMM3_OK;
 }

@@ -755,6 +755,53 @@ void launch_order_select(const OrderArgs &a, hipStream_t s, hipEvent_t ev0, hipE
 void launch_order_pass(const OrderArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);   // one LSD pass on a.byte_pos: count, scan, scatter
 void launch_order_apply(const OrderApplyArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 
+// ---- merging ordered results (imm3_merge_order.hip; the record: imm3_merge_order.h): every ordered row of every query becomes one
+// record whose first six words are its sort key; sorted lists of records are merged by ranking each record in the other lists. ----
+struct MergeOrderPackCol {
+    const uint8_t *src;  // an ORDERED SELECT-list column, width bytes per row
+    int32_t width;
+    int32_t rec_off;     // word offset of its bytes in a record
+};
+struct MergeOrderPackArgs {
+    OrderKeyCol keys[kOrderMaxKeys]; // src: the ordered key columns (the key is built again from them: imm3_order_key.h)
+    int32_t n_keys, key_bytes;
+    int32_t with_key;                // 1: this launch writes the six key words (the first column group of a long SELECT list)
+    int32_t n_cols;
+    const uint32_t *row_index;       // the query's ordered row indices (a table query: virtual rows)
+    uint32_t n_rows;                 // host-known: the grid is sized from it
+    uint32_t segment;                // a segment query's global segment
+    int32_t n_tsegs, rec_words;      // table query: segments of its table (0: a segment query)
+    const uint32_t *tile_start;      // table query: n_tsegs + 1 first tiles
+    const uint32_t *global_index;    // table query: the global segment of each table segment
+    MergeOrderPackCol cols[kMaxProj];
+    uint32_t *recs;                  // record i of this query at recs + i * rec_words
+};
+// a table query whose global indices are not ascending: its records (in list order) cut into one sorted list per table segment
+struct MergeOrderSplitArgs {
+    const uint32_t *src;               // the query's n_rows records, in the query's order
+    uint32_t *dst;                     // the merge's input buffer
+    unsigned long long dst_word;       // word offset of this query's first record there
+    uint32_t n_rows;
+    int32_t n_tsegs, rec_words, pad;
+    const uint32_t *global_index;      // n_tsegs
+    uint32_t *counts;                  // n_tsegs: rows of each table segment (written by the count launch)
+    unsigned long long *lists;         // this query's n_tsegs entries of the list table, written by the move launch
+};
+struct MergeOrderArgs {
+    const uint32_t *recs;              // the input lists
+    unsigned long long buf_words;      // words of `recs`: a list that would reach past them counts as empty
+    const unsigned long long *lists;   // list l = {word offset of its first record in recs, records}; unused when slot_words != 0
+    unsigned long long slot_words;     // != 0: the gathered form -- list l's length is the uint64 at word l * slot_words, its records follow
+    int32_t n_lists, rec_words;
+    uint32_t list_cap;                 // no list is longer (host-known): ceil(list_cap / 64) waves per list
+    uint32_t cut;                      // records whose place is below it are stored
+    uint32_t *out;                     // room for `cut` records
+    unsigned long long *out_total;     // the lists' lengths summed
+};
+void launch_merge_order_pack(const MergeOrderPackArgs &a, hipStream_t s);
+void launch_merge_order_split(const MergeOrderSplitArgs &a, hipStream_t s); // count + move
+void launch_merge_order_rank(const MergeOrderArgs &a, hipStream_t s);
+
 } // namespace imm3
 
 #ifdef __HIPCC__

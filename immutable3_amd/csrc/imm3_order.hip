@@ -19,6 +19,7 @@
 // keeps row order within a digit (stable), and since the input is in ascending row order, rows with equal keys stay in it.
 // The grid never depends on the row count (a device word): nothing here makes the host wait.
 #include "imm3_internal.h"
+#include "imm3_order_key.h"
 
 #include <hip/hip_runtime.h>
 
@@ -67,35 +68,8 @@ __device__ inline uint32_t rows_emitted(const OrderArgs &a) {
     return (uint32_t)(e < a.cap_rows ? e : a.cap_rows);
 }
 
-// the normalised key of projected row i: key byte 0 in the top byte of k[0]
-__device__ inline void build_key(const OrderArgs &a, int64_t i, uint32_t k[kOrderKeyWords]) {
-    unsigned long long hi = 0, lo = 0;
-    auto push = [&](uint32_t byte) {
-        hi = (hi << 8) | (lo >> 56);
-        lo = (lo << 8) | (unsigned long long)(byte & 0xFFu);
-    };
-    for (int c = 0; c < a.n_cols; ++c) {
-        const OrderKeyCol &col = a.cols[c];
-        const uint32_t flip = col.descending ? 0xFFu : 0u;
-        if (col.kind == KIND_I32) {
-            const uint32_t v = ((const uint32_t *)col.src)[i] ^ 0x80000000u;
-            push((v >> 24) ^ flip);
-            push((v >> 16) ^ flip);
-            push((v >> 8) ^ flip);
-            push(v ^ flip);
-        } else if (col.kind == KIND_I8) {
-            push(((uint32_t)col.src[i] ^ 0x80u) ^ flip);
-        } else {
-            const uint8_t *p = col.src + i * col.width;
-            for (int b = 0; b < col.width; ++b) push((uint32_t)p[b] ^ flip);
-        }
-    }
-    for (int b = a.key_bytes; b < kOrderKeyMaxBytes; ++b) push(0u);
-    k[0] = (uint32_t)(hi >> 32);
-    k[1] = (uint32_t)hi;
-    k[2] = (uint32_t)(lo >> 32);
-    k[3] = (uint32_t)lo;
-}
+// the normalised key of projected row i (the rule itself: imm3_order_key.h)
+__device__ inline void build_key(const OrderArgs &a, int64_t i, uint32_t k[kOrderKeyWords]) { order_build_key(a.cols, a.n_cols, a.key_bytes, i, k); }
 
 __device__ inline uint32_t key_digit(const uint32_t k[kOrderKeyWords], int p) {
     const int w = p >> 2;

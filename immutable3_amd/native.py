@@ -52,7 +52,7 @@ EXPORTS = [
     "imm3_query_row_count", "imm3_query_fetch_rows", "imm3_query_device_ptr",
     "imm3_comm_unique_id", "imm3_comm_create", "imm3_comm_create_all", "imm3_comm_destroy", "imm3_comm_info",
     "imm3_comm_sync", "imm3_comm_join", "imm3_comm_allreduce_u64", "imm3_comm_allreduce_count", "imm3_comm_allreduce_count_all", "imm3_comm_merge_groups", "imm3_comm_merge_groups_all",
-    "imm3_comm_merge_groups_wide", "imm3_comm_merge_groups_wide_all",
+    "imm3_comm_merge_groups_wide", "imm3_comm_merge_groups_wide_all", "imm3_comm_merge_ordered", "imm3_comm_merge_ordered_all",
     "imm3_pfor_encode_bound", "imm3_pfor_encode_block", "imm3_pfor_encode_column",
     "imm3_snappy_encode_bound", "imm3_snappy_encode_block",
 ]
@@ -216,6 +216,8 @@ def load() -> C.CDLL:
     L.imm3_comm_merge_groups_all.argtypes = [P(vp), i32, P(P(vp)), P(vp), P(i32), vp, vp, vp, vp, C.c_uint32, P(C.c_uint32)]
     L.imm3_comm_merge_groups_wide.argtypes = [vp, P(vp), vp, i32, vp, vp, vp, vp, P(vp), C.c_uint32, P(C.c_uint32)]
     L.imm3_comm_merge_groups_wide_all.argtypes = [P(vp), i32, P(P(vp)), P(vp), P(i32), vp, vp, vp, vp, P(vp), C.c_uint32, P(C.c_uint32)]
+    L.imm3_comm_merge_ordered.argtypes = [vp, P(vp), vp, i32, i64, vp, vp, P(vp), u64, P(u64)]
+    L.imm3_comm_merge_ordered_all.argtypes = [P(vp), i32, P(P(vp)), P(vp), P(i32), i64, vp, vp, P(vp), u64, P(u64)]
     for name in EXPORTS + DIAG_EXPORTS:
         fn = getattr(L, name)
         if name not in ("imm3_last_error", "imm3_pfor_encode_bound", "imm3_snappy_encode_bound"):
@@ -967,6 +969,68 @@ class Comm:
         _check(load().imm3_comm_merge_groups_wide_all(carr, n, qq, ss, nq, keys.ctypes.data, first.ctypes.data, counts.ctypes.data, vals.ctypes.data,
                                                       ptrs, m, C.byref(g)))
         return keys[:m, :kb], first[:m], counts[:m], vals[:m, :na], {j: b[:m] for j, b in strs.items()}
+
+    @staticmethod
+    def _flat_segments(segment_index) -> np.ndarray:
+        """segment_index of merge_ordered: an int per segment query, a sequence of ints per table query -> the flattened int32 array."""
+        flat: List[int] = []
+        for e in segment_index:
+            flat.extend(int(x) for x in e) if isinstance(e, (list, tuple, np.ndarray)) else flat.append(int(e))
+        return np.ascontiguousarray(flat, dtype=np.int32)
+
+    @staticmethod
+    def _ordered_buffers(q0: "DeviceQuery", n: int):
+        rows = max(n, 1)
+        seg, row = np.zeros(rows, np.uint32), np.zeros(rows, np.uint32)
+        cols = [np.zeros((rows, w), np.uint8) for w in q0.proj_widths]
+        ptrs = (C.c_void_p * max(1, len(cols)))(*[c.ctypes.data for c in cols])
+        return seg, row, cols, ptrs
+
+    def merge_ordered(self, queries: Sequence["DeviceQuery"], segment_index: Sequence, limit: int = 0, max_rows: Optional[int] = None):
+        """The ordered rows (set_order) of this rank's queries and of every other rank's, merged on the device by (key, global segment,
+        row) and cut to `limit` (0: all): (segment uint32[n], row uint32[n], [uint8[n, width] per SELECT-list column]); every rank
+        gets the whole result.  segment_index: per query its global segment index, or for a query over a DeviceTable the global
+        indices of the table's segments in table order.  max_rows: fetch only that many (the total is then the last item)."""
+        qs = (C.c_void_p * max(1, len(queries)))(*[q._h for q in queries])
+        flat = self._flat_segments(segment_index)
+        n = C.c_uint64(0)
+        if max_rows is None:
+            try:                                             # one rank: its queries' rows bound the result, no call to ask for the total
+                cap = sum(q.row_count() for q in queries) if self.world == 1 else None
+            except (Imm3Error, AttributeError):
+                cap = None                                   # (the merge itself says what is wrong with the query)
+            if cap is None:
+                _check(load().imm3_comm_merge_ordered(self._h, qs, flat.ctypes.data, len(queries), limit, None, None, None, 0, C.byref(n)))
+                cap = n.value
+            elif limit > 0:
+                cap = min(cap, limit)
+        else:
+            cap = max_rows
+        seg, row, cols, ptrs = self._ordered_buffers(queries[0], cap)
+        _check(load().imm3_comm_merge_ordered(self._h, qs, flat.ctypes.data, len(queries), limit, seg.ctypes.data, row.ctypes.data, ptrs, cap, C.byref(n)))
+        m = min(n.value, cap)
+        out = (seg[:m], row[:m], [c[:m] for c in cols])
+        return out if max_rows is None else out + (n.value,)
+
+    @staticmethod
+    def merge_ordered_all(comms: Sequence["Comm"], queries_per_comm: Sequence[Sequence["DeviceQuery"]], segments_per_comm: Sequence[Sequence], limit: int = 0):
+        """Single-process flavour of merge_ordered: one Comm per device (create_all), each with its queries and their segment indices."""
+        n = len(comms)
+        carr = (C.c_void_p * n)(*[c._h for c in comms])
+        qarrs = [(C.c_void_p * max(1, len(qs)))(*[q._h for q in qs]) for qs in queries_per_comm]
+        qq = (C.POINTER(C.c_void_p) * n)(*[C.cast(a, C.POINTER(C.c_void_p)) for a in qarrs])
+        segs = [Comm._flat_segments(s) for s in segments_per_comm]
+        ss = (C.c_void_p * n)(*[s.ctypes.data if s.size else None for s in segs])
+        nq = (C.c_int32 * n)(*[len(qs) for qs in queries_per_comm])
+        q0 = next(q for qs in queries_per_comm for q in qs)
+        cap = sum(q.row_count() for qs in queries_per_comm for q in qs)
+        if limit > 0:
+            cap = min(cap, limit)
+        seg, row, cols, ptrs = Comm._ordered_buffers(q0, cap)
+        m = C.c_uint64(0)
+        _check(load().imm3_comm_merge_ordered_all(carr, n, qq, ss, nq, limit, seg.ctypes.data, row.ctypes.data, ptrs, cap, C.byref(m)))
+        k = min(m.value, cap)
+        return seg[:k], row[:k], [c[:k] for c in cols]
 
     @staticmethod
     def allreduce_count_all(comms: Sequence["Comm"], queries_per_comm: Sequence[Sequence["DeviceQuery"]]) -> int:

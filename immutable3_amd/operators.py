@@ -125,6 +125,15 @@ class GpuSegmentManager:
         self._segs: Dict[Tuple[str, int], native.DeviceSegment] = {}
         self._tables: Dict[str, Optional[native.DeviceTable]] = {}
         self._filter = segment_filter
+        self._merge_comms: Dict[int, native.Comm] = {}
+
+    def merge_comm(self, ci: int) -> native.Comm:
+        """The one-rank communicator of context `ci` that the ordered device merge runs on, made once and kept until close():
+        creating one initialises RCCL, which costs far more than a merge.  (One rank: its collectives launch nothing and it
+        reserves nothing on the device.)"""
+        if ci not in self._merge_comms:
+            self._merge_comms[ci] = native.Comm(self.ctxs[ci], 1, 0, native.comm_unique_id())
+        return self._merge_comms[ci]
 
     def getTable(self, tableName: str) -> Table:
         return self.sm.getTable(tableName)
@@ -170,6 +179,9 @@ class GpuSegmentManager:
         return table
 
     def close(self):
+        for c in self._merge_comms.values():
+            c.close()
+        self._merge_comms.clear()
         for t in self._tables.values():
             if t is not None:
                 t.close()
@@ -453,25 +465,40 @@ class ProjectOp(ProjectionOperator):
             return self.op._chain()
         return None
 
-    def run_columns(self):
-        """Fused execution; returns (row_index uint32[n], [typed numpy array per SELECT-list column])."""
+    def _open(self) -> "native.DeviceQuery":
+        """The fused query of this pipeline, created, ordered when there are keys, and run; the caller fetches and closes it."""
         scan, leaves = self._fused()
         for (_, cond) in leaves:
             if not isinstance(cond, SUPPORTED_CONDS):
                 raise Exception(f"Unsupported condition: {cond}")
         q = scan._query(leaves, self.cols, 0 if self.order_keys else self.limit, _expr_of(self.op))
-        if self.order_keys:
-            q.set_order(self.order_keys, self.limit)               # (the limit is applied behind the order: no creation-time limit)
-        q.run()
-        idx, cols = q.fetch_rows()
+        try:
+            if self.order_keys:
+                q.set_order(self.order_keys, self.limit)           # (the limit is applied behind the order: no creation-time limit)
+            q.run()
+        except Exception:
+            q.close()
+            raise
+        return q
+
+    @staticmethod
+    def _typed(cols, codecs):
+        """raw column bytes (uint8[n, width]) -> int32 / int8 arrays for the int codecs, strings as they are"""
         out = []
-        for raw, codec in zip(cols, q.proj_codecs):
+        for raw, codec in zip(cols, codecs):
             if codec in native.INT_CODECS:
                 out.append(raw.reshape(-1).view("<i4"))
             elif codec in native.TINYINT_CODECS:
                 out.append(raw.reshape(-1).view(np.int8))
             else:
                 out.append(raw)
+        return out
+
+    def run_columns(self):
+        """Fused execution; returns (row_index uint32[n], [typed numpy array per SELECT-list column])."""
+        q = self._open()
+        idx, cols = q.fetch_rows()
+        out = self._typed(cols, q.proj_codecs)
         q.close()
         return idx, out
 
@@ -870,8 +897,10 @@ class Engine:
     def __init__(self, sm: GpuSegmentManager, honour_and_or: bool = False, device_merge: bool = False, honour_not_match: bool = False):
         """honour_and_or: a query whose select tree holds an Or runs it as a disjunction (one table launch when the table takes the
         tree, else SelectTreeOp per segment) instead of the reference's conjunction.  Off (the default) nothing changes; a tree without Or is the same either way.
-        device_merge: the per-segment branch of execute_agg merges its queries' groups on the GPU (one imm3_comm_merge_groups_wide
-        over a one-rank communicator per context) instead of combining dicts on the host.  Off (the default) nothing changes.
+        device_merge: the per-segment branches merge on the GPU instead of on the host -- execute_agg its queries' groups (one
+        imm3_comm_merge_groups_wide over a one-rank communicator per context) instead of combining dicts, an ORDER BY statement its
+        per-segment ordered rows (one imm3_comm_merge_ordered) instead of operators.merge_ordered's lexsort; the results are the
+        same.  Off (the default) nothing changes.
         honour_not_match: a query whose select tree holds a NotMatch leaf -- which the reference's SelectOp throws on -- runs as a
         tree, whether or not it has an Or: the leaf is the complement of its Match (IMM3_EXPR_NOT), and the And / Or tags of THAT
         query are then honoured too, whatever honour_and_or says (a complement under a conjunction-for-everything has no meaning
@@ -1069,7 +1098,11 @@ class Engine:
         if okeys:
             # per-segment ordered queries, each with the limit (no segment contributes more), then a stable host merge by
             # (keys, segment, row)
-            _, _, cols = merge_ordered(self.execute_columns(query), okeys, limit)
+            pipes = list(self.pipelines(query))
+            if self.device_merge and pipes and all(proj._fused() is not None for _, proj in pipes):
+                cols = self._execute_ordered_device_merge(pipes, limit)
+            else:
+                _, _, cols = merge_ordered([(segIdx, *proj.run_columns()) for segIdx, proj in pipes], okeys, limit)
             yield from _rows_from_columns(cols)
             return
         total = 0
@@ -1079,6 +1112,34 @@ class Engine:
                     return
                 yield row
                 total += 1
+
+    def _execute_ordered_device_merge(self, pipes, limit: int):
+        """execute's ordered per-segment branch with the merge on the GPU: every owned segment's ordered query stays open, one
+        imm3_comm_merge_ordered (one context) or _all (several) brings their rows together by (keys, segment, row) and cuts them to
+        the limit; the merged columns are decoded as execute_table_columns decodes its own.  The rows operators.merge_ordered gives."""
+        queries: Dict[int, list] = {}          # by index of the segment's context
+        seg_ids: Dict[int, list] = {}
+        try:
+            for segIdx, proj in pipes:
+                ci = segIdx % len(self.sm.ctxs)
+                queries.setdefault(ci, []).append(proj._open())
+                seg_ids.setdefault(ci, []).append(segIdx)
+            order = sorted(queries)
+            codecs = queries[order[0]][0].proj_codecs
+            if len(order) == 1:
+                _, _, cols = self.sm.merge_comm(order[0]).merge_ordered(queries[order[0]], seg_ids[order[0]], limit)
+            else:
+                comms = native.Comm.create_all([self.sm.ctxs[ci] for ci in order])
+                try:
+                    _, _, cols = native.Comm.merge_ordered_all(comms, [queries[ci] for ci in order], [seg_ids[ci] for ci in order], limit)
+                finally:
+                    for c in comms:
+                        c.close()
+        finally:
+            for qs in queries.values():
+                for q in qs:
+                    q.close()
+        return ProjectOp._typed(cols, codecs)
 
     def execute_columns(self, query: Query):
         """Columnar result per segment: [(segIdx, row_index, [column arrays])] (no Row boxing)."""

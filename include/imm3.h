@@ -419,8 +419,8 @@ int imm3_query_reserve_rows(imm3_query *q, uint64_t rows);
  * query with limit <= 0 and pass the limit here; the message says so);
  * IMM3_ERR_STATE -- the query has already run.  imm3_query_run of an ordered query inside imm3_ctx_capture_begin .. _end:
  * IMM3_ERR_STATE (graph replay of ordered queries is not supported).
- * OUT OF SCOPE: merging ordered results across ranks (imm3_comm_*), ordering aggregation results, order keys outside the SELECT
- * list, graph capture of ordered runs. ---- */
+ * Merging the ordered results of several queries -- segments, tables, ranks -- is imm3_comm_merge_ordered.
+ * OUT OF SCOPE: ordering aggregation results, order keys outside the SELECT list, graph capture of ordered runs. ---- */
 typedef struct { int32_t proj; int32_t descending; } imm3_order_key;   /* proj: index into the query's SELECT list */
 #define IMM3_ORDER_MAX_KEYS 4
 #define IMM3_ORDER_KEY_MAX_WIDTH 16   /* sum of the key columns' widths, bytes */
@@ -588,6 +588,40 @@ int imm3_comm_merge_groups_wide_all(imm3_comm *const *comms, int32_t n_comms, im
                                     const int32_t *const *segment_index, const int32_t *n_queries,
                                     uint8_t *key_bytes_out, uint64_t *first, uint64_t *counts, int64_t *vals,
                                     uint8_t *const *str_out, uint32_t max_groups, uint32_t *n_groups);
+
+/* ---- multi-GPU: the merge of ORDERED results ("Merging ordered results").  Every rank brings the ordered
+ * projecting queries of its own segments (at least one): each has had imm3_query_set_order called and has been run on the
+ * communicator's context; all of them, on every rank, have the same SELECT-list shape (number of columns, widths, kinds) and the
+ * same order keys (proj and descending, in the same sequence).  Every rank passes the same `limit`.
+ *   segment_index   flattened: a query over a segment consumes one entry, its global segment index; a query over an imm3_table
+ *                   consumes as many entries as the table has segments, in the table's segment order: the global indices of those
+ *                   segments (with s mod G sharding they are not consecutive, and they need not ascend).  All entries of one rank are
+ *                   >= 0 and pairwise distinct; distinctness across ranks is the caller's contract and is not checked.
+ * Result, the same on every rank: all rows of all queries ordered by (normalised key of imm3_query_set_order, global segment, row in
+ * segment), then the first `limit` of them when limit > 0 -- exactly the rows, and the tie order, of ONE ordered imm3_table query over
+ * all the segments in global order.
+ *   segment_out[i]  the global segment of row i
+ *   row_out[i]      the row in that segment (a table query's rows: what imm3_query_locate_rows gives, not the virtual index)
+ *   col_out[j]      `width` bytes per row of SELECT-list column j, as imm3_query_fetch_rows packs them
+ * Any output pointer may be NULL.  *n_rows is the merged total after the limit even when max_rows is smaller; max_rows rows are written.
+ * The limit rule: with limit > 0 every query's own order limit must be <= 0 or >= limit, with limit <= 0 every query's own limit must
+ * be <= 0 (a list cut shorter may lack rows the merge needs); a table query whose global indices do not ascend must have no limit
+ * of its own (its ties were cut in table order).
+ * IMM3_ERR_ARG: a null query, one that is not an ordered projection, queries (of this rank or of different ranks) that differ in
+ * SELECT-list shape, order keys or limit, a violated limit rule, a negative or repeated segment index on this rank, more than 2^30
+ * rows entering a merge; IMM3_ERR_STATE: a query that has not been run.  All of these are found before the first collective and
+ * reach every rank: the failing rank returns its own error, the others "another rank failed"; no rank is left waiting and the
+ * communicator stays usable.  Synchronous.  Cost: every record is ranked by binary search in every other list -- made for the top-k
+ * case (at most limit rows per list); an unlimited merge of millions of rows is exact but latency-bound. */
+int imm3_comm_merge_ordered(imm3_comm *c, imm3_query *const *queries, const int32_t *segment_index, int32_t n_queries,
+                            int64_t limit, uint32_t *segment_out, uint32_t *row_out, void *const *col_out,
+                            uint64_t max_rows, uint64_t *n_rows);
+/* Single-process flavour (comms from imm3_comm_create_all), as imm3_comm_merge_groups_wide_all: per device the one-rank merge cut to
+ * `limit`, then one merge of the devices' lists inside this process. */
+int imm3_comm_merge_ordered_all(imm3_comm *const *comms, int32_t n_comms, imm3_query *const *const *queries,
+                                const int32_t *const *segment_index, const int32_t *n_queries,
+                                int64_t limit, uint32_t *segment_out, uint32_t *row_out, void *const *col_out,
+                                uint64_t max_rows, uint64_t *n_rows);
 
 /* ---- write side of the PFOR_INT codec (host code, no device involved) ----
  * PFORCodecInt.encode (core/codec/PFORCodec.scala:19-31), which SegmentWriter.flush applies to each block of a PFOR_INT
