@@ -175,7 +175,8 @@ __global__ __launch_bounds__(64) void k_snappy_decode(const SnappyArgs a) {
                     if (kind == 0) {
                         if (len > 60u) {
                             const uint32_t nb = len - 60u;
-                            len = (nb == 4u ? le : (le & ((1u << (8u * nb)) - 1u))) + 1u;
+                            const uint32_t l = nb == 4u ? le : (le & ((1u << (8u * nb)) - 1u));
+                            len = l + (l != 0xFFFFFFFFu); // (2^32 bytes must not wrap to a literal of none: clamped below)
                             hdr = 1u + nb;
                         }
                     } else if (kind == 1) { len = 4u + ((tag >> 2) & 7u); off = ((tag >> 5) << 8) | c1; hdr = 2u; }

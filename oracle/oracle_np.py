@@ -369,6 +369,7 @@ def pfor_decode_block(blk: bytes) -> np.ndarray:
     pos, init, n_mini = 1, 0, n // 32
 
     def unpack(pos, b, init):
+        assert b <= 32 and pos + b <= w.size, "malformed pfor block (width above 32 or data past the block end)"
         if b == 32:
             return w[pos:pos + 32].copy()
         if b == 0:
@@ -379,6 +380,7 @@ def pfor_decode_block(blk: bytes) -> np.ndarray:
 
     m = 0
     while m + 4 <= n_mini:
+        assert pos < w.size
         h = int(w[pos]); pos += 1
         for k in range(4):
             b = (h >> (24 - 8 * k)) & 255
@@ -387,6 +389,7 @@ def pfor_decode_block(blk: bytes) -> np.ndarray:
             init = int(out[32 * (m + k) + 31])
         m += 4
     while m < n_mini:
+        assert pos < w.size
         b = int(w[pos]); pos += 1
         out[32 * m:32 * m + 32] = unpack(pos, b, init)
         pos += b
@@ -398,6 +401,7 @@ def pfor_decode_block(blk: bytes) -> np.ndarray:
         for k in range(32 * n_mini, n):
             val, shift = 0, 0
             while True:
+                assert i < by.size and shift <= 28, "malformed pfor block (tail past the block end or a value of more than five bytes)"
                 c = int(by[i]); i += 1
                 val += (c & 127) << shift
                 if c & 128:
@@ -445,6 +449,7 @@ def crc32c_masked(data: bytes) -> int:
 def snappy_raw_decode(data: bytes) -> bytes:
     ip, want, shift = 0, 0, 0
     while True:
+        assert ip < len(data) and shift <= 28, "malformed preamble"
         b = data[ip]; ip += 1
         want |= (b & 127) << shift
         if not b & 128:
@@ -458,11 +463,14 @@ def snappy_raw_decode(data: bytes) -> bytes:
             ln = (tag >> 2) + 1
             if ln > 60:
                 nb = ln - 60
+                assert ip + nb <= len(data)
                 ln = int.from_bytes(data[ip:ip + nb], "little") + 1
                 ip += nb
+            assert ip + ln <= len(data) and len(out) + ln <= want
             out += data[ip:ip + ln]
             ip += ln
             continue
+        assert ip + (1, 2, 4)[kind - 1] <= len(data)
         if kind == 1:
             ln, off = 4 + ((tag >> 2) & 7), ((tag >> 5) << 8) | data[ip]
             ip += 1
@@ -472,7 +480,7 @@ def snappy_raw_decode(data: bytes) -> bytes:
         else:
             ln, off = 1 + (tag >> 2), int.from_bytes(data[ip:ip + 4], "little")
             ip += 4
-        assert 0 < off <= len(out)
+        assert 0 < off <= len(out) and len(out) + ln <= want
         start = len(out) - off
         pattern = bytes(out[start:start + min(off, ln)])       # an overlapping copy repeats its first `off` bytes
         out += (pattern * (ln // len(pattern) + 1))[:ln]
