@@ -839,6 +839,7 @@ static void query_free(imm3_query *q) {
     pool_release(ctx, q->d_order_state); pool_release(ctx, q->d_order_counts); pool_release(ctx, q->d_order_diff); pool_release(ctx, q->d_order_tally);
     pool_release(ctx, q->d_order_row_index);
     for (auto p : q->d_order_proj) pool_release(ctx, p);
+    group_order_release(q);
     for (auto &p : q->preds) pool_release(ctx, p.d_blob);
     for (auto &t : q->expr_terms)
         for (auto &p : t) pool_release(ctx, p.d_blob);
@@ -2209,6 +2210,7 @@ int imm3::run_agg(imm3_query *q) {
     const int rc = launch_agg(q, a, ctx->stream, true);
     if (rc) return rc;
     q->run.ran_agg = true;
+    q->run.group_order_valid = false; // (new groups: an ordered view is made again when a getter asks)
     return IMM3_OK;
 }
 
@@ -2281,6 +2283,10 @@ extern "C" int imm3_query_agg_shape(const imm3_query *q, int32_t *n_group_cols, 
 
 extern "C" int imm3_query_group_count(imm3_query *q, uint32_t *n_groups) {
     if (!q || !n_groups) return fail(IMM3_ERR_ARG, "null argument");
+    if (q->group_ordered) { // (imm3_query_set_group_order: min(groups, limit))
+        CTX_LIVE(q->ctx);
+        return group_order_settle(q, n_groups);
+    }
     return settle_groups(q, n_groups);
 }
 
@@ -2306,6 +2312,7 @@ static int gather_group_keys(imm3_query *q, uint32_t n, std::vector<uint8_t> &ou
 extern "C" int imm3_query_fetch_groups(imm3_query *q, uint64_t *keys, uint32_t *first_row, uint64_t *counts, int64_t *vals, uint32_t max_groups) {
     if (!q) return fail(IMM3_ERR_ARG, "query is null");
     CTX_LIVE(q->ctx);
+    if (q->group_ordered) return group_order_fetch_groups(q, keys, first_row, counts, vals, max_groups); // (ordered on the device: only the groups asked for are copied)
     uint32_t n = 0;
     const int rc = settle_groups(q, &n);
     if (rc) return rc;
@@ -2354,6 +2361,7 @@ extern "C" int imm3_query_fetch_group_strings(imm3_query *q, int32_t agg, uint8_
     if (q->aggs[(size_t)agg].kind != IMM3_AGG_MAX || sc.vcodec != IMM3_DENSE_STRING) return fail(IMM3_ERR_ARG, "the aggregate is not a MAX over a STRING column");
     if (!out && max_groups > 0) return fail(IMM3_ERR_ARG, "out is null");
     CTX_LIVE(q->ctx);
+    if (q->group_ordered) return group_order_fetch_strings(q, agg, out, max_groups);
     uint32_t n = 0;
     const int rc = settle_groups(q, &n);
     if (rc) return rc;
@@ -2399,6 +2407,7 @@ extern "C" int imm3_query_fetch_group_keys(imm3_query *q, uint8_t *out, uint32_t
     if (!q->is_agg) return fail(IMM3_ERR_ARG, "not an aggregation query");
     if (!out && max_groups > 0) return fail(IMM3_ERR_ARG, "out is null");
     CTX_LIVE(q->ctx);
+    if (q->group_ordered) return group_order_fetch_keys(q, out, max_groups);
     uint32_t n = 0;
     const int rc = settle_groups(q, &n);
     if (rc) return rc;

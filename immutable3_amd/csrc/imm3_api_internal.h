@@ -88,6 +88,13 @@ int expr_normalize(const std::vector<ExprCol> &leaf_cols, const imm3_select *lea
 int order_check_args(bool is_agg, int32_t n_proj, const int32_t *proj_widths, int64_t create_limit, bool has_run,
                      const imm3_order_key *keys, int32_t n_keys, int64_t limit, int32_t *key_bytes_out);
 
+// ---- imm3_group_order_api.cpp: the ordered view of an aggregation's groups (imm3_query_set_group_order) ----
+void group_order_release(imm3_query *q);                              // its buffers back to the pool (query destruction; grown dense arrays)
+int group_order_settle(imm3_query *q, uint32_t *n_groups);            // settle the groups, order them on the device: *n_groups = min(groups, limit)
+int group_order_fetch_groups(imm3_query *q, uint64_t *keys, uint32_t *first_row, uint64_t *counts, int64_t *vals, uint32_t max_groups);
+int group_order_fetch_strings(imm3_query *q, int32_t agg, uint8_t *out, uint32_t max_groups); // `agg` checked by the caller
+int group_order_fetch_keys(imm3_query *q, uint8_t *out, uint32_t max_groups);
+
 // ---- imm3_str_range.cpp: IMM3_STR_RANGE over plain values ----
 int str_range_check_leaf(int32_t n_match, const uint8_t *bytes, const int32_t *lens, int32_t width);   // the leaf's own checks (width <= 0: not held against a column)
 void str_range_pad(const uint8_t *lo, int32_t lo_len, const uint8_t *hi, int32_t hi_len, int32_t width, std::string &lo_out, std::string &hi_out);

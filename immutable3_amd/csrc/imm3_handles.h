@@ -75,6 +75,7 @@ enum TuningVariant : int {
     TV_EAGER_BITMAP = 19,       // a projection through survivor records stores its bitmap in the staging launch
     TV_ORDER_FULL_SORT = 23,    // an ordered query with a limit sorts every row: no radix select in front of the sort
     TV_ORDER_SELECT_ALWAYS = 24, // ... takes the radix select whenever the limit is below the survivors (the threshold sweep of tools/order_bench.py)
+    TV_GROUP_ORDER_RADIX = 25,  // an ordered aggregation (imm3_query_set_group_order) takes the radix path whatever the group count: no one-work-group launch
     TV_TILE_ABLATION = 20,      // 20 .. 22: k_filter_tile's ablation switches (tools' build only)
     TV_EMIT_ABLATION = 34,      // 34 .. 35: k_emit's ablation switches (tools' build only)
     TV_PROJECT_ABLATION = 50,   // 50 + mask (mask <= 255): k_filter_project's ablation mask (tools' build only)
@@ -144,6 +145,7 @@ struct QueryRunState {
     bool limit_gather_ran = false;   // the last projection was k_limit_gather's one launch: settle_rows looks at its give-up tag
     bool ran_single_pass = false;    // the last run went through k_filter_project ...
     bool sp_verified = false;        // ... and its status word has been read since (rows complete, or gathered again from the bitmap)
+    bool group_order_valid = false;  // an ordered aggregation (imm3_query_set_group_order): the ordered group arrays hold the order of the last run's groups (a run clears it: run_agg)
     bool order_valid = false;        // an ordered query (imm3_query_set_order): the ordered arrays hold the order of the rows as last emitted (every re-emit clears it: launch_project)
 };
 
@@ -379,6 +381,19 @@ struct imm3_query {
     std::vector<uint8_t *> d_order_proj;
     uint64_t order_cap_rows = 0;              // rows the order's buffers were sized for
     uint64_t order_select_runs = 0, order_full_runs = 0, order_launches = 0, order_counted = 0; // settled ordered runs that took the radix select / sorted every row; times the order was enqueued (imm3_query_plan)
+    // ORDER BY over groups (imm3_query_set_group_order; imm3_group_order.hip, imm3_group_order_api.cpp): applied when a getter settles the groups
+    bool group_ordered = false;
+    std::vector<imm3_group_order_key> group_order_keys;
+    int64_t group_order_limit = 0;            // <= 0: every group
+    imm3::GroupOrderLayout group_order_layout{};
+    imm3::GroupOrderArgs go{};                 // the ordered arrays (dst_*), the gathered wide keys / strings (src_keyb, src_str) and the radix path's key column, as the kernels take them
+    uint32_t *d_go_keys[2] = {nullptr, nullptr}, *d_go_perm[2] = {nullptr, nullptr}; // radix path: the order's ping-pong buffers and tables, made on first need
+    uint32_t *d_go_state = nullptr, *d_go_counts = nullptr, *d_go_diff = nullptr, *d_go_tally = nullptr;
+    std::vector<void *> go_allocs;            // every pool buffer of the group order (released with the query, or when out_cap has grown)
+    uint32_t go_cap = 0;                      // groups the buffers were sized for (out_cap then)
+    bool go_radix_bufs = false;
+    uint32_t go_n_out = 0;                    // groups of the ordered view, min(groups, limit)
+    int32_t go_path = 0;                      // diagnostics (imm3_query_group_order_path): the GroupOrderPath of the last ordered settle
     uint32_t sp_abandoned_runs = 0, sp_busy_runs = 0; // single-pass runs whose rows were gathered from the bitmap instead: a prefix never came / the device was busy (imm3_query_plan)
 };
 

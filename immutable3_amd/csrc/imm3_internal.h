@@ -804,6 +804,52 @@ void launch_merge_order_rank(const MergeOrderArgs &a, hipStream_t s);
 
 } // namespace imm3
 
+// ---- ORDER BY over groups (imm3_group_order.hip; the key layout: imm3_group_order_plan.h): the dense groups of a settled aggregation
+// ordered by a normalised key of 5 .. 16 bytes (the user's keys, then first_row) into dense arrays of their own.  The host knows the
+// group count behind the settle and picks the path: one launch of one work-group up to kGroupOrderSmall groups, above it the radix
+// sort / select of imm3_order.hip over the keys written as ONE byte-string column. ----
+#include "imm3_group_order_plan.h"
+namespace imm3 {
+// Groups the one-work-group path takes.  Its keys and indices live in static LDS as structure-of-arrays words: 4 key words + 1 index
+// word = 20 bytes per group, 2048 x 20 = 40 KiB of the 64 KiB a work-group may declare statically.
+constexpr int kGroupOrderSmall = 2048;
+constexpr int kGroupOrderSmallThreads = 1024;
+enum GroupOrderPath : int32_t { GROUP_ORDER_NONE = 0, GROUP_ORDER_SMALL = 1, GROUP_ORDER_RADIX_FULL = 2, GROUP_ORDER_RADIX_SELECT = 3 };
+struct GroupOrderArgs {
+    GroupOrderLayout layout;
+    uint32_t n;                          // dense groups (host-known: the settle has synchronised)
+    uint32_t n_out;                      // min(n, limit)
+    int32_t n_agg;
+    int32_t key_bytes;                   // bytes of the packed group key
+    int32_t wide_key;                    // 1: the packed key comes from src_keyb (out_keys holds tags), else from out_keys (little-endian)
+    int32_t str_width[kMaxAggs];         // per aggregate with a wide string MAX: its width, else 0
+    // the dense groups (k_group_collect's output), launch_group_keys' bytes of a wide key, launch_strmax_collect's of wide string maxima
+    const unsigned long long *src_keys;
+    const uint32_t *src_first;
+    const unsigned long long *src_counts;
+    const long long *src_vals;           // kMaxAggs per group
+    const uint8_t *src_keyb;
+    const uint8_t *src_str[kMaxAggs];
+    // the ordered groups
+    unsigned long long *dst_keys;
+    uint32_t *dst_first;
+    unsigned long long *dst_counts;
+    long long *dst_vals;
+    uint8_t *dst_keyb;
+    uint8_t *dst_str[kMaxAggs];
+    unsigned long long *dst_n;           // the ordered count, one 64-bit device word
+    // radix path: the key column (layout.key_bytes per group), the group count as the 64-bit word the order launches read, and the
+    // order's state and permutations (OrderArgs) for the gather behind the last pass
+    uint8_t *key_col;
+    unsigned long long *n_word;
+    const uint32_t *perm[2];
+    const uint32_t *state;
+};
+void launch_group_order_small(const GroupOrderArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+void launch_group_order_keys(const GroupOrderArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+void launch_group_order_apply(const GroupOrderArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+} // namespace imm3
+
 #ifdef __HIPCC__
 #include <hip/hip_ext.h>
 // Kernel launch with optional start / stop events stamped by the launch itself (hipExtLaunchKernelGGL); the plain launch

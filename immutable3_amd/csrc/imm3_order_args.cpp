@@ -11,7 +11,7 @@ int fail(int code, const std::string &msg); // sets the calling thread's imm3_la
 // has_run: any run call has been made on it.  *key_bytes_out: the summed width of the key columns.
 int order_check_args(bool is_agg, int32_t n_proj, const int32_t *proj_widths, int64_t create_limit, bool has_run,
                      const imm3_order_key *keys, int32_t n_keys, int64_t limit, int32_t *key_bytes_out) {
-    if (is_agg) return fail(IMM3_ERR_ARG, "imm3_query_set_order: an aggregation query's groups cannot be ordered");
+    if (is_agg) return fail(IMM3_ERR_ARG, "imm3_query_set_order: an aggregation query's groups are ordered by imm3_query_set_group_order");
     if (n_proj <= 0) return fail(IMM3_ERR_ARG, "imm3_query_set_order: the query projects no column (n_proj == 0): there are no rows to order");
     if (has_run) return fail(IMM3_ERR_STATE, "imm3_query_set_order: the query has already run; set the order before the first run");
     if (n_keys < 1 || n_keys > IMM3_ORDER_MAX_KEYS) return fail(IMM3_ERR_ARG, "imm3_query_set_order: n_keys must be 1 .. " + std::to_string(IMM3_ORDER_MAX_KEYS));

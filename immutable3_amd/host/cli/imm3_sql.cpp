@@ -6,6 +6,8 @@
 //                  Engine.scala:236-245).  With --parse-only it also prints the tree's postfix program.
 //   --order-by     accept `order by f [asc|desc] {, f [asc|desc]}` between the where clause and `limit` (default off: the reference's
 //                  grammar, in which such a statement does not parse); the rows come back sorted on the GPU, `limit` applied behind the order.
+//                  An aggregation takes the clause behind its `group by`: `select count(id), max(age) from t group by state order by
+//                  id_count desc limit 10` -- a key is a group-by column, an alias (<col>_count / _max / _min) or the aggregate call itself.
 //   --string-ranges  accept `f like 'value%'`, `f > 'value'` and `f < 'value'` on string columns (default off: the reference's grammar, in
 //                  which such a statement does not parse): byte-order prefix / range predicates, run on the GPU.  With --parse-only and a
 //                  data directory, the leaves of such conditions are also printed as the bytes the library gets ("leafbytes:").
@@ -45,7 +47,13 @@ static std::string showQuery(const Query &q) {
         static const char *names[] = {"Sum", "Avg", "Min", "Max", "Count"};
         p = "ProjectAgg(List(";
         for (size_t i = 0; i < q.project.aggs.size(); ++i) { if (i) p += ", "; p += std::string(names[q.project.aggs[i].kind]) + "(" + q.project.aggs[i].col + ",None)"; }
-        p += ")," + list(q.project.groupBy) + ")";
+        p += ")," + list(q.project.groupBy);
+        if (!q.project.orderBy.empty() || q.project.limit > 0) { // (only under --order-by: the reference's ProjectAgg has two fields)
+            p += ",List(";
+            for (size_t i = 0; i < q.project.orderBy.size(); ++i) p += std::string(i ? ", " : "") + "(" + q.project.orderBy[i].first + "," + (q.project.orderBy[i].second ? "desc" : "asc") + ")";
+            p += ")," + std::to_string(q.project.limit);
+        }
+        p += ")";
     }
     return "Query(" + q.table + "," + showSelect(*q.select) + "," + p + ")";
 }

@@ -538,12 +538,85 @@ struct Aggregator { // CountAggr / MaxDoubleAggr / MinDoubleAggr / MaxStringAggr
 
 using AggMap = std::vector<Aggregator>;                       // alias order = SELECT-list order (see Engine::executeAgg)
 using AggMapTuple = std::pair<std::string, AggMap>;           // (groupKey, aggregators)
+using RawKey = std::vector<std::string>;                      // the raw bytes of a group key's parts, in batch-column order
+
+// ORDER BY over groups: entries (name, descending) over an aggregation's group-by columns and aliases, resolved.  A name that is
+// neither is refused; so is anything but the four aggregators above (ordering by an average is out of scope).
+struct GroupOrderEntry {
+    bool isAgg;
+    std::string name;
+    bool desc;
+};
+inline std::vector<GroupOrderEntry> groupOrderSpec(const std::vector<Aggregator> &aggs, const std::vector<std::string> &groupBy,
+                                                   const std::vector<std::pair<std::string, bool>> &orderBy) {
+    std::vector<GroupOrderEntry> out;
+    for (const auto &k : orderBy) {
+        bool isGroup = false, isAlias = false;
+        for (const auto &g : groupBy) isGroup = isGroup || g == k.first;
+        for (const auto &a : aggs) isAlias = isAlias || a.alias == k.first;
+        if (!isGroup && !isAlias) throw Exception("order by `" + k.first + "' is neither a group-by column nor an aggregate's alias");
+        out.push_back(GroupOrderEntry{!isGroup, k.first, k.second});
+    }
+    return out;
+}
+
+// The host's ORDER BY over MERGED groups (the per-segment fallback; the Python mirror: operators.order_groups): `groups` in merged
+// first-arrival order, raw[i] the raw key parts of groups[i] in the order of groupCols.  The normal form is the device's
+// (include/imm3.h): signed integers biased to unsigned, big-endian; counts as integers; strings byte-wise; a descending key
+// complemented; ties -- all keys equal -- in arrival order.  Cut to `limit` > 0.
+inline void orderGroups(std::vector<AggMapTuple> &groups, const std::vector<RawKey> &raw, const std::vector<Column> &groupCols,
+                        const std::vector<GroupOrderEntry> &spec, int limit) {
+    auto be64 = [](unsigned long long v) { std::string b(8, '\0'); for (int x = 0; x < 8; ++x) b[(size_t)x] = (char)(v >> (8 * (7 - x))); return b; };
+    if (!spec.empty()) {
+        std::vector<std::string> normal(groups.size());
+        for (size_t i = 0; i < groups.size(); ++i) {
+            for (const auto &e : spec) {
+                std::string b;
+                if (!e.isAgg) {
+                    size_t k = 0;
+                    while (k < groupCols.size() && groupCols[k].name != e.name) ++k;
+                    const std::string &r = raw.at(i).at(k);
+                    if (groupCols[k].columnType == ColumnType::STRING) b = r;
+                    else { // int32 / int8, little-endian: sign-extend, then bias
+                        long long v = 0;
+                        for (size_t x = 0; x < r.size(); ++x) v |= (long long)(unsigned char)r[x] << (8 * x);
+                        const int bits = 8 * (int)r.size();
+                        if (bits < 64 && (v >> (bits - 1)) & 1) v -= 1LL << bits;
+                        b = be64((unsigned long long)v ^ (1ULL << 63));
+                    }
+                } else {
+                    const Aggregator *a = nullptr;
+                    for (const auto &x : groups[i].second) if (x.alias == e.name) a = &x;
+                    if (!a) throw Exception("NoSuchElementException: key not found: " + e.name);
+                    if (a->kind == Aggregator::CountAggr) b = be64((unsigned long long)a->counter);
+                    else if (a->kind == Aggregator::MaxStringAggr) b = a->svalue;
+                    else b = be64((unsigned long long)(long long)a->dvalue ^ (1ULL << 63));
+                }
+                if (e.desc) for (auto &ch : b) ch = (char)~(unsigned char)ch;
+                normal[i] += b;
+            }
+        }
+        std::vector<size_t> idx(groups.size());
+        for (size_t i = 0; i < idx.size(); ++i) idx[i] = i;
+        std::stable_sort(idx.begin(), idx.end(), [&normal](size_t x, size_t y) { return normal[x] < normal[y]; });
+        std::vector<AggMapTuple> sorted;
+        sorted.reserve(groups.size());
+        for (size_t i : idx) sorted.push_back(std::move(groups[i]));
+        groups.swap(sorted);
+    }
+    if (limit > 0 && groups.size() > (size_t)limit) groups.resize((size_t)limit);
+}
 
 // ProjectAggOp(aggs, op, groupBy): one segment, fused on the GPU (scan+select kernel, LDS hash aggregation kernel)
 class ProjectAggOp : public Operator<AggMapTuple> {
   public:
-    ProjectAggOp(std::vector<Aggregator> aggs, std::shared_ptr<ColumnVectorOperator> op, std::vector<std::string> groupBy)
-        : aggs_(std::move(aggs)), op_(std::move(op)), groupBy_(std::move(groupBy)) {}
+    // orderBy -- (name, descending) over the group-by columns and the aliases -- and limit are applied by the device when ONE query
+    // answers (runOn: a table query); per-segment results are ordered after their merge (orderGroups)
+    ProjectAggOp(std::vector<Aggregator> aggs, std::shared_ptr<ColumnVectorOperator> op, std::vector<std::string> groupBy,
+                 std::vector<std::pair<std::string, bool>> orderBy = {}, int limit = 0)
+        : aggs_(std::move(aggs)), op_(std::move(op)), groupBy_(std::move(groupBy)), limit_(limit) { spec_ = groupOrderSpec(aggs_, groupBy_, orderBy); }
+    const std::vector<GroupOrderEntry> &orderSpec() const { return spec_; }
+    const std::vector<RawKey> &rawKeys() const { return rawKeys_; } // of the groups the last iterator() / runOn produced, in their order
     std::unique_ptr<Iterator<AggMapTuple>> iterator() override {
         std::vector<Leaf> leaves;
         std::vector<int32_t> prog;
@@ -575,7 +648,7 @@ class ProjectAggOp : public Operator<AggMapTuple> {
         QueryHandle h;
         scan->makeAggQuery(leaves, group, abi, h, progp);
         auto it = std::make_unique<VectorIterator<AggMapTuple>>();
-        it->items = decode(h, cols, group, aggs, abi);
+        it->items = decode(h, cols, group, aggs, abi, rawKeys_);
         return it;
     }
 
@@ -614,13 +687,25 @@ class ProjectAggOp : public Operator<AggMapTuple> {
         imm3Check((keyBytes > 8 ? imm3_query_create_table_agg_wide : imm3_query_create_table_agg)(
             scanOp->manager().ctx(), table, usedIdx.data(), (int32_t)usedIdx.size(), sels.data(), (int32_t)sels.size(),
             group.data(), (int32_t)group.size(), abi.data(), (int32_t)abi.size(), scanOp->table().blockSize, &h.q));
-        out = decode(h, cols, group, aggs, abi);
+        if (!spec_.empty()) { // this query's groups are the whole answer: the device orders them and cuts them to the limit
+            std::vector<imm3_group_order_key> keys;
+            for (const auto &e : spec_) {
+                imm3_group_order_key k{e.isAgg ? IMM3_GROUP_ORDER_AGG : IMM3_GROUP_ORDER_GROUP_COL, -1, e.desc ? 1 : 0};
+                if (e.isAgg) { for (size_t j = 0; j < aggs.size(); ++j) if (aggs[j].alias == e.name) k.index = (int32_t)j; }
+                else for (size_t g = 0; g < group.size(); ++g) if (cols[(size_t)group[g]].name == e.name) k.index = (int32_t)g;
+                keys.push_back(k);
+            }
+            imm3Check(imm3_query_set_group_order(h.q, keys.data(), (int32_t)keys.size(), limit_));
+        }
+        out = decode(h, cols, group, aggs, abi, rawKeys_);
+        if (spec_.empty() && limit_ > 0 && out.size() > (size_t)limit_) out.resize((size_t)limit_);
         return true;
     }
 
   private:
     static std::vector<AggMapTuple> decode(QueryHandle &h, const std::vector<Column> &cols, const std::vector<int32_t> &group,
-                                           const std::vector<Aggregator> &aggs, const std::vector<imm3_aggregate> &abi) {
+                                           const std::vector<Aggregator> &aggs, const std::vector<imm3_aggregate> &abi, std::vector<RawKey> &rawKeys) {
+        rawKeys.clear();
         imm3Check(imm3_query_run(h.q));
         uint32_t n = 0;
         imm3Check(imm3_query_group_count(h.q, &n));
@@ -648,6 +733,7 @@ class ProjectAggOp : public Operator<AggMapTuple> {
         for (uint32_t g = 0; g < n; ++g) {
             std::string key;
             int off = 0;
+            rawKeys.emplace_back();
             for (size_t k = 0; k < group.size(); ++k) {
                 const Column &c = cols[(size_t)group[k]];
                 const int w = c.width();
@@ -657,6 +743,7 @@ class ProjectAggOp : public Operator<AggMapTuple> {
                 v.data = packed.data() + (size_t)g * keyBytes + (size_t)off;
                 if (k) key += "_";
                 key += v.value(0).toString(); // mkString("_"), ProjectAggregate.scala:144
+                rawKeys.back().emplace_back((const char *)v.data, (size_t)w);
                 off += w;
             }
             AggMap m = aggs;
@@ -684,6 +771,9 @@ class ProjectAggOp : public Operator<AggMapTuple> {
     std::vector<Aggregator> aggs_;
     std::shared_ptr<ColumnVectorOperator> op_;
     std::vector<std::string> groupBy_;
+    std::vector<GroupOrderEntry> spec_;
+    int limit_ = 0;
+    std::vector<RawKey> rawKeys_;
 };
 
 // ---- Engine (Engine.scala:81-197) ----
@@ -819,7 +909,7 @@ class Engine {
             TablePlan p;
             if (tablePlan(q, p)) {
                 auto scan = std::make_shared<ScanOp>(sm_, 0, q.table, p.used);
-                ProjectAggOp op(aggs, scan, q.project.groupBy);
+                ProjectAggOp op(aggs, scan, q.project.groupBy, q.project.orderBy, q.project.limit);
                 std::vector<AggMapTuple> merged;
                 if (op.runOn(p.table, p.used, p.usedIdx, p.sels, p.tree ? &p.prog : nullptr, merged)) {
                     path_ = p.tree ? "one table query: select tree" : "one table query";
@@ -830,13 +920,15 @@ class Engine {
         }
         auto mkScan = ScanOp::mkScanOp(sm_, q.table);
         std::vector<AggMapTuple> result;
+        std::vector<RawKey> raw; // parallel to `result`: the first arrival's key parts
+        const std::vector<GroupOrderEntry> spec = groupOrderSpec(aggs, q.project.groupBy, q.project.orderBy);
         const int nseg = sm_.sm.getTableSegmentCount(table.name);
         for (int seg = 0; seg < nseg; ++seg) {
             std::shared_ptr<ColumnVectorOperator> op = mkScan(used, seg);
             op = selectOps(q, leaves, op);
             ProjectAggOp agg(aggs, op, q.project.groupBy);
             auto it = agg.iterator();
-            while (it->hasNext()) {
+            for (size_t at = 0; it->hasNext(); ++at) {
                 AggMapTuple t = it->next();
                 bool merged = false;
                 for (auto &r : result)
@@ -845,9 +937,17 @@ class Engine {
                         merged = true;
                         break;
                     }
-                if (!merged) result.push_back(std::move(t));
+                if (!merged) {
+                    result.push_back(std::move(t));
+                    raw.push_back(agg.rawKeys().at(at));
+                }
             }
         }
+        // the merged groups ordered on the host, ties in merged first-arrival order, then the limit
+        std::vector<Column> groupCols;
+        for (const auto &c : used)
+            for (const auto &g : q.project.groupBy) if (c.name == g) { groupCols.push_back(c); break; }
+        orderGroups(result, raw, groupCols, spec, q.project.limit);
         return result;
     }
     std::vector<Row> execute(const Query &q) {

@@ -312,14 +312,38 @@ struct Aggregate { // Query.scala:17-26
     std::string alias; // empty = None
 };
 
+// the alias Engine.resolveProjectOp gives an aggregate without one (Engine.scala:130-156): <col>_max / _min / _count
+inline std::string defaultAlias(const Aggregate &a) {
+    static const char *suffix[] = {"sum", "avg", "min", "max", "count"};
+    return a.alias.empty() ? a.col + "_" + suffix[a.kind] : a.alias;
+}
+
 struct ProjectADT {
     enum Kind { Project, ProjectAgg, NoProject } kind = NoProject;
     std::vector<std::string> cols; // Project
-    int limit = 0;
-    std::vector<std::pair<std::string, bool>> orderBy; // Project: (column, descending), most significant first -- the "sort" Query.scala:27 announces; empty: none
+    int limit = 0;                 // ProjectAgg: > 0 keeps the first `limit` groups of the order (without an order: of the first-seen order)
+    // (name, descending), most significant first -- the "sort" Query.scala:27 announces; empty: none.  Project: a SELECT-list column;
+    // ProjectAgg: a group-by column or an aggregate's alias (imm3_query_set_group_order)
+    std::vector<std::pair<std::string, bool>> orderBy;
     std::vector<Aggregate> aggs;   // ProjectAgg
     std::vector<std::string> groupBy;
 };
+
+// ORDER BY entries of an aggregation checked against its group-by columns and its aggregates' aliases: a name that is neither is refused,
+// and so is an average (ordering by a quotient is out of scope: include/imm3.h).  A name that is both means the group column.
+inline void checkGroupOrderNames(const ProjectADT &p) {
+    for (const auto &k : p.orderBy) {
+        bool found = false;
+        for (const auto &g : p.groupBy) found = found || g == k.first;
+        if (found) continue;
+        for (const auto &a : p.aggs)
+            if (defaultAlias(a) == k.first) {
+                if (a.kind == Aggregate::Avg) throw Exception("order by `" + k.first + "': ordering by an average is not supported");
+                found = true;
+            }
+        if (!found) throw Exception("order by `" + k.first + "' is neither a group-by column nor an aggregate's alias");
+    }
+}
 
 // ORDER BY keys as places in the SELECT list: (index into cols, descending).  A key that is not a SELECT-list column is refused.
 inline std::vector<std::pair<int, bool>> orderKeys(const std::vector<std::string> &cols, const std::vector<std::pair<std::string, bool>> &orderBy) {

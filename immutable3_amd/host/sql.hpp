@@ -13,6 +13,9 @@
 // EXTENSION, only when the parser is asked for it (parseAll(sql, true); imm3_sql --order-by) -- the "sort" core/Query.scala:27 announces:
 //   queryProject     := "select" repsep(ident, ",") "from" ident where orderBy limit
 //   orderBy          := opt("order" "by" rep1sep(ident opt("asc" | "desc"), ","))
+//   queryProjectAgg  := "select" rep1sep(agg, ",") "from" ident where ["group" "by" rep1sep(ident, ",")] orderBy limit
+// an aggregation's order key being an ident (a group-by column or an alias) or an aggregate call as written in the SELECT list
+// (`count(id)`), which resolves to its alias (id_count); a name that is neither is refused.
 // With the flag off the grammar is the reference's, and such a statement fails to parse as it always has.
 // EXTENSION, only when asked for (parseAll(sql, orderBy, true); imm3_sql --string-ranges) -- byte-order ranges on string columns
 // (SelectCondition::prefix / strGT / strLT), tried behind the reference's alternatives:
@@ -186,14 +189,33 @@ class SQLParser {
         return true;
     }
     // opt("order" ~ "by" ~> rep1sep(ident ~ opt("asc" | "desc"), ",")): the position behind the clause, or i when there is none
-    size_t orderByClause(size_t i, std::vector<std::pair<std::string, bool>> &out) {
+    // an order key: ident, or -- in an aggregation (aggs) -- an aggregate call as written in the SELECT list, which names its alias
+    bool orderKey(size_t i, bool aggs, std::string &name, size_t &end) {
+        Aggregate a;
+        if (aggs && agg(i, a, end)) { name = defaultAlias(a); return true; }
+        return ident(i, name, end);
+    }
+    // opt("limit" digits): the position behind it, or d when there is none
+    size_t limitClause(size_t d, int &limit) {
+        size_t e;
+        if (lit(d, "limit", e)) {
+            size_t k = skipWs(e), j = k;
+            while (j < s_.size() && std::isdigit((unsigned char)s_[j])) ++j;
+            if (j > k) {
+                limit = std::atoi(s_.substr(k, j - k).c_str());
+                return j;
+            }
+        }
+        return d;
+    }
+    size_t orderByClause(size_t i, std::vector<std::pair<std::string, bool>> &out, bool aggs = false) {
         size_t p, q;
         if (!lit(i, "order", p) || !lit(p, "by", q)) return i;
         std::vector<std::pair<std::string, bool>> keys;
         for (;;) {
             std::string f;
             size_t r, t;
-            if (!ident(q, f, r)) break;
+            if (!orderKey(q, aggs, f, r)) break;
             bool desc = false;
             if (lit(r, "desc", t)) { desc = true; r = t; }
             else if (lit(r, "asc", t)) r = t;
@@ -202,7 +224,7 @@ class SQLParser {
             if (!lit(q, ",", t)) break;
             std::string g;
             size_t u;
-            if (!ident(t, g, u)) break; // (rep1sep backtracks over a dangling separator)
+            if (!orderKey(t, aggs, g, u)) break; // (rep1sep backtracks over a dangling separator)
             q = t;
         }
         if (keys.empty()) return i;
@@ -251,17 +273,18 @@ class SQLParser {
             std::shared_ptr<SelectADT> w;
             if (selectProjectAgg(i, p, a) && fromTable(a, t, b) && where(b, w, c)) {
                 std::vector<std::string> g;
+                // parseAll: this alternative only wins if it consumes everything; otherwise Scala's `|`
+                // has already committed to it (first success), and parseAll then fails on the leftovers.
                 if (lit(c, "group", d) && lit(d, "by", e) && identList(e, true, g, f)) {
                     p.groupBy = g;
-                    out = Query{t, w, p};
                     end = f;
-                    // parseAll: this alternative only wins if it consumes everything; otherwise Scala's `|`
-                    // has already committed to it (first success), and parseAll then fails on the leftovers.
-                    return true;
+                } else end = c; // queryProjectAggNoGroup
+                if (orderBy_) { // (the opt-in: with it off the statement ends here, as in the reference)
+                    end = orderByClause(end, p.orderBy, true);
+                    end = limitClause(end, p.limit);
+                    checkGroupOrderNames(p);
                 }
-                // queryProjectAggNoGroup
                 out = Query{t, w, p};
-                end = c;
                 return true;
             }
         }
@@ -274,16 +297,8 @@ class SQLParser {
                 ProjectADT p;
                 p.kind = ProjectADT::Project;
                 p.cols = cols;
-                size_t e;
                 if (orderBy_) d = orderByClause(d, p.orderBy);
-                if (lit(d, "limit", e)) {
-                    size_t k = skipWs(e), j = k;
-                    while (j < s_.size() && std::isdigit((unsigned char)s_[j])) ++j;
-                    if (j > k) {
-                        p.limit = std::atoi(s_.substr(k, j - k).c_str());
-                        d = j;
-                    }
-                }
+                d = limitClause(d, p.limit);
                 out = Query{t, w, p};
                 end = d;
                 return true;

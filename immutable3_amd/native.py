@@ -44,7 +44,7 @@ EXPORTS = [
     "imm3_table_create", "imm3_table_destroy", "imm3_query_create_table", "imm3_query_create_table_agg",
     "imm3_query_segment_starts", "imm3_query_locate_rows",
     "imm3_query_create", "imm3_query_create_agg", "imm3_query_group_count", "imm3_query_fetch_groups", "imm3_query_agg_shape",
-    "imm3_query_fetch_group_strings", "imm3_query_destroy", "imm3_query_reserve_rows", "imm3_query_set_order",
+    "imm3_query_fetch_group_strings", "imm3_query_destroy", "imm3_query_reserve_rows", "imm3_query_set_order", "imm3_query_set_group_order",
     "imm3_query_create_agg_wide", "imm3_query_create_table_agg_wide", "imm3_query_fetch_group_keys",
     "imm3_query_create_expr", "imm3_query_create_agg_expr", "imm3_query_create_table_expr", "imm3_query_create_table_agg_expr",
     "imm3_query_run", "imm3_query_run_select", "imm3_query_run_count", "imm3_query_sync", "imm3_query_join_count", "imm3_query_log_counts",
@@ -62,11 +62,17 @@ DIAG_EXPORTS = [
     "imm3_ctx_measure_read_gbps", "imm3_ctx_devclock_enable", "imm3_ctx_devclock_collect", "imm3_ctx_devclock_raw", "imm3_query_plan",
     "imm3_ctx_inject_fault", "imm3_ctx_debug_device_lock", "imm3_plan_predict", "imm3_comm_debug_standin", "imm3_plan_limit_scan",
     "imm3_plan_table_limit", "imm3_plan_string_route", "imm3_plan_string_range_route", "imm3_plan_limit_chunks",
-    "imm3_query_agg_form", "imm3_query_expr_form", "imm3_expr_normalize",
+    "imm3_query_agg_form", "imm3_query_expr_form", "imm3_expr_normalize", "imm3_query_group_order_path",
 ]
 COMM_ID_BYTES = 128
 # imm3_query_device_ptr ids of an ordered query's arrays (include/imm3.h)
 PTR_ORDER_ROW_INDEX, PTR_ORDER_ROW_COUNT, PTR_ORDER_COLUMN = 0x1000, 0x1001, 0x2000
+# ORDER BY over groups (include/imm3.h: imm3_query_set_group_order; include/imm3_diag.h: imm3_query_group_order_path)
+GROUP_ORDER_GROUP_COL, GROUP_ORDER_AGG = 0, 1
+GROUP_ORDER_KEY_MAX_WIDTH = 12
+GROUP_ORDER_NONE, GROUP_ORDER_SMALL, GROUP_ORDER_RADIX_FULL, GROUP_ORDER_RADIX_SELECT = 0, 1, 2, 3
+GROUP_ORDER_SMALL_MAX = 2048   # groups the one-work-group launch takes (csrc/imm3_internal.h: kGroupOrderSmall)
+TV_GROUP_ORDER_RADIX = 25      # tuning variant: an ordered aggregation takes the radix path whatever its group count
 TV_ORDER_FULL_SORT, TV_ORDER_SELECT_ALWAYS = 23, 24   # tuning variants (csrc/imm3_handles.h): an ordered query with a limit always sorts every row / always selects
 
 
@@ -174,6 +180,8 @@ def load() -> C.CDLL:
     L.imm3_query_destroy.argtypes = [vp]
     L.imm3_query_reserve_rows.argtypes = [vp, u64]
     L.imm3_query_set_order.argtypes = [vp, vp, i32, i64]
+    L.imm3_query_set_group_order.argtypes = [vp, vp, i32, i64]
+    L.imm3_query_group_order_path.argtypes = [vp, P(i32)]
     L.imm3_query_run.argtypes = [vp]
     L.imm3_query_run_select.argtypes = [vp]
     L.imm3_query_run_count.argtypes = [vp]
@@ -697,6 +705,19 @@ class DeviceQuery:
         first `limit` rows of the ordered result.  Before the first run; row_count / fetch_rows then answer in that order."""
         ks = np.array([[int(p), 1 if d else 0] for (p, d) in keys] or [[0, 0]], dtype=np.int32)
         _check(load().imm3_query_set_order(self._h, ks.ctypes.data, len(keys), int(limit)))
+
+    def set_group_order(self, keys: Sequence[tuple], limit: int = 0):
+        """ORDER BY over groups (imm3_query_set_group_order): keys = [(GROUP_ORDER_GROUP_COL | GROUP_ORDER_AGG, index, descending)], most
+        significant first; limit > 0: the first `limit` groups of the order.  Before or after runs; the group getters then answer in
+        that order.  No keys: first-seen order again."""
+        ks = np.array([[int(k), int(i), 1 if d else 0] for (k, i, d) in keys] or [[0, 0, 0]], dtype=np.int32)
+        _check(load().imm3_query_set_group_order(self._h, ks.ctypes.data, len(keys), int(limit)))
+
+    def group_order_path(self) -> int:
+        """The path the last ordered settle took: GROUP_ORDER_NONE / _SMALL / _RADIX_FULL / _RADIX_SELECT (include/imm3_diag.h)."""
+        p = C.c_int32(0)
+        _check(load().imm3_query_group_order_path(self._h, C.byref(p)))
+        return p.value
 
     def run(self):
         _check(load().imm3_query_run(self._h))

@@ -705,7 +705,61 @@ def resolveProjectOp(projectAgg: ProjectAgg, table: Table):
             aggs.append(CountAggr(a.col, a.alias or a.col + "_count"))
         else:
             raise Exception("Unknown Aggregate type")
-    return lambda op: ProjectAggOp(aggs, op, list(projectAgg.groupBy))
+    return lambda op: ProjectAggOp(aggs, op, list(projectAgg.groupBy), getattr(projectAgg, "order_by", ()), getattr(projectAgg, "limit", 0))
+
+
+def group_order_spec(aggs: Sequence[Aggregator], groupBy: Sequence[str], order_by):
+    """ORDER BY entries (name, descending) over an aggregation's group-by columns and aliases -> [(is_agg, name, descending)].  A name
+    that is neither raises ValueError naming it; so does an AvgDoubleAggr's alias (ordering by a quotient is out of scope)."""
+    by_alias = {a.alias: a for a in aggs}
+    out = []
+    for (name, desc) in order_by:
+        if name in groupBy:
+            out.append((False, name, bool(desc)))
+        elif name in by_alias:
+            if isinstance(by_alias[name], AvgDoubleAggr):
+                raise ValueError(f"order by {name!r}: ordering by an average is not supported")
+            out.append((True, name, bool(desc)))
+        else:
+            raise ValueError(f"order by {name!r} is neither a group-by column {list(groupBy)} nor an aggregate's alias {list(by_alias)}")
+    return out
+
+
+def _order_bytes(v: int, nbytes: int, bias: int) -> bytes:
+    return (int(v) + bias).to_bytes(nbytes, "big")
+
+
+def order_groups(result: Dict[str, dict], raw_keys: Dict[str, Sequence[bytes]], group_cols: Sequence[Column], spec, limit: int = 0) -> Dict[str, dict]:
+    """The host's ORDER BY over MERGED groups (the per-segment fallback and device_merge; the C++ mirror: host/operators.hpp
+    orderGroups): `result` is key -> {alias: Aggregator} in merged first-arrival order, raw_keys[key] the raw bytes of the key's parts
+    in the order of group_cols, spec group_order_spec's.  The normal form is the device's (include/imm3.h): signed integers biased to
+    unsigned, big-endian; counts and sums as integers; strings byte-wise; a descending key complemented; ties -- all keys equal --
+    in arrival order.  Cut to `limit` > 0.  Returns a new dict that iterates in the order asked for."""
+    names = [c.name for c in group_cols]
+    normal = []
+    for arrival, (key, aggmap) in enumerate(result.items()):
+        parts = []
+        for (is_agg, name, desc) in spec:
+            if not is_agg:
+                col, raw = group_cols[names.index(name)], bytes(raw_keys[key][names.index(name)])
+                if col.codec in CodecType.INT_CODECS or col.codec in CodecType.TINYINT_CODECS:
+                    b = _order_bytes(int.from_bytes(raw, "little", signed=True), 8, 1 << 63)
+                else:
+                    b = raw
+            else:
+                a = aggmap[name]
+                if isinstance(a, CountAggr):
+                    b = _order_bytes(a.get(), 16, 0)
+                elif isinstance(a, MaxStringAggr):
+                    b = a.get().encode("utf-8")     # (new String(bytes) of the value: the bytes again for ASCII)
+                else:                                   # Max / MinDoubleAggr: the integral value of an Int / Byte column
+                    b = _order_bytes(int(a.get()), 16, 1 << 127)
+            parts.append(bytes(255 - x for x in b) if desc else b)
+        normal.append((tuple(parts), arrival, key))
+    normal.sort(key=lambda t: (t[0], t[1]))
+    if limit > 0:
+        normal = normal[:limit]
+    return {key: result[key] for (_, _, key) in normal}
 
 
 class ProjectAggOp(Operator):
@@ -713,8 +767,15 @@ class ProjectAggOp(Operator):
     first-seen order.  The whole chain of one segment runs fused on the GPU: scan+select kernel, then the LDS
     hash-aggregation kernel; group keys and aggregates come back already reduced."""
 
-    def __init__(self, aggs: Sequence[Aggregator], op: ColumnVectorOperator, groupBy: Sequence[str]):
+    def __init__(self, aggs: Sequence[Aggregator], op: ColumnVectorOperator, groupBy: Sequence[str], order_by=(), limit: int = 0):
+        """order_by -- entries (name, descending) over the group-by columns and the aggregates' aliases -- and limit are applied by the
+        device when ONE query answers (a table query: _run(ordered=True)); per-segment results are ordered after their merge
+        (order_groups).  raw_keys: group key -> the raw bytes of its parts, for every group this operator has yielded."""
         self.aggs, self.op, self.groupBy = list(aggs), op, list(groupBy)
+        self.order_by = tuple((str(c), bool(d)) for (c, d) in order_by)
+        self.limit = int(limit)
+        self.order_spec = group_order_spec(self.aggs, self.groupBy, self.order_by)   # (ValueError: an unknown name, an average)
+        self.raw_keys: Dict[str, list] = {}
 
     @staticmethod
     def make(aggs, groupBy):           # ProjectAggregate.scala:116-122
@@ -770,10 +831,21 @@ class ProjectAggOp(Operator):
         q.run()
         return q
 
-    def _run(self, seg, cols, used_idx, sels, block_size, expr=None):
-        """seg: a DeviceSegment or a DeviceTable (then the groups are already merged across segments)."""
+    def _native_order(self, cols):
+        """order_spec as imm3_query_set_group_order's keys: places in the native group_cols / aggs lists of _open"""
+        colnames, group_idx, aggs, _, _, _ = self._shape(list(cols))
+        gnames = [colnames[i] for i in group_idx]
+        aliases = [a.alias for a in aggs]
+        return [(native.GROUP_ORDER_AGG, aliases.index(name), desc) if is_agg else (native.GROUP_ORDER_GROUP_COL, gnames.index(name), desc)
+                for (is_agg, name, desc) in self.order_spec]
+
+    def _run(self, seg, cols, used_idx, sels, block_size, expr=None, ordered=False):
+        """seg: a DeviceSegment or a DeviceTable (then the groups are already merged across segments).  ordered: this query's groups are
+        the whole answer -- the device orders them and cuts them to the limit (imm3_query_set_group_order)."""
         _, _, _, _, wide_key, wide_strs = self._shape(list(cols))
         q = self._open(seg, cols, used_idx, sels, block_size, expr)
+        if ordered and self.order_spec:
+            q.set_group_order(self._native_order(cols), self.limit)
         keys, first, counts, vals = q.fetch_groups()
         key_bytes = q.fetch_group_keys() if wide_key else None
         # a MaxStringAggr over a column wider than 8 bytes: vals hold its first 8 bytes, the exact value comes from the device
@@ -793,9 +865,12 @@ class ProjectAggOp(Operator):
         for g in range(counts.shape[0]):
             raw = bytes(key_bytes[g]) if key_bytes is not None else int(keys[g]).to_bytes(8, "little")
             parts, off = [], 0
+            raw_parts = []
             for i, w in zip(group_idx, widths):
                 parts.append(_key_part(scan.cols[i], raw[off: off + w]))
+                raw_parts.append(raw[off: off + w])
                 off += w
+            self.raw_keys.setdefault("_".join(parts), raw_parts)
             out = {}
             for j, a in enumerate(aggs):
                 na = a.make()
@@ -985,8 +1060,8 @@ class Engine:
         if plan is not None:
             dt, used, used_idx, sels, prog = plan
             agg_op = resolveProjectOp(query.project, table)(ScanOp(self.sm, 0, query.table, used))
-            try:
-                return dict(agg_op._run(dt, used, used_idx, sels, table.blockSize, prog))
+            try:   # ONE table query: the device orders its groups and cuts them to the limit
+                return self._cut(dict(agg_op._run(dt, used, used_idx, sels, table.blockSize, prog, ordered=True)), agg_op)
             except native.Imm3Error as e:
                 if not self._table_tree_refused(e, prog):
                     raise
@@ -997,20 +1072,38 @@ class Engine:
         if self.device_merge:
             return self._execute_agg_device_merge(table, used, leaves, mk_scan, mk_agg)
         result = {}
+        raw_keys: Dict[str, list] = {}
+        agg_op = None
         for segIdx in range(self.sm.getTableSegmentCount(table.name)):
             if not self.sm.owns(table.name, segIdx):
                 continue
             op = mk_scan(used, segIdx)
             for leaf in leaves:
                 op = leaf(op)
-            for key, aggmap in mk_agg(op).iterator():
+            agg_op = mk_agg(op)
+            for key, aggmap in agg_op.iterator():
+                raw_keys.setdefault(key, agg_op.raw_keys[key])
                 cur = result.get(key)
                 if cur is None:
                     result[key] = aggmap
                 else:
                     for alias, agg in aggmap.items():
                         cur[alias] = cur[alias].combine(agg) if alias in cur else agg
-        return result
+        return self._order_merged(result, raw_keys, used, agg_op)
+
+    @staticmethod
+    def _cut(result: dict, agg_op) -> dict:
+        """a limit without an order: the first `limit` groups in first-seen order (an ordered query was cut by whoever ordered it)"""
+        if agg_op is None or agg_op.order_spec or agg_op.limit <= 0:
+            return result
+        return dict(list(result.items())[: agg_op.limit])
+
+    def _order_merged(self, result: dict, raw_keys, used, agg_op) -> dict:
+        """ORDER BY / limit over groups that were merged from per-segment results: on the host (order_groups)"""
+        if agg_op is None or not agg_op.order_spec:
+            return self._cut(result, agg_op)
+        group_cols = [c for c in used if c.name in agg_op.groupBy]      # batch-column order: the order of a key's parts
+        return order_groups(result, raw_keys, group_cols, agg_op.order_spec, agg_op.limit)
 
     def _execute_agg_device_merge(self, table, used, leaves, mk_scan, mk_agg):
         """execute_agg's per-segment branch with the combine on the GPU: every owned segment's aggregation query stays open, one
@@ -1051,7 +1144,7 @@ class Engine:
                 for q in qs:
                     q.close()
         wide = {j: strs[j] for j in agg_op._shape(list(used))[5]}
-        return dict(agg_op._groups(used, None, key_bytes, counts, vals, wide))
+        return self._order_merged(dict(agg_op._groups(used, None, key_bytes, counts, vals, wide)), agg_op.raw_keys, used, agg_op)
 
     def execute_table_columns(self, query: Query):
         """Project query over the whole table as ONE fused launch: (segment uint32[n], row uint32[n], [column arrays])

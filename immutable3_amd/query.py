@@ -207,14 +207,39 @@ class Count(Aggregate):            # Query.scala:25
     pass
 
 
+def default_alias(agg: Aggregate) -> str:
+    """the alias Engine.resolveProjectOp gives an aggregate without one (Engine.scala:130-156): <col>_max / _min / _count"""
+    suffix = {Max: "max", Min: "min", Count: "count", Sum: "sum", Avg: "avg"}[type(agg)]
+    return agg.alias or f"{agg.col}_{suffix}"
+
+
+def group_order_names(aggs, groupBy, order_by):
+    """ORDER BY entries (name, descending) of an aggregation checked against its group-by columns and its aggregates' aliases: a name
+    that is neither raises ValueError naming it, and so does an average (ordering by a quotient is out of scope: include/imm3.h).  A
+    name that is both a group column and an alias means the group column."""
+    aliases = {default_alias(a): a for a in aggs}
+    for (name, _) in order_by:
+        if name in groupBy:
+            continue
+        if name not in aliases:
+            raise ValueError(f"order by {name!r} is neither a group-by column {list(groupBy)} nor an aggregate's alias {list(aliases)}")
+        if isinstance(aliases[name], Avg):
+            raise ValueError(f"order by {name!r}: ordering by an average is not supported")
+
+
 @dataclass(frozen=True)
-class ProjectAgg(ProjectADT):      # Query.scala:30
+class ProjectAgg(ProjectADT):      # Query.scala:30; order_by / limit: the "sort" of Query.scala:27 over the groups (imm3_query_set_group_order)
     aggs: tuple
     groupBy: tuple = ()
+    order_by: tuple = ()           # entries (name, descending), most significant first: a group-by column or an aggregate's alias
+    limit: int = 0                 # > 0: the first `limit` groups of the order (without an order: of the first-seen order)
 
-    def __init__(self, aggs, groupBy=()):
+    def __init__(self, aggs, groupBy=(), order_by=(), limit: int = 0):
         object.__setattr__(self, "aggs", tuple(aggs))
         object.__setattr__(self, "groupBy", tuple(groupBy))
+        object.__setattr__(self, "order_by", tuple((str(c), bool(d)) for (c, d) in order_by))
+        object.__setattr__(self, "limit", int(limit))
+        group_order_names(self.aggs, self.groupBy, self.order_by)
 
 
 @dataclass(frozen=True)

@@ -17,6 +17,12 @@ EXTENSION, only when the parser is asked for it -- parseAll(sql, order_by=True) 
   orderBy          := opt("order" "by" rep1sep(ident opt("asc" | "desc"), ","))
 With the flag off the grammar is the reference's, and such a statement fails to parse.
 
+EXTENSION, only when asked for -- parseAll(sql, group_order=True) -- ORDER BY and LIMIT over the groups of an aggregation:
+  queryProjectAgg  := "select" rep1sep(agg, ",") "from" ident where ["group" "by" rep1sep(ident, ",")] orderBy limit
+an order key being an ident (a group-by column or an alias) or an aggregate call as written in the SELECT list (`count(id)`), which
+resolves to its alias (id_count).  A flag of its own, because order_by=True has always left aggregation statements to the reference's
+grammar (imm3_sql's --order-by switches both on).  With the flag off such a statement fails to parse as it always has.
+
 EXTENSION, only when asked for -- parseAll(sql, string_ranges=True) -- byte-order ranges on string columns (query.Prefix / StrGT / StrLT),
 tried behind the reference's alternatives:
   filter           := ... | ident ">" "'" value "'" | ident "<" "'" value "'" | ident "like" "'" value "%" "'"
@@ -36,13 +42,13 @@ class ParseError(Exception):
 
 
 class SQLParser:
-    def __init__(self, s: str, order_by: bool = False, string_ranges: bool = False):
-        self.s, self.order_by, self.string_ranges = s, order_by, string_ranges
+    def __init__(self, s: str, order_by: bool = False, string_ranges: bool = False, group_order: bool = False):
+        self.s, self.order_by, self.string_ranges, self.group_order = s, order_by, string_ranges, group_order
         self.furthest, self.expected = 0, "`select'"
 
     @staticmethod
-    def parseAll(sql: str, order_by: bool = False, string_ranges: bool = False) -> Q.Query:
-        p = SQLParser(sql, order_by, string_ranges)
+    def parseAll(sql: str, order_by: bool = False, string_ranges: bool = False, group_order: bool = False) -> Q.Query:
+        p = SQLParser(sql, order_by, string_ranges, group_order)
         r = p._query(0)
         if r is not None:
             q, end = r
@@ -209,7 +215,24 @@ class SQLParser:
             p = r[1]
         return aggs, p
 
-    def _order_by(self, i):
+    def _order_key(self, i, aggs):
+        """ident, or -- in an aggregation -- an aggregate call, which names its alias"""
+        if aggs:
+            r = self._agg(i)
+            if r is not None:
+                return Q.default_alias(r[0]), r[1]
+        return self._ident(i)
+
+    def _limit(self, d):
+        """opt("limit" digits): (limit, position behind it)"""
+        e = self._lit(d, "limit")
+        if e is not None:
+            m = _DIGITS.match(self.s, self._ws(e))
+            if m:
+                return int(m.group(0)), m.end()
+        return 0, d
+
+    def _order_by(self, i, aggs=False):
         """opt("order" "by" rep1sep(ident opt("asc" | "desc"), ",")): (keys, position behind the clause); no clause: ([], i)"""
         p = self._lit(i, "order")
         q = self._lit(p, "by") if p is not None else None
@@ -217,7 +240,7 @@ class SQLParser:
             return [], i
         keys = []
         while True:
-            r = self._ident(q)
+            r = self._order_key(q, aggs)
             if r is None:
                 break
             name, e = r
@@ -232,7 +255,7 @@ class SQLParser:
             keys.append((name, desc))
             q = e
             t = self._lit(q, ",")
-            if t is None or self._ident(t) is None:      # (rep1sep backtracks over a dangling separator)
+            if t is None or self._order_key(t, aggs) is None:      # (rep1sep backtracks over a dangling separator)
                 break
             q = t
         return (keys, q) if keys else ([], i)
@@ -246,9 +269,12 @@ class SQLParser:
                 d = self._lit(w[1], "group")
                 e = self._lit(d, "by") if d is not None else None
                 g = self._ident_list(e, True) if e is not None else None
-                if g is not None:
-                    return Q.Query(t[0], w[0], Q.ProjectAgg(a[0], g[0])), g[1]
-                return Q.Query(t[0], w[0], Q.ProjectAgg(a[0])), w[1]
+                groups, d = (g[0], g[1]) if g is not None else ([], w[1])
+                order, limit = [], 0
+                if self.group_order:                               # (the opt-in: with it off the statement ends here, as in the reference)
+                    order, d = self._order_by(d, aggs=True)
+                    limit, d = self._limit(d)
+                return Q.Query(t[0], w[0], Q.ProjectAgg(a[0], groups, order, limit)), d
         p = self._lit(i, "select")
         if p is None:
             return None
@@ -260,9 +286,5 @@ class SQLParser:
         d, order, limit = w[1], [], 0
         if self.order_by:
             order, d = self._order_by(d)
-        e = self._lit(d, "limit")
-        if e is not None:
-            m = _DIGITS.match(self.s, self._ws(e))
-            if m:
-                limit, d = int(m.group(0)), m.end()
+        limit, d = self._limit(d)
         return Q.Query(t[0], w[0], Q.Project(cols[0], limit, order)), d

@@ -374,7 +374,8 @@ int imm3_query_agg_shape(const imm3_query *q, int32_t *n_group_cols, int32_t *n_
  * the group; counts: selected rows of the group; vals[g * n_aggs + j]: COUNT -> the count, MIN/MAX numeric -> the
  * int32 value sign-extended, SUM -> the exact int64 sum of the group's selected values (<= 2^32 rows x 2^31: no
  * overflow), MAX string -> the value's bytes packed big-endian (a column wider than 8 bytes: its FIRST 8 bytes packed
- * big-endian; the whole value comes from imm3_query_fetch_group_strings).  Sorted by first_row.
+ * big-endian; the whole value comes from imm3_query_fetch_group_strings).  Sorted by first_row -- or, behind imm3_query_set_group_order,
+ * in that order and cut to its limit (imm3_query_group_count, _fetch_group_strings and _fetch_group_keys likewise).
  * A group key wider than 8 bytes (the _wide entry points): keys[g] holds its FIRST 8 bytes little-endian -- the same packing as a
  * narrow key's, so distinct groups may share keys[g]; the whole key comes from imm3_query_fetch_group_keys. */
 int imm3_query_fetch_groups(imm3_query *q, uint64_t *keys, uint32_t *first_row, uint64_t *counts, int64_t *vals,
@@ -420,11 +421,37 @@ int imm3_query_reserve_rows(imm3_query *q, uint64_t rows);
  * IMM3_ERR_STATE -- the query has already run.  imm3_query_run of an ordered query inside imm3_ctx_capture_begin .. _end:
  * IMM3_ERR_STATE (graph replay of ordered queries is not supported).
  * Merging the ordered results of several queries -- segments, tables, ranks -- is imm3_comm_merge_ordered.
- * OUT OF SCOPE: ordering aggregation results, order keys outside the SELECT list, graph capture of ordered runs. ---- */
+ * Aggregation results are ordered by imm3_query_set_group_order below.
+ * OUT OF SCOPE: order keys outside the SELECT list, graph capture of ordered runs. ---- */
 typedef struct { int32_t proj; int32_t descending; } imm3_order_key;   /* proj: index into the query's SELECT list */
 #define IMM3_ORDER_MAX_KEYS 4
 #define IMM3_ORDER_KEY_MAX_WIDTH 16   /* sum of the key columns' widths, bytes */
 int imm3_query_set_order(imm3_query *q, const imm3_order_key *keys, int32_t n_keys, int64_t limit);
+
+/* ---- ORDER BY over groups: `select state, count(id), max(age) from t group by state order by id_count desc limit 10`.
+ * Called on an AGGREGATION query from any of the eight aggregation creators (segment or table, flat or _expr, narrow or _wide), before
+ * or after runs: nothing in imm3_query_run depends on it (graph capture and replay of aggregation runs are unaffected).  The order is
+ * applied on the device when a getter settles the groups; imm3_query_group_count, _fetch_groups, _fetch_group_strings and
+ * _fetch_group_keys then answer in that order, cut to `limit`, and copy only those groups to the host.  A run, another call of this
+ * function, or a re-collect into grown arrays invalidates the ordered view: the next getter orders again.
+ *   keys    1 .. IMM3_ORDER_MAX_KEYS entries, keys[0] most significant.  kind IMM3_GROUP_ORDER_GROUP_COL: index = a place in the
+ *           creator's group_cols; kind IMM3_GROUP_ORDER_AGG: index = a place in its aggs.  descending != 0 reverses THAT key only.
+ *           n_keys == 0 removes the order: the getters answer in first-seen order again, exactly as on a query never ordered.
+ *   limit   > 0: the first `limit` groups of the order (imm3_query_group_count = min(groups, limit)); <= 0: every group.
+ * Order: the rule of imm3_query_set_order -- lexicographic over the keys, no null semantics.  int32 / int8 group columns and MIN / MAX
+ * over such columns compare as signed integers, COUNT as an unsigned count, SUM as a signed int64, string group columns and string
+ * MAX values byte-wise unsigned over their whole width.  Groups whose keys are ALL equal stay in first-seen order (ascending first
+ * selected row; a table: the virtual row, i.e. (segment, row)) under descending keys too: the result is a pure function of the data.
+ * The keys' normalised widths -- group column: its width; COUNT 5; MIN / MAX on int32 4, on int8 1; SUM 8; string MAX: the column's
+ * width -- sum to at most IMM3_GROUP_ORDER_KEY_MAX_WIDTH bytes.
+ * imm3_comm_merge_groups* read the group tables and ignore the order.
+ * Errors (IMM3_ERR_ARG, the message names the cause): not an aggregation query, n_keys outside 0 .. 4, an unknown kind, an index out
+ * of range, the same (kind, index) twice, key bytes above 12 (a 16-byte group column cannot be a key).
+ * OUT OF SCOPE: ordering merged results (imm3_comm_merge_groups*) on the device, ordering by an average, key bytes beyond 12. ---- */
+enum { IMM3_GROUP_ORDER_GROUP_COL = 0, IMM3_GROUP_ORDER_AGG = 1 };
+typedef struct { int32_t kind; int32_t index; int32_t descending; } imm3_group_order_key;
+#define IMM3_GROUP_ORDER_KEY_MAX_WIDTH 12
+int imm3_query_set_group_order(imm3_query *q, const imm3_group_order_key *keys, int32_t n_keys, int64_t limit);
 
 /* Enqueue the whole pipeline on the context's stream.  n_proj == 0: the scan+select kernel (selection bitmap + count).
  * Unlimited projection whose SELECT list is predicate columns only (one of them an int32 column, or >= 30 % of the rows

@@ -17,7 +17,9 @@ extern "C" {
  * When enabled, every kernel launch of this context is bracketed by an event pair.
  * kernel ids: 0 = scan+select, 1 = offsets scan, 2 = compact+gather, 3 = count reduce, 4 = group-by aggregation,
  *             5 = PFOR_INT / snappy column decode, 6 = refine pass of a MAX over a string wider than 8 bytes (one per pass),
- *             7 = ORDER BY of an ordered query: ONE record per order, from its first kernel's start to its last one's end. */
+ *             7 = ORDER BY of an ordered query: ONE record per order, from its first kernel's start to its last one's end,
+ *             8 = ORDER BY over groups (imm3_query_set_group_order): ONE record per ordered settle, from the small launch's start (or
+ *                 the radix path's key launch's) to the end of the launch that writes the ordered groups. */
 int imm3_ctx_timing_enable(imm3_ctx *ctx, int32_t max_records);
 int imm3_ctx_timing_reset(imm3_ctx *ctx);
 /* Only launches whose kernel id has its bit set in `kernel_mask` are bracketed (default: all). */
@@ -55,7 +57,9 @@ int imm3_ctx_measure_read_gbps(imm3_ctx *ctx, uint64_t bytes, int32_t iters, dou
  * aggregation launch, 18 = group keys wider than 8 bytes hash to 3 bits, so that distinct keys collide by construction (tests of
  * the exactness of the key compare), 19 = a projection through survivor records stores its bitmap in the staging launch (default: the bitmap is
  * materialised when imm3_query_bitmap asks), 23 = an ordered query with a limit sorts every row (no radix select: the
- * yardstick of tests/test_gpu_zz_perf_order.py), 24 = it takes the radix select whenever the limit is below the survivors, 20 - 22 and 34 - 35 = ablation switches of k_filter_tile and k_emit (tools' build,
+ * yardstick of tests/test_gpu_zz_perf_order.py), 24 = it takes the radix select whenever the limit is below the survivors (both also
+ * pin the radix path of imm3_query_set_group_order), 25 = an ordered aggregation takes the radix path whatever its group count (no
+ * one-work-group launch: the yardstick of tests/test_gpu_zz_perf_group_order.py), 20 - 22 and 34 - 35 = ablation switches of k_filter_tile and k_emit (tools' build,
  * libimm3_ablate.so, only), 50 + mask = ablation mask of k_filter_project (tools' build), 100 + AggForm = the aggregation starts at
  * that kernel form, 140 and above = aggregation ablations (tools' build), 200 + P = fixed tiles per range.  The names of these
  * numbers are csrc/imm3_handles.h's TuningVariant. */
@@ -87,6 +91,13 @@ int imm3_query_plan(const imm3_query *q, int64_t *out, int32_t n);
  * (127 keys), 2 = direct, 3 = tile, 4 = general), after any re-run from a later form that a full per-work-group table forced; -1
  * before the first run.  IMM3_ERR_ARG for a query that is not an aggregation. */
 int imm3_query_agg_form(const imm3_query *q, int32_t *form);
+
+/* imm3_query_group_order_path: the path the last ordered settle of an aggregation took (imm3_query_set_group_order; a getter orders
+ * the groups): 0 = none (no order set, or no getter has asked since the last run or change of order), 1 = the one-work-group launch
+ * (k_group_order_small: up to 2048 groups), 2 = the radix path sorting every group, 3 = the radix path with the radix select in front
+ * (0 < limit, groups >= 4 x limit).  IMM3_ERR_ARG for a query that is not an aggregation. */
+#define IMM3_GROUP_ORDER_SMALL_MAX 2048
+int imm3_query_group_order_path(const imm3_query *q, int32_t *path);
 
 /* imm3_query_expr_form: which kernel the last select launch of a select-tree query (an IMM3_EXPR_OR or IMM3_EXPR_NOT in its program) ran: 0 = the tile
  * form (k_filter_expr), 1 = the generic form (k_filter_expr_generic); -1 before the first launch, for a tree that selects nothing
