@@ -1,5 +1,5 @@
 // imm3_handles.h -- the handle structs behind include/imm3.h, shared by the translation units of the C ABI
-// (imm3_api.cpp: creation + getters; imm3_run.cpp: the run and its launches; imm3_planner.cpp: plans; imm3_comm.cpp: the RCCL count reduce).  Private to csrc/.
+// (imm3_api.cpp: creation + getters; imm3_run.cpp: the run and its launches; imm3_planner.cpp: plans; imm3_comm.cpp: the RCCL count reduce; imm3_merge_*.cpp: the cross-rank merges).  Private to csrc/.
 #pragma once
 
 #include "../../include/imm3.h"

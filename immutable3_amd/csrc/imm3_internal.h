@@ -541,7 +541,7 @@ bool group_agg_fuses_select(const AggArgs &a); // would launch_group_agg run a f
 // ---- cross-segment / cross-GPU merge of group tables (ProjectAggregateQueueOp, ProjectAggregateQueue.scala:9-55) ----
 // Keys of <= 2 bytes index a DIRECT table (256 or 65 536 slots; one slot for no group column): every query's dense group
 // list is scattered into it with 64-bit atomics (counts add, first = min of segment << 32 | row, values max / min), and the
-// tables of the ranks then meet in element-wise all-reduces (imm3_comm.cpp).  SUM columns add (64-bit atomics, ncclSum).
+// tables of the ranks then meet in element-wise all-reduces (imm3_merge_groups.cpp).  SUM columns add (64-bit atomics, ncclSum).
 struct MergeArgs {
     const unsigned long long *keys;   // one query's dense groups (k_group_collect's output)
     const uint32_t *first;

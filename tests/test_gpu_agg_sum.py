@@ -2,8 +2,6 @@
 ProjectAggregate.scala:60-75) in every kernel form, in the merges and at the operator level.  Expectations come from numpy:
 np.unique (first-seen order) and np.add.at in int64 -- oracle_np.project_agg knows no SUM."""
 import os
-import subprocess
-import sys
 from decimal import ROUND_HALF_EVEN, Context, Decimal
 
 import numpy as np
@@ -11,6 +9,7 @@ import pytest
 
 from conftest import DENSE_INT, DENSE_STRING, DENSE_TINYINT, GT, LT, PforColumn, RawColumn, blocks_of
 from immutable3_amd import native, synth
+from loopback_util import run_worker
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -302,35 +301,16 @@ def test_sum_merge_of_segment_queries(ctx):
 
 
 LOOPBACK_WORKER = r'''
-import sys, threading
+import sys
 import numpy as np
 import torch  # noqa: F401  (its HIP runtime first: conftest.py says why)
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
 from conftest import DENSE_INT, DENSE_TINYINT, RawColumn, blocks_of
 from immutable3_amd import native
 
-WORLD = 2
-ctxs = [native.Context(0) for _ in range(WORLD)]
-uid = native.comm_unique_id()
-comms = [None] * WORLD
+from loopback_ranks import WORLD, both, start
 
-def both(fn):
-    out, err = [None] * WORLD, [None] * WORLD
-    def run(r):
-        try:
-            out[r] = fn(r)
-        except BaseException as e:      # noqa: BLE001
-            err[r] = e
-    ts = [threading.Thread(target=run, args=(r,)) for r in range(WORLD)]
-    for t in ts: t.start()
-    for t in ts: t.join(120)
-    assert not any(t.is_alive() for t in ts), "a rank is stuck in a collective"
-    return out, err
-
-def mk(r):
-    comms[r] = native.Comm(ctxs[r], WORLD, r, uid)
-out, err = both(mk)
-assert err == [None, None], err
+ctxs, comms = start()
 rng = np.random.default_rng(21)
 rows = [70_000, 50_001, 1024, 33_333]
 cols = []
@@ -377,18 +357,7 @@ print("LOOPBACK-SUM-OK", flush=True)
 
 def test_sum_merge_of_two_ranks_over_the_loopback_transport(tmp_path):
     """Two ranks (threads, one context each on device 0) through tests/native/loopback_rccl.cpp, as test_gpu_comm_loopback.py does."""
-    lib = tmp_path / "libloopback_rccl.so"
-    src = os.path.join(ROOT, "tests", "native", "loopback_rccl.cpp")
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "hip", "--offload-arch=gfx950", src, "-o", str(lib)],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    script = tmp_path / "loopback_sum_worker.py"
-    script.write_text(LOOPBACK_WORKER)
-    env = dict(os.environ, IMM3_RCCL_LIB=str(lib))
-    r = subprocess.run([sys.executable, str(script), ROOT], env=env, capture_output=True, text=True, timeout=900)
-    sys.stdout.write(r.stdout[-4000:])
-    sys.stderr.write(r.stderr[-4000:])
-    assert r.returncode == 0 and "LOOPBACK-SUM-OK" in r.stdout
+    run_worker(tmp_path, "loopback_sum_worker.py", LOOPBACK_WORKER, "LOOPBACK-SUM-OK")
 
 
 # ---- graph capture ---------------------------------------------------------------------------------------------------------

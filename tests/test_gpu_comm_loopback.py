@@ -1,4 +1,5 @@
-"""GPU suite: the WORLD > 1 paths of the communicator (csrc/imm3_comm.cpp) with two ranks -- the count all-reduce
+"""GPU suite: the WORLD > 1 paths of the communicator (csrc/imm3_comm.cpp, csrc/imm3_merge_groups.cpp over the protocol of
+csrc/imm3_merge_protocol.cpp) with two ranks -- the count all-reduce
 (Engine.scala:190-196: the per-segment pipelines' counts meet in one place) and the cross-rank group merge
 (ProjectAggregateQueueOp, ProjectAggregateQueue.scala:9-55): the 5-word shape / error exchange, the list-length flag, the
 allocation flag, ncclAllGather of the packed lists, the second hash table, and "every rank takes the same exit" when ONE rank
@@ -9,18 +10,14 @@ ever run with one rank.  The ranks of this test are two THREADS of one process, 
 nine nccl* entry points the library binds at run time come from tests/native/loopback_rccl.cpp (IMM3_RCCL_LIB): a transport
 that meets at a barrier and reduces through host memory.  It is the library's protocol that is under test, not RCCL; the real
 RCCL runs in the one-rank tests (test_gpu_lifetime.py, test_gpu_agg.py) and in the driver's multi-GPU bench."""
-import os
-import subprocess
-import sys
-
 import pytest
 
+from loopback_util import run_worker
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "native", "loopback_rccl.cpp")
 
 WORKER = r'''
-import sys, threading
+import sys
 import numpy as np
 import torch  # noqa: F401  (its HIP runtime first: conftest.py says why)
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
@@ -28,29 +25,9 @@ from conftest import DENSE_INT, DENSE_TINYINT, GT, LT, RawColumn, blocks_of
 from immutable3_amd import native
 from oracle import oracle_np
 
-WORLD = 2
-ctxs = [native.Context(0) for _ in range(WORLD)]
-uid = native.comm_unique_id()
-comms = [None] * WORLD
+from loopback_ranks import WORLD, both, start
 
-def both(fn):
-    """Run fn(rank) on two threads (the two ranks); returns their results, re-raises what they raised."""
-    out, err = [None] * WORLD, [None] * WORLD
-    def run(r):
-        try:
-            out[r] = fn(r)
-        except BaseException as e:      # noqa: BLE001
-            err[r] = e
-    ts = [threading.Thread(target=run, args=(r,)) for r in range(WORLD)]
-    for t in ts: t.start()
-    for t in ts: t.join(120)
-    assert not any(t.is_alive() for t in ts), "a rank is stuck in a collective: the ranks did not take the same exit"
-    return out, err
-
-def mk(r):
-    comms[r] = native.Comm(ctxs[r], WORLD, r, uid)
-out, err = both(mk)
-assert err == [None, None], err
+ctxs, comms = start()
 
 # ---- data: four segments, segment s on rank s mod 2 (the partition of Engine.scala:176-180 over two GPUs)
 rng = np.random.default_rng(11)
@@ -139,14 +116,4 @@ print("LOOPBACK-OK", flush=True)
 
 
 def test_two_ranks_merge_and_count_over_the_loopback_transport(tmp_path):
-    lib = tmp_path / "libloopback_rccl.so"
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "hip", "--offload-arch=gfx950", SRC, "-o", str(lib)],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    script = tmp_path / "loopback_worker.py"
-    script.write_text(WORKER)
-    env = dict(os.environ, IMM3_RCCL_LIB=str(lib))
-    r = subprocess.run([sys.executable, str(script), ROOT], env=env, capture_output=True, text=True, timeout=900)
-    sys.stdout.write(r.stdout[-4000:])
-    sys.stderr.write(r.stderr[-4000:])
-    assert r.returncode == 0 and "LOOPBACK-OK" in r.stdout
+    run_worker(tmp_path, "loopback_worker.py", WORKER, "LOOPBACK-OK")

@@ -3,18 +3,14 @@ and the rank kernel over them -- over the loopback transport of test_gpu_comm_lo
 threads of one process as the ranks, IMM3_RCCL_LIB).  Six segments, segment s on rank s mod 2: interleaved global indices, so the
 concatenation of the ranks' lists is not the order.  Every rank must receive order_util.expected_table's rows bit for bit, and every
 rank must come back when one of them fails before the first collective."""
-import os
-import subprocess
-import sys
-
 import pytest
 
+from loopback_util import run_worker
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "native", "loopback_rccl.cpp")
 
 WORKER = r'''
-import sys, threading
+import sys
 import numpy as np
 import torch  # noqa: F401  (its HIP runtime first: conftest.py says why)
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
@@ -23,29 +19,9 @@ from immutable3_amd import native
 import merge_order_util as U
 from merge_order_util import AGE, ID, TAG
 
-WORLD = 2
-ctxs = [native.Context(0) for _ in range(WORLD)]
-uid = native.comm_unique_id()
-comms = [None] * WORLD
+from loopback_ranks import WORLD, both, start
 
-def both(fn):
-    """Run fn(rank) on two threads (the two ranks); returns their results and what they raised."""
-    out, err = [None] * WORLD, [None] * WORLD
-    def run(r):
-        try:
-            out[r] = fn(r)
-        except BaseException as e:      # noqa: BLE001
-            err[r] = e
-    ts = [threading.Thread(target=run, args=(r,)) for r in range(WORLD)]
-    for t in ts: t.start()
-    for t in ts: t.join(120)
-    assert not any(t.is_alive() for t in ts), "a rank is stuck in a collective: the ranks did not take the same exit"
-    return out, err
-
-def mk(r):
-    comms[r] = native.Comm(ctxs[r], WORLD, r, uid)
-out, err = both(mk)
-assert err == [None, None], err
+ctxs, comms = start()
 
 # ---- six segments, segment s on rank s mod 2; ids below 3 and three ages: whole (age, id) keys tie inside and across segments
 rng = np.random.default_rng(31)
@@ -129,14 +105,4 @@ print("LOOPBACK-ORDERED-OK", flush=True)
 
 
 def test_two_ranks_merge_ordered_over_the_loopback_transport(tmp_path):
-    lib = tmp_path / "libloopback_rccl.so"
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "hip", "--offload-arch=gfx950", SRC, "-o", str(lib)],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    script = tmp_path / "loopback_ordered_worker.py"
-    script.write_text(WORKER)
-    env = dict(os.environ, IMM3_RCCL_LIB=str(lib))
-    r = subprocess.run([sys.executable, str(script), ROOT], env=env, capture_output=True, text=True, timeout=900)
-    sys.stdout.write(r.stdout[-4000:])
-    sys.stderr.write(r.stderr[-4000:])
-    assert r.returncode == 0 and "LOOPBACK-ORDERED-OK" in r.stdout
+    run_worker(tmp_path, "loopback_ordered_worker.py", WORKER, "LOOPBACK-ORDERED-OK")
