@@ -195,6 +195,10 @@ extern "C" int imm3_ctx_capture_end(imm3_ctx *ctx, imm3_graph **out) {
     if (!ctx->gate.owned_by_me() || !ctx->capture) return fail(IMM3_ERR_STATE, "no capture is open on this context (begin and end belong to one thread)");
     imm3_graph *g = ctx->capture;
     ctx->capture = nullptr;
+    // The recorded runs set the run record of their queries as if they had executed (the plan functions do; capture_note kept a copy
+    // for the replays).  Nothing has executed: every query gets back the record it came with, whether the recording succeeded, was
+    // refused half way or fails below -- a getter between here and the first launch answers for the last run that executed.
+    for (size_t i = 0; i < g->queries.size() && i < g->live.size(); ++i) g->queries[i]->run = g->live[i];
     hipError_t e = hipSetDevice(ctx->device);
     if (e == hipSuccess) e = hipStreamEndCapture(ctx->stream, &g->graph);
     if (e == hipSuccess) e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
@@ -227,9 +231,16 @@ extern "C" int imm3_graph_launch(imm3_graph *g) {
     // A replay is the recorded runs again: every recorded query gets back the run record it had after its recorded run (a getter of a
     // single-pass run then reads THIS replay's status word -- round 3 left `sp_verified` set by an earlier getter, or
     // `ran_single_pass` cleared by an earlier fallback, and a busy or abandoned replay went unnoticed).
+    // Two flags describe the groups, not the recorded run, when that run was a select only: the groups an executed imm3_query_run left stay
+    // readable behind a replayed imm3_query_run_select (the record of a recording made before that run says "no aggregation"), and an
+    // ordered view is valid only if it was when recorded AND is now (imm3_query_set_group_order may have changed the order since).
     for (size_t i = 0; i < g->queries.size() && i < g->states.size(); ++i) {
-        g->queries[i]->run = g->states[i];
-        g->queries[i]->run.sp_verified = false;
+        imm3_query *q = g->queries[i];
+        const QueryRunState before = q->run;
+        q->run = g->states[i];
+        q->run.sp_verified = false;
+        q->run.ran_agg = q->run.ran_agg || before.ran_agg;
+        q->run.group_order_valid = q->run.group_order_valid && before.group_order_valid;
     }
     return IMM3_OK;
 }
@@ -867,6 +878,7 @@ int imm3::ensure_row_capacity(imm3_query *q, uint64_t rows) {
     if (rows < 1) rows = 1;
     imm3_ctx *ctx = q->ctx;
     if (q->d_row_index) graphs_mark_stale(ctx, q); // a recorded run would write through the old pointers (launch: IMM3_ERR_STATE)
+    if (q->d_row_index && q->run.ran_project) q->run.rows_moved = true; // (the last run's rows went with the old arrays: settle_rows emits them again)
     pool_release(ctx, q->d_row_index); // stream-ordered: a gather still in flight finishes before any reuse
     q->d_row_index = nullptr;
     for (auto &p : q->d_proj) {
@@ -904,6 +916,7 @@ int imm3::ensure_order_buffers(imm3_query *q) {
         q->d_order_tally = (uint32_t *)p;
     }
     if (q->order_cap_rows == q->cap_rows && q->d_order_row_index) return IMM3_OK;
+    q->run.order_valid = false; // (the ordered arrays are allocated anew)
     const uint64_t rows = q->cap_rows;
     const uint64_t key_words = (uint64_t)(q->order_key_bytes + 3) / 4;
     for (int b = 0; b < 2; ++b) {
@@ -1865,11 +1878,15 @@ static int settle_rows(imm3_query *q, uint64_t *rows) {
         HIPCHK(hipMemcpyAsync(&emit, q->d_n_emit, sizeof(emit), hipMemcpyDeviceToHost, q->ctx->stream));
         HIPCHK(hipStreamSynchronize(q->ctx->stream));
     }
-    if (emit > q->cap_rows) {
+    if (emit > q->cap_rows || q->run.rows_moved) {
         // the reservation was too small: grow and gather again (offsets are still valid; a single-pass run made none:
-        // they come from the bitmap now)
-        int rc = ensure_row_capacity(q, q->reserved ? emit : std::min<unsigned long long>((unsigned long long)std::max<int64_t>(q->n_rows, 1), emit + emit / 8 + 1024));
+        // they come from the bitmap now) -- or a reservation behind the run moved the arrays: the rows are gathered into the new ones
+        int rc = emit > q->cap_rows ? ensure_row_capacity(q, q->reserved ? emit : std::min<unsigned long long>((unsigned long long)std::max<int64_t>(q->n_rows, 1), emit + emit / 8 + 1024)) : IMM3_OK;
         if (rc) return rc;
+        if (!q->run.stage_written) rc = settle_lazy_bitmap(q); // (records that the reservation's plan change released: the bitmap they stood for)
+        if (rc) return rc;
+        q->run.rows_moved = false;
+        q->run.limit_gather_ran = false;
         rc = scan_offsets(q); // (a single-pass run made no offsets: they come from the bitmap now)
         if (rc) return rc;
         rc = launch_project(q); // (from the records when the run staged them, from the bitmap otherwise)
@@ -2236,8 +2253,14 @@ static int settle_groups(imm3_query *q, uint32_t *n_groups) {
             // lanes (63 keys) -> lanes (127 keys) -> direct -> general
             q->agg_first_form = meta[1] == 3 ? (q->agg_first_form == AGG_FORM_LANES ? AGG_FORM_LANES_WIDE : AGG_FORM_DIRECT) : AGG_FORM_GENERAL;
             g.first_form = q->agg_first_form;
-            {   // (the forms behind the 63-key lanes form read the bitmap: a run that fused the select has none yet)
-                const int arc = settle_agg_select(q);
+            {   // (the forms behind the 63-key lanes form read the bitmap: a run that fused the select has none yet -- and a count-only
+                // run since then has stored none either: the chain runs for this launch, and imm3_query_bitmap goes on refusing)
+                int arc = settle_agg_select(q);
+                if (!arc && !q->run.bitmap_valid) {
+                    if (q->ctx->capture) return fail(IMM3_ERR_STATE, "a graph capture is open on this context");
+                    arc = run_select(q, SEL_DEFAULT);
+                    q->run.bitmap_valid = false;
+                }
                 if (arc) return arc;
                 g.n_fused = 0;
                 g.fused_all = 0;

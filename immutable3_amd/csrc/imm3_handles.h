@@ -146,6 +146,7 @@ struct QueryRunState {
     bool ran_single_pass = false;    // the last run went through k_filter_project ...
     bool sp_verified = false;        // ... and its status word has been read since (rows complete, or gathered again from the bitmap)
     bool group_order_valid = false;  // an ordered aggregation (imm3_query_set_group_order): the ordered group arrays hold the order of the last run's groups (a run clears it: run_agg)
+    bool rows_moved = false;         // the row arrays were allocated anew behind the last projection (imm3_query_reserve_rows): settle_rows emits its rows again
     bool order_valid = false;        // an ordered query (imm3_query_set_order): the ordered arrays hold the order of the rows as last emitted (every re-emit clears it: launch_project)
 };
 
@@ -156,6 +157,8 @@ struct imm3_graph {
     hipGraphExec_t exec = nullptr;
     std::vector<imm3_query *> queries;    // the queries whose runs were recorded (not retained: destroying one makes the graph stale)
     std::vector<QueryRunState> states;    // per query: its run state after the recorded run
+    std::vector<QueryRunState> live;      // per query: its run state when the capture first admitted it -- nothing executes during a capture, so
+                                          // imm3_ctx_capture_end puts it back: until a launch the handle describes the last run that EXECUTED
     bool stale = false;
 };
 

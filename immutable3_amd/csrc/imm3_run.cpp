@@ -488,6 +488,7 @@ int imm3::run_select(imm3_query *q, unsigned mode) {
     }
     q->run.offsets_valid = false; // (a new bitmap)
     q->run.select_partial = false;
+    q->run.agg_select_skipped = false; // (... and a new count: a fused aggregation's select is no longer owed -- behind imm3_query_run_count imm3_query_bitmap refuses, it does not run the chain)
     if (q->always_false || q->n_tiles == 0) {
         // an empty interval / empty IN-list clears every bit; nothing to read
         HIPCHK(hipMemsetAsync(q->d_total, 0, 2 * sizeof(unsigned long long), run.s)); // (an always-false query logs nothing)
@@ -1056,6 +1057,7 @@ static int capture_admit(imm3_query *q) {
     if (std::find(qs.begin(), qs.end(), q) == qs.end()) {
         qs.push_back(q);
         ctx->capture->states.emplace_back();
+        ctx->capture->live.push_back(q->run);
     }
     return IMM3_OK;
 }
@@ -1079,6 +1081,7 @@ static int run_entry(imm3_query *q, int (*plan)(imm3_query *)) {
     const int ca = capture_admit(q);
     if (ca) return ca;
     q->run.ran_project = false;
+    q->run.rows_moved = false;
     return capture_note(q, plan(q));
 }
 

@@ -153,7 +153,15 @@ int imm3_ctx_stream(imm3_ctx *ctx, void **stream_out);
  * Between begin and end the context accepts only imm3_query_run / imm3_query_run_select (nothing executes then: the
  * runs are recorded) -- every other call returns IMM3_ERR_STATE.  A recorded run must not need the host: an unlimited
  * projection has to have rows reserved (imm3_query_reserve_rows), and every recorded query must have run once before (its
- * buffers are allocated on first use).  Destroying a recorded query makes the graph stale (launch: IMM3_ERR_STATE). */
+ * buffers are allocated on first use).  A PROJECTING query is recorded -- whichever of the two calls -- only once its row arrays
+ * exist: after an executed imm3_query_run or a reservation (a query created with a limit has them from creation).  A run that is
+ * refused inside a capture leaves its query as it was; imm3_ctx_capture_end then closes the capture as after any other.
+ * Between imm3_ctx_capture_end and the first imm3_graph_launch a recorded query describes THE LAST RUN THAT EXECUTED, exactly as if
+ * nothing had been recorded: its getters answer for that run (IMM3_ERR_STATE where none has executed).  Every launch then leaves
+ * the query as the recorded run would: the getters answer for the recorded run, whatever runs or getters came in between -- except
+ * that the groups of an aggregation stay readable behind a replayed imm3_query_run_select once any imm3_query_run has executed.
+ * Destroying a recorded query makes the graph stale (launch: IMM3_ERR_STATE, the queries stay as they were); so does anything that
+ * moves a recorded query's buffers: imm3_query_reserve_rows, row arrays that a getter had to grow. */
 int imm3_ctx_capture_begin(imm3_ctx *ctx);
 int imm3_ctx_capture_end(imm3_ctx *ctx, imm3_graph **out);
 int imm3_graph_launch(imm3_graph *g);
@@ -395,7 +403,9 @@ int imm3_query_fetch_group_keys(imm3_query *q, uint8_t *out, uint32_t max_groups
  * unlimited projection sizes them once: a query whose SELECT list is predicate columns only (it runs as ONE launch that
  * writes the rows itself) gets room for every row of the segment; any other one synchronises on its first run to read the
  * count and keeps the arrays (with an eighth of headroom) for every later run -- a steady-state projecting query never
- * synchronises.  A run that outgrows the arrays, reserved or not, is detected when its rows are fetched and emitted again. */
+ * synchronises.  A run that outgrows the arrays, reserved or not, is detected when its rows are fetched and emitted again.
+ * Called BEHIND a run, the call may move the arrays; the rows of that run stay readable (imm3_query_row_count / _fetch_rows emit
+ * them again into the new arrays), device pointers 2 and 16+j fetched before the call are void. */
 int imm3_query_reserve_rows(imm3_query *q, uint64_t rows);
 
 /* ---- ORDER BY: the "sort" core/Query.scala:27 announces above ProjectADT ("// add sort") and the reference does not have.
@@ -467,7 +477,9 @@ int imm3_query_run_select(imm3_query *q);
 /* ScanOp -> SelectOp* for the count alone: `vec.selected.size` summed over the batches (what a count(*)-style consumer of
  * the pipeline reads, Engine.scala:190-196) without materialising the BitSets.  A select chain that is one fused launch then
  * stores no bitmap at all -- on a narrow column the 1/8 byte per row of bitmap is a fifth of the kernel -- and
- * imm3_query_bitmap fails with IMM3_ERR_STATE until the next full run; any other chain runs as imm3_query_run_select. */
+ * imm3_query_bitmap fails with IMM3_ERR_STATE until the next full run (of any query: also of an aggregation whose last
+ * imm3_query_run fused its select, and behind a projection); any other chain runs as imm3_query_run_select.  "Full run" is
+ * imm3_query_run, imm3_query_run_select or a launch of a graph that recorded either. */
 int imm3_query_run_count(imm3_query *q);
 int imm3_query_sync(imm3_query *q);
 /* The selected-row count of a select-only run is reduced on the context's auxiliary stream so that it overlaps the
