@@ -607,7 +607,12 @@ int imm3_comm_merge_groups_all(imm3_comm *const *comms, int32_t n_comms, imm3_qu
  * lists are exchanged with ncclAllGather and merged again.
  *   key_bytes_out[g * key_bytes ..) the whole packed key as imm3_query_fetch_group_keys lays it out (key_bytes from
  *                                   imm3_query_agg_shape; a key of <= 8 bytes: the u64 key little-endian)
- *   first[g]                        segment << 32 | first selected row of the group there
+ *   first[g]                        segment << 32 | first selected row of the group there.  A query over a TABLE brings ONE
+ *                                   segment_index entry for the whole table, and a group it brings carries that index << 32 | the
+ *                                   group's first VIRTUAL row of the table (tile * 1024 + position, what imm3_query_fetch_groups
+ *                                   gives; imm3_query_locate_rows on that query maps it to (segment, row)): the table's groups
+ *                                   keep their (segment, row) order among themselves and sort against other queries' groups by
+ *                                   the table's one index
  *   counts[g], vals[g * n_aggs + j] as imm3_query_fetch_groups (a string MAX wider than 8 bytes: its first 8 bytes big-endian)
  *   str_out                         NULL, or n_aggs pointers: str_out[j] receives `width` bytes per group when aggregate j is a MAX
  *                                   over a STRING column (any width) and must be NULL for every other aggregate
