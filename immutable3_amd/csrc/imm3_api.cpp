@@ -2306,7 +2306,7 @@ extern "C" int imm3_query_agg_shape(const imm3_query *q, int32_t *n_group_cols, 
 
 extern "C" int imm3_query_group_count(imm3_query *q, uint32_t *n_groups) {
     if (!q || !n_groups) return fail(IMM3_ERR_ARG, "null argument");
-    if (q->group_ordered) { // (imm3_query_set_group_order: min(groups, limit))
+    if (q->group_ordered || q->group_filtered) { // (imm3_query_set_group_order: min(groups, limit))
         CTX_LIVE(q->ctx);
         return group_order_settle(q, n_groups);
     }
@@ -2335,7 +2335,7 @@ static int gather_group_keys(imm3_query *q, uint32_t n, std::vector<uint8_t> &ou
 extern "C" int imm3_query_fetch_groups(imm3_query *q, uint64_t *keys, uint32_t *first_row, uint64_t *counts, int64_t *vals, uint32_t max_groups) {
     if (!q) return fail(IMM3_ERR_ARG, "query is null");
     CTX_LIVE(q->ctx);
-    if (q->group_ordered) return group_order_fetch_groups(q, keys, first_row, counts, vals, max_groups); // (ordered on the device: only the groups asked for are copied)
+    if (q->group_ordered || q->group_filtered) return group_order_fetch_groups(q, keys, first_row, counts, vals, max_groups); // (ordered on the device: only the groups asked for are copied)
     uint32_t n = 0;
     const int rc = settle_groups(q, &n);
     if (rc) return rc;
@@ -2384,7 +2384,7 @@ extern "C" int imm3_query_fetch_group_strings(imm3_query *q, int32_t agg, uint8_
     if (q->aggs[(size_t)agg].kind != IMM3_AGG_MAX || sc.vcodec != IMM3_DENSE_STRING) return fail(IMM3_ERR_ARG, "the aggregate is not a MAX over a STRING column");
     if (!out && max_groups > 0) return fail(IMM3_ERR_ARG, "out is null");
     CTX_LIVE(q->ctx);
-    if (q->group_ordered) return group_order_fetch_strings(q, agg, out, max_groups);
+    if (q->group_ordered || q->group_filtered) return group_order_fetch_strings(q, agg, out, max_groups);
     uint32_t n = 0;
     const int rc = settle_groups(q, &n);
     if (rc) return rc;
@@ -2430,7 +2430,7 @@ extern "C" int imm3_query_fetch_group_keys(imm3_query *q, uint8_t *out, uint32_t
     if (!q->is_agg) return fail(IMM3_ERR_ARG, "not an aggregation query");
     if (!out && max_groups > 0) return fail(IMM3_ERR_ARG, "out is null");
     CTX_LIVE(q->ctx);
-    if (q->group_ordered) return group_order_fetch_keys(q, out, max_groups);
+    if (q->group_ordered || q->group_filtered) return group_order_fetch_keys(q, out, max_groups);
     uint32_t n = 0;
     const int rc = settle_groups(q, &n);
     if (rc) return rc;

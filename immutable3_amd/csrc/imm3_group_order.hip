@@ -11,6 +11,10 @@
 //   k_group_order_keys    larger n: the key as one byte-string column of 5 .. 16 bytes per group plus the group count as the 64-bit word
 //                         the launches of imm3_order.hip read; those then sort (or select and sort) it as ONE KIND_STR key, unchanged;
 //   k_group_order_apply   ... and the dense arrays are gathered through the final permutation.
+//
+// HAVING (imm3_query_set_group_filter; "Filtering groups" in the same section): each of the three has a FILTERED instance that takes the
+// checked program (imm3_group_filter_plan.h) as a second argument and runs group_filter_eval on a group as it loads it -- the view is
+// filter, then order, then limit, in the same launches.  A query without a filter launches the instances above, unchanged.
 #include "imm3_internal.h"
 
 #include <hip/hip_runtime.h>
@@ -121,18 +125,38 @@ __device__ inline bool go_less(const GoElem &x, const GoElem &y, uint32_t n) {
 // ds_write_b32 (bank = dword address % 32, conflicts counted per 32-lane half): in the steps at distance >= 64 the 32 lanes of a half
 // hold 32 consecutive elements -- 32 distinct banks, no conflict.  The steps at distance < 64 never touch LDS: a wave keeps its 64
 // consecutive elements in registers and exchanges them with its own lanes.
-__global__ __launch_bounds__(kGroupOrderSmallThreads) void k_group_order_small(const GroupOrderArgs a) {
+//
+// FILT (imm3_query_set_group_filter): the program runs when group e is loaded.  A dropped group becomes a pad -- index P + e, unique and
+// above every group's and every natural pad's -- so the network, go_less and the gather stay as they are; the kept groups are counted
+// in LDS (a wave ballot, one ds_add per wave) and the launch writes {min(kept, n_out), kept}.  P is whole waves, so every wave runs the
+// load loop as one and the ballot sees all of its lanes.
+template <bool FILT>
+__device__ __forceinline__ void go_small_body(const GroupOrderArgs &a, const GroupFilterArgs *f) {
     __shared__ uint32_t s_k[kOrderKeyWords][kGroupOrderSmall];
     __shared__ uint32_t s_i[kGroupOrderSmall];
+    __shared__ uint32_t s_kept;
     const uint32_t t = threadIdx.x, n = a.n < (uint32_t)kGroupOrderSmall ? a.n : (uint32_t)kGroupOrderSmall;
     uint32_t P = 64;
     while (P < n) P <<= 1;
+    if constexpr (FILT) {
+        if (t == 0) s_kept = 0u;
+        __syncthreads();
+    }
     for (uint32_t e = t; e < P; e += kGroupOrderSmallThreads) {
         uint32_t k[kOrderKeyWords] = {0u, 0u, 0u, 0u};
-        if (e < n) go_build_key(a, e, k);
+        uint32_t idx = e;
+        if constexpr (FILT) {
+            const bool keep = e < n && group_filter_eval(f->prog, a.src_counts[e], a.src_vals + (size_t)e * kMaxAggs);
+            const unsigned long long m = __ballot(keep);
+            if ((t & 63u) == 0u && m) atomicAdd(&s_kept, (uint32_t)__popcll(m));
+            if (keep) go_build_key(a, e, k);
+            else if (e < n) idx = P + e;
+        } else {
+            if (e < n) go_build_key(a, e, k);
+        }
 #pragma unroll
         for (int w = 0; w < kOrderKeyWords; ++w) s_k[w][e] = k[w];
-        s_i[e] = e;
+        s_i[e] = idx;
     }
     __syncthreads();
     for (uint32_t k = 2; k <= P; k <<= 1) {
@@ -181,27 +205,61 @@ __global__ __launch_bounds__(kGroupOrderSmallThreads) void k_group_order_small(c
         }
         __syncthreads();
     }
-    const uint32_t n_out = a.n_out < n ? a.n_out : n;
+    uint32_t kept = n;
+    if constexpr (FILT) kept = s_kept;
+    const uint32_t n_out = a.n_out < kept ? a.n_out : kept;
     for (uint32_t i = t; i < n_out; i += kGroupOrderSmallThreads) {
         const uint32_t g = s_i[i];
         if (g < n) go_gather(a, i, g); // (always: the groups sort in front of the pads)
     }
-    if (t == 0) *a.dst_n = n_out;
+    if (t == 0) {
+        a.dst_n[0] = n_out;
+        if constexpr (FILT) a.dst_n[1] = kept;
+    }
+}
+__global__ __launch_bounds__(kGroupOrderSmallThreads) void k_group_order_small(const GroupOrderArgs a) { go_small_body<false>(a, nullptr); }
+__global__ __launch_bounds__(kGroupOrderSmallThreads) void k_group_order_small_filtered(const GroupOrderArgs a, const GroupFilterArgs f) {
+    go_small_body<true>(a, &f);
 }
 
-__global__ __launch_bounds__(kBlockThreads) void k_group_order_keys(const GroupOrderArgs a) {
+// the key of dense group g as row `row` of the key column
+__device__ inline void go_store_key(const GroupOrderArgs &a, uint32_t g, uint32_t row) {
     const int kb = a.layout.key_bytes;
-    for (uint32_t g = blockIdx.x * kBlockThreads + threadIdx.x; g < a.n; g += gridDim.x * kBlockThreads) {
-        uint32_t k[kOrderKeyWords];
-        go_build_key(a, g, k);
-        uint8_t *dst = a.key_col + (size_t)g * (size_t)kb;
-        for (int b = 0; b < kb; ++b) {
-            const int w = b >> 2;
-            const uint32_t word = w == 0 ? k[0] : (w == 1 ? k[1] : (w == 2 ? k[2] : k[3]));
-            dst[b] = (uint8_t)(word >> ((3 - (b & 3)) * 8));
+    uint32_t k[kOrderKeyWords];
+    go_build_key(a, g, k);
+    uint8_t *dst = a.key_col + (size_t)row * (size_t)kb;
+    for (int b = 0; b < kb; ++b) {
+        const int w = b >> 2;
+        const uint32_t word = w == 0 ? k[0] : (w == 1 ? k[1] : (w == 2 ? k[2] : k[3]));
+        dst[b] = (uint8_t)(word >> ((3 - (b & 3)) * 8));
+    }
+}
+__global__ __launch_bounds__(kBlockThreads) void k_group_order_keys(const GroupOrderArgs a) {
+    for (uint32_t g = blockIdx.x * kBlockThreads + threadIdx.x; g < a.n; g += gridDim.x * kBlockThreads) go_store_key(a, g, g);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.n_word = a.n;
+}
+// FILTERED: the keys of the groups the program keeps, compacted, and map[kept position] = dense index.  A wave claims its rows with
+// ONE atomic add on n_word (zeroed on the stream before the launch; the kept count once the launch is over) and places them by the
+// ballot's prefix.  The compaction is not stable -- first_row is part of every key, so the sort gives the same bytes whatever the
+// order of its input.  The loop's bound is the same for a whole work-group: every lane of a wave is in the ballot.  No work-group
+// waits on another.
+__global__ __launch_bounds__(kBlockThreads) void k_group_order_keys_filtered(const GroupOrderArgs a, const GroupFilterArgs f) {
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t base = blockIdx.x * kBlockThreads; base < a.n; base += gridDim.x * kBlockThreads) {
+        const uint32_t g = base + threadIdx.x;
+        const bool keep = g < a.n && group_filter_eval(f.prog, a.src_counts[g], a.src_vals + (size_t)g * kMaxAggs);
+        const unsigned long long m = __ballot(keep);
+        uint32_t first = 0;
+        if (lane == 0u && m) first = (uint32_t)atomicAdd(a.n_word, (unsigned long long)__popcll(m));
+        first = (uint32_t)__shfl((int)first, 0, 64);
+        if (keep) {
+            const uint32_t row = first + (uint32_t)__popcll(m & ((1ULL << lane) - 1ULL));
+            if (row < a.n) { // (always: no more rows are claimed than groups evaluated)
+                go_store_key(a, g, row);
+                f.map[row] = g;
+            }
         }
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) *a.n_word = a.n;
 }
 
 // the ordered groups through the order's final permutation (k_order_apply's reading of the order's state words)
@@ -213,6 +271,21 @@ __global__ __launch_bounds__(kBlockThreads) void k_group_order_apply(const Group
     for (uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x; i < n_out; i += gridDim.x * kBlockThreads) {
         const uint32_t g = perm[i];
         if (g < n) go_gather(a, i, g); // (always: the permutation holds dense indices)
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.dst_n = n_out;
+}
+// FILTERED: the permutation holds kept positions (st[OW_N] = the kept count); map turns them into dense indices.  dst_n[1] is n_word,
+// which holds the kept count already.
+__global__ __launch_bounds__(kBlockThreads) void k_group_order_apply_filtered(const GroupOrderArgs a, const GroupFilterArgs f) {
+    const uint32_t *st = a.state;
+    const uint32_t kept = st[OW_N] < a.n ? st[OW_N] : a.n;
+    const uint32_t n_out = st[OW_N_OUT] < a.n_out ? st[OW_N_OUT] : a.n_out;
+    const uint32_t *perm = a.perm[(st[OW_SELECT] + (uint32_t)__popc(st[OW_ACTIVE])) & 1u];
+    for (uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x; i < n_out; i += gridDim.x * kBlockThreads) {
+        const uint32_t p = perm[i];
+        if (p >= kept) continue; // (never: the permutation holds kept positions)
+        const uint32_t g = f.map[p];
+        if (g < a.n) go_gather(a, i, g);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *a.dst_n = n_out;
 }
@@ -229,6 +302,16 @@ void launch_group_order_keys(const GroupOrderArgs &a, hipStream_t s, hipEvent_t 
 }
 void launch_group_order_apply(const GroupOrderArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     IMM3_LAUNCH(k_group_order_apply, go_grid(a.n_out), kBlockThreads, s, ev0, ev1, a);
+}
+
+void launch_group_order_small_filtered(const GroupOrderArgs &a, const GroupFilterArgs &f, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    IMM3_LAUNCH(k_group_order_small_filtered, 1, kGroupOrderSmallThreads, s, ev0, ev1, a, f);
+}
+void launch_group_order_keys_filtered(const GroupOrderArgs &a, const GroupFilterArgs &f, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    IMM3_LAUNCH(k_group_order_keys_filtered, go_grid(a.n), kBlockThreads, s, ev0, ev1, a, f);
+}
+void launch_group_order_apply_filtered(const GroupOrderArgs &a, const GroupFilterArgs &f, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    IMM3_LAUNCH(k_group_order_apply_filtered, go_grid(a.n_out), kBlockThreads, s, ev0, ev1, a, f);
 }
 
 } // namespace imm3

@@ -1,7 +1,8 @@
 // imm3_group_order_api.cpp -- imm3_query_set_group_order (include/imm3.h): the ordered view of an aggregation's groups.  The order is
 // no part of a run: a getter settles the groups as always (imm3_api.cpp: settle_groups), then this file orders the dense arrays on the
 // device into arrays of their own (imm3_group_order.hip) and the getters copy the first min(groups, limit) of those to the host.  The
-// argument checks and the key layout are imm3_group_order_plan.cpp's.
+// argument checks and the key layout are imm3_group_order_plan.cpp's.  imm3_query_set_group_filter (HAVING) lives here too: the view is
+// filter, then order, then limit, built by the same settle; the program's checks are imm3_group_filter_plan.cpp's.
 #include "imm3_api_internal.h"
 #include "../../include/imm3_diag.h"
 
@@ -81,6 +82,7 @@ int go_ensure(imm3_query *q, bool radix) {
         GO_ALLOC(q->d_go_tally, uint32_t *, (size_t)kOrderWaves * 2 * sizeof(uint32_t));
         q->go_radix_bufs = true;
     }
+    if (radix && q->group_filtered && !q->gf.map) GO_ALLOC(q->gf.map, uint32_t *, (size_t)cap * sizeof(uint32_t));
     return IMM3_OK;
 }
 
@@ -94,11 +96,13 @@ void imm3::group_order_release(imm3_query *q) {
     q->d_go_state = q->d_go_counts = q->d_go_diff = q->d_go_tally = nullptr;
     q->go_cap = 0;
     q->go_radix_bufs = false;
+    q->gf.map = nullptr;
     q->run.group_order_valid = false;
 }
 
-// The ordered view is complete in q->go.dst_*: *n_groups = min(groups, limit).  Settles the groups first; the dense arrays (and what
-// imm3_comm_merge_groups* read) stay as they are.
+// The view is complete in q->go.dst_*: filter (imm3_query_set_group_filter), then order, then limit -- *n_groups = min(groups kept,
+// limit).  Settles the groups first; the dense arrays (and what imm3_comm_merge_groups* read) stay as they are.  A filter without an
+// order takes the same two paths with first_row as the whole key: first-seen order comes from the device.
 int imm3::group_order_settle(imm3_query *q, uint32_t *n_groups) {
     if (q->run.group_order_valid && q->run.ran_agg) {
         *n_groups = q->go_n_out;
@@ -119,9 +123,11 @@ int imm3::group_order_settle(imm3_query *q, uint32_t *n_groups) {
     AggArgs aa;
     query_agg_args(q, aa);
     GroupOrderArgs &a = q->go;
-    a.layout = q->group_order_layout;
+    const bool filt = q->group_filtered;
+    const int64_t limit = q->group_ordered ? q->group_order_limit : 0; // (the limit belongs to the order)
+    a.layout = q->group_ordered ? q->group_order_layout : group_filter_first_seen_layout();
     a.n = n;
-    a.n_out = q->group_order_limit > 0 && (uint64_t)q->group_order_limit < (uint64_t)n ? (uint32_t)q->group_order_limit : n;
+    a.n_out = limit > 0 && (uint64_t)limit < (uint64_t)n ? (uint32_t)limit : n;
     a.n_agg = (int32_t)q->aggs.size();
     a.key_bytes = packed_key_bytes(q);
     a.wide_key = q->agg_wide_key ? 1 : 0;
@@ -138,14 +144,19 @@ int imm3::group_order_settle(imm3_query *q, uint32_t *n_groups) {
     int32_t path = GROUP_ORDER_SMALL;
     {
         LaunchTimer t(ctx, 8); // (one record for the whole order: from its first kernel's start to its last one's end)
-        if (!radix) launch_group_order_small(a, s, t.start, t.stop);
-        else {
-            launch_group_order_keys(a, s, t.start, nullptr);
+        if (!radix) {
+            if (filt) launch_group_order_small_filtered(a, q->gf, s, t.start, t.stop);
+            else launch_group_order_small(a, s, t.start, t.stop);
+        } else {
+            if (filt) { // the kept count grows in n_word, one atomic add per wave
+                HIPCHK(hipMemsetAsync(a.n_word, 0, sizeof(unsigned long long), s));
+                launch_group_order_keys_filtered(a, q->gf, s, t.start, nullptr);
+            } else launch_group_order_keys(a, s, t.start, nullptr);
             OrderArgs o;
             std::memset(&o, 0, sizeof(o));
             o.n_emit = a.n_word;
             o.cap_rows = q->go_cap;
-            o.limit = q->group_order_limit > 0 ? q->group_order_limit : 0;
+            o.limit = limit > 0 ? limit : 0;
             o.cols[0].src = a.key_col; // the whole normalised key as ONE string key: bytes as they are, never complemented again
             o.cols[0].width = a.layout.key_bytes;
             o.cols[0].kind = KIND_STR;
@@ -169,20 +180,24 @@ int imm3::group_order_settle(imm3_query *q, uint32_t *n_groups) {
                 o.byte_pos = p;
                 launch_order_pass(o, s, nullptr, nullptr);
             }
-            launch_group_order_apply(a, s, nullptr, t.stop);
+            if (filt) launch_group_order_apply_filtered(a, q->gf, s, nullptr, t.stop);
+            else launch_group_order_apply(a, s, nullptr, t.stop);
         }
     }
     HIPCHK(hipGetLastError());
-    if (radix) { // which of the two the device took
-        uint32_t st[OW_WORDS];
-        HIPCHK(hipMemcpyAsync(st, q->d_go_state, sizeof(st), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        path = st[OW_SELECT] ? GROUP_ORDER_RADIX_SELECT : GROUP_ORDER_RADIX_FULL;
-    }
+    unsigned long long words[2] = {a.n_out, n}; // {groups of the view, groups kept}: a filtered settle reads them back in one copy
+    uint32_t st[OW_WORDS] = {0};
+    if (filt) HIPCHK(hipMemcpyAsync(words, a.dst_n, sizeof(words), hipMemcpyDeviceToHost, s));
+    if (radix) HIPCHK(hipMemcpyAsync(st, q->d_go_state, sizeof(st), hipMemcpyDeviceToHost, s)); // which of the two the device took
+    if (filt || radix) HIPCHK(hipStreamSynchronize(s));
+    if (radix) path = st[OW_SELECT] ? GROUP_ORDER_RADIX_SELECT : GROUP_ORDER_RADIX_FULL;
+    if (filt && (words[1] > n || words[0] > a.n_out || words[0] > words[1])) return fail(IMM3_ERR_DEVICE, "the group filter's count words are out of range");
     q->go_path = path;
-    q->go_n_out = a.n_out;
+    q->go_n_out = (uint32_t)words[0];
+    q->gf_groups_in = filt ? n : 0;
+    q->gf_groups_kept = filt ? words[1] : 0;
     q->run.group_order_valid = true;
-    *n_groups = a.n_out;
+    *n_groups = q->go_n_out;
     return IMM3_OK;
 }
 
@@ -262,11 +277,13 @@ int imm3::group_order_fetch_keys(imm3_query *q, uint8_t *out, uint32_t max_group
     return IMM3_OK;
 }
 
-extern "C" int imm3_query_set_group_order(imm3_query *q, const imm3_group_order_key *keys, int32_t n_keys, int64_t limit) {
-    if (!q) return fail(IMM3_ERR_ARG, "query is null");
-    CTX_LIVE(q->ctx);
+namespace {
+// what the checks of the order and of the filter read of a query; the arrays are the caller's
+struct ShapeArrays {
     int32_t gk[kMaxGroupCols] = {0}, gw[kMaxGroupCols] = {0}, ak[kMaxAggs] = {0}, ck[kMaxAggs] = {0}, cw[kMaxAggs] = {0};
-    GroupOrderShape sh;
+};
+void query_shape(const imm3_query *q, ShapeArrays &arr, GroupOrderShape &sh) {
+    int32_t *gk = arr.gk, *gw = arr.gw, *ak = arr.ak, *ck = arr.ck, *cw = arr.cw;
     std::memset(&sh, 0, sizeof(sh));
     sh.is_agg = q->is_agg ? 1 : 0;
     if (q->is_agg) {
@@ -288,6 +305,15 @@ extern "C" int imm3_query_set_group_order(imm3_query *q, const imm3_group_order_
     sh.agg_kind = ak;
     sh.agg_col_kind = ck;
     sh.agg_col_width = cw;
+}
+} // namespace
+
+extern "C" int imm3_query_set_group_order(imm3_query *q, const imm3_group_order_key *keys, int32_t n_keys, int64_t limit) {
+    if (!q) return fail(IMM3_ERR_ARG, "query is null");
+    CTX_LIVE(q->ctx);
+    ShapeArrays arr;
+    GroupOrderShape sh;
+    query_shape(q, arr, sh);
     GroupOrderLayout layout;
     const int rc = group_order_plan(sh, keys, n_keys, &layout);
     if (rc) return rc;
@@ -302,6 +328,50 @@ extern "C" int imm3_query_set_group_order(imm3_query *q, const imm3_group_order_
 extern "C" int imm3_query_group_order_path(const imm3_query *q, int32_t *path) {
     if (!q || !path) return fail(IMM3_ERR_ARG, "null argument");
     if (!q->is_agg) return fail(IMM3_ERR_ARG, "not an aggregation query");
-    *path = q->group_ordered && q->run.group_order_valid ? q->go_path : GROUP_ORDER_NONE;
+    *path = (q->group_ordered || q->group_filtered) && q->run.group_order_valid ? q->go_path : GROUP_ORDER_NONE;
+    return IMM3_OK;
+}
+
+extern "C" int imm3_query_set_group_filter(imm3_query *q, const imm3_group_filter_leaf *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog) {
+    if (!q) return fail(IMM3_ERR_ARG, "imm3_query_set_group_filter: query is null");
+    CTX_LIVE(q->ctx);
+    ShapeArrays arr;
+    GroupOrderShape sh;
+    query_shape(q, arr, sh);
+    GroupFilterProg fp;
+    const int rc = group_filter_plan(sh, leaves, n_leaves, prog, n_prog, &fp);
+    if (rc) return rc;
+    q->gf.prog = fp;
+    q->group_filtered = fp.n_prog > 0;
+    q->gf_groups_in = q->gf_groups_kept = 0;
+    q->run.group_order_valid = false;
+    return IMM3_OK;
+}
+
+extern "C" int imm3_query_group_filter_stats(const imm3_query *q, uint64_t *groups_in, uint64_t *groups_kept) {
+    if (!q || !groups_in || !groups_kept) return fail(IMM3_ERR_ARG, "null argument");
+    if (!q->is_agg) return fail(IMM3_ERR_ARG, "not an aggregation query");
+    const bool live = q->group_filtered && q->run.group_order_valid && q->run.ran_agg;
+    *groups_in = live ? q->gf_groups_in : 0;
+    *groups_kept = live ? q->gf_groups_kept : 0;
+    return IMM3_OK;
+}
+
+extern "C" int imm3_group_filter_check(int32_t is_agg, const int32_t *agg_kind, const int32_t *agg_col_kind, int32_t n_aggs, const imm3_group_filter_leaf *leaves,
+                                       int32_t n_leaves, const int32_t *prog, int32_t n_prog, const int64_t *count_vals, int32_t *kept) {
+    if (n_aggs < 0 || n_aggs > kMaxAggs || (n_aggs > 0 && (!agg_kind || !agg_col_kind))) return fail(IMM3_ERR_ARG, "imm3_group_filter_check: bad aggregates");
+    GroupOrderShape sh;
+    std::memset(&sh, 0, sizeof(sh));
+    sh.is_agg = is_agg ? 1 : 0;
+    sh.n_aggs = n_aggs;
+    sh.agg_kind = agg_kind;
+    sh.agg_col_kind = agg_col_kind;
+    GroupFilterProg fp;
+    const int rc = group_filter_plan(sh, leaves, n_leaves, prog, n_prog, &fp);
+    if (rc) return rc;
+    if (count_vals) {
+        if (!kept) return fail(IMM3_ERR_ARG, "imm3_group_filter_check: kept is null");
+        *kept = group_filter_eval(fp, (unsigned long long)count_vals[0], count_vals + 1) ? 1 : 0;
+    }
     return IMM3_OK;
 }

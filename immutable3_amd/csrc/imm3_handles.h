@@ -145,7 +145,7 @@ struct QueryRunState {
     bool limit_gather_ran = false;   // the last projection was k_limit_gather's one launch: settle_rows looks at its give-up tag
     bool ran_single_pass = false;    // the last run went through k_filter_project ...
     bool sp_verified = false;        // ... and its status word has been read since (rows complete, or gathered again from the bitmap)
-    bool group_order_valid = false;  // an ordered aggregation (imm3_query_set_group_order): the ordered group arrays hold the order of the last run's groups (a run clears it: run_agg)
+    bool group_order_valid = false;  // an ordered and / or filtered aggregation (imm3_query_set_group_order, _set_group_filter): "the view is current" -- the ordered group arrays hold the view of the last run's groups (a run clears it: run_agg)
     bool rows_moved = false;         // the row arrays were allocated anew behind the last projection (imm3_query_reserve_rows): settle_rows emits its rows again
     bool order_valid = false;        // an ordered query (imm3_query_set_order): the ordered arrays hold the order of the rows as last emitted (every re-emit clears it: launch_project)
 };
@@ -397,6 +397,10 @@ struct imm3_query {
     bool go_radix_bufs = false;
     uint32_t go_n_out = 0;                    // groups of the ordered view, min(groups, limit)
     int32_t go_path = 0;                      // diagnostics (imm3_query_group_order_path): the GroupOrderPath of the last ordered settle
+    // HAVING (imm3_query_set_group_filter): the view of the groups is filter, then order, then limit; run.group_order_valid says the view is current
+    bool group_filtered = false;
+    imm3::GroupFilterArgs gf{};               // the checked program; map: the radix path's kept position -> dense index (made with the radix buffers)
+    uint64_t gf_groups_in = 0, gf_groups_kept = 0; // diagnostics (imm3_query_group_filter_stats): the last filtered settle's counts
     uint32_t sp_abandoned_runs = 0, sp_busy_runs = 0; // single-pass runs whose rows were gathered from the bitmap instead: a prefix never came / the device was busy (imm3_query_plan)
 };
 

@@ -850,6 +850,22 @@ void launch_group_order_keys(const GroupOrderArgs &a, hipStream_t s, hipEvent_t 
 void launch_group_order_apply(const GroupOrderArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 } // namespace imm3
 
+// ---- HAVING (imm3_query_set_group_filter; the program and its evaluator: imm3_group_filter_plan.h): the FILTERED instances of the three
+// kernels above, a second kernel argument beside GroupOrderArgs.  Small path: a dropped group becomes a pad of the bitonic network and
+// the launch writes {min(kept, n_out), kept} to dst_n[0 .. 1].  Radix path: the keys kernel writes the kept groups' keys compacted (a
+// wave ballot, one atomic add per wave on n_word, which the host zeroes on the stream first -- no work-group waits on another) and
+// map[kept position] = dense index; the order launches read n_word = kept as always; the apply gathers through map[perm[i]]. ----
+#include "imm3_group_filter_plan.h"
+namespace imm3 {
+struct GroupFilterArgs {
+    GroupFilterProg prog;
+    uint32_t *map;                       // radix path: kept position -> dense index, room for n
+};
+void launch_group_order_small_filtered(const GroupOrderArgs &a, const GroupFilterArgs &f, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+void launch_group_order_keys_filtered(const GroupOrderArgs &a, const GroupFilterArgs &f, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+void launch_group_order_apply_filtered(const GroupOrderArgs &a, const GroupFilterArgs &f, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+} // namespace imm3
+
 #ifdef __HIPCC__
 #include <hip/hip_ext.h>
 // Kernel launch with optional start / stop events stamped by the launch itself (hipExtLaunchKernelGGL); the plain launch

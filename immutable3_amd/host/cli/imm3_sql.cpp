@@ -8,6 +8,9 @@
 //                  grammar, in which such a statement does not parse); the rows come back sorted on the GPU, `limit` applied behind the order.
 //                  An aggregation takes the clause behind its `group by`: `select count(id), max(age) from t group by state order by
 //                  id_count desc limit 10` -- a key is a group-by column, an alias (<col>_count / _max / _min) or the aggregate call itself.
+//   --having       accept `having <hfilter>` behind an aggregation's `group by` (default off: such a statement does not parse): and / or
+//                  lists over `alias|aggregate call  > | < | =  integer`; the groups are filtered on the GPU BEFORE the order and the
+//                  limit of --order-by.
 //   --string-ranges  accept `f like 'value%'`, `f > 'value'` and `f < 'value'` on string columns (default off: the reference's grammar, in
 //                  which such a statement does not parse): byte-order prefix / range predicates, run on the GPU.  With --parse-only and a
 //                  data directory, the leaves of such conditions are also printed as the bytes the library gets ("leafbytes:").
@@ -48,10 +51,11 @@ static std::string showQuery(const Query &q) {
         p = "ProjectAgg(List(";
         for (size_t i = 0; i < q.project.aggs.size(); ++i) { if (i) p += ", "; p += std::string(names[q.project.aggs[i].kind]) + "(" + q.project.aggs[i].col + ",None)"; }
         p += ")," + list(q.project.groupBy);
-        if (!q.project.orderBy.empty() || q.project.limit > 0) { // (only under --order-by: the reference's ProjectAgg has two fields)
+        if (!q.project.orderBy.empty() || q.project.limit > 0 || q.project.having) { // (only under --order-by / --having: the reference's ProjectAgg has two fields)
             p += ",List(";
             for (size_t i = 0; i < q.project.orderBy.size(); ++i) p += std::string(i ? ", " : "") + "(" + q.project.orderBy[i].first + "," + (q.project.orderBy[i].second ? "desc" : "asc") + ")";
             p += ")," + std::to_string(q.project.limit);
+            if (q.project.having) p += ",Some(" + showSelect(*q.project.having) + ")";
         }
         p += ")";
     }
@@ -61,7 +65,7 @@ static std::string showQuery(const Query &q) {
 int main(int argc, char **argv) {
     std::string query, dataDir;
     int device = 0, repeat = 0;
-    bool parseOnly = false, honourAndOr = false, explain = false, orderBy = false, stringRanges = false;
+    bool parseOnly = false, honourAndOr = false, explain = false, orderBy = false, stringRanges = false, having = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if ((a == "-q" || a == "--query") && i + 1 < argc) query = argv[++i];
@@ -72,16 +76,17 @@ int main(int argc, char **argv) {
         else if (a == "--honour-and-or") honourAndOr = true;
         else if (a == "--order-by") orderBy = true;
         else if (a == "--string-ranges") stringRanges = true;
+        else if (a == "--having") having = true;
         else if (a == "--explain") explain = true;
         else if (a == "--repeat" && i + 1 < argc) repeat = std::atoi(argv[++i]); // re-run the query N times on the resident table, time to stderr
         else { std::fprintf(stderr, "Error parsing arguments: %s\n", a.c_str()); return 2; }
     }
     if (query.empty() || (dataDir.empty() && !parseOnly)) {
-        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only] [--honour-and-or] [--order-by] [--string-ranges] [--explain]\n");
+        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only] [--honour-and-or] [--order-by] [--having] [--string-ranges] [--explain]\n");
         return 2;
     }
     try {
-        const Query q = SQLParser::parseAll(query, orderBy, stringRanges);
+        const Query q = SQLParser::parseAll(query, orderBy, stringRanges, having);
         if (parseOnly) {
             std::cout << showQuery(q) << "\n";
             if (!dataDir.empty()) {

@@ -607,14 +607,73 @@ inline void orderGroups(std::vector<AggMapTuple> &groups, const std::vector<RawK
     if (limit > 0 && groups.size() > (size_t)limit) groups.resize((size_t)limit);
 }
 
+// HAVING over an aggregation's aggregators: groupFilterLeaves' checks, and a MaxStringAggr's alias is refused (string maxima are not
+// compared).
+inline void groupFilterSpec(const std::vector<Aggregator> &aggs, const std::vector<std::string> &groupBy, const SelectADT *having,
+                            std::vector<GroupFilterLeaf> &leaves, std::vector<int32_t> &prog) {
+    std::vector<std::string> aliases;
+    for (const auto &a : aggs) aliases.push_back(a.alias);
+    groupFilterLeaves(aliases, groupBy, having, leaves, prog);
+    for (const auto &l : leaves)
+        for (const auto &a : aggs)
+            if (a.alias == l.alias && a.kind == Aggregator::MaxStringAggr) throw Exception("having `" + l.alias + "': a string MAX is not compared by having");
+}
+// one leaf on exact integers: lhs <cond> value, or -- an average -- sum <cond> value * count (the device's rule: include/imm3.h,
+// imm3_query_set_group_filter; |value| <= 2^31 and count < 2^32 keep the product inside int64)
+inline bool groupFilterCompare(long long lhs, long long count, const GroupFilterLeaf &l) {
+    const long long rhs = l.average ? l.value * count : l.value;
+    return l.cond == IMM3_GT ? lhs > rhs : (l.cond == IMM3_LT ? lhs < rhs : lhs == rhs);
+}
+// a postfix program over leaf answers (leaf index, IMM3_EXPR_AND / _OR / _NOT)
+template <class LeafFn>
+inline bool groupFilterEval(const std::vector<int32_t> &prog, LeafFn leaf) {
+    std::vector<char> st;
+    for (int32_t op : prog) {
+        if (op >= 0) st.push_back(leaf(op) ? 1 : 0);
+        else if (op == IMM3_EXPR_NOT) st.back() = !st.back();
+        else {
+            const char y = st.back();
+            st.pop_back();
+            st.back() = op == IMM3_EXPR_AND ? (st.back() && y) : (st.back() || y);
+        }
+    }
+    return st.empty() || st.back();
+}
+// The host's HAVING over MERGED groups (the per-segment fallback; the Python mirror: operators.filter_groups): the groups the program
+// keeps, in their order; `raw` (parallel to `groups`) is cut with them.
+inline void filterGroups(std::vector<AggMapTuple> &groups, std::vector<RawKey> &raw, const std::vector<GroupFilterLeaf> &leaves, const std::vector<int32_t> &prog) {
+    if (prog.empty()) return;
+    size_t w = 0;
+    for (size_t i = 0; i < groups.size(); ++i) {
+        const AggMap &m = groups[i].second;
+        const bool keep = groupFilterEval(prog, [&](int32_t at) {
+            const GroupFilterLeaf &l = leaves.at((size_t)at);
+            for (const auto &a : m)
+                if (a.alias == l.alias) return groupFilterCompare(a.kind == Aggregator::CountAggr ? a.counter : (long long)a.dvalue, 1, l);
+            throw Exception("NoSuchElementException: key not found: " + l.alias);
+        });
+        if (!keep) continue;
+        if (w != i) {
+            groups[w] = std::move(groups[i]);
+            if (i < raw.size()) raw[w] = std::move(raw[i]);
+        }
+        ++w;
+    }
+    groups.resize(w);
+    if (raw.size() > w) raw.resize(w);
+}
+
 // ProjectAggOp(aggs, op, groupBy): one segment, fused on the GPU (scan+select kernel, LDS hash aggregation kernel)
 class ProjectAggOp : public Operator<AggMapTuple> {
   public:
     // orderBy -- (name, descending) over the group-by columns and the aliases -- and limit are applied by the device when ONE query
     // answers (runOn: a table query); per-segment results are ordered after their merge (orderGroups)
     ProjectAggOp(std::vector<Aggregator> aggs, std::shared_ptr<ColumnVectorOperator> op, std::vector<std::string> groupBy,
-                 std::vector<std::pair<std::string, bool>> orderBy = {}, int limit = 0)
-        : aggs_(std::move(aggs)), op_(std::move(op)), groupBy_(std::move(groupBy)), limit_(limit) { spec_ = groupOrderSpec(aggs_, groupBy_, orderBy); }
+                 std::vector<std::pair<std::string, bool>> orderBy = {}, int limit = 0, std::shared_ptr<SelectADT> having = nullptr)
+        : aggs_(std::move(aggs)), op_(std::move(op)), groupBy_(std::move(groupBy)), limit_(limit) {
+        spec_ = groupOrderSpec(aggs_, groupBy_, orderBy);
+        groupFilterSpec(aggs_, groupBy_, having.get(), filterLeaves_, filterProg_); // having: applied by the device when ONE query answers (runOn), else filterGroups
+    }
     const std::vector<GroupOrderEntry> &orderSpec() const { return spec_; }
     const std::vector<RawKey> &rawKeys() const { return rawKeys_; } // of the groups the last iterator() / runOn produced, in their order
     std::unique_ptr<Iterator<AggMapTuple>> iterator() override {
@@ -687,6 +746,15 @@ class ProjectAggOp : public Operator<AggMapTuple> {
         imm3Check((keyBytes > 8 ? imm3_query_create_table_agg_wide : imm3_query_create_table_agg)(
             scanOp->manager().ctx(), table, usedIdx.data(), (int32_t)usedIdx.size(), sels.data(), (int32_t)sels.size(),
             group.data(), (int32_t)group.size(), abi.data(), (int32_t)abi.size(), scanOp->table().blockSize, &h.q));
+        if (!filterProg_.empty()) { // filter, then order, then limit: all on the device
+            std::vector<imm3_group_filter_leaf> fl;
+            for (const auto &l : filterLeaves_) {
+                imm3_group_filter_leaf x{-2, l.average ? 1 : 0, l.cond, l.value};
+                for (size_t j = 0; j < aggs.size(); ++j) if (aggs[j].alias == l.alias) x.agg = (int32_t)j;
+                fl.push_back(x);
+            }
+            imm3Check(imm3_query_set_group_filter(h.q, fl.data(), (int32_t)fl.size(), filterProg_.data(), (int32_t)filterProg_.size()));
+        }
         if (!spec_.empty()) { // this query's groups are the whole answer: the device orders them and cuts them to the limit
             std::vector<imm3_group_order_key> keys;
             for (const auto &e : spec_) {
@@ -772,6 +840,8 @@ class ProjectAggOp : public Operator<AggMapTuple> {
     std::shared_ptr<ColumnVectorOperator> op_;
     std::vector<std::string> groupBy_;
     std::vector<GroupOrderEntry> spec_;
+    std::vector<GroupFilterLeaf> filterLeaves_;
+    std::vector<int32_t> filterProg_;
     int limit_ = 0;
     std::vector<RawKey> rawKeys_;
 };
@@ -909,7 +979,7 @@ class Engine {
             TablePlan p;
             if (tablePlan(q, p)) {
                 auto scan = std::make_shared<ScanOp>(sm_, 0, q.table, p.used);
-                ProjectAggOp op(aggs, scan, q.project.groupBy, q.project.orderBy, q.project.limit);
+                ProjectAggOp op(aggs, scan, q.project.groupBy, q.project.orderBy, q.project.limit, q.project.having);
                 std::vector<AggMapTuple> merged;
                 if (op.runOn(p.table, p.used, p.usedIdx, p.sels, p.tree ? &p.prog : nullptr, merged)) {
                     path_ = p.tree ? "one table query: select tree" : "one table query";
@@ -922,6 +992,9 @@ class Engine {
         std::vector<AggMapTuple> result;
         std::vector<RawKey> raw; // parallel to `result`: the first arrival's key parts
         const std::vector<GroupOrderEntry> spec = groupOrderSpec(aggs, q.project.groupBy, q.project.orderBy);
+        std::vector<GroupFilterLeaf> filterLeaves;
+        std::vector<int32_t> filterProg;
+        groupFilterSpec(aggs, q.project.groupBy, q.project.having.get(), filterLeaves, filterProg);
         const int nseg = sm_.sm.getTableSegmentCount(table.name);
         for (int seg = 0; seg < nseg; ++seg) {
             std::shared_ptr<ColumnVectorOperator> op = mkScan(used, seg);
@@ -943,6 +1016,7 @@ class Engine {
                 }
             }
         }
+        filterGroups(result, raw, filterLeaves, filterProg); // HAVING over the merged groups, before their order
         // the merged groups ordered on the host, ties in merged first-arrival order, then the limit
         std::vector<Column> groupCols;
         for (const auto &c : used)

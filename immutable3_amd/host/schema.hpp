@@ -327,7 +327,52 @@ struct ProjectADT {
     std::vector<std::pair<std::string, bool>> orderBy;
     std::vector<Aggregate> aggs;   // ProjectAgg
     std::vector<std::string> groupBy;
+    // ProjectAgg: HAVING -- And / Or over Select(alias, GT | LT | EQ); null: none.  The groups kept, BEFORE the order and the limit
+    // (imm3_query_set_group_filter)
+    std::shared_ptr<SelectADT> having;
 };
+
+// A HAVING tree checked against an aggregation's aliases and group-by columns and flattened: the leaves (alias, condition code --
+// SelectCondition::EQ / GT / LT, the C ABI's IMM3_EQ / IMM3_GT / IMM3_LT --, integer threshold) and the postfix program over their
+// indices with -1 = and, -2 = or (IMM3_EXPR_AND / IMM3_EXPR_OR).  Refused: a name that is no alias, a group-by column (rows are
+// filtered by the where clause), a condition other than GT / LT / EQ, a threshold that is no integer (aggregates are compared exactly).
+struct GroupFilterLeaf {
+    std::string alias;
+    int cond;
+    long long value;
+    bool average = false; // an average's alias: sum <cond> value * count (no aggregator of this host layer is one)
+};
+inline void groupFilterLeaves(const std::vector<std::string> &aliases, const std::vector<std::string> &groupBy, const SelectADT *having,
+                              std::vector<GroupFilterLeaf> &leaves, std::vector<int32_t> &prog) {
+    if (!having) return;
+    if (having->kind == SelectADT::And || having->kind == SelectADT::Or) {
+        groupFilterLeaves(aliases, groupBy, having->op1.get(), leaves, prog);
+        groupFilterLeaves(aliases, groupBy, having->op2.get(), leaves, prog);
+        prog.push_back(having->kind == SelectADT::And ? -1 : -2);
+        return;
+    }
+    if (having->kind != SelectADT::Select) throw Exception("having: neither And, Or nor Select");
+    const std::string &name = having->col;
+    for (const auto &g : groupBy)
+        if (g == name) throw Exception("having `" + name + "': a group-by column is filtered by the select (where), not by having");
+    bool found = false;
+    for (const auto &a : aliases) found = found || a == name;
+    if (!found) throw Exception("having `" + name + "' is not an aggregate's alias");
+    const SelectCondition &c = having->cond;
+    if (c.kind != SelectCondition::GT && c.kind != SelectCondition::LT && c.kind != SelectCondition::EQ)
+        throw Exception("having `" + name + "': the condition must be GT, LT or EQ");
+    if (!(c.value >= -9.2e18 && c.value <= 9.2e18) || (double)(long long)c.value != c.value)
+        throw Exception("having `" + name + "': the threshold is not an integer (aggregates are compared exactly)");
+    prog.push_back((int32_t)leaves.size());
+    leaves.push_back(GroupFilterLeaf{name, (int)c.kind, (long long)c.value});
+}
+inline void checkGroupFilterNames(const ProjectADT &p) {
+    std::vector<std::string> aliases;
+    for (const auto &a : p.aggs) aliases.push_back(defaultAlias(a));
+    std::vector<GroupFilterLeaf> leaves;
+    std::vector<int32_t> prog;
+    groupFilterLeaves(aliases, p.groupBy, p.having.get(), leaves, prog);
+}
 
 // ORDER BY entries of an aggregation checked against its group-by columns and its aggregates' aliases: a name that is neither is refused,
 // and so is an average (ordering by a quotient is out of scope: include/imm3.h).  A name that is both means the group column.

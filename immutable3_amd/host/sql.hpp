@@ -21,6 +21,15 @@
 // (SelectCondition::prefix / strGT / strLT), tried behind the reference's alternatives:
 //   filter           := ... | ident ">" "'" value "'" | ident "<" "'" value "'" | ident "like" "'" value "%" "'"
 // With the flag off those statements fail to parse with the message they have always given.
+// EXTENSION, only when asked for (parseAll(sql, orderBy, stringRanges, true); imm3_sql --having) -- HAVING over the groups of an
+// aggregation, before their order and limit:
+//   queryProjectAgg  := "select" rep1sep(agg, ",") "from" ident where ["group" "by" rep1sep(ident, ",")] having orderBy limit
+//   having           := opt("having" hfilter)
+//   hfilter          := "(" repsep(hfilter,"and") ")" | "(" repsep(hfilter,"or") ")" | hkey ">" value | hkey "<" value | hkey "=" value
+//   hkey             := ident | the aggregate call as written in the SELECT list (count(id) names id_count)
+// orderBy / limit follow only under their own flag.  The tree becomes ProjectADT::having; a name that is no alias, a group-by column
+// and a threshold that is no integer are refused (checkGroupFilterNames).  With the flag off the grammar and every parse-failure
+// message are what they were.
 //   ident = [\w#]+   value = [\w0-9#]+  (no sign, no decimal point)                          (:119-121)
 #pragma once
 
@@ -34,10 +43,11 @@ namespace immutabledb {
 
 class SQLParser {
   public:
-    static Query parseAll(const std::string &input, bool orderBy = false, bool stringRanges = false) {
+    static Query parseAll(const std::string &input, bool orderBy = false, bool stringRanges = false, bool having = false) {
         SQLParser p(input);
         p.orderBy_ = orderBy;
         p.stringRanges_ = stringRanges;
+        p.having_ = having;
         Query q;
         size_t end = 0;
         if (p.query(0, q, end)) {
@@ -52,7 +62,7 @@ class SQLParser {
     explicit SQLParser(const std::string &s) : s_(s) {}
     const std::string &s_;
     size_t furthest_ = 0;
-    bool orderBy_ = false, stringRanges_ = false;
+    bool orderBy_ = false, stringRanges_ = false, having_ = false;
     std::string expected_ = "`select'";
 
     size_t skipWs(size_t i) const {
@@ -195,6 +205,51 @@ class SQLParser {
         if (aggs && agg(i, a, end)) { name = defaultAlias(a); return true; }
         return ident(i, name, end);
     }
+    // hfilter: a parenthesised and-list / or-list of hfilters, or hkey (an ident or an aggregate call) > | < | = value
+    bool hfilter(size_t i, std::shared_ptr<SelectADT> &out, size_t &end) {
+        static const struct { const char *sep; bool isAnd; } lists[] = {{"and", true}, {"or", false}};
+        for (const auto &l : lists) {
+            size_t p, q;
+            if (!lit(i, "(", p)) continue;
+            std::vector<std::shared_ptr<SelectADT>> xs;
+            std::shared_ptr<SelectADT> f;
+            while (hfilter(p, f, q)) {
+                xs.push_back(f);
+                p = q;
+                size_t r;
+                if (!lit(p, l.sep, r)) break;
+                std::shared_ptr<SelectADT> g;
+                size_t u;
+                if (!hfilter(r, g, u)) break; // (repsep backtracks over a dangling separator)
+                p = r;
+            }
+            if (xs.empty() || !lit(p, ")", q)) continue;
+            std::shared_ptr<SelectADT> acc = xs[0];
+            for (size_t k = 1; k < xs.size(); ++k) acc = l.isAnd ? SelectADT::mkAnd(acc, xs[k]) : SelectADT::mkOr(acc, xs[k]);
+            out = acc;
+            end = q;
+            return true;
+        }
+        std::string name, v;
+        size_t k, q, r;
+        if (!orderKey(i, true, name, k)) return false;
+        static const char *ops[] = {">", "<", "="};
+        for (int o = 0; o < 3; ++o)
+            if (lit(k, ops[o], q) && ident(q, v, r)) {
+                const double d = toDouble(v);
+                out = SelectADT::mkSelect(name, o == 0 ? SelectCondition::gt(d) : (o == 1 ? SelectCondition::lt(d) : SelectCondition::eq(d)));
+                end = r;
+                return true;
+            }
+        return false;
+    }
+    // opt("having" hfilter): the position behind the clause, or i when there is none
+    size_t havingClause(size_t i, std::shared_ptr<SelectADT> &out) {
+        size_t p, q;
+        std::shared_ptr<SelectADT> f;
+        if (lit(i, "having", p) && hfilter(p, f, q)) { out = f; return q; }
+        return i;
+    }
     // opt("limit" digits): the position behind it, or d when there is none
     size_t limitClause(size_t d, int &limit) {
         size_t e;
@@ -279,6 +334,10 @@ class SQLParser {
                     p.groupBy = g;
                     end = f;
                 } else end = c; // queryProjectAggNoGroup
+                if (having_) { // (the opt-in, like orderBy_ below)
+                    end = havingClause(end, p.having);
+                    checkGroupFilterNames(p);
+                }
                 if (orderBy_) { // (the opt-in: with it off the statement ends here, as in the reference)
                     end = orderByClause(end, p.orderBy, true);
                     end = limitClause(end, p.limit);

@@ -45,6 +45,7 @@ EXPORTS = [
     "imm3_query_segment_starts", "imm3_query_locate_rows",
     "imm3_query_create", "imm3_query_create_agg", "imm3_query_group_count", "imm3_query_fetch_groups", "imm3_query_agg_shape",
     "imm3_query_fetch_group_strings", "imm3_query_destroy", "imm3_query_reserve_rows", "imm3_query_set_order", "imm3_query_set_group_order",
+    "imm3_query_set_group_filter",
     "imm3_query_create_agg_wide", "imm3_query_create_table_agg_wide", "imm3_query_fetch_group_keys",
     "imm3_query_create_expr", "imm3_query_create_agg_expr", "imm3_query_create_table_expr", "imm3_query_create_table_agg_expr",
     "imm3_query_run", "imm3_query_run_select", "imm3_query_run_count", "imm3_query_sync", "imm3_query_join_count", "imm3_query_log_counts",
@@ -63,6 +64,7 @@ DIAG_EXPORTS = [
     "imm3_ctx_inject_fault", "imm3_ctx_debug_device_lock", "imm3_plan_predict", "imm3_comm_debug_standin", "imm3_plan_limit_scan",
     "imm3_plan_table_limit", "imm3_plan_string_route", "imm3_plan_string_range_route", "imm3_plan_limit_chunks",
     "imm3_query_agg_form", "imm3_query_expr_form", "imm3_expr_normalize", "imm3_query_group_order_path",
+    "imm3_query_group_filter_stats", "imm3_group_filter_check",
 ]
 COMM_ID_BYTES = 128
 # imm3_query_device_ptr ids of an ordered query's arrays (include/imm3.h)
@@ -72,8 +74,38 @@ GROUP_ORDER_GROUP_COL, GROUP_ORDER_AGG = 0, 1
 GROUP_ORDER_KEY_MAX_WIDTH = 12
 GROUP_ORDER_NONE, GROUP_ORDER_SMALL, GROUP_ORDER_RADIX_FULL, GROUP_ORDER_RADIX_SELECT = 0, 1, 2, 3
 GROUP_ORDER_SMALL_MAX = 2048   # groups the one-work-group launch takes (csrc/imm3_internal.h: kGroupOrderSmall)
+# HAVING (include/imm3.h: imm3_query_set_group_filter): a leaf's `agg` for the group's selected-row count; the leaf record
+GROUP_FILTER_COUNT = -1
+GROUP_FILTER_MAX_LEAVES, GROUP_FILTER_MAX_PROG = 8, 32
+GROUP_FILTER_LEAF = np.dtype([("agg", "<i4"), ("average", "<i4"), ("cond", "<i4"), ("value", "<i8")], align=True)
 TV_GROUP_ORDER_RADIX = 25      # tuning variant: an ordered aggregation takes the radix path whatever its group count
 TV_ORDER_FULL_SORT, TV_ORDER_SELECT_ALWAYS = 23, 24   # tuning variants (csrc/imm3_handles.h): an ordered query with a limit always sorts every row / always selects
+
+
+def group_filter_arrays(leaves: Sequence[tuple], prog: Sequence[int]):
+    """imm3_query_set_group_filter's two arrays (never empty: the pointers stay valid)"""
+    ls = np.zeros(max(len(leaves), 1), GROUP_FILTER_LEAF)
+    for i, (agg, average, cond, value) in enumerate(leaves):
+        ls[i] = (int(agg), 1 if average else 0, int(cond), int(value))
+    pg = np.array(list(prog) or [0], dtype=np.int32)
+    return ls, pg
+
+
+def group_filter_check(agg_kinds: Sequence[int], agg_col_kinds: Sequence[int], leaves: Sequence[tuple], prog: Sequence[int], group=None, is_agg: bool = True):
+    """imm3_group_filter_check (include/imm3_diag.h): the entry point's argument checks on plain values, no device.  group = (count,
+    [values]): also the program's answer on that one group, by the evaluator the kernels run.  Raises Imm3Error as the call would."""
+    ak = np.array(list(agg_kinds) or [0], dtype=np.int32)
+    ck = np.array(list(agg_col_kinds) or [0], dtype=np.int32)
+    ls, pg = group_filter_arrays(leaves, prog)
+    kept = C.c_int32(-1)
+    cv = None
+    if group is not None:
+        cv = np.zeros(5, np.int64)
+        cv[0] = int(group[0])
+        cv[1: 1 + len(group[1])] = [int(v) for v in group[1]]
+    _check(load().imm3_group_filter_check(1 if is_agg else 0, ak.ctypes.data, ck.ctypes.data, len(agg_kinds), ls.ctypes.data, len(leaves), pg.ctypes.data, len(prog),
+                                          cv.ctypes.data if cv is not None else None, C.byref(kept)))
+    return None if group is None else bool(kept.value)
 
 
 class Imm3Error(Exception):
@@ -182,6 +214,9 @@ def load() -> C.CDLL:
     L.imm3_query_set_order.argtypes = [vp, vp, i32, i64]
     L.imm3_query_set_group_order.argtypes = [vp, vp, i32, i64]
     L.imm3_query_group_order_path.argtypes = [vp, P(i32)]
+    L.imm3_query_set_group_filter.argtypes = [vp, vp, i32, vp, i32]
+    L.imm3_query_group_filter_stats.argtypes = [vp, P(u64), P(u64)]
+    L.imm3_group_filter_check.argtypes = [i32, vp, vp, i32, vp, i32, vp, i32, vp, P(i32)]
     L.imm3_query_run.argtypes = [vp]
     L.imm3_query_run_select.argtypes = [vp]
     L.imm3_query_run_count.argtypes = [vp]
@@ -718,6 +753,19 @@ class DeviceQuery:
         p = C.c_int32(0)
         _check(load().imm3_query_group_order_path(self._h, C.byref(p)))
         return p.value
+
+    def set_group_filter(self, leaves: Sequence[tuple], prog: Sequence[int]):
+        """HAVING (imm3_query_set_group_filter): leaves = [(agg index | GROUP_FILTER_COUNT, average, GT | LT | EQ, int value)], prog =
+        postfix over leaf indices with EXPR_AND / EXPR_OR / EXPR_NOT.  Before or after runs; the group getters then answer over the
+        groups the program keeps -- filter, then order, then limit.  No leaves and no program: the filter is removed."""
+        ls, pg = group_filter_arrays(leaves, prog)
+        _check(load().imm3_query_set_group_filter(self._h, ls.ctypes.data, len(leaves), pg.ctypes.data, len(prog)))
+
+    def group_filter_stats(self):
+        """(groups the device's filter evaluated, groups it kept) of the last settled view; zeros without a filter or a current view"""
+        gi, gk = C.c_uint64(0), C.c_uint64(0)
+        _check(load().imm3_query_group_filter_stats(self._h, C.byref(gi), C.byref(gk)))
+        return gi.value, gk.value
 
     def run(self):
         _check(load().imm3_query_run(self._h))

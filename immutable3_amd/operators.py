@@ -25,7 +25,7 @@ from . import native
 from .native import Imm3Error
 from .query import (STR_RANGE_CONDS, str_range_bounds)
 from .query import (EQ, GT, LT, And, Avg, Count, Match, Max, Min, NoOp, NoSelect, NotMatch, Or, Project, ProjectAgg,
-                    Query, Select, SelectADT, SelectCondition, Sum, order_keys)
+                    Query, Select, SelectADT, SelectCondition, Sum, group_filter_leaves, order_keys)
 from .schema import CodecType, Column, Row, Table
 from .storage import SegmentManager
 
@@ -705,7 +705,8 @@ def resolveProjectOp(projectAgg: ProjectAgg, table: Table):
             aggs.append(CountAggr(a.col, a.alias or a.col + "_count"))
         else:
             raise Exception("Unknown Aggregate type")
-    return lambda op: ProjectAggOp(aggs, op, list(projectAgg.groupBy), getattr(projectAgg, "order_by", ()), getattr(projectAgg, "limit", 0))
+    return lambda op: ProjectAggOp(aggs, op, list(projectAgg.groupBy), getattr(projectAgg, "order_by", ()), getattr(projectAgg, "limit", 0),
+                                   getattr(projectAgg, "having", None))
 
 
 def group_order_spec(aggs: Sequence[Aggregator], groupBy: Sequence[str], order_by):
@@ -722,6 +723,67 @@ def group_order_spec(aggs: Sequence[Aggregator], groupBy: Sequence[str], order_b
             out.append((True, name, bool(desc)))
         else:
             raise ValueError(f"order by {name!r} is neither a group-by column {list(groupBy)} nor an aggregate's alias {list(by_alias)}")
+    return out
+
+
+class _Alias:
+    """what group_filter_leaves reads of an aggregate: its alias (Aggregators carry theirs)"""
+
+    def __init__(self, alias):
+        self.alias, self.col = alias, alias
+
+
+def group_filter_spec(aggs: Sequence[Aggregator], groupBy: Sequence[str], having):
+    """A HAVING tree over the aggregators' aliases -> ([(alias, average, native cond, int threshold)], postfix program over the leaf
+    indices with native.EXPR_AND / EXPR_OR): what filter_groups evaluates on the host and imm3_query_set_group_filter on the device.
+    An AvgDoubleAggr's alias becomes an `average` leaf on its SUM.  ValueError (query.group_filter_leaves's causes, and): a
+    MaxStringAggr's alias -- string maxima are not compared --, an average's threshold outside [-2^31, 2^31 - 1]."""
+    by_alias = {a.alias: a for a in aggs}
+    named, prog = group_filter_leaves([_Alias(a) for a in by_alias], groupBy, having)
+    leaves = []
+    for (alias, cond, value) in named:
+        a = by_alias[alias]
+        if isinstance(a, MaxStringAggr):
+            raise ValueError(f"having {alias!r}: a string MAX is not compared by having")
+        average = isinstance(a, AvgDoubleAggr)
+        if average and not -2 ** 31 <= value <= 2 ** 31 - 1:
+            raise ValueError(f"having {alias!r}: an average's threshold must lie in [-2^31, 2^31 - 1], got {value}")
+        leaves.append((alias, average, {GT: native.GT, LT: native.LT, EQ: native.EQ}[cond], value))
+    return leaves, [native.EXPR_AND if op == "and" else native.EXPR_OR if op == "or" else op for op in prog]
+
+
+def group_filter_leaf(aggmap: dict, leaf) -> bool:
+    """one leaf on one merged group, in exact integers: a count, the integral value of a Max / MinDoubleAggr, or -- an average --
+    sum <cond> threshold * count (the device's rule: include/imm3.h, imm3_query_set_group_filter)"""
+    alias, average, cond, value = leaf
+    a = aggmap[alias]
+    if isinstance(a, AvgDoubleAggr):
+        lhs, rhs = int(a.sum), int(value) * int(a.counter)
+    elif isinstance(a, CountAggr):
+        lhs, rhs = int(a.get()), int(value)
+    else:
+        lhs, rhs = int(a.get()), int(value)
+    return lhs > rhs if cond == native.GT else (lhs < rhs if cond == native.LT else lhs == rhs)
+
+
+def filter_groups(result: Dict[str, dict], leaves, prog) -> Dict[str, dict]:
+    """The host's HAVING over MERGED groups (the per-segment fallback and device_merge; the C++ mirror: host/operators.hpp
+    filterGroups): the groups of `result` the program keeps, in their order.  leaves / prog: group_filter_spec's; no program: every group."""
+    if not prog:
+        return result
+    out = {}
+    for key, aggmap in result.items():
+        stack = []
+        for op in prog:
+            if op >= 0:
+                stack.append(group_filter_leaf(aggmap, leaves[op]))
+            elif op == native.EXPR_NOT:
+                stack.append(not stack.pop())
+            else:
+                y, x = stack.pop(), stack.pop()
+                stack.append((x and y) if op == native.EXPR_AND else (x or y))
+        if stack[-1]:
+            out[key] = aggmap
     return out
 
 
@@ -767,14 +829,18 @@ class ProjectAggOp(Operator):
     first-seen order.  The whole chain of one segment runs fused on the GPU: scan+select kernel, then the LDS
     hash-aggregation kernel; group keys and aggregates come back already reduced."""
 
-    def __init__(self, aggs: Sequence[Aggregator], op: ColumnVectorOperator, groupBy: Sequence[str], order_by=(), limit: int = 0):
-        """order_by -- entries (name, descending) over the group-by columns and the aggregates' aliases -- and limit are applied by the
+    def __init__(self, aggs: Sequence[Aggregator], op: ColumnVectorOperator, groupBy: Sequence[str], order_by=(), limit: int = 0, having=None):
+        """having -- And / Or over Select(alias, GT | LT | EQ) -- keeps groups BEFORE the order and the limit: on the device when ONE
+        query answers (imm3_query_set_group_filter), on the merged groups otherwise (filter_groups).
+        order_by -- entries (name, descending) over the group-by columns and the aggregates' aliases -- and limit are applied by the
         device when ONE query answers (a table query: _run(ordered=True)); per-segment results are ordered after their merge
         (order_groups).  raw_keys: group key -> the raw bytes of its parts, for every group this operator has yielded."""
         self.aggs, self.op, self.groupBy = list(aggs), op, list(groupBy)
         self.order_by = tuple((str(c), bool(d)) for (c, d) in order_by)
         self.limit = int(limit)
         self.order_spec = group_order_spec(self.aggs, self.groupBy, self.order_by)   # (ValueError: an unknown name, an average)
+        self.having = having
+        self.filter_leaves, self.filter_prog = group_filter_spec(self.aggs, self.groupBy, having)   # (ValueError: see group_filter_spec)
         self.raw_keys: Dict[str, list] = {}
 
     @staticmethod
@@ -839,11 +905,18 @@ class ProjectAggOp(Operator):
         return [(native.GROUP_ORDER_AGG, aliases.index(name), desc) if is_agg else (native.GROUP_ORDER_GROUP_COL, gnames.index(name), desc)
                 for (is_agg, name, desc) in self.order_spec]
 
+    def _native_filter(self, cols):
+        """filter_leaves as imm3_query_set_group_filter's leaves: places in the native aggs list of _open"""
+        aliases = [a.alias for a in self._shape(list(cols))[2]]
+        return [(aliases.index(alias), average, cond, value) for (alias, average, cond, value) in self.filter_leaves]
+
     def _run(self, seg, cols, used_idx, sels, block_size, expr=None, ordered=False):
         """seg: a DeviceSegment or a DeviceTable (then the groups are already merged across segments).  ordered: this query's groups are
         the whole answer -- the device orders them and cuts them to the limit (imm3_query_set_group_order)."""
         _, _, _, _, wide_key, wide_strs = self._shape(list(cols))
         q = self._open(seg, cols, used_idx, sels, block_size, expr)
+        if ordered and self.filter_prog:                      # filter, then order, then limit
+            q.set_group_filter(self._native_filter(cols), self.filter_prog)
         if ordered and self.order_spec:
             q.set_group_order(self._native_order(cols), self.limit)
         keys, first, counts, vals = q.fetch_groups()
@@ -1099,7 +1172,9 @@ class Engine:
         return dict(list(result.items())[: agg_op.limit])
 
     def _order_merged(self, result: dict, raw_keys, used, agg_op) -> dict:
-        """ORDER BY / limit over groups that were merged from per-segment results: on the host (order_groups)"""
+        """HAVING, then ORDER BY / limit over groups that were merged from per-segment results: on the host (filter_groups, order_groups)"""
+        if agg_op is not None:
+            result = filter_groups(result, agg_op.filter_leaves, agg_op.filter_prog)
         if agg_op is None or not agg_op.order_spec:
             return self._cut(result, agg_op)
         group_cols = [c for c in used if c.name in agg_op.groupBy]      # batch-column order: the order of a key's parts

@@ -227,19 +227,55 @@ def group_order_names(aggs, groupBy, order_by):
             raise ValueError(f"order by {name!r}: ordering by an average is not supported")
 
 
+def group_filter_leaves(aggs, groupBy, having):
+    """A HAVING tree -- And / Or over Select(name, GT | LT | EQ), name an aggregate's alias -- checked and flattened:
+    ([(alias, cond class, int threshold)], postfix program over the leaf indices with "and" / "or").  ValueError names the cause: a name
+    that is no alias, a group-by column (rows are filtered by the select), a condition other than GT / LT / EQ, a threshold that is no
+    integer (aggregates are compared exactly in int64: include/imm3.h, imm3_query_set_group_filter).  None: ([], [])."""
+    aliases = {(a.alias or default_alias(a)): a for a in aggs}
+    leaves, prog = [], []
+
+    def rec(node):
+        if isinstance(node, (And, Or)):
+            rec(node.op1)
+            rec(node.op2)
+            prog.append("and" if isinstance(node, And) else "or")
+        elif isinstance(node, Select):
+            if node.col in groupBy:
+                raise ValueError(f"having {node.col!r}: a group-by column is filtered by the select (where), not by having")
+            if node.col not in aliases:
+                raise ValueError(f"having {node.col!r} is not an aggregate's alias {list(aliases)}")
+            if not isinstance(node.cond, (GT, LT, EQ)):
+                raise ValueError(f"having {node.col!r}: the condition must be GT, LT or EQ, not {node.cond!r}")
+            v = {GT: lambda c: c.gt, LT: lambda c: c.lt, EQ: lambda c: c.eq}[type(node.cond)](node.cond)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), float("-inf")) or int(v) != v:
+                raise ValueError(f"having {node.col!r}: the threshold {v!r} is not an integer (aggregates are compared exactly)")
+            prog.append(len(leaves))
+            leaves.append((node.col, type(node.cond), int(v)))
+        else:
+            raise ValueError(f"having: {node!r} is neither And, Or nor Select")
+
+    if having is not None:
+        rec(having)
+    return leaves, prog
+
+
 @dataclass(frozen=True)
 class ProjectAgg(ProjectADT):      # Query.scala:30; order_by / limit: the "sort" of Query.scala:27 over the groups (imm3_query_set_group_order)
     aggs: tuple
     groupBy: tuple = ()
     order_by: tuple = ()           # entries (name, descending), most significant first: a group-by column or an aggregate's alias
     limit: int = 0                 # > 0: the first `limit` groups of the order (without an order: of the first-seen order)
+    having: Optional[SelectADT] = None   # And / Or over Select(alias, GT | LT | EQ): the groups kept, BEFORE the order and the limit (imm3_query_set_group_filter)
 
-    def __init__(self, aggs, groupBy=(), order_by=(), limit: int = 0):
+    def __init__(self, aggs, groupBy=(), order_by=(), limit: int = 0, having=None):
         object.__setattr__(self, "aggs", tuple(aggs))
         object.__setattr__(self, "groupBy", tuple(groupBy))
         object.__setattr__(self, "order_by", tuple((str(c), bool(d)) for (c, d) in order_by))
         object.__setattr__(self, "limit", int(limit))
+        object.__setattr__(self, "having", having)
         group_order_names(self.aggs, self.groupBy, self.order_by)
+        group_filter_leaves(self.aggs, self.groupBy, self.having)
 
 
 @dataclass(frozen=True)

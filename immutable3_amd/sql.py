@@ -26,7 +26,16 @@ grammar (imm3_sql's --order-by switches both on).  With the flag off such a stat
 EXTENSION, only when asked for -- parseAll(sql, string_ranges=True) -- byte-order ranges on string columns (query.Prefix / StrGT / StrLT),
 tried behind the reference's alternatives:
   filter           := ... | ident ">" "'" value "'" | ident "<" "'" value "'" | ident "like" "'" value "%" "'"
-With the flag off those statements fail to parse with the message they have always given."""
+With the flag off those statements fail to parse with the message they have always given.
+
+EXTENSION, only when asked for -- parseAll(sql, having=True) -- HAVING over the groups of an aggregation, before their order and limit:
+  queryProjectAgg  := "select" rep1sep(agg, ",") "from" ident where ["group" "by" rep1sep(ident, ",")] having orderBy limit
+  having           := opt("having" hfilter)
+  hfilter          := "(" repsep(hfilter,"and") ")" | "(" repsep(hfilter,"or") ")" | hkey ">" value | hkey "<" value | hkey "=" value
+  hkey             := ident | the aggregate call as written in the SELECT list (count(id) names id_count)
+orderBy / limit follow only under their own flag (group_order).  The tree becomes ProjectAgg.having -- And / Or over Select(alias, GT |
+LT | EQ) --, whose checks (query.group_filter_leaves: an unknown alias, a group-by column, a threshold that is no integer) raise
+ValueError.  With the flag off the grammar and every parse-failure message are what they were."""
 from __future__ import annotations
 
 import re
@@ -42,13 +51,13 @@ class ParseError(Exception):
 
 
 class SQLParser:
-    def __init__(self, s: str, order_by: bool = False, string_ranges: bool = False, group_order: bool = False):
-        self.s, self.order_by, self.string_ranges, self.group_order = s, order_by, string_ranges, group_order
+    def __init__(self, s: str, order_by: bool = False, string_ranges: bool = False, group_order: bool = False, having: bool = False):
+        self.s, self.order_by, self.string_ranges, self.group_order, self.having = s, order_by, string_ranges, group_order, having
         self.furthest, self.expected = 0, "`select'"
 
     @staticmethod
-    def parseAll(sql: str, order_by: bool = False, string_ranges: bool = False, group_order: bool = False) -> Q.Query:
-        p = SQLParser(sql, order_by, string_ranges, group_order)
+    def parseAll(sql: str, order_by: bool = False, string_ranges: bool = False, group_order: bool = False, having: bool = False) -> Q.Query:
+        p = SQLParser(sql, order_by, string_ranges, group_order, having)
         r = p._query(0)
         if r is not None:
             q, end = r
@@ -223,6 +232,39 @@ class SQLParser:
                 return Q.default_alias(r[0]), r[1]
         return self._ident(i)
 
+    def _hfilter(self, i):
+        """hfilter: a parenthesised and-list / or-list of hfilters, or hkey (an ident or an aggregate call) > | < | = value"""
+        for sep, is_and in (("and", True), ("or", False)):
+            p = self._lit(i, "(")
+            xs = []
+            r = self._hfilter(p) if p is not None else None
+            while r is not None:
+                xs.append(r[0])
+                p = r[1]
+                t = self._lit(p, sep)
+                r = self._hfilter(t) if t is not None else None
+            q = self._lit(p, ")") if p is not None and xs else None
+            if q is not None:
+                acc = xs[0]
+                for x in xs[1:]:
+                    acc = Q.And(acc, x) if is_and else Q.Or(acc, x)
+                return acc, q
+        k = self._order_key(i, True)
+        if k is None:
+            return None
+        for op, mk in ((">", Q.GT), ("<", Q.LT), ("=", Q.EQ)):
+            q = self._lit(k[1], op)
+            v = self._ident(q) if q is not None else None
+            if v is not None:
+                return Q.Select(k[0], mk(self._to_double(v[0]))), v[1]
+        return None
+
+    def _having(self, i):
+        """opt("having" hfilter): (tree or None, position behind the clause)"""
+        p = self._lit(i, "having")
+        r = self._hfilter(p) if p is not None else None
+        return (None, i) if r is None else r
+
     def _limit(self, d):
         """opt("limit" digits): (limit, position behind it)"""
         e = self._lit(d, "limit")
@@ -270,11 +312,13 @@ class SQLParser:
                 e = self._lit(d, "by") if d is not None else None
                 g = self._ident_list(e, True) if e is not None else None
                 groups, d = (g[0], g[1]) if g is not None else ([], w[1])
-                order, limit = [], 0
+                order, limit, having = [], 0, None
+                if self.having:                                    # (the opt-in, like group_order below)
+                    having, d = self._having(d)
                 if self.group_order:                               # (the opt-in: with it off the statement ends here, as in the reference)
                     order, d = self._order_by(d, aggs=True)
                     limit, d = self._limit(d)
-                return Q.Query(t[0], w[0], Q.ProjectAgg(a[0], groups, order, limit)), d
+                return Q.Query(t[0], w[0], Q.ProjectAgg(a[0], groups, order, limit, having)), d
         p = self._lit(i, "select")
         if p is None:
             return None

@@ -443,8 +443,9 @@ int imm3_query_set_order(imm3_query *q, const imm3_order_key *keys, int32_t n_ke
  * or after runs: nothing in imm3_query_run depends on it (graph capture and replay of aggregation runs are unaffected).  The order is
  * applied on the device when a getter settles the groups; imm3_query_group_count, _fetch_groups, _fetch_group_strings and
  * _fetch_group_keys then answer in that order, cut to `limit`, and copy only those groups to the host.  A run, another call of this
- * function, or a re-collect into grown arrays invalidates the ordered view: the next getter orders again.
- *   keys    1 .. IMM3_ORDER_MAX_KEYS entries, keys[0] most significant.  kind IMM3_GROUP_ORDER_GROUP_COL: index = a place in the
+ * function, or a re-collect into grown arrays invalidates the ordered view: the next getter orders again.  With a filter set
+ * (imm3_query_set_group_filter below) the view is filter, then order, then limit: the order and the limit apply to the groups kept.
+ *   keys   1 .. IMM3_ORDER_MAX_KEYS entries, keys[0] most significant.  kind IMM3_GROUP_ORDER_GROUP_COL: index = a place in the
  *           creator's group_cols; kind IMM3_GROUP_ORDER_AGG: index = a place in its aggs.  descending != 0 reverses THAT key only.
  *           n_keys == 0 removes the order: the getters answer in first-seen order again, exactly as on a query never ordered.
  *   limit   > 0: the first `limit` groups of the order (imm3_query_group_count = min(groups, limit)); <= 0: every group.
@@ -462,6 +463,35 @@ enum { IMM3_GROUP_ORDER_GROUP_COL = 0, IMM3_GROUP_ORDER_AGG = 1 };
 typedef struct { int32_t kind; int32_t index; int32_t descending; } imm3_group_order_key;
 #define IMM3_GROUP_ORDER_KEY_MAX_WIDTH 12
 int imm3_query_set_group_order(imm3_query *q, const imm3_group_order_key *keys, int32_t n_keys, int64_t limit);
+
+/* ---- HAVING: `select state, count(id), max(age) from t group by state having id_count > 1000 order by id_count desc limit 10`.
+ * A predicate over the groups' aggregates, evaluated on the device when a getter settles the groups.  Called on an AGGREGATION query
+ * from any of the eight aggregation creators, before or after runs: like the group order, nothing in imm3_query_run depends on it.
+ * The view of the groups is FILTER, then ORDER, then LIMIT: with a filter set, imm3_query_group_count, _fetch_groups,
+ * _fetch_group_strings and _fetch_group_keys answer over the groups the program keeps -- in the order of imm3_query_set_group_order
+ * cut to its limit if one is set (imm3_query_group_count = min(groups kept, limit)), else in first-seen order (ascending first_row),
+ * the order the unfiltered getters give -- and copy only the answered groups to the host.  A run, a call of this function or of
+ * imm3_query_set_group_order, or a re-collect into grown arrays invalidates the view: the next getter builds it again.
+ *   leaves  0 .. IMM3_GROUP_FILTER_MAX_LEAVES.  agg: a place in the creator's aggs, or IMM3_GROUP_FILTER_COUNT: the group's
+ *           selected-row count, whether or not a COUNT aggregate exists.  cond: IMM3_GT / IMM3_LT / IMM3_EQ -- strict >, strict <, ==.
+ *           value is compared exactly in int64: with a COUNT the count, with MIN / MAX on int32 / int8 the sign-extended value, with
+ *           SUM the exact int64 sum.  average != 0 (a SUM aggregate only) compares sum / count as a rational, by
+ *           sum <cond> value * count in int64 -- the HAVING on an average; groups have count >= 1, and value must lie in
+ *           [-2^31, 2^31 - 1], so that with count < 2^32 the product cannot overflow.
+ *   prog    0 .. IMM3_GROUP_FILTER_MAX_PROG entries, postfix over leaf indices with IMM3_EXPR_AND / IMM3_EXPR_OR / IMM3_EXPR_NOT,
+ *           checked like a select tree's program (same messages).  n_leaves == 0 && n_prog == 0 removes the filter: the getters then
+ *           answer exactly as on a query never filtered.
+ * imm3_comm_merge_groups* read the dense group tables and ignore the filter, as they ignore the order.
+ * Errors (IMM3_ERR_ARG, the message names the cause): a null query, not an aggregation query, n_leaves outside 0 .. 8, n_prog outside
+ * 0 .. 32 or 0 with leaves given, a malformed program, agg out of range, a MAX over a STRING column, average on anything but a SUM or
+ * with a value outside [-2^31, 2^31 - 1], an unknown cond.
+ * OUT OF SCOPE: leaves on group columns (that is the select's job), leaves on string MAX values, non-integer thresholds, aggregates
+ * that are not in the query's aggs, filtering merged results (imm3_comm_merge_groups*) on the device, JNI / Scala bindings. ---- */
+#define IMM3_GROUP_FILTER_MAX_LEAVES 8
+#define IMM3_GROUP_FILTER_MAX_PROG   32
+#define IMM3_GROUP_FILTER_COUNT      (-1)
+typedef struct { int32_t agg; int32_t average; int32_t cond; int64_t value; } imm3_group_filter_leaf;
+int imm3_query_set_group_filter(imm3_query *q, const imm3_group_filter_leaf *leaves, int32_t n_leaves, const int32_t *prog, int32_t n_prog);
 
 /* Enqueue the whole pipeline on the context's stream.  n_proj == 0: the scan+select kernel (selection bitmap + count).
  * Unlimited projection whose SELECT list is predicate columns only (one of them an int32 column, or >= 30 % of the rows

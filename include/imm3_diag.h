@@ -99,6 +99,21 @@ int imm3_query_agg_form(const imm3_query *q, int32_t *form);
 #define IMM3_GROUP_ORDER_SMALL_MAX 2048
 int imm3_query_group_order_path(const imm3_query *q, int32_t *path);
 
+/* imm3_query_group_filter_stats: what the device's filter did in the last settled view of an aggregation with a filter set
+ * (imm3_query_set_group_filter): *groups_in = the dense groups it evaluated, *groups_kept = those the program kept (before the limit),
+ * both read back from the device's count words.  Zeros when no filter is set or the view is stale (no getter has asked since the last
+ * run or change of filter / order).  A filtered settle reports its path through imm3_query_group_order_path like an ordered one.
+ * IMM3_ERR_ARG for a null argument or a query that is not an aggregation. */
+int imm3_query_group_filter_stats(const imm3_query *q, uint64_t *groups_in, uint64_t *groups_kept);
+
+/* imm3_group_filter_check: imm3_query_set_group_filter's argument checks on plain values, no query and no device: the n_aggs aggregates'
+ * kinds (IMM3_AGG_*) and their columns' kinds (0 = int32, 1 = int8, 2 = string), then the leaves and the program.  is_agg == 0 stands
+ * for a query that is no aggregation.  Returns what the entry point would return; the message is imm3_last_error's.  With
+ * count_vals != NULL and an accepted program it also evaluates it on ONE group -- count_vals[0] = the count, count_vals[1 .. 4] = the
+ * four values -- with the evaluator the kernels run, and stores 0 / 1 in *kept. */
+int imm3_group_filter_check(int32_t is_agg, const int32_t *agg_kind, const int32_t *agg_col_kind, int32_t n_aggs, const imm3_group_filter_leaf *leaves,
+                            int32_t n_leaves, const int32_t *prog, int32_t n_prog, const int64_t *count_vals, int32_t *kept);
+
 /* imm3_query_expr_form: which kernel the last select launch of a select-tree query (an IMM3_EXPR_OR or IMM3_EXPR_NOT in its program) ran: 0 = the tile
  * form (k_filter_expr), 1 = the generic form (k_filter_expr_generic); -1 before the first launch, for a tree that selects nothing
  * (no launch at all) and for every other query.  A tree that selects EVERY row runs the NoSelect scan: 0 when that is the tile
