@@ -971,7 +971,8 @@ class Comm:
 
     @staticmethod
     def merge_groups_all(comms: Sequence["Comm"], queries_per_comm: Sequence[Sequence["DeviceQuery"]], segments_per_comm: Sequence[Sequence[int]]):
-        """Single-process flavour of merge_groups: one Comm per device (create_all), each with its queries and their segment indices."""
+        """Single-process flavour of merge_groups: one Comm per context -- create_all's (one context per device) or a world-of-one Comm per
+        context, several on one device included: only a Comm's context is read --, each with its queries and their segment indices."""
         n = len(comms)
         carr = (C.c_void_p * n)(*[c._h for c in comms])
         qarrs = [(C.c_void_p * max(1, len(qs)))(*[q._h for q in qs]) for qs in queries_per_comm]
@@ -1022,7 +1023,8 @@ class Comm:
 
     @staticmethod
     def merge_groups_wide_all(comms: Sequence["Comm"], queries_per_comm: Sequence[Sequence["DeviceQuery"]], segments_per_comm: Sequence[Sequence[int]]):
-        """Single-process flavour of merge_groups_wide: one Comm per device (create_all), each with its queries and their segment indices."""
+        """Single-process flavour of merge_groups_wide: one Comm per context -- create_all's (one context per device) or a world-of-one Comm per
+        context, several on one device included: only a Comm's context is read --, each with its queries and their segment indices."""
         n = len(comms)
         carr = (C.c_void_p * n)(*[c._h for c in comms])
         qarrs = [(C.c_void_p * max(1, len(qs)))(*[q._h for q in qs]) for qs in queries_per_comm]
@@ -1083,7 +1085,8 @@ class Comm:
 
     @staticmethod
     def merge_ordered_all(comms: Sequence["Comm"], queries_per_comm: Sequence[Sequence["DeviceQuery"]], segments_per_comm: Sequence[Sequence], limit: int = 0):
-        """Single-process flavour of merge_ordered: one Comm per device (create_all), each with its queries and their segment indices."""
+        """Single-process flavour of merge_ordered: one Comm per context -- create_all's (one context per device) or a world-of-one Comm per
+        context, several on one device included: only a Comm's context is read --, each with its queries and their segment indices."""
         n = len(comms)
         carr = (C.c_void_p * n)(*[c._h for c in comms])
         qarrs = [(C.c_void_p * max(1, len(qs)))(*[q._h for q in qs]) for qs in queries_per_comm]

@@ -1208,12 +1208,10 @@ class Engine:
                 finally:
                     comm.close()
             else:
-                comms = native.Comm.create_all([self.sm.ctxs[ci] for ci in order])
-                try:
-                    key_bytes, _, counts, vals, strs = native.Comm.merge_groups_wide_all(comms, [queries[ci] for ci in order], [seg_ids[ci] for ci in order])
-                finally:
-                    for c in comms:
-                        c.close()
+                # several contexts: each one's world-of-one communicator (the _all merges use a communicator's context only).  Not
+                # Comm.create_all: that is one context per DEVICE, and a manager may hold several contexts on one device.
+                comms = [self.sm.merge_comm(ci) for ci in order]
+                key_bytes, _, counts, vals, strs = native.Comm.merge_groups_wide_all(comms, [queries[ci] for ci in order], [seg_ids[ci] for ci in order])
         finally:
             for qs in queries.values():
                 for q in qs:
@@ -1297,12 +1295,8 @@ class Engine:
             if len(order) == 1:
                 _, _, cols = self.sm.merge_comm(order[0]).merge_ordered(queries[order[0]], seg_ids[order[0]], limit)
             else:
-                comms = native.Comm.create_all([self.sm.ctxs[ci] for ci in order])
-                try:
-                    _, _, cols = native.Comm.merge_ordered_all(comms, [queries[ci] for ci in order], [seg_ids[ci] for ci in order], limit)
-                finally:
-                    for c in comms:
-                        c.close()
+                comms = [self.sm.merge_comm(ci) for ci in order]      # (world-of-one each, as in _execute_agg_device_merge)
+                _, _, cols = native.Comm.merge_ordered_all(comms, [queries[ci] for ci in order], [seg_ids[ci] for ci in order], limit)
         finally:
             for qs in queries.values():
                 for q in qs:

@@ -624,8 +624,10 @@ int imm3_comm_allreduce_count_all(imm3_comm *const *comms, int32_t n_comms, imm3
  * Synchronous (the merged table is returned to the host). */
 int imm3_comm_merge_groups(imm3_comm *c, imm3_query *const *queries, const int32_t *segment_index, int32_t n_queries,
                            uint64_t *keys, uint64_t *first, uint64_t *counts, int64_t *vals, uint32_t max_groups, uint32_t *n_groups);
-/* Single-process flavour (comms from imm3_comm_create_all): comms[i] brings queries[i][0 .. n_queries[i]) with
- * segment_index[i][...]; the devices' tables are merged inside this process. */
+/* Single-process flavour: comms[i] brings queries[i][0 .. n_queries[i]) with segment_index[i][...]; the tables are merged inside this
+ * process.  Only a communicator's CONTEXT is read (no collective runs), so any communicators with one context each do: those of
+ * imm3_comm_create_all (one context per device), or a world-of-one communicator per context, several of them on one device included.
+ * comms[i]'s queries must have been created on its context.  The same holds for the two _all merges below. */
 int imm3_comm_merge_groups_all(imm3_comm *const *comms, int32_t n_comms, imm3_query *const *const *queries,
                                const int32_t *const *segment_index, const int32_t *n_queries,
                                uint64_t *keys, uint64_t *first, uint64_t *counts, int64_t *vals, uint32_t max_groups, uint32_t *n_groups);
@@ -656,8 +658,8 @@ int imm3_comm_merge_groups_all(imm3_comm *const *comms, int32_t n_comms, imm3_qu
 int imm3_comm_merge_groups_wide(imm3_comm *c, imm3_query *const *queries, const int32_t *segment_index, int32_t n_queries,
                                 uint8_t *key_bytes_out, uint64_t *first, uint64_t *counts, int64_t *vals,
                                 uint8_t *const *str_out, uint32_t max_groups, uint32_t *n_groups);
-/* Single-process flavour (comms from imm3_comm_create_all), as imm3_comm_merge_groups_all: per device the one-rank merge, then one
- * merge by byte key inside this process. */
+/* Single-process flavour (communicators as for imm3_comm_merge_groups_all): per communicator the one-rank merge on its context, then
+ * one merge by byte key inside this process. */
 int imm3_comm_merge_groups_wide_all(imm3_comm *const *comms, int32_t n_comms, imm3_query *const *const *queries,
                                     const int32_t *const *segment_index, const int32_t *n_queries,
                                     uint8_t *key_bytes_out, uint64_t *first, uint64_t *counts, int64_t *vals,
@@ -690,8 +692,8 @@ int imm3_comm_merge_groups_wide_all(imm3_comm *const *comms, int32_t n_comms, im
 int imm3_comm_merge_ordered(imm3_comm *c, imm3_query *const *queries, const int32_t *segment_index, int32_t n_queries,
                             int64_t limit, uint32_t *segment_out, uint32_t *row_out, void *const *col_out,
                             uint64_t max_rows, uint64_t *n_rows);
-/* Single-process flavour (comms from imm3_comm_create_all), as imm3_comm_merge_groups_wide_all: per device the one-rank merge cut to
- * `limit`, then one merge of the devices' lists inside this process. */
+/* Single-process flavour (communicators as for imm3_comm_merge_groups_all): per communicator the one-rank merge on its context, cut to
+ * `limit`, then one merge of their lists inside this process. */
 int imm3_comm_merge_ordered_all(imm3_comm *const *comms, int32_t n_comms, imm3_query *const *const *queries,
                                 const int32_t *const *segment_index, const int32_t *n_queries,
                                 int64_t limit, uint32_t *segment_out, uint32_t *row_out, void *const *col_out,

@@ -129,3 +129,29 @@ def test_with_a_select_and_without_clauses(tables):
             assert as_plain(plain) == expected(rows, aggs, group, [], 0), block
         finally:
             gsm.close()
+
+
+def test_two_contexts_on_one_device_merge_on_the_device(tables):
+    """Several contexts need not mean several devices.  With device_merge=True the Engine's several-context branch used to ask for one
+    communicator per DEVICE (Comm.create_all), which refuses two contexts on one device; it now takes each context's own world-of-one
+    communicator.  The segments alternate between the contexts, so every group and every tie crosses them.  (Pinned from the statement
+    fuzz, test_gpu_stmt_fuzz.py, configuration d.)"""
+    from immutable3_amd import native
+    from immutable3_amd.operators import Engine, GpuSegmentManager
+    from immutable3_amd.query import Project
+    from immutable3_amd.storage import SegmentManager
+    rows, dirs = tables
+    ctxs = [native.Context(0) for _ in range(2)]
+    gsm = GpuSegmentManager(SegmentManager(dirs[1024]), ctxs)
+    try:
+        assert gsm.device_table("people") is None                      # no table over several contexts: per-segment queries
+        aggs, group, order_by, limit = CASES[2]
+        got = Engine(gsm, device_merge=True).execute_agg(mk_query(aggs, group, order_by, limit))
+        assert as_plain(got) == expected(rows, aggs, group, order_by, limit)
+        q = Query("people", NoSelect, Project(["age", "id"], 7, [("age", True)]))
+        want = sorted(((r["age"], r["id"]) for r in rows), key=lambda t: -t[0])[:7]       # stable: ties in (segment, row)
+        assert [tuple(r) for r in Engine(gsm, device_merge=True).execute(q)] == want
+    finally:
+        gsm.close()
+        for c in ctxs:
+            c.close()

@@ -87,6 +87,10 @@ def test_null_query_and_accepted_shapes():
     # a COUNT aggregate and IMM3_GROUP_FILTER_COUNT both read the group's count, never vals
     for agg in (0, CNT):
         assert native.group_filter_check(KINDS, COLS, [(agg, 0, EQ, 5)], [0], group=(5, [99, 0, 0, 0])) is True
+    # ... whatever its column: count(name) over a string column is compared like count(id) (found by the statement fuzz: the table path
+    # refused `select count(state) from t group by state having state_count > 537`, which the per-segment path answers)
+    assert native.group_filter_check([C, MX], [STR, STR], [(0, 0, GT, 4)], [0], group=(5, [0, 0, 0, 0])) is True
+    assert native.group_filter_check([C, MX], [STR, STR], [(0, 0, LT, 5)], [0], group=(5, [0, 0, 0, 0])) is False
 
 
 # ---- 2. random trees: the library's evaluator, the Python filter_groups and the C++ filterGroups against Fractions ---------------------------
