@@ -25,6 +25,7 @@ struct imm3_comm {
     int32_t standin_wgs = 0;
     uint32_t standin_ticks = 0;   // how long each of its work-groups spins, in ticks of the 100 MHz device clock
     bool reserves = false;        // counted in ctx->comms_attached: its collectives launch kernels (more than one rank, or the stand-in)
+    int32_t view_path = 0;        // diagnostics (imm3_comm_merge_view_path): the GroupOrderPath of the last imm3_comm_merge_groups_view
 };
 
 namespace imm3 {
@@ -130,5 +131,25 @@ int merge_gather(imm3_comm *c, hipStream_t s, void *d_send, void *d_recv, size_t
 // The first check of both group merges (imm3_merge_groups.cpp): every query is an aggregation that has run, all of them aggregate
 // alike, and there is at least one.
 void merge_check_agg_queries(imm3_query *const *queries, int32_t n, LocalVerdict &verdict);
+
+// ---- views of merged groups (imm3_merge_view_api.cpp; the plan: imm3_merge_view_plan.h).  imm3_merge_wide.cpp runs its merge as always
+// and keeps the final record list on the device; these pieces check the view, make the ranks agree on it and compute it there. ----
+struct MergeViewCall {
+    MergeViewPlan plan;            // the user keys, the program and the limit once merge_view_check has passed; the tie once merge_view_agree has
+    uint32_t largest_segment = 0;  // of this rank's segment_index
+};
+// The view's own checks on this rank (the rules of imm3_query_set_group_order and imm3_query_set_group_filter over queries[0]'s
+// shape), into the verdict: they travel with the shape vote.  Called once the queries themselves have passed.
+void merge_view_check(imm3_query *const *queries, const int32_t *segment_index, int32_t n_queries, const imm3_group_view *view, MergeViewCall &v, LocalVerdict &verdict);
+// Behind the shape vote: every rank brought the same view (one more merge_vote, on the hash of its canonical bytes), the largest
+// segment index of any rank (one merge_max_word), then the tie or its refusal -- the same answer on every rank, before any gather.
+int merge_view_agree(imm3_comm *c, hipStream_t s, MergeViewCall &v);
+// The view of the `n` records at d_list (device, geometry `geo`), computed on the device: the first min(view, max_groups) records in
+// the view's order in `out`, *n_view = min(kept, limit), *n_kept.  Local to this rank: nothing collective.
+int merge_view_device(imm3_comm *c, MergeViewCall &v, const MergeWideArgs &geo, const unsigned long long *d_list, unsigned long long n, uint32_t max_groups,
+                      std::vector<unsigned long long> &out, uint64_t *n_view, uint64_t *n_kept);
+// ... and of `n` records on the host (merge_view_host): the single-process flavour
+void merge_view_of_host_records(MergeViewCall &v, const MergeWideArgs &geo, const std::vector<unsigned long long> &recs, std::vector<unsigned long long> &out,
+                                uint64_t *n_view, uint64_t *n_kept);
 
 } // namespace imm3

@@ -36,8 +36,19 @@ struct GroupFilterProg {
 
 // one leaf on a group.  V: the element type of the group's kMaxAggs values (int64_t on the host, long long on the device); `vals` may
 // point into global memory -- the one dynamically indexed load is from there, never from a register array.
-template <class V>
+// WIDE (a view of MERGED groups, imm3_merge_view_plan.h): a merged count can pass 2^32, where value * count no longer fits int64 -- the
+// leaf then compares in 128 bits.  The instances without the flag are what they always were.
+template <class V, bool WIDE = false>
 IMM3_GF_HD bool group_filter_leaf(const GroupFilterLeaf &l, unsigned long long count, const V *vals) {
+    if constexpr (WIDE) {
+        __int128 lhs, rhs = (__int128)l.value;
+        if (l.src == GF_COUNT) lhs = (__int128)count;
+        else {
+            lhs = (__int128)(long long)vals[l.at];
+            if (l.src == GF_AVG) rhs = rhs * (__int128)count;
+        }
+        return l.cond == IMM3_GT ? lhs > rhs : (l.cond == IMM3_LT ? lhs < rhs : lhs == rhs);
+    }
     long long lhs, rhs = (long long)l.value;
     if (l.src == GF_COUNT) lhs = (long long)count;
     else {
@@ -50,13 +61,13 @@ IMM3_GF_HD bool group_filter_leaf(const GroupFilterLeaf &l, unsigned long long c
 // The program on one group.  The stack is the bits of one 32-bit word, its top in bit 0: a checked program of at most
 // IMM3_GROUP_FILTER_MAX_PROG entries that ends with one result never holds more than 17.  The program is the same for every group, so
 // on the device the walk is uniform across a wave.
-template <class V>
+template <class V, bool WIDE = false>
 IMM3_GF_HD bool group_filter_eval(const GroupFilterProg &f, unsigned long long count, const V *vals) {
     if (f.n_prog <= 0) return true;
     uint32_t st = 0;
     for (int32_t i = 0; i < f.n_prog; ++i) {
         const int32_t op = f.prog[i];
-        if (op >= 0) st = (st << 1) | (group_filter_leaf(f.leaf[op], count, vals) ? 1u : 0u);
+        if (op >= 0) st = (st << 1) | (group_filter_leaf<V, WIDE>(f.leaf[op], count, vals) ? 1u : 0u);
         else if (op == IMM3_EXPR_NOT) st ^= 1u;
         else {
             const uint32_t b = st & 1u;

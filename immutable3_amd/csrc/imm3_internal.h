@@ -866,6 +866,33 @@ void launch_group_order_keys_filtered(const GroupOrderArgs &a, const GroupFilter
 void launch_group_order_apply_filtered(const GroupOrderArgs &a, const GroupFilterArgs &f, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 } // namespace imm3
 
+// ---- views of MERGED groups (imm3_comm_merge_groups_view; imm3_merge_view.hip; the plan and the key builder: imm3_merge_view_plan.h):
+// filter, then order, then limit over the record list a merge by byte key leaves on the device (MergeWideArgs::out_recs), into a list
+// of n_out ordered records.  The two paths of the group order: one launch of one work-group up to kGroupOrderSmall records, above it
+// a keys launch (plain, or filtered: compacted by one atomic add per wave on n_word, with map[kept position] = record index), the
+// order launches of imm3_order.hip over the key column as ONE KIND_STR key, and an apply launch that gathers whole records. ----
+#include "imm3_merge_view_plan.h"
+namespace imm3 {
+static_assert(kMergeViewAggs == kMaxAggs && kMergeViewHead == kMergeWideHead && kMergeViewKeyBytes == kOrderKeyMaxBytes, "imm3_merge_view_plan.h restates these");
+struct MergeViewArgs {
+    MergeViewPlan plan;
+    const unsigned long long *recs;      // n records of plan.rec_words words
+    uint32_t n;                          // host-known
+    uint32_t n_out;                      // min(n, limit)
+    unsigned long long *dst;             // room for n_out records
+    unsigned long long *dst_n;           // {records of the view, records kept}
+    // radix path (as GroupOrderArgs)
+    uint8_t *key_col;
+    unsigned long long *n_word;
+    uint32_t *map;
+    const uint32_t *perm[2];
+    const uint32_t *state;
+};
+void launch_merge_view_small(const MergeViewArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+void launch_merge_view_keys(const MergeViewArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // (filtered: n_word zeroed on the stream first)
+void launch_merge_view_apply(const MergeViewArgs &a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+} // namespace imm3
+
 #ifdef __HIPCC__
 #include <hip/hip_ext.h>
 // Kernel launch with optional start / stop events stamped by the launch itself (hipExtLaunchKernelGGL); the plain launch

@@ -5,7 +5,8 @@
 // whose slots hold the index of the record that claimed them, the occupied slots come out as records again (the local phase,
 // wide_local), and with more than one rank those lists are exchanged with ncclAllGather -- fixed-size slots, sized by an
 // all-reduce(max) of the list lengths -- and go through the same table once more (wide_exchange, built from the protocol of
-// imm3_comm_internal.h).
+// imm3_comm_internal.h).  imm3_comm_merge_groups_view[_all] (at the end) are this merge with its final list left on the device for
+// the view's launches (imm3_merge_view_api.cpp / imm3_merge_view.hip).
 #include "imm3_comm_internal.h"
 
 #include <algorithm>
@@ -115,13 +116,13 @@ void combine_wide(unsigned long long *into, const unsigned long long *g, const M
     }
 }
 
-// records (any order) -> the caller's arrays, ascending first arrival
+// records (any order) -> the caller's arrays, ascending first arrival; in_list_order: as they come (a view ordered them already)
 void unpack_wide(const std::vector<unsigned long long> &recs, const WideSpec &sp, const MergeWideArgs &geo, uint8_t *key_bytes_out, uint64_t *first,
-                 uint64_t *counts, int64_t *vals, uint8_t *const *str_out, uint32_t max_groups, uint32_t *n_groups) {
+                 uint64_t *counts, int64_t *vals, uint8_t *const *str_out, uint32_t max_groups, uint32_t *n_groups, bool in_list_order = false) {
     const size_t R = (size_t)geo.rec_words, n = recs.size() / R;
     std::vector<const unsigned long long *> order(n);
     for (size_t i = 0; i < n; ++i) order[i] = recs.data() + i * R;
-    std::sort(order.begin(), order.end(), [](const unsigned long long *x, const unsigned long long *y) { return x[0] < y[0]; }); // first arrival first
+    if (!in_list_order) std::sort(order.begin(), order.end(), [](const unsigned long long *x, const unsigned long long *y) { return x[0] < y[0]; }); // first arrival first
     *n_groups = (uint32_t)n;
     for (size_t o = 0; o < n && o < max_groups; ++o) {
         const unsigned long long *w = order[o];
@@ -262,11 +263,24 @@ int wide_local(imm3_ctx *ctx, imm3_query *const *queries, const int32_t *segment
     return read_records(a1.out_recs, L.mine, R, s, L.recs);
 }
 
-// The ranks' records into one list, on every rank: L.recs.
-int wide_exchange(imm3_comm *c, WideLocal &L) {
+// a view behind the merge (imm3_comm_merge_groups_view): the final list stays on the device -- n records at d_list, in `block` (the
+// exchange's) or in the local phase's block -- for the launches of imm3_merge_view.hip
+struct WideKeep {
+    MergeViewCall *view = nullptr;
+    DeviceBlock block;
+    const unsigned long long *d_list = nullptr;
+    unsigned long long n = 0;
+};
+
+// The ranks' records into one list, on every rank: L.recs -- or, with `keep`, left on the device once the ranks agree on the view.
+int wide_exchange(imm3_comm *c, WideLocal &L, WideKeep *keep = nullptr) {
     hipStream_t s = c->ctx->stream;
     int rc = merge_vote(c, s, L.sp.vote(0), L.sp.vote(1), L.verdict, "the ranks' aggregation queries differ in key width, aggregates or string MAX widths");
     if (rc) return rc;
+    if (keep) { // (every rank is here with a checked view: the same answer on all of them, before the gather)
+        rc = merge_view_agree(c, s, *keep->view);
+        if (rc) return rc;
+    }
     unsigned long long most = 0;
     rc = merge_list_length(c, s, L.step, L.mine, "a rank could not build its merge table; no rank has merged anything", &most);
     if (rc) return rc;
@@ -275,7 +289,7 @@ int wide_exchange(imm3_comm *c, WideLocal &L) {
     const unsigned long long entries = most * (unsigned long long)c->world;
     if (entries > kMaxMergeEntries) return fail(IMM3_ERR_ARG, "too many groups to merge"); // (the same figure on every rank: every rank leaves here)
     const unsigned long long slots2 = pow2_at_least(2 * entries);
-    DeviceBlock x; // {send slot, the ranks' slots, second table}
+    DeviceBlock x_here, &x = keep ? keep->block : x_here; // {send slot, the ranks' slots, second table}
     rc = merge_exchange_alloc(c, s, (per_rank + per_rank * (size_t)c->world) * sizeof(unsigned long long) + wide_table_bytes(L.geo, slots2, entries), x);
     if (rc) return rc;
     unsigned long long *d_send = (unsigned long long *)x.p, *d_recv = d_send + per_rank;
@@ -294,7 +308,40 @@ int wide_exchange(imm3_comm *c, WideLocal &L) {
     unsigned long long n2 = 0;
     HIPCHK(hipMemcpyAsync(&n2, a2.out_n, sizeof(n2), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    if (keep) {
+        keep->d_list = a2.out_recs;
+        keep->n = n2;
+        return IMM3_OK;
+    }
     return read_records(a2.out_recs, n2, R, s, L.recs);
+}
+
+// The single-process flavours' merge: per communicator the one-rank merge on its context, then one merge by byte key on the host
+// into `merged` (no particular order).
+int wide_all_records(imm3_comm *const *comms, int32_t n_comms, imm3_query *const *const *queries, const int32_t *const *segment_index, const int32_t *n_queries,
+                     uint8_t *const *str_out, WideSpec &sp, MergeWideArgs &geo, std::vector<unsigned long long> &merged) {
+    bool have = false;
+    geo = wide_geometry(sp);
+    std::map<std::string, std::vector<unsigned long long>> all;
+    for (int32_t i = 0; i < n_comms; ++i) {
+        if (!comms[i] || n_queries[i] < 0 || (n_queries[i] > 0 && (!queries[i] || !segment_index[i]))) return fail(IMM3_ERR_ARG, "bad argument");
+        if (n_queries[i] == 0) continue;
+        WideLocal L;
+        const int rc = wide_local(comms[i]->ctx, queries[i], segment_index[i], n_queries[i], str_out, true, L);
+        if (rc) return rc;
+        if (!have) { sp = L.sp; geo = L.geo; have = true; }
+        else if (!(L.sp == sp)) return fail(IMM3_ERR_ARG, "the devices' aggregation queries differ in key width, aggregates or string MAX widths");
+        const size_t R = (size_t)geo.rec_words;
+        for (size_t g = 0; g < L.recs.size() / R; ++g) {
+            const unsigned long long *w = L.recs.data() + g * R;
+            std::string key((const char *)(w + kMergeWideHead), (size_t)sp.key_bytes);
+            auto it = all.find(key);
+            if (it == all.end()) all.emplace(std::move(key), std::vector<unsigned long long>(w, w + R));
+            else combine_wide(it->second.data(), w, geo);
+        }
+    }
+    for (auto &kv : all) merged.insert(merged.end(), kv.second.begin(), kv.second.end());
+    return IMM3_OK;
 }
 
 } // namespace
@@ -319,29 +366,87 @@ extern "C" int imm3_comm_merge_groups_wide_all(imm3_comm *const *comms, int32_t 
                                                uint8_t *key_bytes_out, uint64_t *first, uint64_t *counts, int64_t *vals,
                                                uint8_t *const *str_out, uint32_t max_groups, uint32_t *n_groups) {
     if (!comms || n_comms < 1 || !queries || !segment_index || !n_queries || !n_groups) return fail(IMM3_ERR_ARG, "bad argument");
-    bool have = false;
     WideSpec sp;
-    MergeWideArgs geo = wide_geometry(sp);
-    std::map<std::string, std::vector<unsigned long long>> all;
-    for (int32_t i = 0; i < n_comms; ++i) {
-        if (!comms[i] || n_queries[i] < 0 || (n_queries[i] > 0 && (!queries[i] || !segment_index[i]))) return fail(IMM3_ERR_ARG, "bad argument");
-        if (n_queries[i] == 0) continue;
-        WideLocal L;
-        const int rc = wide_local(comms[i]->ctx, queries[i], segment_index[i], n_queries[i], str_out, true, L);
-        if (rc) return rc;
-        if (!have) { sp = L.sp; geo = L.geo; have = true; }
-        else if (!(L.sp == sp)) return fail(IMM3_ERR_ARG, "the devices' aggregation queries differ in key width, aggregates or string MAX widths");
-        const size_t R = (size_t)geo.rec_words;
-        for (size_t g = 0; g < L.recs.size() / R; ++g) {
-            const unsigned long long *w = L.recs.data() + g * R;
-            std::string key((const char *)(w + kMergeWideHead), (size_t)sp.key_bytes);
-            auto it = all.find(key);
-            if (it == all.end()) all.emplace(std::move(key), std::vector<unsigned long long>(w, w + R));
-            else combine_wide(it->second.data(), w, geo);
-        }
-    }
+    MergeWideArgs geo;
     std::vector<unsigned long long> merged;
-    for (auto &kv : all) merged.insert(merged.end(), kv.second.begin(), kv.second.end());
+    const int rc = wide_all_records(comms, n_comms, queries, segment_index, n_queries, str_out, sp, geo, merged);
+    if (rc) return rc;
     unpack_wide(merged, sp, geo, key_bytes_out, first, counts, vals, str_out, max_groups, n_groups);
+    return IMM3_OK;
+}
+
+// ---- views of the merged groups (include/imm3.h: imm3_comm_merge_groups_view; DESIGN.md section 21, "Views of merged groups") ----
+// The merge above, unchanged, with its final record list left on the device; the view -- filter, then order, then limit -- is computed
+// there (imm3_merge_view_api.cpp / .hip) and only its records are copied and unpacked, in list order.
+extern "C" int imm3_comm_merge_groups_view(imm3_comm *c, imm3_query *const *queries, const int32_t *segment_index, int32_t n_queries,
+                                           const imm3_group_view *view, uint8_t *key_bytes_out, uint64_t *first, uint64_t *counts, int64_t *vals,
+                                           uint8_t *const *str_out, uint32_t max_groups, uint32_t *n_groups, uint64_t *n_kept) {
+    if (!c || !n_groups || n_queries < 0 || (n_queries > 0 && (!queries || !segment_index))) return fail(IMM3_ERR_ARG, "bad argument");
+    imm3::GateScope gate(&c->ctx->gate); // (held across all phases)
+    c->view_path = GROUP_ORDER_NONE;
+    WideLocal L;
+    MergeViewCall view_call;
+    WideKeep keep;
+    keep.view = &view_call;
+    int rc = wide_local(c->ctx, queries, segment_index, n_queries, str_out, false, L);
+    if (rc) return rc;
+    merge_view_check(queries, segment_index, n_queries, view, view_call, L.verdict); // (behind the queries' own checks: their error comes first)
+    if (c->world > 1) rc = wide_exchange(c, L, &keep);
+    else {
+        rc = merge_local_result(L.verdict, L.step);
+        if (!rc) rc = merge_view_agree(c, c->ctx->stream, view_call);
+        keep.d_list = L.a1.out_recs;
+        keep.n = L.mine;
+    }
+    if (rc) return rc;
+    std::vector<unsigned long long> recs;
+    uint64_t n_view = 0, kept = 0;
+    rc = merge_view_device(c, view_call, L.geo, keep.d_list, keep.n, max_groups, recs, &n_view, &kept);
+    if (rc) return rc;
+    uint32_t unpacked = 0;
+    unpack_wide(recs, L.sp, L.geo, key_bytes_out, first, counts, vals, str_out, max_groups, &unpacked, true);
+    *n_groups = (uint32_t)n_view; // (the groups of the view, also when max_groups is smaller)
+    if (n_kept) *n_kept = kept;
+    return IMM3_OK;
+}
+
+// Single-process flavour: the merge finishes on the host (imm3_comm_merge_groups_wide_all), and so does its view (merge_view_host).
+extern "C" int imm3_comm_merge_groups_view_all(imm3_comm *const *comms, int32_t n_comms, imm3_query *const *const *queries,
+                                               const int32_t *const *segment_index, const int32_t *n_queries, const imm3_group_view *view,
+                                               uint8_t *key_bytes_out, uint64_t *first, uint64_t *counts, int64_t *vals,
+                                               uint8_t *const *str_out, uint32_t max_groups, uint32_t *n_groups, uint64_t *n_kept) {
+    if (!comms || n_comms < 1 || !queries || !segment_index || !n_queries || !n_groups) return fail(IMM3_ERR_ARG, "bad argument");
+    WideSpec sp;
+    MergeWideArgs geo;
+    std::vector<unsigned long long> merged;
+    int rc = wide_all_records(comms, n_comms, queries, segment_index, n_queries, str_out, sp, geo, merged);
+    if (rc) return rc;
+    MergeViewCall view_call;
+    LocalVerdict verdict;
+    bool checked = false;
+    uint32_t largest = 0;
+    for (int32_t i = 0; i < n_comms; ++i) {
+        if (n_queries[i] == 0) continue;
+        if (!checked) merge_view_check(queries[i], segment_index[i], n_queries[i], view, view_call, verdict); // (every query has passed the merge's checks)
+        checked = true;
+        for (int32_t k = 0; k < n_queries[i]; ++k) largest = std::max(largest, (uint32_t)segment_index[i][k]);
+    }
+    if (!checked) { // (no communicator brought a query: the empty result of imm3_comm_merge_groups_wide_all)
+        *n_groups = 0;
+        if (n_kept) *n_kept = 0;
+        return IMM3_OK;
+    }
+    if (!verdict.ok()) return fail(verdict.rc, verdict.why);
+    rc = merge_view_tie(&view_call.plan.layout, largest, &view_call.plan.seg_bytes);
+    if (rc) return rc;
+    rc = merge_view_check_groups(merged.size() / (size_t)geo.rec_words);
+    if (rc) return rc;
+    std::vector<unsigned long long> recs;
+    uint64_t n_view = 0, kept = 0;
+    merge_view_of_host_records(view_call, geo, merged, recs, &n_view, &kept);
+    uint32_t unpacked = 0;
+    unpack_wide(recs, sp, geo, key_bytes_out, first, counts, vals, str_out, max_groups, &unpacked, true);
+    *n_groups = (uint32_t)n_view;
+    if (n_kept) *n_kept = kept;
     return IMM3_OK;
 }

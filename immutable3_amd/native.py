@@ -31,6 +31,9 @@ EXPR_AND, EXPR_OR, EXPR_NOT = -1, -2, -4
 EXPR_FORM_TILE, EXPR_FORM_GENERIC = 0, 1
 # how every "this tree does not fit a table" refusal of the _table_expr entry points begins (include/imm3.h: IMM3_TABLE_TREE_REFUSED)
 TABLE_TREE_REFUSED = "a select tree over a table takes "
+# how every "this view does not fit the device's order" refusal of imm3_comm_merge_groups_view begins (include/imm3.h:
+# IMM3_MERGE_VIEW_REFUSED): the caller merges with merge_groups_wide and orders on the host
+MERGE_VIEW_REFUSED = "a view of merged groups takes "
 
 OK = 0
 ERR_UNSUPPORTED_CONDITION, ERR_UNSUPPORTED_VECTOR, ERR_NO_CODEC, ERR_LAYOUT, ERR_ARG, ERR_DEVICE, ERR_STATE = 1, 2, 3, 4, 5, 6, 7
@@ -54,6 +57,7 @@ EXPORTS = [
     "imm3_comm_unique_id", "imm3_comm_create", "imm3_comm_create_all", "imm3_comm_destroy", "imm3_comm_info",
     "imm3_comm_sync", "imm3_comm_join", "imm3_comm_allreduce_u64", "imm3_comm_allreduce_count", "imm3_comm_allreduce_count_all", "imm3_comm_merge_groups", "imm3_comm_merge_groups_all",
     "imm3_comm_merge_groups_wide", "imm3_comm_merge_groups_wide_all", "imm3_comm_merge_ordered", "imm3_comm_merge_ordered_all",
+    "imm3_comm_merge_groups_view", "imm3_comm_merge_groups_view_all",
     "imm3_pfor_encode_bound", "imm3_pfor_encode_block", "imm3_pfor_encode_column",
     "imm3_snappy_encode_bound", "imm3_snappy_encode_block",
 ]
@@ -64,7 +68,7 @@ DIAG_EXPORTS = [
     "imm3_ctx_inject_fault", "imm3_ctx_debug_device_lock", "imm3_plan_predict", "imm3_comm_debug_standin", "imm3_plan_limit_scan",
     "imm3_plan_table_limit", "imm3_plan_string_route", "imm3_plan_string_range_route", "imm3_plan_limit_chunks",
     "imm3_query_agg_form", "imm3_query_expr_form", "imm3_expr_normalize", "imm3_query_group_order_path",
-    "imm3_query_group_filter_stats", "imm3_group_filter_check",
+    "imm3_query_group_filter_stats", "imm3_group_filter_check", "imm3_comm_merge_view_path", "imm3_merge_view_plan_json",
 ]
 COMM_ID_BYTES = 128
 # imm3_query_device_ptr ids of an ordered query's arrays (include/imm3.h)
@@ -72,6 +76,7 @@ PTR_ORDER_ROW_INDEX, PTR_ORDER_ROW_COUNT, PTR_ORDER_COLUMN = 0x1000, 0x1001, 0x2
 # ORDER BY over groups (include/imm3.h: imm3_query_set_group_order; include/imm3_diag.h: imm3_query_group_order_path)
 GROUP_ORDER_GROUP_COL, GROUP_ORDER_AGG = 0, 1
 GROUP_ORDER_KEY_MAX_WIDTH = 12
+ORDER_MAX_KEYS = 4             # IMM3_ORDER_MAX_KEYS: keys of an order, of rows and of groups alike
 GROUP_ORDER_NONE, GROUP_ORDER_SMALL, GROUP_ORDER_RADIX_FULL, GROUP_ORDER_RADIX_SELECT = 0, 1, 2, 3
 GROUP_ORDER_SMALL_MAX = 2048   # groups the one-work-group launch takes (csrc/imm3_internal.h: kGroupOrderSmall)
 # HAVING (include/imm3.h: imm3_query_set_group_filter): a leaf's `agg` for the group's selected-row count; the leaf record
@@ -137,6 +142,43 @@ class CSelect(C.Structure):
         ("match_lens", C.c_void_p),
         ("n_match", C.c_int32),
     ]
+
+
+class CGroupView(C.Structure):
+    """imm3_group_view (include/imm3.h): a view of merged groups -- filter, then order, then limit"""
+    _fields_ = [
+        ("order", C.c_void_p),
+        ("n_order", C.c_int32),
+        ("leaves", C.c_void_p),
+        ("n_leaves", C.c_int32),
+        ("prog", C.c_void_p),
+        ("n_prog", C.c_int32),
+        ("limit", C.c_int64),
+    ]
+
+
+def group_view(order: Sequence[tuple] = (), leaves: Sequence[tuple] = (), prog: Sequence[int] = (), limit: int = 0):
+    """(CGroupView, the arrays it points into -- keep them alive as long as the view): order as set_group_order's keys, leaves / prog
+    as set_group_filter's"""
+    ks = np.array([[int(k), int(i), 1 if d else 0] for (k, i, d) in order] or [[0, 0, 0]], dtype=np.int32)
+    ls, pg = group_filter_arrays(leaves, prog)
+    v = CGroupView(ks.ctypes.data, len(order), ls.ctypes.data, len(leaves), pg.ctypes.data, len(prog), int(limit))
+    return v, (ks, ls, pg)
+
+
+def merge_view_plan(group_kinds: Sequence[int], group_widths: Sequence[int], agg_kinds: Sequence[int], agg_col_kinds: Sequence[int], agg_col_widths: Sequence[int],
+                    largest_segment_index: int, order: Sequence[tuple] = (), leaves: Sequence[tuple] = (), prog: Sequence[int] = (), limit: int = 0) -> dict:
+    """imm3_merge_view_plan_json (include/imm3_diag.h): the host-only plan of a view of merged groups on plain values, no device --
+    {"seg_bytes", "user_bytes", "key_bytes", "canonical_bytes", "hash"}.  Column kinds: 0 = int32, 1 = int8, 2 = string.  Raises
+    Imm3Error as imm3_comm_merge_groups_view would (a bad key or leaf; the refusal that begins with MERGE_VIEW_REFUSED)."""
+    import json
+    arrs = [np.array(list(a) or [0], dtype=np.int32) for a in (group_kinds, group_widths, agg_kinds, agg_col_kinds, agg_col_widths)]
+    v, keep = group_view(order, leaves, prog, limit)
+    buf = C.create_string_buffer(512)
+    _check(load().imm3_merge_view_plan_json(len(group_kinds), arrs[0].ctypes.data, arrs[1].ctypes.data, len(agg_kinds), arrs[2].ctypes.data, arrs[3].ctypes.data,
+                                            arrs[4].ctypes.data, C.byref(v), int(largest_segment_index), buf, 512, None))
+    del keep
+    return json.loads(buf.value.decode())
 
 
 _lib = None
@@ -259,6 +301,10 @@ def load() -> C.CDLL:
     L.imm3_comm_merge_groups_all.argtypes = [P(vp), i32, P(P(vp)), P(vp), P(i32), vp, vp, vp, vp, C.c_uint32, P(C.c_uint32)]
     L.imm3_comm_merge_groups_wide.argtypes = [vp, P(vp), vp, i32, vp, vp, vp, vp, P(vp), C.c_uint32, P(C.c_uint32)]
     L.imm3_comm_merge_groups_wide_all.argtypes = [P(vp), i32, P(P(vp)), P(vp), P(i32), vp, vp, vp, vp, P(vp), C.c_uint32, P(C.c_uint32)]
+    L.imm3_comm_merge_groups_view.argtypes = [vp, P(vp), vp, i32, P(CGroupView), vp, vp, vp, vp, P(vp), C.c_uint32, P(C.c_uint32), P(u64)]
+    L.imm3_comm_merge_groups_view_all.argtypes = [P(vp), i32, P(P(vp)), P(vp), P(i32), P(CGroupView), vp, vp, vp, vp, P(vp), C.c_uint32, P(C.c_uint32), P(u64)]
+    L.imm3_comm_merge_view_path.argtypes = [vp, P(i32)]
+    L.imm3_merge_view_plan_json.argtypes = [i32, vp, vp, i32, vp, vp, vp, P(CGroupView), C.c_uint32, vp, i64, P(i64)]
     L.imm3_comm_merge_ordered.argtypes = [vp, P(vp), vp, i32, i64, vp, vp, P(vp), u64, P(u64)]
     L.imm3_comm_merge_ordered_all.argtypes = [P(vp), i32, P(P(vp)), P(vp), P(i32), i64, vp, vp, P(vp), u64, P(u64)]
     for name in EXPORTS + DIAG_EXPORTS:
@@ -1040,6 +1086,62 @@ class Comm:
         _check(load().imm3_comm_merge_groups_wide_all(carr, n, qq, ss, nq, keys.ctypes.data, first.ctypes.data, counts.ctypes.data, vals.ctypes.data,
                                                       ptrs, m, C.byref(g)))
         return keys[:m, :kb], first[:m], counts[:m], vals[:m, :na], {j: b[:m] for j, b in strs.items()}
+
+    def merge_groups_view(self, queries: Sequence["DeviceQuery"], segment_index: Sequence[int], order: Sequence[tuple] = (), leaves: Sequence[tuple] = (),
+                          prog: Sequence[int] = (), limit: int = 0, max_groups: Optional[int] = None):
+        """A view of the merged groups (imm3_comm_merge_groups_view): merge_groups_wide's merge, then filter (leaves / prog as
+        set_group_filter's), then order (keys as set_group_order's), then limit, all on the device -- only the view's groups come
+        back: (key_bytes, first, counts, vals, {j: string bytes}, n_kept) in the view's order, n_kept = the groups the filter kept
+        before the limit.  With a limit (or max_groups) the call is made once, sized by it; else once for the count and once for the
+        groups.  Imm3Error(ERR_ARG) whose message begins with MERGE_VIEW_REFUSED: the keys and the tie do not fit the device's order
+        -- merge_groups_wide and the host's order are the way then."""
+        qs = (C.c_void_p * max(1, len(queries)))(*[q._h for q in queries])
+        seg = np.ascontiguousarray(segment_index, dtype=np.int32)
+        view, keep = group_view(order, leaves, prog, limit)
+        n, kept = C.c_uint32(0), C.c_uint64(0)
+        cap = max_groups if max_groups is not None else (int(limit) if limit > 0 else None)
+        if cap is None:
+            _check(load().imm3_comm_merge_groups_view(self._h, qs, seg.ctypes.data, len(queries), C.byref(view), None, None, None, None, None, 0, C.byref(n), C.byref(kept)))
+            cap = n.value
+        keys, first, counts, vals, strs, ptrs, na, kb = self._wide_buffers(queries[0], cap)
+        _check(load().imm3_comm_merge_groups_view(self._h, qs, seg.ctypes.data, len(queries), C.byref(view), keys.ctypes.data, first.ctypes.data, counts.ctypes.data,
+                                                  vals.ctypes.data, ptrs, cap, C.byref(n), C.byref(kept)))
+        del keep
+        g = min(n.value, cap)
+        return keys[:g, :kb], first[:g], counts[:g], vals[:g, :na], {j: b[:g] for j, b in strs.items()}, kept.value
+
+    @staticmethod
+    def merge_groups_view_all(comms: Sequence["Comm"], queries_per_comm: Sequence[Sequence["DeviceQuery"]], segments_per_comm: Sequence[Sequence[int]],
+                              order: Sequence[tuple] = (), leaves: Sequence[tuple] = (), prog: Sequence[int] = (), limit: int = 0):
+        """Single-process flavour of merge_groups_view (communicators as for merge_groups_wide_all): the merge finishes on the host,
+        and so does the view, under the same rule.  Returns what merge_groups_view returns."""
+        n = len(comms)
+        carr = (C.c_void_p * n)(*[c._h for c in comms])
+        qarrs = [(C.c_void_p * max(1, len(qs)))(*[q._h for q in qs]) for qs in queries_per_comm]
+        qq = (C.POINTER(C.c_void_p) * n)(*[C.cast(a, C.POINTER(C.c_void_p)) for a in qarrs])
+        segs = [np.ascontiguousarray(s, dtype=np.int32) for s in segments_per_comm]
+        ss = (C.c_void_p * n)(*[s.ctypes.data if s.size else None for s in segs])
+        nq = (C.c_int32 * n)(*[len(qs) for qs in queries_per_comm])
+        q0 = next(q for qs in queries_per_comm for q in qs)
+        view, keep = group_view(order, leaves, prog, limit)
+        g, kept = C.c_uint32(0), C.c_uint64(0)
+        cap = int(limit) if limit > 0 else None
+        if cap is None:
+            _check(load().imm3_comm_merge_groups_view_all(carr, n, qq, ss, nq, C.byref(view), None, None, None, None, None, 0, C.byref(g), C.byref(kept)))
+            cap = g.value
+        keys, first, counts, vals, strs, ptrs, na, kb = Comm._wide_buffers(q0, cap)
+        _check(load().imm3_comm_merge_groups_view_all(carr, n, qq, ss, nq, C.byref(view), keys.ctypes.data, first.ctypes.data, counts.ctypes.data, vals.ctypes.data,
+                                                      ptrs, cap, C.byref(g), C.byref(kept)))
+        del keep
+        m = min(g.value, cap)
+        return keys[:m, :kb], first[:m], counts[:m], vals[:m, :na], {j: b[:m] for j, b in strs.items()}, kept.value
+
+    def merge_view_path(self) -> int:
+        """The path the last merge_groups_view on this communicator took: GROUP_ORDER_NONE / _SMALL / _RADIX_FULL / _RADIX_SELECT
+        (include/imm3_diag.h: imm3_comm_merge_view_path)."""
+        p = C.c_int32(0)
+        _check(load().imm3_comm_merge_view_path(self._h, C.byref(p)))
+        return p.value
 
     @staticmethod
     def _flat_segments(segment_index) -> np.ndarray:

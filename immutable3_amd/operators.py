@@ -905,6 +905,20 @@ class ProjectAggOp(Operator):
         return [(native.GROUP_ORDER_AGG, aliases.index(name), desc) if is_agg else (native.GROUP_ORDER_GROUP_COL, gnames.index(name), desc)
                 for (is_agg, name, desc) in self.order_spec]
 
+    def _order_key_bytes(self, cols) -> int:
+        """the bytes order_spec's keys take in the device's normal form (include/imm3.h: imm3_query_set_group_order): a group column its
+        width, COUNT 5, SUM 8, MIN / MAX its column's width"""
+        by_name = {c.name: c for c in cols}
+        by_alias = {a.alias: a for a in self._shape(list(cols))[2]}
+        total = 0
+        for (is_agg, name, _) in self.order_spec:
+            if not is_agg:
+                total += by_name[name].width
+            else:
+                a = by_alias[name]
+                total += 5 if a.kind == native.AGG_COUNT else 8 if a.kind == native.AGG_SUM else by_name[a.col].width
+        return total
+
     def _native_filter(self, cols):
         """filter_leaves as imm3_query_set_group_filter's leaves: places in the native aggs list of _open"""
         aliases = [a.alias for a in self._shape(list(cols))[2]]
@@ -1057,6 +1071,9 @@ class Engine:
         self.honour_and_or = honour_and_or
         self.device_merge = device_merge
         self.honour_not_match = honour_not_match
+        # who applied having / order by / limit to the groups of the last device merge: "device" (imm3_comm_merge_groups_view), "host"
+        # (the library refused the view: plain merge, ordered here), None (no such clause, or no device merge yet)
+        self.last_merge_view = None
 
     def _not_tree(self, query: Query) -> bool:
         return self.honour_not_match and has_not_match(query.select)
@@ -1187,6 +1204,7 @@ class Engine:
         queries: Dict[int, list] = {}          # by index of the segment's context
         seg_ids: Dict[int, list] = {}
         agg_op = None
+        self.last_merge_view = None
         try:
             for segIdx in range(self.sm.getTableSegmentCount(table.name)):
                 if not self.sm.owns(table.name, segIdx):
@@ -1201,23 +1219,49 @@ class Engine:
             if agg_op is None:
                 return {}
             order = sorted(queries)
+            # having / order by / limit: the view of the merged groups comes from the merge itself (imm3_comm_merge_groups_view), in
+            # its order and cut to its limit -- unless the library refuses the view (keys and tie beyond the order's 16 bytes): then
+            # the plain merge, ordered on the host as before
+            view = None
+            if agg_op._order_key_bytes(used) > native.GROUP_ORDER_KEY_MAX_WIDTH or len(agg_op.order_spec) > native.ORDER_MAX_KEYS:
+                # no device order takes such keys (imm3.h: four keys, 12 bytes): the host's does
+                self.last_merge_view = "host"
+            elif agg_op.filter_prog or agg_op.order_spec or agg_op.limit > 0:
+                view = dict(order=agg_op._native_order(used), leaves=agg_op._native_filter(used), prog=agg_op.filter_prog, limit=max(agg_op.limit, 0))
             if len(order) == 1:
                 comm = native.Comm(self.sm.ctxs[order[0]], 1, 0, native.comm_unique_id())
-                try:
-                    key_bytes, _, counts, vals, strs = comm.merge_groups_wide(queries[order[0]], seg_ids[order[0]])
-                finally:
-                    comm.close()
+                merges = (lambda: comm.merge_groups_view(queries[order[0]], seg_ids[order[0]], **view),
+                          lambda: comm.merge_groups_wide(queries[order[0]], seg_ids[order[0]]), comm.close)
             else:
                 # several contexts: each one's world-of-one communicator (the _all merges use a communicator's context only).  Not
                 # Comm.create_all: that is one context per DEVICE, and a manager may hold several contexts on one device.
                 comms = [self.sm.merge_comm(ci) for ci in order]
-                key_bytes, _, counts, vals, strs = native.Comm.merge_groups_wide_all(comms, [queries[ci] for ci in order], [seg_ids[ci] for ci in order])
+                per_comm = ([queries[ci] for ci in order], [seg_ids[ci] for ci in order])
+                merges = (lambda: native.Comm.merge_groups_view_all(comms, *per_comm, **view), lambda: native.Comm.merge_groups_wide_all(comms, *per_comm), lambda: None)
+            try:
+                merged = None
+                if view is not None:
+                    try:
+                        merged = merges[0]()
+                        self.last_merge_view = "device"
+                    except native.Imm3Error as e:
+                        if not (e.code == native.ERR_ARG and e.msg.startswith(native.MERGE_VIEW_REFUSED)):
+                            raise
+                        self.last_merge_view = "host"
+                if merged is None:
+                    merged = merges[1]()
+            finally:
+                merges[2]()
+            key_bytes, _, counts, vals, strs = merged[:5]
         finally:
             for qs in queries.values():
                 for q in qs:
                     q.close()
         wide = {j: strs[j] for j in agg_op._shape(list(used))[5]}
-        return self._order_merged(dict(agg_op._groups(used, None, key_bytes, counts, vals, wide)), agg_op.raw_keys, used, agg_op)
+        groups = dict(agg_op._groups(used, None, key_bytes, counts, vals, wide))
+        if self.last_merge_view == "device":         # already the view: decoded in the order it arrived
+            return groups
+        return self._order_merged(groups, agg_op.raw_keys, used, agg_op)
 
     def execute_table_columns(self, query: Query):
         """Project query over the whole table as ONE fused launch: (segment uint32[n], row uint32[n], [column arrays])

@@ -458,7 +458,8 @@ int imm3_query_set_order(imm3_query *q, const imm3_order_key *keys, int32_t n_ke
  * imm3_comm_merge_groups* read the group tables and ignore the order.
  * Errors (IMM3_ERR_ARG, the message names the cause): not an aggregation query, n_keys outside 0 .. 4, an unknown kind, an index out
  * of range, the same (kind, index) twice, key bytes above 12 (a 16-byte group column cannot be a key).
- * OUT OF SCOPE: ordering merged results (imm3_comm_merge_groups*) on the device, ordering by an average, key bytes beyond 12. ---- */
+ * Merged results are ordered on the device by imm3_comm_merge_groups_view.
+ * OUT OF SCOPE: ordering by an average, key bytes beyond 12. ---- */
 enum { IMM3_GROUP_ORDER_GROUP_COL = 0, IMM3_GROUP_ORDER_AGG = 1 };
 typedef struct { int32_t kind; int32_t index; int32_t descending; } imm3_group_order_key;
 #define IMM3_GROUP_ORDER_KEY_MAX_WIDTH 12
@@ -486,7 +487,7 @@ int imm3_query_set_group_order(imm3_query *q, const imm3_group_order_key *keys, 
  * 0 .. 32 or 0 with leaves given, a malformed program, agg out of range, a MAX over a STRING column, average on anything but a SUM or
  * with a value outside [-2^31, 2^31 - 1], an unknown cond.
  * OUT OF SCOPE: leaves on group columns (that is the select's job), leaves on string MAX values, non-integer thresholds, aggregates
- * that are not in the query's aggs, filtering merged results (imm3_comm_merge_groups*) on the device, JNI / Scala bindings. ---- */
+ * that are not in the query's aggs, JNI / Scala bindings (merged results are filtered on the device by imm3_comm_merge_groups_view). ---- */
 #define IMM3_GROUP_FILTER_MAX_LEAVES 8
 #define IMM3_GROUP_FILTER_MAX_PROG   32
 #define IMM3_GROUP_FILTER_COUNT      (-1)
@@ -664,6 +665,48 @@ int imm3_comm_merge_groups_wide_all(imm3_comm *const *comms, int32_t n_comms, im
                                     const int32_t *const *segment_index, const int32_t *n_queries,
                                     uint8_t *key_bytes_out, uint64_t *first, uint64_t *counts, int64_t *vals,
                                     uint8_t *const *str_out, uint32_t max_groups, uint32_t *n_groups);
+
+/* ---- multi-GPU: a VIEW of the merged groups ("Views of merged groups"):
+ * `select count(id) from t group by name having id_count > 1000 order by id_count desc limit 10` when several queries -- segments
+ * sharded over ranks, several contexts, a table mixed with segments -- bring the groups.  The merge of imm3_comm_merge_groups_wide,
+ * unchanged, then FILTER, then ORDER, then LIMIT over its merged list on the device: only the groups of the view cross to the host.
+ * Queries, segment_index, the output arrays and their packing are imm3_comm_merge_groups_wide's.
+ *   view->order    0 .. IMM3_ORDER_MAX_KEYS keys under the rule of imm3_query_set_group_order (kinds, normal form, user bytes <=
+ *                  IMM3_GROUP_ORDER_KEY_MAX_WIDTH; an average is no key), checked against queries[0]'s shape.  n_order == 0: first-arrival
+ *                  order, ascending `first`.  A COUNT key stays 5 bytes: merged counts of 2^40 or more are outside the contract.
+ *   view->leaves / prog   the rule of imm3_query_set_group_filter; n_prog == 0: every group is kept.  Leaves compare in 128 bits, so an
+ *                  `average` leaf (sum <cond> value * count) is exact for merged counts of 2^32 and more.
+ *   view->limit    > 0: the first `limit` groups of the order (of first arrival without one); <= 0: none.  Every value is accepted.
+ *   *n_groups      min(groups kept, limit): the groups of the view, reported even when max_groups is smaller; max_groups of them are written
+ *   *n_kept        (may be NULL) the groups the filter kept, before the limit
+ * TIES: groups whose user keys are all equal come in ascending `first` (segment << 32 | first row), the arrival order of the merge.
+ * The order's key is 16 bytes, so the tie takes 4 bytes of row plus S bytes of segment, S = the bytes the largest segment_index entry
+ * of ANY rank needs (0 when it is 0, 1 up to 255, 2 up to 65535, 3, 4).  A view with user bytes + 4 + S > 16, or with more than 2^30
+ * merged groups, is REFUSED: IMM3_ERR_ARG with a message that begins with IMM3_MERGE_VIEW_REFUSED (part of the contract), on every rank
+ * in the same call, before any list is exchanged.  A caller that sees the prefix calls imm3_comm_merge_groups_wide and orders on the
+ * host.  Any other IMM3_ERR_ARG is an argument error: a null view, a bad key or leaf (the messages of the two setters), the errors of
+ * imm3_comm_merge_groups_wide; IMM3_ERR_STATE: a query that has not been run.  All ranks must bring the same view: ranks whose views
+ * differ (keys, program, limit) all get IMM3_ERR_ARG "the ranks' views of the merged groups differ ...".  Every such error reaches
+ * every rank before the first exchange of lists: no rank is left waiting, and the communicator stays usable.
+ * An empty view (no order, no filter, no limit) gives imm3_comm_merge_groups_wide's result byte for byte.  Synchronous.
+ * OUT OF SCOPE: ordering by an average, more than 12 user key bytes, views through imm3_comm_merge_groups (this entry accepts every
+ * query that one does). ---- */
+typedef struct {
+    const imm3_group_order_key *order; int32_t n_order;            /* 0: first-arrival order (ascending `first`) */
+    const imm3_group_filter_leaf *leaves; int32_t n_leaves;
+    const int32_t *prog; int32_t n_prog;                           /* 0: every group is kept */
+    int64_t limit;                                                 /* <= 0: none */
+} imm3_group_view;
+#define IMM3_MERGE_VIEW_REFUSED "a view of merged groups takes "
+int imm3_comm_merge_groups_view(imm3_comm *c, imm3_query *const *queries, const int32_t *segment_index, int32_t n_queries,
+                                const imm3_group_view *view, uint8_t *key_bytes_out, uint64_t *first, uint64_t *counts, int64_t *vals,
+                                uint8_t *const *str_out, uint32_t max_groups, uint32_t *n_groups, uint64_t *n_kept);
+/* Single-process flavour (communicators as for imm3_comm_merge_groups_all).  imm3_comm_merge_groups_wide_all finishes its merge on the
+ * host, and so does this: the view is computed ON THE HOST, under the same rule (same keys, ties, refusals and results). */
+int imm3_comm_merge_groups_view_all(imm3_comm *const *comms, int32_t n_comms, imm3_query *const *const *queries,
+                                    const int32_t *const *segment_index, const int32_t *n_queries, const imm3_group_view *view,
+                                    uint8_t *key_bytes_out, uint64_t *first, uint64_t *counts, int64_t *vals,
+                                    uint8_t *const *str_out, uint32_t max_groups, uint32_t *n_groups, uint64_t *n_kept);
 
 /* ---- multi-GPU: the merge of ORDERED results ("Merging ordered results").  Every rank brings the ordered
  * projecting queries of its own segments (at least one): each has had imm3_query_set_order called and has been run on the

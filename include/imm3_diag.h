@@ -19,7 +19,9 @@ extern "C" {
  *             5 = PFOR_INT / snappy column decode, 6 = refine pass of a MAX over a string wider than 8 bytes (one per pass),
  *             7 = ORDER BY of an ordered query: ONE record per order, from its first kernel's start to its last one's end,
  *             8 = ORDER BY over groups (imm3_query_set_group_order): ONE record per ordered settle, from the small launch's start (or
- *                 the radix path's key launch's) to the end of the launch that writes the ordered groups. */
+ *                 the radix path's key launch's) to the end of the launch that writes the ordered groups,
+ *             9 = a view of merged groups (imm3_comm_merge_groups_view): ONE record per view, from the small launch's start (or the
+ *                 radix path's key launch's) to the end of the launch that writes the ordered records. */
 int imm3_ctx_timing_enable(imm3_ctx *ctx, int32_t max_records);
 int imm3_ctx_timing_reset(imm3_ctx *ctx);
 /* Only launches whose kernel id has its bit set in `kernel_mask` are bracketed (default: all). */
@@ -98,6 +100,21 @@ int imm3_query_agg_form(const imm3_query *q, int32_t *form);
  * (0 < limit, groups >= 4 x limit).  IMM3_ERR_ARG for a query that is not an aggregation. */
 #define IMM3_GROUP_ORDER_SMALL_MAX 2048
 int imm3_query_group_order_path(const imm3_query *q, int32_t *path);
+
+/* imm3_comm_merge_view_path: the path the last imm3_comm_merge_groups_view on this communicator took, with the values above: 0 = none
+ * (no view yet, a failed call, or an empty merged list), 1 = the one-work-group launch (up to 2048 merged groups), 2 = the radix path
+ * sorting every kept group, 3 = the radix path with the radix select in front. */
+int imm3_comm_merge_view_path(const imm3_comm *c, int32_t *path);
+
+/* imm3_merge_view_plan_json: the host-only plan of a view of merged groups, without a device or a handle.  The aggregation's shape
+ * is given as plain values (column kinds: 0 = int32, 1 = int8, 2 = string); json_out receives, NUL-terminated,
+ *   {"seg_bytes":S,"user_bytes":U,"key_bytes":U+S+4,"canonical_bytes":N,"hash":"<16 hex digits>"}
+ * -- S the tie's segment bytes for `largest_segment_index`, the hash that of the canonical bytes (keys, program, limit) the ranks vote
+ * on.  `needed` (may be NULL) the bytes that takes; cap = 0 only asks for `needed`.  Errors as imm3_comm_merge_groups_view's: a bad key
+ * or leaf, or the refusal that begins with IMM3_MERGE_VIEW_REFUSED. */
+int imm3_merge_view_plan_json(int32_t n_group, const int32_t *group_kind, const int32_t *group_width, int32_t n_aggs, const int32_t *agg_kind,
+                              const int32_t *agg_col_kind, const int32_t *agg_col_width, const imm3_group_view *view, uint32_t largest_segment_index,
+                              char *json_out, int64_t cap, int64_t *needed);
 
 /* imm3_query_group_filter_stats: what the device's filter did in the last settled view of an aggregation with a filter set
  * (imm3_query_set_group_filter): *groups_in = the dense groups it evaluated, *groups_kept = those the program kept (before the limit),
