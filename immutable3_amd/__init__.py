@@ -8,7 +8,7 @@ schema.py, query.py   Column / Table / Row and the Query ADT
 sql.py       SQLParser: the reference's SQL subset (the mirror of host/sql.hpp), `order by` behind a flag
 synth.py     seeded synthetic tables of BASELINE.json's configs
 """
-from .query import (EQ, GT, LT, And, Avg, Count, Match, Max, Min, NoOp, NoSelect, NotMatch, Or, Project,  # noqa: F401
+from .query import (EQ, GT, LT, And, Avg, Count, CountDistinct, Match, Max, Min, NoOp, NoSelect, NotMatch, Or, Project,  # noqa: F401
                     ProjectAgg, Query, Select, Sum)
 from .schema import CodecType, Column, ColumnType, Row, Table, TableIO  # noqa: F401
 

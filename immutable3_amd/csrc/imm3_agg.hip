@@ -136,7 +136,7 @@ __device__ __forceinline__ GroupRef agg_locate(const AggArgs &a, const LdsTable 
 // fold value v of aggregate j into the row's group
 __device__ __forceinline__ void agg_fold(const AggArgs &a, const LdsTable &t, const GroupRef &r, int j, long long v) {
     const int kind = a.aggs[j].kind;
-    if (kind == AGG_COUNT) return;
+    if (kind == AGG_COUNT || kind == AGG_COUNT_DISTINCT) return; // (COUNT_DISTINCT: k_distinct_mark's, behind this launch)
     const bool str = a.aggs[j].is_str;
     if (r.slot >= 0) {
         long long *p = &t.vals[r.slot * kMaxAggs + j];
@@ -452,7 +452,7 @@ __global__ __launch_bounds__(kAggThreads) void k_group_agg(const AggArgs a) {
             }
             // then every aggregate column: one load for the 4 rows, fold, next column
             for (int q = 0; q < a.n_agg; ++q) {
-                if (a.aggs[q].kind == AGG_COUNT) continue;
+                if (a.aggs[q].kind == AGG_COUNT || a.aggs[q].kind == AGG_COUNT_DISTINCT) continue;
                 if (WIDE && a.aggs[q].alive) {
                     const int wd = a.aggs[q].width;
                     uint32_t cand = 0; // bit k: row0 + k may hold its group's maximum
@@ -1538,7 +1538,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_group_init(const AggArgs a) {
         for (int j = 0; j < kMaxAggs; ++j) {
             const int kind = j < a.n_agg ? a.aggs[j].kind : AGG_COUNT;
             const bool str = j < a.n_agg && a.aggs[j].is_str;
-            a.vals[(size_t)i * kMaxAggs + j] = kind == AGG_MIN ? INT64_MAX : ((str || kind == AGG_SUM) ? 0 : INT64_MIN);
+            a.vals[(size_t)i * kMaxAggs + j] = kind == AGG_MIN ? INT64_MAX : ((str || kind == AGG_SUM || kind == AGG_COUNT_DISTINCT) ? 0 : INT64_MIN);
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -1559,6 +1559,7 @@ bool group_agg_fast_ok(const AggArgs &a) {
     if (key_bytes > 4) return false;
     for (int q = 0; q < a.n_agg; ++q) {
         if (a.aggs[q].tile_ptrs) return false;
+        if (a.aggs[q].kind == AGG_COUNT_DISTINCT) return false; // (k_distinct_mark reads the general form's table: find_slot)
         if (a.aggs[q].kind == AGG_COUNT) continue;
         const int w = a.aggs[q].width;
         if (a.aggs[q].is_str ? (w != 1 && w != 2 && w != 4) : (w != 1 && w != 4)) return false;
@@ -1812,6 +1813,79 @@ void launch_strmax_collect(const AggArgs &a, int j, uint32_t n_groups, uint8_t *
     const int grid = (int)std::max<uint32_t>(1u, std::min<uint32_t>((n_groups + kBlockThreads - 1) / kBlockThreads, 256u));
     if (a.wide_key) hipLaunchKernelGGL(k_strmax_collect<true>, dim3(grid), dim3(kBlockThreads), 0, s, a, j, n_groups, out);
     else hipLaunchKernelGGL(k_strmax_collect<false>, dim3(grid), dim3(kBlockThreads), 0, s, a, j, n_groups, out);
+}
+
+// ---- COUNT(DISTINCT): the pair set (AggCol::dset) ----
+// Aggregate j's walk of the select bitmap, behind the aggregation launch (the general form: its table is what find_slot reads).  The
+// walk is k_strmax_refine's: a lane reads one bitmap word of 64, the wave skips the zero words with one ballot, then takes the others
+// one at a time, a lane per row.  A selected row's entry, slot << 32 | its value's raw bytes (1 .. 4 of them, little-endian), is
+// hashed and probed linearly; the lane whose compare-and-swap claims an empty place is the pair's first arrival and adds 1 to the
+// group's figure.  A row whose key has no slot (an overflowed table: the host reports it) is skipped.
+// The PLAIN READ in front of the compare-and-swap: within one launch a place goes from empty to its final entry exactly once (the
+// clear is an earlier operation on the stream, and nothing ever empties or rewrites a place).  The XCDs' L2s are not coherent and a
+// vector L1 is never refreshed by another CU's stores, so the read may be stale -- but a stale read can only show the EARLIER state,
+// "empty", and then the compare-and-swap (performed at the memory side, on the current value) settles it; a non-empty read is the
+// place's final entry, whoever wrote it.  Neither outcome can count a pair twice or miss one.
+// The table holds at most half its entries (imm3_distinct_plan.h), so a probe always meets an empty place or its own entry.
+// distinct_mark_row: one selected row (lane <-> row of bitmap word wi)
+template <bool KEYW>
+__device__ __forceinline__ void distinct_mark_row(const AggArgs &a, const AggCol &c, const int j, const int64_t wi, const int lane) {
+    const int wd = c.width;
+    const int64_t row = a.word_row_base ? (int64_t)a.word_row_base[wi] + lane : wi * 64 + lane;
+    uint32_t g;
+    if constexpr (KEYW) g = find_slot_row_wide(a, row);
+    else {
+        unsigned long long key = 0;
+        for (int q = 0; q < a.n_group; ++q) {
+            const uint8_t *kp = row_ptr(a.groups[q].data, a.groups[q].tile_ptrs, row, a.groups[q].width);
+            unsigned long long v = 0;
+            for (int x = 0; x < a.groups[q].width; ++x) v |= (unsigned long long)kp[x] << (8 * x);
+            key |= v << (8 * a.groups[q].shift);
+        }
+        g = find_slot(a, key);
+    }
+    if (g == 0xFFFFFFFFu) return;
+    const uint8_t *p = row_ptr(c.data, c.tile_ptrs, row, wd);
+    uint32_t v = 0;
+    if (wd == 4) v = *(const uint32_t *)p;
+    else
+        for (int x = 0; x < wd; ++x) v |= (uint32_t)p[x] << (8 * x);
+    const unsigned long long entry = ((unsigned long long)g << 32) | v;
+    uint32_t at = hash_key(entry) & c.dset_mask;
+    for (uint32_t probes = 0; probes <= c.dset_mask; ++probes) {
+        unsigned long long cur = c.dset[at]; // (plain: see above)
+        if (cur == kEmptyKey) {
+            cur = atomicCAS(&c.dset[at], kEmptyKey, entry);
+            if (cur == kEmptyKey) { // this lane's is the pair's first arrival
+                atomicAdd((unsigned long long *)&a.vals[(size_t)g * kMaxAggs + j], 1ULL);
+                break;
+            }
+        }
+        if (cur == entry) break;
+        at = (at + 1) & c.dset_mask;
+    }
+}
+template <bool KEYW>
+__global__ __launch_bounds__(kBlockThreads) void k_distinct_mark(const AggArgs a, const int j) {
+    const AggCol &c = a.aggs[j];
+    const int lane = threadIdx.x & 63;
+    for (int64_t base = (int64_t)blockIdx.x * kBlockThreads + (threadIdx.x & ~63); base < a.n_words; base += (int64_t)gridDim.x * kBlockThreads) {
+        const uint64_t mine = base + lane < a.n_words ? a.bitmap[base + lane] : 0ULL;
+        uint64_t todo = ballot64(mine != 0ULL);
+        while (todo) { // wave-uniform
+            const int b = __builtin_ctzll(todo);
+            todo &= todo - 1ULL;
+            const int64_t wi = base + b;
+            const uint64_t word = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(mine >> 32), b) << 32) | (uint32_t)__shfl((int)(uint32_t)mine, b);
+            if ((word >> lane) & 1ULL) distinct_mark_row<KEYW>(a, c, j, wi, lane); // (all lanes meet again before the next shuffle)
+        }
+    }
+}
+void launch_distinct_mark(const AggArgs &a, int j, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    const int64_t waves = (a.n_words + 63) / 64; // one bitmap word per lane
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + kBlockThreads / 64 - 1) / (kBlockThreads / 64), 2048));
+    if (a.wide_key) IMM3_LAUNCH(k_distinct_mark<true>, grid, kBlockThreads, s, ev0, ev1, a, j);
+    else IMM3_LAUNCH(k_distinct_mark<false>, grid, kBlockThreads, s, ev0, ev1, a, j);
 }
 
 // wide keys: every dense group's key bytes, read at its first row (any row of the group carries its key)

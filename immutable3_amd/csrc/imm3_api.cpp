@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "imm3_handles.h"
+#include "imm3_distinct_plan.h"
 #include "imm3_api_internal.h" // (shared with the run, imm3_run.cpp, and the planner, imm3_planner.cpp)
 
 using namespace imm3;
@@ -863,7 +864,7 @@ static void query_free(imm3_query *q) {
     pool_release(ctx, q->d_akeys); pool_release(ctx, q->d_acounts); pool_release(ctx, q->d_okeys); pool_release(ctx, q->d_ocounts);
     pool_release(ctx, q->d_afirst); pool_release(ctx, q->d_ofirst); pool_release(ctx, q->d_ameta);
     pool_release(ctx, q->d_avals); pool_release(ctx, q->d_ovals);
-    for (int j = 0; j < kMaxAggs; ++j) { pool_release(ctx, q->d_alive[j]); pool_release(ctx, q->d_chunks[j]); }
+    for (int j = 0; j < kMaxAggs; ++j) { pool_release(ctx, q->d_alive[j]); pool_release(ctx, q->d_chunks[j]); pool_release(ctx, q->d_dset[j]); }
     if (q->ev_filter_done) (void)hipEventDestroy(q->ev_filter_done);
     if (q->ev_total_done) (void)hipEventDestroy(q->ev_total_done);
     // the query kept its inputs alive (imm3_handles.h, "Lifetimes")
@@ -2007,12 +2008,22 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
     if (key_bytes > kGroupKeyMaxWidth)
         return fail(IMM3_ERR_ARG, "group key wider than " + std::to_string(kGroupKeyMaxWidth) + " bytes is not supported on the GPU path");
     const bool has_batches = table ? !table->batch_size.empty() : !q->layout->size.empty();
+    bool has_distinct = false;
     for (int32_t j = 0; j < n_aggs; ++j) {
         if (aggs[j].column < 0 || aggs[j].column >= n_used) return fail(IMM3_ERR_ARG, "aggregate column is not among the used columns");
         const SegCol &sc = seg->cols[(size_t)q->used[(size_t)aggs[j].column]];
         const bool is_str = sc.vcodec == IMM3_DENSE_STRING;
-        if (aggs[j].kind != IMM3_AGG_COUNT && aggs[j].kind != IMM3_AGG_MIN && aggs[j].kind != IMM3_AGG_MAX && aggs[j].kind != IMM3_AGG_SUM)
+        if (aggs[j].kind != IMM3_AGG_COUNT && aggs[j].kind != IMM3_AGG_MIN && aggs[j].kind != IMM3_AGG_MAX && aggs[j].kind != IMM3_AGG_SUM &&
+            aggs[j].kind != IMM3_AGG_COUNT_DISTINCT)
             return fail(IMM3_ERR_ARG, "Unknown Aggregate type");
+        if (aggs[j].kind == IMM3_AGG_COUNT_DISTINCT) {
+            // an entry of the pair set holds the value's raw bytes in 32 bits.  OUT OF SCOPE: values wider than 4 bytes
+            const bool ok = is_str ? (sc.width >= 1 && sc.width <= kDistinctMaxWidth) : (sc.width == 1 || sc.width == 4);
+            if (!ok)
+                return fail(IMM3_ERR_ARG, "COUNT_DISTINCT takes int32, int8 and string columns of at most " + std::to_string(kDistinctMaxWidth) +
+                                              " bytes on the GPU path (this column is " + std::to_string(sc.width) + " bytes wide)");
+            has_distinct = true;
+        }
         // ProjectAggregate.scala:176-220: a String vector only takes CountAggr / MaxStringAggr (AvgDoubleAggr's sum is numeric only)
         if (has_batches && is_str && (aggs[j].kind == IMM3_AGG_MIN || aggs[j].kind == IMM3_AGG_SUM)) return fail(IMM3_ERR_UNSUPPORTED_VECTOR, "bad aggregator for this data type");
         if (is_str && aggs[j].kind == IMM3_AGG_MAX && sc.width > kStrMaxWidth)
@@ -2025,7 +2036,8 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
     {   // SelectOp fused into the aggregation launch (k_group_agg_lanes' FUSED instances; whether the lanes form takes the query is
         // the launcher's call at run time)
         bool ok = !table && !q->ragged && !q->always_false && has_batches && q->n_rows > 0 && q->preds.size() <= (size_t)kMaxAggPreds &&
-                  !q->is_expr; // (a select tree's launch writes the bitmap, the aggregation reads it)
+                  !q->is_expr && // (a select tree's launch writes the bitmap, the aggregation reads it)
+                  !has_distinct; // (k_distinct_mark walks the bitmap; the fast forms decline the kind anyway: group_agg_fast_ok)
         for (const auto &fp : q->preds)
             ok = ok && !fp.pfor && (fp.kind == KIND_I8 || fp.kind == KIND_I32) && col_flat(seg->cols[(size_t)fp.seg_col]) != nullptr;
         q->agg_fusable = ok;
@@ -2050,6 +2062,15 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
         if (sc.vcodec != IMM3_DENSE_STRING || aggs[j].kind != IMM3_AGG_MAX || sc.width <= 8) continue;
         HIPCHK(pool_alloc(ctx, &p, (size_t)std::max<int64_t>(q->n_words, 1) * sizeof(uint64_t))); q->d_alive[j] = (uint64_t *)p;
         HIPCHK(pool_alloc(ctx, &p, (size_t)((sc.width + 7) / 8 - 1) * n * sizeof(unsigned long long))); q->d_chunks[j] = (unsigned long long *)p;
+    }
+    for (int32_t j = 0; j < n_aggs; ++j) { // COUNT_DISTINCT: the pair set, sized here once (imm3_distinct_plan.h)
+        if (aggs[j].kind != IMM3_AGG_COUNT_DISTINCT) continue;
+        const SegCol &sc = seg->cols[(size_t)q->used[(size_t)aggs[j].column]];
+        const int64_t entries = distinct_capacity(q->n_rows, key_bytes, sc.width);
+        if (entries < 0)
+            return fail(IMM3_ERR_ARG, "COUNT_DISTINCT: the pair set of this query would need more than 2^28 entries (2 GiB; more than 2^27 rows)");
+        HIPCHK(pool_alloc(ctx, &p, (size_t)entries * sizeof(unsigned long long))); q->d_dset[j] = (unsigned long long *)p;
+        q->dset_entries[j] = (uint64_t)entries;
     }
     *out = guard.release();
     return IMM3_OK;
@@ -2138,6 +2159,8 @@ static void fill_agg_args(const imm3_query *q, AggArgs &a) {
         a.aggs[j].is_str = sc.vcodec == IMM3_DENSE_STRING;
         a.aggs[j].chunks = q->d_chunks[j];
         a.aggs[j].alive = q->d_alive[j];
+        a.aggs[j].dset = q->d_dset[j];
+        a.aggs[j].dset_mask = q->d_dset[j] ? (uint32_t)(q->dset_entries[j] - 1) : 0u;
     }
     a.n_agg = (int32_t)q->aggs.size();
     if (q->agg_fusable && q->ctx->filter_variant != TV_AGG_SELECT_LAUNCH) { // (filter launch + aggregation launch, as before round 5)
@@ -2202,6 +2225,18 @@ static int launch_agg(imm3_query *q, const AggArgs &a, hipStream_t s, bool timed
     bool wide = false;
     for (int j = 0; j < a.n_agg; ++j) wide |= a.aggs[j].alive != nullptr;
     if (wide) launch_strmax_init(a, s);
+    for (int j = 0; j < a.n_agg; ++j) { // COUNT_DISTINCT: every run starts from the empty set (kernel 11: one record per clear)
+        if (!a.aggs[j].dset) continue;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (timed) {
+            LaunchTimer t(ctx, 11);
+            e0 = t.start;
+            e1 = t.stop;
+        }
+        if (e0) HIPCHK(hipEventRecord(e0, s));
+        HIPCHK(hipMemsetAsync(a.aggs[j].dset, 0xFF, ((size_t)a.aggs[j].dset_mask + 1) * sizeof(unsigned long long), s));
+        if (e1) HIPCHK(hipEventRecord(e1, s));
+    }
     if (timed) {
         LaunchTimer t(ctx, 4);
         q->agg_form_ran = launch_group_agg(a, s, t.start, t.stop);
@@ -2214,6 +2249,13 @@ static int launch_agg(imm3_query *q, const AggArgs &a, hipStream_t s, bool timed
                 launch_strmax_refine(a, j, k, s, t.start, t.stop);
             } else launch_strmax_refine(a, j, k, s, nullptr, nullptr);
         }
+    }
+    for (int j = 0; j < a.n_agg; ++j) { // COUNT_DISTINCT: the mark pass (kernel 10), behind the table's last writer
+        if (!a.aggs[j].dset) continue;
+        if (timed) {
+            LaunchTimer t(ctx, 10);
+            launch_distinct_mark(a, j, s, t.start, t.stop);
+        } else launch_distinct_mark(a, j, s, nullptr, nullptr);
     }
     HIPCHK(hipGetLastError());
     return IMM3_OK;

@@ -40,8 +40,9 @@ int group_filter_plan(const GroupOrderShape &shape, const imm3_group_filter_leaf
         if (l.agg < 0 || l.agg >= shape.n_aggs)
             return fail(IMM3_ERR_ARG, fn + leaf + " names aggregate " + std::to_string(l.agg) + " of " + std::to_string(shape.n_aggs));
         const int32_t ak = shape.agg_kind[l.agg], ck = shape.agg_col_kind[l.agg];
-        // (a COUNT over a STRING column is a count like any other: only the string MAXIMUM has nothing a threshold compares with)
-        if (ck == 2 && ak != IMM3_AGG_COUNT) return fail(IMM3_ERR_ARG, fn + leaf + ": aggregate " + std::to_string(l.agg) + " is a MAX over a STRING column, which a filter does not compare");
+        // (a COUNT over a STRING column is a count like any other: only the string MAXIMUM has nothing a threshold compares with;
+        // so is a COUNT_DISTINCT: the number of distinct strings, an int64 in the value table)
+        if (ck == 2 && ak != IMM3_AGG_COUNT && ak != IMM3_AGG_COUNT_DISTINCT) return fail(IMM3_ERR_ARG, fn + leaf + ": aggregate " + std::to_string(l.agg) + " is a MAX over a STRING column, which a filter does not compare");
         if (l.average && ak != IMM3_AGG_SUM) return fail(IMM3_ERR_ARG, fn + leaf + ": average is for a SUM aggregate only");
         if (l.average && (l.value < -(int64_t)2147483648LL || l.value > (int64_t)2147483647LL))
             return fail(IMM3_ERR_ARG, fn + leaf + ": an average is compared as sum <cond> value * count in int64, so value must lie in [-2^31, 2^31 - 1]");

@@ -36,7 +36,7 @@ int group_order_plan(const GroupOrderShape &shape, const imm3_group_order_key *k
             d.at = k.index;
             const int32_t ak = shape.agg_kind[k.index], ck = shape.agg_col_kind[k.index], cw = shape.agg_col_width[k.index];
             if (ak == IMM3_AGG_COUNT) { d.src = GO_COUNT; d.width = 5; }
-            else if (ak == IMM3_AGG_SUM) { d.src = GO_SUM; d.width = 8; }
+            else if (ak == IMM3_AGG_SUM || ak == IMM3_AGG_COUNT_DISTINCT) { d.src = GO_SUM; d.width = 8; } // (COUNT_DISTINCT: an int64 in the value table, whatever its column)
             else if (ck == 0) { d.src = GO_VAL_I32; d.width = 4; }
             else if (ck == 1) { d.src = GO_VAL_I8; d.width = 1; }
             else { d.src = cw <= 8 ? GO_VAL_STR : GO_WIDE_STR; d.width = cw; }

@@ -315,6 +315,9 @@ struct imm3_query {
     // per aggregate that is a string MAX wider than 8 bytes (else null): the refine passes' alive bitmap and chunk table (AggCol)
     uint64_t *d_alive[imm3::kMaxAggs] = {nullptr, nullptr, nullptr, nullptr};
     unsigned long long *d_chunks[imm3::kMaxAggs] = {nullptr, nullptr, nullptr, nullptr};
+    // per IMM3_AGG_COUNT_DISTINCT aggregate (else null / 0): its pair set and the set's entries (imm3_distinct_plan.h)
+    unsigned long long *d_dset[imm3::kMaxAggs] = {nullptr, nullptr, nullptr, nullptr};
+    uint64_t dset_entries[imm3::kMaxAggs] = {0, 0, 0, 0};
     uint32_t out_cap = 0;
     bool agg_wide_key = false;         // group key wider than 8 bytes (the _wide entry points): tables hold tags (AggArgs::wide_key)
     bool agg_fusable = false;          // the select chain is closed intervals over <= 2 dense int8 / int32 columns of one uniform segment (or empty): the aggregation kernel can evaluate it itself

@@ -463,7 +463,8 @@ struct LimitGatherArgs {
 // ---- group-by aggregation (imm3_agg.hip) ----
 constexpr int kMaxGroupCols = 4;
 constexpr int kMaxAggs = 4;
-enum AggKind : int32_t { AGG_COUNT = 0, AGG_MIN = 1, AGG_MAX = 2, AGG_SUM = 3 }; // SUM: exact int64 over int32 / int8 columns
+enum AggKind : int32_t { AGG_COUNT = 0, AGG_MIN = 1, AGG_MAX = 2, AGG_SUM = 3, AGG_COUNT_DISTINCT = 5 }; // SUM: exact int64 over int32 / int8 columns
+// COUNT_DISTINCT: no fold in the aggregation launch -- k_distinct_mark fills AggCol::dset behind it and counts into the value table
 // The kernel forms of the aggregation, fastest first (imm3_agg.hip).  A query starts at AGG_FORM_LANES; a form whose
 // per-work-group table cannot hold the query's keys raises the overflow word (3: a lanes form, 2: direct / tile) and the
 // host aggregates again from the next form, remembering it in the query handle.
@@ -489,6 +490,10 @@ struct AggCol {
     // keeps the rows whose chunk k - 1 equals the group's and folds chunk k into chunks[k - 1][slot] (mask + 2 slots per chunk)
     unsigned long long *chunks;
     uint64_t *alive;
+    // AGG_COUNT_DISTINCT (else null): the exact set of (group, value) pairs, dset_mask + 1 open-addressing entries of
+    // slot << 32 | the value's raw bytes, ~0 = empty (a slot is <= 2^27: no entry is the empty marker).  Cleared before every run.
+    unsigned long long *dset;
+    uint32_t dset_mask, pad2;
 };
 constexpr int kStrMaxWidth = 256; // widest string MAX (IMM3_STRING_MAX_WIDTH)
 
@@ -626,6 +631,9 @@ void launch_group_collect(const AggArgs &a, hipStream_t s);
 void launch_strmax_init(const AggArgs &a, hipStream_t s);
 void launch_strmax_refine(const AggArgs &a, int j, int k, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 void launch_strmax_collect(const AggArgs &a, int j, uint32_t n_groups, uint8_t *out, hipStream_t s);
+// AGG_COUNT_DISTINCT aggregate j (AggCol::dset, cleared): one walk of the select bitmap behind the aggregation launch; every pair's
+// first arrival adds 1 to vals[slot][j]
+void launch_distinct_mark(const AggArgs &a, int j, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 // wide keys: the packed key bytes (the group columns' raw bytes in order, key_bytes per group) of every dense group, read at its
 // first row (k_group_collect's order: after it)
 void launch_group_keys(const AggArgs &a, uint32_t n_groups, int key_bytes, uint8_t *out, hipStream_t s);

@@ -31,6 +31,12 @@ void imm3::merge_check_agg_queries(imm3_query *const *queries, int32_t n, LocalV
         bool same = q->aggs.size() == q0->aggs.size() && q->group_cols.size() == q0->group_cols.size();
         for (size_t j = 0; same && j < q->aggs.size(); ++j) same = q->aggs[j].kind == q0->aggs[j].kind;
         if (!same) return verdict.fail(IMM3_ERR_ARG, "the queries aggregate differently");
+        // Counts of distinct values do not add, and a merge sees the figures, not the sets.  Refused HERE, before the kinds are packed
+        // into the vote's two bits each: the verdict travels through the vote like any other, and no rank is left in a collective.
+        // OUT OF SCOPE: a getter for the sets themselves, and with it exact merges across queries and ranks
+        for (size_t j = 0; j < q->aggs.size(); ++j)
+            if (q->aggs[j].kind == IMM3_AGG_COUNT_DISTINCT)
+                return verdict.fail(IMM3_ERR_ARG, "aggregate " + std::to_string(j) + " is a COUNT_DISTINCT: counts of distinct values do not add, so a merge of groups refuses the query");
     }
     if (n == 0) verdict.fail(IMM3_ERR_ARG, "a rank joins the merge with at least one aggregation query (the aggregates' kinds come from it)");
 }

@@ -11,6 +11,10 @@
 //   --having       accept `having <hfilter>` behind an aggregation's `group by` (default off: such a statement does not parse): and / or
 //                  lists over `alias|aggregate call  > | < | =  integer`; the groups are filtered on the GPU BEFORE the order and the
 //                  limit of --order-by.
+//   --count-distinct  accept `count(distinct f)` wherever an aggregate call may stand (default off: such a statement does not parse): the
+//                  number of distinct values of f per group, exact, counted on the GPU (f: int32, int8 or a string of at most 4 bytes).
+//                  The statement runs as ONE table query (or its single segment's); a table that would need per-segment queries is
+//                  refused: "count(distinct) runs as one table query only".
 //   --string-ranges  accept `f like 'value%'`, `f > 'value'` and `f < 'value'` on string columns (default off: the reference's grammar, in
 //                  which such a statement does not parse): byte-order prefix / range predicates, run on the GPU.  With --parse-only and a
 //                  data directory, the leaves of such conditions are also printed as the bytes the library gets ("leafbytes:").
@@ -47,7 +51,7 @@ static std::string showQuery(const Query &q) {
         p += ")";
     }
     else {
-        static const char *names[] = {"Sum", "Avg", "Min", "Max", "Count"};
+        static const char *names[] = {"Sum", "Avg", "Min", "Max", "Count", "CountDistinct"};
         p = "ProjectAgg(List(";
         for (size_t i = 0; i < q.project.aggs.size(); ++i) { if (i) p += ", "; p += std::string(names[q.project.aggs[i].kind]) + "(" + q.project.aggs[i].col + ",None)"; }
         p += ")," + list(q.project.groupBy);
@@ -65,7 +69,7 @@ static std::string showQuery(const Query &q) {
 int main(int argc, char **argv) {
     std::string query, dataDir;
     int device = 0, repeat = 0;
-    bool parseOnly = false, honourAndOr = false, explain = false, orderBy = false, stringRanges = false, having = false;
+    bool parseOnly = false, honourAndOr = false, explain = false, orderBy = false, stringRanges = false, having = false, countDistinct = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if ((a == "-q" || a == "--query") && i + 1 < argc) query = argv[++i];
@@ -77,16 +81,17 @@ int main(int argc, char **argv) {
         else if (a == "--order-by") orderBy = true;
         else if (a == "--string-ranges") stringRanges = true;
         else if (a == "--having") having = true;
+        else if (a == "--count-distinct") countDistinct = true;
         else if (a == "--explain") explain = true;
         else if (a == "--repeat" && i + 1 < argc) repeat = std::atoi(argv[++i]); // re-run the query N times on the resident table, time to stderr
         else { std::fprintf(stderr, "Error parsing arguments: %s\n", a.c_str()); return 2; }
     }
     if (query.empty() || (dataDir.empty() && !parseOnly)) {
-        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only] [--honour-and-or] [--order-by] [--having] [--string-ranges] [--explain]\n");
+        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only] [--honour-and-or] [--order-by] [--having] [--count-distinct] [--string-ranges] [--explain]\n");
         return 2;
     }
     try {
-        const Query q = SQLParser::parseAll(query, orderBy, stringRanges, having);
+        const Query q = SQLParser::parseAll(query, orderBy, stringRanges, having, countDistinct);
         if (parseOnly) {
             std::cout << showQuery(q) << "\n";
             if (!dataDir.empty()) {

@@ -504,8 +504,12 @@ inline std::string javaDoubleToString(double v) { // Double.toString for the int
     return std::string(iv < 0 ? "-" : "") + digits[0] + "." + frac + "E" + std::to_string(digits.size() - 1);
 }
 
-struct Aggregator { // CountAggr / MaxDoubleAggr / MinDoubleAggr / MaxStringAggr, folded into one tagged value
-    enum Kind { CountAggr, MaxDoubleAggr, MinDoubleAggr, MaxStringAggr } kind = CountAggr;
+// CountDistinctAggr (not in the reference): count(distinct col), the number of distinct values per group (IMM3_AGG_COUNT_DISTINCT); its
+// figure is `counter`.  The figure is exact because ONE query counts it over a set on the device; two figures do not add, so combine()
+// throws -- OUT OF SCOPE: a getter for the sets themselves, and with it the engines' per-segment fallback.
+constexpr const char *kCountDistinctOneQuery = "count(distinct) runs as one table query only";
+struct Aggregator { // CountAggr / MaxDoubleAggr / MinDoubleAggr / MaxStringAggr / CountDistinctAggr, folded into one tagged value
+    enum Kind { CountAggr, MaxDoubleAggr, MinDoubleAggr, MaxStringAggr, CountDistinctAggr } kind = CountAggr;
     std::string col, alias;
     long long counter = 0;
     double dvalue = 0;
@@ -518,18 +522,20 @@ struct Aggregator { // CountAggr / MaxDoubleAggr / MinDoubleAggr / MaxStringAggr
         a.dvalue = k == MaxDoubleAggr ? -1.7976931348623157e308 : 1.7976931348623157e308; // Double.MinValue / MaxValue
         return a;
     }
-    int abiKind() const { return kind == CountAggr ? IMM3_AGG_COUNT : (kind == MinDoubleAggr ? IMM3_AGG_MIN : IMM3_AGG_MAX); }
+    int abiKind() const { return kind == CountAggr ? IMM3_AGG_COUNT : (kind == CountDistinctAggr ? IMM3_AGG_COUNT_DISTINCT : (kind == MinDoubleAggr ? IMM3_AGG_MIN : IMM3_AGG_MAX)); }
+    bool isCounter() const { return kind == CountAggr || kind == CountDistinctAggr; } // an exact integer in `counter`
     void combine(const Aggregator &o) { // ProjectAggregateQueue.scala:27-34
         switch (kind) {
         case CountAggr: counter += o.counter; break;
         case MaxDoubleAggr: if (o.dvalue > dvalue) dvalue = o.dvalue; break;
         case MinDoubleAggr: if (o.dvalue < dvalue) dvalue = o.dvalue; break;
         case MaxStringAggr: if (svalue.empty() || o.svalue > svalue) svalue = o.svalue; break;
+        case CountDistinctAggr: throw Exception(std::string(kCountDistinctOneQuery) + ": `" + alias + "' of two queries cannot be combined (counts of distinct values do not add)");
         }
     }
     std::string repr() const {
         switch (kind) {
-        case CountAggr: return std::to_string(counter);
+        case CountAggr: case CountDistinctAggr: return std::to_string(counter);
         case MaxStringAggr: return svalue;
         default: return javaDoubleToString(dvalue);
         }
@@ -588,7 +594,7 @@ inline void orderGroups(std::vector<AggMapTuple> &groups, const std::vector<RawK
                     const Aggregator *a = nullptr;
                     for (const auto &x : groups[i].second) if (x.alias == e.name) a = &x;
                     if (!a) throw Exception("NoSuchElementException: key not found: " + e.name);
-                    if (a->kind == Aggregator::CountAggr) b = be64((unsigned long long)a->counter);
+                    if (a->isCounter()) b = be64((unsigned long long)a->counter);
                     else if (a->kind == Aggregator::MaxStringAggr) b = a->svalue;
                     else b = be64((unsigned long long)(long long)a->dvalue ^ (1ULL << 63));
                 }
@@ -649,7 +655,7 @@ inline void filterGroups(std::vector<AggMapTuple> &groups, std::vector<RawKey> &
         const bool keep = groupFilterEval(prog, [&](int32_t at) {
             const GroupFilterLeaf &l = leaves.at((size_t)at);
             for (const auto &a : m)
-                if (a.alias == l.alias) return groupFilterCompare(a.kind == Aggregator::CountAggr ? a.counter : (long long)a.dvalue, 1, l);
+                if (a.alias == l.alias) return groupFilterCompare(a.isCounter() ? a.counter : (long long)a.dvalue, 1, l);
             throw Exception("NoSuchElementException: key not found: " + l.alias);
         });
         if (!keep) continue;
@@ -819,6 +825,7 @@ class ProjectAggOp : public Operator<AggMapTuple> {
                 const int64_t x = vals[(size_t)g * aggs.size() + j];
                 switch (m[j].kind) {
                 case Aggregator::CountAggr: m[j].counter = (long long)counts[g]; break;
+                case Aggregator::CountDistinctAggr: m[j].counter = (long long)x; break; // the pair set's figure, an int64 in the value column
                 case Aggregator::MaxStringAggr: {
                     const int w = cols[(size_t)abi[j].column].width();
                     std::string sv((size_t)w, '\0');
@@ -961,6 +968,7 @@ class Engine {
             case Aggregate::Max: out.push_back(Aggregator::make(isStr ? Aggregator::MaxStringAggr : Aggregator::MaxDoubleAggr, a.col, a.alias.empty() ? a.col + "_max" : a.alias)); break;
             case Aggregate::Min: out.push_back(Aggregator::make(isStr ? Aggregator::MaxStringAggr : Aggregator::MinDoubleAggr, a.col, a.alias.empty() ? a.col + "_min" : a.alias)); break;
             case Aggregate::Count: out.push_back(Aggregator::make(Aggregator::CountAggr, a.col, a.alias.empty() ? a.col + "_count" : a.alias)); break;
+            case Aggregate::CountDistinct: out.push_back(Aggregator::make(Aggregator::CountDistinctAggr, a.col, a.alias.empty() ? a.col + "_distinct" : a.alias)); break;
             default: throw Exception("Unknown Aggregate type");
             }
         }
@@ -996,6 +1004,11 @@ class Engine {
         std::vector<int32_t> filterProg;
         groupFilterSpec(aggs, q.project.groupBy, q.project.having.get(), filterLeaves, filterProg);
         const int nseg = sm_.sm.getTableSegmentCount(table.name);
+        // count(distinct): no table query answered -- a single segment still does (its query's figure is the table's), several queries'
+        // groups cannot be combined
+        for (const auto &a : aggs)
+            if (a.kind == Aggregator::CountDistinctAggr && nseg > 1)
+                throw Exception(std::string(kCountDistinctOneQuery) + ": the table's " + std::to_string(nseg) + " segments would run as per-segment queries (" + path_ + ")");
         for (int seg = 0; seg < nseg; ++seg) {
             std::shared_ptr<ColumnVectorOperator> op = mkScan(used, seg);
             op = selectOps(q, leaves, op);

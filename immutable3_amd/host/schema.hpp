@@ -307,14 +307,14 @@ struct SelectADT {
 };
 
 struct Aggregate { // Query.scala:17-26
-    enum Kind { Sum, Avg, Min, Max, Count } kind = Count;
+    enum Kind { Sum, Avg, Min, Max, Count, CountDistinct } kind = Count; // CountDistinct: not in the reference -- count(distinct col), SQLParser's opt-in
     std::string col;
     std::string alias; // empty = None
 };
 
-// the alias Engine.resolveProjectOp gives an aggregate without one (Engine.scala:130-156): <col>_max / _min / _count
+// the alias Engine.resolveProjectOp gives an aggregate without one (Engine.scala:130-156): <col>_max / _min / _count; a CountDistinct: <col>_distinct
 inline std::string defaultAlias(const Aggregate &a) {
-    static const char *suffix[] = {"sum", "avg", "min", "max", "count"};
+    static const char *suffix[] = {"sum", "avg", "min", "max", "count", "distinct"};
     return a.alias.empty() ? a.col + "_" + suffix[a.kind] : a.alias;
 }
 

@@ -30,6 +30,13 @@
 // orderBy / limit follow only under their own flag.  The tree becomes ProjectADT::having; a name that is no alias, a group-by column
 // and a threshold that is no integer are refused (checkGroupFilterNames).  With the flag off the grammar and every parse-failure
 // message are what they were.
+// EXTENSION, only when asked for (parseAll(sql, orderBy, stringRanges, having, true); imm3_sql --count-distinct) -- the number of
+// distinct values per group (Aggregate::CountDistinct), tried in front of the reference's aggregates:
+//   agg              := "count" "(" "distinct" ident ")" | ...
+// wherever an aggregate call may stand (the SELECT list, an order key, a having key: `count(distinct age)` names age_distinct).
+// Literals match as prefixes, as everywhere here, so under the flag `count(distinctx)` is count(distinct x); a column called `distinct`
+// itself still counts as before (no ident follows).  With the flag off the grammar is exactly what it was: `count(distinct x)` fails
+// with "`)' expected".
 //   ident = [\w#]+   value = [\w0-9#]+  (no sign, no decimal point)                          (:119-121)
 #pragma once
 
@@ -43,8 +50,9 @@ namespace immutabledb {
 
 class SQLParser {
   public:
-    static Query parseAll(const std::string &input, bool orderBy = false, bool stringRanges = false, bool having = false) {
+    static Query parseAll(const std::string &input, bool orderBy = false, bool stringRanges = false, bool having = false, bool countDistinct = false) {
         SQLParser p(input);
+        p.countDistinct_ = countDistinct;
         p.orderBy_ = orderBy;
         p.stringRanges_ = stringRanges;
         p.having_ = having;
@@ -62,7 +70,7 @@ class SQLParser {
     explicit SQLParser(const std::string &s) : s_(s) {}
     const std::string &s_;
     size_t furthest_ = 0;
-    bool orderBy_ = false, stringRanges_ = false, having_ = false;
+    bool orderBy_ = false, stringRanges_ = false, having_ = false, countDistinct_ = false;
     std::string expected_ = "`select'";
 
     size_t skipWs(size_t i) const {
@@ -289,6 +297,17 @@ class SQLParser {
     bool agg(size_t i, Aggregate &a, size_t &end) { // aggSumP | aggMinP | aggMaxP | aggCountP (:103-117)
         static const struct { const char *kw; Aggregate::Kind k; } kinds[] = {
             {"sum", Aggregate::Sum}, {"min", Aggregate::Min}, {"max", Aggregate::Max}, {"count", Aggregate::Count}};
+        if (countDistinct_) { // (the opt-in: "count" "(" "distinct" ident ")")
+            size_t p, q, d, r, t;
+            std::string name;
+            if (lit(i, "count", p) && lit(p, "(", q) && lit(q, "distinct", d) && ident(d, name, r) && lit(r, ")", t)) {
+                a.kind = Aggregate::CountDistinct;
+                a.col = name;
+                a.alias.clear();
+                end = t;
+                return true;
+            }
+        }
         for (const auto &k : kinds) {
             size_t p, q, r, t;
             std::string name;

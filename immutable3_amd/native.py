@@ -66,7 +66,7 @@ DIAG_EXPORTS = [
     "imm3_ctx_timing_enable", "imm3_ctx_timing_reset", "imm3_ctx_timing_mask", "imm3_ctx_timing_collect", "imm3_ctx_set_tuning",
     "imm3_ctx_measure_read_gbps", "imm3_ctx_devclock_enable", "imm3_ctx_devclock_collect", "imm3_ctx_devclock_raw", "imm3_query_plan",
     "imm3_ctx_inject_fault", "imm3_ctx_debug_device_lock", "imm3_plan_predict", "imm3_comm_debug_standin", "imm3_plan_limit_scan",
-    "imm3_plan_table_limit", "imm3_plan_string_route", "imm3_plan_string_range_route", "imm3_plan_limit_chunks",
+    "imm3_plan_table_limit", "imm3_plan_string_route", "imm3_plan_string_range_route", "imm3_plan_limit_chunks", "imm3_plan_distinct_capacity",
     "imm3_query_agg_form", "imm3_query_expr_form", "imm3_expr_normalize", "imm3_query_group_order_path",
     "imm3_query_group_filter_stats", "imm3_group_filter_check", "imm3_comm_merge_view_path", "imm3_merge_view_plan_json",
 ]
@@ -575,6 +575,11 @@ class DeviceSegment:
 
 
 AGG_COUNT, AGG_MIN, AGG_MAX, AGG_SUM = 0, 1, 2, 3
+# include/imm3.h: IMM3_AGG_COUNT_DISTINCT -- the number of distinct values of the column among the group's selected rows (int32, int8,
+# strings of 1 .. 4 bytes); 5, not 4: kinds 4 and 9 stay "Unknown Aggregate type"
+AGG_COUNT_DISTINCT = 5
+# kernel ids of Context.timing_collect (include/imm3_diag.h): the mark pass of a COUNT_DISTINCT aggregate, the clear of its pair set
+KERNEL_DISTINCT_MARK, KERNEL_DISTINCT_CLEAR = 10, 11
 # the aggregation's kernel forms (csrc/imm3_internal.h: AggForm; DeviceQuery.agg_form, tuning 100 + form)
 AGG_FORM_LANES, AGG_FORM_LANES_WIDE, AGG_FORM_DIRECT, AGG_FORM_TILE, AGG_FORM_GENERAL = 0, 1, 2, 3, 4
 GROUP_KEY_MAX_WIDTH = 256  # include/imm3.h: IMM3_GROUP_KEY_MAX_WIDTH (DeviceQuery(..., wide_keys=True))
@@ -666,6 +671,16 @@ def plan_string_range_route(width: int) -> int:
     L = load()
     L.imm3_plan_string_range_route.argtypes = [C.c_int32]
     return int(L.imm3_plan_string_range_route(width))
+
+
+def plan_distinct_capacity(rows: int, key_bytes: int, width: int) -> int:
+    """include/imm3_diag.h: imm3_plan_distinct_capacity -- the entries of a COUNT_DISTINCT aggregate's pair set: the power of two at
+    or above 2 x min(rows, min(rows, 256^key_bytes) x 256^width), at least 1024; -1 above 2^28 (creation refuses), -2 for a bad
+    argument; a pure function, no device needed."""
+    L = load()
+    L.imm3_plan_distinct_capacity.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    L.imm3_plan_distinct_capacity.restype = C.c_int64
+    return int(L.imm3_plan_distinct_capacity(rows, key_bytes, width))
 
 
 def expr_normalize(col_codecs: Sequence[int], col_widths: Sequence[int], leaves: Sequence[tuple], prog: Sequence[int]):

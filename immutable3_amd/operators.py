@@ -24,7 +24,7 @@ import numpy as np
 from . import native
 from .native import Imm3Error
 from .query import (STR_RANGE_CONDS, str_range_bounds)
-from .query import (EQ, GT, LT, And, Avg, Count, Match, Max, Min, NoOp, NoSelect, NotMatch, Or, Project, ProjectAgg,
+from .query import (EQ, GT, LT, And, Avg, Count, CountDistinct, Match, Max, Min, NoOp, NoSelect, NotMatch, Or, Project, ProjectAgg,
                     Query, Select, SelectADT, SelectCondition, Sum, group_filter_leaves, order_keys)
 from .schema import CodecType, Column, Row, Table
 from .storage import SegmentManager
@@ -667,6 +667,51 @@ class AvgDoubleAggr(Aggregator):     # :60-75
         return str(self._DECIMAL128.divide(decimal.Decimal(f"{self.sum}.0"), decimal.Decimal(self.counter)))
 
 
+COUNT_DISTINCT_ONE_QUERY = "count(distinct) runs as one table query only"
+
+
+class CountDistinctAggr(Aggregator):
+    """count(distinct col): the number of distinct values of col among the group's selected rows (IMM3_AGG_COUNT_DISTINCT; not in the
+    reference).  The figure is exact because ONE query counts it over a set on the device; two figures do not add, so combine()
+    raises -- OUT OF SCOPE: a getter for the sets themselves, and with it the engines' per-segment fallback."""
+    kind = native.AGG_COUNT_DISTINCT
+
+    def __init__(self, col, alias):
+        super().__init__(col, alias)
+        self.counter = 0
+
+    def set(self, n):
+        self.counter = int(n)
+
+    def get(self):
+        return self.counter
+
+    def combine(self, other):
+        raise Exception(COUNT_DISTINCT_ONE_QUERY + f": {self.alias!r} of two queries cannot be combined (counts of distinct values do not add)")
+
+    def repr(self):
+        return str(self.counter)
+
+
+def count_distinct_route(has_count_distinct: bool, table_query: bool, owned_segments: int, device_merge: bool, n_contexts: int) -> str:
+    """How Engine.execute_agg answers a statement: "table" (ONE table query: exact over all segments, HAVING / ORDER BY / LIMIT on the
+    device), "segment" (the table's single owned segment as that segment's query) or "merge" (per-segment queries whose groups are
+    combined -- what a statement without count(distinct) may always do).  A statement WITH one that would have to combine several
+    queries' groups raises: table_query is False (no table could be built, or it refused the statement) and the segments are several,
+    or merge on the device, or live on several contexts.  Decided from these facts alone: no device is asked."""
+    if table_query:
+        return "table"
+    if not has_count_distinct:
+        return "merge"
+    if device_merge:
+        raise Exception(COUNT_DISTINCT_ONE_QUERY + ": device_merge combines per-segment queries, and counts of distinct values do not add")
+    if owned_segments > 1 and n_contexts > 1:
+        raise Exception(COUNT_DISTINCT_ONE_QUERY + f": the {owned_segments} segments live on {n_contexts} contexts")
+    if owned_segments > 1:
+        raise Exception(COUNT_DISTINCT_ONE_QUERY + f": this rank owns {owned_segments} segments of a table it cannot run as one query")
+    return "segment"
+
+
 class MaxStringAggr(Aggregator):     # :79-91
     kind = native.AGG_MAX
 
@@ -703,6 +748,8 @@ def resolveProjectOp(projectAgg: ProjectAgg, table: Table):
             aggs.append((MaxStringAggr if ct == "STRING" else MinDoubleAggr)(a.col, a.alias or a.col + "_min"))
         elif isinstance(a, Count):
             aggs.append(CountAggr(a.col, a.alias or a.col + "_count"))
+        elif isinstance(a, CountDistinct):
+            aggs.append(CountDistinctAggr(a.col, a.alias or a.col + "_distinct"))
         else:
             raise Exception("Unknown Aggregate type")
     return lambda op: ProjectAggOp(aggs, op, list(projectAgg.groupBy), getattr(projectAgg, "order_by", ()), getattr(projectAgg, "limit", 0),
@@ -759,7 +806,7 @@ def group_filter_leaf(aggmap: dict, leaf) -> bool:
     a = aggmap[alias]
     if isinstance(a, AvgDoubleAggr):
         lhs, rhs = int(a.sum), int(value) * int(a.counter)
-    elif isinstance(a, CountAggr):
+    elif isinstance(a, (CountAggr, CountDistinctAggr)):
         lhs, rhs = int(a.get()), int(value)
     else:
         lhs, rhs = int(a.get()), int(value)
@@ -810,7 +857,7 @@ def order_groups(result: Dict[str, dict], raw_keys: Dict[str, Sequence[bytes]], 
                     b = raw
             else:
                 a = aggmap[name]
-                if isinstance(a, CountAggr):
+                if isinstance(a, (CountAggr, CountDistinctAggr)):
                     b = _order_bytes(a.get(), 16, 0)
                 elif isinstance(a, MaxStringAggr):
                     b = a.get().encode("utf-8")     # (new String(bytes) of the value: the bytes again for ASCII)
@@ -916,7 +963,7 @@ class ProjectAggOp(Operator):
                 total += by_name[name].width
             else:
                 a = by_alias[name]
-                total += 5 if a.kind == native.AGG_COUNT else 8 if a.kind == native.AGG_SUM else by_name[a.col].width
+                total += 5 if a.kind == native.AGG_COUNT else 8 if a.kind in (native.AGG_SUM, native.AGG_COUNT_DISTINCT) else by_name[a.col].width
         return total
 
     def _native_filter(self, cols):
@@ -963,6 +1010,8 @@ class ProjectAggOp(Operator):
                 na = a.make()
                 if isinstance(na, CountAggr):
                     na.set(int(counts[g]))
+                elif isinstance(na, CountDistinctAggr):   # the pair set's figure, an int64 in the value column
+                    na.set(int(vals[g, j]))
                 elif isinstance(na, AvgDoubleAggr):  # the group's exact sum; every selected row added once to the counter
                     na.sum, na.counter = int(vals[g, j]), int(counts[g])
                 elif isinstance(na, MaxStringAggr) and j in wide:
@@ -1155,6 +1204,9 @@ class Engine:
             except native.Imm3Error as e:
                 if not self._table_tree_refused(e, prog):
                     raise
+        # count(distinct): no table query answered -- a single owned segment still does, several queries' groups cannot be combined
+        owned = sum(1 for s in range(self.sm.getTableSegmentCount(table.name)) if self.sm.owns(table.name, s))
+        count_distinct_route(any(isinstance(a, CountDistinct) for a in query.project.aggs), False, owned, self.device_merge, len(self.sm.ctxs))
         used = getColumns(query, table)
         leaves = self._select_ops(query)
         mk_scan = ScanOp.mkScanOp(self.sm, query.table)

@@ -207,9 +207,13 @@ class Count(Aggregate):            # Query.scala:25
     pass
 
 
+class CountDistinct(Aggregate):    # not in the reference: count(distinct col), the number of distinct values per group (IMM3_AGG_COUNT_DISTINCT)
+    pass
+
+
 def default_alias(agg: Aggregate) -> str:
-    """the alias Engine.resolveProjectOp gives an aggregate without one (Engine.scala:130-156): <col>_max / _min / _count"""
-    suffix = {Max: "max", Min: "min", Count: "count", Sum: "sum", Avg: "avg"}[type(agg)]
+    """the alias Engine.resolveProjectOp gives an aggregate without one (Engine.scala:130-156): <col>_max / _min / _count; a CountDistinct: <col>_distinct"""
+    suffix = {Max: "max", Min: "min", Count: "count", Sum: "sum", Avg: "avg", CountDistinct: "distinct"}[type(agg)]
     return agg.alias or f"{agg.col}_{suffix}"
 
 

@@ -35,7 +35,15 @@ EXTENSION, only when asked for -- parseAll(sql, having=True) -- HAVING over the 
   hkey             := ident | the aggregate call as written in the SELECT list (count(id) names id_count)
 orderBy / limit follow only under their own flag (group_order).  The tree becomes ProjectAgg.having -- And / Or over Select(alias, GT |
 LT | EQ) --, whose checks (query.group_filter_leaves: an unknown alias, a group-by column, a threshold that is no integer) raise
-ValueError.  With the flag off the grammar and every parse-failure message are what they were."""
+ValueError.  With the flag off the grammar and every parse-failure message are what they were.
+
+EXTENSION, only when asked for -- parseAll(sql, count_distinct=True) -- the number of distinct values per group (query.CountDistinct),
+tried in front of the reference's aggregates:
+  agg              := "count" "(" "distinct" ident ")" | ...
+wherever an aggregate call may stand (the SELECT list, an order key, a having key: `count(distinct age)` names age_distinct).  Literals
+match as prefixes, as everywhere here, so under the flag `count(distinctx)` is count(distinct x); a column called `distinct` itself
+still counts as before (no ident follows).  With the flag off the grammar is exactly what it was: `count(distinct x)` fails with
+"`)' expected"."""
 from __future__ import annotations
 
 import re
@@ -51,13 +59,16 @@ class ParseError(Exception):
 
 
 class SQLParser:
-    def __init__(self, s: str, order_by: bool = False, string_ranges: bool = False, group_order: bool = False, having: bool = False):
+    def __init__(self, s: str, order_by: bool = False, string_ranges: bool = False, group_order: bool = False, having: bool = False,
+                 count_distinct: bool = False):
         self.s, self.order_by, self.string_ranges, self.group_order, self.having = s, order_by, string_ranges, group_order, having
+        self.count_distinct = count_distinct
         self.furthest, self.expected = 0, "`select'"
 
     @staticmethod
-    def parseAll(sql: str, order_by: bool = False, string_ranges: bool = False, group_order: bool = False, having: bool = False) -> Q.Query:
-        p = SQLParser(sql, order_by, string_ranges, group_order, having)
+    def parseAll(sql: str, order_by: bool = False, string_ranges: bool = False, group_order: bool = False, having: bool = False,
+                 count_distinct: bool = False) -> Q.Query:
+        p = SQLParser(sql, order_by, string_ranges, group_order, having, count_distinct)
         r = p._query(0)
         if r is not None:
             q, end = r
@@ -200,6 +211,14 @@ class SQLParser:
         return out, p
 
     def _agg(self, i):
+        if self.count_distinct:                                # (the opt-in: "count" "(" "distinct" ident ")")
+            p = self._lit(i, "count")
+            q = self._lit(p, "(") if p is not None else None
+            d = self._lit(q, "distinct") if q is not None else None
+            r = self._ident(d) if d is not None else None
+            t = self._lit(r[1], ")") if r is not None else None
+            if t is not None:
+                return Q.CountDistinct(r[0]), t
         for kw, mk in (("sum", Q.Sum), ("min", Q.Min), ("max", Q.Max), ("count", Q.Count)):
             p = self._lit(i, kw)
             q = self._lit(p, "(") if p is not None else None

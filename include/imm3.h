@@ -185,7 +185,21 @@ int imm3_segment_wait(imm3_segment *seg);
 int imm3_segment_destroy(imm3_segment *seg);
 int imm3_segment_bytes(const imm3_segment *seg, uint64_t *device_bytes);
 
-enum { IMM3_AGG_COUNT = 0, IMM3_AGG_MIN = 1, IMM3_AGG_MAX = 2, IMM3_AGG_SUM = 3 };
+enum { IMM3_AGG_COUNT = 0, IMM3_AGG_MIN = 1, IMM3_AGG_MAX = 2, IMM3_AGG_SUM = 3, IMM3_AGG_COUNT_DISTINCT = 5 };
+/* IMM3_AGG_COUNT_DISTINCT: the number of distinct values of `column` among the group's selected rows -- `select state,
+ * count(distinct age) from t group by state`.  (5, not 4: kinds 4 and 9 are what callers and tests feed as "an unknown kind" and stay
+ * unknown, the decision IMM3_EXPR_NOT = -4 records.)  All eight aggregation creators take it; up to four may stand in one query,
+ * beside any other aggregate.  Columns: int32, int8 and STRING columns of 1 .. 4 bytes -- a value is its raw bytes, and distinct raw
+ * bytes are distinct values; a wider string column is refused at creation with IMM3_ERR_ARG.  The figure is EXACT: each such
+ * aggregate owns a device-resident open-addressing set of (group slot << 32 | value) entries, the power of two at or above
+ * 2 x min(rows, bound on groups x 256^width) and at least 1024 of them (imm3_plan_distinct_capacity, imm3_diag.h), refused with
+ * IMM3_ERR_ARG above 2^28 entries.  A run clears the sets, aggregates (always the general kernel form: the fast forms and the fused
+ * select decline the kind), then walks the select bitmap once per such aggregate; a recorded run replays all of it.  Over an
+ * imm3_table the figure counts over ALL segments.  The getters return it as the aggregate's int64 value (imm3_query_fetch_groups and
+ * its ordered form); ORDER BY over groups takes it as an 8-byte key, a group filter as a value leaf -- over a string column too.
+ * Counts of distinct values do not add: every imm3_comm_merge_groups* entry point refuses a query that carries the kind.
+ * OUT OF SCOPE: values wider than 4 bytes; a getter for the sets themselves, and with it exact merges across queries and ranks; a
+ * set in LDS for narrow value domains; the fast aggregation forms carrying the kind; the JNI / Scala binding. */
 /* widest STRING column that IMM3_AGG_MAX takes on the GPU path (bytes) */
 #define IMM3_STRING_MAX_WIDTH 256
 /* widest group key (the sum of the group columns' widths) that the _wide aggregation entry points take (bytes) */

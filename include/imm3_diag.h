@@ -21,7 +21,8 @@ extern "C" {
  *             8 = ORDER BY over groups (imm3_query_set_group_order): ONE record per ordered settle, from the small launch's start (or
  *                 the radix path's key launch's) to the end of the launch that writes the ordered groups,
  *             9 = a view of merged groups (imm3_comm_merge_groups_view): ONE record per view, from the small launch's start (or the
- *                 radix path's key launch's) to the end of the launch that writes the ordered records. */
+ *                 radix path's key launch's) to the end of the launch that writes the ordered records,
+ *             10 = the mark pass of an IMM3_AGG_COUNT_DISTINCT aggregate (one per such aggregate), 11 = the clear of its pair set. */
 int imm3_ctx_timing_enable(imm3_ctx *ctx, int32_t max_records);
 int imm3_ctx_timing_reset(imm3_ctx *ctx);
 /* Only launches whose kernel id has its bit set in `kernel_mask` are bracketed (default: all). */
@@ -188,6 +189,11 @@ int imm3_plan_string_route(int32_t width, int32_t n_match);
  * 1 = the string pass (k_filter_str_range: widths 4, 8, ... 256), 2 = the word-at-a-time kernel (every other width in 1 .. 256: what
  * a table refuses), -1 outside. */
 int imm3_plan_string_range_route(int32_t width);
+/* imm3_plan_distinct_capacity: the entries of an IMM3_AGG_COUNT_DISTINCT aggregate's pair set (csrc/imm3_distinct_plan.cpp:
+ * distinct_capacity, pure) for a query over `rows` rows with a packed group key of `key_bytes` bytes and a value column of `width`
+ * bytes: the power of two at or above 2 x min(rows, min(rows, 256^key_bytes) x 256^width), at least 1024.  -1: more than 2^28 (what
+ * creation refuses); -2: rows < 0, key_bytes < 0 or width outside 1 .. 4. */
+int64_t imm3_plan_distinct_capacity(int64_t rows, int32_t key_bytes, int32_t width);
 struct imm3_comm;
 int imm3_comm_debug_standin(struct imm3_comm *comm, int32_t work_groups, uint32_t spin_us);
 int imm3_ctx_inject_fault(imm3_ctx *ctx, int32_t work_group, int32_t span, uint32_t max_polls);
