@@ -48,6 +48,7 @@ static const char *cond_name(int c) {
     switch (c) {
     case IMM3_MATCH: return "Match";
     case IMM3_STR_RANGE: return "StrRange";
+    case IMM3_INT_IN: return "IntIn";
     case IMM3_NOTMATCH: return "NotMatch";
     case IMM3_EQ: return "EQ";
     case IMM3_GT: return "GT";
@@ -1066,7 +1067,7 @@ static int check_create_args(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
     // whether or not the segment has any block.
     for (int32_t i = 0; i < n_sels; ++i) {
         const int c = sels[i].cond;
-        if (c != IMM3_MATCH && c != IMM3_GT && c != IMM3_LT && c != IMM3_EQ && c != IMM3_STR_RANGE)
+        if (c != IMM3_MATCH && c != IMM3_GT && c != IMM3_LT && c != IMM3_EQ && c != IMM3_STR_RANGE && c != IMM3_INT_IN)
             return fail(IMM3_ERR_UNSUPPORTED_CONDITION, std::string("Unsupported condition: ") + cond_name(c));
         if (c == IMM3_MATCH && sels[i].n_match > 0 && (!sels[i].match_bytes || !sels[i].match_lens))
             return fail(IMM3_ERR_ARG, "Match without values");
@@ -1074,6 +1075,10 @@ static int check_create_args(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
             const SegCol &sc = seg->cols[(size_t)used_cols[sels[i].column]];
             const int rrc = str_range_check_leaf(sels[i].n_match, sels[i].match_bytes, sels[i].match_lens, sc.vcodec == IMM3_DENSE_STRING ? sc.width : 0);
             if (rrc) return rrc;
+        }
+        if (c == IMM3_INT_IN) { // (the count and the pointer; a STRING column fails scan_layout's vector check)
+            const int lrc = int_list_check_leaf(sels[i].n_match, sels[i].match_bytes);
+            if (lrc) return lrc;
         }
     }
     return IMM3_OK;
@@ -1277,7 +1282,7 @@ static int place_compressed(imm3_query *q, bool have_batches, const std::vector<
         bool projected = false;
         for (int32_t pj : q->proj) projected |= (pj == i);
         FoldedPred *fp = pred_on(q->preds, sci);
-        const bool fused = sc.codec == IMM3_PFOR_INT && fp && !q->table && !q->ragged && sc.tile_aligned && !projected && !agg_reads &&
+        const bool fused = sc.codec == IMM3_PFOR_INT && fp && !fp->has_list && !q->table && !q->ragged && sc.tile_aligned && !projected && !agg_reads &&
                            fv != TV_GENERIC_ONLY && fv != TV_PFOR_DECODED;
         if (fused) fp->pfor = true;
         else if (!q->table) { // a table decodes its PFOR_INT columns when it is created
@@ -1288,9 +1293,31 @@ static int place_compressed(imm3_query *q, bool have_batches, const std::vector<
     return IMM3_OK;
 }
 
-// Step 5: IN-lists too long for the kernel arguments go to the device.
+// Step 5: IN-lists too long for the kernel arguments go to the device -- and so does the probe table of an int32 column's folded
+// IMM3_INT_IN list of more than kMaxMatch values (built here, once: imm3_int_list_plan.cpp; the list pass's LDS / GLOBAL forms and the
+// word-at-a-time kernels probe it); a shorter list travels as its values and an int8 column's list as its 256-bit set, both in the
+// kernel arguments.
 static int upload_match_blobs(imm3_query *q, std::vector<FoldedPred> &preds) {
     for (auto &p : preds) {
+        if (p.kind != KIND_STR && p.has_list && !p.list.empty()) {
+            if (p.kind == KIND_I8) {
+                int_list_set256(p.list, p.list_set);
+                continue;
+            }
+            if (int_list_form(p.width, (int64_t)p.list.size()) == INT_LIST_ARGS) continue; // (the values travel in the kernel arguments on every route: no table, no allocation, no wait)
+            IntListTable t;
+            int_list_build_table(p.list, t);
+            p.list_mask = t.mask;
+            p.list_shift = t.shift;
+            p.list_max_probe = t.max_probe;
+            p.list_empty = t.empty;
+            void *d = nullptr;
+            HIPCHK(pool_alloc(q->ctx, &d, t.slots.size() * sizeof(int32_t)));
+            p.d_blob = (uint8_t *)d;
+            HIPCHK(hipMemcpyAsync(d, t.slots.data(), t.slots.size() * sizeof(int32_t), hipMemcpyHostToDevice, q->ctx->stream));
+            HIPCHK(hipStreamSynchronize(q->ctx->stream)); // (the host image goes away with this scope)
+            continue;
+        }
         if (p.kind != KIND_STR || (!p.has_range && (p.match.empty() || (p.width <= 8 && p.match.size() <= (size_t)kMaxMatch)))) continue;
         std::string blob;
         for (auto &v : p.match) blob += v;
@@ -1391,6 +1418,9 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
         if (has_or || has_not)
             for (int32_t i = 0; i < n_sels; ++i)
                 if (sels[i].cond == IMM3_STR_RANGE) return fail(IMM3_ERR_ARG, kTreeRangeRefusal);
+        if (has_or || has_not)
+            for (int32_t i = 0; i < n_sels; ++i)
+                if (sels[i].cond == IMM3_INT_IN) return fail(IMM3_ERR_ARG, kTreeIntInRefusal);
         if (!has_or && !has_not) {
             for (int32_t i = 0; i < n_prog; ++i)
                 if (prog[i] >= 0) flat.push_back(sels[prog[i]]);
@@ -2039,7 +2069,7 @@ static int query_create_agg_impl(imm3_ctx *ctx, const imm3_segment *seg, const i
                   !q->is_expr && // (a select tree's launch writes the bitmap, the aggregation reads it)
                   !has_distinct; // (k_distinct_mark walks the bitmap; the fast forms decline the kind anyway: group_agg_fast_ok)
         for (const auto &fp : q->preds)
-            ok = ok && !fp.pfor && (fp.kind == KIND_I8 || fp.kind == KIND_I32) && col_flat(seg->cols[(size_t)fp.seg_col]) != nullptr;
+            ok = ok && !fp.pfor && !fp.has_list && (fp.kind == KIND_I8 || fp.kind == KIND_I32) && col_flat(seg->cols[(size_t)fp.seg_col]) != nullptr;
         q->agg_fusable = ok;
     }
     // table capacity: twice the number of possible groups, bounded by the rows and by 2^27 slots (a wide key's domain saturates)

@@ -107,7 +107,8 @@ bool str_range_successor(std::string &v);
 bool str_range_predecessor(std::string &v);
 int str_range_route(int32_t width);
 void str_range_pack(const std::string &lo, const std::string &hi, std::vector<uint8_t> &blob, uint32_t lo4[4], uint32_t hi4[4]);
-extern const char *const kTableRangeRefusal;                          // a table has no word-at-a-time kernel: a range on a width the string pass does not take
+extern const char *const kTreeIntInRefusal;                           // imm3_expr_norm.cpp: a program with an OR or a NOT takes no IMM3_INT_IN leaf
+extern const char *const kTableRangeRefusal;                       // a table has no word-at-a-time kernel: a range on a width the string pass does not take
 
 // ---- imm3_planner.cpp ----
 constexpr int kSampleChunks = 8;                                      // the sample a plan is made on: eight chunks of 64 tiles spread over the segment / table
@@ -141,7 +142,7 @@ int single_pass_restore(imm3_query *q, uint64_t survivors);
 // on a column whose width is a multiple of 4, then the word-at-a-time passes.
 struct SelectChain {
     std::vector<std::vector<const FoldedPred *>> tile_passes;
-    std::vector<const FoldedPred *> pfor, str_passes, generic;
+    std::vector<const FoldedPred *> pfor, str_passes, list_passes, generic; // (list_passes: IMM3_INT_IN, k_filter_int_list, one column per launch)
     bool single_tile_pass = false; // exactly ONE launch in the whole chain: its column order is the records' and the one launch's
 };
 SelectChain plan_select_chain(const imm3_query *q);

@@ -202,8 +202,24 @@ __device__ __forceinline__ bool match_row(const ColPred &c, int64_t row) {
 
 __device__ __forceinline__ bool eval_row(const ColPred &c, int64_t row) {
     switch (c.kind) {
-    case KIND_I32: return in_closed(((const int32_t *)c.data)[row], c.lo, c.hi);
-    case KIND_I8: return in_closed((int32_t)((const int8_t *)c.data)[row], c.lo, c.hi);
+    case KIND_I32: {
+        const int32_t v = ((const int32_t *)c.data)[row];
+        bool in = in_closed(v, c.lo, c.hi);
+        // IMM3_INT_IN: the bounded probe of k_filter_int_list (imm3_int_list_plan.h) against the table in device memory
+        if (c.list == 2 && in) { // at most kMaxMatch values, in match[] (the unused entries repeat the first)
+            const int32_t *vals = (const int32_t *)c.match;
+            in = false;
+#pragma unroll
+            for (int m = 0; m < kMaxMatch; ++m) in = in || v == vals[m];
+        } else if (c.list && in) in = int_list_probe((const int32_t *)c.match_blob, c.list_mask, c.list_shift, c.list_empty, c.list_max_probe, v);
+        return in;
+    }
+    case KIND_I8: {
+        const int32_t v = (int32_t)((const int8_t *)c.data)[row];
+        bool in = in_closed(v, c.lo, c.hi);
+        if (c.list && in) in = int_list_set_has((const uint32_t *)c.match, v);
+        return in;
+    }
     default: return match_row(c, row);
     }
 }

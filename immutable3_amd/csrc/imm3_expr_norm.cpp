@@ -23,6 +23,25 @@ __attribute__((weak)) bool str_range_empty(const std::string &lo, const std::str
 __attribute__((weak)) bool str_range_full(const std::string &lo, const std::string &hi);
 __attribute__((weak)) void str_range_intersect(std::string &lo, std::string &hi, const std::string &lo2, const std::string &hi2);
 __attribute__((weak)) void str_range_filter_match(const std::string &lo, const std::string &hi, std::vector<std::string> &match);
+// ... and so is the list logic of IMM3_INT_IN (imm3_int_list_plan.cpp)
+__attribute__((weak)) int int_list_parse(int32_t n_match, const uint8_t *bytes, int32_t width, std::vector<int32_t> &out);
+__attribute__((weak)) void int_list_clip(std::vector<int32_t> &list, int64_t lo, int64_t hi);
+__attribute__((weak)) void int_list_intersect(std::vector<int32_t> &list, const std::vector<int32_t> &other);
+
+const char *const kTreeIntInRefusal =
+    "a select program with an IMM3_EXPR_OR or an IMM3_EXPR_NOT does not take IMM3_INT_IN leaves (its normal form would need "
+    "negated lists and intervals with exclusions); a program of IMM3_EXPR_AND alone does";
+
+namespace {
+// a numeric predicate with a list, settled: the list's values inside the interval, the interval tightened to the list's minimum and
+// maximum; no value left: the empty interval (lo > hi), which is what every caller reads as "selects nothing"
+void settle_list(FoldedPred &p) {
+    if (!p.has_list) return;
+    int_list_clip(p.list, p.lo, p.hi);
+    if (p.list.empty()) { p.lo = 1; p.hi = 0; }
+    else { p.lo = p.list.front(); p.hi = p.list.back(); }
+}
+} // namespace
 
 // One SelectOp leaf on a column of DENSE_* codec `vcodec`: GT / LT / EQ narrow the column type's full interval (threshold narrowed
 // per leaf: d.toInt / d.toByte, Select.scala:65,73), Match keeps the values of exactly `width` bytes, each once.
@@ -46,6 +65,12 @@ int leaf_pred(int32_t seg_col, int32_t vcodec, int32_t width, const imm3_select 
             }
             off += len;
         }
+    } else if (leaf.cond == IMM3_INT_IN) { // a member of the list (imm3_int_list_plan.cpp)
+        if (!int_list_parse || !int_list_clip || !int_list_intersect) return fail(IMM3_ERR_ARG, "IMM3_INT_IN: this build holds no list logic");
+        const int rc = int_list_parse(leaf.n_match, leaf.match_bytes, width, out.list);
+        if (rc) return rc;
+        out.has_list = true;
+        settle_list(out);
     } else {
         const int64_t t = out.kind == KIND_I32 ? (int64_t)jvm_d2i(leaf.value) : (int64_t)jvm_d2b(leaf.value);
         if (leaf.cond == IMM3_GT) out.lo = std::max(out.lo, t + 1);      // strict >, Select.scala:68,76
@@ -86,9 +111,12 @@ void merge_pred(FoldedPred &into, const FoldedPred &other) {
             if (has(cut, v) == keep_common) left.push_back(v);
         into.match = left;
         into.negated = false;
-    } else {
+    } else { // an interval, and optionally a list: two lists intersect, the list keeps its values inside the interval
         into.lo = std::max(into.lo, other.lo);
         into.hi = std::min(into.hi, other.hi);
+        if (into.has_list && other.has_list) int_list_intersect(into.list, other.list);
+        else if (other.has_list) { into.has_list = true; into.list = other.list; }
+        settle_list(into);
     }
 }
 
@@ -101,6 +129,7 @@ bool pred_empty(const FoldedPred &p) { // (a NOT-IN is never empty)
 bool pred_unconstrained(const FoldedPred &p) {
     if (p.kind == KIND_STR && p.has_range) return str_range_full(p.range_lo, p.range_hi);
     if (p.kind == KIND_STR) return p.negated && p.match.empty();
+    if (p.has_list) return false; // (a list is a constraint even when it holds every value of the type)
     const FoldedPred full = unfolded_pred(p.seg_col, p.kind == KIND_I32 ? IMM3_DENSE_INT : IMM3_DENSE_TINYINT, p.width);
     return p.lo <= full.lo && p.hi >= full.hi;
 }
@@ -132,7 +161,7 @@ int expr_check_program(const int32_t *prog, int32_t n_prog, int32_t n_leaves, bo
 namespace {
 bool same_pred(const FoldedPred &a, const FoldedPred &b) {
     if (a.seg_col != b.seg_col) return false;
-    if (a.kind != KIND_STR) return a.lo == b.lo && a.hi == b.hi;
+    if (a.kind != KIND_STR) return a.lo == b.lo && a.hi == b.hi && a.has_list == b.has_list && a.list == b.list;
     if (a.negated != b.negated || a.match.size() != b.match.size()) return false;
     for (auto &v : a.match)
         if (std::find(b.match.begin(), b.match.end(), v) == b.match.end()) return false;
@@ -318,12 +347,19 @@ extern "C" int imm3_expr_normalize(const int32_t *col_codec, const int32_t *col_
     for (int32_t i = 0; i < n_leaves; ++i) {
         const int32_t c = leaves[i].column, cond = leaves[i].cond;
         if (c < 0 || c >= n_cols) return fail(IMM3_ERR_ARG, "select column is not among the columns");
-        if (cond != IMM3_MATCH && cond != IMM3_GT && cond != IMM3_LT && cond != IMM3_EQ) return fail(IMM3_ERR_UNSUPPORTED_CONDITION, "Unsupported condition");
+        if (cond != IMM3_MATCH && cond != IMM3_GT && cond != IMM3_LT && cond != IMM3_EQ && cond != IMM3_INT_IN) return fail(IMM3_ERR_UNSUPPORTED_CONDITION, "Unsupported condition");
         const int32_t vc = value_codec(col_codec[c]);
         if (vc != IMM3_DENSE_INT && vc != IMM3_DENSE_TINYINT && vc != IMM3_DENSE_STRING) return fail(IMM3_ERR_NO_CODEC, "No implementation for codec " + std::to_string(col_codec[c]));
         if ((cond == IMM3_MATCH) != (vc == IMM3_DENSE_STRING)) return fail(IMM3_ERR_UNSUPPORTED_VECTOR, "Unsupported column vector");
         if (cond == IMM3_MATCH && leaves[i].n_match > 0 && (!leaves[i].match_bytes || !leaves[i].match_lens)) return fail(IMM3_ERR_ARG, "Match without values");
         leaf_cols.push_back(ExprCol{c, vc, col_width[c]});
+    }
+    {   // (as query creation: a program with an OR or a NOT takes no list)
+        bool has_or = false, has_not = false;
+        const int prc = expr_check_program(prog, n_prog, n_leaves, &has_or, &has_not);
+        if (prc) return prc;
+        for (int32_t i = 0; (has_or || has_not) && i < n_leaves; ++i)
+            if (leaves[i].cond == IMM3_INT_IN) return fail(IMM3_ERR_ARG, kTreeIntInRefusal);
     }
     std::vector<ExprTerm> terms;
     const int rc = expr_normalize(leaf_cols, leaves, n_leaves, prog, n_prog, terms);
@@ -347,7 +383,14 @@ extern "C" int imm3_expr_normalize(const int32_t *col_codec, const int32_t *col_
                     js += "\"";
                 }
                 js += "]";
-            } else js += ",\"lo\":" + std::to_string(p.lo) + ",\"hi\":" + std::to_string(p.hi);
+            } else {
+                js += ",\"lo\":" + std::to_string(p.lo) + ",\"hi\":" + std::to_string(p.hi);
+                if (p.has_list) {
+                    js += ",\"list\":[";
+                    for (size_t m = 0; m < p.list.size(); ++m) js += (m ? "," : "") + std::to_string(p.list[m]);
+                    js += "]";
+                }
+            }
             js += "}";
         }
         js += "]";

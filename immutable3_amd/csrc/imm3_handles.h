@@ -248,6 +248,11 @@ struct FoldedPred { // all SelectOp leaves on one segment column, folded
     int32_t seg_col = 0;
     int32_t kind = 0, width = 0;
     int64_t lo = 0, hi = 0;                // numeric closed interval
+    bool has_list = false;                 // numeric: AND a member of `list` (IMM3_INT_IN leaves, folded: imm3_int_list_plan.cpp); never in a program with an OR or a NOT
+    std::vector<int32_t> list;             // ... ascending, each value once, all inside [lo, hi] = [its minimum, its maximum]; an empty folded list is lo > hi
+    uint32_t list_set[8] = {0, 0, 0, 0, 0, 0, 0, 0};                  // ... int8: the 256-bit membership set (upload_match_blobs)
+    uint32_t list_mask = 0, list_shift = 0, list_max_probe = 0;        // ... int32: the probe table at d_blob (IntListTable)
+    int32_t list_empty = 0;
     std::vector<std::string> match;        // string: surviving IN-list values (each exactly width bytes)
     bool negated = false;                  // string, select trees only: `match` are EXCLUSIONS -- every value but these passes (a complemented Match)
     bool has_range = false;                // string: a byte-order range INSTEAD of an IN-list (IMM3_STR_RANGE; `match` is empty, never negated):

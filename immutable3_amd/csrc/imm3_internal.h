@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <algorithm>
 
+#include "imm3_int_list_plan.h"
+
 // Ablation switches ("what does the kernel cost without its stores?") exist only in the tools' build of the library
 // (make -C csrc ablate: -DIMM3_ABLATE -> lib/libimm3_ablate.so, loaded through IMM3_LIB_PATH).  In the shipped build
 // IMM3_ABLATED is the constant false and the kernels carry none of it.
@@ -51,6 +53,12 @@ struct ColPred {
                                  // lo' then hi') at match_blob; n_match is 0
     uint64_t match[kMaxMatch];   // value bytes packed little-endian (byte 0 = first character)
     const uint8_t *match_blob;   // otherwise: n_match * width bytes in device memory
+    // numeric, IMM3_INT_IN: != 0 = the row must also be a member of the folded list (inside [lo, hi]) -- int8 (1): the 256-bit set in the
+    // first 32 bytes of match[]; int32 (1): the probe table (imm3_int_list_plan.h) at match_blob, list_mask + 1 slots; int32 with at most
+    // kMaxMatch values (2): the values as int32 in the first 32 bytes of match[], the unused entries repeating the first -- no table
+    int32_t list;
+    int32_t list_empty;
+    uint32_t list_mask, list_shift, list_max_probe;
 };
 
 // ---- tile kernel (compile-time column kinds) ----
@@ -346,6 +354,30 @@ struct StrRangeArgs {
     const void *const *tile_ptrs;
 };
 bool launch_filter_str_range(const StrRangeArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // false: no instance for this width
+
+// ---- k_filter_int_list (imm3_intlist.hip): IMM3_INT_IN on one int32 / int8 column; k_filter_str_rows' geometry, bitmap line and partials ----
+struct IntListArgs {
+    const void *data;                // flat (decoded) column in HBM, 16-byte aligned
+    int32_t width;                   // 4 (int32) or 1 (int8)
+    int32_t form;                    // IntListForm (imm3_int_list_plan.h): selects the instance
+    int32_t and_existing;            // 1: AND into the bitmap already in memory
+    int32_t n_values;                // INT_LIST_ARGS: values in inl[]
+    int32_t lo, hi;                  // the folded interval: the list's minimum and maximum
+    union {
+        int32_t inl[kMaxMatch];      // INT_LIST_ARGS: the values, the unused entries repeating the first
+        uint32_t set[8];             // INT_LIST_I8: bit (uint8_t)v of the 256-bit membership set
+    };
+    const int32_t *table;            // INT_LIST_LDS / INT_LIST_GLOBAL: the probe table in device memory, mask + 1 slots
+    uint32_t mask, shift, max_probe; // slots - 1 (INT_LIST_LDS: < kIntListLdsSlots), 32 - log2(slots), the step bound of every probe
+    int32_t empty;                   // what an empty slot holds (never a member)
+    int64_t n_rows, n_words, n_tiles;
+    uint64_t *bitmap;                // allocated in whole tiles
+    uint32_t *block_partials;
+    const uint32_t *tile_rows;       // table queries, as StrRowsArgs
+    const void *const *tile_ptrs;
+};
+int int_list_grid(int64_t n_tiles, int grid_blocks, int32_t width);
+bool launch_filter_int_list(const IntListArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // false: arguments no instance takes
 
 // ---- select trees (imm3_expr.hip): AND / OR over the leaves, as a disjunction of TERMS ----
 // The host rewrites a tree into terms (imm3_expr_norm.cpp): each term is a conjunction with at most one folded predicate per column --

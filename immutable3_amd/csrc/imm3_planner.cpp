@@ -70,6 +70,7 @@ bool table_limit_applies(const TableLimitInputs &in) {
 }
 
 int tile_kind(const FoldedPred &fp) {
+    if (fp.kind != KIND_STR && fp.has_list) return TK_NONE; // (a folded IMM3_INT_IN list: a pass of its own, k_filter_int_list)
     if (fp.kind == KIND_I32) return TK_I32;
     if (fp.kind == KIND_I8) return TK_I8;
     if (fp.kind == KIND_STR && fp.width == 2 && !fp.match.empty() && fp.match.size() <= (size_t)kMaxTileMatch) return TK_S2;
@@ -84,8 +85,9 @@ bool str_rows_pred(const FoldedPred &fp) {
 }
 
 // Which kernel a folded predicate goes to on a uniform layout: 0 the tile kernel, 1 k_filter_str_rows, 2 the word-at-a-time kernel
-// (the only one a table does not have).
+// (the only one a table does not have), 3 k_filter_int_list (an int32 / int8 predicate with a list; a table has its instances).
 int pred_route(const FoldedPred &fp) {
+    if (fp.kind != KIND_STR && fp.has_list) return 3;
     if (tile_kind(fp) != TK_NONE) return 0;
     return str_rows_pred(fp) ? 1 : 2;
 }
@@ -102,6 +104,7 @@ SelectChain plan_select_chain(const imm3_query *q) {
         if (p.pfor) c.pfor.push_back(&p);
         else if (tiles && pred_route(p) == 0) tile_preds.push_back(&p);
         else if (tiles && pred_route(p) == 1) c.str_passes.push_back(&p);
+        else if (tiles && pred_route(p) == 3) c.list_passes.push_back(&p);
         else c.generic.push_back(&p);
     }
     std::stable_sort(tile_preds.begin(), tile_preds.end(),
@@ -121,7 +124,7 @@ SelectChain plan_select_chain(const imm3_query *q) {
         c.tile_passes.push_back(take);
     }
     if (q->preds.empty() && tiles) c.tile_passes.emplace_back();
-    c.single_tile_pass = c.generic.empty() && c.pfor.empty() && c.str_passes.empty() && c.tile_passes.size() == 1; // (a string pass: the bitmap path, as with a generic pass)
+    c.single_tile_pass = c.generic.empty() && c.pfor.empty() && c.str_passes.empty() && c.list_passes.empty() && c.tile_passes.size() == 1; // (a string or list pass: the bitmap path, as with a generic pass)
     return c;
 }
 

@@ -38,6 +38,21 @@ void imm3::fill_colpred(const imm3_query *q, const FoldedPred &fp, ColPred &cp) 
         cp.match_in_args = 0;
         cp.n_match = 0;
     }
+    if (fp.kind != KIND_STR && fp.has_list) { // IMM3_INT_IN: the set (int8) or the probe table (int32: upload_match_blobs)
+        cp.list = 1;
+        cp.n_match = 0;
+        std::memcpy(cp.match, fp.list_set, sizeof(fp.list_set));
+        if (fp.kind == KIND_I32 && int_list_form(fp.width, (int64_t)fp.list.size()) == INT_LIST_ARGS) { // no table: the values themselves, a shorter list repeating its first
+            cp.list = 2;
+            int32_t vals[kMaxMatch];
+            for (size_t m = 0; m < (size_t)kMaxMatch; ++m) vals[m] = fp.list[m < fp.list.size() ? m : 0];
+            std::memcpy(cp.match, vals, sizeof(vals));
+        }
+        cp.list_empty = fp.list_empty;
+        cp.list_mask = fp.list_mask;
+        cp.list_shift = fp.list_shift;
+        cp.list_max_probe = fp.kind == KIND_I32 && fp.d_blob ? fp.list_max_probe : 0; // (no table: no step)
+    }
     if (cp.match_in_args) {
         for (size_t m = 0; m < fp.match.size(); ++m) {
             uint64_t v = 0;
@@ -412,6 +427,43 @@ static int launch_str_rows_pass(imm3_query *q, SelectRun &run, const FoldedPred 
     return IMM3_OK;
 }
 
+// A list pass (k_filter_int_list): one int32 / int8 column with a folded IMM3_INT_IN list per launch, a segment or a table's tile table
+static int launch_int_list_pass(imm3_query *q, SelectRun &run, const FoldedPred &fp) {
+    imm3_ctx *ctx = q->ctx;
+    IntListArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.data = col_flat(q->seg->cols[(size_t)fp.seg_col]);
+    a.width = fp.width;
+    a.form = int_list_form(fp.width, (int64_t)fp.list.size());
+    a.lo = (int32_t)fp.lo;
+    a.hi = (int32_t)fp.hi;
+    if (a.form == INT_LIST_I8) std::memcpy(a.set, fp.list_set, sizeof(a.set));
+    else if (a.form == INT_LIST_ARGS) {
+        a.n_values = (int32_t)fp.list.size();
+        for (size_t m = 0; m < (size_t)kMaxMatch; ++m) a.inl[m] = fp.list[m < fp.list.size() ? m : 0]; // (the kernel compares all kMaxMatch: a shorter list repeats its first value)
+    } else {
+        if (!fp.d_blob) return fail(IMM3_ERR_ARG, "internal: an integer list without its table on the device");
+        a.table = (const int32_t *)fp.d_blob;
+        a.mask = fp.list_mask;
+        a.shift = fp.list_shift;
+        a.max_probe = fp.list_max_probe;
+        a.empty = fp.list_empty;
+    }
+    fill_pass_tail(q, run, a);
+    if (q->table) {
+        a.tile_rows = q->table->d_tile_rows;
+        a.tile_ptrs = (const void *const *)q->table->d_tile_ptrs[(size_t)fp.seg_col];
+    }
+    run.grid = int_list_grid(q->n_tiles, ctx->grid_blocks, fp.width);
+    {
+        LaunchTimer t(ctx, 0);
+        if (!launch_filter_int_list(a, run.grid, run.s, t.start, t.stop)) return fail(IMM3_ERR_ARG, "internal: no integer list kernel for these arguments");
+    }
+    HIPCHK(hipGetLastError());
+    ++run.pass;
+    return IMM3_OK;
+}
+
 // A word-at-a-time pass (k_filter_generic) over up to kMaxPredCols of the chain's generic predicates from `first` on (none at all:
 // the query without predicates on a layout the tile kernel does not take)
 static int launch_generic_pass(imm3_query *q, SelectRun &run, size_t first) {
@@ -525,6 +577,7 @@ int imm3::run_select(imm3_query *q, unsigned mode) {
     q->run.has_pfor_pass = !run.chain.pfor.empty();
     for (size_t i = 0; !rc && i < run.chain.pfor.size(); ++i) rc = launch_pfor_pass(q, run, *run.chain.pfor[i]);
     for (size_t i = 0; !rc && i < run.chain.str_passes.size(); ++i) rc = launch_str_rows_pass(q, run, *run.chain.str_passes[i]);
+    for (size_t i = 0; !rc && i < run.chain.list_passes.size(); ++i) rc = launch_int_list_pass(q, run, *run.chain.list_passes[i]);
     const bool need_empty_generic = q->preds.empty() && run.pass == 0;
     for (size_t gi = 0; !rc && (gi < run.chain.generic.size() || (need_empty_generic && run.pass == 0)); gi += kMaxPredCols) rc = launch_generic_pass(q, run, gi);
     if (rc) return rc;

@@ -69,7 +69,7 @@ static std::string showQuery(const Query &q) {
 int main(int argc, char **argv) {
     std::string query, dataDir;
     int device = 0, repeat = 0;
-    bool parseOnly = false, honourAndOr = false, explain = false, orderBy = false, stringRanges = false, having = false, countDistinct = false;
+    bool parseOnly = false, honourAndOr = false, explain = false, orderBy = false, stringRanges = false, having = false, countDistinct = false, intLists = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if ((a == "-q" || a == "--query") && i + 1 < argc) query = argv[++i];
@@ -82,16 +82,17 @@ int main(int argc, char **argv) {
         else if (a == "--string-ranges") stringRanges = true;
         else if (a == "--having") having = true;
         else if (a == "--count-distinct") countDistinct = true;
+        else if (a == "--int-lists") intLists = true;
         else if (a == "--explain") explain = true;
         else if (a == "--repeat" && i + 1 < argc) repeat = std::atoi(argv[++i]); // re-run the query N times on the resident table, time to stderr
         else { std::fprintf(stderr, "Error parsing arguments: %s\n", a.c_str()); return 2; }
     }
     if (query.empty() || (dataDir.empty() && !parseOnly)) {
-        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only] [--honour-and-or] [--order-by] [--having] [--count-distinct] [--string-ranges] [--explain]\n");
+        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only] [--honour-and-or] [--order-by] [--having] [--count-distinct] [--string-ranges] [--int-lists] [--explain]\n");
         return 2;
     }
     try {
-        const Query q = SQLParser::parseAll(query, orderBy, stringRanges, having, countDistinct);
+        const Query q = SQLParser::parseAll(query, orderBy, stringRanges, having, countDistinct, intLists);
         if (parseOnly) {
             std::cout << showQuery(q) << "\n";
             if (!dataDir.empty()) {

@@ -236,20 +236,33 @@ struct SelectCondition {
     // IMM3_STR_RANGE; the order of ORDER BY and the string MAX aggregate -- unsigned, byte-wise, from the first byte).  StrRange(lo, hi)
     // is closed, lo padded to the column's width with 0x00 and hi with 0xFF; Prefix(p) = StrRange(p, p); StrGT(v) / StrLT(v) are strict,
     // relative to v padded with 0x00.
-    enum Kind { Match, NotMatch, EQ, GT, LT, NoOp, StrRange, Prefix, StrGT, StrLT } kind = NoOp;
+    // EXTENSION, behind those: IntIn(values), an IN-list on an int32 / int8 column (include/imm3.h: IMM3_INT_IN) -- exact integer
+    // membership, duplicates once, an empty list selects nothing; not under an Or or a NotMatch-as-NOT tree (the library refuses it).
+    enum Kind { Match, NotMatch, EQ, GT, LT, NoOp, StrRange, Prefix, StrGT, StrLT, IntIn } kind = NoOp;
     double value = 0;                 // EQ / GT / LT
     std::vector<std::string> values;  // Match / NotMatch; StrRange: {lo, hi}; Prefix / StrGT / StrLT: {the value}
+    std::vector<int32_t> ints;        // IntIn
+    static SelectCondition intIn(std::vector<int32_t> v) { SelectCondition c; c.kind = IntIn; c.ints = std::move(v); return c; }
     static SelectCondition strRange(std::string lo, std::string hi) { SelectCondition c; c.kind = StrRange; c.values = {std::move(lo), std::move(hi)}; return c; }
     static SelectCondition prefix(std::string p) { SelectCondition c; c.kind = Prefix; c.values = {std::move(p)}; return c; }
     static SelectCondition strGT(std::string v) { SelectCondition c; c.kind = StrGT; c.values = {std::move(v)}; return c; }
     static SelectCondition strLT(std::string v) { SelectCondition c; c.kind = StrLT; c.values = {std::move(v)}; return c; }
-    bool isStrRange() const { return kind >= StrRange; }
+    bool isStrRange() const { return kind >= StrRange && kind <= StrLT; }
     // what the C ABI's leaf carries: the condition code (a range form: 6, IMM3_STR_RANGE) and the values -- of a range form the leaf's
     // {lo, hi} on a string column of `width` bytes.  StrGT(v) is from the successor of v padded with 0x00 on, StrLT(v) up to its
     // predecessor (big-endian arithmetic over the column's width); where there is none the leaf is one no row passes (lo 01, hi 00:
     // 01 00 00 .. > 00 FF FF ..).  A bound longer than the column throws (the library refuses it too).
-    int32_t abiCond() const { return isStrRange() ? 6 : (int32_t)kind; }
+    // An IntIn leaf (7, IMM3_INT_IN) carries each value as its 4 little-endian bytes: concatenated they are the leaf's match_bytes.
+    int32_t abiCond() const { return kind == IntIn ? 7 : (isStrRange() ? 6 : (int32_t)kind); }
     std::vector<std::string> abiValues(int width) const {
+        if (kind == IntIn) {
+            std::vector<std::string> out;
+            for (int32_t v : ints) {
+                const uint32_t u = (uint32_t)v;
+                out.push_back(std::string{(char)(u & 255), (char)((u >> 8) & 255), (char)((u >> 16) & 255), (char)(u >> 24)});
+            }
+            return out;
+        }
         if (!isStrRange()) return values;
         for (const auto &b : values)
             if ((int)b.size() > width) throw Exception("string bound '" + b + "' is longer than the column's " + std::to_string(width) + " bytes");
@@ -290,6 +303,7 @@ struct SelectCondition {
         case Prefix: return "Prefix(" + values[0] + ")";
         case StrGT: return "StrGT(" + values[0] + ")";
         case StrLT: return "StrLT(" + values[0] + ")";
+        case IntIn: { std::string s = "IntIn(List("; for (size_t i = 0; i < ints.size(); ++i) s += (i ? ", " : "") + std::to_string(ints[i]); return s + "))"; }
         default: return "NoOp";
         }
     }

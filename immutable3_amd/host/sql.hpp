@@ -37,7 +37,12 @@
 // Literals match as prefixes, as everywhere here, so under the flag `count(distinctx)` is count(distinct x); a column called `distinct`
 // itself still counts as before (no ident follows).  With the flag off the grammar is exactly what it was: `count(distinct x)` fails
 // with "`)' expected".
-//   ident = [\w#]+   value = [\w0-9#]+  (no sign, no decimal point)                          (:119-121)
+// EXTENSION, only when asked for (parseAll(sql, orderBy, stringRanges, having, countDistinct, true); imm3_sql --int-lists) -- IN-lists
+// on int32 / int8 columns (SelectCondition::IntIn), tried behind the reference's alternatives (and behind the string ranges):
+//   filter           := ... | ident "in" "(" rep1sep(int, ",") ")"        int = -?[0-9]+
+// A literal outside int32 throws (kIntListRangeError + the literal) at parse time.  With the flag off the grammar and every
+// parse-failure message are what they were.
+//   ident =[\w#]+   value = [\w0-9#]+  (no sign, no decimal point)                          (:119-121)
 #pragma once
 
 #include <cctype>
@@ -50,8 +55,11 @@ namespace immutabledb {
 
 class SQLParser {
   public:
-    static Query parseAll(const std::string &input, bool orderBy = false, bool stringRanges = false, bool having = false, bool countDistinct = false) {
+    static constexpr const char *kIntListRangeError = "integer literal out of range for an IN-list (int32): ";
+    static Query parseAll(const std::string &input, bool orderBy = false, bool stringRanges = false, bool having = false, bool countDistinct = false,
+                          bool intLists = false) {
         SQLParser p(input);
+        p.intLists_ = intLists;
         p.countDistinct_ = countDistinct;
         p.orderBy_ = orderBy;
         p.stringRanges_ = stringRanges;
@@ -70,7 +78,7 @@ class SQLParser {
     explicit SQLParser(const std::string &s) : s_(s) {}
     const std::string &s_;
     size_t furthest_ = 0;
-    bool orderBy_ = false, stringRanges_ = false, having_ = false, countDistinct_ = false;
+    bool orderBy_ = false, stringRanges_ = false, having_ = false, countDistinct_ = false, intLists_ = false;
     std::string expected_ = "`select'";
 
     size_t skipWs(size_t i) const {
@@ -177,7 +185,43 @@ class SQLParser {
                 return true;
             }
         }
+        if (intLists_) { // filterIn: ident "in" "(" rep1sep(int, ",") ")"
+            std::vector<int32_t> ints;
+            int32_t x = 0;
+            if (ident(i, f, p) && lit(p, "in", q) && lit(q, "(", r) && intLiteral(r, x, t)) {
+                ints.push_back(x);
+                for (;;) {
+                    size_t c, u;
+                    if (!lit(t, ",", c) || !intLiteral(c, x, u)) break; // rep1sep backtracks over a dangling separator
+                    ints.push_back(x);
+                    t = u;
+                }
+                size_t u;
+                if (lit(t, ")", u)) {
+                    out = SelectADT::mkSelect(f, SelectCondition::intIn(ints));
+                    end = u;
+                    return true;
+                }
+            }
+        }
         return false;
+    }
+    bool intLiteral(size_t i, int32_t &val, size_t &out) { // -?[0-9]+ ; a literal outside int32 is an error, not a parse failure
+        i = skipWs(i);
+        size_t j = i;
+        if (j < s_.size() && s_[j] == '-') ++j;
+        const size_t digits = j;
+        while (j < s_.size() && s_[j] >= '0' && s_[j] <= '9') ++j;
+        if (j == digits) { note(i, "string matching regex `-?[0-9]+'"); return false; }
+        const std::string text = s_.substr(i, j - i);
+        size_t k = digits - i; // leading zeros do not count towards the length
+        while (k + 1 < text.size() && text[k] == '0') ++k;
+        if (text.size() - k > 10) throw Exception(kIntListRangeError + text);
+        const long long v = std::strtoll(text.c_str(), nullptr, 10);
+        if (v < -2147483648LL || v > 2147483647LL) throw Exception(kIntListRangeError + text);
+        val = (int32_t)v;
+        out = j;
+        return true;
     }
     bool where(size_t i, std::shared_ptr<SelectADT> &out, size_t &end) { // opt("where" ~> filter)
         size_t p, q;

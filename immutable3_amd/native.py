@@ -25,6 +25,10 @@ MATCH, NOTMATCH, EQ, GT, LT, NOOP = 0, 1, 2, 3, 4, 5
 # extension (include/imm3.h: IMM3_STR_RANGE): a closed byte-order range on a string column; operand (lo, hi), each 0 .. width bytes,
 # lo padded with 0x00 and hi with 0xFF
 STR_RANGE = 6
+# extension (include/imm3.h: IMM3_INT_IN): an IN-list on an int32 / int8 column; operand: the integers (each an int32), any order
+INT_IN = 7
+INT_IN_MAX_VALUES = 1 << 24   # IMM3_INT_IN_MAX_VALUES
+INT_LIST_I8, INT_LIST_ARGS, INT_LIST_LDS, INT_LIST_GLOBAL = 0, 1, 2, 3   # plan_int_list_form (csrc/imm3_int_list_plan.h: IntListForm)
 # operators of a select tree's postfix program (include/imm3.h: IMM3_EXPR_AND / IMM3_EXPR_OR / IMM3_EXPR_NOT); values >= 0 are leaf
 # indices.  NOT pops one operand and pushes its complement (-4: -3 stays the unknown operator it has always been)
 EXPR_AND, EXPR_OR, EXPR_NOT = -1, -2, -4
@@ -67,6 +71,7 @@ DIAG_EXPORTS = [
     "imm3_ctx_measure_read_gbps", "imm3_ctx_devclock_enable", "imm3_ctx_devclock_collect", "imm3_ctx_devclock_raw", "imm3_query_plan",
     "imm3_ctx_inject_fault", "imm3_ctx_debug_device_lock", "imm3_plan_predict", "imm3_comm_debug_standin", "imm3_plan_limit_scan",
     "imm3_plan_table_limit", "imm3_plan_string_route", "imm3_plan_string_range_route", "imm3_plan_limit_chunks", "imm3_plan_distinct_capacity",
+    "imm3_plan_int_list_table", "imm3_plan_int_list_form", "imm3_plan_int_list_probe",
     "imm3_query_agg_form", "imm3_query_expr_form", "imm3_expr_normalize", "imm3_query_group_order_path",
     "imm3_query_group_filter_stats", "imm3_group_filter_check", "imm3_comm_merge_view_path", "imm3_merge_view_plan_json",
 ]
@@ -615,6 +620,14 @@ class DeviceTable:
             pass
 
 
+class RawIntList:
+    """An INT_IN operand handed to the library as it stands: n_match and the values' buffer (None: a null match_bytes) -- for callers
+    that hold the leaf's fields themselves, and for the tests of its argument checks."""
+
+    def __init__(self, n_match: int, values=None):
+        self.n_match, self.values = int(n_match), values
+
+
 def _cselects(sels):
     """(CSelect array, the numpy buffers it points into) for [(column, cond, operand)]"""
     cs = (CSelect * max(1, len(sels)))()
@@ -631,6 +644,21 @@ def _cselects(sels):
             keep += [blob, lens]
             cs[i].match_bytes = blob.ctypes.data
             cs[i].match_lens = lens.ctypes.data
+            cs[i].n_match = len(vals)
+        elif cond == INT_IN and isinstance(operand, RawIntList):   # the leaf's fields as given (the library's own checks)
+            blob = None if operand.values is None else np.array(list(operand.values) or [0], dtype="<i4")
+            keep.append(blob)
+            cs[i].match_bytes = None if blob is None else blob.ctypes.data
+            cs[i].match_lens = None
+            cs[i].n_match = operand.n_match
+        elif cond == INT_IN:   # 4-byte little-endian values; no lengths
+            vals = [int(v) for v in (operand if operand is not None else [])]
+            if any(not -(1 << 31) <= v < (1 << 31) for v in vals):
+                raise ValueError("an IntIn value is outside int32")
+            blob = np.array(vals or [0], dtype="<i4")
+            keep.append(blob)
+            cs[i].match_bytes = blob.ctypes.data
+            cs[i].match_lens = None
             cs[i].n_match = len(vals)
         elif operand is not None:
             cs[i].value = float(operand)
@@ -671,6 +699,36 @@ def plan_string_range_route(width: int) -> int:
     L = load()
     L.imm3_plan_string_range_route.argtypes = [C.c_int32]
     return int(L.imm3_plan_string_range_route(width))
+
+
+def plan_int_list_form(width: int, n: int) -> int:
+    """include/imm3_diag.h: imm3_plan_int_list_form -- the form of k_filter_int_list a folded IMM3_INT_IN list of n values takes on a
+    column of `width` bytes: INT_LIST_I8 / _ARGS / _LDS / _GLOBAL, -1 for a bad argument; a pure function, no device needed."""
+    L = load()
+    L.imm3_plan_int_list_form.argtypes = [C.c_int32, C.c_int64]
+    return int(L.imm3_plan_int_list_form(width, n))
+
+
+def plan_int_list_table(values):
+    """include/imm3_diag.h: imm3_plan_int_list_table -- (slots int32[], empty, max_probe): the open-addressing table query creation
+    builds for these int32 values; a pure function, no device needed."""
+    L = load()
+    L.imm3_plan_int_list_table.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    v = np.ascontiguousarray(np.asarray(values, dtype=np.int32))
+    n_slots, empty, max_probe = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+    vp = v.ctypes.data if v.size else None
+    _check(L.imm3_plan_int_list_table(vp, v.size, None, 0, C.byref(n_slots), C.byref(empty), C.byref(max_probe)))
+    slots = np.zeros(n_slots.value, dtype=np.int32)
+    _check(L.imm3_plan_int_list_table(vp, v.size, slots.ctypes.data, slots.size, C.byref(n_slots), C.byref(empty), C.byref(max_probe)))
+    return slots, int(empty.value), int(max_probe.value)
+
+
+def plan_int_list_probe(slots, empty: int, max_probe: int, v: int) -> int:
+    """include/imm3_diag.h: imm3_plan_int_list_probe -- the kernels' bounded probe on the host: 1 found, 0 not, -1 bad table."""
+    L = load()
+    L.imm3_plan_int_list_probe.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
+    s = np.ascontiguousarray(np.asarray(slots, dtype=np.int32))
+    return int(L.imm3_plan_int_list_probe(s.ctypes.data, s.size, empty, max_probe, v))
 
 
 def plan_distinct_capacity(rows: int, key_bytes: int, width: int) -> int:

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import native
 from .native import Imm3Error
-from .query import (STR_RANGE_CONDS, str_range_bounds)
+from .query import (STR_RANGE_CONDS, IntIn, str_range_bounds)
 from .query import (EQ, GT, LT, And, Avg, Count, CountDistinct, Match, Max, Min, NoOp, NoSelect, NotMatch, Or, Project, ProjectAgg,
                     Query, Select, SelectADT, SelectCondition, Sum, group_filter_leaves, order_keys)
 from .schema import CodecType, Column, Row, Table
@@ -210,13 +210,15 @@ class ProjectionOperator(Operator):    # Operator.scala:26-28
     pass
 
 
-SUPPORTED_CONDS = (Match, GT, LT, EQ) + STR_RANGE_CONDS      # what SelectOp.iterator lets through (Select.scala:17-23, and the range extension)
+SUPPORTED_CONDS = (Match, GT, LT, EQ) + STR_RANGE_CONDS + (IntIn,)   # what SelectOp.iterator lets through (Select.scala:17-23, and the range and integer-list extensions)
 
 
 def _cond_spec(cond: SelectCondition, width: int = 0):
     """(native cond, operand) of one leaf; width: bytes of the leaf's column (the range forms are made for it)"""
     if isinstance(cond, STR_RANGE_CONDS):
         return native.STR_RANGE, list(str_range_bounds(cond, width))
+    if isinstance(cond, IntIn):
+        return native.INT_IN, list(cond.values)
     if isinstance(cond, Match):
         return native.MATCH, [v.encode("utf-8") if isinstance(v, str) else bytes(v) for v in cond.values]
     if isinstance(cond, NotMatch):

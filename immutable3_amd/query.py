@@ -114,6 +114,28 @@ def str_range_bounds(cond: SelectCondition, width: int):
     return STR_RANGE_NONE if hi is None else (b"", hi)
 
 
+# ---- EXTENSION: an IN-list on an int32 / int8 column (include/imm3.h: IMM3_INT_IN): the rows whose value is one of `values`.
+# Membership is exact on integers (no narrowing: a value outside an int8 column's range matches nothing); duplicates count once, an
+# empty list selects no row.  Not under an Or or a NotMatch-as-NOT tree (the library refuses the program). ----
+INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
+INT_IN_RANGE_ERROR = "integer literal out of range for an IN-list (int32): "
+
+
+@dataclass(frozen=True)
+class IntIn(SelectCondition):
+    values: tuple
+
+    def __init__(self, values):
+        vals = []
+        for v in values:
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError(f"IntIn takes integers, not {v!r}")
+            if not INT32_MIN <= int(v) <= INT32_MAX:
+                raise ValueError(INT_IN_RANGE_ERROR + str(int(v)))
+            vals.append(int(v))
+        object.__setattr__(self, "values", tuple(vals))
+
+
 @dataclass(frozen=True)
 class _NoOp(SelectCondition):      # Query.scala:9
     pass

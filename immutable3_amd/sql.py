@@ -43,7 +43,13 @@ tried in front of the reference's aggregates:
 wherever an aggregate call may stand (the SELECT list, an order key, a having key: `count(distinct age)` names age_distinct).  Literals
 match as prefixes, as everywhere here, so under the flag `count(distinctx)` is count(distinct x); a column called `distinct` itself
 still counts as before (no ident follows).  With the flag off the grammar is exactly what it was: `count(distinct x)` fails with
-"`)' expected"."""
+"`)' expected".
+
+EXTENSION, only when asked for -- parseAll(sql, int_lists=True) -- IN-lists on int32 / int8 columns (query.IntIn), tried behind the
+reference's alternatives (and behind the string ranges):
+  filter           := ... | ident "in" "(" rep1sep(int, ",") ")"        int = -?[0-9]+
+A literal outside int32 raises ValueError (query.INT_IN_RANGE_ERROR + the literal), at parse time.  With the flag off the grammar and
+every parse-failure message are what they were."""
 from __future__ import annotations
 
 import re
@@ -52,6 +58,7 @@ from . import query as Q
 
 _WORD = re.compile(r"[A-Za-z0-9_#]+")
 _DIGITS = re.compile(r"[0-9]+")
+_INT = re.compile(r"-?[0-9]+")
 
 
 class ParseError(Exception):
@@ -60,15 +67,16 @@ class ParseError(Exception):
 
 class SQLParser:
     def __init__(self, s: str, order_by: bool = False, string_ranges: bool = False, group_order: bool = False, having: bool = False,
-                 count_distinct: bool = False):
+                 count_distinct: bool = False, int_lists: bool = False):
+        self.int_lists = int_lists
         self.s, self.order_by, self.string_ranges, self.group_order, self.having = s, order_by, string_ranges, group_order, having
         self.count_distinct = count_distinct
         self.furthest, self.expected = 0, "`select'"
 
     @staticmethod
     def parseAll(sql: str, order_by: bool = False, string_ranges: bool = False, group_order: bool = False, having: bool = False,
-                 count_distinct: bool = False) -> Q.Query:
-        p = SQLParser(sql, order_by, string_ranges, group_order, having, count_distinct)
+                 count_distinct: bool = False, int_lists: bool = False) -> Q.Query:
+        p = SQLParser(sql, order_by, string_ranges, group_order, having, count_distinct, int_lists)
         r = p._query(0)
         if r is not None:
             q, end = r
@@ -182,7 +190,35 @@ class SQLParser:
                 u = self._lit(u, "'") if u is not None else None
                 if u is not None:
                     return Q.Select(c[0], mk(v[0])), u
+        if self.int_lists:                                     # ident "in" "(" rep1sep(int, ",") ")"
+            c = self._cmp(i, "in")
+            p = self._lit(c[1], "(") if c is not None else None
+            r = self._int(p) if p is not None else None
+            if r is not None:
+                ints, p = [r[0]], r[1]
+                while True:
+                    t = self._lit(p, ",")
+                    r = self._int(t) if t is not None else None
+                    if r is None:                              # (rep1sep backtracks over a dangling separator)
+                        break
+                    ints.append(r[0])
+                    p = r[1]
+                u = self._lit(p, ")")
+                if u is not None:
+                    return Q.Select(c[0], Q.IntIn(ints)), u
         return None
+
+    def _int(self, i):
+        """-?[0-9]+ ; a literal outside int32 is a ValueError, not a parse failure"""
+        i = self._ws(i)
+        m = _INT.match(self.s, i)
+        if not m:
+            self._note(i, "string matching regex `-?[0-9]+'")
+            return None
+        v = int(m.group(0))
+        if not Q.INT32_MIN <= v <= Q.INT32_MAX:
+            raise ValueError(Q.INT_IN_RANGE_ERROR + m.group(0))
+        return v, m.end()
 
     def _where(self, i):
         p = self._lit(i, "where")

@@ -79,6 +79,24 @@ enum { IMM3_MATCH = 0, IMM3_NOTMATCH = 1, IMM3_EQ = 2, IMM3_GT = 3, IMM3_LT = 4,
  * with IMM3_ERR_ARG (segment and table alike; not an IMM3_TABLE_TREE_REFUSED refusal: per-segment queries would be refused the same
  * way) -- the normal form would need complemented ranges and ranges with exclusions. */
 enum { IMM3_STR_RANGE = 6 };
+/* EXTENSION (not a SelectCondition value): an IN-list on an int32 or int8 column -- `id in (3, 17, 4096)`.  A leaf with this cond
+ * carries n_match values in match_bytes, each a 4-byte little-endian two's-complement int32; match_lens may be NULL and `value` is
+ * ignored.  It selects the rows whose value is a member of the list.  Membership is exact on integers: there is no d.toByte /
+ * d.toInt narrowing, and on an int8 column a value outside -128 .. 127 is no member of anything and is dropped, the way a Match value
+ * of the wrong length is.  Duplicates count once; n_match == 0 selects no row.  n_match runs up to IMM3_INT_IN_MAX_VALUES (2^24: the
+ * probe table of such a list has 2^25 four-byte slots, 128 MiB of device memory per query).
+ * Errors: a negative count, a null match_bytes with n_match > 0, or a count above the cap: IMM3_ERR_ARG, the message says which; a
+ * leaf on a STRING column: "Unsupported column vector" iff the segment has >= 1 batch.  IMM3_MATCH on an int column keeps its error.
+ * Every creator that takes `sels` or `leaves` accepts the leaf.  Leaves on one column fold: a list and GT / LT / EQ leaves to the
+ * list's values inside the interval, two lists to their intersection; an empty folded list selects nothing.  Uniform layouts and
+ * tables run a folded list through a pass of its own (k_filter_int_list, one column per launch: a 256-bit set for int8, the values as
+ * kernel arguments up to 8 of them, else an open-addressing table probed from LDS or from device memory); ragged layouts and the
+ * generic-only tuning variant test the same set, values or table in the word-at-a-time kernel.
+ * OUT OF SCOPE: a select-tree program that has an IMM3_EXPR_OR or an IMM3_EXPR_NOT *and* an IMM3_INT_IN leaf is refused at creation
+ * with IMM3_ERR_ARG (segment and table alike; not an IMM3_TABLE_TREE_REFUSED refusal) -- NOT IN and lists inside disjunctions need
+ * negated lists and intervals with exclusions in the normal form.  The JNI / Scala binding does not carry the leaf. */
+enum { IMM3_INT_IN = 7 };
+#define IMM3_INT_IN_MAX_VALUES (1 << 24)
 
 /* status codes */
 enum {
@@ -117,7 +135,7 @@ typedef struct {
  * below (the _expr entry points). */
 typedef struct {
     int32_t column;             /* index into the query's used-column list                           */
-    int32_t cond;               /* IMM3_GT / IMM3_LT / IMM3_EQ / IMM3_MATCH / IMM3_STR_RANGE (others -> error) */
+    int32_t cond;               /* IMM3_GT / IMM3_LT / IMM3_EQ / IMM3_MATCH / IMM3_STR_RANGE / IMM3_INT_IN (others -> error) */
     double value;               /* GT/LT/EQ operand as the Query ADT carries it (core/Query.scala:6-8);
                                    narrowed per column type INSIDE the library: Int column d.toInt,
                                    TinyInt column d.toByte (Select.scala:65,73)                      */

@@ -189,6 +189,19 @@ int imm3_plan_string_route(int32_t width, int32_t n_match);
  * 1 = the string pass (k_filter_str_range: widths 4, 8, ... 256), 2 = the word-at-a-time kernel (every other width in 1 .. 256: what
  * a table refuses), -1 outside. */
 int imm3_plan_string_range_route(int32_t width);
+/* IMM3_INT_IN (csrc/imm3_int_list_plan.cpp, pure).  imm3_plan_int_list_table: the open-addressing table query creation builds for
+ * `n` int32 values (any order, duplicates count once): *n_slots slots (a power of two, >= 16 and >= 2 x the distinct values), empty
+ * slots holding *empty (an int32 the list does not hold), values inserted in ascending order by linear probing from the home slot
+ * (the top bits of (uint32_t)v * 0x9E3779B1), *max_probe = the longest insertion distance + 1 -- the step bound of every probe.  With
+ * cap == 0 only the three figures are returned; else slots_out takes the slots (cap >= *n_slots, or IMM3_ERR_ARG).
+ * imm3_plan_int_list_form: the form of k_filter_int_list a folded list of n values takes on a column of `width` bytes: 0 = int8 (a
+ * 256-bit set, any n), 1 = int32, the values as kernel arguments, 2 = int32, the table copied into LDS, 3 = int32, the table in
+ * device memory; -1: width not 1 or 4, n outside 0 .. IMM3_INT_IN_MAX_VALUES.
+ * imm3_plan_int_list_probe: the kernels' probe on the host (the same inline code): 1 = v is found within max_probe steps, 0 = not,
+ * -1 = n_slots is no power of two in 16 .. 2^25. */
+int imm3_plan_int_list_table(const int32_t *values, int64_t n, int32_t *slots_out, int64_t cap, int64_t *n_slots, int32_t *empty, int32_t *max_probe);
+int imm3_plan_int_list_form(int32_t width, int64_t n);
+int imm3_plan_int_list_probe(const int32_t *slots, int64_t n_slots, int32_t empty, int32_t max_probe, int32_t v);
 /* imm3_plan_distinct_capacity: the entries of an IMM3_AGG_COUNT_DISTINCT aggregate's pair set (csrc/imm3_distinct_plan.cpp:
  * distinct_capacity, pure) for a query over `rows` rows with a packed group key of `key_bytes` bytes and a value column of `width`
  * bytes: the power of two at or above 2 x min(rows, min(rows, 256^key_bytes) x 256^width), at least 1024.  -1: more than 2^28 (what
