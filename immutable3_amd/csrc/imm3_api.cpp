@@ -490,6 +490,7 @@ static void segment_free(imm3_segment *seg) {
         if (c.d_block_off) (void)hipFree(c.d_block_off);
         if (c.d_row_base) (void)hipFree(c.d_row_base);
         if (c.d_dense) (void)hipFree(c.d_dense);
+        if (c.d_hi16) (void)hipFree(c.d_hi16);
     }
     for (auto &kv : seg->d_sample_ptrs) (void)hipFree(kv.second);
     (void)hipFree(seg->d_sample_rows);
@@ -700,6 +701,53 @@ static int ensure_dense(imm3_ctx *ctx, const imm3_segment *cseg, int32_t col) {
                                                               : "malformed snappy block (bad element, length mismatch or CRC-32C mismatch)");
     }
     sc.d_dense = (uint8_t *)p;
+    seg->device_bytes += bytes;
+    return IMM3_OK;
+}
+
+// The 16-bit high-half plane of a DENSE_INT column (SegCol::d_hi16), made once per segment the first time a query's plan wants it,
+// as the decoded form above is: under the segment's mutex, on the context's stream (the caller has made that stream wait for an
+// asynchronously created segment: segment_await), never in a run.  One kernel reads the column, writes the plane and reduces the
+// halves' span; a column spanning fewer than kHi16MinSpan halves gives its plane back and is remembered as having none, and so is one
+// whose plane could not be allocated -- neither is an error, the int32 scan stays.  While a graph capture is open nothing is built
+// (the host has to wait for the span): the question stays open for the next query.
+static int ensure_hi16(imm3_ctx *ctx, const imm3_segment *cseg, int32_t col) {
+    imm3_segment *seg = const_cast<imm3_segment *>(cseg);
+    SegCol &sc = seg->cols[(size_t)col];
+    if (sc.codec != IMM3_DENSE_INT || sc.width != 4) return IMM3_OK;
+    std::lock_guard<std::mutex> g(seg->decode_mu);
+    if (sc.hi16_state != 0 || ctx->capture) return IMM3_OK;
+    const int64_t rows = (int64_t)(sc.bytes / 4);
+    const size_t bytes = (size_t)rows * 2 + kPad; // (the column's own slack: a tile's loads never leave the allocation)
+    void *p = nullptr, *pm = nullptr;
+    if (rows < 1 || hipMalloc(&p, bytes) != hipSuccess || hipMalloc(&pm, 2 * sizeof(int32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (p) (void)hipFree(p);
+        sc.hi16_state = -1;
+        return IMM3_OK;
+    }
+    int32_t min_max[2] = {32767, -32768};
+    hipError_t e = hipMemcpyAsync(pm, min_max, sizeof(min_max), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync((uint8_t *)p + (size_t)rows * 2, 0, kPad, ctx->stream);
+    if (e == hipSuccess) {
+        LaunchTimer t(ctx, 5);
+        launch_hi16_build((const int32_t *)sc.d_data, (int16_t *)p, rows, (int32_t *)pm, ctx->stream, t.start, t.stop);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(min_max, pm, sizeof(min_max), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(pm);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        HIPCHK(e);
+    }
+    if (!hi16_span_ok(min_max[0], min_max[1])) {
+        (void)hipFree(p);
+        sc.hi16_state = -1;
+        return IMM3_OK;
+    }
+    sc.d_hi16 = (uint8_t *)p;
+    sc.hi16_state = 1;
     seg->device_bytes += bytes;
     return IMM3_OK;
 }
@@ -1293,6 +1341,28 @@ static int place_compressed(imm3_query *q, bool have_batches, const std::vector<
     return IMM3_OK;
 }
 
+// Step 4b: the high-half planes this query's tile passes can scan (hi16_eligible with the run-time facts open).  A column that has
+// no plane yet gets one here.  A projection with a limit is left alone altogether: its runs scan in chunks over the column itself, and
+// it neither makes a plane nor takes one.  What creation found goes into the folded predicate; a run reads nothing else.
+static int place_hi16(imm3_query *q, bool have_batches) {
+    const int fv = q->ctx->filter_variant;
+    if (!have_batches || q->table || q->is_expr || q->ragged || q->always_false || fv == TV_I32_SCAN || fv == TV_GENERIC_ONLY) return IMM3_OK;
+    if (q->limit > 0 && !q->proj.empty()) return IMM3_OK;
+    const SelectChain chain = plan_select_chain(q);
+    for (const auto &take : chain.tile_passes)
+        for (const FoldedPred *cfp : take) {
+            if (tile_kind(*cfp) != TK_I32) continue;
+            Hi16Inputs in = hi16_inputs(q, *cfp, take);
+            in.has_plane = true; // (it may get one)
+            if (!hi16_eligible(in)) continue;
+            const int rc = ensure_hi16(q->ctx, q->seg, cfp->seg_col);
+            if (rc) return rc;
+            std::lock_guard<std::mutex> g(const_cast<imm3_segment *>(q->seg)->decode_mu);
+            pred_on(q->preds, cfp->seg_col)->d_hi16 = q->seg->cols[(size_t)cfp->seg_col].d_hi16;
+        }
+    return IMM3_OK;
+}
+
 // Step 5: IN-lists too long for the kernel arguments go to the device -- and so does the probe table of an int32 column's folded
 // IMM3_INT_IN list of more than kMaxMatch values (built here, once: imm3_int_list_plan.cpp; the list pass's LDS / GLOBAL forms and the
 // word-at-a-time kernels probe it); a shorter list travels as its values and an int8 column's list as its 256-bit set, both in the
@@ -1449,6 +1519,7 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
     if (nb >= 1 && (has_or || has_not)) { rc = fold_tree(q.get(), sels, n_sels, prog, n_prog); if (rc) return rc; }
     else if (nb >= 1) { rc = fold_selects(q.get(), sels, n_sels); if (rc) return rc; }
     rc = place_compressed(q.get(), nb >= 1, row_cols); if (rc) return rc;
+    rc = place_hi16(q.get(), nb >= 1); if (rc) return rc;
     if (table) // (a flat select list; a tree's terms are checked by expr_setup)
         for (const FoldedPred &p : q->preds)
             if (pred_route(p) == 2 && (p.has_range ? !q->always_false : !p.match.empty())) return fail(IMM3_ERR_ARG, p.has_range ? kTableRangeRefusal : kTableGenericRefusal);
@@ -2001,11 +2072,12 @@ extern "C" int imm3_query_device_ptr(imm3_query *q, int32_t which, void **ptr) {
 
 extern "C" int imm3_query_plan(const imm3_query *q, int64_t *out, int32_t n) {
     if (!q || !out) return fail(IMM3_ERR_ARG, "null argument");
-    const int64_t v[14] = {q->single_pass ? 1 : 0, q->sp_P, q->sp_grid, q->sp_spans, q->d_stage_rec ? 1 : 0,
+    const int64_t v[15] = {q->single_pass ? 1 : 0, q->sp_P, q->sp_grid, q->sp_spans, q->d_stage_rec ? 1 : 0,
                            (q->single_pass || q->d_stage_rec) ? rec_layout(q->stage_kinds, -1).dwords : 0, q->run.ran_single_pass ? 1 : 0, (int64_t)q->run_syncs,
                            (int64_t)q->sp_abandoned_runs, (int64_t)q->sp_busy_runs, (int64_t)q->limit_gather_gave_up,
-                           (int64_t)q->order_select_runs, (int64_t)q->order_full_runs, (int64_t)q->order_launches};
-    for (int32_t i = 0; i < n && i < 14; ++i) out[i] = v[i];
+                           (int64_t)q->order_select_runs, (int64_t)q->order_full_runs, (int64_t)q->order_launches,
+                           q->hi16_ran ? 1 : 0};
+    for (int32_t i = 0; i < n && i < 15; ++i) out[i] = v[i];
     return IMM3_OK;
 }
 

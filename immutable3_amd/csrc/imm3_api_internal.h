@@ -60,6 +60,7 @@ int run_order(imm3_query *q);                                        // an order
 int join_total(imm3_query *q, hipStream_t s);                        // make `s` wait for the count reduce on the aux stream
 void fill_colpred(const imm3_query *q, const FoldedPred &fp, ColPred &cp);
 void fill_tile_col(const imm3_query *q, const FoldedPred &fp, TileCol &c, int kind);
+Hi16Inputs hi16_inputs(const imm3_query *q, const FoldedPred &fp, const std::vector<const FoldedPred *> &take); // what hi16_eligible asks of a tile pass's int32 predicate (imm3_run.cpp)
 #ifdef IMM3_ABLATE
 int single_pass_lock_word(int device, unsigned long long **out);     // the device's ticket word of the single-pass kernel (imm3_ctx_debug_device_lock)
 #endif

@@ -76,6 +76,7 @@ enum TuningVariant : int {
     TV_ORDER_FULL_SORT = 23,    // an ordered query with a limit sorts every row: no radix select in front of the sort
     TV_ORDER_SELECT_ALWAYS = 24, // ... takes the radix select whenever the limit is below the survivors (the threshold sweep of tools/order_bench.py)
     TV_GROUP_ORDER_RADIX = 25,  // an ordered aggregation (imm3_query_set_group_order) takes the radix path whatever the group count: no one-work-group launch
+    TV_I32_SCAN = 26,           // int32 range predicates scan the column itself: no high-half plane is made or read (A/B runs of the tools)
     TV_TILE_ABLATION = 20,      // 20 .. 22: k_filter_tile's ablation switches (tools' build only)
     TV_EMIT_ABLATION = 34,      // 34 .. 35: k_emit's ablation switches (tools' build only)
     TV_PROJECT_ABLATION = 50,   // 50 + mask (mask <= 255): k_filter_project's ablation mask (tools' build only)
@@ -187,6 +188,11 @@ struct SegCol {
     uint32_t *d_block_off = nullptr;   // n_blocks + 1 byte offsets
     uint32_t *d_row_base = nullptr;    // n_blocks + 1 first rows
     uint8_t *d_dense = nullptr;        // decoded int32 column, made on first need (Project, aggregation, ragged, table)
+    // DENSE_INT: the 16-bit high-half plane, int16[rows] = (int16_t)(v >> 16), made the first time a query's plan wants it
+    // (ensure_hi16, imm3_api.cpp; guarded by the segment's decode_mu) and kept for the segment's life.  hi16_state: 0 = not asked
+    // yet, 1 = d_hi16 is there, -1 = the column gets none (its halves span fewer than kHi16MinSpan values, or no memory)
+    uint8_t *d_hi16 = nullptr;
+    int32_t hi16_state = 0;
 };
 
 // Batches of one segment as ScanOp yields them (Scan.scala:55,72; Segment.scala:159-168): block k of the FIRST used column holds
@@ -209,7 +215,7 @@ struct imm3_segment {
     std::vector<void *> registered;    // host ranges pinned in place for an asynchronous create (unpinned by imm3_segment_wait)
     hipEvent_t ready = nullptr;        // recorded on the context's copy stream behind the last column's copy
     std::atomic<bool> ready_pending{false}; // the copies may still be in flight: consumers make their stream wait for `ready`
-    std::mutex decode_mu;              // guards the lazy d_dense of PFOR_INT columns
+    std::mutex decode_mu;              // guards the lazy d_dense of PFOR_INT columns and the lazy d_hi16 of DENSE_INT ones
     std::mutex layout_mu;              // guards the two caches below
     std::map<int32_t, std::shared_ptr<const SegLayout>> layouts; // by first used column
     std::map<std::pair<int32_t, int32_t>, bool> same_blocks;     // (first column, other column) -> holds the same rows in the same blocks (checked once)
@@ -260,6 +266,7 @@ struct FoldedPred { // all SelectOp leaves on one segment column, folded
     uint32_t range_lo4[4] = {0, 0, 0, 0}, range_hi4[4] = {0, 0, 0, 0}; // ... their first 16 bytes as the string pass's kernel arguments (str_range_pack)
     uint8_t *d_blob = nullptr;             // device copy when it does not fit the kernel arguments
     bool pfor = false;                     // PFOR_INT column evaluated on its compressed blocks (k_filter_pfor)
+    const uint8_t *d_hi16 = nullptr;       // int32 interval: the column's high-half plane as creation found or made it (SegCol::d_hi16), null: none
 };
 // The predicate no leaf has narrowed yet, for a column of DENSE_* codec `codec`: an int32 / int8 interval every value passes; a
 // string's IN-list is the first leaf's.
@@ -379,6 +386,7 @@ struct imm3_query {
     imm3::ColPred *d_expr_preds = nullptr;
     int32_t *d_expr_term_start = nullptr;
     int32_t expr_form_ran = -1;             // diagnostics (imm3_query_expr_form): 0 = tile, 1 = generic, -1 before any launch
+    bool hi16_ran = false;                  // diagnostics (imm3_query_plan): a pass of the last select run scanned a high-half plane (TK_H16)
     bool expr_universal = false;            // the tree's normal form is the one term without a predicate: every row -- the query is the NoSelect form (is_expr stays false)
     bool count_log_on = false;              // imm3_query_log_counts is installed: every run logs the segment's count (a limit query then scans whole)
     // ORDER BY (imm3_query_set_order; imm3_order.hip): the projected rows ordered behind every emit, into arrays of their own

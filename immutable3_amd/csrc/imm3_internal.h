@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "imm3_int_list_plan.h"
+#include "imm3_hi16_plan.h"
 
 // Ablation switches ("what does the kernel cost without its stores?") exist only in the tools' build of the library
 // (make -C csrc ablate: -DIMM3_ABLATE -> lib/libimm3_ablate.so, loaded through IMM3_LIB_PATH).  In the shipped build
@@ -62,23 +63,36 @@ struct ColPred {
 };
 
 // ---- tile kernel (compile-time column kinds) ----
-enum TileKind : int32_t { TK_I32 = 0, TK_I8 = 1, TK_S2 = 2, TK_NONE = 3 };
+// The numbers are template arguments (they show in the kernels' names) and stay as they are; a launch's kinds are sorted by
+// tile_kind_rank(), in which TK_NONE stays last: TK_H16 ranks behind TK_S2, whose place it takes in the lane (lane_tile()).
+// TK_H16: a DENSE_INT column scanned over its 16-bit high-half plane (SegCol::d_hi16), exact through the full column where a half
+// does not decide (ColRegs<TK_H16>).  Segment select passes only: no records (rec_layout / ring_layout never see it), no table.
+enum TileKind : int32_t { TK_I32 = 0, TK_I8 = 1, TK_S2 = 2, TK_NONE = 3, TK_H16 = 4 };
+constexpr int tile_kind_rank(int kind) { return kind == TK_H16 ? 3 : (kind == TK_NONE ? 4 : kind); }
 constexpr int kMaxTileCols = 3;
 constexpr int kDeferLines = 64;     // bitmap lines a wave parks in LDS between store bursts (32 KiB per work-group)
 constexpr int kMaxTileMatch = 8;
 constexpr int kMaxArenaSlots = 256; // tiles per wave of a staging launch (the wave's start table sits in LDS)
 
 struct TileCol {
-    const void *data;               // flat column in HBM, 16-byte aligned
-    int32_t lo, hi;                 // TK_I32 / TK_I8: closed interval
+    const void *data;               // flat column in HBM, 16-byte aligned (TK_H16: the plane)
+    int32_t lo, hi;                 // TK_I32 / TK_I8 / TK_H16: closed interval
     int32_t n_match;                // TK_S2: IN-list size (1..kMaxTileMatch)
     int32_t negated;                // TK_S2, select trees only (k_filter_expr): 1 = keep the rows that equal NONE of the values
-    uint32_t match[kMaxTileMatch];  // TK_S2: the two value bytes, little-endian
+    uint32_t match[kMaxTileMatch];  // TK_S2: the two value bytes, little-endian; TK_H16: match[0..3] = the interval's windows over the halves (Hi16Bounds),
+                                    // match[4..5] = the int32 column itself (undecided rows, the partial tile): tile_col_full()
 };
+// TK_H16's pointer to the full column rides in two words of match[] that an int kind never uses: the record keeps the size and the
+// field offsets it had, so the code of every instance without a plane is what it was
+IMM3_HOST_DEVICE inline const void *tile_col_full(const TileCol &c) { return (const void *)(uintptr_t)(((uint64_t)c.match[5] << 32) | (uint64_t)c.match[4]); }
+inline void tile_col_set_full(TileCol &c, const void *full) {
+    c.match[4] = (uint32_t)(uintptr_t)full;
+    c.match[5] = (uint32_t)((uint64_t)(uintptr_t)full >> 32);
+}
 
 struct TileArgs {
     TileCol cols[kMaxTileCols];
-    int32_t kinds[kMaxTileCols];    // sorted ascending, TK_NONE last (selects the template instance)
+    int32_t kinds[kMaxTileCols];    // sorted by tile_kind_rank(), TK_NONE last (selects the template instance)
     int32_t and_existing;
     int32_t defer_lines;            // > 0: park the bitmap lines in (dynamic) LDS and store them in bursts (single segment only)
     int32_t ablate;                 // read only by the tools' build (IMM3_ABLATED below); 0 otherwise
@@ -692,6 +706,9 @@ struct PforArgs {
     int32_t *out;                 // decode: dense int32 column
     uint32_t *status;             // bit 0 set when a block is malformed
 };
+// k_hi16_build (imm3_kernels.hip): dst[i] = (int16_t)(src[i] >> 16) for i < n_rows; min_max = {smallest, largest} half (the caller
+// starts them at {32767, -32768})
+void launch_hi16_build(const int32_t *src, int16_t *dst, int64_t n_rows, int32_t *min_max, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 void launch_pfor_counts(const uint8_t *data, const uint32_t *block_off, int64_t n_blocks, int32_t *counts, hipStream_t s);
 void launch_filter_pfor(const PforArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 void launch_pfor_decode(const PforArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);

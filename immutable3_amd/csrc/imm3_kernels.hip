@@ -118,9 +118,58 @@ __device__ __forceinline__ void stage_full_tile(const TileArgs &a, int lane, con
 // bitmap word with two DPP moves: lane 4 w owns word w.  No LDS, no ballot, no v_writelane, ~55 instructions per tile.
 // With a 2-byte-string column among them the lanes keep TWO runs of 8 rows instead (8 l .. + 7 and 512 + 8 l .. + 7: what the string
 // column's dense 16-byte loads bring), eight neighbouring lanes make a word, and lane 8 w owns words w and 8 + w (lane_tile() == 2).
+// An int32 column over its high-half plane (TK_H16) takes the 2-byte-string column's place: the same two loads, the same two runs.
 constexpr int lane_tile(int k0, int k1, int k2, bool stage) {
-    if (stage || !(k0 == TK_I8 || k0 == TK_S2) || k1 == TK_I32 || k2 == TK_I32) return 0;
-    return (k0 == TK_S2 || k1 == TK_S2 || k2 == TK_S2) ? 2 : 1;
+    if (stage || !(k0 == TK_I8 || k0 == TK_S2 || k0 == TK_H16) || k1 == TK_I32 || k2 == TK_I32) return 0;
+    return (k0 == TK_S2 || k1 == TK_S2 || k2 == TK_S2 || k0 == TK_H16 || k1 == TK_H16 || k2 == TK_H16) ? 2 : 1;
+}
+
+// eight lanes' bytes -> one word, for both runs of the lane_tile() == 2 layout at once (byte 0 of m: rows 8 lane .. + 7, byte 1:
+// 512 + 8 lane .. + 7): pairs (byte permute), quads, then the upper quad's half.  Lane 8 w holds words w (a) and 8 + w (b).
+__device__ __forceinline__ void lane_runs_to_halves(uint32_t m, uint32_t &lo_a, uint32_t &lo_b, uint32_t &hi_a, uint32_t &hi_b) {
+    const uint32_t odd = (uint32_t)__builtin_amdgcn_mov_dpp((int)m, 0xF5, 0xF, 0xF, true);      // quad_perm [1,1,3,3]
+    const uint32_t x = __builtin_amdgcn_perm(odd, m, 0x05010400u);                                 // even lanes: {a, a', b, b'} (a: low run, b: high run)
+    const uint32_t y = (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xAA, 0xF, 0xF, true);         // quad_perm [2,2,2,2]
+    lo_a = __builtin_amdgcn_perm(y, x, 0x05040100u), lo_b = __builtin_amdgcn_perm(y, x, 0x07060302u); // lane 0 of a quad: 32 rows of each run
+    hi_a = (uint32_t)__builtin_amdgcn_mov_dpp((int)lo_a, 0x104, 0xF, 0xF, true);  // row_shl:4: the quad above
+    hi_b = (uint32_t)__builtin_amdgcn_mov_dpp((int)lo_b, 0x104, 0xF, 0xF, true);
+}
+__device__ __forceinline__ void lane_runs_to_words(uint32_t m, uint64_t &word_a, uint64_t &word_b) {
+    uint32_t lo_a, lo_b, hi_a, hi_b;
+    lane_runs_to_halves(m, lo_a, lo_b, hi_a, hi_b);
+    word_a = ((uint64_t)hi_a << 32) | (uint64_t)lo_a;
+    word_b = ((uint64_t)hi_b << 32) | (uint64_t)lo_b;
+}
+
+// The exact refine of a TK_H16 tile: `und` are the lane's rows that passed every column's test so far and whose half does not decide.
+// Their words are put together as the tile's own are; for each of the 16 words with such a row the lanes of those rows load the full
+// value (ColRegs<TK_I32>'s row-strided dword load, under the word as exec mask), compare it exactly, and the word's owner lane clears
+// the rows that fail.  Sixteen steps whatever the data: a fully undecided tile costs the int32 tile's 16 loads, one undecided row one.
+__device__ __forceinline__ void refine_undecided(const TileCol &c, int64_t row0, int lane, uint32_t und, uint64_t &word_a, uint64_t &word_b) {
+    uint64_t und_a, und_b;
+    lane_runs_to_words(und, und_a, und_b);
+    const IMM3_GLOBAL int32_t *full = (const IMM3_GLOBAL int32_t *)tile_col_full(c) + row0 + lane;
+    uint64_t u[kTileWords]; // wave-uniform: word j's undecided rows
+    int32_t v[kTileWords];
+    // every load first, the compares behind them: the words' loads are in flight together, not one round trip after the other
+#pragma unroll
+    for (int j = 0; j < kTileWords; ++j) {
+        const int owner = 8 * (j & 7);
+        const uint64_t mine = j < kTileWords / 2 ? und_a : und_b;
+        u[j] = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(mine >> 32), owner) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mine, owner);
+        v[j] = 0;
+        if (u[j] != 0ULL) // wave-uniform
+            if ((u[j] >> lane) & 1ULL) v[j] = full[64 * j];
+    }
+#pragma unroll
+    for (int j = 0; j < kTileWords; ++j) {
+        if (u[j] == 0ULL) continue; // wave-uniform
+        const uint64_t keep = ~u[j] | ballot64(in_closed(v[j], c.lo, c.hi));
+        if (lane == 8 * (j & 7)) {
+            if (j < kTileWords / 2) word_a &= keep;
+            else word_b &= keep;
+        }
+    }
 }
 
 template <int LANE, int K>
@@ -138,17 +187,24 @@ __device__ __forceinline__ uint32_t finish_full_tile(const TileArgs &a, int64_t 
                                                      int64_t wave_id, uint64_t *park = nullptr, const uint64_t *earlier = nullptr) {
     if constexpr (lane_tile(K0, K1, K2, STAGE) == 2) {
         const uint32_t m = c0.lane_mask(a.cols[0]) & c1.lane_mask(a.cols[1]) & c2.lane_mask(a.cols[2]); // byte 0: rows 8 lane .. + 7, byte 1: 512 + 8 lane .. + 7
-        if (!a.bitmap) return (uint32_t)__popc(m); // count-only run (wave-uniform): every lane counts its own rows
-        // eight lanes' bytes -> one word, for both runs at once: pairs (byte permute), quads, then the upper quad's half
-        const uint32_t odd = (uint32_t)__builtin_amdgcn_mov_dpp((int)m, 0xF5, 0xF, 0xF, true);      // quad_perm [1,1,3,3]
-        const uint32_t x = __builtin_amdgcn_perm(odd, m, 0x05010400u);                                 // even lanes: {a, a', b, b'} (a: low run, b: high run)
-        const uint32_t y = (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xAA, 0xF, 0xF, true);         // quad_perm [2,2,2,2]
-        const uint32_t lo_a = __builtin_amdgcn_perm(y, x, 0x05040100u), lo_b = __builtin_amdgcn_perm(y, x, 0x07060302u); // lane 0 of a quad: 32 rows of each run
-        const uint32_t hi_a = (uint32_t)__builtin_amdgcn_mov_dpp((int)lo_a, 0x104, 0xF, 0xF, true);  // row_shl:4: the quad above
-        const uint32_t hi_b = (uint32_t)__builtin_amdgcn_mov_dpp((int)lo_b, 0x104, 0xF, 0xF, true);
+        // TK_H16: the rows whose half sits on a boundary of the interval (and that no other column has failed) need their full value
+        constexpr int kH16 = K0 == TK_H16 ? 0 : (K1 == TK_H16 ? 1 : (K2 == TK_H16 ? 2 : -1));
+        bool refine = false; // wave-uniform
+        uint32_t und = 0;
+        if constexpr (kH16 >= 0) {
+            und = m & (lane_undecided(c0) | lane_undecided(c1) | lane_undecided(c2));
+            refine = ballot64(und != 0u) != 0ULL;
+        }
+        if (!a.bitmap && !refine) return (uint32_t)__popc(m); // count-only run (wave-uniform): every lane counts its own rows
+        uint32_t lo_a, lo_b, hi_a, hi_b;
+        lane_runs_to_halves(m, lo_a, lo_b, hi_a, hi_b);
         const bool owner = (lane & 7) == 0; // lane 8 w owns words w and 8 + w: 8 lanes x 8 B = half a line, twice
         const int64_t wl = tile * kTileWords + (lane >> 3);
         uint64_t word_a = ((uint64_t)hi_a << 32) | (uint64_t)lo_a, word_b = ((uint64_t)hi_b << 32) | (uint64_t)lo_b;
+        if constexpr (kH16 >= 0) {
+            if (refine) refine_undecided(a.cols[kH16], tile * kTileRows, lane, und, word_a, word_b); // (segment instances only: tile t starts at row 1024 t)
+            if (!a.bitmap) return owner ? (uint32_t)(__popcll(word_a) + __popcll(word_b)) : 0u; // (a count-only run whose tile needed the refine)
+        }
         if (a.and_existing) { // (the pipelined loop does not prefetch the earlier words for this layout: `earlier` is null)
             word_a &= owner ? a.bitmap[wl] : 0ULL;
             word_b &= owner ? a.bitmap[wl + kTileWords / 2] : 0ULL;
@@ -435,7 +491,7 @@ __global__ __launch_bounds__(kBlockThreads, tile_min_waves(K0, K1, STAGE)) void 
             tile_load<kLane>(c2, a.cols[2].data, row0, lane);
             lane_total += finish_full_tile<K0, K1, K2, STAGE>(a, tile, lane, c0, c1, c2, xp, lds, tstart, A, wave_id);
         } else { // rolled, bounds-checked
-            lane_total += partial_tile<K0, K1, K2, STAGE>(a, tile, lane, a.cols[0].data, a.cols[1].data, a.cols[2].data, row0, a.n_rows - row0, c0, c1, c2, lds, tstart, A, wave_id);
+            lane_total += partial_tile<K0, K1, K2, STAGE>(a, tile, lane, tile_rows_ptr<K0>(a.cols[0]), tile_rows_ptr<K1>(a.cols[1]), tile_rows_ptr<K2>(a.cols[2]), row0, a.n_rows - row0, c0, c1, c2, lds, tstart, A, wave_id);
         }
     }
     if constexpr (STAGE) {
@@ -1110,7 +1166,17 @@ int filter_grid(int64_t units, bool generic, bool any_i32, int grid_blocks, int 
         return true;                                                                            \
     }
 
-// kinds must be sorted ascending with TK_NONE (= 3) last; at most one TK_S2 column per launch.
+// The high-half plane's instances: segment launches without records, with and without parked bitmap lines.  Nothing else exists.
+#define IMM3_TILE_CASE_H16(k0, k1, k2, T)                                                       \
+    if (a.kinds[0] == k0 && a.kinds[1] == k1 && a.kinds[2] == k2) {                             \
+        if (a.stage_rec || a.tile_rows || a.chunked || (!a.bitmap && a.defer_lines)) return false; \
+        else if (a.defer_lines) IMM3_LAUNCH_LDS((k_filter_tile<k0, k1, k2, T, false, true, false>), grid, kBlockThreads,       \
+                             (size_t)kWavesPerBlock * (size_t)a.defer_lines * kTileWords * sizeof(uint64_t), s, ev0, ev1, a); \
+        else IMM3_LAUNCH((k_filter_tile<k0, k1, k2, T, false, false, false>), grid, kBlockThreads, s, ev0, ev1, a); \
+        return true;                                                                            \
+    }
+
+// kinds must be sorted by tile_kind_rank() with TK_NONE last; at most one TK_S2 column per launch.
 // T (tiles per wave iteration): 2 for the lone int8 column (1 KiB tiles), 1 elsewhere -- the pipelined loop keeps the next group's
 // loads in flight under the current group's evaluation, and filter_grid() sizes the launch to the bytes per row.  (Round 5 measured
 // T = 4 / 2 / 2 / 2 for I8, S2, I8+I8, I8+S2 at half the work-groups: the same or slower.)
@@ -1122,8 +1188,12 @@ int filter_grid(int64_t units, bool generic, bool any_i32, int grid_blocks, int 
     X(TK_I32, TK_I32, TK_I32, 1) X(TK_I32, TK_I32, TK_I8, 1) X(TK_I32, TK_I8, TK_I8, 1)              \
     X(TK_I8, TK_I8, TK_I8, 2) X(TK_I32, TK_I32, TK_S2, 1) X(TK_I32, TK_I8, TK_S2, 1) X(TK_I8, TK_I8, TK_S2, 1)
 
+// ... and the plane's: the lone column (TK_S2's geometry: one tile per iteration, filter_grid's 768 work-groups) and int8 + int32
+#define IMM3_TILE_KINDS_H16(X) X(TK_H16, TK_NONE, TK_NONE, 1) X(TK_I8, TK_H16, TK_NONE, 1)
+
 bool launch_filter_tile(const TileArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     IMM3_TILE_KINDS(IMM3_TILE_CASE)
+    IMM3_TILE_KINDS_H16(IMM3_TILE_CASE_H16)
     return false;
 }
 
@@ -1140,11 +1210,57 @@ bool launch_filter_table_limit(const TileArgs &a, int grid, hipStream_t s, hipEv
     return false;
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_hi16_build: the 16-bit high-half plane of a DENSE_INT column (SegCol::d_hi16), once per column: one read of the column (two
+// 16-byte loads = 8 rows per thread), one 16-byte store, and the smallest and largest half for the rule that says whether the column
+// keeps its plane (hi16_span_ok).  The rows behind the last whole group of 8 go one per thread.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlockThreads) void k_hi16_build(const int32_t *src, int16_t *dst, int64_t n_rows, int32_t *min_max) {
+    const int64_t n8 = n_rows / 8;
+    int32_t mn = 32767, mx = -32768;
+    const IMM3_GLOBAL v4i *in = (const IMM3_GLOBAL v4i *)src;
+    IMM3_GLOBAL v4i *out = (IMM3_GLOBAL v4i *)dst;
+    for (int64_t i = (int64_t)blockIdx.x * kBlockThreads + threadIdx.x; i < n8; i += (int64_t)gridDim.x * kBlockThreads) {
+        const v4i x = __builtin_nontemporal_load(in + 2 * i), y = __builtin_nontemporal_load(in + 2 * i + 1);
+        const int32_t h[8] = {x[0] >> 16, x[1] >> 16, x[2] >> 16, x[3] >> 16, y[0] >> 16, y[1] >> 16, y[2] >> 16, y[3] >> 16};
+        v4i o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            o[k] = (int32_t)(((uint32_t)h[2 * k] & 0xFFFFu) | ((uint32_t)h[2 * k + 1] << 16));
+            mn = min(mn, min(h[2 * k], h[2 * k + 1]));
+            mx = max(mx, max(h[2 * k], h[2 * k + 1]));
+        }
+        out[i] = o;
+    }
+    const int64_t tail = 8 * n8 + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x < 8 && tail < n_rows) {
+        const int32_t h = src[tail] >> 16;
+        dst[tail] = (int16_t)h;
+        mn = min(mn, h);
+        mx = max(mx, h);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        mn = min(mn, __shfl_xor(mn, d));
+        mx = max(mx, __shfl_xor(mx, d));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicMin(min_max, mn);
+        atomicMax(min_max + 1, mx);
+    }
+}
+
+void launch_hi16_build(const int32_t *src, int16_t *dst, int64_t n_rows, int32_t *min_max, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    const int grid = clamp_grid((n_rows / 8 + kBlockThreads - 1) / kBlockThreads, 2048);
+    IMM3_LAUNCH(k_hi16_build, grid, kBlockThreads, s, ev0, ev1, src, dst, n_rows, min_max);
+}
+
 // tiles per wave iteration of the instance launch_filter_tile picks for these kinds (0: no such instance)
 int filter_tile_group(const int32_t *kinds) {
 #define IMM3_TILE_T(k0, k1, k2, T) \
     if (kinds[0] == k0 && kinds[1] == k1 && kinds[2] == k2) return T;
     IMM3_TILE_KINDS(IMM3_TILE_T)
+    IMM3_TILE_KINDS_H16(IMM3_TILE_T)
 #undef IMM3_TILE_T
     return 0;
 }

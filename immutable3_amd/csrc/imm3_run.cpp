@@ -97,7 +97,7 @@ template <class Args> static void fill_pass_tail(const imm3_query *q, const Sele
     fill_bitmap_tail(q, a);
 }
 
-static int tile_kind_bytes(int kind) { return kind == TK_I32 ? 4 : (kind == TK_S2 ? 2 : (kind == TK_I8 ? 1 : 0)); }
+static int tile_kind_bytes(int kind) { return kind == TK_I32 ? 4 : ((kind == TK_S2 || kind == TK_H16) ? 2 : (kind == TK_I8 ? 1 : 0)); } // (TK_H16: what the scan streams, the plane)
 
 // what filter_grid asks about a tile launch's columns: an int32 column among them, else the bytes per row of the narrow ones
 struct TileGridHint {
@@ -219,6 +219,55 @@ static int launch_tree_pass(imm3_query *q, SelectRun &run) {
     return IMM3_OK;
 }
 
+// what hi16_eligible (imm3_hi16_plan.h) asks about the int32 predicate `fp` of a tile pass over `take`; creation (imm3_api.cpp:
+// place_hi16) asks the same with the run-time facts left false
+imm3::Hi16Inputs imm3::hi16_inputs(const imm3_query *q, const FoldedPred &fp, const std::vector<const FoldedPred *> &take) {
+    Hi16Inputs in;
+    in.table = q->table != nullptr;
+    in.tree = q->is_expr;
+    in.ragged = q->ragged;
+    in.dense_int = q->seg->cols[(size_t)fp.seg_col].codec == IMM3_DENSE_INT;
+    in.has_list = fp.has_list;
+    in.has_plane = fp.d_hi16 != nullptr;
+    for (const FoldedPred *p : take) {
+        const int tk = tile_kind(*p);
+        in.n_i32 += tk == TK_I32;
+        in.n_i8 += tk == TK_I8;
+        in.n_s2 += tk == TK_S2;
+    }
+    return in;
+}
+
+// The pass's int32 column becomes TK_H16 -- the scan reads its 16-bit high-half plane, 2 bytes per row, and the full column only where a
+// half does not decide -- when hi16_eligible says so.  The kinds stay sorted (tile_kind_rank): the plane goes behind an int8 column.
+static void take_hi16_plane(imm3_query *q, const SelectRun &run, const std::vector<const FoldedPred *> &take, TileArgs &a) {
+    for (int k = 0; k < (int)take.size() && k < kMaxTileCols; ++k) {
+        if (a.kinds[k] != TK_I32) continue;
+        const FoldedPred &fp = *take[(size_t)k];
+        if (!fp.d_hi16) return; // (creation found or made no plane: nothing to decide)
+        Hi16Inputs in = hi16_inputs(q, fp, take);
+        in.stages = a.stage_rec != nullptr;
+        in.chunked = run.chunked || (q->limit > 0 && run.count_in_scan && !(run.mode & SEL_WHOLE)); // (the select of a projection with a limit: its chunks, or the one launch of a segment the first chunk covers)
+        in.pinned_i32 = run.fv == TV_I32_SCAN;
+        if (!hi16_eligible(in)) return;
+        TileCol &c = a.cols[k];
+        tile_col_set_full(c, c.data);
+        c.data = fp.d_hi16;
+        const Hi16Bounds b = hi16_bounds(c.lo, c.hi);
+        c.match[0] = b.possible_first;
+        c.match[1] = b.possible_count;
+        c.match[2] = b.certain_first;
+        c.match[3] = b.certain_count;
+        a.kinds[k] = TK_H16;
+        for (int j = k; j + 1 < kMaxTileCols && tile_kind_rank(a.kinds[j + 1]) < tile_kind_rank(a.kinds[j]); ++j) {
+            std::swap(a.kinds[j], a.kinds[j + 1]);
+            std::swap(a.cols[j], a.cols[j + 1]);
+        }
+        q->hi16_ran = true;
+        return; // (one int32 column per instance)
+    }
+}
+
 // The arguments of one tile pass over the columns of `take`, and with them what the pass decides for the run: whether it stages
 // survivor records, stores a bitmap, reduces the count itself; run.grid is the grid of a launch over the whole segment.
 static int fill_tile_args(imm3_query *q, SelectRun &run, const std::vector<const FoldedPred *> &take, TileArgs &a) {
@@ -242,6 +291,7 @@ static int fill_tile_args(imm3_query *q, SelectRun &run, const std::vector<const
         a.max_slots = q->stage_max_slots;
         q->run.stage_written = true;
     }
+    take_hi16_plane(q, run, take, a);
     a.ablate = tile_ablation(run.fv); // (tools' build only)
     fill_pass_tail(q, run, a);
     // A records run whose offsets scan follows (imm3_query_run of a projection) stores NO bitmap: the records carry the positions
@@ -540,6 +590,7 @@ int imm3::run_select(imm3_query *q, unsigned mode) {
     }
     q->run.offsets_valid = false; // (a new bitmap)
     q->run.select_partial = false;
+    q->hi16_ran = false;
     q->run.agg_select_skipped = false; // (... and a new count: a fused aggregation's select is no longer owed -- behind imm3_query_run_count imm3_query_bitmap refuses, it does not run the chain)
     if (q->always_false || q->n_tiles == 0) {
         // an empty interval / empty IN-list clears every bit; nothing to read

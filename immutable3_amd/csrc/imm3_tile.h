@@ -281,6 +281,78 @@ struct ColRegs<TK_S2> {
     }
 };
 
+// A DENSE_INT column over its 16-bit high-half plane (SegCol::d_hi16: (int16_t)(v >> 16) per row).  In-lane only, with TK_S2's loads
+// and TK_S2's place in the lane: raw[0] = the halves of rows 8 lane .. + 7, raw[1] = of rows 512 + 8 lane .. + 7.  lane_mask() is the
+// POSSIBLE mask (the half lies within the interval's boundary halves) and leaves in `und` the rows among them whose half does not
+// decide (a boundary half: imm3_hi16_plan.h); finish_full_tile compares those rows' full values in the same launch.
+// Per row: the half minus each window's first half (v_pk_sub_u16, two rows per instruction), one unsigned compare against each
+// window's count (SDWA word select) and one add-with-carry per mask -- 5 vector instructions per row, 2.5 per byte scanned.
+template <>
+struct ColRegs<TK_H16> {
+    v4i raw[2];
+    uint32_t und; // after lane_mask(): bit k = row k of the lane's sixteen is possible and not certain
+    __device__ __forceinline__ void load(const void *data, int64_t row0, int lane) {
+        const IMM3_GLOBAL v4i *p = (const IMM3_GLOBAL v4i *)((const IMM3_GLOBAL uint16_t *)data + row0) + lane;
+        raw[0] = __builtin_nontemporal_load(p);
+        raw[1] = __builtin_nontemporal_load(p + 64);
+    }
+    __device__ __forceinline__ void touch() { asm volatile("" : "+v"(raw[0]), "+v"(raw[1])); }
+    static constexpr int kLoads = 2;
+    __device__ __forceinline__ void keep() const { asm volatile("" ::"v"(raw[0]), "v"(raw[1])); }
+    __device__ __forceinline__ void load_lane_rows(const void *data, int64_t row0, int lane) { load(data, row0, lane); } // (never alone in that layout: lane_tile())
+    __device__ __forceinline__ void load_lane_rows_split(const void *data, int64_t row0, int lane) { load(data, row0, lane); }
+    // the transposing form never takes this kind (lane_tile()): its hooks are empty
+    __device__ __forceinline__ void eval(const TileCol &, uint64_t (&)[kTileWords], int, uint8_t *) {}
+    __device__ __forceinline__ void stage(int, uint8_t *) {}
+    __device__ __forceinline__ void test(const TileCol &, uint64_t (&)[kTileWords]) {}
+    __device__ __forceinline__ uint32_t value(int) const { return 0u; }
+    // the partial tile goes row by row over the FULL column (partial_tile is handed tile_col_full() for this kind: tile_rows_ptr)
+    __device__ __forceinline__ bool row(const void *full, const TileCol &c, int64_t r) { return in_closed(((const IMM3_GLOBAL int32_t *)full)[r], c.lo, c.hi); }
+    __device__ __forceinline__ uint32_t rowval(const void *full, int64_t r) const { return ((const IMM3_GLOBAL uint32_t *)full)[r]; }
+    // four rows (two dwords) per asm block, both masks: as ColRegs<TK_I8>::rows4, every compare's mask three instructions away from its reader
+    static __device__ __forceinline__ void rows4(uint32_t &p, uint32_t &c, int32_t d_hi, int32_t d_lo, uint32_t p_first2, uint32_t p_count, uint32_t c_first2, uint32_t c_count) {
+        uint32_t ta, tb, ua, ub;
+        uint64_t s0, s1, s2, s3;
+        asm("v_pk_sub_u16 %[ta], %[a], %[pf]\n\t"
+            "v_pk_sub_u16 %[tb], %[b], %[pf]\n\t"
+            "v_pk_sub_u16 %[ua], %[a], %[cf]\n\t"
+            "v_pk_sub_u16 %[ub], %[b], %[cf]\n\t"
+            "v_cmp_lt_u32_sdwa %[s0], %[ta], %[pn] src0_sel:WORD_1 src1_sel:DWORD\n\t"
+            "v_cmp_lt_u32_sdwa %[s1], %[ta], %[pn] src0_sel:WORD_0 src1_sel:DWORD\n\t"
+            "v_cmp_lt_u32_sdwa %[s2], %[tb], %[pn] src0_sel:WORD_1 src1_sel:DWORD\n\t"
+            "v_cmp_lt_u32_sdwa %[s3], %[tb], %[pn] src0_sel:WORD_0 src1_sel:DWORD\n\t"
+            "v_addc_co_u32_e64 %[p], %[s0], %[p], %[p], %[s0]\n\t"
+            "v_addc_co_u32_e64 %[p], %[s1], %[p], %[p], %[s1]\n\t"
+            "v_addc_co_u32_e64 %[p], %[s2], %[p], %[p], %[s2]\n\t"
+            "v_addc_co_u32_e64 %[p], %[s3], %[p], %[p], %[s3]\n\t"
+            "v_cmp_lt_u32_sdwa %[s0], %[ua], %[cn] src0_sel:WORD_1 src1_sel:DWORD\n\t"
+            "v_cmp_lt_u32_sdwa %[s1], %[ua], %[cn] src0_sel:WORD_0 src1_sel:DWORD\n\t"
+            "v_cmp_lt_u32_sdwa %[s2], %[ub], %[cn] src0_sel:WORD_1 src1_sel:DWORD\n\t"
+            "v_cmp_lt_u32_sdwa %[s3], %[ub], %[cn] src0_sel:WORD_0 src1_sel:DWORD\n\t"
+            "v_addc_co_u32_e64 %[c], %[s0], %[c], %[c], %[s0]\n\t"
+            "v_addc_co_u32_e64 %[c], %[s1], %[c], %[c], %[s1]\n\t"
+            "v_addc_co_u32_e64 %[c], %[s2], %[c], %[c], %[s2]\n\t"
+            "v_addc_co_u32_e64 %[c], %[s3], %[c], %[c], %[s3]"
+            : [p] "+v"(p), [c] "+v"(c), [ta] "=&v"(ta), [tb] "=&v"(tb), [ua] "=&v"(ua), [ub] "=&v"(ub), [s0] "=&s"(s0), [s1] "=&s"(s1), [s2] "=&s"(s2), [s3] "=&s"(s3)
+            : [a] "v"(d_hi), [b] "v"(d_lo), [pf] "s"(p_first2), [pn] "s"(p_count), [cf] "s"(c_first2), [cn] "s"(c_count));
+    }
+    __device__ __forceinline__ uint32_t lane_mask(const TileCol &col) {
+        const uint32_t pf = col.match[0] | (col.match[0] << 16), pn = col.match[1], cf = col.match[2] | (col.match[2] << 16), cn = col.match[3];
+        uint32_t p = 0, c = 0;
+        rows4(p, c, raw[1][3], raw[1][2], pf, pn, cf, cn); // (row 15 first: each step shifts the rows so far up)
+        rows4(p, c, raw[1][1], raw[1][0], pf, pn, cf, cn);
+        rows4(p, c, raw[0][3], raw[0][2], pf, pn, cf, cn);
+        rows4(p, c, raw[0][1], raw[0][0], pf, pn, cf, cn);
+        und = p & ~c;
+        return p;
+    }
+};
+
+// the undecided rows of a tile's columns in the lane layout (only TK_H16 has any), and the pointer partial_tile walks row by row
+template <int K> __device__ __forceinline__ uint32_t lane_undecided(const ColRegs<K> &) { return 0u; }
+template <> __device__ __forceinline__ uint32_t lane_undecided<TK_H16>(const ColRegs<TK_H16> &c) { return c.und; }
+template <int K> __device__ __forceinline__ const void *tile_rows_ptr(const TileCol &c) { return K == TK_H16 ? tile_col_full(c) : c.data; }
+
 // ---- survivor records ---------------------------------------------------------------------------------------
 // A projecting query whose select chain is ONE tile launch compacts, per tile, one RECORD per survivor -- its position
 // in the tile and the value of every predicate column, all of which are in registers here -- through a per-wave LDS

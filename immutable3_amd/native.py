@@ -72,6 +72,7 @@ DIAG_EXPORTS = [
     "imm3_ctx_inject_fault", "imm3_ctx_debug_device_lock", "imm3_plan_predict", "imm3_comm_debug_standin", "imm3_plan_limit_scan",
     "imm3_plan_table_limit", "imm3_plan_string_route", "imm3_plan_string_range_route", "imm3_plan_limit_chunks", "imm3_plan_distinct_capacity",
     "imm3_plan_int_list_table", "imm3_plan_int_list_form", "imm3_plan_int_list_probe",
+    "imm3_plan_hi16_bounds", "imm3_plan_hi16_class", "imm3_plan_hi16_span_ok", "imm3_plan_hi16_eligible",
     "imm3_query_agg_form", "imm3_query_expr_form", "imm3_expr_normalize", "imm3_query_group_order_path",
     "imm3_query_group_filter_stats", "imm3_group_filter_check", "imm3_comm_merge_view_path", "imm3_merge_view_plan_json",
 ]
@@ -88,6 +89,7 @@ GROUP_ORDER_SMALL_MAX = 2048   # groups the one-work-group launch takes (csrc/im
 GROUP_FILTER_COUNT = -1
 GROUP_FILTER_MAX_LEAVES, GROUP_FILTER_MAX_PROG = 8, 32
 GROUP_FILTER_LEAF = np.dtype([("agg", "<i4"), ("average", "<i4"), ("cond", "<i4"), ("value", "<i8")], align=True)
+TV_I32_SCAN = 26               # tuning variant: int32 range predicates scan the column itself, no high-half plane (csrc/imm3_handles.h)
 TV_GROUP_ORDER_RADIX = 25      # tuning variant: an ordered aggregation takes the radix path whatever its group count
 TV_ORDER_FULL_SORT, TV_ORDER_SELECT_ALWAYS = 23, 24   # tuning variants (csrc/imm3_handles.h): an ordered query with a limit always sorts every row / always selects
 
@@ -709,6 +711,44 @@ def plan_int_list_form(width: int, n: int) -> int:
     return int(L.imm3_plan_int_list_form(width, n))
 
 
+# the 16-bit high-half plane (include/imm3_diag.h, csrc/imm3_hi16_plan.h)
+HI16_FAIL, HI16_PASS, HI16_UNDECIDED = 0, 1, 2
+HI16_MIN_SPAN = 64
+HI16_FLAGS = ("table", "tree", "ragged", "dense_int", "has_list", "stages", "chunked", "has_plane", "pinned_i32")
+
+
+def plan_hi16_bounds(lo: int, hi: int):
+    """imm3_plan_hi16_bounds -- (possible_first, possible_count, certain_first, certain_count) of [lo, hi] over the halves v >> 16."""
+    L = load()
+    L.imm3_plan_hi16_bounds.argtypes = [C.c_int32, C.c_int32, C.c_void_p]
+    out = np.zeros(4, np.uint32)
+    _check(L.imm3_plan_hi16_bounds(lo, hi, out.ctypes.data))
+    return tuple(int(x) for x in out)
+
+
+def plan_hi16_class(lo: int, hi: int, half: int) -> int:
+    """imm3_plan_hi16_class -- HI16_FAIL / HI16_PASS / HI16_UNDECIDED for a row whose half (v >> 16) is `half`."""
+    L = load()
+    L.imm3_plan_hi16_class.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    return int(L.imm3_plan_hi16_class(lo, hi, half))
+
+
+def plan_hi16_span_ok(min_half: int, max_half: int) -> bool:
+    L = load()
+    L.imm3_plan_hi16_span_ok.argtypes = [C.c_int32, C.c_int32]
+    return bool(L.imm3_plan_hi16_span_ok(min_half, max_half))
+
+
+def plan_hi16_eligible(n_i32=1, n_i8=0, n_s2=0, **facts) -> bool:
+    """imm3_plan_hi16_eligible -- does a tile pass's int32 predicate scan the plane; facts: the names of HI16_FLAGS."""
+    L = load()
+    L.imm3_plan_hi16_eligible.argtypes = [C.c_uint32, C.c_int32, C.c_int32, C.c_int32]
+    flags = 0
+    for name, on in facts.items():
+        flags |= (1 << HI16_FLAGS.index(name)) if on else 0
+    return bool(L.imm3_plan_hi16_eligible(flags, n_i32, n_i8, n_s2))
+
+
 def plan_int_list_table(values):
     """include/imm3_diag.h: imm3_plan_int_list_table -- (slots int32[], empty, max_probe): the open-addressing table query creation
     builds for these int32 values; a pure function, no device needed."""
@@ -968,12 +1008,13 @@ class DeviceQuery:
 
     def plan(self) -> dict:
         """How the library planned this query (include/imm3_diag.h: imm3_query_plan)."""
-        v = np.zeros(14, np.int64)
-        _check(load().imm3_query_plan(self._h, v.ctypes.data, 14))
+        v = np.zeros(15, np.int64)
+        _check(load().imm3_query_plan(self._h, v.ctypes.data, 15))
         return {"single_pass": bool(v[0]), "P": int(v[1]), "grid": int(v[2]), "spans": int(v[3]), "records": bool(v[4]),
                 "rec_dwords": int(v[5]), "ran_single_pass": bool(v[6]), "run_syncs": int(v[7]),
                 "abandoned_runs": int(v[8]), "busy_runs": int(v[9]), "limit_gather_gave_up": int(v[10]),
-                "order_select_runs": int(v[11]), "order_full_runs": int(v[12]), "order_launches": int(v[13])}
+                "order_select_runs": int(v[11]), "order_full_runs": int(v[12]), "order_launches": int(v[13]),
+                "hi16_plane": bool(v[14])}
 
     def agg_form(self) -> int:
         """The kernel form (AGG_FORM_*) of this aggregation's last launch, -1 before the first (include/imm3_diag.h)."""

@@ -62,7 +62,8 @@ int imm3_ctx_measure_read_gbps(imm3_ctx *ctx, uint64_t bytes, int32_t iters, dou
  * materialised when imm3_query_bitmap asks), 23 = an ordered query with a limit sorts every row (no radix select: the
  * yardstick of tests/test_gpu_zz_perf_order.py), 24 = it takes the radix select whenever the limit is below the survivors (both also
  * pin the radix path of imm3_query_set_group_order), 25 = an ordered aggregation takes the radix path whatever its group count (no
- * one-work-group launch: the yardstick of tests/test_gpu_zz_perf_group_order.py), 20 - 22 and 34 - 35 = ablation switches of k_filter_tile and k_emit (tools' build,
+ * one-work-group launch: the yardstick of tests/test_gpu_zz_perf_group_order.py), 26 = int32 range predicates scan the column itself (no
+ * 16-bit high-half plane is made at creation or read by a run: A/B runs of the tools), 20 - 22 and 34 - 35 = ablation switches of k_filter_tile and k_emit (tools' build,
  * libimm3_ablate.so, only), 50 + mask = ablation mask of k_filter_project (tools' build), 100 + AggForm = the aggregation starts at
  * that kernel form, 140 and above = aggregation ablations (tools' build), 200 + P = fixed tiles per range.  The names of these
  * numbers are csrc/imm3_handles.h's TuningVariant. */
@@ -87,7 +88,9 @@ int imm3_plan_predict(int64_t n_rows, const int32_t *pred_width, const int32_t *
  * gathered the rows again with k_scan + k_gather.
  * Ordered queries (imm3_query_set_order), the tail: out[11] / out[12] = ordered runs, as far as a row getter has settled them, that
  * took the radix select in front of the sort (0 < limit, survivors >= 4 x limit) / that sorted every row; out[13] = times the order
- * has been enqueued (once per run, once more whenever a getter had to emit the rows again).  n <= 14 values. */
+ * has been enqueued (once per run, once more whenever a getter had to emit the rows again).
+ * out[14] = 1 when a pass of the last select run scanned an int32 column over its 16-bit high-half plane (the TK_H16 tile kind), 0 when
+ * every int32 predicate read the column itself.  n <= 15 values. */
 int imm3_query_plan(const imm3_query *q, int64_t *out, int32_t n);
 
 /* imm3_query_agg_form: the kernel form of an aggregation's last launch (csrc/imm3_internal.h's AggForm: 0 = lanes (63 keys), 1 = lanes
@@ -202,6 +205,20 @@ int imm3_plan_string_range_route(int32_t width);
 int imm3_plan_int_list_table(const int32_t *values, int64_t n, int32_t *slots_out, int64_t cap, int64_t *n_slots, int32_t *empty, int32_t *max_probe);
 int imm3_plan_int_list_form(int32_t width, int64_t n);
 int imm3_plan_int_list_probe(const int32_t *slots, int64_t n_slots, int32_t empty, int32_t max_probe, int32_t v);
+/* The 16-bit high-half plane of a DENSE_INT column (csrc/imm3_hi16_plan.cpp, pure).  imm3_plan_hi16_bounds: the closed interval
+ * [lo, hi] over the halves v >> 16 as two windows of 16-bit wrap-around arithmetic, out4 = {possible_first, possible_count,
+ * certain_first, certain_count}: a half h is in a window when (uint16_t)(h - first) < count; outside the possible window a row fails,
+ * inside the certain window it passes, in between its full value is compared.
+ * imm3_plan_hi16_class: what that says of one half (-32768 .. 32767; -1 outside): 0 = fails, 1 = passes, 2 = undecided.
+ * imm3_plan_hi16_span_ok: 1 when a column whose halves span min_half .. max_half keeps its plane (at least 64 distinct halves).
+ * imm3_plan_hi16_eligible: 1 when a tile pass's int32 predicate scans the plane.  flags: bit 0 the query is over a table, 1 it is a
+ * select tree, 2 the layout is ragged, 3 the column is DENSE_INT, 4 the folded predicate is an IN-list, 5 the pass stages survivor
+ * records, 6 it is a chunk of a limit scan, 7 the column has a plane, 8 the tuning variant pins the int32 scan; n_i32 / n_i8 / n_s2:
+ * the pass's columns by kind. */
+int imm3_plan_hi16_bounds(int32_t lo, int32_t hi, uint32_t *out4);
+int imm3_plan_hi16_class(int32_t lo, int32_t hi, int32_t half);
+int imm3_plan_hi16_span_ok(int32_t min_half, int32_t max_half);
+int imm3_plan_hi16_eligible(uint32_t flags, int32_t n_i32, int32_t n_i8, int32_t n_s2);
 /* imm3_plan_distinct_capacity: the entries of an IMM3_AGG_COUNT_DISTINCT aggregate's pair set (csrc/imm3_distinct_plan.cpp:
  * distinct_capacity, pure) for a query over `rows` rows with a packed group key of `key_bytes` bytes and a value column of `width`
  * bytes: the power of two at or above 2 x min(rows, min(rows, 256^key_bytes) x 256^width), at least 1024.  -1: more than 2^28 (what
