@@ -741,6 +741,8 @@ static int ensure_hi16(imm3_ctx *ctx, const imm3_segment *cseg, int32_t col) {
         (void)hipFree(p);
         HIPCHK(e);
     }
+    sc.hi16_min = min_max[0];
+    sc.hi16_max = min_max[1];
     if (!hi16_span_ok(min_max[0], min_max[1])) {
         (void)hipFree(p);
         sc.hi16_state = -1;
@@ -865,6 +867,20 @@ extern "C" int imm3_segment_destroy(imm3_segment *seg) {
     for (void *p : seg->registered) unpin_range(seg->ctx, p); // the caller may unmap its buffers after destroy
     seg->registered.clear();
     segment_release(seg); // tables / queries built on it keep the columns alive until they are destroyed
+    return IMM3_OK;
+}
+
+// diagnostics (include/imm3_diag.h): the plane as the build kernel wrote it, and the span it reduced
+extern "C" int imm3_segment_hi16_plane(const imm3_segment *seg, int32_t col, int16_t *out, int64_t cap_rows, int32_t *state, int32_t *min_max) {
+    if (!seg || !state || !min_max || col < 0 || (size_t)col >= seg->cols.size()) return fail(IMM3_ERR_ARG, "bad argument");
+    const SegCol &sc = seg->cols[(size_t)col];
+    *state = sc.hi16_state;
+    min_max[0] = sc.hi16_min;
+    min_max[1] = sc.hi16_max;
+    if (sc.hi16_state == 1 && out) {
+        const int64_t rows = (int64_t)(sc.bytes / 4);
+        HIPCHK(hipMemcpy(out, sc.d_hi16, (size_t)(rows < cap_rows ? rows : cap_rows) * sizeof(int16_t), hipMemcpyDeviceToHost));
+    }
     return IMM3_OK;
 }
 
@@ -2078,6 +2094,21 @@ extern "C" int imm3_query_plan(const imm3_query *q, int64_t *out, int32_t n) {
                            (int64_t)q->order_select_runs, (int64_t)q->order_full_runs, (int64_t)q->order_launches,
                            q->hi16_ran ? 1 : 0};
     for (int32_t i = 0; i < n && i < 15; ++i) out[i] = v[i];
+    return IMM3_OK;
+}
+
+// The word a plane scan's refining tiles set (finish[kFinishHi16Refined]), read and cleared: it speaks of the runs since the last
+// call.  Waits for the context's stream; refused inside an open capture.
+extern "C" int imm3_query_hi16_refined(imm3_query *q, int32_t *refined) {
+    if (!q || !refined) return fail(IMM3_ERR_ARG, "null argument");
+    if (q->ctx->capture) return fail(IMM3_ERR_STATE, "a graph capture is open");
+    *refined = 0;
+    if (!q->d_total) return IMM3_OK;
+    unsigned long long w = 0;
+    HIPCHK(hipMemcpyAsync(&w, q->d_total + kFinishHi16Refined, sizeof(w), hipMemcpyDeviceToHost, q->ctx->stream));
+    HIPCHK(hipStreamSynchronize(q->ctx->stream));
+    if (w) HIPCHK(hipMemsetAsync(q->d_total + kFinishHi16Refined, 0, sizeof(w), q->ctx->stream));
+    *refined = w ? 1 : 0;
     return IMM3_OK;
 }
 

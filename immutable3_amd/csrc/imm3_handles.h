@@ -193,6 +193,7 @@ struct SegCol {
     // yet, 1 = d_hi16 is there, -1 = the column gets none (its halves span fewer than kHi16MinSpan values, or no memory)
     uint8_t *d_hi16 = nullptr;
     int32_t hi16_state = 0;
+    int32_t hi16_min = 32767, hi16_max = -32768; // the halves' span as the build reduced it (diagnostics: imm3_segment_hi16_plane)
 };
 
 // Batches of one segment as ScanOp yields them (Scan.scala:55,72; Segment.scala:159-168): block k of the FIRST used column holds

@@ -80,7 +80,8 @@ struct TileCol {
     int32_t n_match;                // TK_S2: IN-list size (1..kMaxTileMatch)
     int32_t negated;                // TK_S2, select trees only (k_filter_expr): 1 = keep the rows that equal NONE of the values
     uint32_t match[kMaxTileMatch];  // TK_S2: the two value bytes, little-endian; TK_H16: match[0..3] = the interval's windows over the halves (Hi16Bounds),
-                                    // match[4..5] = the int32 column itself (undecided rows, the partial tile): tile_col_full()
+                                    // match[4..5] = the int32 column itself (undecided rows, the partial tile): tile_col_full(),
+                                    // match[6..7] = the query's "a tile refined" word: tile_col_refined()
 };
 // TK_H16's pointer to the full column rides in two words of match[] that an int kind never uses: the record keeps the size and the
 // field offsets it had, so the code of every instance without a plane is what it was
@@ -88,6 +89,13 @@ IMM3_HOST_DEVICE inline const void *tile_col_full(const TileCol &c) { return (co
 inline void tile_col_set_full(TileCol &c, const void *full) {
     c.match[4] = (uint32_t)(uintptr_t)full;
     c.match[5] = (uint32_t)((uint64_t)(uintptr_t)full >> 32);
+}
+// ... and in match[6..7] a device word of the query (finish[kFinishHi16Refined]) that a wave sets when a tile of its takes the refine:
+// diagnostics (imm3_query_hi16_refined), one plain store per refining tile
+IMM3_HOST_DEVICE inline unsigned long long *tile_col_refined(const TileCol &c) { return (unsigned long long *)(uintptr_t)(((uint64_t)c.match[7] << 32) | (uint64_t)c.match[6]); }
+inline void tile_col_set_refined(TileCol &c, unsigned long long *word) {
+    c.match[6] = (uint32_t)(uintptr_t)word;
+    c.match[7] = (uint32_t)((uint64_t)(uintptr_t)word >> 32);
 }
 
 struct TileArgs {
@@ -260,6 +268,7 @@ constexpr int kFinishDense = 9;         // finish[9]: single-pass projection: ra
 constexpr int kFinishLimitRows = 11;    // finish[11]: rows selected by the chunks of this run so far
 constexpr int kFinishLimitTiles = 12;   // finish[12]: tiles those chunks scanned (the offsets scan and the gather stop there)
 constexpr int kFinishLimitGaveUp = 13;  // finish[13]: k_limit_gather's look-back ran into its poll cap in the run with this tag: gather with k_scan + k_gather
+constexpr int kFinishHi16Refined = 14;  // finish[14]: non-zero once a full tile of a plane scan (TK_H16) has compared full values; imm3_query_hi16_refined reads and clears it
 // A TABLE query's limit stops the scan inside ONE launch (k_filter_table_limit, imm3_kernels.hip): its work-groups claim runs of
 // kTableLimitClaimTiles consecutive virtual tiles from a ticket counter, in ascending order, and stop claiming once the runs that are
 // done have selected `limit` rows (finish[kFinishLimitRows]); the launch's last work-group turns the tickets into finish[kFinishLimitTiles]
@@ -685,11 +694,11 @@ void launch_distinct_mark(const AggArgs &a, int j, hipStream_t s, hipEvent_t ev0
 void launch_group_keys(const AggArgs &a, uint32_t n_groups, int key_bytes, uint8_t *out, hipStream_t s);
 
 constexpr int kSubTallies = 32;                       // in-kernel count reduce: sub-tallies (finish_add, imm3_device.h)
-constexpr int kFinishWords = 16 + kSubTallies * 16;   // u64 words of a query's `finish` block: header (9 used, padded to a 128-byte line) + one line per sub-tally
+constexpr int kFinishWords = 16 + kSubTallies * 16;   // u64 words of a query's `finish` block: header (15 used, padded to a 128-byte line) + one line per sub-tally
 constexpr int kFinishLimitTicket = 16 + 16 * (kSubTallies - 1) + kFinishLimitTicketLineWord; // finish[520]: claims handed out so far in this launch (zero between runs)
 static_assert(kFinishLimitTicket < kFinishWords && kFinishLimitTicketLineWord > 0 && kFinishLimitTicketLineWord < 16, "the ticket word lies inside the finish block, beside the last sub-tally");
 constexpr int kMaxFilterGrid = 4096; // capacity of block_partials
-int filter_grid(int64_t units, bool generic, bool any_i32, int grid_blocks, int narrow_row_bytes = 0); // narrow_row_bytes: bytes per row of a launch without an int32 column
+int filter_grid(int64_t units, bool generic, bool any_i32, int grid_blocks, int narrow_row_bytes = 0, bool lone_plane = false); // narrow_row_bytes: bytes per row of a launch without an int32 column; lone_plane: it is the lone TK_H16 column
 // ev0/ev1: optional events stamped with the kernel's own start/end (hipExtLaunchKernelGGL), else null
 // ---- PFOR_INT blocks (imm3_codec.hip) ----
 struct PforArgs {

@@ -202,7 +202,10 @@ __device__ __forceinline__ uint32_t finish_full_tile(const TileArgs &a, int64_t 
         const int64_t wl = tile * kTileWords + (lane >> 3);
         uint64_t word_a = ((uint64_t)hi_a << 32) | (uint64_t)lo_a, word_b = ((uint64_t)hi_b << 32) | (uint64_t)lo_b;
         if constexpr (kH16 >= 0) {
-            if (refine) refine_undecided(a.cols[kH16], tile * kTileRows, lane, und, word_a, word_b); // (segment instances only: tile t starts at row 1024 t)
+            if (refine) {
+                if (lane == 0) *tile_col_refined(a.cols[kH16]) = 1ULL; // (diagnostics: imm3_query_hi16_refined; retires with the refine's loads)
+                refine_undecided(a.cols[kH16], tile * kTileRows, lane, und, word_a, word_b); // (segment instances only: tile t starts at row 1024 t)
+            }
             if (!a.bitmap) return owner ? (uint32_t)(__popcll(word_a) + __popcll(word_b)) : 0u; // (a count-only run whose tile needed the refine)
         }
         if (a.and_existing) { // (the pipelined loop does not prefetch the earlier words for this layout: `earlier` is null)
@@ -462,7 +465,10 @@ __global__ __launch_bounds__(kBlockThreads, tile_min_waves(K0, K1, STAGE)) void 
             }
             // unconditional (the last iteration re-reads its own group): a load the compiler sees on every path is a load its
             // s_waitcnt can count past
-            load_group(n0, n1, n2, grp + n_waves < n_groups ? grp + n_waves : grp);
+            // (the plane's instances run twice the waves: there the last iteration reads group 0, ONE group for every wave of the
+            // launch -- it stays in L2 -- not a group of its own per wave)
+            constexpr bool kPlane = K0 == TK_H16 || K1 == TK_H16 || K2 == TK_H16;
+            load_group(n0, n1, n2, grp + n_waves < n_groups ? grp + n_waves : (kPlane ? (int64_t)0 : grp));
             if constexpr (STAGE)
                 if (arena_full<kRecDwords>(A, 2 * A.last)) arena_flush<kRecDwords>(a, A, lds, wave_id, lane); // the next tile will probably not fit: the buffered records go out here, behind the prefetch
         } else {
@@ -1134,14 +1140,21 @@ static inline int clamp_grid(int64_t want, int cap) {
     return (int)(want > cap ? cap : want);
 }
 
-int filter_grid(int64_t units, bool generic, bool any_i32, int grid_blocks, int narrow_row_bytes) {
+int filter_grid(int64_t units, bool generic, bool any_i32, int grid_blocks, int narrow_row_bytes, bool lone_plane) {
     // tile kernel with an int32 column: 512 workgroups = 2 per CU (see k_filter_tile).  Without one (int8 / 2-byte strings only) a
     // tile is 1-2 KiB and more waves must be resident to keep as many bytes in flight: 6 work-groups per CU for one byte per row, 3
     // for two, 2 from three on (round 5, the in-lane instances, 100 M rows, two runs each on one device: I8 19.0 / 18.5 us at 1536,
     // 20.1 / 19.9 at 1024, 23.7 at 512; S2 33.7 / 34.2 at 768, 35.8 at 1536, 37.5 at 512; I8+I8 34.3 / 34.8 at 768, 40.8 at 512;
     // I8+S2 47.0 / 47.1 at 512, 51.1 at 1024, 55.7 at 1536.  Twice the tiles per iteration at half the work-groups measured the same
     // or worse everywhere).  The word-at-a-time kernel keeps 8 per CU.
-    const int narrow = narrow_row_bytes <= 1 ? 1536 : (narrow_row_bytes == 2 ? 768 : 512);
+    // The lone high-half plane (TK_H16) streams TK_S2's two bytes per row but takes 6 per CU: a tile with a row on a boundary half
+    // (6 % of the uniform column's for one such half, 12 % for two) stops its wave for the round trip of the full values' loads, and
+    // at 3 waves per SIMD nothing covers that (the same scan over an interval whose boundaries decide themselves runs at S2's rate at
+    // 768 to 1536 work-groups).  100 M rows, two devices, median of 30 launches, us at 768 / 1024 / 1536 / 2048: one boundary half 40.3 / 38.6 / 36.9
+    // / 38.8 and 39.9 / 37.8 / 35.7 / 38.5; two 42.4 / 38.6 / 36.2 / 39.3; none 34.4 / 33.1 / 34.0 / 37.1.  int8 + plane keeps the
+    // three-byte rule's 512: 51.1 / 51.2 / 51.8 / 53.9 / 56.3 at 512 / 768 / 1024 / 1536 / 2048 (profiles/hi16_edges.txt).
+    constexpr int kPlaneGrid = 1536;
+    const int narrow = lone_plane ? kPlaneGrid : (narrow_row_bytes <= 1 ? 1536 : (narrow_row_bytes == 2 ? 768 : 512));
     const int dflt = generic ? 2048 : (any_i32 ? 512 : narrow);
     const int cap = grid_blocks > 0 ? (grid_blocks > kMaxFilterGrid ? kMaxFilterGrid : grid_blocks) : dflt;
     return clamp_grid((units + kWavesPerBlock - 1) / kWavesPerBlock, cap);
@@ -1188,7 +1201,7 @@ int filter_grid(int64_t units, bool generic, bool any_i32, int grid_blocks, int 
     X(TK_I32, TK_I32, TK_I32, 1) X(TK_I32, TK_I32, TK_I8, 1) X(TK_I32, TK_I8, TK_I8, 1)              \
     X(TK_I8, TK_I8, TK_I8, 2) X(TK_I32, TK_I32, TK_S2, 1) X(TK_I32, TK_I8, TK_S2, 1) X(TK_I8, TK_I8, TK_S2, 1)
 
-// ... and the plane's: the lone column (TK_S2's geometry: one tile per iteration, filter_grid's 768 work-groups) and int8 + int32
+// ... and the plane's: the lone column (TK_S2's tile and one tile per iteration, at filter_grid's kPlaneGrid work-groups) and int8 + int32
 #define IMM3_TILE_KINDS_H16(X) X(TK_H16, TK_NONE, TK_NONE, 1) X(TK_I8, TK_H16, TK_NONE, 1)
 
 bool launch_filter_tile(const TileArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
@@ -1213,24 +1226,45 @@ bool launch_filter_table_limit(const TileArgs &a, int grid, hipStream_t s, hipEv
 // ---------------------------------------------------------------------------------------------
 // k_hi16_build: the 16-bit high-half plane of a DENSE_INT column (SegCol::d_hi16), once per column: one read of the column (two
 // 16-byte loads = 8 rows per thread), one 16-byte store, and the smallest and largest half for the rule that says whether the column
-// keeps its plane (hi16_span_ok).  The rows behind the last whole group of 8 go one per thread.
+// keeps its plane (hi16_span_ok).  The rows behind the last whole group of 8 go one per thread.  (As first written -- two loads, the
+// store, and a full wait in front of the next two loads -- it ran at 2.5 TB/s: 237-243 us per 100 M rows.)
 // ---------------------------------------------------------------------------------------------
+// eight rows of the plane from two 16-byte loads; the halves' span so far
+__device__ __forceinline__ v4i hi16_pack8(const v4i x, const v4i y, int32_t &mn, int32_t &mx) {
+    const int32_t h[8] = {x[0] >> 16, x[1] >> 16, x[2] >> 16, x[3] >> 16, y[0] >> 16, y[1] >> 16, y[2] >> 16, y[3] >> 16};
+    v4i o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        o[k] = (int32_t)(((uint32_t)h[2 * k] & 0xFFFFu) | ((uint32_t)h[2 * k + 1] << 16));
+        mn = min(mn, min(h[2 * k], h[2 * k + 1]));
+        mx = max(mx, max(h[2 * k], h[2 * k + 1]));
+    }
+    return o;
+}
+
+// Four grid strides per iteration: the eight loads go out before the first is used, and the (non-temporal) stores' acknowledgements
+// are waited for once per four groups, not in front of every pair of loads.  The strides that are left go one at a time.
 __global__ __launch_bounds__(kBlockThreads) void k_hi16_build(const int32_t *src, int16_t *dst, int64_t n_rows, int32_t *min_max) {
+    constexpr int kUnroll = 4;
     const int64_t n8 = n_rows / 8;
     int32_t mn = 32767, mx = -32768;
     const IMM3_GLOBAL v4i *in = (const IMM3_GLOBAL v4i *)src;
     IMM3_GLOBAL v4i *out = (IMM3_GLOBAL v4i *)dst;
-    for (int64_t i = (int64_t)blockIdx.x * kBlockThreads + threadIdx.x; i < n8; i += (int64_t)gridDim.x * kBlockThreads) {
-        const v4i x = __builtin_nontemporal_load(in + 2 * i), y = __builtin_nontemporal_load(in + 2 * i + 1);
-        const int32_t h[8] = {x[0] >> 16, x[1] >> 16, x[2] >> 16, x[3] >> 16, y[0] >> 16, y[1] >> 16, y[2] >> 16, y[3] >> 16};
-        v4i o;
+    const int64_t stride = (int64_t)gridDim.x * kBlockThreads;
+    int64_t i = (int64_t)blockIdx.x * kBlockThreads + threadIdx.x;
+    for (; i + (kUnroll - 1) * stride < n8; i += kUnroll * stride) { // (every group i + u * stride, u < kUnroll, lies below n8)
+        v4i x[kUnroll], y[kUnroll];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            o[k] = (int32_t)(((uint32_t)h[2 * k] & 0xFFFFu) | ((uint32_t)h[2 * k + 1] << 16));
-            mn = min(mn, min(h[2 * k], h[2 * k + 1]));
-            mx = max(mx, max(h[2 * k], h[2 * k + 1]));
+        for (int u = 0; u < kUnroll; ++u) {
+            x[u] = __builtin_nontemporal_load(in + 2 * (i + u * stride));
+            y[u] = __builtin_nontemporal_load(in + 2 * (i + u * stride) + 1);
         }
-        out[i] = o;
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) __builtin_nontemporal_store(hi16_pack8(x[u], y[u], mn, mx), out + (i + u * stride));
+    }
+    for (; i < n8; i += stride) {
+        const v4i x = __builtin_nontemporal_load(in + 2 * i), y = __builtin_nontemporal_load(in + 2 * i + 1);
+        __builtin_nontemporal_store(hi16_pack8(x, y, mn, mx), out + i);
     }
     const int64_t tail = 8 * n8 + threadIdx.x;
     if (blockIdx.x == 0 && threadIdx.x < 8 && tail < n_rows) {
@@ -1251,7 +1285,8 @@ __global__ __launch_bounds__(kBlockThreads) void k_hi16_build(const int32_t *src
 }
 
 void launch_hi16_build(const int32_t *src, int16_t *dst, int64_t n_rows, int32_t *min_max, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    const int grid = clamp_grid((n_rows / 8 + kBlockThreads - 1) / kBlockThreads, 2048);
+    const int64_t per_group = (int64_t)kBlockThreads * 4; // (the kernel's four strides per iteration: a small column still gets them)
+    const int grid = clamp_grid((n_rows / 8 + per_group - 1) / per_group, 2048);
     IMM3_LAUNCH(k_hi16_build, grid, kBlockThreads, s, ev0, ev1, src, dst, n_rows, min_max);
 }
 

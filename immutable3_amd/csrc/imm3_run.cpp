@@ -99,10 +99,12 @@ template <class Args> static void fill_pass_tail(const imm3_query *q, const Sele
 
 static int tile_kind_bytes(int kind) { return kind == TK_I32 ? 4 : ((kind == TK_S2 || kind == TK_H16) ? 2 : (kind == TK_I8 ? 1 : 0)); } // (TK_H16: what the scan streams, the plane)
 
-// what filter_grid asks about a tile launch's columns: an int32 column among them, else the bytes per row of the narrow ones
+// what filter_grid asks about a tile launch's columns: an int32 column among them, else the bytes per row of the narrow ones -- and the
+// lone high-half plane, which streams TK_S2's two bytes per row but wants twice its work-groups (filter_grid: kPlaneGrid)
 struct TileGridHint {
     bool any_i32 = false;
     int narrow_bytes = 0;
+    bool lone_plane = false;
 };
 static TileGridHint tile_grid_hint(const int32_t *kinds) {
     TileGridHint h;
@@ -110,6 +112,7 @@ static TileGridHint tile_grid_hint(const int32_t *kinds) {
         h.any_i32 |= kinds[k] == TK_I32;
         if (kinds[k] != TK_I32) h.narrow_bytes += tile_kind_bytes(kinds[k]);
     }
+    h.lone_plane = kinds[0] == TK_H16 && kinds[1] == TK_NONE; // (sorted: nothing behind a TK_NONE)
     return h;
 }
 
@@ -258,6 +261,7 @@ static void take_hi16_plane(imm3_query *q, const SelectRun &run, const std::vect
         c.match[1] = b.possible_count;
         c.match[2] = b.certain_first;
         c.match[3] = b.certain_count;
+        tile_col_set_refined(c, q->d_total + kFinishHi16Refined);
         a.kinds[k] = TK_H16;
         for (int j = k; j + 1 < kMaxTileCols && tile_kind_rank(a.kinds[j + 1]) < tile_kind_rank(a.kinds[j]); ++j) {
             std::swap(a.kinds[j], a.kinds[j + 1]);
@@ -304,7 +308,7 @@ static int fill_tile_args(imm3_query *q, SelectRun &run, const std::vector<const
     }
     a.tile_rows = q->table ? q->table->d_tile_rows : nullptr; // table query: address the columns through the tile table
     const TileGridHint hint = tile_grid_hint(a.kinds);
-    run.grid = filter_grid(q->n_tiles, false, hint.any_i32, ctx->grid_blocks, hint.narrow_bytes); // (no column at all: the store-only kernel also likes 1536 groups, 9.9 vs 17.2 us)
+    run.grid = filter_grid(q->n_tiles, false, hint.any_i32, ctx->grid_blocks, hint.narrow_bytes, hint.lone_plane); // (no column at all: the store-only kernel also likes 1536 groups, 9.9 vs 17.2 us)
     if (q->run.stage_written) run.grid = q->stage_grid; // fixed at creation: the arena layout depends on it
     // A select chain that is ONE tile pass also reduces its count in the kernel (one relaxed atomic per work-group into a
     // two-level tally, finish_add): no k_total launch.  TV_COUNT_BY_K_TOTAL = never; TV_COUNT_SMALL_GRID = only at <= 512 work-groups (what

@@ -73,7 +73,7 @@ DIAG_EXPORTS = [
     "imm3_plan_table_limit", "imm3_plan_string_route", "imm3_plan_string_range_route", "imm3_plan_limit_chunks", "imm3_plan_distinct_capacity",
     "imm3_plan_int_list_table", "imm3_plan_int_list_form", "imm3_plan_int_list_probe",
     "imm3_plan_hi16_bounds", "imm3_plan_hi16_class", "imm3_plan_hi16_span_ok", "imm3_plan_hi16_eligible",
-    "imm3_query_agg_form", "imm3_query_expr_form", "imm3_expr_normalize", "imm3_query_group_order_path",
+    "imm3_query_agg_form", "imm3_query_hi16_refined", "imm3_segment_hi16_plane", "imm3_query_expr_form", "imm3_expr_normalize", "imm3_query_group_order_path",
     "imm3_query_group_filter_stats", "imm3_group_filter_check", "imm3_comm_merge_view_path", "imm3_merge_view_plan_json",
 ]
 COMM_ID_BYTES = 128
@@ -565,6 +565,16 @@ class DeviceSegment:
         _check(load().imm3_segment_bytes(self._h, C.byref(n)))
         return n.value
 
+    def hi16_plane(self, col: int, rows: int):
+        """imm3_segment_hi16_plane -- (state, (min half, max half), plane or None) of a DENSE_INT column's 16-bit high-half plane."""
+        L = load()
+        L.imm3_segment_hi16_plane.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_void_p]
+        out = np.zeros(max(rows, 1), np.int16)
+        state = C.c_int32(0)
+        mm = np.zeros(2, np.int32)
+        _check(L.imm3_segment_hi16_plane(self._h, col, out.ctypes.data, rows, C.byref(state), mm.ctypes.data))
+        return state.value, (int(mm[0]), int(mm[1])), (out[:rows] if state.value == 1 else None)
+
     def wait(self):
         """The copies of an async_copy segment have consumed the host buffers."""
         _check(load().imm3_segment_wait(self._h))
@@ -1015,6 +1025,14 @@ class DeviceQuery:
                 "abandoned_runs": int(v[8]), "busy_runs": int(v[9]), "limit_gather_gave_up": int(v[10]),
                 "order_select_runs": int(v[11]), "order_full_runs": int(v[12]), "order_launches": int(v[13]),
                 "hi16_plane": bool(v[14])}
+
+    def hi16_refined(self) -> bool:
+        """imm3_query_hi16_refined -- has a full tile of a plane scan compared full values since the last call (reads and clears)."""
+        L = load()
+        L.imm3_query_hi16_refined.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        r = C.c_int32(0)
+        _check(L.imm3_query_hi16_refined(self._h, C.byref(r)))
+        return bool(r.value)
 
     def agg_form(self) -> int:
         """The kernel form (AGG_FORM_*) of this aggregation's last launch, -1 before the first (include/imm3_diag.h)."""

@@ -93,6 +93,16 @@ int imm3_plan_predict(int64_t n_rows, const int32_t *pred_width, const int32_t *
  * every int32 predicate read the column itself.  n <= 15 values. */
 int imm3_query_plan(const imm3_query *q, int64_t *out, int32_t n);
 
+/* imm3_query_hi16_refined: *refined = 1 when a FULL tile of a plane scan of this query (out[14] above) has compared full values -- held a
+ * row whose half does not decide and that no other column had failed: the refine -- in a run since the last call, else 0 (the rolled
+ * last tile of a segment reads the column itself and does not count).  The word is set on the device by such a tile; the call waits
+ * for the context's stream, reads it and clears it.  IMM3_ERR_STATE while a graph capture is open.
+ * imm3_segment_hi16_plane: the plane of column `col` as k_hi16_build wrote it.  *state: 0 = no query has asked for one yet, 1 = it is
+ * there (up to cap_rows halves are copied to `out` when out is not null), -1 = the column gets none; min_max = {smallest, largest}
+ * half as the build reduced them ({32767, -32768} before any build). */
+int imm3_query_hi16_refined(imm3_query *q, int32_t *refined);
+int imm3_segment_hi16_plane(const imm3_segment *seg, int32_t col, int16_t *out, int64_t cap_rows, int32_t *state, int32_t *min_max);
+
 /* imm3_query_agg_form: the kernel form of an aggregation's last launch (csrc/imm3_internal.h's AggForm: 0 = lanes (63 keys), 1 = lanes
  * (127 keys), 2 = direct, 3 = tile, 4 = general), after any re-run from a later form that a full per-work-group table forced; -1
  * before the first run.  IMM3_ERR_ARG for a query that is not an aggregation. */
