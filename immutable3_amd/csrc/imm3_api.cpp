@@ -49,6 +49,7 @@ static const char *cond_name(int c) {
     case IMM3_MATCH: return "Match";
     case IMM3_STR_RANGE: return "StrRange";
     case IMM3_INT_IN: return "IntIn";
+    case IMM3_INT_IN_SET: return "IntInSet";
     case IMM3_NOTMATCH: return "NotMatch";
     case IMM3_EQ: return "EQ";
     case IMM3_GT: return "GT";
@@ -917,7 +918,9 @@ static void query_free(imm3_query *q) {
     pool_release(ctx, q->d_order_row_index);
     for (auto p : q->d_order_proj) pool_release(ctx, p);
     group_order_release(q);
-    for (auto &p : q->preds) pool_release(ctx, p.d_blob);
+    for (auto &p : q->preds)
+        if (!pred_list_shared(p)) pool_release(ctx, p.d_blob); // (a shared set's table is the set's)
+    for (imm3_int_set *s : q->sets) int_set_release(s);
     for (auto &t : q->expr_terms)
         for (auto &p : t) pool_release(ctx, p.d_blob);
     pool_release(ctx, q->d_expr_preds);
@@ -1131,7 +1134,7 @@ static int check_create_args(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
     // whether or not the segment has any block.
     for (int32_t i = 0; i < n_sels; ++i) {
         const int c = sels[i].cond;
-        if (c != IMM3_MATCH && c != IMM3_GT && c != IMM3_LT && c != IMM3_EQ && c != IMM3_STR_RANGE && c != IMM3_INT_IN)
+        if (c != IMM3_MATCH && c != IMM3_GT && c != IMM3_LT && c != IMM3_EQ && c != IMM3_STR_RANGE && c != IMM3_INT_IN && c != IMM3_INT_IN_SET)
             return fail(IMM3_ERR_UNSUPPORTED_CONDITION, std::string("Unsupported condition: ") + cond_name(c));
         if (c == IMM3_MATCH && sels[i].n_match > 0 && (!sels[i].match_bytes || !sels[i].match_lens))
             return fail(IMM3_ERR_ARG, "Match without values");
@@ -1144,6 +1147,17 @@ static int check_create_args(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
             const int lrc = int_list_check_leaf(sels[i].n_match, sels[i].match_bytes);
             if (lrc) return lrc;
         }
+        if (c == IMM3_INT_IN_SET) { // (the handle; a STRING column fails scan_layout's vector check)
+            const int src = int_set_check_leaf(ctx, sels[i].n_match, sels[i].match_bytes);
+            if (src) return src;
+        }
+    }
+    // a column with a set leaf takes no other list: whatever the sizes, so that the refusal does not depend on data
+    for (int32_t i = 0; i < n_sels; ++i) {
+        if (sels[i].cond != IMM3_INT_IN_SET) continue;
+        for (int32_t k = 0; k < n_sels; ++k)
+            if (k != i && used_cols[sels[k].column] == used_cols[sels[i].column] && (sels[k].cond == IMM3_INT_IN || sels[k].cond == IMM3_INT_IN_SET))
+                return fail(IMM3_ERR_ARG, kIntSetOneListRefusal);
     }
     return IMM3_OK;
 }
@@ -1385,12 +1399,24 @@ static int place_hi16(imm3_query *q, bool have_batches) {
 // kernel arguments.
 static int upload_match_blobs(imm3_query *q, std::vector<FoldedPred> &preds) {
     for (auto &p : preds) {
+        if (p.kind != KIND_STR && pred_list_shared(p)) { // IMM3_INT_IN_SET: everything is on the device already, in the set
+            const imm3_int_set *set = p.set;
+            if (p.kind == KIND_I8) std::memcpy(p.list_set, set->set256, sizeof(p.list_set));
+            else {
+                p.list_mask = set->mask;
+                p.list_shift = set->shift;
+                p.list_max_probe = set->max_probe;
+                p.list_empty = set->empty;
+                p.d_blob = (uint8_t *)set->d_table; // (not owned: query_free)
+            }
+            continue;
+        }
         if (p.kind != KIND_STR && p.has_list && !p.list.empty()) {
             if (p.kind == KIND_I8) {
                 int_list_set256(p.list, p.list_set);
                 continue;
             }
-            if (int_list_form(p.width, (int64_t)p.list.size()) == INT_LIST_ARGS) continue; // (the values travel in the kernel arguments on every route: no table, no allocation, no wait)
+            if (int_list_form(p.width, pred_list_count(p)) == INT_LIST_ARGS) continue; // (the values travel in the kernel arguments on every route: no table, no allocation, no wait)
             IntListTable t;
             int_list_build_table(p.list, t);
             p.list_mask = t.mask;
@@ -1507,6 +1533,9 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
         if (has_or || has_not)
             for (int32_t i = 0; i < n_sels; ++i)
                 if (sels[i].cond == IMM3_INT_IN) return fail(IMM3_ERR_ARG, kTreeIntInRefusal);
+        if (has_or || has_not)
+            for (int32_t i = 0; i < n_sels; ++i)
+                if (sels[i].cond == IMM3_INT_IN_SET) return fail(IMM3_ERR_ARG, kTreeIntSetRefusal);
         if (!has_or && !has_not) {
             for (int32_t i = 0; i < n_prog; ++i)
                 if (prog[i] >= 0) flat.push_back(sels[prog[i]]);
@@ -1528,6 +1557,8 @@ static int query_create_impl(imm3_ctx *ctx, const imm3_segment *seg, const imm3_
     q->used.assign(used_cols, used_cols + n_used);
     q->proj.assign(proj, proj + n_proj);
     q->limit = limit;
+    for (int32_t i = 0; i < n_sels; ++i) // the sets of the leaves stay alive as long as the query does (its predicates point into them)
+        if (sels[i].cond == IMM3_INT_IN_SET) q->sets.push_back(int_set_retain((imm3_int_set *)const_cast<uint8_t *>(sels[i].match_bytes)));
 
     int32_t nb = 0;
     rc = scan_layout(q.get(), sels, n_sels, nb); if (rc) return rc;
@@ -1937,6 +1968,20 @@ static int settle(imm3_query *q, SettleNeed need) {
 // The hand-off to device-side consumers of the count word (imm3_query_join_count, imm3_comm_allreduce_count): it is the segment's
 // count -- after a limit scan that stopped early the whole select runs first, enqueued, no host wait.
 int imm3::join_query_count(imm3_query *q) { return settle(q, NEED_DEVICE_COUNT); }
+
+// The query's select bitmap as imm3_query_bitmap would hand it out, left on the device (imm3_int_set_create's sources): what the last
+// run left undone is settled; a query whose last run stored no bitmap (count-only), or that has never run, runs its select chain.
+int imm3::query_bitmap_current(imm3_query *q) {
+    int rc = q->run.ran_select ? settle(q, NEED_BITMAP) : IMM3_OK;
+    if (rc) return rc;
+    if (!q->run.ran_select || !q->run.bitmap_valid) {
+        rc = run_select(q, SEL_WHOLE | SEL_PLAIN);
+        if (rc) return rc;
+        q->run.offsets_valid = false;
+    }
+    return q->run.bitmap_valid ? IMM3_OK : fail(IMM3_ERR_STATE, "internal: the select run stored no bitmap");
+}
+int imm3::segment_dense_column(imm3_ctx *ctx, const imm3_segment *seg, int32_t col) { return ensure_dense(ctx, seg, col); }
 
 extern "C" int imm3_query_count(imm3_query *q, uint64_t *selected_rows) {
     if (!q || !selected_rows) return fail(IMM3_ERR_ARG, "null argument");

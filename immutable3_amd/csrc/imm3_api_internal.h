@@ -27,6 +27,15 @@ int ensure_row_capacity(imm3_query *q, uint64_t rows);               // the proj
 extern const char *const kTableGenericRefusal;                       // a table has no word-at-a-time kernel: the refusal's text, at creation and at a run
 int run_agg(imm3_query *q);                                          // ProjectAggOp behind (or fused with) the select: the aggregation launch
 bool agg_run_fuses(const imm3_query *q);                             // ... which evaluates the select chain itself: no run_select
+int query_bitmap_current(imm3_query *q);                             // the select bitmap of the whole selection on the device, as imm3_query_bitmap settles it (and a run where none was stored)
+int segment_dense_column(imm3_ctx *ctx, const imm3_segment *seg, int32_t col); // the decoded form of a PFOR_INT / snappy column, made on first need
+
+// ---- imm3_int_set_api.cpp: integer sets built from selections (imm3_int_set_create) and their leaf, IMM3_INT_IN_SET ----
+imm3_int_set *int_set_retain(imm3_int_set *s);
+void int_set_release(imm3_int_set *s);
+int int_set_check_leaf(imm3_ctx *ctx, int32_t n_match, const uint8_t *handle); // the leaf's own checks: one handle, live, of this context
+extern const char *const kIntSetOneListRefusal;                       // a column with a set leaf takes no other IMM3_INT_IN / IMM3_INT_IN_SET leaf
+extern const char *const kTreeIntSetRefusal;                          // a program with an OR or a NOT takes no IMM3_INT_IN_SET leaf
 
 // Hands out one event pair per launch when timing is on; the launcher stamps it with the kernel's own
 // start and end (hipExtLaunchKernelGGL), so elapsed time == kernel duration as rocprofv3 reports it.

@@ -27,16 +27,28 @@ __attribute__((weak)) void str_range_filter_match(const std::string &lo, const s
 __attribute__((weak)) int int_list_parse(int32_t n_match, const uint8_t *bytes, int32_t width, std::vector<int32_t> &out);
 __attribute__((weak)) void int_list_clip(std::vector<int32_t> &list, int64_t lo, int64_t hi);
 __attribute__((weak)) void int_list_intersect(std::vector<int32_t> &list, const std::vector<int32_t> &other);
+// ... and the set leaf's interval (IMM3_INT_IN_SET: imm3_int_set_plan.cpp)
+__attribute__((weak)) void int_set_fold_interval(int64_t &lo, int64_t &hi, int64_t n, int32_t min, int32_t max);
 
 const char *const kTreeIntInRefusal =
     "a select program with an IMM3_EXPR_OR or an IMM3_EXPR_NOT does not take IMM3_INT_IN leaves (its normal form would need "
     "negated lists and intervals with exclusions); a program of IMM3_EXPR_AND alone does";
+const char *const kTreeIntSetRefusal =
+    "a select program with an IMM3_EXPR_OR or an IMM3_EXPR_NOT does not take IMM3_INT_IN_SET leaves (NOT IN (sub-query) and a set under "
+    "OR are out of scope: its normal form would need negated sets and intervals with exclusions); a program of IMM3_EXPR_AND alone does";
+const char *const kIntSetOneListRefusal =
+    "a column with an IMM3_INT_IN_SET leaf takes no other IMM3_INT_IN or IMM3_INT_IN_SET leaf (the intersection of device-resident sets "
+    "is not built); intersect in the sub-query instead";
 
 namespace {
 // a numeric predicate with a list, settled: the list's values inside the interval, the interval tightened to the list's minimum and
 // maximum; no value left: the empty interval (lo > hi), which is what every caller reads as "selects nothing"
 void settle_list(FoldedPred &p) {
     if (!p.has_list) return;
+    if (pred_list_shared(p)) { // the values stay on the device: the interval is already cut to the set's span, and the probe tests it first
+        if (p.lo > p.hi) { p.lo = 1; p.hi = 0; }
+        return;
+    }
     int_list_clip(p.list, p.lo, p.hi);
     if (p.list.empty()) { p.lo = 1; p.hi = 0; }
     else { p.lo = p.list.front(); p.hi = p.list.back(); }
@@ -70,6 +82,19 @@ int leaf_pred(int32_t seg_col, int32_t vcodec, int32_t width, const imm3_select 
         const int rc = int_list_parse(leaf.n_match, leaf.match_bytes, width, out.list);
         if (rc) return rc;
         out.has_list = true;
+        settle_list(out);
+    } else if (leaf.cond == IMM3_INT_IN_SET) { // a member of a shared set (the handle has passed int_set_check_leaf)
+        if (!int_list_clip || !int_set_fold_interval) return fail(IMM3_ERR_ARG, "IMM3_INT_IN_SET: this build holds no set logic");
+        const imm3_int_set *set = (const imm3_int_set *)leaf.match_bytes;
+        out.has_list = true;
+        out.set = set;
+        if (!pred_list_shared(out)) out.list = set->small; // an ordinary short list from here on (int8: settle_list drops what no row holds)
+        else {
+            int_set_fold_interval(out.lo, out.hi, set->n, set->min, set->max);
+            bool any8 = false;
+            for (int i = 0; i < 8; ++i) any8 = any8 || set->set256[i] != 0;
+            if (out.kind == KIND_I8 && !any8) { out.lo = 1; out.hi = 0; } // none of its values is an int8
+        }
         settle_list(out);
     } else {
         const int64_t t = out.kind == KIND_I32 ? (int64_t)jvm_d2i(leaf.value) : (int64_t)jvm_d2b(leaf.value);
@@ -115,7 +140,7 @@ void merge_pred(FoldedPred &into, const FoldedPred &other) {
         into.lo = std::max(into.lo, other.lo);
         into.hi = std::min(into.hi, other.hi);
         if (into.has_list && other.has_list) int_list_intersect(into.list, other.list);
-        else if (other.has_list) { into.has_list = true; into.list = other.list; }
+        else if (other.has_list) { into.has_list = true; into.list = other.list; into.set = other.set; }
         settle_list(into);
     }
 }

@@ -251,6 +251,24 @@ struct imm3_table { // all segments of one table as one scan unit: the tile tabl
     std::vector<int64_t> seg_first_word;      // n_segs + 1
 };
 
+// A device-resident integer set (imm3_int_set_create; imm3_int_set_api.cpp builds it, imm3_intset.hip holds the kernels; DESIGN.md
+// §3d).  Immutable once created.  Reference counted like every handle: the caller's handle holds one reference, every query created
+// with an IMM3_INT_IN_SET leaf on it another.  What it holds is exactly what a folded IMM3_INT_IN list gives the kernels: the probe
+// table (IntListTable's fields), the 256-bit set of its values in -128 .. 127, and -- at most kMaxMatch values -- the values themselves.
+struct imm3_int_set {
+    std::atomic<int> refs{1};
+    std::atomic<bool> closed{false};
+    imm3_ctx *ctx = nullptr;               // retained
+    int64_t n = 0;                         // distinct values
+    int32_t min = 0, max = 0;              // their extremes (0, 0 when n == 0)
+    int32_t *d_table = nullptr;            // n > 0: int_list_slots(n) slots (pool memory of ctx)
+    uint32_t mask = 0, shift = 0, max_probe = 0;
+    int32_t empty = 0;
+    uint32_t set256[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<int32_t> small;            // n <= kMaxMatch: the values, ascending (such a set is an ordinary short list on the host)
+    bool host_route = false;               // diagnostics: the table was built on the host (the set holds INT32_MIN and INT32_MAX)
+};
+
 struct FoldedPred { // all SelectOp leaves on one segment column, folded
     int32_t seg_col = 0;
     int32_t kind = 0, width = 0;
@@ -260,6 +278,8 @@ struct FoldedPred { // all SelectOp leaves on one segment column, folded
     uint32_t list_set[8] = {0, 0, 0, 0, 0, 0, 0, 0};                  // ... int8: the 256-bit membership set (upload_match_blobs)
     uint32_t list_mask = 0, list_shift = 0, list_max_probe = 0;        // ... int32: the probe table at d_blob (IntListTable)
     int32_t list_empty = 0;
+    const imm3_int_set *set = nullptr;     // ... an IMM3_INT_IN_SET leaf: the list lives in this shared set (kept alive by imm3_query::sets).  A set of more than kMaxMatch values
+                                           // leaves `list` EMPTY: d_blob is the set's table (not owned), the count is the set's (pred_list_count); a smaller one IS `list`
     std::vector<std::string> match;        // string: surviving IN-list values (each exactly width bytes)
     bool negated = false;                  // string, select trees only: `match` are EXCLUSIONS -- every value but these passes (a complemented Match)
     bool has_range = false;                // string: a byte-order range INSTEAD of an IN-list (IMM3_STR_RANGE; `match` is empty, never negated):
@@ -280,6 +300,11 @@ static inline FoldedPred unfolded_pred(int32_t seg_col, int32_t codec, int32_t w
     else fp.kind = imm3::KIND_STR;
     return fp;
 }
+// the list lives in a shared set and only there (more than kMaxMatch values: no host copy)
+static inline bool pred_list_shared(const FoldedPred &fp) { return fp.set && fp.set->n > (int64_t)imm3::kMaxMatch; }
+// the values a numeric predicate's folded list holds, as int_list_form wants them: the set's own count where the list is shared (the
+// interval may cut it further: the probe does not mind)
+static inline int64_t pred_list_count(const FoldedPred &fp) { return pred_list_shared(fp) ? fp.set->n : (int64_t)fp.list.size(); }
 // the folded predicate on segment column `sci` (at most one per column), or null
 static inline FoldedPred *pred_on(std::vector<FoldedPred> &preds, int32_t sci) {
     for (auto &p : preds)
@@ -301,6 +326,7 @@ struct imm3_query {
     bool ragged = false;
     bool always_false = false;
     std::vector<FoldedPred> preds;
+    std::vector<imm3_int_set *> sets;   // the sets of this query's IMM3_INT_IN_SET leaves, retained until the query goes
     // device buffers
     uint64_t *d_bitmap = nullptr;
     uint32_t *d_tile_offsets = nullptr, *d_chunk_sums = nullptr, *d_block_partials = nullptr;

@@ -402,6 +402,45 @@ struct IntListArgs {
 int int_list_grid(int64_t n_tiles, int grid_blocks, int32_t width);
 bool launch_filter_int_list(const IntListArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // false: arguments no instance takes
 
+// ---- integer sets built from selections (imm3_intset.hip): imm3_int_set_create's device passes; DESIGN.md §3d ----
+// The header every pass reports through, one per build, in device memory (32-bit words; the host reads it whole)
+enum IntSetHeaderWord : int {
+    ISH_MIN = 0,        // int32: the smallest selected value (INT32_MAX before any)
+    ISH_MAX = 1,        // int32: the largest (INT32_MIN before any)
+    ISH_ROWS_LO = 2,    // the selected rows of all sources, 64 bits (ISH_ROWS_LO, + 1)
+    ISH_COUNT0 = 4,     // values the insert pass placed in the scratch table
+    ISH_PROBE0 = 5,     // ... the longest insertion distance + 1 there
+    ISH_OVERFLOW = 6,   // != 0: a value found no free slot (more distinct values than the table was sized for)
+    ISH_COUNT1 = 7,     // values the rehash placed in the final table
+    ISH_PROBE1 = 8,     // ... the longest insertion distance + 1 there
+    ISH_SET256 = 16,    // 8 words: bit (uint8_t)v per value in -128 .. 127
+    ISH_WORDS = 24,
+};
+// one source: a query's select bitmap and one of its columns (flat, or through a table's tile pointers)
+struct IntSetSource {
+    const uint64_t *bitmap;
+    int64_t n_words, n_rows;            // n_rows: uniform segment layouts (a word's valid rows)
+    const void *data;                   // flat (decoded) column; null for a table
+    const void *const *tile_ptrs;       // table: per-tile column pointers
+    const uint32_t *tile_rows;          // table: valid rows per tile
+    const uint32_t *word_row_base;      // ragged layouts: the first row of every bitmap word, else null
+    const uint8_t *word_nvalid;         // ... and its valid rows
+    int32_t width;                      // 4 (int32) or 1 (int8, sign-extended)
+    int32_t has_skip, skip;             // has_skip: rows whose value is `skip` are passed over (the host route adds that value itself)
+};
+struct IntSetTable {
+    int32_t *slots;                     // mask + 1 of them, a power of two
+    uint32_t mask, shift;               // shift = 32 - log2(slots): int_list_home
+    int32_t empty;                      // what a free slot holds: a value no source row has
+};
+void launch_int_set_init(uint32_t *header, hipStream_t s);
+void launch_int_set_stats(const IntSetSource &src, uint32_t *header, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+void launch_int_set_fill(const IntSetTable &t, hipStream_t s);
+// `cap`: the distinct values the build may hold; the pass raises the overflow flag as soon as its running count passes it, and leaves
+void launch_int_set_insert(const IntSetSource &src, const IntSetTable &t, uint32_t cap, uint32_t *header, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+// one pass over the slots of `from`: every value into `to` (to.slots == null: none -- the table stays) and the values in -128 .. 127 into the header's 256-bit set
+void launch_int_set_rehash(const IntSetTable &from, const IntSetTable &to, uint32_t *header, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+
 // ---- select trees (imm3_expr.hip): AND / OR over the leaves, as a disjunction of TERMS ----
 // The host rewrites a tree into terms (imm3_expr_norm.cpp): each term is a conjunction with at most one folded predicate per column --
 // exactly what a flat select list folds to -- and the selection is the OR of the terms.

@@ -42,7 +42,7 @@ void imm3::fill_colpred(const imm3_query *q, const FoldedPred &fp, ColPred &cp) 
         cp.list = 1;
         cp.n_match = 0;
         std::memcpy(cp.match, fp.list_set, sizeof(fp.list_set));
-        if (fp.kind == KIND_I32 && int_list_form(fp.width, (int64_t)fp.list.size()) == INT_LIST_ARGS) { // no table: the values themselves, a shorter list repeating its first
+        if (fp.kind == KIND_I32 && int_list_form(fp.width, pred_list_count(fp)) == INT_LIST_ARGS) { // no table: the values themselves, a shorter list repeating its first
             cp.list = 2;
             int32_t vals[kMaxMatch];
             for (size_t m = 0; m < (size_t)kMaxMatch; ++m) vals[m] = fp.list[m < fp.list.size() ? m : 0];
@@ -488,7 +488,7 @@ static int launch_int_list_pass(imm3_query *q, SelectRun &run, const FoldedPred 
     std::memset(&a, 0, sizeof(a));
     a.data = col_flat(q->seg->cols[(size_t)fp.seg_col]);
     a.width = fp.width;
-    a.form = int_list_form(fp.width, (int64_t)fp.list.size());
+    a.form = int_list_form(fp.width, pred_list_count(fp));
     a.lo = (int32_t)fp.lo;
     a.hi = (int32_t)fp.hi;
     if (a.form == INT_LIST_I8) std::memcpy(a.set, fp.list_set, sizeof(a.set));

@@ -18,6 +18,9 @@
 //   --string-ranges  accept `f like 'value%'`, `f > 'value'` and `f < 'value'` on string columns (default off: the reference's grammar, in
 //                  which such a statement does not parse): byte-order prefix / range predicates, run on the GPU.  With --parse-only and a
 //                  data directory, the leaves of such conditions are also printed as the bytes the library gets ("leafbytes:").
+//   --subqueries   accept `f in (select g from t where ...)` on int32 / int8 columns (default off: such a statement does not parse): the
+//                  semi-join.  The inner selection's distinct values become a set built and kept on the GPU (imm3_int_set_create), the
+//                  outer statement probes it; --explain also says how the sub-queries ran.
 //   --explain      after the rows, one line on stderr: whether the query ran as one table query or per segment ("path: ...").
 #include <chrono>
 #include <cstdio>
@@ -29,14 +32,7 @@
 
 using namespace immutabledb;
 
-static std::string showSelect(const SelectADT &s) {
-    switch (s.kind) {
-    case SelectADT::And: return "And(" + showSelect(*s.op1) + "," + showSelect(*s.op2) + ")";
-    case SelectADT::Or: return "Or(" + showSelect(*s.op1) + "," + showSelect(*s.op2) + ")";
-    case SelectADT::Select: return "Select(" + s.col + "," + s.cond.toString() + ")";
-    default: return "NoSelect";
-    }
-}
+static std::string showSelect(const SelectADT &s) { return showSelectADT(s); }
 
 static std::string showQuery(const Query &q) {
     std::string p;
@@ -69,7 +65,7 @@ static std::string showQuery(const Query &q) {
 int main(int argc, char **argv) {
     std::string query, dataDir;
     int device = 0, repeat = 0;
-    bool parseOnly = false, honourAndOr = false, explain = false, orderBy = false, stringRanges = false, having = false, countDistinct = false, intLists = false;
+    bool parseOnly = false, honourAndOr = false, explain = false, orderBy = false, stringRanges = false, having = false, countDistinct = false, intLists = false, subqueries = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if ((a == "-q" || a == "--query") && i + 1 < argc) query = argv[++i];
@@ -83,16 +79,17 @@ int main(int argc, char **argv) {
         else if (a == "--having") having = true;
         else if (a == "--count-distinct") countDistinct = true;
         else if (a == "--int-lists") intLists = true;
+        else if (a == "--subqueries") subqueries = true;
         else if (a == "--explain") explain = true;
         else if (a == "--repeat" && i + 1 < argc) repeat = std::atoi(argv[++i]); // re-run the query N times on the resident table, time to stderr
         else { std::fprintf(stderr, "Error parsing arguments: %s\n", a.c_str()); return 2; }
     }
     if (query.empty() || (dataDir.empty() && !parseOnly)) {
-        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only] [--honour-and-or] [--order-by] [--having] [--count-distinct] [--string-ranges] [--int-lists] [--explain]\n");
+        std::fprintf(stderr, "Usage: imm3_sql -q <sql> -d <dataDir> [--device n] [--parse-only] [--honour-and-or] [--order-by] [--having] [--count-distinct] [--string-ranges] [--int-lists] [--subqueries] [--explain]\n");
         return 2;
     }
     try {
-        const Query q = SQLParser::parseAll(query, orderBy, stringRanges, having, countDistinct, intLists);
+        const Query q = SQLParser::parseAll(query, orderBy, stringRanges, having, countDistinct, intLists, subqueries);
         if (parseOnly) {
             std::cout << showQuery(q) << "\n";
             if (!dataDir.empty()) {

@@ -157,6 +157,13 @@ class GpuSegmentManager {
 };
 
 struct Leaf { std::string col; SelectCondition cond; };
+// an IntInSet leaf carries the set's handle where the other leaves carry their values' bytes (include/imm3.h: IMM3_INT_IN_SET)
+inline void setLeaf(imm3_select &s, const SelectCondition &c) {
+    if (c.kind != SelectCondition::IntInSet) return;
+    s.match_bytes = (const uint8_t *)c.set.get();
+    s.match_lens = nullptr;
+    s.n_match = 1;
+}
 
 // RAII imm3_query
 struct QueryHandle {
@@ -198,6 +205,7 @@ class ScanOp : public ColumnVectorOperator {
             sels[i].match_bytes = (const uint8_t *)blobs[i].data();
             sels[i].match_lens = lens[i].data();
             sels[i].n_match = (int32_t)lens[i].size();
+            setLeaf(sels[i], leaves[i].cond);
         }
         std::vector<int32_t> proj;
         for (const auto &n : projNames) {
@@ -233,6 +241,7 @@ class ScanOp : public ColumnVectorOperator {
             sels[i].match_bytes = (const uint8_t *)blobs[i].data();
             sels[i].match_lens = lens[i].data();
             sels[i].n_match = (int32_t)lens[i].size();
+            setLeaf(sels[i], leaves[i].cond);
         }
         int keyBytes = 0; // a group key wider than 8 bytes: the _wide entry point
         for (int32_t g : group) keyBytes += cols_[(size_t)g].width();
@@ -329,6 +338,8 @@ class SelectOp : public ColumnVectorOperator {
         for (const auto &l : leaves)
             if (l.cond.kind == SelectCondition::NotMatch || l.cond.kind == SelectCondition::NoOp)
                 throw Exception("Unsupported condition: " + l.cond.toString()); // Select.scala:22
+        for (const auto &l : leaves)
+            if (l.cond.kind == SelectCondition::IntInQuery) throw Exception("IntInQuery: a sub-query runs through Engine::execute / executeAgg, which resolve it to a set");
     }
     std::unique_ptr<Iterator<ColumnVectorBatch>> iterator() override {
         std::vector<Leaf> leaves;
@@ -952,6 +963,7 @@ class Engine {
             p.sels[i].match_bytes = (const uint8_t *)p.blobs[i].data();
             p.sels[i].match_lens = p.lens[i].data();
             p.sels[i].n_match = (int32_t)p.lens[i].size();
+            setLeaf(p.sels[i], leaves[i].cond);
         }
         return true;
     }
@@ -977,7 +989,88 @@ class Engine {
     // ProjectAgg: per-segment ProjectAggOp + ProjectAggregateQueueOp's combine by key (first arrival first; segments
     // ascending).  Rows list the aggregators' repr in SELECT-list order (the reference iterates a mutable.HashMap
     // keyed by alias, whose order is not reproduced).
+    // ---- IN (sub-query): every IntInQuery leaf becomes IntInSet(the device-resident set of its inner selection) ----
+    static bool hasSubquery(const SelectADT &s) {
+        if (s.kind == SelectADT::And || s.kind == SelectADT::Or) return hasSubquery(*s.op1) || hasSubquery(*s.op2);
+        return s.kind == SelectADT::Select && s.cond.kind == SelectCondition::IntInQuery;
+    }
+    static bool hasResolvedSet(const SelectADT &s) {
+        if (s.kind == SelectADT::And || s.kind == SelectADT::Or) return hasResolvedSet(*s.op1) || hasResolvedSet(*s.op2);
+        return s.kind == SelectADT::Select && s.cond.kind == SelectCondition::IntInSet;
+    }
+    // The statement with its sub-queries resolved: the inner query's selects run as one table query where tablePlan takes them, else as
+    // per-segment queries; either way all of them are the sources of one imm3_int_set, and the outer statement then takes whichever
+    // plan it would take with an IntIn.  (This manager has one context: there is no host route here.)
+    Query resolveSubqueries(const Query &q) {
+        subPaths_.clear();
+        Query out = q;
+        out.select = resolveSelect(*q.select);
+        return out;
+    }
+    std::shared_ptr<SelectADT> resolveSelect(const SelectADT &s) {
+        if (s.kind == SelectADT::And) return SelectADT::mkAnd(resolveSelect(*s.op1), resolveSelect(*s.op2));
+        if (s.kind == SelectADT::Or) return SelectADT::mkOr(resolveSelect(*s.op1), resolveSelect(*s.op2));
+        if (s.kind == SelectADT::Select && s.cond.kind == SelectCondition::IntInQuery) return SelectADT::mkSelect(s.col, resolveInner(*s.cond.inner));
+        return std::make_shared<SelectADT>(s);
+    }
+    SelectCondition resolveInner(const Query &inner0) {
+        const size_t at = subPaths_.size();
+        subPaths_.push_back("");
+        Query inner = inner0;
+        inner.select = resolveSelect(*inner0.select); // (sub-queries of the sub-query first)
+        const Table &table = sm_.sm.getTable(inner.table);
+        const Column &col = table.getColumn(inner.project.cols.at(0));
+        if (col.columnType == ColumnType::STRING) throw Exception("IntInQuery: the inner column `" + col.name + "' is neither int32 nor int8 (Unsupported column vector)");
+        std::vector<std::unique_ptr<QueryHandle>> opened;
+        std::vector<imm3_query *> sources;
+        std::vector<int32_t> columns;
+        auto placeOf = [&](const std::vector<Column> &used) -> int32_t {
+            for (size_t k = 0; k < used.size(); ++k) if (used[k].name == col.name) return (int32_t)k;
+            throw Exception("NoSuchElementException: key not found: " + col.name);
+        };
+        TablePlan p;
+        if (tablePlan(inner, p)) {
+            opened.push_back(std::make_unique<QueryHandle>());
+            int rc;
+            if (p.tree) rc = imm3_query_create_table_expr(sm_.ctx(), p.table, p.usedIdx.data(), (int32_t)p.usedIdx.size(), p.sels.data(), (int32_t)p.sels.size(),
+                                                          p.prog.data(), (int32_t)p.prog.size(), nullptr, 0, 0, table.blockSize, &opened.back()->q);
+            else rc = imm3_query_create_table(sm_.ctx(), p.table, p.usedIdx.data(), (int32_t)p.usedIdx.size(), p.sels.data(), (int32_t)p.sels.size(),
+                                              nullptr, 0, 0, table.blockSize, &opened.back()->q);
+            if (p.tree && tableTreeRefused(rc)) opened.clear();
+            else {
+                imm3Check(rc);
+                sources.push_back(opened.back()->q);
+                columns.push_back(placeOf(p.used));
+                subPaths_[at] = "set/table";
+            }
+        }
+        if (sources.empty()) {
+            subPaths_[at] = "set/segments";
+            const std::vector<Column> used = getColumns(inner, table);
+            std::vector<Leaf> leaves;
+            std::vector<int32_t> prog;
+            const bool tree = asTree(inner);
+            if (tree) SelectTreeOp::program(*inner.select, leaves, prog, notTree(inner));
+            else leaves = resolveSelectOps(inner);
+            SelectOp::checkConditions(leaves);
+            const int nseg = sm_.sm.getTableSegmentCount(table.name);
+            for (int seg = 0; seg < nseg; ++seg) {
+                ScanOp scan(sm_, seg, inner.table, used);
+                opened.push_back(std::make_unique<QueryHandle>());
+                scan.makeQuery(leaves, {}, 0, *opened.back(), tree ? &prog : nullptr);
+                sources.push_back(opened.back()->q);
+                columns.push_back(placeOf(used));
+            }
+        }
+        if (sources.empty()) return SelectCondition::intIn({}); // no segment at all: the empty list
+        imm3_int_set *set = nullptr;
+        imm3Check(imm3_int_set_create(sm_.ctx(), sources.data(), columns.data(), (int32_t)sources.size(), &set)); // (runs every source's select chain; sources are not retained)
+        return SelectCondition::intInSet(std::shared_ptr<void>(set, [](void *h) { imm3_int_set_destroy((imm3_int_set *)h); }));
+    }
+
     std::vector<AggMapTuple> executeAgg(const Query &q) {
+        if (hasSubquery(*q.select)) return executeAgg(resolveSubqueries(q));
+        if (!hasResolvedSet(*q.select)) subPaths_.clear(); // (a resolved statement keeps what its resolution recorded)
         const Table &table = sm_.sm.getTable(q.table);
         const std::vector<Column> used = getColumns(q, table);
         const std::vector<Leaf> leaves = resolveSelectOps(q);
@@ -1047,6 +1140,8 @@ class Engine {
             }
             return rows;
         }
+        if (hasSubquery(*q.select)) return execute(resolveSubqueries(q));
+        if (!hasResolvedSet(*q.select)) subPaths_.clear();
         if (q.project.kind != ProjectADT::Project) throw Exception("NoProject");
         const std::vector<std::pair<int, bool>> okeys = orderKeys(q.project.cols, q.project.orderBy); // (throws for a key outside the SELECT list)
         const bool ordered = !okeys.empty();
@@ -1141,12 +1236,19 @@ class Engine {
 
     // which way the last execute / executeAgg went: "one table query[: select tree, <kernel form>]", or "per-segment queries[: <the
     // library's refusal of the tree>]" (imm3_sql --explain prints it)
-    const std::string &lastPath() const { return path_; }
+    // ... and, for a statement with sub-queries, how each ran, outermost first: "set/table" (one table query was the set's source) or
+    // "set/segments" (per-segment queries were)
+    std::string lastPath() const {
+        std::string out = path_;
+        for (size_t i = 0; i < subPaths_.size(); ++i) out += (i ? "," : "; sub-queries: ") + subPaths_[i];
+        return out;
+    }
 
   private:
     GpuSegmentManager &sm_;
     bool honourAndOr_ = false, honourNotMatch_ = false;
     std::string path_;
+    std::vector<std::string> subPaths_;
 };
 
 } // namespace immutabledb

@@ -231,6 +231,8 @@ struct Row {
 };
 
 // ---- Query ADT (Query.scala:3-46) ----
+struct Query;
+inline std::string showInnerQuery(const Query &q); // (defined behind Query: an IntInQuery condition prints its inner statement)
 struct SelectCondition {
     // Match .. NoOp: same order as IMM3_MATCH .. IMM3_NOOP.  EXTENSION, behind them: byte-order ranges on a string column (include/imm3.h:
     // IMM3_STR_RANGE; the order of ORDER BY and the string MAX aggregate -- unsigned, byte-wise, from the first byte).  StrRange(lo, hi)
@@ -238,10 +240,18 @@ struct SelectCondition {
     // relative to v padded with 0x00.
     // EXTENSION, behind those: IntIn(values), an IN-list on an int32 / int8 column (include/imm3.h: IMM3_INT_IN) -- exact integer
     // membership, duplicates once, an empty list selects nothing; not under an Or or a NotMatch-as-NOT tree (the library refuses it).
-    enum Kind { Match, NotMatch, EQ, GT, LT, NoOp, StrRange, Prefix, StrGT, StrLT, IntIn } kind = NoOp;
+    // EXTENSION, behind that: IntInQuery(query), IN (sub-query) -- the rows whose value is one the inner query's column takes among the
+    // rows it selects (include/imm3.h: IMM3_INT_IN_SET).  The inner query is a plain projection of exactly one int32 / int8 column
+    // with a where tree: an aggregation, an order by or a limit inside is refused (intInQuery).  Engine::execute resolves it to
+    // IntInSet(set) -- the device-resident set built from the inner selection (imm3_int_set_create) -- which is what the operators see.
+    enum Kind { Match, NotMatch, EQ, GT, LT, NoOp, StrRange, Prefix, StrGT, StrLT, IntIn, IntInQuery, IntInSet } kind = NoOp;
     double value = 0;                 // EQ / GT / LT
     std::vector<std::string> values;  // Match / NotMatch; StrRange: {lo, hi}; Prefix / StrGT / StrLT: {the value}
     std::vector<int32_t> ints;        // IntIn
+    std::shared_ptr<Query> inner;     // IntInQuery
+    std::shared_ptr<void> set;        // IntInSet: the imm3_int_set handle (destroyed with the last condition that holds it)
+    static inline SelectCondition intInQuery(const Query &q); // (defined behind Query)
+    static SelectCondition intInSet(std::shared_ptr<void> handle) { SelectCondition c; c.kind = IntInSet; c.set = std::move(handle); return c; }
     static SelectCondition intIn(std::vector<int32_t> v) { SelectCondition c; c.kind = IntIn; c.ints = std::move(v); return c; }
     static SelectCondition strRange(std::string lo, std::string hi) { SelectCondition c; c.kind = StrRange; c.values = {std::move(lo), std::move(hi)}; return c; }
     static SelectCondition prefix(std::string p) { SelectCondition c; c.kind = Prefix; c.values = {std::move(p)}; return c; }
@@ -253,7 +263,8 @@ struct SelectCondition {
     // predecessor (big-endian arithmetic over the column's width); where there is none the leaf is one no row passes (lo 01, hi 00:
     // 01 00 00 .. > 00 FF FF ..).  A bound longer than the column throws (the library refuses it too).
     // An IntIn leaf (7, IMM3_INT_IN) carries each value as its 4 little-endian bytes: concatenated they are the leaf's match_bytes.
-    int32_t abiCond() const { return kind == IntIn ? 7 : (isStrRange() ? 6 : (int32_t)kind); }
+    // An IntInSet leaf (8, IMM3_INT_IN_SET) carries no values: its match_bytes is the handle itself, n_match 1 (operators.hpp: setLeaf).
+    int32_t abiCond() const { return kind == IntInSet ? 8 : (kind == IntIn ? 7 : (isStrRange() ? 6 : (int32_t)kind)); }
     std::vector<std::string> abiValues(int width) const {
         if (kind == IntIn) {
             std::vector<std::string> out;
@@ -304,6 +315,8 @@ struct SelectCondition {
         case StrGT: return "StrGT(" + values[0] + ")";
         case StrLT: return "StrLT(" + values[0] + ")";
         case IntIn: { std::string s = "IntIn(List("; for (size_t i = 0; i < ints.size(); ++i) s += (i ? ", " : "") + std::to_string(ints[i]); return s + "))"; }
+        case IntInQuery: return "IntInQuery(" + showInnerQuery(*inner) + ")";
+        case IntInSet: return "IntInSet";
         default: return "NoOp";
         }
     }
@@ -433,5 +446,28 @@ struct Query {
     std::shared_ptr<SelectADT> select;
     ProjectADT project;
 };
+
+inline std::string showSelectADT(const SelectADT &s) {
+    switch (s.kind) {
+    case SelectADT::And: return "And(" + showSelectADT(*s.op1) + "," + showSelectADT(*s.op2) + ")";
+    case SelectADT::Or: return "Or(" + showSelectADT(*s.op1) + "," + showSelectADT(*s.op2) + ")";
+    case SelectADT::Select: return "Select(" + s.col + "," + s.cond.toString() + ")";
+    default: return "NoSelect";
+    }
+}
+// an IntInQuery's inner statement: always a projection of one column without a limit
+inline std::string showInnerQuery(const Query &q) {
+    return "Query(" + q.table + "," + showSelectADT(*q.select) + ",Project(List(" + (q.project.cols.empty() ? std::string() : q.project.cols[0]) + "),0))";
+}
+inline SelectCondition SelectCondition::intInQuery(const Query &q) {
+    if (q.project.kind != ProjectADT::Project) throw Exception("IntInQuery: the inner query is an aggregation; it must be a plain projection of one column");
+    if (q.project.cols.size() != 1) throw Exception("IntInQuery: the inner query must project exactly one column, not " + std::to_string(q.project.cols.size()));
+    if (!q.project.orderBy.empty()) throw Exception("IntInQuery: the inner query has an order by; the set is its whole selection, unordered");
+    if (q.project.limit != 0) throw Exception("IntInQuery: the inner query has a limit; the set is its whole selection");
+    SelectCondition c;
+    c.kind = IntInQuery;
+    c.inner = std::make_shared<Query>(q);
+    return c;
+}
 
 } // namespace immutabledb

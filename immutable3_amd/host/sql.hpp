@@ -42,6 +42,11 @@
 //   filter           := ... | ident "in" "(" rep1sep(int, ",") ")"        int = -?[0-9]+
 // A literal outside int32 throws (kIntListRangeError + the literal) at parse time.  With the flag off the grammar and every
 // parse-failure message are what they were.
+// EXTENSION, only when asked for (parseAll(sql, ..., intLists, true); imm3_sql --subqueries) -- IN (sub-query) on int32 / int8 columns
+// (SelectCondition::IntInQuery), tried behind everything above:
+//   filter           := ... | ident "in" "(" "select" ident from where ")"
+// The inner statement is one column, a table and an optional where tree (which may hold further sub-queries): no aggregate, no group
+// by, order by or limit can be spelled there.  With the flag off the grammar and every parse-failure message are what they were.
 //   ident =[\w#]+   value = [\w0-9#]+  (no sign, no decimal point)                          (:119-121)
 #pragma once
 
@@ -57,9 +62,10 @@ class SQLParser {
   public:
     static constexpr const char *kIntListRangeError = "integer literal out of range for an IN-list (int32): ";
     static Query parseAll(const std::string &input, bool orderBy = false, bool stringRanges = false, bool having = false, bool countDistinct = false,
-                          bool intLists = false) {
+                          bool intLists = false, bool subqueries = false) {
         SQLParser p(input);
         p.intLists_ = intLists;
+        p.subqueries_ = subqueries;
         p.countDistinct_ = countDistinct;
         p.orderBy_ = orderBy;
         p.stringRanges_ = stringRanges;
@@ -78,7 +84,7 @@ class SQLParser {
     explicit SQLParser(const std::string &s) : s_(s) {}
     const std::string &s_;
     size_t furthest_ = 0;
-    bool orderBy_ = false, stringRanges_ = false, having_ = false, countDistinct_ = false, intLists_ = false;
+    bool orderBy_ = false, stringRanges_ = false, having_ = false, countDistinct_ = false, intLists_ = false, subqueries_ = false;
     std::string expected_ = "`select'";
 
     size_t skipWs(size_t i) const {
@@ -199,6 +205,22 @@ class SQLParser {
                 size_t u;
                 if (lit(t, ")", u)) {
                     out = SelectADT::mkSelect(f, SelectCondition::intIn(ints));
+                    end = u;
+                    return true;
+                }
+            }
+        }
+        if (subqueries_) { // filterInQuery: ident "in" "(" "select" ident from where ")"
+            std::string g, tbl;
+            size_t s, a, b, e, u;
+            if (ident(i, f, p) && lit(p, "in", q) && lit(q, "(", r) && lit(r, "select", s) && ident(s, g, a) && fromTable(a, tbl, b)) {
+                Query inner;
+                inner.table = tbl;
+                where(b, inner.select, e);
+                if (lit(e, ")", u)) {
+                    inner.project.kind = ProjectADT::Project;
+                    inner.project.cols = {g};
+                    out = SelectADT::mkSelect(f, SelectCondition::intInQuery(inner));
                     end = u;
                     return true;
                 }

@@ -29,6 +29,9 @@ STR_RANGE = 6
 INT_IN = 7
 INT_IN_MAX_VALUES = 1 << 24   # IMM3_INT_IN_MAX_VALUES
 INT_LIST_I8, INT_LIST_ARGS, INT_LIST_LDS, INT_LIST_GLOBAL = 0, 1, 2, 3   # plan_int_list_form (csrc/imm3_int_list_plan.h: IntListForm)
+# extension (include/imm3.h: IMM3_INT_IN_SET): membership in a device-resident set built from other queries' selections -- IN
+# (sub-query); operand: an IntSet of the same context
+INT_IN_SET = 8
 # operators of a select tree's postfix program (include/imm3.h: IMM3_EXPR_AND / IMM3_EXPR_OR / IMM3_EXPR_NOT); values >= 0 are leaf
 # indices.  NOT pops one operand and pushes its complement (-4: -3 stays the unknown operator it has always been)
 EXPR_AND, EXPR_OR, EXPR_NOT = -1, -2, -4
@@ -64,6 +67,7 @@ EXPORTS = [
     "imm3_comm_merge_groups_view", "imm3_comm_merge_groups_view_all",
     "imm3_pfor_encode_bound", "imm3_pfor_encode_block", "imm3_pfor_encode_column",
     "imm3_snappy_encode_bound", "imm3_snappy_encode_block",
+    "imm3_int_set_create", "imm3_int_set_destroy", "imm3_int_set_info", "imm3_int_set_values",
 ]
 # include/imm3_diag.h: measurement / tuning hooks, not part of the drop-in boundary
 DIAG_EXPORTS = [
@@ -75,6 +79,7 @@ DIAG_EXPORTS = [
     "imm3_plan_hi16_bounds", "imm3_plan_hi16_class", "imm3_plan_hi16_span_ok", "imm3_plan_hi16_eligible",
     "imm3_query_agg_form", "imm3_query_hi16_refined", "imm3_segment_hi16_plane", "imm3_query_expr_form", "imm3_expr_normalize", "imm3_query_group_order_path",
     "imm3_query_group_filter_stats", "imm3_group_filter_check", "imm3_comm_merge_view_path", "imm3_merge_view_plan_json",
+    "imm3_plan_int_set_scratch_slots", "imm3_int_set_create_capped", "imm3_int_set_table",
 ]
 COMM_ID_BYTES = 128
 # imm3_query_device_ptr ids of an ordered query's arrays (include/imm3.h)
@@ -314,10 +319,18 @@ def load() -> C.CDLL:
     L.imm3_merge_view_plan_json.argtypes = [i32, vp, vp, i32, vp, vp, vp, P(CGroupView), C.c_uint32, vp, i64, P(i64)]
     L.imm3_comm_merge_ordered.argtypes = [vp, P(vp), vp, i32, i64, vp, vp, P(vp), u64, P(u64)]
     L.imm3_comm_merge_ordered_all.argtypes = [P(vp), i32, P(P(vp)), P(vp), P(i32), i64, vp, vp, P(vp), u64, P(u64)]
+    L.imm3_int_set_create.argtypes = [vp, P(vp), vp, i32, P(vp)]
+    L.imm3_int_set_create_capped.argtypes = [vp, P(vp), vp, i32, i64, P(vp)]
+    L.imm3_int_set_destroy.argtypes = [vp]
+    L.imm3_int_set_info.argtypes = [vp, P(i64), P(i32), P(i32), P(i32)]
+    L.imm3_int_set_values.argtypes = [vp, vp, i64]
+    L.imm3_int_set_table.argtypes = [vp, vp, i64, P(i64), P(i32), P(i32), vp, P(i32)]
+    L.imm3_plan_int_set_scratch_slots.argtypes = [i64, i32, i32, i64]
     for name in EXPORTS + DIAG_EXPORTS:
         fn = getattr(L, name)
         if name not in ("imm3_last_error", "imm3_pfor_encode_bound", "imm3_snappy_encode_bound"):
             fn.restype = C.c_int
+    L.imm3_plan_int_set_scratch_slots.restype = C.c_int64
     L.imm3_snappy_encode_bound.restype = C.c_uint64
     L.imm3_snappy_encode_bound.argtypes = [C.c_uint64]
     L.imm3_snappy_encode_block.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -464,7 +477,7 @@ class Context:
             # returns their device memory now instead of when the garbage collector gets to them.
             with self._children_mu:
                 kids = list(self._children)
-            for kind in (Graph, Comm, DeviceQuery, DeviceTable, DeviceSegment):   # graphs, comms, queries -> tables -> segments
+            for kind in (Graph, Comm, DeviceQuery, IntSet, DeviceTable, DeviceSegment):   # graphs, comms, queries -> sets -> tables -> segments
                 for k in kids:
                     if isinstance(k, kind):
                         k.close()
@@ -640,6 +653,73 @@ class RawIntList:
         self.n_match, self.values = int(n_match), values
 
 
+class RawIntSet:
+    """An INT_IN_SET operand handed to the library as it stands: n_match and the handle (None: a null match_bytes) -- for the tests
+    of the leaf's argument checks."""
+
+    def __init__(self, n_match: int, int_set=None):
+        self.n_match, self.int_set = int(n_match), int_set
+
+
+class IntSet:
+    """imm3_int_set: the distinct values one column takes among the rows a query selects, united over [(query, column), ...] --
+    built on the device and kept there (imm3_int_set_create).  `column` indexes the query's used columns.  The operand of an
+    INT_IN_SET leaf, (col, INT_IN_SET, int_set), in any number of queries of the same context; they keep it alive, so close() may
+    come before they run.  max_values: the diagnostic creator with a lower cap on the distinct values (imm3_diag.h)."""
+
+    def __init__(self, ctx: Context, sources: Sequence[tuple], max_values: Optional[int] = None):
+        self.ctx = ctx
+        srcs = list(sources)
+        hs = (C.c_void_p * max(1, len(srcs)))(*[(q._h if q is not None else None) for q, _ in srcs])
+        cols = np.array([int(c) for _, c in srcs] or [0], dtype=np.int32)
+        self._h = C.c_void_p()
+        if max_values is None:
+            _check(load().imm3_int_set_create(ctx._h, hs, cols.ctypes.data, len(srcs), C.byref(self._h)))
+        else:
+            _check(load().imm3_int_set_create_capped(ctx._h, hs, cols.ctypes.data, len(srcs), int(max_values), C.byref(self._h)))
+        ctx._adopt(self)
+
+    def info(self):
+        """(n_values, min, max, form): the distinct values, their extremes (0, 0 when empty), the INT_LIST_* form an int32 consumer probes"""
+        n, lo, hi, form = C.c_int64(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _check(load().imm3_int_set_info(self._h, C.byref(n), C.byref(lo), C.byref(hi), C.byref(form)))
+        return int(n.value), int(lo.value), int(hi.value), int(form.value)
+
+    def values(self) -> np.ndarray:
+        """the values, ascending, each once (copied from the device, sorted on the host)"""
+        n = self.info()[0]
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        _check(load().imm3_int_set_values(self._h, out.ctypes.data, n))
+        return out[:n]
+
+    def table(self):
+        """imm3_diag.h: imm3_int_set_table -- (slots int32[], empty, max_probe, set256 uint32[8], host_route)"""
+        n_slots, empty, max_probe, host = C.c_int64(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        set256 = np.zeros(8, np.uint32)
+        _check(load().imm3_int_set_table(self._h, None, 0, C.byref(n_slots), C.byref(empty), C.byref(max_probe), set256.ctypes.data, C.byref(host)))
+        slots = np.zeros(max(n_slots.value, 1), dtype=np.int32)
+        if n_slots.value:
+            _check(load().imm3_int_set_table(self._h, slots.ctypes.data, slots.size, C.byref(n_slots), C.byref(empty), C.byref(max_probe), set256.ctypes.data, C.byref(host)))
+        return slots[: n_slots.value], int(empty.value), int(max_probe.value), set256, bool(host.value)
+
+    def close(self):
+        if self._h:
+            load().imm3_int_set_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def plan_int_set_scratch_slots(selected_rows: int, lo: int, hi: int, cap: int = INT_IN_MAX_VALUES) -> int:
+    """include/imm3_diag.h: imm3_plan_int_set_scratch_slots -- the slots of the scratch table an IntSet build inserts into; a pure
+    function, no device needed."""
+    return int(load().imm3_plan_int_set_scratch_slots(selected_rows, lo, hi, cap))
+
+
 def _cselects(sels):
     """(CSelect array, the numpy buffers it points into) for [(column, cond, operand)]"""
     cs = (CSelect * max(1, len(sels)))()
@@ -663,6 +743,12 @@ def _cselects(sels):
             cs[i].match_bytes = None if blob is None else blob.ctypes.data
             cs[i].match_lens = None
             cs[i].n_match = operand.n_match
+        elif cond == INT_IN_SET:   # the handle itself travels in match_bytes
+            raw = operand if isinstance(operand, RawIntSet) else RawIntSet(1, operand)
+            keep.append(raw.int_set)   # (the library retains the set; this keeps the Python object from closing it mid-call)
+            cs[i].match_bytes = None if raw.int_set is None else raw.int_set._h
+            cs[i].match_lens = None
+            cs[i].n_match = raw.n_match
         elif cond == INT_IN:   # 4-byte little-endian values; no lengths
             vals = [int(v) for v in (operand if operand is not None else [])]
             if any(not -(1 << 31) <= v < (1 << 31) for v in vals):

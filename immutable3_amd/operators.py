@@ -23,7 +23,7 @@ import numpy as np
 
 from . import native
 from .native import Imm3Error
-from .query import (STR_RANGE_CONDS, IntIn, str_range_bounds)
+from .query import (STR_RANGE_CONDS, IntIn, IntInQuery, str_range_bounds)
 from .query import (EQ, GT, LT, And, Avg, Count, CountDistinct, Match, Max, Min, NoOp, NoSelect, NotMatch, Or, Project, ProjectAgg,
                     Query, Select, SelectADT, SelectCondition, Sum, group_filter_leaves, order_keys)
 from .schema import CodecType, Column, Row, Table
@@ -210,7 +210,18 @@ class ProjectionOperator(Operator):    # Operator.scala:26-28
     pass
 
 
-SUPPORTED_CONDS = (Match, GT, LT, EQ) + STR_RANGE_CONDS + (IntIn,)   # what SelectOp.iterator lets through (Select.scala:17-23, and the range and integer-list extensions)
+class IntInSet(SelectCondition):
+    """An IntInQuery whose inner query has run: membership in the device-resident set built from its selection (native.IntSet,
+    IMM3_INT_IN_SET).  Made by Engine.resolve_subqueries only; every consumer query retains the set."""
+
+    def __init__(self, int_set: "native.IntSet"):
+        self.int_set = int_set
+
+    def __repr__(self):
+        return f"IntInSet({self.int_set.info()[0]} values)"
+
+
+SUPPORTED_CONDS = (Match, GT, LT, EQ) + STR_RANGE_CONDS + (IntIn, IntInSet)   # what SelectOp.iterator lets through (Select.scala:17-23, and the range, integer-list and set extensions)
 
 
 def _cond_spec(cond: SelectCondition, width: int = 0):
@@ -219,6 +230,8 @@ def _cond_spec(cond: SelectCondition, width: int = 0):
         return native.STR_RANGE, list(str_range_bounds(cond, width))
     if isinstance(cond, IntIn):
         return native.INT_IN, list(cond.values)
+    if isinstance(cond, IntInSet):
+        return native.INT_IN_SET, cond.int_set
     if isinstance(cond, Match):
         return native.MATCH, [v.encode("utf-8") if isinstance(v, str) else bytes(v) for v in cond.values]
     if isinstance(cond, NotMatch):
@@ -1125,6 +1138,82 @@ class Engine:
         # who applied having / order by / limit to the groups of the last device merge: "device" (imm3_comm_merge_groups_view), "host"
         # (the library refused the view: plain merge, ordered here), None (no such clause, or no device merge yet)
         self.last_merge_view = None
+        # how the sub-queries (IntInQuery) of the last statement ran, outermost first: "set/table" (one table query was the set's source),
+        # "set/segments" (per-segment queries were), "host" (several contexts: the inner values fetched, an IntIn leaf instead)
+        self.last_subquery_paths: List[str] = []
+
+    def lastPath(self) -> str:
+        """which route the last statement's sub-queries took (`--explain`): the paths joined by ",", "" for a statement without one"""
+        return ",".join(self.last_subquery_paths)
+
+    def resolve_subqueries(self, query: Query) -> Query:
+        """The statement with every IntInQuery leaf replaced by what it resolves to: the inner query's selects run (one table query
+        where _table_plan takes them, else per-segment queries), ALL of them become the sources of one native.IntSet, and the leaf
+        becomes IntInSet(that set) -- so the outer statement takes whichever plan it would take with an IntIn.  A segment manager
+        with more than one context cannot share a set: the inner values are fetched and the leaf becomes an IntIn."""
+        def holds(sel, kind):
+            if isinstance(sel, (And, Or)):
+                return holds(sel.op1, kind) or holds(sel.op2, kind)
+            return isinstance(sel, Select) and isinstance(sel.cond, kind)
+        if not holds(query.select, IntInQuery):
+            if not holds(query.select, IntInSet):              # (a statement resolved already keeps what its resolution recorded)
+                self.last_subquery_paths = []
+            return query
+        self.last_subquery_paths = []
+        return Query(query.table, self._resolve_select(query.select), query.project)
+
+    def _resolve_select(self, sel: SelectADT) -> SelectADT:
+        if isinstance(sel, (And, Or)):
+            return type(sel)(self._resolve_select(sel.op1), self._resolve_select(sel.op2))
+        if isinstance(sel, Select) and isinstance(sel.cond, IntInQuery):
+            return Select(sel.col, self._resolve_inner(sel.cond.query))
+        return sel
+
+    def _resolve_inner(self, inner: Query) -> SelectCondition:
+        at = len(self.last_subquery_paths)
+        self.last_subquery_paths.append("")
+        inner = Query(inner.table, self._resolve_select(inner.select), inner.project)   # (sub-queries of the sub-query first)
+        table = self.sm.getTable(inner.table)
+        col = table.getColumn(inner.project.cols[0])
+        if not (col.codec in CodecType.INT_CODECS or col.codec in CodecType.TINYINT_CODECS):
+            raise Exception(f"IntInQuery: the inner column {col.name!r} is neither int32 nor int8 (Unsupported column vector)")
+        if len(self.sm.ctxs) > 1:
+            self.last_subquery_paths[at] = "host"
+            parts = [cols[0] for (_, _, cols) in self._columns(inner)]   # (resolved above: not through resolve_subqueries again)
+            vals = np.unique(np.concatenate(parts).astype(np.int64)) if parts else np.zeros(0, np.int64)
+            return IntIn([int(v) for v in vals])
+        sources, opened = [], []
+        try:
+            plan = self._table_plan(inner)
+            if plan is not None:
+                dt, used, used_idx, sels, prog = plan
+                try:
+                    q = native.DeviceQuery(dt.ctx, dt, used_idx, sels, [], 0, table.blockSize, expr=prog)
+                    opened.append(q)
+                    sources.append((q, [c.name for c in used].index(col.name)))
+                    self.last_subquery_paths[at] = "set/table"
+                except native.Imm3Error as e:
+                    if not self._table_tree_refused(e, prog):
+                        raise
+            if not sources:
+                self.last_subquery_paths[at] = "set/segments"
+                for _, proj in self.pipelines(inner):
+                    fused = proj._fused()
+                    if fused is None:
+                        raise Exception("IntInQuery: the inner query must be a fused scan / select pipeline")
+                    scan, leaves = fused
+                    for (_, cond) in leaves:
+                        if not isinstance(cond, SUPPORTED_CONDS):
+                            raise Exception(f"Unsupported condition: {cond}")
+                    q = scan._query(leaves, (), 0, _expr_of(proj.op))
+                    opened.append(q)
+                    sources.append((q, [c.name for c in scan.cols].index(col.name)))
+            if not sources:                                    # no segment at all: the empty list
+                return IntIn([])
+            return IntInSet(native.IntSet(self.sm.ctxs[0], sources))   # (runs every source's select chain: none has run yet)
+        finally:
+            for q in opened:                                   # sources are not retained
+                q.close()
 
     def _not_tree(self, query: Query) -> bool:
         return self.honour_not_match and has_not_match(query.select)
@@ -1196,6 +1285,7 @@ class Engine:
         """ProjectAgg queries: per-segment ProjectAggOp, then ProjectAggregateQueueOp's combine by group key
         (first arrival first; segments in ascending order).  Returns an ordered dict key -> {alias: Aggregator}.
         When the table qualifies, the whole thing is one imm3 table query (groups already merged on the GPU)."""
+        query = self.resolve_subqueries(query)
         table = self.sm.getTable(query.table)
         plan = self._table_plan(query)
         if plan is not None:
@@ -1320,6 +1410,9 @@ class Engine:
     def execute_table_columns(self, query: Query):
         """Project query over the whole table as ONE fused launch: (segment uint32[n], row uint32[n], [column arrays])
         in ascending (segment, row) order with the global limit applied -- or None when the table does not qualify."""
+        return self._table_columns(self.resolve_subqueries(query))
+
+    def _table_columns(self, query: Query):
         plan = self._table_plan(query)
         if plan is None:
             return None
@@ -1353,7 +1446,8 @@ class Engine:
             for _, aggmap in self.execute_agg(query).items():
                 yield Row(*[a.repr() for a in aggmap.values()])
             return
-        fused = self.execute_table_columns(query)
+        query = self.resolve_subqueries(query)                   # (once: what follows sees IntInSet / IntIn leaves)
+        fused = self._table_columns(query)
         if fused is not None:
             yield from _rows_from_columns(fused[2])
             return
@@ -1403,4 +1497,7 @@ class Engine:
 
     def execute_columns(self, query: Query):
         """Columnar result per segment: [(segIdx, row_index, [column arrays])] (no Row boxing)."""
+        return self._columns(self.resolve_subqueries(query))
+
+    def _columns(self, query: Query):
         return [(segIdx, *proj.run_columns()) for segIdx, proj in self.pipelines(query)]

@@ -136,6 +136,38 @@ class IntIn(SelectCondition):
         object.__setattr__(self, "values", tuple(vals))
 
 
+# ---- EXTENSION: IN (sub-query), the semi-join (include/imm3.h: IMM3_INT_IN_SET): the rows whose value is one the inner query's column
+# takes among the rows the inner query selects.  The inner query is a plain projection of exactly ONE int32 / int8 column with a where
+# tree: no aggregation, no order by, no limit (the set is the whole selection's either way; refused so that nobody reads a cut into
+# it).  Uncorrelated: the inner query names its own table and nothing of the outer one.  Not under an Or or a NotMatch-as-NOT tree.
+# `query` is typed loosely because Query is defined below. ----
+INT_IN_QUERY_ERRORS = {
+    "query": "IntInQuery takes a Query, not ",
+    "agg": "IntInQuery: the inner query is an aggregation; it must be a plain projection of one column",
+    "cols": "IntInQuery: the inner query must project exactly one column, not ",
+    "order": "IntInQuery: the inner query has an order by; the set is its whole selection, unordered",
+    "limit": "IntInQuery: the inner query has a limit; the set is its whole selection",
+}
+
+
+@dataclass(frozen=True)
+class IntInQuery(SelectCondition):
+    query: object
+
+    def __init__(self, query):
+        if not isinstance(query, Query):
+            raise ValueError(INT_IN_QUERY_ERRORS["query"] + repr(query))
+        if not isinstance(query.project, Project):
+            raise ValueError(INT_IN_QUERY_ERRORS["agg"])
+        if len(query.project.cols) != 1:
+            raise ValueError(INT_IN_QUERY_ERRORS["cols"] + str(list(query.project.cols)))
+        if query.project.order_by:
+            raise ValueError(INT_IN_QUERY_ERRORS["order"])
+        if query.project.limit != 0:
+            raise ValueError(INT_IN_QUERY_ERRORS["limit"])
+        object.__setattr__(self, "query", query)
+
+
 @dataclass(frozen=True)
 class _NoOp(SelectCondition):      # Query.scala:9
     pass

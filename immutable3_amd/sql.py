@@ -49,7 +49,13 @@ EXTENSION, only when asked for -- parseAll(sql, int_lists=True) -- IN-lists on i
 reference's alternatives (and behind the string ranges):
   filter           := ... | ident "in" "(" rep1sep(int, ",") ")"        int = -?[0-9]+
 A literal outside int32 raises ValueError (query.INT_IN_RANGE_ERROR + the literal), at parse time.  With the flag off the grammar and
-every parse-failure message are what they were."""
+every parse-failure message are what they were.
+
+EXTENSION, only when asked for -- parseAll(sql, subqueries=True) -- IN (sub-query) on int32 / int8 columns (query.IntInQuery), tried
+behind everything above:
+  filter           := ... | ident "in" "(" "select" ident from where ")"
+The inner statement is one column, a table and an optional where tree (which may hold further sub-queries): no aggregate, no
+group by, order by or limit can be spelled there.  With the flag off the grammar and every parse-failure message are what they were."""
 from __future__ import annotations
 
 import re
@@ -67,16 +73,17 @@ class ParseError(Exception):
 
 class SQLParser:
     def __init__(self, s: str, order_by: bool = False, string_ranges: bool = False, group_order: bool = False, having: bool = False,
-                 count_distinct: bool = False, int_lists: bool = False):
+                 count_distinct: bool = False, int_lists: bool = False, subqueries: bool = False):
         self.int_lists = int_lists
+        self.subqueries = subqueries
         self.s, self.order_by, self.string_ranges, self.group_order, self.having = s, order_by, string_ranges, group_order, having
         self.count_distinct = count_distinct
         self.furthest, self.expected = 0, "`select'"
 
     @staticmethod
     def parseAll(sql: str, order_by: bool = False, string_ranges: bool = False, group_order: bool = False, having: bool = False,
-                 count_distinct: bool = False, int_lists: bool = False) -> Q.Query:
-        p = SQLParser(sql, order_by, string_ranges, group_order, having, count_distinct, int_lists)
+                 count_distinct: bool = False, int_lists: bool = False, subqueries: bool = False) -> Q.Query:
+        p = SQLParser(sql, order_by, string_ranges, group_order, having, count_distinct, int_lists, subqueries)
         r = p._query(0)
         if r is not None:
             q, end = r
@@ -206,6 +213,17 @@ class SQLParser:
                 u = self._lit(p, ")")
                 if u is not None:
                     return Q.Select(c[0], Q.IntIn(ints)), u
+        if self.subqueries:                                    # ident "in" "(" "select" ident from where ")"
+            c = self._cmp(i, "in")
+            p = self._lit(c[1], "(") if c is not None else None
+            p = self._lit(p, "select") if p is not None else None
+            g = self._ident(p) if p is not None else None
+            f = self._from(g[1]) if g is not None else None
+            if f is not None:
+                w, e = self._where(f[1])
+                u = self._lit(e, ")")
+                if u is not None:
+                    return Q.Select(c[0], Q.IntInQuery(Q.Query(f[0], w, Q.Project([g[0]])))), u
         return None
 
     def _int(self, i):

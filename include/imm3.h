@@ -97,6 +97,23 @@ enum { IMM3_STR_RANGE = 6 };
  * negated lists and intervals with exclusions in the normal form.  The JNI / Scala binding does not carry the leaf. */
 enum { IMM3_INT_IN = 7 };
 #define IMM3_INT_IN_MAX_VALUES (1 << 24)
+/* EXTENSION (not a SelectCondition value): `id in (sub-query)`, the semi-join -- membership in a device-resident integer set built
+ * on the GPU from other queries' selections (imm3_int_set_create, below).  A leaf with this cond has n_match == 1 and match_bytes ==
+ * the imm3_int_set * itself (the handle, not bytes it points at); match_lens and `value` are ignored.  It selects the rows of an
+ * int32 or int8 column whose value is a member of the set; on an int8 column only the set's values in -128 .. 127 are members
+ * (IMM3_INT_IN's rule).  The query RETAINS the set: destroying the set while queries use it is legal.
+ * Errors (IMM3_ERR_ARG): n_match != 1, a null handle, a set of another context; a destroyed set: IMM3_ERR_STATE; a leaf on a STRING
+ * column: "Unsupported column vector" iff the segment has >= 1 batch.
+ * Every creator that takes `sels` or `leaves` accepts the leaf.  GT / LT / EQ leaves on the same column fold to their interval,
+ * intersected with the set's [min, max]; an empty intersection, like an empty set, selects nothing.  A column with a set leaf takes NO
+ * other IMM3_INT_IN / IMM3_INT_IN_SET leaf (IMM3_ERR_ARG, one fixed message, whatever the sizes: the intersection of two
+ * device-resident sets is not built).  The pass that probes it is IMM3_INT_IN's (k_filter_int_list and the word-at-a-time kernels read
+ * the set's table, 256-bit set or, up to 8 values, its host copy), so what holds for a list -- the bitmap path, no fused
+ * aggregation, `limit` bounding the gather, table launches, graph capture of the consumer's runs -- holds for the set.
+ * OUT OF SCOPE: a select-tree program that has an IMM3_EXPR_OR or an IMM3_EXPR_NOT and this leaf is refused at creation (IMM3_ERR_ARG, a
+ * fixed message of its own, not an IMM3_TABLE_TREE_REFUSED refusal): NOT IN (sub-query) and the leaf under OR.  Also out of scope:
+ * string or multi-column sets, sets shared across contexts or ranks, correlated sub-queries; the JNI / Scala binding does not carry it. */
+enum { IMM3_INT_IN_SET = 8 };
 
 /* status codes */
 enum {
@@ -115,6 +132,7 @@ typedef struct imm3_segment imm3_segment; /* one segment's columns resident in H
 typedef struct imm3_table imm3_table;     /* all resident segments of one table: scanned by ONE launch    */
 typedef struct imm3_query imm3_query;     /* one PipelineThread: ScanOp -> SelectOp* -> ProjectOp        */
 typedef struct imm3_graph imm3_graph;     /* a recorded sequence of query runs (hipGraph)                */
+typedef struct imm3_int_set imm3_int_set; /* a device-resident set of int32 values built from selections  */
 
 /* One column of one segment as the reference stores it: `<col>_<id>.dat` bytes + the
  * `blockOffset` array of `<col>_<id>.meta` (core/storage/Segment.scala:33-58, 154-181;
@@ -135,11 +153,11 @@ typedef struct {
  * below (the _expr entry points). */
 typedef struct {
     int32_t column;             /* index into the query's used-column list                           */
-    int32_t cond;               /* IMM3_GT / IMM3_LT / IMM3_EQ / IMM3_MATCH / IMM3_STR_RANGE / IMM3_INT_IN (others -> error) */
+    int32_t cond;               /* IMM3_GT / IMM3_LT / IMM3_EQ / IMM3_MATCH / IMM3_STR_RANGE / IMM3_INT_IN / IMM3_INT_IN_SET (others -> error) */
     double value;               /* GT/LT/EQ operand as the Query ADT carries it (core/Query.scala:6-8);
                                    narrowed per column type INSIDE the library: Int column d.toInt,
                                    TinyInt column d.toByte (Select.scala:65,73)                      */
-    const uint8_t *match_bytes; /* MATCH: the IN-list values, concatenated; STR_RANGE: lo, then hi     */
+    const uint8_t *match_bytes; /* MATCH: the IN-list values, concatenated; STR_RANGE: lo, then hi; INT_IN: the values; INT_IN_SET: the imm3_int_set * itself */
     const int32_t *match_lens;  /* MATCH: byte length of each value; STR_RANGE: of lo and of hi       */
     int32_t n_match;
 } imm3_select;
@@ -773,6 +791,36 @@ int imm3_comm_merge_ordered_all(imm3_comm *const *comms, int32_t n_comms, imm3_q
                                 const int32_t *const *segment_index, const int32_t *n_queries,
                                 int64_t limit, uint32_t *segment_out, uint32_t *row_out, void *const *col_out,
                                 uint64_t max_rows, uint64_t *n_rows);
+
+/* ---- integer sets built on the device from selections: IN (sub-query), the semi-join (csrc/imm3_intset.hip) ----
+ * imm3_int_set_create: the set of the DISTINCT values that column columns[i] (an index into that query's used-column list, as
+ * imm3_select.column is) takes among the rows sources[i] selects, united over the n_sources sources.  A source is any
+ * non-aggregation query of this context (flat, tree, segment or table); its column is int32 or int8 of any codec (PFOR_INT / snappy
+ * columns are read decoded, int8 values are sign-extended).  The set is the WHOLE selection's: a source's `limit`, order and SELECT
+ * list play no part.  Each source's bitmap is made current first the way imm3_query_bitmap does (a lazy bitmap, a limit scan that
+ * stopped early, a count-only last run or a query never run: its select chain runs).  That is a visible effect on the SOURCE: a source
+ * whose chain had to run is afterwards in the state imm3_query_run_select leaves -- imm3_query_count / _bitmap answer for the whole
+ * selection (a query never run now counts as run; rows a projection emitted before stay what they were), exactly as after the
+ * getters imm3_query_bitmap / imm3_query_count settle such a query.  No buffer of the source moves, so a graph that recorded the
+ * source's runs stays valid, and replaying it puts the recorded run's state back as always.  Sources are NOT retained and may be
+ * destroyed afterwards.  The call synchronises and reads back a small header (count, minimum, maximum, probe bound, overflow flag, the
+ * 256-bit set of the values in -128 .. 127); the values stay on the device, with two exceptions: a set of at most 8 values is
+ * also copied to the host (it is probed as a short list), and a set that holds BOTH INT32_MIN and INT32_MAX is rebuilt on the host
+ * (no sentinel just outside [min, max] is free).  Under an open stream capture it fails with IMM3_ERR_STATE, as every creation does
+ * (it allocates, launches and waits); capture the consumers' runs instead.
+ * Errors, IMM3_ERR_ARG with the cause in the message: n_sources < 1 or null arrays, a null source, a source of another context, an
+ * aggregation source, a column index out of range, more than IMM3_INT_IN_MAX_VALUES distinct values; a string column:
+ * IMM3_ERR_UNSUPPORTED_VECTOR ("Unsupported column vector").  "Too many distinct values" is found early: the insert pass keeps a
+ * running count and stops every walk once the cap is passed, so the refusal costs about what a build of IMM3_INT_IN_MAX_VALUES values
+ * costs, whatever the number of rows.
+ * imm3_int_set_destroy drops the caller's reference (queries created with the set keep it alive).
+ * imm3_int_set_info: the number of distinct values, their extremes (0, 0 when empty) and the form an int32 consumer probes it in
+ * (imm3_diag.h: imm3_plan_int_list_form).  imm3_int_set_values: the values, ascending, each once (a getter: copied from the device and
+ * sorted on the host); cap < n_values: IMM3_ERR_ARG. */
+int imm3_int_set_create(imm3_ctx *ctx, imm3_query *const *sources, const int32_t *columns, int32_t n_sources, imm3_int_set **out);
+int imm3_int_set_destroy(imm3_int_set *s);
+int imm3_int_set_info(const imm3_int_set *s, int64_t *n_values, int32_t *min, int32_t *max, int32_t *form);
+int imm3_int_set_values(imm3_int_set *s, int32_t *out, int64_t cap);
 
 /* ---- write side of the PFOR_INT codec (host code, no device involved) ----
  * PFORCodecInt.encode (core/codec/PFORCodec.scala:19-31), which SegmentWriter.flush applies to each block of a PFOR_INT

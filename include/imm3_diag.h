@@ -215,6 +215,18 @@ int imm3_plan_string_range_route(int32_t width);
 int imm3_plan_int_list_table(const int32_t *values, int64_t n, int32_t *slots_out, int64_t cap, int64_t *n_slots, int32_t *empty, int32_t *max_probe);
 int imm3_plan_int_list_form(int32_t width, int64_t n);
 int imm3_plan_int_list_probe(const int32_t *slots, int64_t n_slots, int32_t empty, int32_t max_probe, int32_t v);
+/* Integer sets built from selections (imm3_int_set_create; csrc/imm3_int_set_plan.cpp is pure, the rest needs a device).
+ * imm3_plan_int_set_scratch_slots: the slots of the scratch table a build inserts into, for `selected_rows` selected rows whose values
+ * span [min, max] under a cap of `cap` distinct values: imm3_plan_int_list_table's slot rule (a power of two, >= 16, >= 2 x) applied to
+ * min(selected_rows, max - min + 1, cap), 16 for no rows or min > max; -1: cap outside 0 .. IMM3_INT_IN_MAX_VALUES.
+ * imm3_int_set_create_capped: imm3_int_set_create with `max_values` (1 .. IMM3_INT_IN_MAX_VALUES) in the cap's place: more distinct
+ * values than that give the IMM3_ERR_ARG of "too many distinct values" at a size a test can afford.
+ * imm3_int_set_table: the set's probe table as it stands on the device -- *n_slots slots (0 for an empty set), what a free slot holds,
+ * the step bound of every probe, the 256-bit set of the values in -128 .. 127 (8 words), and whether the host built the table (the set
+ * holds INT32_MIN and INT32_MAX).  With cap == 0 only the figures are returned; else slots_out takes the slots (cap >= *n_slots). */
+int64_t imm3_plan_int_set_scratch_slots(int64_t selected_rows, int32_t min, int32_t max, int64_t cap);
+int imm3_int_set_create_capped(imm3_ctx *ctx, imm3_query *const *sources, const int32_t *columns, int32_t n_sources, int64_t max_values, imm3_int_set **out);
+int imm3_int_set_table(imm3_int_set *s, int32_t *slots_out, int64_t cap, int64_t *n_slots, int32_t *empty, int32_t *max_probe, uint32_t *set256, int32_t *host_route);
 /* The 16-bit high-half plane of a DENSE_INT column (csrc/imm3_hi16_plan.cpp, pure).  imm3_plan_hi16_bounds: the closed interval
  * [lo, hi] over the halves v >> 16 as two windows of 16-bit wrap-around arithmetic, out4 = {possible_first, possible_count,
  * certain_first, certain_count}: a half h is in a window when (uint16_t)(h - first) < count; outside the possible window a row fails,
