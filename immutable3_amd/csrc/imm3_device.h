@@ -41,6 +41,13 @@ __device__ __forceinline__ uint32_t lane_read(uint32_t v, int src_lane) {
     return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v);
 }
 
+// the sum of `x` over the wave's 64 lanes, in every lane
+__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) x += (uint32_t)__shfl_xor((int)x, d);
+    return x;
+}
+
 // Move 16 wave-uniform words into lanes 0..15 (lane j receives word j) with v_writelane.
 __device__ __forceinline__ uint64_t words_to_lanes(const uint64_t (&acc)[kTileWords]) {
     int lo = 0, hi = 0;

@@ -341,49 +341,48 @@ struct FilterArgs {
     const uint8_t *word_nvalid;
 };
 
-// ---- k_filter_str_rows (imm3_strmatch.hip): Match on one string column whose width is a whole number of dwords ----
-// One wave per 1024-row tile, lane l on row 64 j + l; the tile's 16 bitmap words leave as one 128-byte line.
-constexpr int kStrPrefixDwords = 4;  // dwords of a row compared first; the rest only for the rows that pass (widths above 16 bytes)
-struct StrRowsArgs {
+// ---- the one-column passes of the select chain: k_filter_str_rows, k_filter_str_range (imm3_strmatch.hip), k_filter_int_list
+// (imm3_intlist.hip).  One wave per 1024-row tile, lane l on row 64 j + l; the tile's 16 bitmap words leave as one 128-byte line.
+// What every such pass takes is the head below; what a kernel does with it is imm3_pass.h.
+// (The order is measured, not taste: with the three row counts in front of the pointers, k_filter_str_rows<2, 2, false, false>
+// -- whose eight values fill the scalar registers -- compiled to 20 bytes of scratch per lane, whatever code the kernel used.)
+struct ColumnPassArgs {
     const void *data;                // flat (decoded) column in HBM, 16-byte aligned
-    int32_t width;                   // bytes per row: a multiple of 4, 4 .. 256
-    int32_t n_match;                 // IN-list size
+    int32_t width;                   // bytes per row
     int32_t and_existing;            // 1: AND into the bitmap already in memory
-    int32_t pad;
-    uint32_t inl[kMaxMatch][2];      // values == null (width <= 8 and n_match <= kMaxMatch): the values' dwords, little-endian
-    const uint32_t *values;          // else: n_match * width bytes in device memory (FoldedPred::d_blob)
-    int64_t n_rows, n_words, n_tiles;
     uint64_t *bitmap;                // allocated in whole tiles
     uint32_t *block_partials;
     // table queries: tile t holds tile_rows[t] valid rows starting at tile_ptrs[t] (as TileArgs); null for one segment
     const uint32_t *tile_rows;
     const void *const *tile_ptrs;
+    int64_t n_rows, n_words, n_tiles;
+};
+
+// k_filter_str_rows: Match on one string column whose width is a whole number of dwords (pass.width: a multiple of 4, 4 .. 256)
+constexpr int kStrPrefixDwords = 4;  // dwords of a row compared first; the rest only for the rows that pass (widths above 16 bytes)
+struct StrRowsArgs {
+    ColumnPassArgs pass;
+    int32_t n_match;                 // IN-list size
+    int32_t pad;
+    uint32_t inl[kMaxMatch][2];      // values == null (width <= 8 and n_match <= kMaxMatch): the values' dwords, little-endian
+    const uint32_t *values;          // else: n_match * width bytes in device memory (FoldedPred::d_blob)
 };
 bool str_rows_width_ok(int32_t width);            // a multiple of 4 in 4 .. 256
 int str_rows_grid(int64_t n_tiles, int grid_blocks);
 bool launch_filter_str_rows(const StrRowsArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // false: no instance for this width
-// ---- k_filter_str_range (imm3_strmatch.hip): lo' <= row <= hi' in byte order on one such column; k_filter_str_rows' geometry and grid ----
+// k_filter_str_range: lo' <= row <= hi' in byte order on one such column; k_filter_str_rows' grid
 struct StrRangeArgs {
-    const void *data;                // flat (decoded) column in HBM, 16-byte aligned
-    int32_t width;                   // bytes per row: a multiple of 4, 4 .. 256
-    int32_t and_existing;            // 1: AND into the bitmap already in memory
+    ColumnPassArgs pass;
     uint32_t lo[kStrPrefixDwords];   // the first min(width, 16) bytes of lo' and hi', each dword's bytes swapped (its first byte most
     uint32_t hi[kStrPrefixDwords];   // significant): unsigned dword order is then byte order
     const uint32_t *tails;           // device memory: all width / 4 swapped dwords of lo', then of hi' (read for widths above 16 bytes only)
-    int64_t n_rows, n_words, n_tiles;
-    uint64_t *bitmap;                // allocated in whole tiles
-    uint32_t *block_partials;
-    const uint32_t *tile_rows;       // table queries, as StrRowsArgs
-    const void *const *tile_ptrs;
 };
 bool launch_filter_str_range(const StrRangeArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // false: no instance for this width
 
-// ---- k_filter_int_list (imm3_intlist.hip): IMM3_INT_IN on one int32 / int8 column; k_filter_str_rows' geometry, bitmap line and partials ----
+// k_filter_int_list: IMM3_INT_IN on one int32 / int8 column (pass.width: 4 or 1)
 struct IntListArgs {
-    const void *data;                // flat (decoded) column in HBM, 16-byte aligned
-    int32_t width;                   // 4 (int32) or 1 (int8)
+    ColumnPassArgs pass;
     int32_t form;                    // IntListForm (imm3_int_list_plan.h): selects the instance
-    int32_t and_existing;            // 1: AND into the bitmap already in memory
     int32_t n_values;                // INT_LIST_ARGS: values in inl[]
     int32_t lo, hi;                  // the folded interval: the list's minimum and maximum
     union {
@@ -393,11 +392,6 @@ struct IntListArgs {
     const int32_t *table;            // INT_LIST_LDS / INT_LIST_GLOBAL: the probe table in device memory, mask + 1 slots
     uint32_t mask, shift, max_probe; // slots - 1 (INT_LIST_LDS: < kIntListLdsSlots), 32 - log2(slots), the step bound of every probe
     int32_t empty;                   // what an empty slot holds (never a member)
-    int64_t n_rows, n_words, n_tiles;
-    uint64_t *bitmap;                // allocated in whole tiles
-    uint32_t *block_partials;
-    const uint32_t *tile_rows;       // table queries, as StrRowsArgs
-    const void *const *tile_ptrs;
 };
 int int_list_grid(int64_t n_tiles, int grid_blocks, int32_t width);
 bool launch_filter_int_list(const IntListArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1); // false: arguments no instance takes
@@ -737,6 +731,12 @@ constexpr int kFinishWords = 16 + kSubTallies * 16;   // u64 words of a query's 
 constexpr int kFinishLimitTicket = 16 + 16 * (kSubTallies - 1) + kFinishLimitTicketLineWord; // finish[520]: claims handed out so far in this launch (zero between runs)
 static_assert(kFinishLimitTicket < kFinishWords && kFinishLimitTicketLineWord > 0 && kFinishLimitTicketLineWord < 16, "the ticket word lies inside the finish block, beside the last sub-tally");
 constexpr int kMaxFilterGrid = 4096; // capacity of block_partials
+// what every launch_filter_* of a one-column pass asks of the head: a bitmap, a grid block_partials can hold, and a column -- flat
+// data, or a complete tile table
+inline bool column_pass_ok(const ColumnPassArgs &p, int grid) {
+    if (!p.bitmap || grid < 1 || grid > kMaxFilterGrid) return false;
+    return p.tile_rows ? p.tile_ptrs != nullptr : p.data != nullptr;
+}
 int filter_grid(int64_t units, bool generic, bool any_i32, int grid_blocks, int narrow_row_bytes = 0, bool lone_plane = false); // narrow_row_bytes: bytes per row of a launch without an int32 column; lone_plane: it is the lone TK_H16 column
 // ev0/ev1: optional events stamped with the kernel's own start/end (hipExtLaunchKernelGGL), else null
 // ---- PFOR_INT blocks (imm3_codec.hip) ----
@@ -1008,5 +1008,13 @@ void launch_merge_view_apply(const MergeViewArgs &a, hipStream_t s, hipEvent_t e
         else hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s, __VA_ARGS__);                             \
     } while (0)
 #define IMM3_LAUNCH(kern, grid, block, s, ev0, ev1, ...) IMM3_LAUNCH_LDS(kern, grid, block, 0, s, ev0, ev1, __VA_ARGS__)
+// A one-column pass (ColumnPassArgs): launches kern<..., TABLE> on the launcher's (a, grid, s, ev0, ev1) -- the table instance when
+// the pass has a tile table -- and returns true.  The variadic arguments are the kernel's template arguments in front of TABLE.
+#define IMM3_COLUMN_PASS_LAUNCH(kern, ...)                                                                          \
+    do {                                                                                                            \
+        if (a.pass.tile_rows) IMM3_LAUNCH((kern<__VA_ARGS__, true>), grid, kBlockThreads, s, ev0, ev1, a);          \
+        else IMM3_LAUNCH((kern<__VA_ARGS__, false>), grid, kBlockThreads, s, ev0, ev1, a);                          \
+        return true;                                                                                                \
+    } while (0)
 #endif
 

@@ -1,12 +1,9 @@
 // imm3_intlist.hip -- k_filter_int_list: IMM3_INT_IN, "the row's value is a member of the list", over one DENSE_INT / DENSE_TINYINT
-// column (or its decoded form), for gfx950 (wave64).  A pass of the select chain with k_filter_str_rows' contract.
-//
-// k_filter_tile's geometry: one wave per 1024-row tile, grid-stride; lane l holds row 64 j + l of the tile in register set j, so the
-// ballot over "row is a member" IS bitmap word j, and the tile's 16 words leave as one 128-byte non-temporal line (lanes 0..15).
+// column (or its decoded form), for gfx950 (wave64).  A one-column pass of the select chain: geometry, tile addressing, the
+// partial-tile rule, the bitmap line and the count are imm3_pass.h's; what is here is the loads and the test.
 //
 // Loads.  All 16 loads of a tile (one dword or one byte per lane and row block) are issued before the first test, non-temporal: the
-// column is read once.  A partial last tile (the end of a segment) loads under the row's validity: nothing at or beyond the tile's
-// valid count is read.
+// column is read once.
 //
 // Test.  Every form first holds the value against the folded interval [lo, hi] = [the list's minimum, its maximum]; what is left to
 // do is wave-uniform over "any candidate left", so a tile of a sorted key outside the list's span costs a plain scan.  The forms
@@ -20,10 +17,8 @@
 // The probe: step 0 of all 16 row blocks at once (16 independent reads in flight), then a rolled loop over the steps 1 ..
 // max_probe - 1 for the rows that met another value, wave-uniform over "any row still undecided".  No loop depends on meeting an
 // empty slot, and every slot index is masked: a corrupted table can give a wrong answer, never a hang or a read outside the table.
-//
-// Count: per-work-group partials (block_partial_store), summed by k_total, like the string pass's.
 #include "imm3_internal.h"
-#include "imm3_device.h"
+#include "imm3_pass.h"
 #include <hip/hip_ext.h>
 
 namespace imm3 {
@@ -31,10 +26,8 @@ namespace imm3 {
 template <int FORM, bool TABLE>
 __global__ __launch_bounds__(kBlockThreads) void k_filter_int_list(const IntListArgs a) {
     constexpr bool I8 = FORM == INT_LIST_I8;
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int64_t wave_id = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
+    const PassWave w = pass_wave();
+    const int lane = w.lane;
     const int32_t lo = a.lo, hi = a.hi;
     const uint32_t mask = FORM == INT_LIST_LDS ? (a.mask & (kIntListLdsSlots - 1)) : a.mask; // (the LDS copy is never indexed outside itself)
     const int32_t *tab = nullptr;
@@ -52,20 +45,11 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_int_list(const IntList
         tab = a.table;
     }
     uint32_t lane_total = 0; // lanes 0..15: survivors in the words they stored
-    for (int64_t tile = wave_id; tile < a.n_tiles; tile += n_waves) {
-        const uint8_t *base;
-        uint32_t rows_here;
-        if constexpr (TABLE) {
-            rows_here = a.tile_rows[tile];
-            base = (const uint8_t *)as_global(a.tile_ptrs[tile]); // (as_global: no flat loads through a pointer read from memory)
-        } else {
-            const int64_t left = a.n_rows - tile * kTileRows;
-            rows_here = left >= kTileRows ? (uint32_t)kTileRows : (uint32_t)left;
-            base = (const uint8_t *)a.data + (size_t)tile * kTileRows * (I8 ? 1 : 4);
-        }
-        const int64_t w = tile * kTileWords + lane; // lane j < 16 owns bitmap word j of the tile
-        uint64_t mine = ~0ULL;
-        if (a.and_existing) mine = lane < kTileWords ? a.bitmap[w] : 0ULL;
+    for (int64_t tile = w.first; tile < a.pass.n_tiles; tile += w.step) {
+        const PassTile t = pass_tile<TABLE>(a.pass, tile, I8 ? 1 : 4);
+        const uint8_t *base = t.base;
+        const uint32_t rows_here = t.rows_here;
+        const uint64_t mine = pass_line_begin(a.pass, tile, lane);
         int32_t v[kTileWords];
         uint32_t valid = 0xFFFFu; // bit j: row 64 j + lane exists
         if (rows_here == (uint32_t)kTileRows) { // wave-uniform
@@ -146,14 +130,9 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_int_list(const IntList
 #pragma unroll
             for (int j = 0; j < kTileWords; ++j) acc[j] = ballot64((found >> j) & 1u);
         }
-        mine &= words_to_lanes(acc);
-        if (lane >= kTileWords) mine = 0;
-        if (lane < kTileWords) __builtin_nontemporal_store(mine, a.bitmap + w); // 16 lanes x 8 B = one 128-B line (the bitmap is allocated in whole tiles)
-        lane_total += (uint32_t)__popcll(mine);
+        lane_total += pass_line_end(a.pass, tile, lane, rows_here, mine, acc);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) lane_total += __shfl_xor(lane_total, d);
-    block_partial_store(a.block_partials, lane_total, lane, wave);
+    pass_count_end(a.pass, lane_total, w);
 }
 
 // An int8 column: k_filter_tile's 6 work-groups per CU (filter_grid; a tile is 1 KiB).  An int32 column: 4 per CU -- a wave has ONE tile,
@@ -166,35 +145,28 @@ int int_list_grid(int64_t n_tiles, int grid_blocks, int32_t width) {
     return (int)std::max<int64_t>(1, std::min<int64_t>((n_tiles + kWavesPerBlock - 1) / kWavesPerBlock, 1024));
 }
 
-#define IMM3_INT_LIST_LAUNCH(FORM)                                                                              \
-    do {                                                                                                        \
-        if (a.tile_rows) IMM3_LAUNCH((k_filter_int_list<FORM, true>), grid, kBlockThreads, s, ev0, ev1, a);     \
-        else IMM3_LAUNCH((k_filter_int_list<FORM, false>), grid, kBlockThreads, s, ev0, ev1, a);                \
-        return true;                                                                                            \
-    } while (0)
-
 // false: arguments no instance takes -- the form does not fit the width, the values or the table are not where the form reads them,
 // or the table is not a power of two of slots the form can index
 bool launch_filter_int_list(const IntListArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    if (!a.bitmap || grid < 1 || grid > kMaxFilterGrid || (!a.tile_rows && !a.data) || (a.tile_rows && !a.tile_ptrs)) return false;
+    if (!column_pass_ok(a.pass, grid)) return false;
     if (a.form == INT_LIST_I8) {
-        if (a.width != 1) return false;
-        IMM3_INT_LIST_LAUNCH(INT_LIST_I8);
+        if (a.pass.width != 1) return false;
+        IMM3_COLUMN_PASS_LAUNCH(k_filter_int_list, INT_LIST_I8);
     }
-    if (a.width != 4) return false;
+    if (a.pass.width != 4) return false;
     if (a.form == INT_LIST_ARGS) {
         if (a.n_values < 1 || a.n_values > kMaxMatch) return false;
         for (int m = a.n_values; m < kMaxMatch; ++m)
             if (a.inl[m] != a.inl[0]) return false; // (the kernel compares all kMaxMatch: the unused ones repeat the first)
-        IMM3_INT_LIST_LAUNCH(INT_LIST_ARGS);
+        IMM3_COLUMN_PASS_LAUNCH(k_filter_int_list, INT_LIST_ARGS);
     }
     const uint64_t slots = (uint64_t)a.mask + 1;
     if (!a.table || slots < kIntListMinSlots || (slots & a.mask) != 0 || slots > (1ull << 25) || a.shift >= 32 || (32 - a.shift) != (uint32_t)__builtin_ctzll(slots)) return false;
     if (a.form == INT_LIST_LDS) {
         if (slots > kIntListLdsSlots) return false;
-        IMM3_INT_LIST_LAUNCH(INT_LIST_LDS);
+        IMM3_COLUMN_PASS_LAUNCH(k_filter_int_list, INT_LIST_LDS);
     }
-    if (a.form == INT_LIST_GLOBAL) IMM3_INT_LIST_LAUNCH(INT_LIST_GLOBAL);
+    if (a.form == INT_LIST_GLOBAL) IMM3_COLUMN_PASS_LAUNCH(k_filter_int_list, INT_LIST_GLOBAL);
     return false;
 }
 

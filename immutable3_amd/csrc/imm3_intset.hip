@@ -35,11 +35,6 @@ namespace imm3 {
 
 namespace {
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x += (uint32_t)__shfl_xor((int)x, d);
-    return x;
-}
 __device__ __forceinline__ uint32_t wave_max(uint32_t x) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {

@@ -1,5 +1,6 @@
 // imm3_run.cpp -- the run calls of include/imm3.h (imm3_query_run, _run_select, _run_count, _join_count, _sync) and every launch
-// they enqueue: the select run as one launcher per pass kind (run_select), the one-launch projection (run_single_pass), the
+// they enqueue: the select run as one launcher per pass kind (run_select; the one-column passes -- string match, string range, integer
+// list -- share fill_column_pass and launch_column_pass), the one-launch projection (run_single_pass), the
 // projection behind a select (run_project: offsets scan, gather / records / the fused limit gather), and the graph-capture
 // bookkeeping around a run.  Query creation, the getters (which settle what a run left undone through run_select, launch_project
 // and join_total: imm3_api_internal.h) and aggregation (run_agg shares its argument filling with the group getters) are
@@ -428,66 +429,62 @@ static int launch_pfor_pass(imm3_query *q, SelectRun &run, const FoldedPred &fp)
     return IMM3_OK;
 }
 
-// The string pass of a range (k_filter_str_range): the geometry, grid and tile table of k_filter_str_rows
+// ---- the one-column passes (ColumnPassArgs, imm3_internal.h): one predicate's column per launch, a segment or a table's tile table.
+// Each launcher below fills only what is its kernel's own and names its grid.
+// the pass's head: the column of `fp`, flat and through the table's tile table, and the pass tail
+static void fill_column_pass(const imm3_query *q, const SelectRun &run, const FoldedPred &fp, ColumnPassArgs &p) {
+    p.data = col_flat(q->seg->cols[(size_t)fp.seg_col]);
+    p.width = fp.width;
+    fill_pass_tail(q, run, p);
+    if (q->table) {
+        p.tile_rows = q->table->d_tile_rows;
+        p.tile_ptrs = (const void *const *)q->table->d_tile_ptrs[(size_t)fp.seg_col];
+    }
+}
+
+// the pass's launch, `grid` work-groups under the select launch's timer; `refused`: what to say when the launcher takes no such arguments
+template <class Args>
+static int launch_column_pass(imm3_query *q, SelectRun &run, const Args &a, int grid, bool (*launch)(const Args &, int, hipStream_t, hipEvent_t, hipEvent_t), const char *refused) {
+    run.grid = grid;
+    {
+        LaunchTimer t(q->ctx, 0);
+        if (!launch(a, run.grid, run.s, t.start, t.stop)) return fail(IMM3_ERR_ARG, refused);
+    }
+    HIPCHK(hipGetLastError());
+    ++run.pass;
+    return IMM3_OK;
+}
+
+// The string pass of a range (k_filter_str_range)
 static int launch_str_range_pass(imm3_query *q, SelectRun &run, const FoldedPred &fp) {
-    imm3_ctx *ctx = q->ctx;
     StrRangeArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.data = col_flat(q->seg->cols[(size_t)fp.seg_col]);
-    a.width = fp.width;
+    fill_column_pass(q, run, fp, a.pass);
     std::memcpy(a.lo, fp.range_lo4, sizeof(a.lo));
     std::memcpy(a.hi, fp.range_hi4, sizeof(a.hi));
     if (!fp.d_blob) return fail(IMM3_ERR_ARG, "internal: a string range without its bounds on the device");
     a.tails = (const uint32_t *)(fp.d_blob + 2 * (size_t)fp.width); // (behind the byte-for-byte bounds: str_range_pack)
-    fill_pass_tail(q, run, a);
-    if (q->table) {
-        a.tile_rows = q->table->d_tile_rows;
-        a.tile_ptrs = (const void *const *)q->table->d_tile_ptrs[(size_t)fp.seg_col];
-    }
-    run.grid = str_rows_grid(q->n_tiles, ctx->grid_blocks);
-    {
-        LaunchTimer t(ctx, 0);
-        if (!launch_filter_str_range(a, run.grid, run.s, t.start, t.stop)) return fail(IMM3_ERR_ARG, "internal: no string range kernel for this column width");
-    }
-    HIPCHK(hipGetLastError());
-    ++run.pass;
-    return IMM3_OK;
+    return launch_column_pass(q, run, a, str_rows_grid(q->n_tiles, q->ctx->grid_blocks), launch_filter_str_range, "internal: no string range kernel for this column width");
 }
 
-// A string pass (k_filter_str_rows): one column whose width is a multiple of 4 per launch, a segment or a table's tile table
+// A string pass (k_filter_str_rows): a column whose width is a multiple of 4
 static int launch_str_rows_pass(imm3_query *q, SelectRun &run, const FoldedPred &fp) {
     if (fp.has_range) return launch_str_range_pass(q, run, fp);
-    imm3_ctx *ctx = q->ctx;
     StrRowsArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.data = col_flat(q->seg->cols[(size_t)fp.seg_col]);
-    a.width = fp.width;
+    fill_column_pass(q, run, fp, a.pass);
     a.n_match = (int32_t)fp.match.size();
     a.values = (const uint32_t *)fp.d_blob;
     if (!a.values) // (upload_match_blobs: width <= 8 and <= kMaxMatch values)
         for (size_t m = 0; m < fp.match.size() && m < (size_t)kMaxMatch; ++m) std::memcpy(a.inl[m], fp.match[m].data(), std::min<size_t>((size_t)fp.width, sizeof(a.inl[m])));
-    fill_pass_tail(q, run, a);
-    if (q->table) {
-        a.tile_rows = q->table->d_tile_rows;
-        a.tile_ptrs = (const void *const *)q->table->d_tile_ptrs[(size_t)fp.seg_col];
-    }
-    run.grid = str_rows_grid(q->n_tiles, ctx->grid_blocks);
-    {
-        LaunchTimer t(ctx, 0);
-        if (!launch_filter_str_rows(a, run.grid, run.s, t.start, t.stop)) return fail(IMM3_ERR_ARG, "internal: no string kernel for this column width");
-    }
-    HIPCHK(hipGetLastError());
-    ++run.pass;
-    return IMM3_OK;
+    return launch_column_pass(q, run, a, str_rows_grid(q->n_tiles, q->ctx->grid_blocks), launch_filter_str_rows, "internal: no string kernel for this column width");
 }
 
-// A list pass (k_filter_int_list): one int32 / int8 column with a folded IMM3_INT_IN list per launch, a segment or a table's tile table
+// A list pass (k_filter_int_list): an int32 / int8 column with a folded IMM3_INT_IN list
 static int launch_int_list_pass(imm3_query *q, SelectRun &run, const FoldedPred &fp) {
-    imm3_ctx *ctx = q->ctx;
     IntListArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.data = col_flat(q->seg->cols[(size_t)fp.seg_col]);
-    a.width = fp.width;
+    fill_column_pass(q, run, fp, a.pass);
     a.form = int_list_form(fp.width, pred_list_count(fp));
     a.lo = (int32_t)fp.lo;
     a.hi = (int32_t)fp.hi;
@@ -503,19 +500,7 @@ static int launch_int_list_pass(imm3_query *q, SelectRun &run, const FoldedPred 
         a.max_probe = fp.list_max_probe;
         a.empty = fp.list_empty;
     }
-    fill_pass_tail(q, run, a);
-    if (q->table) {
-        a.tile_rows = q->table->d_tile_rows;
-        a.tile_ptrs = (const void *const *)q->table->d_tile_ptrs[(size_t)fp.seg_col];
-    }
-    run.grid = int_list_grid(q->n_tiles, ctx->grid_blocks, fp.width);
-    {
-        LaunchTimer t(ctx, 0);
-        if (!launch_filter_int_list(a, run.grid, run.s, t.start, t.stop)) return fail(IMM3_ERR_ARG, "internal: no integer list kernel for these arguments");
-    }
-    HIPCHK(hipGetLastError());
-    ++run.pass;
-    return IMM3_OK;
+    return launch_column_pass(q, run, a, int_list_grid(q->n_tiles, q->ctx->grid_blocks, fp.width), launch_filter_int_list, "internal: no integer list kernel for these arguments");
 }
 
 // A word-at-a-time pass (k_filter_generic) over up to kMaxPredCols of the chain's generic predicates from `first` on (none at all:

@@ -2,25 +2,24 @@
 // whose width is a whole number of dwords (4 .. 256 bytes), for gfx950 (wave64); and k_filter_str_range, its sibling for a
 // byte-order range on such a column (IMM3_STR_RANGE; described at the kernel, below).
 //
-// k_filter_tile's geometry: one wave per 1024-row tile, grid-stride; lane l holds row 64 j + l of the tile in register set j, so the
-// ballot over "row matches" IS bitmap word j, and the tile's 16 words leave as one 128-byte line (lanes 0..15, 8 bytes each).
+// Both are one-column passes of the select chain: geometry, tile addressing, the partial-tile rule, the bitmap line and the count are
+// imm3_pass.h's; what is here is the loads and the two tests.
 //
-// Loads.  A tile starts at a multiple of 1024 * width bytes from a 16-byte-aligned base and width is a multiple of 4, so every row is
-// dword-aligned: a lane reads the first P = min(width / 4, 4) dwords of each of its 16 rows with dword / dwordx2 / dwordx4 loads
-// (as wide as width's alignment allows), all 16 issued before the first compare -- up to 16 KiB in flight per wave.
+// Loads.  A tile starts at a multiple of 1024 * width bytes from a 16-byte-aligned base and width is a multiple of 4, so every row
+// is dword-aligned: a lane reads the first P = min(width / 4, 4) dwords of each of its 16 rows with dword / dwordx2 / dwordx4
+// loads (as wide as width's alignment allows), all 16 issued before the first compare -- up to 16 KiB in flight per wave.
+// Two pieces are NOT shared, on measurements (profiles/column_pass.txt).  Each kernel carries the load block itself, and
+// k_filter_str_range clears a partial tile's padding bits in that block's partial branch and ends its line with pass_line_store:
+// with the loads as one function of both kernels, or with the rule left to pass_line_end, the compiler drops the range kernel's
+// counted waits (s_waitcnt vmcnt(15) .. vmcnt(0)) behind a full tile's loads, and every compare waits for all 16 (S4: 70 -> 90 us).
 //
 // Compare.  The IN-list is walked ONCE PER TILE, not once per row: for value m (its dwords wave-uniform -- kernel arguments when the
 // list fits them, else the device blob the fold step uploaded, read with scalar loads) every lane compares its 16 prefixes and
 // collects a 16-bit candidate mask, bit j = row 64 j + l.  Up to 16 bytes the prefix is the whole row.  Wider rows: the candidates'
 // remaining dwords are compared in a rolled loop that is wave-uniform over "any candidate left" -- per row block j with a candidate,
 // chunk after chunk until the value ends or no lane of the wave is still a candidate.  A selective IN-list never enters it.
-//
-// Bounds.  A partial last tile (the end of a segment) loads under the row's validity: no byte of a row at or beyond the tile's valid
-// count is read, so the kernel needs no readable slack behind the column however wide its rows are.
-//
-// Count: per-work-group partials (block_partial_store), summed by k_total, like the word-at-a-time kernel's.
 #include "imm3_internal.h"
-#include "imm3_device.h"
+#include "imm3_pass.h"
 #include <hip/hip_ext.h>
 
 namespace imm3 {
@@ -54,30 +53,18 @@ __device__ __forceinline__ void load_dwords(uint32_t (&v)[N], const uint8_t *p) 
 template <int P, int C, bool TAIL, bool TABLE>
 __global__ __launch_bounds__(kBlockThreads) void k_filter_str_rows(const StrRowsArgs a) {
     static_assert(P % C == 0 && P <= kStrPrefixDwords, "the prefix is whole chunks");
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int64_t wave_id = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
-    const uint32_t W = (uint32_t)a.width;   // bytes per row
-    const int D = a.width >> 2;             // dwords per row
-    uint32_t lane_total = 0;                // lanes 0..15: survivors in the words they stored
-    for (int64_t tile = wave_id; tile < a.n_tiles; tile += n_waves) {
-        const uint8_t *base;
-        uint32_t rows_here;
-        if constexpr (TABLE) {
-            rows_here = a.tile_rows[tile];
-            base = (const uint8_t *)as_global(a.tile_ptrs[tile]); // (as_global: no flat loads through a pointer read from memory)
-        } else {
-            const int64_t left = a.n_rows - tile * kTileRows;
-            rows_here = left >= kTileRows ? (uint32_t)kTileRows : (uint32_t)left;
-            base = (const uint8_t *)a.data + (size_t)tile * kTileRows * W;
-        }
-        const int64_t w = tile * kTileWords + lane; // lane j < 16 owns bitmap word j of the tile
-        uint64_t mine = ~0ULL;
-        if (a.and_existing) mine = lane < kTileWords ? a.bitmap[w] : 0ULL;
+    const PassWave w = pass_wave();
+    const int lane = w.lane;
+    const uint32_t W = (uint32_t)a.pass.width; // bytes per row
+    const int D = a.pass.width >> 2;           // dwords per row
+    uint32_t lane_total = 0;                   // lanes 0..15: survivors in the words they stored
+    for (int64_t tile = w.first; tile < a.pass.n_tiles; tile += w.step) {
+        const PassTile t = pass_tile<TABLE>(a.pass, tile, W);
+        const uint8_t *base = t.base;
+        const uint64_t mine = pass_line_begin(a.pass, tile, lane);
         uint32_t pre[kTileWords][P];
         uint32_t valid = 0xFFFFu; // bit j: row 64 j + lane exists
-        if (rows_here == (uint32_t)kTileRows) { // wave-uniform
+        if (t.rows_here == (uint32_t)kTileRows) { // wave-uniform
 #pragma unroll
             for (int j = 0; j < kTileWords; ++j) load_dwords<P, C>(pre[j], base + (uint32_t)(64 * j + lane) * W);
         } else { // the end of a segment: nothing at or beyond the valid count is read
@@ -86,7 +73,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_str_rows(const StrRows
             for (int j = 0; j < kTileWords; ++j) {
 #pragma unroll
                 for (int d = 0; d < P; ++d) pre[j][d] = 0;
-                if ((uint32_t)(64 * j + lane) < rows_here) {
+                if ((uint32_t)(64 * j + lane) < t.rows_here) {
                     load_dwords<P, C>(pre[j], base + (uint32_t)(64 * j + lane) * W);
                     valid |= 1u << j;
                 }
@@ -137,19 +124,14 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_str_rows(const StrRows
         uint64_t acc[kTileWords]; // wave-uniform words
 #pragma unroll
         for (int j = 0; j < kTileWords; ++j) acc[j] = ballot64((found >> j) & 1u);
-        mine &= words_to_lanes(acc);
-        if (lane >= kTileWords) mine = 0;
-        if (lane < kTileWords) __builtin_nontemporal_store(mine, a.bitmap + w); // 16 lanes x 8 B = one 128-B line (the bitmap is allocated in whole tiles)
-        lane_total += (uint32_t)__popcll(mine);
+        lane_total += pass_line_end(a.pass, tile, lane, t.rows_here, mine, acc);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) lane_total += __shfl_xor(lane_total, d);
-    block_partial_store(a.block_partials, lane_total, lane, wave);
+    pass_count_end(a.pass, lane_total, w);
 }
 
 // ---- k_filter_str_range: IMM3_STR_RANGE, lo' <= row <= hi' in unsigned byte order, on the same columns --------------------------
-// k_filter_str_rows' geometry, loads, partial-tile rule, bitmap line and partials; the compare is an ORDER test where Match's is an
-// equality test.  Byte order is unsigned dword order once a dword's bytes are swapped (one v_perm_b32 per dword); the host hands the
+// k_filter_str_rows' loads; the compare is an ORDER test where Match's is an equality test.  Byte order is unsigned dword order
+// once a dword's bytes are swapped (one v_perm_b32 per dword); the host hands the
 // bounds already swapped (str_range_pack), wave-uniform: the first 16 bytes as kernel arguments, the tails of wider rows in device
 // memory.  Against each bound a row's prefix is below, tied or above -- the first dword that differs decides, which is what the
 // chain below computes from the last prefix dword to the first (the lane masks it combines are scalar registers: the vector unit
@@ -161,33 +143,21 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_str_rows(const StrRows
 template <int P, int C, bool TAIL, bool TABLE>
 __global__ __launch_bounds__(kBlockThreads) void k_filter_str_range(const StrRangeArgs a) {
     static_assert(P % C == 0 && P <= kStrPrefixDwords, "the prefix is whole chunks");
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int64_t wave_id = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-    const int64_t n_waves = (int64_t)gridDim.x * kWavesPerBlock;
-    const uint32_t W = (uint32_t)a.width;   // bytes per row
-    const int D = a.width >> 2;             // dwords per row
+    const PassWave w = pass_wave();
+    const int lane = w.lane;
+    const uint32_t W = (uint32_t)a.pass.width; // bytes per row
+    const int D = a.pass.width >> 2;           // dwords per row
     uint32_t lo[P], hi[P];
 #pragma unroll
     for (int d = 0; d < P; ++d) { lo[d] = a.lo[d]; hi[d] = a.hi[d]; }
-    uint32_t lane_total = 0;                // lanes 0..15: survivors in the words they stored
-    for (int64_t tile = wave_id; tile < a.n_tiles; tile += n_waves) {
-        const uint8_t *base;
-        uint32_t rows_here;
-        if constexpr (TABLE) {
-            rows_here = a.tile_rows[tile];
-            base = (const uint8_t *)as_global(a.tile_ptrs[tile]);
-        } else {
-            const int64_t left = a.n_rows - tile * kTileRows;
-            rows_here = left >= kTileRows ? (uint32_t)kTileRows : (uint32_t)left;
-            base = (const uint8_t *)a.data + (size_t)tile * kTileRows * W;
-        }
-        const int64_t w = tile * kTileWords + lane; // lane j < 16 owns bitmap word j of the tile
-        uint64_t mine = ~0ULL;
-        if (a.and_existing) mine = lane < kTileWords ? a.bitmap[w] : 0ULL;
+    uint32_t lane_total = 0;                   // lanes 0..15: survivors in the words they stored
+    for (int64_t tile = w.first; tile < a.pass.n_tiles; tile += w.step) {
+        const PassTile t = pass_tile<TABLE>(a.pass, tile, W);
+        const uint8_t *base = t.base;
+        uint64_t mine = pass_line_begin(a.pass, tile, lane);
         uint32_t pre[kTileWords][P];
         uint32_t valid = 0xFFFFu; // bit j: row 64 j + lane exists
-        if (rows_here == (uint32_t)kTileRows) { // wave-uniform
+        if (t.rows_here == (uint32_t)kTileRows) { // wave-uniform
 #pragma unroll
             for (int j = 0; j < kTileWords; ++j) load_dwords<P, C>(pre[j], base + (uint32_t)(64 * j + lane) * W);
         } else { // the end of a segment: nothing at or beyond the valid count is read
@@ -196,13 +166,14 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_str_range(const StrRan
             for (int j = 0; j < kTileWords; ++j) {
 #pragma unroll
                 for (int d = 0; d < P; ++d) pre[j][d] = 0;
-                if ((uint32_t)(64 * j + lane) < rows_here) {
+                if ((uint32_t)(64 * j + lane) < t.rows_here) {
                     load_dwords<P, C>(pre[j], base + (uint32_t)(64 * j + lane) * W);
                     valid |= 1u << j;
                 }
             }
-            // (a row that does not exist compares as zeros, which a range may hold: its bit goes with the word's valid mask)
-            mine &= low_mask((int64_t)rows_here - 64 * (int64_t)lane);
+            // This kernel's own partial-tile rule, where the parent had it (a row that does not exist compares as zeros, which a
+            // range may hold), and pass_line_store below instead of pass_line_end: see the file-head comment
+            mine &= low_mask((int64_t)t.rows_here - 64 * (int64_t)lane);
         }
         uint64_t acc[kTileWords]; // wave-uniform words
         uint32_t in = 0, tie_lo = 0, tie_hi = 0; // TAIL: bit j = row 64 j + lane is in by its prefix / tied with lo's / with hi's
@@ -259,14 +230,9 @@ __global__ __launch_bounds__(kBlockThreads) void k_filter_str_range(const StrRan
 #pragma unroll
             for (int j = 0; j < kTileWords; ++j) acc[j] = ballot64((in >> j) & 1u);
         }
-        mine &= words_to_lanes(acc);
-        if (lane >= kTileWords) mine = 0;
-        if (lane < kTileWords) __builtin_nontemporal_store(mine, a.bitmap + w); // one 128-B line, as k_filter_str_rows
-        lane_total += (uint32_t)__popcll(mine);
+        lane_total += pass_line_store(a.pass, tile, lane, mine, acc);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) lane_total += __shfl_xor(lane_total, d);
-    block_partial_store(a.block_partials, lane_total, lane, wave);
+    pass_count_end(a.pass, lane_total, w);
 }
 
 bool str_rows_width_ok(int32_t width) { return width >= 4 && width <= kStrMaxWidth && width % 4 == 0; }
@@ -278,44 +244,31 @@ int str_rows_grid(int64_t n_tiles, int grid_blocks) {
     return (int)std::max<int64_t>(1, std::min<int64_t>((n_tiles + kWavesPerBlock - 1) / kWavesPerBlock, cap));
 }
 
-#define IMM3_STR_LAUNCH(P, C, TAIL)                                                                                \
-    do {                                                                                                           \
-        if (a.tile_rows) IMM3_LAUNCH((k_filter_str_rows<P, C, TAIL, true>), grid, kBlockThreads, s, ev0, ev1, a);  \
-        else IMM3_LAUNCH((k_filter_str_rows<P, C, TAIL, false>), grid, kBlockThreads, s, ev0, ev1, a);             \
-        return true;                                                                                               \
+// the seven <P, C, TAIL> instances of either kernel, by width (a multiple of 4); launches one and returns true
+#define IMM3_STR_LAUNCH_BY_WIDTH(kern)                                               \
+    do {                                                                             \
+        const int32_t width = a.pass.width;                                          \
+        if (width == 4) IMM3_COLUMN_PASS_LAUNCH(kern, 1, 1, false);                  \
+        if (width == 8) IMM3_COLUMN_PASS_LAUNCH(kern, 2, 2, false);                  \
+        if (width == 12) IMM3_COLUMN_PASS_LAUNCH(kern, 3, 1, false);                 \
+        if (width == 16) IMM3_COLUMN_PASS_LAUNCH(kern, 4, 4, false);                 \
+        if (width % 16 == 0) IMM3_COLUMN_PASS_LAUNCH(kern, 4, 4, true);              \
+        if (width % 8 == 0) IMM3_COLUMN_PASS_LAUNCH(kern, 4, 2, true);               \
+        IMM3_COLUMN_PASS_LAUNCH(kern, 4, 1, true);                                   \
     } while (0)
 
 // false: no instance for this width, or the IN-list's values are not where the instance reads them
 bool launch_filter_str_rows(const StrRowsArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    if (!str_rows_width_ok(a.width) || !a.bitmap || grid < 1 || grid > kMaxFilterGrid || a.n_match < 0) return false;
-    if (!a.values && (a.width > 8 || a.n_match > kMaxMatch)) return false;
-    if (a.width == 4) IMM3_STR_LAUNCH(1, 1, false);
-    if (a.width == 8) IMM3_STR_LAUNCH(2, 2, false);
-    if (a.width == 12) IMM3_STR_LAUNCH(3, 1, false);
-    if (a.width == 16) IMM3_STR_LAUNCH(4, 4, false);
-    if (a.width % 16 == 0) IMM3_STR_LAUNCH(4, 4, true);
-    if (a.width % 8 == 0) IMM3_STR_LAUNCH(4, 2, true);
-    IMM3_STR_LAUNCH(4, 1, true);
+    if (!column_pass_ok(a.pass, grid) || !str_rows_width_ok(a.pass.width) || a.n_match < 0) return false;
+    if (!a.values && (a.pass.width > 8 || a.n_match > kMaxMatch)) return false;
+    IMM3_STR_LAUNCH_BY_WIDTH(k_filter_str_rows);
 }
 
-#define IMM3_STR_RANGE_LAUNCH(P, C, TAIL)                                                                          \
-    do {                                                                                                           \
-        if (a.tile_rows) IMM3_LAUNCH((k_filter_str_range<P, C, TAIL, true>), grid, kBlockThreads, s, ev0, ev1, a); \
-        else IMM3_LAUNCH((k_filter_str_range<P, C, TAIL, false>), grid, kBlockThreads, s, ev0, ev1, a);            \
-        return true;                                                                                               \
-    } while (0)
-
-// the same seven instances by width; false: no instance for this width, or the tails are not where the instance reads them
+// false: no instance for this width, or the tails are not where the instance reads them
 bool launch_filter_str_range(const StrRangeArgs &a, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    if (!str_rows_width_ok(a.width) || !a.bitmap || grid < 1 || grid > kMaxFilterGrid) return false;
-    if (a.width > 16 && !a.tails) return false;
-    if (a.width == 4) IMM3_STR_RANGE_LAUNCH(1, 1, false);
-    if (a.width == 8) IMM3_STR_RANGE_LAUNCH(2, 2, false);
-    if (a.width == 12) IMM3_STR_RANGE_LAUNCH(3, 1, false);
-    if (a.width == 16) IMM3_STR_RANGE_LAUNCH(4, 4, false);
-    if (a.width % 16 == 0) IMM3_STR_RANGE_LAUNCH(4, 4, true);
-    if (a.width % 8 == 0) IMM3_STR_RANGE_LAUNCH(4, 2, true);
-    IMM3_STR_RANGE_LAUNCH(4, 1, true);
+    if (!column_pass_ok(a.pass, grid) || !str_rows_width_ok(a.pass.width)) return false;
+    if (a.pass.width > 16 && !a.tails) return false;
+    IMM3_STR_LAUNCH_BY_WIDTH(k_filter_str_range);
 }
 
 } // namespace imm3
