@@ -12,7 +12,7 @@ from str_rows_util import in_lists, make_strings, pool_for
 
 pytestmark = pytest.mark.gpu
 TV_GENERIC_ONLY = 1
-WIDTHS = [4, 8, 12, 16, 20, 64, 256]
+WIDTHS = [4, 8, 12, 16, 20, 24, 40, 64, 256]      # every instance of the string pass
 # rows and blocks: around a bitmap word and a tile, the loader quirk (a trailing 1-row block), blocks that are multiples of 64
 SHAPES = [(0, []), (1, [1]), (63, [63]), (64, [64]), (65, [65]), (1023, [1023]), (1024, [1024]), (1025, blocks_of(1025, 1024)),
           (2 * 1024 + 1, [1024, 1024, 1]), (4 * 64 + 5, [64, 128, 64, 5])]
